@@ -26,7 +26,10 @@ Multi-GPU (one process per GPU, RCCL):
     tile is its own "image" for the attention / squeeze-excite / luma statistics: 22.5 dB from the untiled reference with
     these weights (tests/golden/tiling_psnr.json).
 
-Rank 0 prints ONE JSON line.  Besides the driver's fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times ``--steps`` steps and reports them (``value``,
+``ms_per_step``); ``--dump-outputs DIR`` then writes what the last timed step returned as ``DIR/<name>.npy`` (float32, a
+seeded sample of an output larger than 32 MiB; inputs and weights are seeded, so two builds compare output for output).
+With ``--full`` (``--no-profile`` / ``--no-cpu-baseline`` leave parts out) the line also carries
   roofline      the dominant kernel (largest share of the forward), timed live with HIP events
                 on the launch stream (rf_profile_begin/end) over the same K steps in a second,
                 untimed pass, priced against its algorithmic FLOPs / bytes (SURVEY.md section 8d);
@@ -311,6 +314,33 @@ def dwt_microbench(device):
     return res
 
 
+DUMP_SAMPLE = 1 << 23          # elements kept of a larger output array (32 MiB of float32)
+DUMP_MAX_BYTES = 64 * 10 ** 6  # all arrays of one --dump-outputs together
+
+
+def dump_outputs(arrays, out_dir):
+    """``out_dir/<name>.npy`` in float32 for every tensor of ``arrays``.  An array of more than DUMP_SAMPLE elements is written
+    as a sample of its flattened elements: sorted indices drawn from a fixed seed, so the same shape gives the same indices
+    and two builds compare element for element."""
+    import numpy as np
+    import torch
+
+    dumped = {}
+    for name, t in arrays.items():
+        a = t.detach().float()
+        if a.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(20240).choice(a.numel(), DUMP_SAMPLE, replace=False))
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+        dumped[name] = a.cpu().numpy()
+    total = sum(a.nbytes for a in dumped.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in dumped.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"outputs of the last timed step written to {out_dir}: " + ", ".join(f"{n} {list(a.shape)}" for n, a in dumped.items()))
+
+
 def synthetic_state(model, seed):
     """Seeded weights for every parameter the library's registry (rf_param_info) declares, by name and shape; the
     module's constant buffers (luma weights, Haar filters) keep the values its constructor gave them."""
@@ -330,12 +360,18 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the profiled pass (roofline, kernels, dwt_roofline) and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: leave out the profiled pass")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (rank 0; seeded sample of large outputs)")
     ap.add_argument("--dry-run", action="store_true", help="CPU + gloo + stand-in forward: launcher / sharding / collective rehearsal")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -473,6 +509,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert torch.isfinite(out).all()
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed step receives: the sRGB frames, or after a training step its loss and the updated weights
+        # (with the gradient they were updated by)
+        dump_outputs({"loss": out, "params": trainer.flat, "grads": trainer.grads} if trainer is not None else {"output": out},
+                     args.dump_outputs)
 
     mp_per_step = (1 if (tiled or exact) else world) * batch * hm * wm / 1e6
     model_name = {32: "S", 48: "B", 64: "L"}[dim]
@@ -513,7 +554,7 @@ def main():
     # forward_window, the gradient buckets) EVERY rank must run it or rank 0's collectives have no partner and the job
     # hangs until the watchdog fires; only rank 0 keeps the records.  A collective-free step is profiled on rank 0 alone.
     step_has_collectives = world > 1 and (tiled or exact or args.workload == "cfg5")
-    do_profile = not args.no_profile and (rank == 0 or step_has_collectives)
+    do_profile = args.full and not args.no_profile and (rank == 0 or step_has_collectives)
     recs = None
     if do_profile:
         prof_step = step if (tiled or exact or args.workload == "cfg5") else (lambda: forward(x))
@@ -567,7 +608,7 @@ def main():
         if args.workload == "cfg2" and not args.dry_run:
             line["dwt_roofline"] = dwt_microbench(device)
             log("dwt microbench done")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.dry_run:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.dry_run:
         line["cpu_baseline"] = cpu_baseline(dim, hm, wm, sd)
     if use_dist:
         dist.barrier()

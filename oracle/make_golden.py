@@ -18,6 +18,8 @@ Usage:  python oracle/make_golden.py [--big]
 from __future__ import annotations
 
 import argparse
+import copy
+import glob
 import math
 import json
 import os
@@ -102,11 +104,37 @@ def maxabs(a, b):
     return float((a - b).abs().max())
 
 
+MAX_FILE_BYTES = 1 << 20   # a committed file stays below 1 MiB: a larger fixture is stored as <name>.part<i>.npz (tests/cases.golden)
+
+
 def save(name, **arrays):
+    arrays = {k: (v.detach().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in arrays.items()}
+    for old in glob.glob(os.path.join(GOLD, glob.escape(name) + ".npz")) + glob.glob(os.path.join(GOLD, glob.escape(name) + ".part*.npz")):
+        os.remove(old)
     path = os.path.join(GOLD, name + ".npz")
-    np.savez_compressed(path, **{k: (v.detach().numpy() if torch.is_tensor(v) else np.asarray(v))
-                                 for k, v in arrays.items()})
-    log(f"  wrote {os.path.relpath(path, REPO)} ({os.path.getsize(path)} B)")
+    np.savez_compressed(path, **arrays)
+    size = os.path.getsize(path)
+    if size < MAX_FILE_BYTES:
+        log(f"  wrote {os.path.relpath(path, REPO)} ({size} B)")
+        return
+    os.remove(path)
+    keys, total = list(arrays), sum(a.nbytes for a in arrays.values())
+    nparts = -(-size * 4 // (3 * MAX_FILE_BYTES))          # parts of about 3/4 MiB compressed, split by raw bytes in key order
+    while True:
+        chunks, acc = [[] for _ in range(nparts)], 0
+        for k in keys:
+            chunks[min(nparts - 1, acc * nparts // max(total, 1))].append(k)
+            acc += arrays[k].nbytes
+        paths = [os.path.join(GOLD, f"{name}.part{i}.npz") for i in range(nparts)]
+        for pth, ks in zip(paths, chunks):
+            np.savez_compressed(pth, **{k: arrays[k] for k in ks})
+        if max(os.path.getsize(pth) for pth in paths) < MAX_FILE_BYTES:
+            break
+        for pth in paths:
+            os.remove(pth)
+        nparts += 1
+    for pth in paths:
+        log(f"  wrote {os.path.relpath(pth, REPO)} ({os.path.getsize(pth)} B)")
 
 
 def sd_of(module):
@@ -438,6 +466,13 @@ FFAB_CASES = (("ffab16", 16, (2, 16, 16, 16)), ("ffab8", 8, (1, 8, 8, 12)))
 WMB_CASES = (("wmb16", 16, (2, 16, 16, 24)),)
 
 
+def float64_output(module, x):
+    """The module's output for ``x`` computed in float64 (on a copy): a pin of the oracle that holds on every host -- the
+    float32 outputs depend on the CPU code path the math library takes (FFT, GEMM) at the level of the float32 noise."""
+    with torch.no_grad():
+        return copy.deepcopy(module).double()(x.double())
+
+
 def ffab(blocks_mod, wfb_ns):
     """f2: ``FEB`` / ``FFAB`` of RawFomer_WFB_FFAB/blocks.py:11-92 (the module imports with inert timm stubs), the two
     transforms it is built on, and the Mamba-free wavelet branch of ``WMB.forward`` (model.py:215-243) assembled from the
@@ -459,6 +494,7 @@ def ffab(blocks_mod, wfb_ns):
         log(f"  FEB {tag} nc={nc} {shape}: oracle vs reference {maxabs(y, mine):.2e}, |y|max {float(y.abs().max()):.2f}")
         assert maxabs(y, mine) < 1e-6
         out[f"{tag}.out"] = y
+        out[f"{tag}.out64"] = float64_output(m, x)
     for tag, nc, shape in FFAB_CASES:
         m = fill(blocks_mod.FFAB(nc), 2000 + nc)
         x = rnd(61, f"ffab.{tag}.x", shape)
@@ -468,6 +504,7 @@ def ffab(blocks_mod, wfb_ns):
         log(f"  FFAB {tag} nc={nc} {shape}: oracle vs reference {maxabs(y, mine):.2e}, |y|max {float(y.abs().max()):.2f}")
         assert maxabs(y, mine) < 1e-6
         out[f"{tag}.out"] = y
+        out[f"{tag}.out64"] = float64_output(m, x)
     # WMB without Mamba: the reference's LayerNorm (WithBias), DWT, Illumination_Estimator, FFAB, IWT in WMB.forward's order
     src = open(os.path.join(REF, "RawFomer_WFB_FFAB", "model.py")).read()
     seg = src[src.index("class Illumination_Estimator"):src.index("class WMB(nn.Module)")]

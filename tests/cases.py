@@ -7,6 +7,7 @@ tests check the HIP path against both.
 """
 from __future__ import annotations
 
+import glob
 import os
 import sys
 
@@ -23,8 +24,28 @@ GOLDEN = os.path.join(REPO, "tests", "golden")
 SEED = 11
 
 
+class _Parts(dict):
+    """The arrays of a fixture stored in parts, with the ``files`` list an ``np.load`` result has."""
+
+    @property
+    def files(self):
+        return list(self)
+
+
 def golden(name: str):
-    return np.load(os.path.join(GOLDEN, name + ".npz"))
+    """``tests/golden/<name>.npz``, or the union of ``<name>.part<i>.npz`` for a fixture stored in parts (every committed file
+    stays below 1 MiB; oracle/make_golden.py ``save`` splits)."""
+    path = os.path.join(GOLDEN, name + ".npz")
+    if os.path.exists(path):
+        return np.load(path)
+    parts = sorted(glob.glob(os.path.join(GOLDEN, glob.escape(name) + ".part*.npz")))
+    if not parts:
+        raise FileNotFoundError(path)
+    out = _Parts()
+    for p in parts:
+        with np.load(p) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
 
 
 def rnd(name, shape, lo=-1.0, hi=1.0, seed=SEED):

@@ -32,7 +32,7 @@ def _both_ranks_profiled(r, line):
 
 
 def test_gpus_2_launches_two_ranks_batch_sharded():
-    r = _run("--gpus", "2", "--dry-run", "--steps", "2", "--warmup", "1")
+    r = _run("--gpus", "2", "--dry-run", "--full", "--steps", "2", "--warmup", "1")
     assert r.returncode == 0, r.stderr[-2000:]
     line = _json_line(r.stdout)
     assert line["n_gpus"] == 2 and line["dry_run"] is True and line["scaling"] == "weak"
@@ -45,7 +45,7 @@ def test_gpus_2_launches_two_ranks_batch_sharded():
 
 
 def test_cfg4_two_ranks_tile_sharded_with_the_all_gather_in_the_step():
-    r = _run("--gpus", "2", "--dry-run", "--workload", "cfg4t", "--steps", "2", "--warmup", "1")
+    r = _run("--gpus", "2", "--dry-run", "--full", "--workload", "cfg4t", "--steps", "2", "--warmup", "1")
     assert r.returncode == 0, r.stderr[-2000:]
     line = _json_line(r.stdout)
     assert line["n_gpus"] == 2 and line["scaling"] == "strong"
@@ -56,7 +56,7 @@ def test_cfg4_two_ranks_tile_sharded_with_the_all_gather_in_the_step():
 
 @pytest.mark.parametrize("name", ["cfg4", "cfg4x"])          # BASELINE configs[3] runs in the exact mode by default
 def test_cfg4_two_ranks_exact_row_shards_with_their_collectives_in_the_step(name):
-    r = _run("--gpus", "2", "--dry-run", "--workload", name, "--steps", "2", "--warmup", "1")
+    r = _run("--gpus", "2", "--dry-run", "--full", "--workload", name, "--steps", "2", "--warmup", "1")
     assert r.returncode == 0, r.stderr[-2000:]
     line = _json_line(r.stdout)
     assert line["n_gpus"] == 2 and line["scaling"] == "strong"
@@ -65,7 +65,7 @@ def test_cfg4_two_ranks_exact_row_shards_with_their_collectives_in_the_step(name
 
 
 def test_cfg5_two_ranks_rehearse_the_bucketed_gradient_all_reduce():
-    r = _run("--gpus", "2", "--dry-run", "--workload", "cfg5", "--steps", "2", "--warmup", "1")
+    r = _run("--gpus", "2", "--dry-run", "--full", "--workload", "cfg5", "--steps", "2", "--warmup", "1")
     assert r.returncode == 0, r.stderr[-2000:]
     line = _json_line(r.stdout)
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and "training step" in line["metric"]
@@ -84,3 +84,44 @@ def test_single_rank_without_a_gpu_fails_loudly():
         pytest.skip("a GPU is present")
     r = _run("--steps", "1", "--warmup", "0")
     assert r.returncode != 0 and "no CPU fallback" in (r.stderr + r.stdout)
+
+
+def test_plain_run_times_the_steps_and_runs_nothing_else():
+    r = _run("--dry-run", "--steps", "3", "--warmup", "1")
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = _json_line(r.stdout)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line, line
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    assert "profiled pass" not in r.stderr
+    assert not {"roofline", "kernels", "profiled_ms_per_step", "cpu_baseline", "dwt_roofline"} & set(line)
+
+
+def test_dump_outputs_are_identical_from_run_to_run(tmp_path):
+    import numpy as np
+
+    outs = []
+    for tag in ("a", "b"):
+        r = _run("--dry-run", "--steps", "2", "--warmup", "0", "--dump-outputs", str(tmp_path / tag))
+        assert r.returncode == 0, r.stderr[-2000:]
+        outs.append(np.load(tmp_path / tag / "output.npy"))
+    assert outs[0].dtype == np.float32 and outs[0].shape == (8, 3, 128, 128)
+    assert np.array_equal(outs[0], outs[1]) and np.abs(outs[0]).max() > 0
+
+
+def test_dump_outputs_samples_a_large_output_with_fixed_indices(tmp_path):
+    import numpy as np
+    import torch
+
+    import bench
+
+    n = bench.DUMP_SAMPLE + 12345
+    big = torch.arange(n, dtype=torch.float64)
+    for tag in ("a", "b"):
+        bench.dump_outputs({"output": big, "loss": torch.tensor([0.5])}, str(tmp_path / tag))
+    a, b = (np.load(tmp_path / t / "output.npy") for t in ("a", "b"))
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_SAMPLE,)
+    assert np.array_equal(a, b)
+    assert np.all(np.diff(a.astype(np.float64)) > 0) and a[0] >= 0 and a[-1] < n     # distinct, sorted element indices
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= bench.DUMP_MAX_BYTES
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [0.5]

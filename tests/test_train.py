@@ -88,7 +88,7 @@ def test_two_adam_steps_match_torch_optim(device):
 
 
 def _ref_case(tag):
-    g = np.load(os.path.join(cases.GOLDEN, "train_cfg5.npz"))
+    g = cases.golden("train_cfg5")
     import json
     names = json.load(open(os.path.join(cases.GOLDEN, "train_cfg5_params.json")))
     return g, names

@@ -15,7 +15,7 @@ for w in $wl; do
   steps=5; [ "$w" = cfg2 ] && steps=20
   B="python3 bench.py --workload $w --no-cpu-baseline --no-profile --steps 2 --warmup 1"
   echo "[profile_round] $w: kernel statistics"
-  rocprofv3 --kernel-trace --stats -d $out/stats_$w -o s --output-format csv -- python3 bench.py --workload $w --no-cpu-baseline --steps $steps > $out/bench_${w}_under_rocprof.json 2> $out/stats_$w.log
+  rocprofv3 --kernel-trace --stats -d $out/stats_$w -o s --output-format csv -- python3 bench.py --workload $w --full --no-cpu-baseline --steps $steps > $out/bench_${w}_under_rocprof.json 2> $out/stats_$w.log
   echo "[profile_round] $w: FETCH_SIZE"
   rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $out/fetch_$w -o f --output-format csv -- $B > $out/fetch_$w.log 2>&1
   echo "[profile_round] $w: WRITE_SIZE"
@@ -26,8 +26,8 @@ for w in $wl; do
   python3 tools/mfma_util.py $out/sq_$w $out/mfma_util_$w.json $w > $out/mfma_util_$w.txt 2>&1
   cp $(find $out/stats_$w -name "*_kernel_stats.csv" | head -1) $out/bench_${w}_kernel_stats.csv 2>/dev/null
   echo "[profile_round] $w: bench line"
-  if [ "$w" = cfg2 ]; then python3 bench.py > $out/bench_$w.json 2> $out/bench_$w.err; else python3 bench.py --workload $w --no-cpu-baseline > $out/bench_$w.json 2> $out/bench_$w.err; fi
+  if [ "$w" = cfg2 ]; then python3 bench.py --full > $out/bench_$w.json 2> $out/bench_$w.err; else python3 bench.py --workload $w --full --no-cpu-baseline > $out/bench_$w.json 2> $out/bench_$w.err; fi
   rm -rf $out/fetch_$w $out/write_$w $out/sq_$w $out/stats_$w
 done
-for w in cfg1 frame1; do python3 bench.py --workload $w --no-cpu-baseline > $out/bench_$w.json 2> $out/bench_$w.err; done
+for w in cfg1 frame1; do python3 bench.py --workload $w --full --no-cpu-baseline > $out/bench_$w.json 2> $out/bench_$w.err; done
 ls $out
