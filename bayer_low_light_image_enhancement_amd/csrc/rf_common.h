@@ -315,8 +315,9 @@ int launch_tc_color_head(float* x, const float* const* prm, int B, size_t P, hip
 
 // ---- training kernels (rf_train.hip)
 size_t gram2_partial_floats(int B, int Ca, int Cb, int h, int w, int ntap);
+// partial_cap: floats available at partial (the launch needs gram2 slabs x (ntap Ca Cb + Ca when db); checked, never exceeded)
 int launch_gram2(const float* a, int64_t a_bstride, int Ca, const float* b, int64_t b_bstride, int Cb, float* out, int ld, float* partial,
-                 int B, int h, int w, int ntap, int sy, int sx, int per_image, size_t out_istride, int accumulate, hipStream_t st,
+                 size_t partial_cap, int B, int h, int w, int ntap, int sy, int sx, int per_image, size_t out_istride, int accumulate, hipStream_t st,
                  float* db = nullptr /* [Ca] (+)= row sums of a over all images and pixels: the bias gradient of the same layer */,
                  const float* b2 = nullptr, int64_t b2_bstride = 0, int Cb2 = 0 /* input = cat(b, b2) along channels, read in place */);
 int launch_reduce_rows(const float* partial, float* out, int nrows, size_t n, int accumulate, hipStream_t st);
@@ -340,7 +341,7 @@ int launch_adam(float* p, const float* g, float* m, float* v, size_t n, float lr
 size_t flca_bwd_scratch_floats(int B, int C, int h, int w);
 int launch_flca_backward(const float* feat, const float* guide, const float* xs, const float* dz, int64_t dz_bstride, const float* ch,
                          const float* pool_partial, int pool_nblk, const float* const* prm, float* const* grd, float* dfeat, int accumulate,
-                         float* scratch, int B, int C, int h, int w, hipStream_t st);
+                         float* scratch, size_t scratch_floats, int B, int C, int h, int w, hipStream_t st);
 
 // ---- FLCA (rf_flca.hip)
 size_t guidance_scratch_floats(int B, int H, int W);

@@ -730,7 +730,7 @@ size_t gram2_partial_floats(int B, int Ca, int Cb, int h, int w, int ntap) {
 // out[(i * ld + j) * ntap + tap] = weight layout [Ca][ld >= Cb][taps] (ntap = 9: the 3x3 window in (dy, dx) row-major order;
 // ntap = 1: the single shift (sy, sx)); per_image: out[b * out_istride + ...] without the sum over images; accumulate adds
 int launch_gram2(const float* a, int64_t a_bstride, int Ca, const float* b, int64_t b_bstride, int Cb, float* out, int ld, float* partial,
-                 int B, int h, int w, int ntap, int sy, int sx, int per_image, size_t out_istride, int accumulate, hipStream_t st, float* db,
+                 size_t partial_cap, int B, int h, int w, int ntap, int sy, int sx, int per_image, size_t out_istride, int accumulate, hipStream_t st, float* db,
                  const float* b2, int64_t b2_bstride, int Cb2) {
     RF_CHECK_ARG(w % 4 == 0 && aligned16(a) && aligned16(b) && a_bstride % 4 == 0 && b_bstride % 4 == 0,
                  "gram2: width %d must be a multiple of 4 and the operands 16-byte aligned", w);
@@ -749,6 +749,9 @@ int launch_gram2(const float* a, int64_t a_bstride, int Ca, const float* b, int6
     const int nslab = B * g.slabs_per_image;
     g.nslab = nslab; g.nty = cdiv(Ca, 16 * na); g.ntz = cdiv(Cb, 16 * tj);
     const size_t n = (size_t)ntap * Ca * Cb;
+    RF_CHECK_ARG((size_t)nslab * (n + (db ? Ca : 0)) <= partial_cap,
+                 "gram2: %d slabs x %zu partial floats (Ca = %d, Cb = %d, %d taps, %dx%d, B = %d) exceed the %zu-float partial buffer",
+                 nslab, n + (db ? Ca : 0), Ca, Cb, ntap, h, w, B, partial_cap);
     if (db) g.bias_partial = partial + (size_t)nslab * n;
     ProfScope prof(st, ntap == 1 ? "gram2_kernel<1>" : "gram2_kernel<9>", 2.0 * ntap * Ca * Cb * (double)B * h * w, 4.0 * (double)B * h * w * (Ca + Cb));
     const dim3 grid1((unsigned)(cdiv(nslab, 8) * 8 * g.nty * g.ntz));
@@ -1247,7 +1250,7 @@ size_t flca_bwd_scratch_floats(int B, int C, int h, int w) {
 // prm / grd: alpha, beta, gamma, low_attn.0.w, high_attn.0.w, chroma_attn.0.w, se.1.w, se.1.b, se.3.w, se.3.b (parameters / their gradients)
 int launch_flca_backward(const float* feat, const float* guide, const float* xs, const float* dz, int64_t dz_bstride, const float* ch,
                          const float* pool_partial, int pool_nblk, const float* const* prm, float* const* grd, float* dfeat, int accumulate,
-                         float* scratch, int B, int C, int h, int w, hipStream_t st) {
+                         float* scratch, size_t scratch_floats, int B, int C, int h, int w, hipStream_t st) {
     RF_CHECK_ARG(C <= 512 && B <= 65535 && w % 4 == 0, "flca backward: C=%d, w=%d unsupported", C, w);
     const int P = h * w, nblk = cdiv(P, 256), dnblk = chan_sum_nblk(P), hid = C / 8 > 8 ? C / 8 : 8;
     const size_t plane = (size_t)B * C * P;
@@ -1258,6 +1261,9 @@ int launch_flca_backward(const float* feat, const float* guide, const float* xs,
     float* se_contrib = dmP + (size_t)B * C + 64;
     const size_t n_se = (size_t)2 * C * hid + hid + C;
     float* gpart = se_contrib + align_up((size_t)B * n_se, 64);
+    RF_CHECK_ARG((size_t)(gpart - scratch) <= scratch_floats, "flca backward: scratch of %zu floats, the fixed part alone needs %zu",
+                 scratch_floats, (size_t)(gpart - scratch));
+    const size_t gcap = scratch_floats - (size_t)(gpart - scratch);      // the slab partials of the tap gradients (gram2 / fused kernel)
     // the four squeeze-excite tensors follow each other in the flat gradient buffer (registry order, sizes multiples of 4)
     RF_CHECK_ARG(grd[7] == grd[6] + (size_t)hid * C && grd[8] == grd[7] + hid && grd[9] == grd[8] + (size_t)C * hid,
                  "flca backward: the gradients of se.1.weight, se.1.bias, se.3.weight, se.3.bias must be contiguous");
@@ -1273,6 +1279,8 @@ int launch_flca_backward(const float* feat, const float* guide, const float* xs,
         int slab_px, per_image;
         gram2_slabs(B, P, cdiv(C, 16), &slab_px, &per_image);
         const int nslab = B * per_image, nti = cdiv(C, 16);
+        RF_CHECK_ARG((size_t)(nslab + 1) * C * 36 <= gcap, "flca backward: %d slabs x %d floats exceed the %zu-float partial buffer",
+                     nslab, C * 36, gcap);
         float* sums = gpart + (size_t)nslab * C * 36;
         float* abg2 = ds;
         ProfScope prof(st, "flca_backward(fused)", 2.0 * 36 * (double)B * C * P + 200.0 * B * C * P, 12.0 * (double)B * C * P + 8.0 * B * C * P);
@@ -1292,9 +1300,9 @@ int launch_flca_backward(const float* feat, const float* guide, const float* xs,
         flca_abg_kernel<<<1, 256, 0, st>>>(abg, B * nblk, grd[0], grd[1], grd[2]);
         if (int rc = check_launch("flca_backward")) return rc;
     }
-    if (int rc = launch_gram2(ds, (int64_t)C * P, C, guide, (int64_t)4 * P, 1, grd[3], 1, gpart, B, h, w, 9, 0, 0, 0, 0, 1, st)) return rc;
-    if (int rc = launch_gram2(ds + plane, (int64_t)C * P, C, guide + P, (int64_t)4 * P, 1, grd[4], 1, gpart, B, h, w, 9, 0, 0, 0, 0, 1, st)) return rc;
-    return launch_gram2(ds + 2 * plane, (int64_t)C * P, C, guide + 2 * (size_t)P, (int64_t)4 * P, 2, grd[5], 2, gpart, B, h, w, 9, 0, 0, 0, 0, 1, st);
+    if (int rc = launch_gram2(ds, (int64_t)C * P, C, guide, (int64_t)4 * P, 1, grd[3], 1, gpart, gcap, B, h, w, 9, 0, 0, 0, 0, 1, st)) return rc;
+    if (int rc = launch_gram2(ds + plane, (int64_t)C * P, C, guide + P, (int64_t)4 * P, 1, grd[4], 1, gpart, gcap, B, h, w, 9, 0, 0, 0, 0, 1, st)) return rc;
+    return launch_gram2(ds + 2 * plane, (int64_t)C * P, C, guide + 2 * (size_t)P, (int64_t)4 * P, 2, grd[5], 2, gpart, gcap, B, h, w, 9, 0, 0, 0, 0, 1, st);
 }
 
 }  // namespace rf

@@ -64,12 +64,14 @@ struct TrainPlan {
     Stash st[8];                       // 1..7
     float *x4, *e, *down[3], *up[3], *catr[3], *pred;
     float *gscratch, *guide[4], *flca_scr;
+    size_t flca_scr_floats;
     float *tA, *tB, *tC, *tD, *tE;     // backward temporaries (3 * U0 each)
     float *dskip[3], *dpred, *ga, *gb;
     float *wt1, *wt2;                  // on-the-fly packed / flipped weights (shapes the pack cache does not hold)
     float *pack_cache;                 // every packed weight form of the step, written by a few batched launches at its start
     float *part;                       // reduction partials
     float *part_wg;                    // ... of the kernels on the weight-gradient stream
+    size_t part_floats;                // capacity of each of part / part_wg (launch_gram2 checks its slab partials against it)
     float *sb[16];                     // stage_backward's temporaries, one buffer per tensor (see there)
     float *small;                      // attention: per-image C x C matrices and packed per-image weights
     float *loss_part;
@@ -172,8 +174,9 @@ int make_train_plan(const rf_handle* h, float* base, int B, int H, int W, TrainP
     p.ga = b.take(U0); p.gb = b.take(U0);
     p.wt1 = b.take(wt); p.wt2 = b.take(wt);
     p.pack_cache = b.take(build_pack_list(h, nullptr, nullptr, nullptr));
-    p.part = b.take(max_sz(part, (size_t)B * 64 * 512));
-    p.part_wg = b.take(max_sz(part, (size_t)B * 64 * 512));
+    p.part_floats = max_sz(part, (size_t)B * 64 * 512);
+    p.part = b.take(p.part_floats);
+    p.part_wg = b.take(p.part_floats);
     {   // d_pre, d_cr, d_cat, d_f2, d_f1, ln2, d_ln2, d_x1, o, d_o, d_qkv, d_qkvp, ln1, d_ln1, d_xs, d_tr   (units of U0)
         const size_t hx = (size_t)hcx;
         const size_t units[16] = {1, 1, 2, hx, hx, 1, 1, 1, 1, 1, 3, 3, 1, 1, 1, 1};
@@ -182,6 +185,7 @@ int make_train_plan(const rf_handle* h, float* base, int B, int H, int W, TrainP
     p.small = b.take(small);
     p.loss_part = b.take(4096);
     p.flca_scr = b.take(fscr);
+    p.flca_scr_floats = fscr;
     p.total = b.off;
     return RF_OK;
 }
@@ -285,10 +289,11 @@ int b_conv1x1_dw(const Ctx& c, const float* dy, int Cout, const float* x, int Cx
     const hipStream_t ws = c.dw_stream();
     float* part = c.dw_part();
     if (Cx2 && Cx % 16 != 0) {       // the two-source contraction cuts the inputs at a tile boundary: otherwise one pass per input
-        RF_TRY(launch_gram2(dy, dys, Cout, x, (int64_t)Cx * hh * ww, Cx, dW + col0, ld, part, c.B, hh, ww, 1, 0, 0, 0, 0, 1, ws, col0 == 0 ? db : nullptr));
-        return launch_gram2(dy, dys, Cout, x2, (int64_t)Cx2 * hh * ww, Cx2, dW + col0 + Cx, ld, part, c.B, hh, ww, 1, 0, 0, 0, 0, 1, ws);
+        RF_TRY(launch_gram2(dy, dys, Cout, x, (int64_t)Cx * hh * ww, Cx, dW + col0, ld, part, c.p->part_floats, c.B, hh, ww, 1, 0, 0, 0, 0, 1, ws,
+                            col0 == 0 ? db : nullptr));
+        return launch_gram2(dy, dys, Cout, x2, (int64_t)Cx2 * hh * ww, Cx2, dW + col0 + Cx, ld, part, c.p->part_floats, c.B, hh, ww, 1, 0, 0, 0, 0, 1, ws);
     }
-    return launch_gram2(dy, dys, Cout, x, (int64_t)Cx * hh * ww, Cx, dW + col0, ld, part, c.B, hh, ww,
+    return launch_gram2(dy, dys, Cout, x, (int64_t)Cx * hh * ww, Cx, dW + col0, ld, part, c.p->part_floats, c.B, hh, ww,
                         1, 0, 0, 0, 0, 1, ws, col0 == 0 ? db : nullptr, x2, (int64_t)Cx2 * hh * ww, Cx2);
 }
 
@@ -304,7 +309,7 @@ int b_conv3x3_dx(const Ctx& c, const float* dy, int Cout, const float* w, int Ci
 
 int b_conv3x3_dw(const Ctx& c, const float* dy, int Cout, const float* x, int Cin, float* dW, float* db, int hh, int ww) {
     RF_TRY(c.fork());
-    return launch_gram2(dy, (int64_t)Cout * hh * ww, Cout, x, (int64_t)Cin * hh * ww, Cin, dW, Cin, c.dw_part(), c.B, hh, ww, 9, 0, 0, 0, 0, 1, c.dw_stream(), db);
+    return launch_gram2(dy, (int64_t)Cout * hh * ww, Cout, x, (int64_t)Cin * hh * ww, Cin, dW, Cin, c.dw_part(), c.p->part_floats, c.B, hh, ww, 9, 0, 0, 0, 0, 1, c.dw_stream(), db);
 }
 
 int b_dw(const Ctx& c, const float* dy, const float* x, const float* w, float* dx, float* dW, float* db, int C, int hh, int ww) {
@@ -546,7 +551,7 @@ int stage_backward(const Ctx& c, int i, int lvl, float* dout, float* din, int H,
         float* grd[10];
         for (int k = 0; k < 10; ++k) { prm[k] = P(h, f + names[k]); grd[k] = c.G(f + names[k]); }
         RF_TRY(launch_flca_backward(s.in, c.p->guide[lvl], s.xraw, dxs, half_bs, s.ch, s.pool, flca_nblk(hh, ww), prm, grd, din, 0,
-                                    c.p->flca_scr, c.B, C, hh, ww, c.st));                             // din = branch part
+                                    c.p->flca_scr, c.p->flca_scr_floats, c.B, C, hh, ww, c.st));                             // din = branch part
     } else {
         // conv branch
         if (cfg.branch_lrelu) RF_TRY(launch_ewise(d_xs, s.xs, d_xs, U, 2, 0.2f, c.st));
@@ -581,7 +586,7 @@ int stage_backward(const Ctx& c, int i, int lvl, float* dout, float* din, int H,
     RF_TRY(b_conv1x1_dw(c, d_x1, C, o, C, c.G(t + "attn.project_out.weight"), C, 0, c.G(t + "attn.project_out.bias"), hh, ww));
     RF_TRY(b_conv1x1_dx(c, d_x1, C, P(h, t + "attn.project_out.weight"), C, d_o, Pn));
     // dA per image: on the dX chain (the softmax adjoint waits for it)
-    RF_TRY(launch_gram2(d_o, (int64_t)C * Pn, C, v, (int64_t)3 * C * Pn, C, c.p->small, C, c.p->part, c.B, hh, ww, 1, 0, 0, 1, per, 0, c.st));
+    RF_TRY(launch_gram2(d_o, (int64_t)C * Pn, C, v, (int64_t)3 * C * Pn, C, c.p->small, C, c.p->part, c.p->part_floats, c.B, hh, ww, 1, 0, 0, 1, per, 0, c.st));
     RF_TRY(attn_small(c, s, P(h, t + "attn.temperature"), C, heads, 0, c.G(t + "attn.temperature")));
     {   // d(qkv): [dq ; dk] = M2 [q ; k],  dv = blockdiag(A^T) do
         Conv1x1Args a{};
@@ -688,7 +693,10 @@ int rf_flat_offset(const rf_handle* h, int index, size_t* offset) {
 }
 
 int rf_train_workspace_bytes(const rf_handle* h, int B, int H, int W, size_t* bytes) {
-    RF_CHECK_ARG(h && bytes && B > 0 && H % 8 == 0 && W % 8 == 0 && H > 0 && W > 0, "rf_train_workspace_bytes: bad arguments");
+    RF_CHECK_ARG(h && bytes, "rf_train_workspace_bytes: null argument");
+    RF_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0, "rf_train_workspace_bytes: B = %d, packed size %dx%d", B, H, W);
+    RF_CHECK_ARG(H % 8 == 0, "rf_train_workspace_bytes: packed height %d is not a multiple of 8", H);
+    RF_CHECK_ARG(W % 32 == 0, "rf_train_workspace_bytes: packed width %d is not a multiple of 32", W);
     TrainPlan p;
     RF_TRY(make_train_plan(h, nullptr, B, H, W, p));
     *bytes = p.total * sizeof(float);
@@ -700,7 +708,9 @@ int rf_train_step(rf_handle* h, const float* in, const float* gt, float* grads, 
     RF_CHECK_ARG(h && in && gt && grads && loss_out && workspace && aligned16(workspace) && aligned16(grads), "rf_train_step: bad arguments");
     RF_CHECK_ARG((h->cfg.variant == RF_VARIANT_PLAIN || h->cfg.variant == RF_VARIANT_FLCA) && !h->cfg.clamp_io,
                  "rf_train_step: variants 'plain' and 'flca' without clamp_io have their adjoint so far");
-    RF_CHECK_ARG(B > 0 && B <= 65535 && H % 8 == 0 && W % 8 == 0 && W % 32 == 0, "rf_train_step: packed size %dx%d (H %% 8, W %% 32 == 0)", H, W);
+    RF_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0, "rf_train_step: B = %d, packed size %dx%d", B, H, W);
+    RF_CHECK_ARG(H % 8 == 0, "rf_train_step: packed height %d is not a multiple of 8", H);
+    RF_CHECK_ARG(W % 32 == 0, "rf_train_step: packed width %d is not a multiple of 32", W);
     for (const Param& q : h->params) RF_CHECK_ARG(q.ptr, "rf_train_step: parameter '%s' not set", q.name.c_str());
     TrainPlan p;
     RF_TRY(make_train_plan(h, (float*)workspace, B, H, W, p));
@@ -790,7 +800,7 @@ int rf_train_step(rf_handle* h, const float* in, const float* gt, float* grads, 
         RF_TRY(launch_chan_sum(p.tA, (int64_t)C * Pn, c.G(u + ".bias"), p.part, B, C, Pn, 1, st));
         RF_TRY(launch_pixel_unshuffle2(p.tA, p.tB, B, C, hh / 2, ww / 2, st));                 // [B, 4C, hh/2, ww/2]
         const float* xin = (i == 1) ? p.st[4].out : p.st[4 + i - 1].out;
-        RF_TRY(launch_gram2(xin, (int64_t)2 * C * (Pn / 4), 2 * C, p.tB, (int64_t)4 * C * (Pn / 4), 4 * C, c.G(u + ".weight"), 4 * C, p.part, B, hh / 2, ww / 2,
+        RF_TRY(launch_gram2(xin, (int64_t)2 * C * (Pn / 4), 2 * C, p.tB, (int64_t)4 * C * (Pn / 4), 4 * C, c.G(u + ".weight"), 4 * C, p.part, p.part_floats, B, hh / 2, ww / 2,
                             1, 0, 0, 0, 0, 1, st));
         const float* upb = c.pk(P(h, u + ".weight"), PF_CTB);
         if (!upb) {

@@ -189,13 +189,14 @@ def bayer_luma_chroma(x4: Tensor, eps: float = 1e-6) -> Tuple[Tensor, Tensor, Te
 
 def bilinear_resize(x: Tensor, size: Tuple[int, int]) -> Tensor:
     """``F.interpolate(mode='bilinear', align_corners=False)`` written out:
-    ``src = (dst + 0.5) * in/out - 0.5`` clamped at 0, neighbour index clamped at in-1."""
+    ``src = (dst + 0.5) * in/out - 0.5`` clamped at 0, neighbour index clamped at in-1.
+    The weights are computed in ``x.dtype`` (a float64 input gets float64 weights)."""
     def axis(n_in: int, n_out: int):
         scale = n_in / n_out
-        src = ((torch.arange(n_out, dtype=torch.float32) + 0.5) * scale - 0.5).clamp_min(0.0)
+        src = ((torch.arange(n_out, dtype=x.dtype) + 0.5) * scale - 0.5).clamp_min(0.0)
         i0 = src.floor().to(torch.int64).clamp_max(n_in - 1)
         i1 = (i0 + 1).clamp_max(n_in - 1)
-        lam = src - i0.to(torch.float32)
+        lam = src - i0.to(x.dtype)
         return i0, i1, lam
 
     y0, y1, ly = axis(x.shape[-2], size[0])
