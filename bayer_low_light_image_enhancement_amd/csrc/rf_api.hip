@@ -62,12 +62,6 @@ static const float kHaarOrtho[16] = {  // HaarDWT, bands LL,LH,HL,HH
 
 using namespace rf;
 
-#define RF_TRY(expr)            \
-    do {                        \
-        const int rc_ = (expr); \
-        if (rc_) return rc_;    \
-    } while (0)
-
 extern "C" {
 
 const char* rf_last_error(void) { return g_err; }

@@ -6,12 +6,6 @@
 
 namespace rf {
 
-#define RF_TRY(expr)            \
-    do {                        \
-        const int rc_ = (expr); \
-        if (rc_) return rc_;    \
-    } while (0)
-
 size_t transformer_scratch_floats(int B, int C, int heads, int hc, int h, int w, TbBufOffsets* o) {
     const size_t P = (size_t)h * w;
     size_t off = 0;

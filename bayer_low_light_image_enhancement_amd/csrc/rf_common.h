@@ -23,6 +23,12 @@ int check_launch(const char* what);
         }                                  \
     } while (0)
 
+#define RF_TRY(expr)            \
+    do {                        \
+        const int rc_ = (expr); \
+        if (rc_) return rc_;    \
+    } while (0)
+
 // Optional per-launch HIP-event bracket (rf_profile_begin / rf_profile_end in the C ABI):
 // bench.py uses it to time each kernel class on the stream it is launched on.
 struct ProfScope {

@@ -12,12 +12,6 @@
 
 namespace rf {
 
-#define RF_TRY(expr)            \
-    do {                        \
-        const int rc_ = (expr); \
-        if (rc_) return rc_;    \
-    } while (0)
-
 namespace {
 
 struct Bump {

@@ -26,6 +26,32 @@ struct PackItem {
     size_t floats;
 };
 
+// The handle's second stream.  rf_forward and rf_train_step run part of their work on it: fork = an event on the caller's stream
+// that the side stream waits for, join = the reverse.  The stream and both events are created on first use; if that fails,
+// everything stays on the caller's stream.  Defined in rf_model.hip (one definition for the product and the diagnostic objects).
+struct SideStream {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    bool failed = false;    // creation failed: one stream from then on
+    bool pending = false;   // forked and not joined yet
+    int forks = 0;          // forks since the current call began (the diagnostic build's RF_FAIL_FORK counts them)
+    hipStream_t get(hipStream_t st);                // the side stream; `st` while profiling or when it cannot be created
+    int fork(hipStream_t st, hipStream_t side);     // everything enqueued on st so far precedes what is enqueued on side from now on
+    int join(hipStream_t st, hipStream_t side);     // ... and the reverse; both no-ops when side == st
+    void join_pending(hipStream_t st);              // join what a fork left pending, reporting nothing (SideJoinGuard)
+    void destroy();
+};
+
+// One at the top of every entry point that forks: on an early error return it joins what is still pending, so from the
+// caller's side all work of the call is ordered on `st` also then.  On success paths every fork is already joined and it issues
+// no HIP call.
+struct SideJoinGuard {
+    SideStream& s;
+    hipStream_t st;
+    SideJoinGuard(SideStream& s_, hipStream_t st_) : s(s_), st(st_) { s.forks = 0; }
+    ~SideJoinGuard() { s.join_pending(st); }
+};
+
 struct rf_handle {
     rf_config cfg;
     std::vector<Param> params;
@@ -46,11 +72,8 @@ struct rf_handle {
     int shard_y_lo = 0, shard_y_hi = 0, shard_total_rows = 0;
     void (*shard_allreduce)(void* user, float* buf, size_t n, int op, void* stream) = nullptr;
     void* shard_user = nullptr;
-    // branch stream (rf_forward): the guidance pyramid and each stage's FLCA / 3x3 branch run beside the TransformerBlock;
-    // forked from and joined into the caller's stream with the two events, created on first use
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    bool side_failed = false;
+    // second stream: the forward's branches and the training step's weight-gradient kernels run on it (SideStream above)
+    SideStream side;
     // training: notification that a range of the flat gradient buffer is final (rf_set_grad_ready)
     void (*grad_ready)(void* user, size_t offset, size_t count, void* stream) = nullptr;
     void* grad_ready_user = nullptr;

@@ -218,47 +218,6 @@ int make_plan(const rf_handle* h, int B, int H, int W, Plan& p) {
     return RF_OK;
 }
 
-#define RF_TRY(expr)          \
-    do {                      \
-        const int rc_ = (expr); \
-        if (rc_) return rc_;  \
-    } while (0)
-
-// ---- branch stream -------------------------------------------------------------------------
-// A stage's branch (FLCA gates + squeeze-excite fold, or the plain variant's 3x3) depends on the stage input only, like the
-// TransformerBlock beside it; so does the guidance pyramid at the head of the forward.  On a single frame every kernel of both
-// chains is a few dozen microseconds of mostly latency, so the branch runs on a second stream: fork = an event on the caller's
-// stream that the branch stream waits for, join = the reverse before channel_reduce.  Off while profiling (the per-kernel
-// brackets assume one stream), for a spatial shard (its collectives stay on the caller's stream) and for TrueColor (its
-// branch shares bufA with the block).
-hipStream_t branch_stream(rf_handle* h, hipStream_t st) {
-    if (h->side_failed || profiling_active() || h->shard_allreduce || h->cfg.variant == RF_VARIANT_TRUECOLOR) return st;
-#ifdef RF_DIAG   // diagnostic build only: everything on the caller's stream
-    if (getenv("RF_NO_SIDE")) return st;
-#endif
-    if (!h->side) {
-        if (hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess) {
-            (void)hipGetLastError();
-            h->side_failed = true;       // no second stream: the single-stream schedule is always valid
-            h->side = nullptr;
-            return st;
-        }
-    }
-    return h->side;
-}
-int fork_branch(rf_handle* h, hipStream_t st, hipStream_t side) {
-    if (side == st) return RF_OK;
-    RF_TRY(check_hip(hipEventRecord(h->ev_fork, st), "branch fork (record)"));
-    return check_hip(hipStreamWaitEvent(side, h->ev_fork, 0), "branch fork (wait)");
-}
-int join_branch(rf_handle* h, hipStream_t st, hipStream_t side) {
-    if (side == st) return RF_OK;
-    RF_TRY(check_hip(hipEventRecord(h->ev_join, side), "branch join (record)"));
-    return check_hip(hipStreamWaitEvent(st, h->ev_join, 0), "branch join (wait)");
-}
-
 // one Conv_Transformer stage
 int run_stage(rf_handle* h, int i, int lvl, const float* in, float* out, float* ws, const Plan& p,
               int B, int H, int W, hipStream_t st, hipStream_t side) {
@@ -301,7 +260,7 @@ int run_stage(rf_handle* h, int i, int lvl, const float* in, float* out, float* 
     // the branch is launched first (on the branch stream when there is one), the block beside it; TrueColor's branch borrows
     // bufA and therefore follows the block on the same stream
     if (cfg.variant == RF_VARIANT_TRUECOLOR) RF_TRY(run_transformer(tp, in, trans, ws, to, B, C, heads, hc, hh, ww, st));
-    else RF_TRY(fork_branch(h, st, side));
+    else RF_TRY(h->side.fork(st, side));
 
     // branch, cat, channel_reduce -------------------------------------------------------------
     Conv1x1Args r{};
@@ -358,7 +317,7 @@ int run_stage(rf_handle* h, int i, int lvl, const float* in, float* out, float* 
     }
     if (cfg.variant != RF_VARIANT_TRUECOLOR) {
         RF_TRY(run_transformer(tp, in, trans, ws, to, B, C, heads, hc, hh, ww, st));
-        RF_TRY(join_branch(h, st, side));
+        RF_TRY(h->side.join(st, side));
     }
     if (compose) {
         r.wp = nullptr;
@@ -377,6 +336,64 @@ int run_stage(rf_handle* h, int i, int lvl, const float* in, float* out, float* 
 }
 
 }  // namespace
+
+// ---- second stream (rf_handle.h) ----------------------------------------------------------
+hipStream_t SideStream::get(hipStream_t st) {
+    if (failed || profiling_active()) return st;       // the per-kernel profiling brackets assume one stream
+    if (!stream &&
+        (hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess ||
+         hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming) != hipSuccess ||
+         hipEventCreateWithFlags(&ev_join, hipEventDisableTiming) != hipSuccess)) {
+        (void)hipGetLastError();
+        destroy();
+        failed = true;          // no second stream: the single-stream schedule is always valid
+        return st;
+    }
+    return stream;
+}
+
+int SideStream::fork(hipStream_t st, hipStream_t side) {
+    if (side == st) return RF_OK;
+    pending = true;
+    ++forks;
+    RF_TRY(check_hip(hipEventRecord(ev_fork, st), "side stream fork (record)"));
+    RF_TRY(check_hip(hipStreamWaitEvent(side, ev_fork, 0), "side stream fork (wait)"));
+#ifdef RF_DIAG   // diagnostic build only: the n-th fork of a call fails after it has been enqueued
+    const char* n = getenv("RF_FAIL_FORK");
+    if (n && forks == atoi(n)) {
+        set_error("RF_FAIL_FORK=%s: injected failure of fork %d", n, forks);
+        return RF_E_DEVICE;
+    }
+#endif
+    return RF_OK;
+}
+
+int SideStream::join(hipStream_t st, hipStream_t side) {
+    if (side == st) return RF_OK;
+    RF_TRY(check_hip(hipEventRecord(ev_join, side), "side stream join (record)"));
+    RF_TRY(check_hip(hipStreamWaitEvent(st, ev_join, 0), "side stream join (wait)"));
+    pending = false;
+    return RF_OK;
+}
+
+void SideStream::destroy() {
+    if (stream) (void)hipStreamDestroy(stream);
+    if (ev_fork) (void)hipEventDestroy(ev_fork);
+    if (ev_join) (void)hipEventDestroy(ev_join);
+    stream = nullptr;
+    ev_fork = ev_join = nullptr;
+}
+
+// An event record and wait are legal inside a stream capture, a host synchronise is not: the fallback is for a failed record
+// or wait only.  rf_last_error keeps the call's own error.
+void SideStream::join_pending(hipStream_t st) {
+    if (!pending) return;
+    if (hipEventRecord(ev_join, stream) != hipSuccess || hipStreamWaitEvent(st, ev_join, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(stream);
+    }
+    pending = false;
+}
 
 extern "C" {
 
@@ -463,9 +480,7 @@ int rf_create(const rf_config* cfg, rf_handle** out) {
 
 void rf_destroy(rf_handle* h) {
     if (!h) return;
-    if (h->side) (void)hipStreamDestroy(h->side);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
+    h->side.destroy();
     delete h;
 }
 
@@ -625,17 +640,27 @@ int rf_forward(rf_handle* h, const float* in, float* out, void* workspace, size_
     }
     const rf_config& cfg = h->cfg;
     hipStream_t st = (hipStream_t)stream;
+    SideJoinGuard joined(h->side, st);
     float* ws = (float*)workspace;
     const int d = cfg.dim;
     const int mosaic = packed_input ? 0 : 1;
 
     const int levels = cfg.flca_levels > 0 ? cfg.flca_levels : 2;
-    const hipStream_t side = branch_stream(h, st);
+    // A stage's branch (FLCA gates + squeeze-excite fold, or the plain variant's 3x3) depends on the stage input only, like the
+    // TransformerBlock beside it; so does the guidance pyramid at the head of the forward.  On a single frame every kernel of
+    // both chains is a few dozen microseconds of mostly latency, so the branch runs on the handle's second stream, forked
+    // before it and joined before channel_reduce.  Not for a spatial shard (its collectives stay on the caller's stream) nor
+    // for TrueColor (its branch shares bufA with the block).
+    bool use_side = !h->shard_allreduce && cfg.variant != RF_VARIANT_TRUECOLOR;
+#ifdef RF_DIAG   // diagnostic build only: everything on the caller's stream
+    if (getenv("RF_NO_SIDE")) use_side = false;
+#endif
+    const hipStream_t side = use_side ? h->side.get(st) : st;
     if (p.ks_floats)      // tickets of the 3x3 convs' input-channel split (the kernels leave them zero; the workspace is the caller's)
         RF_TRY(check_hip(hipMemsetAsync(ws + p.ks, 0, conv3x3_ksplit_counter_bytes(), st), "rf_forward: memset"));
     if (cfg.variant == RF_VARIANT_FLCA) {
         // the guidance pyramid feeds the FLCA branches only: it runs on their stream, beside the embedding
-        RF_TRY(fork_branch(h, st, side));
+        RF_TRY(h->side.fork(st, side));
         RF_TRY(launch_guidance_base(in, mosaic, cfg.clamp_io, ws + p.gscratch, B, H, W, side, h->shard_allreduce, h->shard_user));
         for (int l = 0; l < 4; ++l)
             RF_TRY(launch_guidance_level(ws + p.gscratch, ws + p.guide[l], B, H, W, H >> l, W >> l, side));

@@ -35,12 +35,6 @@
 
 using namespace rf;
 
-#define RF_TRY(expr)            \
-    do {                        \
-        const int rc_ = (expr); \
-        if (rc_) return rc_;    \
-    } while (0)
-
 namespace {
 
 struct Bump {
@@ -198,25 +192,13 @@ struct Ctx {
     float* grads;      // flat gradient buffer
     int B;
     hipStream_t st;
+    // weight-gradient stream: inside stage_backward (on its own copy of the Ctx) the side stream, where the dW kernels -- which
+    // nothing downstream of the stage waits for -- run beside the dX chain; st everywhere else
+    hipStream_t wg;
+    SideStream* side;
     const PackMap* packs = nullptr;
-    // weight-gradient stream: inside stage_backward the dW kernels (which nothing downstream of the stage waits for) run beside the
-    // dX chain; wg == st: one stream (profiling, or the second stream could not be created)
-    hipStream_t wg = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    mutable bool in_stage = false;
-    bool forked() const { return in_stage && wg != st; }
-    hipStream_t dw_stream() const { return forked() ? wg : st; }
+    bool forked() const { return wg != st; }
     float* dw_part() const { return forked() ? p->part_wg : p->part; }
-    int fork() const {                 // everything enqueued on st so far precedes what is enqueued on wg from now on
-        if (!forked()) return RF_OK;
-        if (int rc = check_hip(hipEventRecord(ev_fork, st), "weight-gradient stream fork (record)")) return rc;
-        return check_hip(hipStreamWaitEvent(wg, ev_fork, 0), "weight-gradient stream fork (wait)");
-    }
-    int join() const {                 // ... and the reverse
-        if (!forked()) return RF_OK;
-        if (int rc = check_hip(hipEventRecord(ev_join, wg), "weight-gradient stream join (record)")) return rc;
-        return check_hip(hipStreamWaitEvent(st, ev_join, 0), "weight-gradient stream join (wait)");
-    }
     float* G(const std::string& n) const { return grads + h->flat_offset[rf_param_index(h, n)]; }
     const float* pk(const float* w, int form) const {      // nullptr: not in the cache (the helper packs on the fly)
         if (!packs) return nullptr;
@@ -285,8 +267,8 @@ int b_conv1x1_dx(const Ctx& c, const float* dy, int Cout, const float* w, int K,
 int b_conv1x1_dw(const Ctx& c, const float* dy, int Cout, const float* x, int Cx, float* dW, int ld, int col0, float* db, int hh, int ww,
                  int64_t dy_bstride = 0, const float* x2 = nullptr, int Cx2 = 0) {
     const int64_t dys = dy_bstride ? dy_bstride : (int64_t)Cout * hh * ww;
-    RF_TRY(c.fork());
-    const hipStream_t ws = c.dw_stream();
+    RF_TRY(c.side->fork(c.st, c.wg));
+    const hipStream_t ws = c.wg;
     float* part = c.dw_part();
     if (Cx2 && Cx % 16 != 0) {       // the two-source contraction cuts the inputs at a tile boundary: otherwise one pass per input
         RF_TRY(launch_gram2(dy, dys, Cout, x, (int64_t)Cx * hh * ww, Cx, dW + col0, ld, part, c.p->part_floats, c.B, hh, ww, 1, 0, 0, 0, 0, 1, ws,
@@ -308,13 +290,13 @@ int b_conv3x3_dx(const Ctx& c, const float* dy, int Cout, const float* w, int Ci
 }
 
 int b_conv3x3_dw(const Ctx& c, const float* dy, int Cout, const float* x, int Cin, float* dW, float* db, int hh, int ww) {
-    RF_TRY(c.fork());
-    return launch_gram2(dy, (int64_t)Cout * hh * ww, Cout, x, (int64_t)Cin * hh * ww, Cin, dW, Cin, c.dw_part(), c.p->part_floats, c.B, hh, ww, 9, 0, 0, 0, 0, 1, c.dw_stream(), db);
+    RF_TRY(c.side->fork(c.st, c.wg));
+    return launch_gram2(dy, (int64_t)Cout * hh * ww, Cout, x, (int64_t)Cin * hh * ww, Cin, dW, Cin, c.dw_part(), c.p->part_floats, c.B, hh, ww, 9, 0, 0, 0, 0, 1, c.wg, db);
 }
 
 int b_dw(const Ctx& c, const float* dy, const float* x, const float* w, float* dx, float* dW, float* db, int C, int hh, int ww) {
-    RF_TRY(c.fork());
-    RF_TRY(launch_dw_wgrad(x, dy, dW, db, c.dw_part(), c.B, C, hh, ww, 1, c.dw_stream()));
+    RF_TRY(c.side->fork(c.st, c.wg));
+    RF_TRY(launch_dw_wgrad(x, dy, dW, db, c.dw_part(), c.B, C, hh, ww, 1, c.wg));
     const float* wf = c.pk(w, PF_T);
     if (!wf) {
         RF_TRY(launch_flip3x3(w, c.p->wt2, C, 1, 0, c.st));
@@ -513,8 +495,11 @@ int stage_forward(const Ctx& c, int i, int lvl, const float* in, int H, int W) {
     return RF_OK;
 }
 
-// dout: gradient w.r.t. the stage output (consumed); din: receives the gradient w.r.t. the stage input
-int stage_backward(const Ctx& c, int i, int lvl, float* dout, float* din, int H, int W) {
+// dout: gradient w.r.t. the stage output (consumed); din: receives the gradient w.r.t. the stage input; wg: the stage's
+// weight-gradient stream
+int stage_backward(const Ctx& outer, hipStream_t wg, int i, int lvl, float* dout, float* din, int H, int W) {
+    Ctx c = outer;
+    c.wg = wg;
     const rf_handle* h = c.h;
     const rf_config& cfg = h->cfg;
     const int C = cfg.dim << lvl, hh = H >> lvl, ww = W >> lvl, Pn = hh * ww, heads = cfg.heads[lvl], hc = C * cfg.ffn_expansion;
@@ -526,7 +511,6 @@ int stage_backward(const Ctx& c, int i, int lvl, float* dout, float* din, int H,
     float* const* sb = c.p->sb;
     float *d_pre = sb[0], *d_cr = sb[1], *d_cat = sb[2], *d_f2 = sb[3], *d_f1 = sb[4], *ln2 = sb[5], *d_ln2 = sb[6], *d_x1 = sb[7], *o = sb[8],
           *d_o = sb[9], *d_qkv = sb[10], *d_qkvp = sb[11], *ln1 = sb[12], *d_ln1 = sb[13], *d_xs = sb[14], *d_tr = sb[15];
-    c.in_stage = true;
     // Conv_out + LeakyReLU
     RF_TRY(launch_ewise(dout, s.out, d_pre, U, 2, 0.2f, c.st));                                      // d(pre-activation)
     RF_TRY(b_conv3x3_dw(c, d_pre, C, s.cr, C, c.G(pre + "Conv_out.weight"), c.G(pre + "Conv_out.bias"), hh, ww));
@@ -604,26 +588,7 @@ int stage_backward(const Ctx& c, int i, int lvl, float* dout, float* din, int H,
     RF_TRY(b_conv1x1_dx(c, d_qkvp, 3 * C, P(h, t + "attn.qkv.weight"), C, d_ln1, Pn));                // d LN1 out
     // din (branch part) += dx1 (residual of x1 = in + attention) + (LayerNorm adjoint)
     RF_TRY(launch_ln_bwd(s.in, d_ln1, P(h, t + "norm1.body.weight"), din, c.G(t + "norm1.body.weight"), c.p->part, c.B, C, Pn, 1e-5f, 1, 1, c.st, d_x1, (int64_t)C * Pn));
-    RF_TRY(c.join());
-    c.in_stage = false;
-    return RF_OK;
-}
-
-// second stream of the step (the handle's branch stream and events, rf_handle.h): none while profiling -- the per-kernel brackets
-// assume one stream -- or when it cannot be created
-hipStream_t train_side_stream(rf_handle* h, hipStream_t st) {
-    if (h->side_failed || profiling_active()) return st;
-    if (!h->side) {
-        if (hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess) {
-            (void)hipGetLastError();
-            h->side_failed = true;
-            h->side = nullptr;
-            return st;
-        }
-    }
-    return h->side;
+    return c.side->join(c.st, c.wg);
 }
 
 }  // namespace
@@ -721,15 +686,15 @@ int rf_train_step(rf_handle* h, const float* in, const float* gt, float* grads, 
     hipStream_t st = (hipStream_t)stream;
     const rf_config& cfg = h->cfg;
     const int d = cfg.dim, oc = cfg.out_channels;
-    Ctx c{h, &p, grads, B, st};
+    SideJoinGuard joined(h->side, st);
+    Ctx c{h, &p, grads, B, st, st, &h->side};
     RF_TRY(check_hip(hipMemsetAsync(grads, 0, h->flat_floats * sizeof(float), st), "memset grads"));
     std::vector<PackDesc> pack_list;
     PackMap pack_map;
     build_pack_list(h, p.pack_cache, &pack_list, &pack_map);
     RF_TRY(launch_pack_batch(pack_list.data(), (int)pack_list.size(), st));
     c.packs = &pack_map;
-    c.wg = train_side_stream(h, st);
-    c.ev_fork = h->ev_fork; c.ev_join = h->ev_join;
+    const hipStream_t wg = h->side.get(st);      // the stages' weight-gradient stream
 
     // ------------------------------------------------------------------ forward
     RF_TRY(launch_pixel_unshuffle2(in, p.x4, B, 1, H, W, st));
@@ -790,7 +755,7 @@ int rf_train_step(rf_handle* h, const float* in, const float* gt, float* grads, 
     for (int i = 3; i >= 1; --i) {
         const int lvl = 3 - i, C = d << lvl, hh = H >> lvl, ww = W >> lvl, Pn = hh * ww;
         const std::string u = "up" + std::to_string(i), r = "channel_reduce" + std::to_string(i);
-        RF_TRY(stage_backward(c, 4 + i, lvl, ga, gb, H, W));                                   // gb = d(catr_i)
+        RF_TRY(stage_backward(c, wg, 4 + i, lvl, ga, gb, H, W));                                   // gb = d(catr_i)
         note.done("conv_tran" + std::to_string(4 + i) + ".");
         // channel_reduce_i over cat[up, skip]
         RF_TRY(b_conv1x1_dw(c, gb, C, p.up[i - 1], C, c.G(r + ".weight"), 2 * C, 0, c.G(r + ".bias"), hh, ww, 0, p.st[lvl + 1].out, C));
@@ -824,7 +789,7 @@ int rf_train_step(rf_handle* h, const float* in, const float* gt, float* grads, 
             RF_TRY(b_conv3x3_dx(c, p.tA, C / 2, P(h, "down" + std::to_string(i) + ".body.0.weight"), C, ga, hh, ww));
             RF_TRY(launch_ewise(ga, p.dskip[lvl], ga, (size_t)B * C * Pn, 0, 0.f, st));
         }
-        RF_TRY(stage_backward(c, i, lvl, ga, gb, H, W));                                       // gb = d(stage i input)
+        RF_TRY(stage_backward(c, wg, i, lvl, ga, gb, H, W));                                       // gb = d(stage i input)
         note.done("conv_tran" + std::to_string(i) + ".");                                      // and down_i, whose gradient came first
     }
     float* dcur = gb;

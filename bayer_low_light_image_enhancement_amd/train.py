@@ -43,8 +43,10 @@ class OverlappedReducer:
     ``nn.DataParallel``, train.py:108-111).  ``rf_train_step`` announces ranges of the flat buffer whose gradients are final, from
     the end of the buffer towards its start (``rf_set_grad_ready``); ``ready`` coalesces them into buckets of at least
     ``bucket_floats`` and starts each bucket's asynchronous all-reduce at once -- with the ``nccl`` backend (RCCL) the collective
-    is ordered behind the kernels already enqueued on the current stream and runs beside the rest of the backward pass; ``finish``
-    waits for all of them.  Works on any tensor / backend (the CPU tests drive it with ``gloo``)."""
+    is ordered behind the kernels already enqueued on the current stream and runs beside the rest of the backward pass; ``wait``
+    waits for all of them; ``finish`` checks that the whole buffer was announced, then waits.  ``begin`` waits too: a new round
+    never starts while the previous one may still write into the buffer.  Works on any tensor / backend (the CPU tests drive it
+    with ``gloo``)."""
 
     def __init__(self, flat: torch.Tensor, group=None, bucket_floats: int = 1 << 20):
         self.flat, self.group, self.bucket_floats = flat, group, int(bucket_floats)
@@ -52,7 +54,8 @@ class OverlappedReducer:
         self.hi = self.lo = flat.numel()
 
     def begin(self) -> None:
-        self.works, self.buckets = [], []
+        self.wait()
+        self.buckets = []
         self.hi = self.lo = self.flat.numel()
 
     def ready(self, offset: int, count: int) -> None:
@@ -69,6 +72,10 @@ class OverlappedReducer:
     def finish(self) -> None:
         if self.lo != 0:
             raise RuntimeError(f"gradient ranges stopped at float {self.lo}: the step did not announce the whole buffer")
+        self.wait()
+
+    def wait(self) -> None:
+        """Wait for the all-reduces started so far (none: nothing to do)."""
         for w in self.works:
             w.wait()
         self.works = []
@@ -121,6 +128,9 @@ class Trainer:
         model.invalidate_packed()
 
     def grad_of(self, key: str) -> torch.Tensor:
+        """View of ``key``'s gradient in ``self.grads``: this rank's local gradient on the serial path (until ``optimizer_step``
+        all-reduces it), the sum over the ranks after an overlapped step.  An all-reduce still in flight is waited first."""
+        self.reducer.wait()
         off, n = self.slices[key]
         return self.grads[off: off + n].view(dict(self.model.named_parameters())[key].shape)
 

@@ -452,3 +452,68 @@ np.save(sys.argv[2], y)
     close(res["two"], ref, 2e-5)
     close(res["composed"], res["two"], 1e-5)
     assert not np.array_equal(res["composed"], res["two"]), "the switch changed nothing"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["flca", "plain", "train"])
+def test_a_failed_call_leaves_no_side_stream_work_unjoined(device, tmp_path, mode):
+    """The diagnostic twin's RF_FAIL_FORK=2 fails the second fork of a call after enqueuing it; the call must still join the side
+    stream into the caller's stream before it returns.  Forward (flca: the guidance pyramid is still on the side stream; plain:
+    only the failed fork's wait is) inside a stream capture, which ends with an "unjoined" error if a fork is left open; training:
+    one weight-gradient kernel is in flight.  Then a normal call on the same handle repeats the clean result bit for bit."""
+    import os
+    import subprocess
+    import sys
+    from bayer_low_light_image_enhancement_amd import build
+    diag = build.build_diag_library()
+    code = r'''
+import os, sys, torch
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
+import cases
+from bayer_low_light_image_enhancement_amd import RawFormer, synth
+from bayer_low_light_image_enhancement_amd.train import Trainer
+dev, mode = torch.device("cuda:0"), sys.argv[2]
+
+def failing(call):
+    os.environ["RF_FAIL_FORK"] = "2"            # read by the library at every fork
+    try:
+        call()
+    except RuntimeError as e:
+        assert "RF_FAIL_FORK" in str(e), str(e)
+    else:
+        raise AssertionError("the injected failure did not surface")
+    finally:
+        del os.environ["RF_FAIL_FORK"]
+
+if mode == "train":
+    dim, seed = 16, 61
+    x = torch.from_numpy(synth.bayer_mosaic(seed, 1, 64, 128)).to(dev)
+    gt = torch.from_numpy(synth.smooth_rgb(seed, 1, 64, 128)).to(dev)
+    m = RawFormer(dim=dim)
+    m.load_state_dict({**m.state_dict(), **cases.model_state(dim, seed, "flca")}, strict=True)
+    tr = Trainer(m.to(dev).train())
+    loss = float(tr.forward_backward(x, gt))
+    ref = tr.grads.clone()
+    failing(lambda: tr.forward_backward(x, gt))
+    assert float(tr.forward_backward(x, gt)) == loss
+    assert torch.equal(tr.grads, ref)
+else:
+    kw = dict(variant="flca") if mode == "flca" else dict(variant="plain", branch_lrelu=True)
+    m = RawFormer(dim=32, **kw)
+    m.load_state_dict({**m.state_dict(), **cases.model_state(32, 41, mode)}, strict=True)
+    m = m.to(dev).eval()
+    x = torch.from_numpy(synth.bayer_mosaic(41, 1, 128, 160)).to(dev)
+    with torch.no_grad():
+        ref = m(x).clone()                      # warm-up: the side stream, packed weights and workspace exist before the capture
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):               # never replayed: only the end of the capture is checked
+            failing(lambda: m(x))
+        y = m(x)
+        torch.cuda.synchronize()
+        assert torch.equal(y, ref)
+print("ok")
+'''
+    r = subprocess.run([sys.executable, "-c", code, cases.REPO, mode], env=dict(os.environ, RF_LIB_PATH=diag), capture_output=True,
+                       text=True, timeout=600)
+    assert r.returncode == 0 and "ok" in r.stdout, (r.stdout + r.stderr)[-3000:]

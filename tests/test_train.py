@@ -255,6 +255,43 @@ def test_overlapped_gradient_allreduce_equals_the_serial_one_two_gloo_ranks(tmp_
     assert rec["n"] > 2_000_000 and len(rec["ranges"]) == 12          # RawFormer-S (FLCA): 2.48 M gradients in 12 module ranges
 
 
+def _abandoned_round_worker(rank, world, port, out):
+    """Two gloo ranks: one round of OverlappedReducer starts the all-reduce of every bucket and is never finished (a step whose
+    gradients nobody used), then a full round runs on new gradients in the same buffer.  begin() must wait for the first round's
+    all-reduces, so the buffer ends equal to the serial all-reduce of the second gradients, bit for bit."""
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from bayer_low_light_image_enhancement_amd.train import OverlappedReducer, allreduce_flat, bucket_bounds
+    n = 3_000_017
+    ranges = [(lo, hi - lo) for lo, hi in reversed(bucket_bounds(n, 100_000))]      # announced from the end of the buffer
+    g = torch.Generator().manual_seed(200 + rank)
+    first, second = torch.randn(n, generator=g), torch.randn(n, generator=g)
+    serial = second.clone()
+    allreduce_flat(serial)
+    flat = first.clone()
+    red = OverlappedReducer(flat, bucket_floats=1 << 18)
+    red.begin()
+    for lo, c in ranges:
+        red.ready(lo, c)
+    assert red.works                           # in flight, never finished
+    red.begin()
+    for lo, c in ranges:
+        flat[lo:lo + c] = second[lo:lo + c]
+        red.ready(lo, c)
+    red.finish()
+    red.wait()                                 # nothing left: a no-op
+    assert red.works == [] and torch.equal(flat, serial)
+    if rank == 0:
+        torch.save({"buckets": red.buckets}, out)
+    dist.destroy_process_group()
+
+
+def test_reducer_waits_for_an_unfinished_round_before_the_next_two_gloo_ranks(tmp_path):
+    out = str(tmp_path / "a.pt")
+    mp.spawn(_abandoned_round_worker, args=(2, _free_port(), out), nprocs=2, join=True)
+    assert len(torch.load(out, weights_only=True)["buckets"]) >= 4
+
+
 @pytest.mark.gpu
 def test_train_step_announces_every_gradient_once_and_in_order(device):
     """rf_train_step calls the gradient-ready callback for [offset, offset + count) from the end of the flat buffer to its start,
