@@ -1,16 +1,26 @@
-// The RawFormer handle (internal): parameter registry, packed-weight plan.  Shared by the forward schedule (rf_model.hip) and
-// the training schedule (rf_trainstep.hip).
+// The RawFormer handle (internal): parameter registry, packed-weight plans and the index table that the forward schedule
+// (rf_model.hip) and the training schedule (rf_trainstep.hip) read.  rf_create registers every tensor by name once (add_param)
+// and records its registry index where the schedules need it: per Conv_Transformer stage in `stage[1..7]`, per other module in
+// the fields below.  The schedules take pointers through those indices (prm / pk / pk3); names serve rf_set_param and
+// rf_param_info only.
 #pragma once
 #include <string>
 #include <unordered_map>
 #include <vector>
 #include "rf_common.h"
 
+// Forms of a weight in the training step's pack cache: as it multiplies in the forward (PF_N); transposed -- 3x3: also
+// tap-flipped -- for the dX product of the backward (PF_T); a ConvTranspose2d's dX GEMM (PF_CTB); ..3: the same matrix in b3 form
+enum PackForm { PF_N, PF_T, PF_CTB, PF_N3, PF_T3, PF_CTB3, PF_COUNT };
+constexpr size_t kNotCached = ~(size_t)0;
+
 struct Param {
     std::string name;
     int64_t shape[4];
     int ndim;
     const float* ptr;
+    int pack = -1, pack3 = -1;        // packs[] entries of its packed and its b3 form (rf_pack_params), -1: none
+    size_t cache[PF_COUNT];           // floats into the training pack cache per PackForm, kNotCached: not held
     size_t numel() const {
         size_t n = 1;
         for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
@@ -24,6 +34,27 @@ struct PackItem {
     PackKind kind;
     size_t offset;   // floats into the packed buffer
     size_t floats;
+};
+
+struct CachePack {   // one weight form of the training pack cache: `d` without its addresses (src = the parameter, dst = offset)
+    int param;
+    size_t offset;
+    rf::PackDesc d;
+};
+
+// registry indices of one Conv_Transformer stage (add_stage)
+struct StageIx {
+    int lvl;         // U-Net level: channels dim << lvl, size H >> lvl
+    int first;       // its first parameter
+    int ln1_w, ln1_b, temperature /* or log_temperature */, qkv_w, qkv_b, qkv_dw_w, qkv_dw_b, proj_w, proj_b;
+    int ln2_w, ln2_b, pw1_w, pw1_b, dw_w, dw_b, pw2_w, pw2_b;
+    int cr_w, cr_b, out_w, out_b;     // channel_reduce, Conv_out
+    int conv_w, conv_b;               // plain branch
+    int flca[10];    // FLCA branch, registry order = launch_flca_backward's: alpha, beta, gamma, low / high / chroma gate, se.1 w, b, se.3 w, b
+    int tc[14];      // TrueColor branch, registry order: weight and bias of color_attention, low_attn, high_attn, se.1, se.3, res_proj.0, .2
+    // composed tail (rf_flca.hip pack_tail), floats into the packed buffer of [Wb W2 | b'] (0 = not composed) and, plain variant
+    // only, of the static b3 weights [Wa | Wb | Wb W2]
+    size_t tail_offset = 0, tail3_offset = 0;
 };
 
 // The handle's second stream.  rf_forward and rf_train_step run part of their work on it: fork = an event on the caller's stream
@@ -55,18 +86,24 @@ struct SideJoinGuard {
 struct rf_handle {
     rf_config cfg;
     std::vector<Param> params;
-    std::unordered_map<std::string, int> index;
+    std::unordered_map<std::string, int> index;   // name -> params[] (rf_set_param)
     std::vector<PackItem> packs;
-    std::unordered_map<std::string, int> pack_index;   // weight name -> packs[]
-    std::unordered_map<std::string, int> pack3_index;  // weight name -> packs[] entry of its b3 form
     size_t packed_floats = 0;
-    size_t upcat_offset[3] = {0, 0, 0};   // composed decoder-step weights (rf_upcat.hip), floats into the packed buffer
-    // composed stage tails (rf_flca.hip pack_tail): per Conv_Transformer stage 1..7, floats into the packed buffer of [Wb W2 | b']
-    // (0 = stage not composed) and, plain variant only, of the static b3 weights [Wa | Wb | Wb W2]
-    size_t tail_offset[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tail3_offset[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const float* packed = nullptr;   // caller memory, valid after rf_pack_params
-    std::vector<size_t> flat_offset;  // float offset of every parameter in the flat parameter / gradient buffers (training)
+    // the index table
+    StageIx stage[8];                // 1..7
+    int embedding_w, embedding_b, conv_out_w, conv_out_b;
+    int down_w[3], up_w[3], up_b[3], upcr_w[3], upcr_b[3];   // down<i>, up<i>, channel_reduce<i> at [i - 1]
+    int bp[10], cc[9];               // TrueColor: bayer_processor.* and color_correction.*, registry order
+    size_t upcat_offset[3] = {0, 0, 0};   // composed decoder-step weights (rf_upcat.hip), floats into the packed buffer
+    // training (plan_training): float offset of every parameter in the flat parameter / gradient buffers; the gradient ranges in
+    // the order the step announces them; the pack cache's forms in the order it writes them
+    std::vector<size_t> flat_offset;
     size_t flat_floats = 0;
+    struct GradRange { size_t offset, count; };
+    std::vector<GradRange> grad_ranges;
+    std::vector<CachePack> cache_packs;
+    size_t cache_floats = 0;
     // spatial shard of one frame (rf_set_shard): interior rows [y_lo, y_hi) of the local window and the frame's total rows, in
     // packed (level-0) rows; `allreduce` sums a float buffer over the ranks on the given stream
     int shard_y_lo = 0, shard_y_hi = 0, shard_total_rows = 0;
@@ -77,8 +114,11 @@ struct rf_handle {
     // training: notification that a range of the flat gradient buffer is final (rf_set_grad_ready)
     void (*grad_ready)(void* user, size_t offset, size_t count, void* stream) = nullptr;
     void* grad_ready_user = nullptr;
+
+    const float* prm(int ix) const { return params[ix].ptr; }
+    const float* pk(int ix) const { return packed + packs[params[ix].pack].offset; }
+    const float* pk3(int ix) const { return packed + packs[params[ix].pack3].offset; }
 };
 
-
-inline const float* rf_param_ptr(const rf_handle* h, const std::string& name) { return h->params[h->index.at(name)].ptr; }
-inline int rf_param_index(const rf_handle* h, const std::string& name) { return h->index.at(name); }
+// rf_trainstep.hip: lay out the flat buffers, the gradient ranges and the pack cache (rf_create, once the registry is complete)
+void plan_training(rf_handle* h);

@@ -14,7 +14,7 @@ using namespace rf;
 
 namespace {
 
-void add_param(rf_handle* h, const std::string& name, std::initializer_list<int64_t> shape) {
+int add_param(rf_handle* h, const std::string& name, std::initializer_list<int64_t> shape) {
     Param p;
     p.name = name;
     p.ndim = (int)shape.size();
@@ -24,11 +24,11 @@ void add_param(rf_handle* h, const std::string& name, std::initializer_list<int6
     p.ptr = nullptr;
     h->index[name] = (int)h->params.size();
     h->params.push_back(p);
+    return (int)h->params.size() - 1;
 }
 
-void add_pack(rf_handle* h, const std::string& name, PackKind kind) {
-    const int pi = h->index.at(name);
-    const Param& p = h->params[pi];
+void add_pack(rf_handle* h, int pi, PackKind kind) {
+    Param& p = h->params[pi];
     PackItem it;
     it.param = pi;
     it.kind = kind;
@@ -38,7 +38,7 @@ void add_pack(rf_handle* h, const std::string& name, PackKind kind) {
     else if (kind == PK_1x1_B3) it.floats = packed1x1_b3_floats((int)p.shape[1], (int)p.shape[0]);
     else it.floats = packed1x1_floats((int)p.shape[0], 4 * (int)p.shape[1]);
     h->packed_floats += align_up(it.floats, 64);
-    (kind == PK_1x1_B3 ? h->pack3_index : h->pack_index)[name] = (int)h->packs.size();
+    (kind == PK_1x1_B3 ? p.pack3 : p.pack) = (int)h->packs.size();
     h->packs.push_back(it);
 }
 
@@ -47,96 +47,92 @@ void add_pack(rf_handle* h, const std::string& name, PackKind kind) {
 // (run_stage decides per call: the fused kernel takes only some image sizes).
 bool tail_composable(int C, int hc) { return C % 32 == 0 && hc % 32 == 0 && hc > 0; }
 
-void add_stage(rf_handle* h, int i, int C, int heads) {
+void add_stage(rf_handle* h, int i, int lvl) {
     const rf_config& cfg = h->cfg;
+    const int C = cfg.dim << lvl;
+    StageIx& s = h->stage[i];
+    s.lvl = lvl;
+    s.first = (int)h->params.size();
     const std::string pre = "conv_tran" + std::to_string(i) + ".";
     if (cfg.variant == RF_VARIANT_TRUECOLOR) {
         // EnhancedFLCA (BayerTORGBColorMultiLvl.py:192-231), state_dict order
         const std::string f = pre + "FLCA.";
         const int hid = C / 8 > 8 ? C / 8 : 8;
-        add_param(h, f + "color_attention.0.weight", {C, 5, 3, 3});
-        add_param(h, f + "color_attention.0.bias", {C});
-        add_param(h, f + "low_attn.0.weight", {C, 1, 3, 3});
-        add_param(h, f + "low_attn.0.bias", {C});
-        add_param(h, f + "high_attn.0.weight", {C, 1, 3, 3});
-        add_param(h, f + "high_attn.0.bias", {C});
-        add_param(h, f + "se.1.weight", {hid, C, 1, 1});
-        add_param(h, f + "se.1.bias", {hid});
-        add_param(h, f + "se.3.weight", {C, hid, 1, 1});
-        add_param(h, f + "se.3.bias", {C});
-        add_param(h, f + "res_proj.0.weight", {C, C, 1, 1});
-        add_param(h, f + "res_proj.0.bias", {C});
-        add_param(h, f + "res_proj.2.weight", {C, C, 1, 1});
-        add_param(h, f + "res_proj.2.bias", {C});
-        for (const char* n : {"res_proj.0.weight", "res_proj.2.weight"}) {
-            add_pack(h, f + n, PK_1x1);
-            add_pack(h, f + n, PK_1x1_B3);
+        s.tc[0] = add_param(h, f + "color_attention.0.weight", {C, 5, 3, 3});
+        s.tc[1] = add_param(h, f + "color_attention.0.bias", {C});
+        s.tc[2] = add_param(h, f + "low_attn.0.weight", {C, 1, 3, 3});
+        s.tc[3] = add_param(h, f + "low_attn.0.bias", {C});
+        s.tc[4] = add_param(h, f + "high_attn.0.weight", {C, 1, 3, 3});
+        s.tc[5] = add_param(h, f + "high_attn.0.bias", {C});
+        s.tc[6] = add_param(h, f + "se.1.weight", {hid, C, 1, 1});
+        s.tc[7] = add_param(h, f + "se.1.bias", {hid});
+        s.tc[8] = add_param(h, f + "se.3.weight", {C, hid, 1, 1});
+        s.tc[9] = add_param(h, f + "se.3.bias", {C});
+        s.tc[10] = add_param(h, f + "res_proj.0.weight", {C, C, 1, 1});
+        s.tc[11] = add_param(h, f + "res_proj.0.bias", {C});
+        s.tc[12] = add_param(h, f + "res_proj.2.weight", {C, C, 1, 1});
+        s.tc[13] = add_param(h, f + "res_proj.2.bias", {C});
+        for (int k : {10, 12}) {
+            add_pack(h, s.tc[k], PK_1x1);
+            add_pack(h, s.tc[k], PK_1x1_B3);
         }
     } else if (cfg.variant == RF_VARIANT_FLCA) {
         const std::string f = pre + "FLCA.";
         const int hid = C / 8 > 8 ? C / 8 : 8;
-        add_param(h, f + "alpha", {});
-        add_param(h, f + "beta", {});
-        add_param(h, f + "gamma", {});
-        add_param(h, f + "low_attn.0.weight", {C, 1, 3, 3});
-        add_param(h, f + "high_attn.0.weight", {C, 1, 3, 3});
-        add_param(h, f + "chroma_attn.0.weight", {C, 2, 3, 3});
-        add_param(h, f + "se.1.weight", {hid, C, 1, 1});
-        add_param(h, f + "se.1.bias", {hid});
-        add_param(h, f + "se.3.weight", {C, hid, 1, 1});
-        add_param(h, f + "se.3.bias", {C});
+        s.flca[0] = add_param(h, f + "alpha", {});
+        s.flca[1] = add_param(h, f + "beta", {});
+        s.flca[2] = add_param(h, f + "gamma", {});
+        s.flca[3] = add_param(h, f + "low_attn.0.weight", {C, 1, 3, 3});
+        s.flca[4] = add_param(h, f + "high_attn.0.weight", {C, 1, 3, 3});
+        s.flca[5] = add_param(h, f + "chroma_attn.0.weight", {C, 2, 3, 3});
+        s.flca[6] = add_param(h, f + "se.1.weight", {hid, C, 1, 1});
+        s.flca[7] = add_param(h, f + "se.1.bias", {hid});
+        s.flca[8] = add_param(h, f + "se.3.weight", {C, hid, 1, 1});
+        s.flca[9] = add_param(h, f + "se.3.bias", {C});
     } else {
-        add_param(h, pre + "conv.weight", {C, C, 3, 3});
-        add_param(h, pre + "conv.bias", {C});
-        add_pack(h, pre + "conv.weight", PK_3x3);
+        s.conv_w = add_param(h, pre + "conv.weight", {C, C, 3, 3});
+        s.conv_b = add_param(h, pre + "conv.bias", {C});
+        add_pack(h, s.conv_w, PK_3x3);
     }
     const std::string t = pre + "Transformer.";
-    const int hc = C * cfg.ffn_expansion;
-    add_param(h, t + "norm1.body.weight", {C});
-    add_param(h, t + "norm1.body.bias", {C});
-    add_param(h, t + (cfg.variant == RF_VARIANT_TRUECOLOR ? "attn.log_temperature" : "attn.temperature"), {heads, 1, 1});
-    add_param(h, t + "attn.qkv.weight", {3 * C, C, 1, 1});
-    add_param(h, t + "attn.qkv.bias", {3 * C});
-    add_param(h, t + "attn.qkv_dwconv.weight", {3 * C, 1, 3, 3});
-    add_param(h, t + "attn.qkv_dwconv.bias", {3 * C});
-    add_param(h, t + "attn.project_out.weight", {C, C, 1, 1});
-    add_param(h, t + "attn.project_out.bias", {C});
-    add_param(h, t + "norm2.body.weight", {C});
-    add_param(h, t + "norm2.body.bias", {C});
-    add_param(h, t + "ffn.pointwise1.weight", {hc, C, 1, 1});
-    add_param(h, t + "ffn.pointwise1.bias", {hc});
-    add_param(h, t + "ffn.depthwise.weight", {hc, 1, 3, 3});
-    add_param(h, t + "ffn.depthwise.bias", {hc});
-    add_param(h, t + "ffn.pointwise2.weight", {C, hc, 1, 1});
-    add_param(h, t + "ffn.pointwise2.bias", {C});
-    add_param(h, pre + "channel_reduce.weight", {C, 2 * C, 1, 1});
-    add_param(h, pre + "channel_reduce.bias", {C});
-    add_param(h, pre + "Conv_out.weight", {C, C, 3, 3});
-    add_param(h, pre + "Conv_out.bias", {C});
-    add_pack(h, t + "attn.qkv.weight", PK_1x1);
-    add_pack(h, t + "ffn.pointwise1.weight", PK_1x1);
-    add_pack(h, t + "ffn.pointwise2.weight", PK_1x1);
-    add_pack(h, t + "attn.qkv.weight", PK_1x1_B3);          // b3 forms for the bf16x3 GEMM kernels (rf_common.h)
-    add_pack(h, t + "ffn.pointwise1.weight", PK_1x1_B3);
-    add_pack(h, t + "ffn.pointwise2.weight", PK_1x1_B3);
+    const int hc = C * cfg.ffn_expansion, heads = cfg.heads[lvl];
+    s.ln1_w = add_param(h, t + "norm1.body.weight", {C});
+    s.ln1_b = add_param(h, t + "norm1.body.bias", {C});
+    s.temperature = add_param(h, t + (cfg.variant == RF_VARIANT_TRUECOLOR ? "attn.log_temperature" : "attn.temperature"), {heads, 1, 1});
+    s.qkv_w = add_param(h, t + "attn.qkv.weight", {3 * C, C, 1, 1});
+    s.qkv_b = add_param(h, t + "attn.qkv.bias", {3 * C});
+    s.qkv_dw_w = add_param(h, t + "attn.qkv_dwconv.weight", {3 * C, 1, 3, 3});
+    s.qkv_dw_b = add_param(h, t + "attn.qkv_dwconv.bias", {3 * C});
+    s.proj_w = add_param(h, t + "attn.project_out.weight", {C, C, 1, 1});
+    s.proj_b = add_param(h, t + "attn.project_out.bias", {C});
+    s.ln2_w = add_param(h, t + "norm2.body.weight", {C});
+    s.ln2_b = add_param(h, t + "norm2.body.bias", {C});
+    s.pw1_w = add_param(h, t + "ffn.pointwise1.weight", {hc, C, 1, 1});
+    s.pw1_b = add_param(h, t + "ffn.pointwise1.bias", {hc});
+    s.dw_w = add_param(h, t + "ffn.depthwise.weight", {hc, 1, 3, 3});
+    s.dw_b = add_param(h, t + "ffn.depthwise.bias", {hc});
+    s.pw2_w = add_param(h, t + "ffn.pointwise2.weight", {C, hc, 1, 1});
+    s.pw2_b = add_param(h, t + "ffn.pointwise2.bias", {C});
+    s.cr_w = add_param(h, pre + "channel_reduce.weight", {C, 2 * C, 1, 1});
+    s.cr_b = add_param(h, pre + "channel_reduce.bias", {C});
+    s.out_w = add_param(h, pre + "Conv_out.weight", {C, C, 3, 3});
+    s.out_b = add_param(h, pre + "Conv_out.bias", {C});
+    for (int w : {s.qkv_w, s.pw1_w, s.pw2_w}) add_pack(h, w, PK_1x1);
+    for (int w : {s.qkv_w, s.pw1_w, s.pw2_w}) add_pack(h, w, PK_1x1_B3);      // b3 forms for the bf16x3 GEMM kernels (rf_common.h)
     if (cfg.variant == RF_VARIANT_PLAIN) {
-        add_pack(h, pre + "channel_reduce.weight", PK_1x1);
-        add_pack(h, pre + "channel_reduce.weight", PK_1x1_B3);
+        add_pack(h, s.cr_w, PK_1x1);
+        add_pack(h, s.cr_w, PK_1x1_B3);
     }
     if (tail_composable(C, hc)) {      // pointwise2 composed into channel_reduce (run_stage)
-        h->tail_offset[i] = h->packed_floats;
+        s.tail_offset = h->packed_floats;
         h->packed_floats += align_up(tail_composed_floats(C, hc), 64);
         if (cfg.variant == RF_VARIANT_PLAIN) {
-            h->tail3_offset[i] = h->packed_floats;
+            s.tail3_offset = h->packed_floats;
             h->packed_floats += align_up(packed1x1_b3_floats(2 * C + hc, C), 64);
         }
     }
-    add_pack(h, pre + "Conv_out.weight", PK_3x3);
+    add_pack(h, s.out_w, PK_3x3);
 }
-
-const float* P(const rf_handle* h, const std::string& name) { return h->params[h->index.at(name)].ptr; }
-const float* PK(const rf_handle* h, const std::string& name) { return h->packed + h->packs[h->pack_index.at(name)].offset; }
-const float* PK3(const rf_handle* h, const std::string& name) { return h->packed + h->packs[h->pack3_index.at(name)].offset; }
 
 // ---- workspace plan ---------------------------------------------------------------------
 struct Plan {
@@ -219,29 +215,28 @@ int make_plan(const rf_handle* h, int B, int H, int W, Plan& p) {
 }
 
 // one Conv_Transformer stage
-int run_stage(rf_handle* h, int i, int lvl, const float* in, float* out, float* ws, const Plan& p,
+int run_stage(rf_handle* h, int i, const float* in, float* out, float* ws, const Plan& p,
               int B, int H, int W, hipStream_t st, hipStream_t side) {
     const rf_config& cfg = h->cfg;
-    const int C = cfg.dim << lvl, hh = H >> lvl, ww = W >> lvl, Pn = hh * ww, heads = cfg.heads[lvl];
+    const StageIx& x = h->stage[i];
+    const int lvl = x.lvl, C = cfg.dim << lvl, hh = H >> lvl, ww = W >> lvl, Pn = hh * ww, heads = cfg.heads[lvl];
     const int hc = C * cfg.ffn_expansion;
-    const std::string pre = "conv_tran" + std::to_string(i) + ".", t = pre + "Transformer.";
     float* trans = ws + p.trans;
     float* xs = ws + p.xs;
     float* crb = ws + p.cr;
 
     // TransformerBlock: x + attn(LN1(x)), then x + ffn(LN2(x))  (rf_block.hip)
     TbParams tp{};
-    tp.ln1_w = P(h, t + "norm1.body.weight"); tp.ln1_b = P(h, t + "norm1.body.bias");
-    if (cfg.variant != RF_VARIANT_TRUECOLOR) tp.temperature = P(h, t + "attn.temperature");
-    tp.qkv_wp = PK(h, t + "attn.qkv.weight"); tp.qkv_b = P(h, t + "attn.qkv.bias");
-    tp.qkv_dw_w = P(h, t + "attn.qkv_dwconv.weight"); tp.qkv_dw_b = P(h, t + "attn.qkv_dwconv.bias");
-    tp.proj_w = P(h, t + "attn.project_out.weight"); tp.proj_b = P(h, t + "attn.project_out.bias");
-    tp.ln2_w = P(h, t + "norm2.body.weight"); tp.ln2_b = P(h, t + "norm2.body.bias");
-    tp.pw1_wp = PK(h, t + "ffn.pointwise1.weight"); tp.pw1_b = P(h, t + "ffn.pointwise1.bias");
-    tp.dw_w = P(h, t + "ffn.depthwise.weight"); tp.dw_b = P(h, t + "ffn.depthwise.bias");
-    tp.pw2_wp = PK(h, t + "ffn.pointwise2.weight"); tp.pw2_b = P(h, t + "ffn.pointwise2.bias");
-    tp.qkv_wp3 = PK3(h, t + "attn.qkv.weight"); tp.pw1_wp3 = PK3(h, t + "ffn.pointwise1.weight"); tp.pw2_wp3 = PK3(h, t + "ffn.pointwise2.weight");
-    if (cfg.variant == RF_VARIANT_TRUECOLOR) { tp.temperature = P(h, t + "attn.log_temperature"); tp.log_temperature = 1; }
+    tp.ln1_w = h->prm(x.ln1_w); tp.ln1_b = h->prm(x.ln1_b);
+    tp.temperature = h->prm(x.temperature); tp.log_temperature = cfg.variant == RF_VARIANT_TRUECOLOR;
+    tp.qkv_wp = h->pk(x.qkv_w); tp.qkv_b = h->prm(x.qkv_b);
+    tp.qkv_dw_w = h->prm(x.qkv_dw_w); tp.qkv_dw_b = h->prm(x.qkv_dw_b);
+    tp.proj_w = h->prm(x.proj_w); tp.proj_b = h->prm(x.proj_b);
+    tp.ln2_w = h->prm(x.ln2_w); tp.ln2_b = h->prm(x.ln2_b);
+    tp.pw1_wp = h->pk(x.pw1_w); tp.pw1_b = h->prm(x.pw1_b);
+    tp.dw_w = h->prm(x.dw_w); tp.dw_b = h->prm(x.dw_b);
+    tp.pw2_wp = h->pk(x.pw2_w); tp.pw2_b = h->prm(x.pw2_b);
+    tp.qkv_wp3 = h->pk3(x.qkv_w); tp.pw1_wp3 = h->pk3(x.pw1_w); tp.pw2_wp3 = h->pk3(x.pw2_w);
     // spatial shard: this level's interior rows and the frame's pixel count for the pooled mean
     const bool sharded = h->shard_allreduce != nullptr;
     const int ylo = sharded ? h->shard_y_lo >> lvl : 0, yhi = sharded ? h->shard_y_hi >> lvl : 0;
@@ -251,12 +246,12 @@ int run_stage(rf_handle* h, int i, int lvl, const float* in, float* out, float* 
     // Composed tail: where the FFN runs op by op, its last GEMM (x1 + W2 g + b2 -> trans, K = hidden) and channel_reduce
     // ([Wa' | Wb] [xs ; trans], K = 2C) become ONE GEMM over [xs ; x1 ; g] with [Wa' | Wb | Wb W2] (same MFMA count; `trans` --
     // C floats per pixel written and read back -- never exists).  The bias and Wb W2 are composed at parameter load.
-    bool compose = h->tail_offset[i] != 0 && Pn % 4 == 0 && !transformer_ffn_is_fused(tp, C, hc, hh, ww);
+    bool compose = x.tail_offset != 0 && Pn % 4 == 0 && !transformer_ffn_is_fused(tp, C, hc, hh, ww);
 #ifdef RF_DIAG   // diagnostic build only: the two-GEMM form
     if (getenv("RF_NO_COMPOSE") || getenv("RF_NO_B3")) compose = false;
 #endif
     tp.defer_pw2 = compose;
-    const float* composed = compose ? h->packed + h->tail_offset[i] : nullptr;
+    const float* composed = compose ? h->packed + x.tail_offset : nullptr;
     // the branch is launched first (on the branch stream when there is one), the block beside it; TrueColor's branch borrows
     // bufA and therefore follows the block on the same stream
     if (cfg.variant == RF_VARIANT_TRUECOLOR) RF_TRY(run_transformer(tp, in, trans, ws, to, B, C, heads, hc, hh, ww, st));
@@ -266,54 +261,51 @@ int run_stage(rf_handle* h, int i, int lvl, const float* in, float* out, float* 
     Conv1x1Args r{};
     r.x1 = xs; r.C1 = C; r.x1_bstride = (int64_t)C * Pn;
     r.x2 = trans; r.C2 = C; r.x2_bstride = (int64_t)C * Pn;
-    r.bias = P(h, pre + "channel_reduce.bias");
+    r.bias = h->prm(x.cr_b);
     r.out = crb; r.out_bstride = (int64_t)C * Pn; r.Cout = C; r.B = B; r.P = Pn; r.w = ww;
     if (cfg.variant == RF_VARIANT_TRUECOLOR) {
         // EnhancedFLCA (BayerTORGBColorMultiLvl.py:249-293): spatial gate -> x + 0.2 tanh(res_proj(x)) -> squeeze-excite (folded
         // into channel_reduce like the FLCA variant's)
-        const std::string f = pre + "FLCA.";
-        RF_TRY(launch_tc_spatial(in, xs, ws + p.guide[lvl], P(h, f + "color_attention.0.weight"), P(h, f + "color_attention.0.bias"),
-                                 P(h, f + "low_attn.0.weight"), P(h, f + "low_attn.0.bias"), P(h, f + "high_attn.0.weight"),
-                                 P(h, f + "high_attn.0.bias"), B, C, hh, ww, st));
+        const int* b = x.tc;   // registry order (StageIx)
+        RF_TRY(launch_tc_spatial(in, xs, ws + p.guide[lvl], h->prm(b[0]), h->prm(b[1]), h->prm(b[2]), h->prm(b[3]), h->prm(b[4]), h->prm(b[5]),
+                                 B, C, hh, ww, st));
         Conv1x1Args r0{};
-        r0.x1 = xs; r0.C1 = C; r0.x1_bstride = (int64_t)C * Pn; r0.wp = PK(h, f + "res_proj.0.weight"); r0.wp3 = PK3(h, f + "res_proj.0.weight");
-        r0.bias = P(h, f + "res_proj.0.bias"); r0.out = crb; r0.out_bstride = (int64_t)C * Pn; r0.Cout = C; r0.B = B; r0.P = Pn; r0.w = ww; r0.act = 2;
+        r0.x1 = xs; r0.C1 = C; r0.x1_bstride = (int64_t)C * Pn; r0.wp = h->pk(b[10]); r0.wp3 = h->pk3(b[10]);
+        r0.bias = h->prm(b[11]); r0.out = crb; r0.out_bstride = (int64_t)C * Pn; r0.Cout = C; r0.B = B; r0.P = Pn; r0.w = ww; r0.act = 2;
         RF_TRY(launch_conv1x1(r0, st));
         Conv1x1Args r2 = r0;
-        r2.x1 = crb; r2.wp = PK(h, f + "res_proj.2.weight"); r2.wp3 = PK3(h, f + "res_proj.2.weight"); r2.bias = P(h, f + "res_proj.2.bias");
+        r2.x1 = crb; r2.wp = h->pk(b[12]); r2.wp3 = h->pk3(b[12]); r2.bias = h->prm(b[13]);
         r2.out = ws + p.bufA; r2.act = 0;
         RF_TRY(launch_conv1x1(r2, st));
         RF_TRY(launch_tc_residual(xs, ws + p.bufA, xs, ws + p.flca_partial, B, C, hh, ww, st));
         const int hid = C / 8 > 8 ? C / 8 : 8;
-        RF_TRY(launch_flca_se_fold(ws + p.flca_partial, tc_nblk(hh, ww), Pn, P(h, f + "se.1.weight"), P(h, f + "se.1.bias"),
-                                   P(h, f + "se.3.weight"), P(h, f + "se.3.bias"), hid, P(h, pre + "channel_reduce.weight"),
-                                   ws + p.wfold_cr, ws + p.wfold_cr3, ws + p.ch, B, C, st, composed, hc));
+        RF_TRY(launch_flca_se_fold(ws + p.flca_partial, tc_nblk(hh, ww), Pn, h->prm(b[6]), h->prm(b[7]), h->prm(b[8]), h->prm(b[9]), hid,
+                                   h->prm(x.cr_w), ws + p.wfold_cr, ws + p.wfold_cr3, ws + p.ch, B, C, st, composed, hc));
         r.wp = ws + p.wfold_cr; r.wp_bstride = (int64_t)packed1x1_floats(2 * C, C);
         r.wp3 = ws + p.wfold_cr3; r.wp3_bstride = (int64_t)packed1x1_b3_floats(compose ? 2 * C + hc : 2 * C, C);
     } else if (cfg.variant == RF_VARIANT_FLCA) {
-        const std::string f = pre + "FLCA.";
+        const int* b = x.flca;   // registry order (StageIx)
         FlcaSpatialArgs s{};
         s.feat = in; s.xs = xs; s.guide = ws + p.guide[lvl];
-        s.w_low = P(h, f + "low_attn.0.weight"); s.w_high = P(h, f + "high_attn.0.weight"); s.w_chr = P(h, f + "chroma_attn.0.weight");
-        s.alpha = P(h, f + "alpha"); s.beta = P(h, f + "beta"); s.gamma = P(h, f + "gamma");
+        s.w_low = h->prm(b[3]); s.w_high = h->prm(b[4]); s.w_chr = h->prm(b[5]);
+        s.alpha = h->prm(b[0]); s.beta = h->prm(b[1]); s.gamma = h->prm(b[2]);
         s.partial = ws + p.flca_partial; s.B = B; s.C = C; s.h = hh; s.w = ww; s.nblk = flca_nblk(hh, ww);
         s.ylo = ylo; s.yhi = yhi;
         RF_TRY(launch_flca_spatial(s, side));
         if (sharded) h->shard_allreduce(h->shard_user, s.partial, (size_t)B * s.nblk * C, 0, (void*)side);
         const int hid = C / 8 > 8 ? C / 8 : 8;
-        RF_TRY(launch_flca_se_fold(s.partial, s.nblk, P_pool, P(h, f + "se.1.weight"), P(h, f + "se.1.bias"),
-                                   P(h, f + "se.3.weight"), P(h, f + "se.3.bias"), hid, P(h, pre + "channel_reduce.weight"),
+        RF_TRY(launch_flca_se_fold(s.partial, s.nblk, P_pool, h->prm(b[6]), h->prm(b[7]), h->prm(b[8]), h->prm(b[9]), hid, h->prm(x.cr_w),
                                    ws + p.wfold_cr, ws + p.wfold_cr3, ws + p.ch, B, C, side, composed, hc));
         r.wp = ws + p.wfold_cr; r.wp_bstride = (int64_t)packed1x1_floats(2 * C, C);
         r.wp3 = ws + p.wfold_cr3; r.wp3_bstride = (int64_t)packed1x1_b3_floats(compose ? 2 * C + hc : 2 * C, C);
     } else {
         Conv3x3Args cb{};
-        cb.x = in; cb.x_bstride = (int64_t)C * Pn; cb.wp = PK(h, pre + "conv.weight"); cb.bias = P(h, pre + "conv.bias");
+        cb.x = in; cb.x_bstride = (int64_t)C * Pn; cb.wp = h->pk(x.conv_w); cb.bias = h->prm(x.conv_b);
         cb.out = xs; cb.out_bstride = (int64_t)C * Pn; cb.B = B; cb.Cin = C; cb.Cout = C; cb.h = hh; cb.w = ww;
         cb.act = cfg.branch_lrelu ? 1 : 0;
         RF_TRY(launch_conv3x3(cb, side));
-        r.wp = PK(h, pre + "channel_reduce.weight");
-        r.wp3 = compose ? h->packed + h->tail3_offset[i] : PK3(h, pre + "channel_reduce.weight");
+        r.wp = h->pk(x.cr_w);
+        r.wp3 = compose ? h->packed + x.tail3_offset : h->pk3(x.cr_w);
     }
     if (cfg.variant != RF_VARIANT_TRUECOLOR) {
         RF_TRY(run_transformer(tp, in, trans, ws, to, B, C, heads, hc, hh, ww, st));
@@ -328,7 +320,7 @@ int run_stage(rf_handle* h, int i, int lvl, const float* in, float* out, float* 
     RF_TRY(launch_conv1x1(r, st));
 
     Conv3x3Args co{};
-    co.x = crb; co.x_bstride = (int64_t)C * Pn; co.wp = PK(h, pre + "Conv_out.weight"); co.bias = P(h, pre + "Conv_out.bias");
+    co.x = crb; co.x_bstride = (int64_t)C * Pn; co.wp = h->pk(x.out_w); co.bias = h->prm(x.out_b);
     co.out = out; co.out_bstride = (int64_t)C * Pn; co.B = B; co.Cin = C; co.Cout = C; co.h = hh; co.w = ww; co.act = 1;
     if (p.ks_floats) { co.ks_scratch = ws + p.ks; co.ks_floats = p.ks_floats; }
     RF_TRY(launch_conv3x3(co, st));
@@ -418,62 +410,56 @@ int rf_create(const rf_config* cfg, rf_handle** out) {
     h->cfg = *cfg;
     const int d = cfg->dim;
     if (cfg->variant == RF_VARIANT_TRUECOLOR) {   // EnhancedBayerProcessor (BayerTORGBColorMultiLvl.py:73-98), state_dict order
-        add_param(h, "bayer_processor.wb_gains", {4});
-        add_param(h, "bayer_processor.color_matrix", {3, 4});
-        add_param(h, "bayer_processor.demosaic_refine.0.weight", {32, 3, 3, 3});
-        add_param(h, "bayer_processor.demosaic_refine.0.bias", {32});
-        add_param(h, "bayer_processor.demosaic_refine.2.weight", {3, 32, 3, 3});
-        add_param(h, "bayer_processor.demosaic_refine.2.bias", {3});
-        add_param(h, "bayer_processor.chroma_extractor.0.weight", {16, 4, 3, 3});
-        add_param(h, "bayer_processor.chroma_extractor.0.bias", {16});
-        add_param(h, "bayer_processor.chroma_extractor.2.weight", {2, 16, 3, 3});
-        add_param(h, "bayer_processor.chroma_extractor.2.bias", {2});
-        for (const char* n : {"demosaic_refine.0.weight", "demosaic_refine.2.weight", "chroma_extractor.0.weight", "chroma_extractor.2.weight"})
-            add_pack(h, std::string("bayer_processor.") + n, PK_3x3);
+        h->bp[0] = add_param(h, "bayer_processor.wb_gains", {4});
+        h->bp[1] = add_param(h, "bayer_processor.color_matrix", {3, 4});
+        h->bp[2] = add_param(h, "bayer_processor.demosaic_refine.0.weight", {32, 3, 3, 3});
+        h->bp[3] = add_param(h, "bayer_processor.demosaic_refine.0.bias", {32});
+        h->bp[4] = add_param(h, "bayer_processor.demosaic_refine.2.weight", {3, 32, 3, 3});
+        h->bp[5] = add_param(h, "bayer_processor.demosaic_refine.2.bias", {3});
+        h->bp[6] = add_param(h, "bayer_processor.chroma_extractor.0.weight", {16, 4, 3, 3});
+        h->bp[7] = add_param(h, "bayer_processor.chroma_extractor.0.bias", {16});
+        h->bp[8] = add_param(h, "bayer_processor.chroma_extractor.2.weight", {2, 16, 3, 3});
+        h->bp[9] = add_param(h, "bayer_processor.chroma_extractor.2.bias", {2});
+        for (int k : {2, 4, 6, 8}) add_pack(h, h->bp[k], PK_3x3);
     }
-    add_param(h, "embedding.weight", {d, 4 * cfg->inp_channels, 3, 3});
-    add_param(h, "embedding.bias", {d});
-    add_pack(h, "embedding.weight", PK_3x3);
+    h->embedding_w = add_param(h, "embedding.weight", {d, 4 * cfg->inp_channels, 3, 3});
+    h->embedding_b = add_param(h, "embedding.bias", {d});
+    add_pack(h, h->embedding_w, PK_3x3);
     for (int i = 1; i <= 3; ++i) {
         const int C = d << (i - 1);
-        add_stage(h, i, C, cfg->heads[i - 1]);
-        const std::string n = "down" + std::to_string(i) + ".body.0.weight";
-        add_param(h, n, {C / 2, C, 3, 3});
-        add_pack(h, n, PK_3x3);
+        add_stage(h, i, i - 1);
+        h->down_w[i - 1] = add_param(h, "down" + std::to_string(i) + ".body.0.weight", {C / 2, C, 3, 3});
+        add_pack(h, h->down_w[i - 1], PK_3x3);
     }
-    add_stage(h, 4, d * 8, cfg->heads[3]);
+    add_stage(h, 4, 3);
     for (int i = 1; i <= 3; ++i) {
         const int lvl = 3 - i, C = d << lvl;
         const std::string u = "up" + std::to_string(i), r = "channel_reduce" + std::to_string(i);
-        add_param(h, u + ".weight", {2 * C, C, 2, 2});
-        add_param(h, u + ".bias", {C});
-        add_param(h, r + ".weight", {C, 2 * C, 1, 1});
-        add_param(h, r + ".bias", {C});
-        add_pack(h, u + ".weight", PK_CONVT);      // the two-kernel form stays available for widths that are not
-        add_pack(h, r + ".weight", PK_1x1);        // multiples of 4 (e.g. level 3 of a 1424 x 2128 frame)
+        h->up_w[i - 1] = add_param(h, u + ".weight", {2 * C, C, 2, 2});
+        h->up_b[i - 1] = add_param(h, u + ".bias", {C});
+        h->upcr_w[i - 1] = add_param(h, r + ".weight", {C, 2 * C, 1, 1});
+        h->upcr_b[i - 1] = add_param(h, r + ".bias", {C});
+        add_pack(h, h->up_w[i - 1], PK_CONVT);      // the two-kernel form stays available for widths that are not
+        add_pack(h, h->upcr_w[i - 1], PK_1x1);      // multiples of 4 (e.g. level 3 of a 1424 x 2128 frame)
         h->upcat_offset[i - 1] = h->packed_floats;
         h->packed_floats += align_up(upcat_packed_floats(C), 64);
-        add_stage(h, 4 + i, C, cfg->heads[lvl]);
+        add_stage(h, 4 + i, lvl);
     }
-    add_param(h, "conv_out.weight", {4 * cfg->out_channels, d, 3, 3});
-    add_param(h, "conv_out.bias", {4 * cfg->out_channels});
-    add_pack(h, "conv_out.weight", PK_3x3);
+    h->conv_out_w = add_param(h, "conv_out.weight", {4 * cfg->out_channels, d, 3, 3});
+    h->conv_out_b = add_param(h, "conv_out.bias", {4 * cfg->out_channels});
+    add_pack(h, h->conv_out_w, PK_3x3);
     if (cfg->variant == RF_VARIANT_TRUECOLOR) {   // CameraAwareColorCorrection (BayerTORGBColorMultiLvl.py:139-158)
-        add_param(h, "color_correction.gamma_param", {});
-        add_param(h, "color_correction.color_transform.0.weight", {64, 3, 1, 1});
-        add_param(h, "color_correction.color_transform.0.bias", {64});
-        add_param(h, "color_correction.color_transform.2.weight", {3, 64, 1, 1});
-        add_param(h, "color_correction.color_transform.2.bias", {3});
-        add_param(h, "color_correction.tone_curve.0.weight", {32, 1, 1, 1});
-        add_param(h, "color_correction.tone_curve.0.bias", {32});
-        add_param(h, "color_correction.tone_curve.2.weight", {1, 32, 1, 1});
-        add_param(h, "color_correction.tone_curve.2.bias", {1});
+        h->cc[0] = add_param(h, "color_correction.gamma_param", {});
+        h->cc[1] = add_param(h, "color_correction.color_transform.0.weight", {64, 3, 1, 1});
+        h->cc[2] = add_param(h, "color_correction.color_transform.0.bias", {64});
+        h->cc[3] = add_param(h, "color_correction.color_transform.2.weight", {3, 64, 1, 1});
+        h->cc[4] = add_param(h, "color_correction.color_transform.2.bias", {3});
+        h->cc[5] = add_param(h, "color_correction.tone_curve.0.weight", {32, 1, 1, 1});
+        h->cc[6] = add_param(h, "color_correction.tone_curve.0.bias", {32});
+        h->cc[7] = add_param(h, "color_correction.tone_curve.2.weight", {1, 32, 1, 1});
+        h->cc[8] = add_param(h, "color_correction.tone_curve.2.bias", {1});
     }
-    // flat layout for training: registry order, every tensor on a 16-byte boundary (a LayerNorm's weight and bias stay adjacent)
-    for (const Param& q : h->params) {
-        h->flat_offset.push_back(h->flat_floats);
-        h->flat_floats += align_up(q.numel(), 4);
-    }
+    plan_training(h);
     *out = h;
     return RF_OK;
 }
@@ -547,20 +533,16 @@ int rf_pack_params(rf_handle* h, void* packed_dev, size_t bytes, void* stream) {
         else rc = pack_convT(p.ptr, base + it.offset, (int)p.shape[0], (int)p.shape[1], st);
         if (rc) return rc;
     }
-    for (int i = 1; i <= 3; ++i) {
-        const int C = h->cfg.dim << (3 - i);
-        const std::string u = "up" + std::to_string(i), r = "channel_reduce" + std::to_string(i);
-        RF_TRY(pack_upcat(P(h, u + ".weight"), P(h, u + ".bias"), P(h, r + ".weight"), P(h, r + ".bias"), base + h->upcat_offset[i - 1], C, st));
-    }
+    for (int i = 0; i < 3; ++i)
+        RF_TRY(pack_upcat(h->prm(h->up_w[i]), h->prm(h->up_b[i]), h->prm(h->upcr_w[i]), h->prm(h->upcr_b[i]), base + h->upcat_offset[i],
+                          h->cfg.dim << (2 - i), st));
     for (int i = 1; i <= 7; ++i) {
-        if (!h->tail_offset[i]) continue;
-        const int lvl = i <= 4 ? i - 1 : 7 - i, C = h->cfg.dim << lvl, hc = C * h->cfg.ffn_expansion;
-        const std::string pre = "conv_tran" + std::to_string(i) + ".";
-        float* composed = base + h->tail_offset[i];
-        RF_TRY(pack_tail(P(h, pre + "channel_reduce.weight"), P(h, pre + "channel_reduce.bias"), P(h, pre + "Transformer.ffn.pointwise2.weight"),
-                         P(h, pre + "Transformer.ffn.pointwise2.bias"), composed, C, hc, st));
-        if (h->tail3_offset[i])
-            RF_TRY(launch_tail_fold(P(h, pre + "channel_reduce.weight"), nullptr, composed, base + h->tail3_offset[i], 1, C, hc, st));
+        const StageIx& x = h->stage[i];
+        if (!x.tail_offset) continue;
+        const int C = h->cfg.dim << x.lvl, hc = C * h->cfg.ffn_expansion;
+        float* composed = base + x.tail_offset;
+        RF_TRY(pack_tail(h->prm(x.cr_w), h->prm(x.cr_b), h->prm(x.pw2_w), h->prm(x.pw2_b), composed, C, hc, st));
+        if (x.tail3_offset) RF_TRY(launch_tail_fold(h->prm(x.cr_w), nullptr, composed, base + x.tail3_offset, 1, C, hc, st));
     }
     h->packed = base;
     return RF_OK;
@@ -610,13 +592,13 @@ int rf_forward_stage(rf_handle* h, int stage, const float* in, const float* pack
     }
     hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)workspace;
-    const int lvl = stage <= 4 ? stage - 1 : 7 - stage;
+    const int lvl = h->stage[stage].lvl;
     if (h->cfg.variant == RF_VARIANT_FLCA) {
         RF_TRY(launch_guidance_base(packed, 0, h->cfg.clamp_io, ws + p.gscratch, B, H, W, st));
         RF_TRY(launch_guidance_level(ws + p.gscratch, ws + p.guide[lvl], B, H, W, H >> lvl, W >> lvl, st));
     }
     if (p.ks_floats) RF_TRY(check_hip(hipMemsetAsync(ws + p.ks, 0, conv3x3_ksplit_counter_bytes(), st), "rf_forward_stage: memset"));
-    return run_stage(h, stage, lvl, in, out, ws, p, B, H, W, st, st);
+    return run_stage(h, stage, in, out, ws, p, B, H, W, st, st);
 }
 
 int rf_forward(rf_handle* h, const float* in, float* out, void* workspace, size_t workspace_bytes,
@@ -665,19 +647,16 @@ int rf_forward(rf_handle* h, const float* in, float* out, void* workspace, size_
         for (int l = 0; l < 4; ++l)
             RF_TRY(launch_guidance_level(ws + p.gscratch, ws + p.guide[l], B, H, W, H >> l, W >> l, side));
     } else if (cfg.variant == RF_VARIANT_TRUECOLOR) {
-        const std::string bp = "bayer_processor.";
-        RF_TRY(launch_tc_front(in, mosaic, P(h, bp + "wb_gains"), P(h, bp + "color_matrix"),
-                               PK(h, bp + "chroma_extractor.0.weight"), P(h, bp + "chroma_extractor.0.bias"),
-                               PK(h, bp + "chroma_extractor.2.weight"), P(h, bp + "chroma_extractor.2.bias"),
-                               PK(h, bp + "demosaic_refine.0.weight"), P(h, bp + "demosaic_refine.0.bias"),
-                               PK(h, bp + "demosaic_refine.2.weight"), P(h, bp + "demosaic_refine.2.bias"),
+        const int* bp = h->bp;   // wb_gains, color_matrix, demosaic_refine.0 / .2, chroma_extractor.0 / .2 (weight, bias each)
+        RF_TRY(launch_tc_front(in, mosaic, h->prm(bp[0]), h->prm(bp[1]), h->pk(bp[6]), h->prm(bp[7]), h->pk(bp[8]), h->prm(bp[9]),
+                               h->pk(bp[2]), h->prm(bp[3]), h->pk(bp[4]), h->prm(bp[5]),
                                ws + p.gscratch, B, H, W, levels, st));
         for (int l = 0; l < 4; ++l)
             RF_TRY(launch_tc_guide_level(ws + p.gscratch, ws + p.guide[l], B, H, W, levels, H >> l, W >> l, st));
     }
     // embedding (reads the mosaic through the Bayer pack)
     Conv3x3Args e{};
-    e.x = in; e.x_bstride = (int64_t)4 * H * W; e.wp = PK(h, "embedding.weight"); e.bias = P(h, "embedding.bias");
+    e.x = in; e.x_bstride = (int64_t)4 * H * W; e.wp = h->pk(h->embedding_w); e.bias = h->prm(h->embedding_b);
     e.out = ws + p.tA; e.out_bstride = (int64_t)d * H * W; e.B = B; e.Cin = 4; e.Cout = d; e.h = H; e.w = W;
     e.unshuffle_in = mosaic; e.clamp_in = cfg.clamp_io;
     RF_TRY(launch_conv3x3(e, st));
@@ -686,19 +665,18 @@ int rf_forward(rf_handle* h, const float* in, float* out, void* workspace, size_
     float* skip[3] = {ws + p.skip[0], ws + p.skip[1], ws + p.skip[2]};
     for (int i = 1; i <= 3; ++i) {
         const int lvl = i - 1, C = d << lvl, hh = H >> lvl, ww = W >> lvl;
-        RF_TRY(run_stage(h, i, lvl, ws + p.tA, skip[lvl], ws, p, B, H, W, st, side));
+        RF_TRY(run_stage(h, i, ws + p.tA, skip[lvl], ws, p, B, H, W, st, side));
         Conv3x3Args dn{};
-        dn.x = skip[lvl]; dn.x_bstride = (int64_t)C * hh * ww; dn.wp = PK(h, "down" + std::to_string(i) + ".body.0.weight");
+        dn.x = skip[lvl]; dn.x_bstride = (int64_t)C * hh * ww; dn.wp = h->pk(h->down_w[i - 1]);
         dn.out = ws + p.tA; dn.out_bstride = (int64_t)2 * C * (hh / 2) * (ww / 2);
         dn.B = B; dn.Cin = C; dn.Cout = C / 2; dn.h = hh; dn.w = ww; dn.store = 1;
         if (p.ks_floats) { dn.ks_scratch = ws + p.ks; dn.ks_floats = p.ks_floats; }
         RF_TRY(launch_conv3x3(dn, st));
     }
-    RF_TRY(run_stage(h, 4, 3, ws + p.tA, ws + p.tB, ws, p, B, H, W, st, side));
+    RF_TRY(run_stage(h, 4, ws + p.tA, ws + p.tB, ws, p, B, H, W, st, side));
     // decoder
     for (int i = 1; i <= 3; ++i) {
         const int lvl = 3 - i, C = d << lvl, hh = H >> lvl, ww = W >> lvl, Pn = hh * ww;
-        const std::string u = "up" + std::to_string(i), r = "channel_reduce" + std::to_string(i);
         bool fuse_up = upcat_supported(C, hh / 2, ww / 2, ws + p.tB, skip[lvl], ws + p.tA);
 #ifdef RF_DIAG   // diagnostic build only (build.py --diag): force the two-kernel decoder step
         if (getenv("RF_NO_UPCAT")) fuse_up = false;
@@ -706,34 +684,32 @@ int rf_forward(rf_handle* h, const float* in, float* out, void* workspace, size_
         if (fuse_up) {
             // ConvTranspose2d + cat + 1x1 as one kernel on composed weights: `up` never reaches HBM
             RF_TRY(launch_upcat(ws + p.tB, skip[lvl], ws + p.tA, h->packed + h->upcat_offset[i - 1], B, C, hh / 2, ww / 2, st));
-            RF_TRY(run_stage(h, 4 + i, lvl, ws + p.tA, ws + p.tB, ws, p, B, H, W, st, side));
+            RF_TRY(run_stage(h, 4 + i, ws + p.tA, ws + p.tB, ws, p, B, H, W, st, side));
             continue;
         }
         Conv1x1Args up{};
         up.x1 = ws + p.tB; up.C1 = 2 * C; up.x1_bstride = (int64_t)2 * C * (Pn / 4);
-        up.wp = PK(h, u + ".weight"); up.bias = P(h, u + ".bias");
+        up.wp = h->pk(h->up_w[i - 1]); up.bias = h->prm(h->up_b[i - 1]);
         up.out = ws + p.tU; up.out_bstride = (int64_t)C * Pn; up.Cout = 4 * C; up.B = B; up.P = Pn / 4; up.w = ww / 2; up.mode = 1;
         RF_TRY(launch_conv1x1(up, st));
         Conv1x1Args cr{};
         cr.x1 = ws + p.tU; cr.C1 = C; cr.x1_bstride = (int64_t)C * Pn;
         cr.x2 = skip[lvl]; cr.C2 = C; cr.x2_bstride = (int64_t)C * Pn;
-        cr.wp = PK(h, r + ".weight"); cr.bias = P(h, r + ".bias");
+        cr.wp = h->pk(h->upcr_w[i - 1]); cr.bias = h->prm(h->upcr_b[i - 1]);
         cr.out = ws + p.tA; cr.out_bstride = (int64_t)C * Pn; cr.Cout = C; cr.B = B; cr.P = Pn; cr.w = ww;
         RF_TRY(launch_conv1x1(cr, st));
-        RF_TRY(run_stage(h, 4 + i, lvl, ws + p.tA, ws + p.tB, ws, p, B, H, W, st, side));
+        RF_TRY(run_stage(h, 4 + i, ws + p.tA, ws + p.tB, ws, p, B, H, W, st, side));
     }
     // conv_out + LeakyReLU + PixelShuffle (+ clamp)
     Conv3x3Args o{};
-    o.x = ws + p.tB; o.x_bstride = (int64_t)d * H * W; o.wp = PK(h, "conv_out.weight"); o.bias = P(h, "conv_out.bias");
+    o.x = ws + p.tB; o.x_bstride = (int64_t)d * H * W; o.wp = h->pk(h->conv_out_w); o.bias = h->prm(h->conv_out_b);
     o.out = out; o.out_bstride = (int64_t)cfg.out_channels * 4 * H * W;
     o.B = B; o.Cin = d; o.Cout = 4 * cfg.out_channels; o.h = H; o.w = W; o.act = 1; o.store = 2; o.clamp_out = cfg.clamp_io;
     if (cfg.variant == RF_VARIANT_TRUECOLOR) o.act = 2;      // F.relu before the PixelShuffle (BayerTORGBColorMultiLvl.py:458)
     RF_TRY(launch_conv3x3(o, st));
     if (cfg.variant == RF_VARIANT_TRUECOLOR) {
-        const std::string cc = "color_correction.";
-        const float* prm[9] = {P(h, cc + "gamma_param"), P(h, cc + "color_transform.0.weight"), P(h, cc + "color_transform.0.bias"),
-                               P(h, cc + "color_transform.2.weight"), P(h, cc + "color_transform.2.bias"), P(h, cc + "tone_curve.0.weight"),
-                               P(h, cc + "tone_curve.0.bias"), P(h, cc + "tone_curve.2.weight"), P(h, cc + "tone_curve.2.bias")};
+        const float* prm[9];
+        for (int k = 0; k < 9; ++k) prm[k] = h->prm(h->cc[k]);
         RF_TRY(launch_tc_color_head(out, prm, B, (size_t)4 * H * W, st));
     }
     return RF_OK;

@@ -642,17 +642,6 @@ __global__ void __launch_bounds__(256) split_halves_kernel(const float4* __restr
     }
 }
 
-// w'[c][8 - t] = w[c][t] (depthwise);  w'[ci][co][2-dy][2-dx] = w[co][ci][dy][dx] (dense 3x3)
-__global__ void __launch_bounds__(256) flip_kernel(const float* __restrict__ w, float* __restrict__ out, int Cout, int Cin, int dense) {
-    const size_t total = (size_t)Cout * (dense ? Cin : 1) * 9;
-    for (size_t i = blockIdx.x * 256ull + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int t = (int)(i % 9);
-        if (!dense) { out[i - t + 8 - t] = w[i]; continue; }
-        const int ci = (int)((i / 9) % Cin), co = (int)(i / ((size_t)9 * Cin));
-        out[((size_t)ci * Cout + co) * 9 + 8 - t] = w[i];
-    }
-}
-
 // loss (mode 0: L1 = mean |d|; 1: Charbonnier = mean sqrt(d^2 + eps^2), train.py:16-25) and its gradient w.r.t. pred
 __global__ void __launch_bounds__(256) loss_kernel(const float* __restrict__ pred, const float* __restrict__ gt, float* __restrict__ grad,
                                                    float* __restrict__ partial, size_t n, int mode, float eps, float inv_n) {
@@ -882,11 +871,6 @@ int launch_split_halves(const float* src, float* a, float* b, int B, int C, int 
     ProfScope prof(st, "split_halves_kernel", 0.0, 32.0 * half4 * B);
     split_halves_kernel<<<grid1d(total4), 256, 0, st>>>(reinterpret_cast<const float4*>(src), reinterpret_cast<float4*>(a), reinterpret_cast<float4*>(b), half4, total4);
     return check_launch("split_halves");
-}
-
-int launch_flip3x3(const float* w, float* out, int Cout, int Cin, int dense, hipStream_t st) {
-    flip_kernel<<<grid1d((size_t)Cout * (dense ? Cin : 1) * 9), 256, 0, st>>>(w, out, Cout, Cin, dense);
-    return check_launch("flip3x3");
 }
 
 int loss_nblk() { return 1024; }

@@ -20,16 +20,15 @@
 // Variants 'plain' (conv branch) and 'flca' (rf_train.hip: launch_flca_backward).
 //
 // Schedule-level choices (round 3): every packed / transposed / tap-flipped weight form of the step is written by three batched
-// launches before the forward (pack cache, build_pack_list); bias gradients are row sums inside gram2; the depthwise 3x3 of the
+// launches before the forward (pack cache, laid out once by plan_training); bias gradients are row sums inside gram2; the depthwise 3x3 of the
 // FFN writes its pre-activation and GELU(.) in one pass; the halves of a concatenated-input gradient are read in place through
 // strides; both residual adds of a block ride on the LayerNorm adjoints; inside a stage every backward tensor has its own
 // buffer so that the weight-gradient kernels run on a second stream beside the dX chain (fork before each, join at the end of
 // the stage); finished ranges of the flat gradient buffer are announced to the caller (rf_set_grad_ready) from its end towards
 // its start so that the gradient all-reduce overlaps the rest of the backward.
-#include <cstring>
-#include <map>
-#include <string>
-#include <utility>
+//
+// Every tensor is reached through the handle's index table (rf_handle.h): raw pointers by registry index, packed forms at the
+// offsets plan_training fixed at rf_create, gradients at the parameter's flat offset.
 #include <vector>
 #include "rf_handle.h"
 
@@ -61,8 +60,7 @@ struct TrainPlan {
     size_t flca_scr_floats;
     float *tA, *tB, *tC, *tD, *tE;     // backward temporaries (3 * U0 each)
     float *dskip[3], *dpred, *ga, *gb;
-    float *wt1, *wt2;                  // on-the-fly packed / flipped weights (shapes the pack cache does not hold)
-    float *pack_cache;                 // every packed weight form of the step, written by a few batched launches at its start
+    float *pack_cache;                 // every packed weight form of the step (rf_handle::cache_packs), written at its start
     float *part;                       // reduction partials
     float *part_wg;                    // ... of the kernels on the weight-gradient stream
     size_t part_floats;                // capacity of each of part / part_wg (launch_gram2 checks its slab partials against it)
@@ -73,45 +71,6 @@ struct TrainPlan {
 };
 
 size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
-
-// ---- pack cache ------------------------------------------------------------------------------------------------------
-// The step needs most weights in two packed forms: as they multiply in the forward (PF_N) and transposed -- 3x3: also tap-flipped
-// -- for the dX product of the backward (PF_T); ConvTranspose2d has a third (PF_CTB, its dX GEMM).  They were packed where they
-// were used: ~125 launches of a few microseconds per step.  Now the list is derived from the parameter shapes and filled by
-// launch_pack_batch (3 launches) before the forward; the helpers look a weight up by (pointer, form).
-enum PackForm { PF_N = 0, PF_T = 1, PF_CTB = 2, PF_N3 = 3, PF_T3 = 4, PF_CTB3 = 5 };      // ..3: the same matrix in b3 form (K >= 128: bf16x3 GEMM)
-typedef std::map<std::pair<const float*, int>, const float*> PackMap;
-
-size_t build_pack_list(const rf_handle* h, float* base, std::vector<PackDesc>* list, PackMap* map) {
-    size_t off = 0;
-    auto add = [&](const Param& q, int form, int kind, int rows, int cols, int64_t rs, int64_t cs, int flip) {
-        PackDesc d{q.ptr, base ? base + off : nullptr, kind, rows, cols, rs, cs, flip};
-        if (list) list->push_back(d);
-        if (map) (*map)[std::make_pair(q.ptr, form)] = d.dst;
-        off += align_up(pack_desc_floats(d), 64);
-    };
-    for (const Param& q : h->params) {
-        if (q.ndim != 4 || q.name.find("FLCA.") != std::string::npos) continue;      // the gate convolutions have their own kernels
-        const int n0 = (int)q.shape[0], n1 = (int)q.shape[1], kh = (int)q.shape[2];
-        if (kh == 1) {                                   // 1x1 conv [Cout][K]
-            add(q, PF_N, 0, n0, n1, n1, 1, 0);
-            add(q, PF_T, 0, n1, n0, 1, n1, 0);
-            if (n1 >= 128) add(q, PF_N3, 3, n0, n1, n1, 1, 0);
-            if (n0 >= 128) add(q, PF_T3, 3, n1, n0, 1, n1, 0);
-        } else if (kh == 3 && n1 == 1) {                 // depthwise [C][1][3][3]: dX runs the forward kernel on flipped taps
-            add(q, PF_T, 2, n0, 9, 9, 1, 0);
-        } else if (kh == 3) {                            // 3x3 conv [Cout][Cin][3][3]
-            add(q, PF_N, 1, n0, n1, (int64_t)n1 * 9, 9, 0);
-            add(q, PF_T, 1, n1, n0, 9, (int64_t)n1 * 9, 1);
-        } else if (kh == 2) {                            // ConvTranspose2d [Cin][Cout][2][2]: GEMM row 4 o + 2 i + j, column k (pack_convT)
-            add(q, PF_N, 0, 4 * n1, n0, 1, (int64_t)4 * n1, 0);
-            add(q, PF_CTB, 0, n0, 4 * n1, (int64_t)4 * n1, 1, 0);
-            if (n0 >= 128) add(q, PF_N3, 3, 4 * n1, n0, 1, (int64_t)4 * n1, 0);
-            if (4 * n1 >= 128) add(q, PF_CTB3, 3, n0, 4 * n1, (int64_t)4 * n1, 1, 0);
-        }
-    }
-    return off;
-}
 
 int make_train_plan(const rf_handle* h, float* base, int B, int H, int W, TrainPlan& p) {
     const rf_config& c = h->cfg;
@@ -125,7 +84,7 @@ int make_train_plan(const rf_handle* h, float* base, int B, int H, int W, TrainP
         p.gscratch = b.take(guidance_scratch_floats(B, H, W));
         for (int l = 0; l < 4; ++l) p.guide[l] = b.take((size_t)B * 4 * (H >> l) * (W >> l));
     }
-    size_t part = 0, small = 0, wt = 0, fscr = 0;
+    size_t part = 0, small = 0, fscr = 0;
     auto stage = [&](int i, int lvl) -> int {
         const int C = c.dim << lvl, hh = H >> lvl, ww = W >> lvl;
         const size_t U = (size_t)B * C * hh * ww;
@@ -147,7 +106,6 @@ int make_train_plan(const rf_handle* h, float* base, int B, int H, int W, TrainP
         part = max_sz(part, ln_bwd_partial_floats(B, C, hh * ww));
         part = max_sz(part, dw_wgrad_partial_floats(B, 3 * C > hc ? 3 * C : hc, hh * ww));
         small = max_sz(small, (size_t)B * (3 * (size_t)C * C + packed1x1_floats(2 * C, 2 * C) + 2 * packed1x1_floats(C, C) + 64) + 64);
-        wt = max_sz(wt, max_sz(packed3x3_floats(2 * C, 2 * C), max_sz(packed1x1_floats(4 * C, 4 * C), (size_t)C * C * 9 * 4)));
         return RF_OK;
     };
     for (int i = 1; i <= 4; ++i) {
@@ -166,8 +124,7 @@ int make_train_plan(const rf_handle* h, float* base, int B, int H, int W, TrainP
     const size_t T = max_sz(3, (size_t)hcx) * U0;
     p.tA = b.take(T); p.tB = b.take(T); p.tC = b.take(T); p.tD = b.take(T); p.tE = b.take(64);
     p.ga = b.take(U0); p.gb = b.take(U0);
-    p.wt1 = b.take(wt); p.wt2 = b.take(wt);
-    p.pack_cache = b.take(build_pack_list(h, nullptr, nullptr, nullptr));
+    p.pack_cache = b.take(h->cache_floats);
     p.part_floats = max_sz(part, (size_t)B * 64 * 512);
     p.part = b.take(p.part_floats);
     p.part_wg = b.take(p.part_floats);
@@ -184,8 +141,6 @@ int make_train_plan(const rf_handle* h, float* base, int B, int H, int W, TrainP
     return RF_OK;
 }
 
-const float* P(const rf_handle* h, const std::string& n) { return rf_param_ptr(h, n); }
-
 struct Ctx {
     const rf_handle* h;
     TrainPlan* p;
@@ -196,45 +151,44 @@ struct Ctx {
     // nothing downstream of the stage waits for -- run beside the dX chain; st everywhere else
     hipStream_t wg;
     SideStream* side;
-    const PackMap* packs = nullptr;
     bool forked() const { return wg != st; }
     float* dw_part() const { return forked() ? p->part_wg : p->part; }
-    float* G(const std::string& n) const { return grads + h->flat_offset[rf_param_index(h, n)]; }
-    const float* pk(const float* w, int form) const {      // nullptr: not in the cache (the helper packs on the fly)
-        if (!packs) return nullptr;
-        auto it = packs->find(std::make_pair(w, form));
-        return it == packs->end() ? nullptr : it->second;
+    float* G(int ix) const { return grads + h->flat_offset[ix]; }
+    // weight `ix` in pack-cache form `form`; the b3 forms are optional (nullptr: the f32 kernels), the others an error when missing
+    const float* pk(int ix, int form) const {
+        const size_t off = h->params[ix].cache[form];
+        return off == kNotCached ? nullptr : p->pack_cache + off;
+    }
+    int pk(int ix, int form, const float** out) const {
+        *out = pk(ix, form);
+        if (*out) return RF_OK;
+        static const char* const names[PF_COUNT] = {"PF_N", "PF_T", "PF_CTB", "PF_N3", "PF_T3", "PF_CTB3"};
+        set_error("rf_train_step: the pack cache holds no %s form of '%s'", names[form], h->params[ix].name.c_str());
+        return RF_E_INVALID;
     }
 };
 
-// ---- forward helpers (raw weights, packed on the fly) ---------------------------------------------------------------
-int f_conv1x1(const Ctx& c, const float* x1, int C1, const float* x2, int C2, const float* w, const float* bias, const float* ln_w, const float* ln_b,
-              const float* res, float* out, int Cout, int P_, const float* wp_pre = nullptr, int64_t wp_bstride = 0) {
-    const int K = C1 + C2;
-    const float* wp3 = nullptr;
-    if (!wp_pre) {
-        wp_pre = c.pk(w, PF_N);
-        if (wp_pre) wp3 = c.pk(w, PF_N3);
-    }
-    if (!wp_pre) RF_TRY(pack_1x1(w, c.p->wt1, Cout, K, K, 1, c.st));
+// ---- forward helpers (weights by registry index, packed forms from the pack cache) --------------------------------------
+int f_conv1x1(const Ctx& c, const float* x1, int C1, const float* x2, int C2, int w, const float* bias, const float* ln_w, const float* ln_b,
+              const float* res, float* out, int Cout, int P_) {
     Conv1x1Args a{};
-    a.wp3 = wp3;
+    RF_TRY(c.pk(w, PF_N, &a.wp));
+    a.wp3 = c.pk(w, PF_N3);
     a.x1 = x1; a.C1 = C1; a.x1_bstride = (int64_t)C1 * P_;
     a.x2 = x2; a.C2 = C2; a.x2_bstride = (int64_t)C2 * P_;
-    a.wp = wp_pre ? wp_pre : c.p->wt1; a.wp_bstride = wp_bstride; a.bias = bias; a.ln_w = ln_w; a.ln_b = ln_b; a.ln_eps = 1e-5f;
+    a.bias = bias; a.ln_w = ln_w; a.ln_b = ln_b; a.ln_eps = 1e-5f;
     a.res = res; a.res_bstride = (int64_t)Cout * P_;
     a.out = out; a.out_bstride = (int64_t)Cout * P_; a.Cout = Cout; a.B = c.B; a.P = P_; a.w = P_;
     return launch_conv1x1(a, c.st);
 }
 
-int f_conv3x3(const Ctx& c, const float* x, int Cin, const float* w, const float* bias, float* out, int Cout, int hh, int ww, int act, int store,
-              int unshuffle_in = 0, const float* wp_pre = nullptr) {
-    if (!wp_pre && w) wp_pre = c.pk(w, PF_N);
-    if (!wp_pre) RF_TRY(pack_3x3(w, c.p->wt1, Cout, Cin, c.st));
+// form PF_N: the forward conv; PF_T: its dX (b_conv3x3_dx)
+int f_conv3x3(const Ctx& c, const float* x, int Cin, int w, const float* bias, float* out, int Cout, int hh, int ww, int act, int store,
+              int form = PF_N) {
     Conv3x3Args a{};
-    a.x = x; a.x_bstride = (int64_t)Cin * hh * ww; a.wp = wp_pre ? wp_pre : c.p->wt1; a.bias = bias; a.out = out;
+    RF_TRY(c.pk(w, form, &a.wp));
+    a.x = x; a.x_bstride = (int64_t)Cin * hh * ww; a.bias = bias; a.out = out;
     a.out_bstride = (int64_t)Cout * hh * ww; a.B = c.B; a.Cin = Cin; a.Cout = Cout; a.h = hh; a.w = ww; a.act = act; a.store = store;
-    a.unshuffle_in = unshuffle_in;
     return launch_conv3x3(a, c.st);
 }
 
@@ -248,15 +202,11 @@ int f_dw(const Ctx& c, const float* x, const float* w, const float* bias, float*
 // ---- backward helpers ------------------------------------------------------------------------------------------------
 // dX of a 1x1 conv with raw weight [Cout][K]: conv1x1 with W^T (out: K channels)
 // (dy_bstride: floats between the images of dy when it is a channel slice of a wider tensor; 0 = contiguous)
-int b_conv1x1_dx(const Ctx& c, const float* dy, int Cout, const float* w, int K, float* dx, int P_, const float* res = nullptr, int64_t dy_bstride = 0) {
-    const float* wt = c.pk(w, PF_T);
-    if (!wt) {
-        RF_TRY(pack_1x1(w, c.p->wt1, K, Cout, 1, K, c.st));             // rows = k, cols = co : element W[co][k] at co * K + k
-        wt = c.p->wt1;
-    }
+int b_conv1x1_dx(const Ctx& c, const float* dy, int Cout, int w, int K, float* dx, int P_, const float* res = nullptr, int64_t dy_bstride = 0) {
     Conv1x1Args a{};
-    a.x1 = dy; a.C1 = Cout; a.x1_bstride = dy_bstride ? dy_bstride : (int64_t)Cout * P_; a.wp = wt;
-    if (wt != c.p->wt1) a.wp3 = c.pk(w, PF_T3);
+    RF_TRY(c.pk(w, PF_T, &a.wp));
+    a.wp3 = c.pk(w, PF_T3);
+    a.x1 = dy; a.C1 = Cout; a.x1_bstride = dy_bstride ? dy_bstride : (int64_t)Cout * P_;
     a.res = res; a.res_bstride = (int64_t)K * P_;
     a.out = dx; a.out_bstride = (int64_t)K * P_; a.Cout = K; a.B = c.B; a.P = P_; a.w = P_;
     return launch_conv1x1(a, c.st);
@@ -279,14 +229,8 @@ int b_conv1x1_dw(const Ctx& c, const float* dy, int Cout, const float* x, int Cx
                         1, 0, 0, 0, 0, 1, ws, col0 == 0 ? db : nullptr, x2, (int64_t)Cx2 * hh * ww, Cx2);
 }
 
-int b_conv3x3_dx(const Ctx& c, const float* dy, int Cout, const float* w, int Cin, float* dx, int hh, int ww) {
-    const float* wt = c.pk(w, PF_T);
-    if (!wt) {
-        RF_TRY(launch_flip3x3(w, c.p->wt2, Cout, Cin, 1, c.st));        // [Cin][Cout][flipped taps]
-        RF_TRY(pack_3x3(c.p->wt2, c.p->wt1, Cin, Cout, c.st));
-        wt = c.p->wt1;
-    }
-    return f_conv3x3(c, dy, Cout, nullptr, nullptr, dx, Cin, hh, ww, 0, 0, 0, wt);
+int b_conv3x3_dx(const Ctx& c, const float* dy, int Cout, int w, int Cin, float* dx, int hh, int ww) {
+    return f_conv3x3(c, dy, Cout, w, nullptr, dx, Cin, hh, ww, 0, 0, PF_T);
 }
 
 int b_conv3x3_dw(const Ctx& c, const float* dy, int Cout, const float* x, int Cin, float* dW, float* db, int hh, int ww) {
@@ -294,14 +238,12 @@ int b_conv3x3_dw(const Ctx& c, const float* dy, int Cout, const float* x, int Ci
     return launch_gram2(dy, (int64_t)Cout * hh * ww, Cout, x, (int64_t)Cin * hh * ww, Cin, dW, Cin, c.dw_part(), c.p->part_floats, c.B, hh, ww, 9, 0, 0, 0, 0, 1, c.wg, db);
 }
 
-int b_dw(const Ctx& c, const float* dy, const float* x, const float* w, float* dx, float* dW, float* db, int C, int hh, int ww) {
+// depthwise 3x3 with weight `w`: dW, db on the weight-gradient stream, dX = the forward kernel on the flipped taps
+int b_dw(const Ctx& c, const float* dy, const float* x, int w, float* dx, float* dW, float* db, int C, int hh, int ww) {
     RF_TRY(c.side->fork(c.st, c.wg));
     RF_TRY(launch_dw_wgrad(x, dy, dW, db, c.dw_part(), c.B, C, hh, ww, 1, c.wg));
-    const float* wf = c.pk(w, PF_T);
-    if (!wf) {
-        RF_TRY(launch_flip3x3(w, c.p->wt2, C, 1, 0, c.st));
-        wf = c.p->wt2;
-    }
+    const float* wf;
+    RF_TRY(c.pk(w, PF_T, &wf));
     return f_dw(c, dy, wf, nullptr, dx, C, hh, ww);
 }
 
@@ -445,65 +387,60 @@ int attn_small(const Ctx& c, const Stash& s, const float* temperature, int C, in
 // ---- the step ---------------------------------------------------------------------------------------------------------
 namespace {
 
-struct StageNames { std::string pre, t; };
-
-int stage_forward(const Ctx& c, int i, int lvl, const float* in, int H, int W) {
+int stage_forward(const Ctx& c, int i, const float* in, int H, int W) {
     const rf_handle* h = c.h;
     const rf_config& cfg = h->cfg;
-    const int C = cfg.dim << lvl, hh = H >> lvl, ww = W >> lvl, Pn = hh * ww, heads = cfg.heads[lvl], hc = C * cfg.ffn_expansion;
-    const std::string pre = "conv_tran" + std::to_string(i) + ".", t = pre + "Transformer.";
+    const StageIx& x = h->stage[i];
+    const int lvl = x.lvl, C = cfg.dim << lvl, hh = H >> lvl, ww = W >> lvl, Pn = hh * ww, heads = cfg.heads[lvl], hc = C * cfg.ffn_expansion;
     Stash& s = c.p->st[i];
     s.in = in;
-    RF_TRY(f_conv1x1(c, in, C, nullptr, 0, P(h, t + "attn.qkv.weight"), P(h, t + "attn.qkv.bias"), P(h, t + "norm1.body.weight"),
-                     P(h, t + "norm1.body.bias"), nullptr, s.qkvp, 3 * C, Pn));
-    RF_TRY(f_dw(c, s.qkvp, P(h, t + "attn.qkv_dwconv.weight"), P(h, t + "attn.qkv_dwconv.bias"), s.qkv, 3 * C, hh, ww));
+    RF_TRY(f_conv1x1(c, in, C, nullptr, 0, x.qkv_w, h->prm(x.qkv_b), h->prm(x.ln1_w), h->prm(x.ln1_b), nullptr, s.qkvp, 3 * C, Pn));
+    RF_TRY(f_dw(c, s.qkvp, h->prm(x.qkv_dw_w), h->prm(x.qkv_dw_b), s.qkv, 3 * C, hh, ww));
     GramArgs g{};
     g.q = s.qkv; g.k = s.qkv + (size_t)C * Pn; g.bstride = (int64_t)3 * C * Pn; g.B = c.B; g.C = C; g.heads = heads; g.P = Pn;
     g.partial = s.partial; g.nslab = s.nslab; g.slab = s.slab;
     RF_TRY(launch_gram(g, c.st));
     // attention map -> per-image folded projection (forward only), x1 = in + W_out A v + b
     float* wfold = c.p->small;
-    RF_TRY(launch_attn_fold(s.partial, s.nslab, P(h, t + "attn.temperature"), P(h, t + "attn.project_out.weight"), wfold, nullptr, c.B, C, heads, c.st));
+    RF_TRY(launch_attn_fold(s.partial, s.nslab, h->prm(x.temperature), h->prm(x.proj_w), wfold, nullptr, c.B, C, heads, c.st));
     {
         Conv1x1Args a{};
         a.x1 = s.qkv + (size_t)2 * C * Pn; a.C1 = C; a.x1_bstride = (int64_t)3 * C * Pn; a.wp = wfold; a.wp_bstride = (int64_t)packed1x1_floats(C, C);
-        a.bias = P(h, t + "attn.project_out.bias"); a.res = in; a.res_bstride = (int64_t)C * Pn;
+        a.bias = h->prm(x.proj_b); a.res = in; a.res_bstride = (int64_t)C * Pn;
         a.out = s.x1; a.out_bstride = (int64_t)C * Pn; a.Cout = C; a.B = c.B; a.P = Pn; a.w = ww;
         RF_TRY(launch_conv1x1(a, c.st));
     }
-    RF_TRY(f_conv1x1(c, s.x1, C, nullptr, 0, P(h, t + "ffn.pointwise1.weight"), P(h, t + "ffn.pointwise1.bias"), P(h, t + "norm2.body.weight"),
-                     P(h, t + "norm2.body.bias"), nullptr, s.f1, hc, Pn));
-    RF_TRY(f_dw(c, s.f1, P(h, t + "ffn.depthwise.weight"), P(h, t + "ffn.depthwise.bias"), s.f2, hc, hh, ww, s.g));   // f2 and g = gelu(f2)
-    RF_TRY(f_conv1x1(c, s.g, hc, nullptr, 0, P(h, t + "ffn.pointwise2.weight"), P(h, t + "ffn.pointwise2.bias"), nullptr, nullptr, s.x1, s.trans, C, Pn));
+    RF_TRY(f_conv1x1(c, s.x1, C, nullptr, 0, x.pw1_w, h->prm(x.pw1_b), h->prm(x.ln2_w), h->prm(x.ln2_b), nullptr, s.f1, hc, Pn));
+    RF_TRY(f_dw(c, s.f1, h->prm(x.dw_w), h->prm(x.dw_b), s.f2, hc, hh, ww, s.g));   // f2 and g = gelu(f2)
+    RF_TRY(f_conv1x1(c, s.g, hc, nullptr, 0, x.pw2_w, h->prm(x.pw2_b), nullptr, nullptr, s.x1, s.trans, C, Pn));
     if (cfg.variant == RF_VARIANT_FLCA) {
-        const std::string f = pre + "FLCA.";
+        const int* b = x.flca;   // registry order (StageIx)
         FlcaSpatialArgs sa{};
         sa.feat = in; sa.xs = s.xraw; sa.guide = c.p->guide[lvl];
-        sa.w_low = P(h, f + "low_attn.0.weight"); sa.w_high = P(h, f + "high_attn.0.weight"); sa.w_chr = P(h, f + "chroma_attn.0.weight");
-        sa.alpha = P(h, f + "alpha"); sa.beta = P(h, f + "beta"); sa.gamma = P(h, f + "gamma");
+        sa.w_low = h->prm(b[3]); sa.w_high = h->prm(b[4]); sa.w_chr = h->prm(b[5]);
+        sa.alpha = h->prm(b[0]); sa.beta = h->prm(b[1]); sa.gamma = h->prm(b[2]);
         sa.partial = s.pool; sa.B = c.B; sa.C = C; sa.h = hh; sa.w = ww; sa.nblk = flca_nblk(hh, ww);
         RF_TRY(launch_flca_spatial(sa, c.st));
         const int hid = C / 8 > 8 ? C / 8 : 8;
-        RF_TRY(launch_flca_se(s.pool, sa.nblk, Pn, P(h, f + "se.1.weight"), P(h, f + "se.1.bias"), P(h, f + "se.3.weight"), P(h, f + "se.3.bias"),
-                              hid, s.ch, c.B, C, c.st));
+        RF_TRY(launch_flca_se(s.pool, sa.nblk, Pn, h->prm(b[6]), h->prm(b[7]), h->prm(b[8]), h->prm(b[9]), hid, s.ch, c.B, C, c.st));
         RF_TRY(launch_scale_channels_to(s.xraw, s.xs, s.ch, c.B, C, Pn, c.st));                         // xs = branch output z
     } else {
-        RF_TRY(f_conv3x3(c, in, C, P(h, pre + "conv.weight"), P(h, pre + "conv.bias"), s.xs, C, hh, ww, cfg.branch_lrelu ? 1 : 0, 0));
+        RF_TRY(f_conv3x3(c, in, C, x.conv_w, h->prm(x.conv_b), s.xs, C, hh, ww, cfg.branch_lrelu ? 1 : 0, 0));
     }
-    RF_TRY(f_conv1x1(c, s.xs, C, s.trans, C, P(h, pre + "channel_reduce.weight"), P(h, pre + "channel_reduce.bias"), nullptr, nullptr, nullptr, s.cr, C, Pn));
-    RF_TRY(f_conv3x3(c, s.cr, C, P(h, pre + "Conv_out.weight"), P(h, pre + "Conv_out.bias"), s.out, C, hh, ww, 1, 0));
+    RF_TRY(f_conv1x1(c, s.xs, C, s.trans, C, x.cr_w, h->prm(x.cr_b), nullptr, nullptr, nullptr, s.cr, C, Pn));
+    RF_TRY(f_conv3x3(c, s.cr, C, x.out_w, h->prm(x.out_b), s.out, C, hh, ww, 1, 0));
     return RF_OK;
 }
 
 // dout: gradient w.r.t. the stage output (consumed); din: receives the gradient w.r.t. the stage input; wg: the stage's
 // weight-gradient stream
-int stage_backward(const Ctx& outer, hipStream_t wg, int i, int lvl, float* dout, float* din, int H, int W) {
+int stage_backward(const Ctx& outer, hipStream_t wg, int i, float* dout, float* din, int H, int W) {
     Ctx c = outer;
     c.wg = wg;
     const rf_handle* h = c.h;
     const rf_config& cfg = h->cfg;
-    const int C = cfg.dim << lvl, hh = H >> lvl, ww = W >> lvl, Pn = hh * ww, heads = cfg.heads[lvl], hc = C * cfg.ffn_expansion;
-    const std::string pre = "conv_tran" + std::to_string(i) + ".", t = pre + "Transformer.";
+    const StageIx& x = h->stage[i];
+    const int lvl = x.lvl, C = cfg.dim << lvl, hh = H >> lvl, ww = W >> lvl, Pn = hh * ww, heads = cfg.heads[lvl], hc = C * cfg.ffn_expansion;
     const Stash& s = c.p->st[i];
     const size_t U = (size_t)c.B * C * Pn;
     // One buffer per tensor: the weight-gradient kernels read them from their own stream while the dX chain moves on, so nothing
@@ -513,11 +450,11 @@ int stage_backward(const Ctx& outer, hipStream_t wg, int i, int lvl, float* dout
           *d_o = sb[9], *d_qkv = sb[10], *d_qkvp = sb[11], *ln1 = sb[12], *d_ln1 = sb[13], *d_xs = sb[14], *d_tr = sb[15];
     // Conv_out + LeakyReLU
     RF_TRY(launch_ewise(dout, s.out, d_pre, U, 2, 0.2f, c.st));                                      // d(pre-activation)
-    RF_TRY(b_conv3x3_dw(c, d_pre, C, s.cr, C, c.G(pre + "Conv_out.weight"), c.G(pre + "Conv_out.bias"), hh, ww));
-    RF_TRY(b_conv3x3_dx(c, d_pre, C, P(h, pre + "Conv_out.weight"), C, d_cr, hh, ww));
+    RF_TRY(b_conv3x3_dw(c, d_pre, C, s.cr, C, c.G(x.out_w), c.G(x.out_b), hh, ww));
+    RF_TRY(b_conv3x3_dx(c, d_pre, C, x.out_w, C, d_cr, hh, ww));
     // channel_reduce over cat[xs, trans]
-    RF_TRY(b_conv1x1_dw(c, d_cr, C, s.xs, C, c.G(pre + "channel_reduce.weight"), 2 * C, 0, c.G(pre + "channel_reduce.bias"), hh, ww, 0, s.trans, C));
-    RF_TRY(b_conv1x1_dx(c, d_cr, C, P(h, pre + "channel_reduce.weight"), 2 * C, d_cat, Pn));           // d_cat = [dxs ; dtrans] per image
+    RF_TRY(b_conv1x1_dw(c, d_cr, C, s.xs, C, c.G(x.cr_w), 2 * C, 0, c.G(x.cr_b), hh, ww, 0, s.trans, C));
+    RF_TRY(b_conv1x1_dx(c, d_cr, C, x.cr_w, 2 * C, d_cat, Pn));           // d_cat = [dxs ; dtrans] per image
     // dxs and dtrans are read in place as channel slices of d_cat (image stride 2C Pn) by the kernels that take a stride; only the
     // plain variant's element-wise LeakyReLU adjoint (and a LayerNorm shape without the fused kernel) needs contiguous halves
     const float* dxs = d_cat;
@@ -528,35 +465,32 @@ int stage_backward(const Ctx& outer, hipStream_t wg, int i, int lvl, float* dout
         dxs = d_xs; dtr = d_tr; half_bs = (int64_t)C * Pn;
     }
     if (cfg.variant == RF_VARIANT_FLCA) {
-        const std::string f = pre + "FLCA.";
-        const char* names[10] = {"alpha", "beta", "gamma", "low_attn.0.weight", "high_attn.0.weight", "chroma_attn.0.weight",
-                                 "se.1.weight", "se.1.bias", "se.3.weight", "se.3.bias"};
         const float* prm[10];
         float* grd[10];
-        for (int k = 0; k < 10; ++k) { prm[k] = P(h, f + names[k]); grd[k] = c.G(f + names[k]); }
+        for (int k = 0; k < 10; ++k) { prm[k] = h->prm(x.flca[k]); grd[k] = c.G(x.flca[k]); }
         RF_TRY(launch_flca_backward(s.in, c.p->guide[lvl], s.xraw, dxs, half_bs, s.ch, s.pool, flca_nblk(hh, ww), prm, grd, din, 0,
                                     c.p->flca_scr, c.p->flca_scr_floats, c.B, C, hh, ww, c.st));                             // din = branch part
     } else {
         // conv branch
         if (cfg.branch_lrelu) RF_TRY(launch_ewise(d_xs, s.xs, d_xs, U, 2, 0.2f, c.st));
-        RF_TRY(b_conv3x3_dw(c, d_xs, C, s.in, C, c.G(pre + "conv.weight"), c.G(pre + "conv.bias"), hh, ww));
-        RF_TRY(b_conv3x3_dx(c, d_xs, C, P(h, pre + "conv.weight"), C, din, hh, ww));                  // din = branch part
+        RF_TRY(b_conv3x3_dw(c, d_xs, C, s.in, C, c.G(x.conv_w), c.G(x.conv_b), hh, ww));
+        RF_TRY(b_conv3x3_dx(c, d_xs, C, x.conv_w, C, din, hh, ww));                  // din = branch part
     }
     // FFN:  trans = x1 + pw2(gelu(dw(pw1(LN2(x1)))))          dtr = dtrans (also the residual part of dx1)
-    RF_TRY(b_conv1x1_dw(c, dtr, C, s.g, hc, c.G(t + "ffn.pointwise2.weight"), hc, 0, c.G(t + "ffn.pointwise2.bias"), hh, ww, half_bs));
-    RF_TRY(b_conv1x1_dx(c, dtr, C, P(h, t + "ffn.pointwise2.weight"), hc, d_f2, Pn, nullptr, half_bs));   // dg ...
+    RF_TRY(b_conv1x1_dw(c, dtr, C, s.g, hc, c.G(x.pw2_w), hc, 0, c.G(x.pw2_b), hh, ww, half_bs));
+    RF_TRY(b_conv1x1_dx(c, dtr, C, x.pw2_w, hc, d_f2, Pn, nullptr, half_bs));   // dg ...
     RF_TRY(launch_ewise(d_f2, s.f2, d_f2, (size_t)c.B * hc * Pn, 1, 0.f, c.st));                      // ... -> df2, in place
-    RF_TRY(b_dw(c, d_f2, s.f1, P(h, t + "ffn.depthwise.weight"), d_f1, c.G(t + "ffn.depthwise.weight"), c.G(t + "ffn.depthwise.bias"), hc, hh, ww));
-    RF_TRY(launch_layernorm2d(s.x1, ln2, P(h, t + "norm2.body.weight"), P(h, t + "norm2.body.bias"), 1e-5f, c.B, C, Pn, c.st));   // LN2(x1) again
-    RF_TRY(b_conv1x1_dw(c, d_f1, hc, ln2, C, c.G(t + "ffn.pointwise1.weight"), C, 0, c.G(t + "ffn.pointwise1.bias"), hh, ww));
-    RF_TRY(b_conv1x1_dx(c, d_f1, hc, P(h, t + "ffn.pointwise1.weight"), C, d_ln2, Pn));               // d LN2 out
+    RF_TRY(b_dw(c, d_f2, s.f1, x.dw_w, d_f1, c.G(x.dw_w), c.G(x.dw_b), hc, hh, ww));
+    RF_TRY(launch_layernorm2d(s.x1, ln2, h->prm(x.ln2_w), h->prm(x.ln2_b), 1e-5f, c.B, C, Pn, c.st));   // LN2(x1) again
+    RF_TRY(b_conv1x1_dw(c, d_f1, hc, ln2, C, c.G(x.pw1_w), C, 0, c.G(x.pw1_b), hh, ww));
+    RF_TRY(b_conv1x1_dx(c, d_f1, hc, x.pw1_w, C, d_ln2, Pn));               // d LN2 out
     // d_x1 = dtrans + (LayerNorm adjoint), dtrans read in place
-    RF_TRY(launch_ln_bwd(s.x1, d_ln2, P(h, t + "norm2.body.weight"), d_x1, c.G(t + "norm2.body.weight"), c.p->part, c.B, C, Pn, 1e-5f, 0, 1, c.st, dtr, half_bs));
+    RF_TRY(launch_ln_bwd(s.x1, d_ln2, h->prm(x.ln2_w), d_x1, c.G(x.ln2_w), c.p->part, c.B, C, Pn, 1e-5f, 0, 1, c.st, dtr, half_bs));
     // attention:  x1 = in + W_out (A v) + b          (the residual din += dx1 rides on the last kernel of the stage)
     const size_t CC = (size_t)C * C;
     const size_t per = 3 * CC + packed1x1_floats(2 * C, 2 * C) + 2 * packed1x1_floats(C, C);
     RF_TRY(check_hip(hipMemsetAsync(c.p->small, 0, (c.B * (per + 64)) * sizeof(float), c.st), "memset"));
-    RF_TRY(attn_small(c, s, P(h, t + "attn.temperature"), C, heads, 1, nullptr));                     // packed A, A^T
+    RF_TRY(attn_small(c, s, h->prm(x.temperature), C, heads, 1, nullptr));                     // packed A, A^T
     float* m2 = c.p->small + 3 * CC;
     float* at = m2 + packed1x1_floats(2 * C, 2 * C);
     float* ap = at + packed1x1_floats(C, C);
@@ -567,11 +501,11 @@ int stage_backward(const Ctx& outer, hipStream_t wg, int i, int lvl, float* dout
         a.out = o; a.out_bstride = (int64_t)C * Pn; a.Cout = C; a.B = c.B; a.P = Pn; a.w = ww;
         RF_TRY(launch_conv1x1(a, c.st));
     }
-    RF_TRY(b_conv1x1_dw(c, d_x1, C, o, C, c.G(t + "attn.project_out.weight"), C, 0, c.G(t + "attn.project_out.bias"), hh, ww));
-    RF_TRY(b_conv1x1_dx(c, d_x1, C, P(h, t + "attn.project_out.weight"), C, d_o, Pn));
+    RF_TRY(b_conv1x1_dw(c, d_x1, C, o, C, c.G(x.proj_w), C, 0, c.G(x.proj_b), hh, ww));
+    RF_TRY(b_conv1x1_dx(c, d_x1, C, x.proj_w, C, d_o, Pn));
     // dA per image: on the dX chain (the softmax adjoint waits for it)
     RF_TRY(launch_gram2(d_o, (int64_t)C * Pn, C, v, (int64_t)3 * C * Pn, C, c.p->small, C, c.p->part, c.p->part_floats, c.B, hh, ww, 1, 0, 0, 1, per, 0, c.st));
-    RF_TRY(attn_small(c, s, P(h, t + "attn.temperature"), C, heads, 0, c.G(t + "attn.temperature")));
+    RF_TRY(attn_small(c, s, h->prm(x.temperature), C, heads, 0, c.G(x.temperature)));
     {   // d(qkv): [dq ; dk] = M2 [q ; k],  dv = blockdiag(A^T) do
         Conv1x1Args a{};
         a.x1 = s.qkv; a.C1 = 2 * C; a.x1_bstride = (int64_t)3 * C * Pn; a.wp = m2; a.wp_bstride = (int64_t)per;
@@ -582,39 +516,66 @@ int stage_backward(const Ctx& outer, hipStream_t wg, int i, int lvl, float* dout
         d.out = d_qkv + (size_t)2 * C * Pn; d.out_bstride = (int64_t)3 * C * Pn; d.Cout = C; d.B = c.B; d.P = Pn; d.w = ww;
         RF_TRY(launch_conv1x1(d, c.st));
     }
-    RF_TRY(b_dw(c, d_qkv, s.qkvp, P(h, t + "attn.qkv_dwconv.weight"), d_qkvp, c.G(t + "attn.qkv_dwconv.weight"), c.G(t + "attn.qkv_dwconv.bias"), 3 * C, hh, ww));
-    RF_TRY(launch_layernorm2d(s.in, ln1, P(h, t + "norm1.body.weight"), P(h, t + "norm1.body.bias"), 1e-5f, c.B, C, Pn, c.st));   // LN1(in) again
-    RF_TRY(b_conv1x1_dw(c, d_qkvp, 3 * C, ln1, C, c.G(t + "attn.qkv.weight"), C, 0, c.G(t + "attn.qkv.bias"), hh, ww));
-    RF_TRY(b_conv1x1_dx(c, d_qkvp, 3 * C, P(h, t + "attn.qkv.weight"), C, d_ln1, Pn));                // d LN1 out
+    RF_TRY(b_dw(c, d_qkv, s.qkvp, x.qkv_dw_w, d_qkvp, c.G(x.qkv_dw_w), c.G(x.qkv_dw_b), 3 * C, hh, ww));
+    RF_TRY(launch_layernorm2d(s.in, ln1, h->prm(x.ln1_w), h->prm(x.ln1_b), 1e-5f, c.B, C, Pn, c.st));   // LN1(in) again
+    RF_TRY(b_conv1x1_dw(c, d_qkvp, 3 * C, ln1, C, c.G(x.qkv_w), C, 0, c.G(x.qkv_b), hh, ww));
+    RF_TRY(b_conv1x1_dx(c, d_qkvp, 3 * C, x.qkv_w, C, d_ln1, Pn));                // d LN1 out
     // din (branch part) += dx1 (residual of x1 = in + attention) + (LayerNorm adjoint)
-    RF_TRY(launch_ln_bwd(s.in, d_ln1, P(h, t + "norm1.body.weight"), din, c.G(t + "norm1.body.weight"), c.p->part, c.B, C, Pn, 1e-5f, 1, 1, c.st, d_x1, (int64_t)C * Pn));
+    RF_TRY(launch_ln_bwd(s.in, d_ln1, h->prm(x.ln1_w), din, c.G(x.ln1_w), c.p->part, c.B, C, Pn, 1e-5f, 1, 1, c.st, d_x1, (int64_t)C * Pn));
     return c.side->join(c.st, c.wg);
 }
 
 }  // namespace
 
-// Modules in the order their gradients become final = reverse registry order (the registry is in forward order).
-std::vector<std::string> grad_order(const rf_handle* h) {
-    (void)h;
-    return {"conv_out.", "conv_tran7.", "up3.", "conv_tran6.", "up2.", "conv_tran5.", "up1.", "conv_tran4.", "conv_tran3.", "conv_tran2.", "conv_tran1.", "embedding."};
-}
-// first flat float of the module with this prefix ("up<i>." is followed by "channel_reduce<i>." in the registry, "conv_tran<i>." by
-// "down<i>.": a range runs from its module's first float to the previous watermark, so those ride along)
-size_t module_start(const rf_handle* h, const std::string& prefix) {
-    size_t best = h->flat_floats;
-    for (size_t i = 0; i < h->params.size(); ++i)
-        if (h->params[i].name.compare(0, prefix.size(), prefix) == 0 && h->flat_offset[i] < best) best = h->flat_offset[i];
-    return best;
-}
-struct GradNotifier {
-    const rf_handle* h; hipStream_t st; size_t watermark;
-    void done(const std::string& prefix) {
-        const size_t lo = module_start(h, prefix);
-        if (lo >= watermark) return;
-        if (h->grad_ready) h->grad_ready(h->grad_ready_user, lo, watermark - lo, (void*)st);
-        watermark = lo;
+// ---- training layout, fixed by the registry (rf_create) -----------------------------------------------------------------
+void plan_training(rf_handle* h) {
+    // flat buffers: registry order, every tensor on a 16-byte boundary (a LayerNorm's weight and bias stay adjacent)
+    for (const Param& q : h->params) {
+        h->flat_offset.push_back(h->flat_floats);
+        h->flat_floats += align_up(q.numel(), 4);
     }
-};
+    // Gradient ranges in the order they become final = reverse registry order of the modules (the registry is in forward
+    // order): conv_out, conv_tran7, up3, conv_tran6, up2, conv_tran5, up1, conv_tran4 .. conv_tran1, embedding.  A range runs from
+    // its module's first float to the previous one's, so channel_reduce<i> rides with up<i>, down<i> with conv_tran<i>, and
+    // TrueColor's color_correction with conv_out.
+    const int first[12] = {h->conv_out_w, h->stage[7].first, h->up_w[2], h->stage[6].first, h->up_w[1], h->stage[5].first, h->up_w[0],
+                           h->stage[4].first, h->stage[3].first, h->stage[2].first, h->stage[1].first, h->embedding_w};
+    size_t watermark = h->flat_floats;
+    for (int ix : first) {
+        h->grad_ranges.push_back({h->flat_offset[ix], watermark - h->flat_offset[ix]});
+        watermark = h->flat_offset[ix];
+    }
+    // Pack cache: the forms of every weight the step multiplies by a GEMM / conv kernel, in registry order (the gate
+    // convolutions of FLCA have their own kernels).  The step writes them with launch_pack_batch before its forward.
+    for (size_t ix = 0; ix < h->params.size(); ++ix) {
+        Param& q = h->params[ix];
+        for (size_t& off : q.cache) off = kNotCached;
+        if (q.ndim != 4 || q.name.find("FLCA.") != std::string::npos) continue;
+        auto add = [&](int form, int kind, int rows, int cols, int64_t rs, int64_t cs, int flip) {
+            const PackDesc d{nullptr, nullptr, kind, rows, cols, rs, cs, flip};
+            q.cache[form] = h->cache_floats;
+            h->cache_packs.push_back({(int)ix, h->cache_floats, d});
+            h->cache_floats += align_up(pack_desc_floats(d), 64);
+        };
+        const int n0 = (int)q.shape[0], n1 = (int)q.shape[1], kh = (int)q.shape[2];
+        if (kh == 1) {                                   // 1x1 conv [Cout][K]
+            add(PF_N, 0, n0, n1, n1, 1, 0);
+            add(PF_T, 0, n1, n0, 1, n1, 0);
+            if (n1 >= 128) add(PF_N3, 3, n0, n1, n1, 1, 0);
+            if (n0 >= 128) add(PF_T3, 3, n1, n0, 1, n1, 0);
+        } else if (kh == 3 && n1 == 1) {                 // depthwise [C][1][3][3]: dX runs the forward kernel on flipped taps
+            add(PF_T, 2, n0, 9, 9, 1, 0);
+        } else if (kh == 3) {                            // 3x3 conv [Cout][Cin][3][3]
+            add(PF_N, 1, n0, n1, (int64_t)n1 * 9, 9, 0);
+            add(PF_T, 1, n1, n0, 9, (int64_t)n1 * 9, 1);
+        } else if (kh == 2) {                            // ConvTranspose2d [Cin][Cout][2][2]: GEMM row 4 o + 2 i + j, column k (pack_convT)
+            add(PF_N, 0, 4 * n1, n0, 1, (int64_t)4 * n1, 0);
+            add(PF_CTB, 0, n0, 4 * n1, (int64_t)4 * n1, 1, 0);
+            if (n0 >= 128) add(PF_N3, 3, 4 * n1, n0, 1, (int64_t)4 * n1, 0);
+            if (4 * n1 >= 128) add(PF_CTB3, 3, n0, 4 * n1, (int64_t)4 * n1, 1, 0);
+        }
+    }
+}
 
 extern "C" {
 
@@ -626,23 +587,17 @@ int rf_set_grad_ready(rf_handle* h, rf_grad_ready_fn ready, void* user) {
 
 int rf_grad_range_count(const rf_handle* h, int* count) {
     RF_CHECK_ARG(h && count, "rf_grad_range_count: null argument");
-    size_t wm = h->flat_floats; int n = 0;
-    for (const std::string& m : grad_order(h)) { const size_t lo = module_start(h, m); if (lo < wm) { ++n; wm = lo; } }
-    *count = n;
+    *count = (int)h->grad_ranges.size();
     return RF_OK;
 }
 
 int rf_grad_range(const rf_handle* h, int index, size_t* offset, size_t* count) {
     RF_CHECK_ARG(h && offset && count && index >= 0, "rf_grad_range: bad arguments");
-    size_t wm = h->flat_floats; int n = 0;
-    for (const std::string& m : grad_order(h)) {
-        const size_t lo = module_start(h, m);
-        if (lo >= wm) continue;
-        if (n == index) { *offset = lo; *count = wm - lo; return RF_OK; }
-        ++n; wm = lo;
-    }
-    set_error("rf_grad_range: index %d out of range (%d ranges)", index, n);
-    return RF_E_INVALID;
+    const int n = (int)h->grad_ranges.size();
+    RF_CHECK_ARG(index < n, "rf_grad_range: index %d out of range (%d ranges)", index, n);
+    *offset = h->grad_ranges[index].offset;
+    *count = h->grad_ranges[index].count;
+    return RF_OK;
 }
 
 int rf_flat_param_floats(const rf_handle* h, size_t* floats) {
@@ -689,11 +644,13 @@ int rf_train_step(rf_handle* h, const float* in, const float* gt, float* grads, 
     SideJoinGuard joined(h->side, st);
     Ctx c{h, &p, grads, B, st, st, &h->side};
     RF_TRY(check_hip(hipMemsetAsync(grads, 0, h->flat_floats * sizeof(float), st), "memset grads"));
-    std::vector<PackDesc> pack_list;
-    PackMap pack_map;
-    build_pack_list(h, p.pack_cache, &pack_list, &pack_map);
-    RF_TRY(launch_pack_batch(pack_list.data(), (int)pack_list.size(), st));
-    c.packs = &pack_map;
+    std::vector<PackDesc> packs;
+    for (const CachePack& k : h->cache_packs) {
+        packs.push_back(k.d);
+        packs.back().src = h->prm(k.param);
+        packs.back().dst = p.pack_cache + k.offset;
+    }
+    RF_TRY(launch_pack_batch(packs.data(), (int)packs.size(), st));
     const hipStream_t wg = h->side.get(st);      // the stages' weight-gradient stream
 
     // ------------------------------------------------------------------ forward
@@ -702,34 +659,29 @@ int rf_train_step(rf_handle* h, const float* in, const float* gt, float* grads, 
         RF_TRY(launch_guidance_base(p.x4, 0, 0, p.gscratch, B, H, W, st));
         for (int l = 0; l < 4; ++l) RF_TRY(launch_guidance_level(p.gscratch, p.guide[l], B, H, W, H >> l, W >> l, st));
     }
-    RF_TRY(f_conv3x3(c, p.x4, 4, P(h, "embedding.weight"), P(h, "embedding.bias"), p.e, d, H, W, 0, 0));
+    RF_TRY(f_conv3x3(c, p.x4, 4, h->embedding_w, h->prm(h->embedding_b), p.e, d, H, W, 0, 0));
     const float* cur = p.e;
     for (int i = 1; i <= 3; ++i) {
         const int lvl = i - 1, C = d << lvl, hh = H >> lvl, ww = W >> lvl;
-        RF_TRY(stage_forward(c, i, lvl, cur, H, W));
-        RF_TRY(f_conv3x3(c, p.st[i].out, C, P(h, "down" + std::to_string(i) + ".body.0.weight"), nullptr, p.down[i - 1], C / 2, hh, ww, 0, 1));
+        RF_TRY(stage_forward(c, i, cur, H, W));
+        RF_TRY(f_conv3x3(c, p.st[i].out, C, h->down_w[i - 1], nullptr, p.down[i - 1], C / 2, hh, ww, 0, 1));
         cur = p.down[i - 1];
     }
-    RF_TRY(stage_forward(c, 4, 3, cur, H, W));
+    RF_TRY(stage_forward(c, 4, cur, H, W));
     cur = p.st[4].out;
     for (int i = 1; i <= 3; ++i) {
         const int lvl = 3 - i, C = d << lvl, hh = H >> lvl, ww = W >> lvl, Pn = hh * ww;
-        const std::string u = "up" + std::to_string(i), r = "channel_reduce" + std::to_string(i);
-        const float* upw = c.pk(P(h, u + ".weight"), PF_N);
-        if (!upw) {
-            RF_TRY(pack_convT(P(h, u + ".weight"), p.wt1, 2 * C, C, st));
-            upw = p.wt1;
-        }
         Conv1x1Args up{};
-        up.x1 = cur; up.C1 = 2 * C; up.x1_bstride = (int64_t)2 * C * (Pn / 4); up.wp = upw; up.bias = P(h, u + ".bias");
-        if (upw != p.wt1) up.wp3 = c.pk(P(h, u + ".weight"), PF_N3);
+        RF_TRY(c.pk(h->up_w[i - 1], PF_N, &up.wp));
+        up.wp3 = c.pk(h->up_w[i - 1], PF_N3);
+        up.x1 = cur; up.C1 = 2 * C; up.x1_bstride = (int64_t)2 * C * (Pn / 4); up.bias = h->prm(h->up_b[i - 1]);
         up.out = p.up[i - 1]; up.out_bstride = (int64_t)C * Pn; up.Cout = 4 * C; up.B = B; up.P = Pn / 4; up.w = ww / 2; up.mode = 1;
         RF_TRY(launch_conv1x1(up, st));
-        RF_TRY(f_conv1x1(c, p.up[i - 1], C, p.st[lvl + 1].out, C, P(h, r + ".weight"), P(h, r + ".bias"), nullptr, nullptr, nullptr, p.catr[i - 1], C, Pn));
-        RF_TRY(stage_forward(c, 4 + i, lvl, p.catr[i - 1], H, W));
+        RF_TRY(f_conv1x1(c, p.up[i - 1], C, p.st[lvl + 1].out, C, h->upcr_w[i - 1], h->prm(h->upcr_b[i - 1]), nullptr, nullptr, nullptr, p.catr[i - 1], C, Pn));
+        RF_TRY(stage_forward(c, 4 + i, p.catr[i - 1], H, W));
         cur = p.st[4 + i].out;
     }
-    RF_TRY(f_conv3x3(c, cur, d, P(h, "conv_out.weight"), P(h, "conv_out.bias"), p.pred, 4 * oc, H, W, 1, 2));
+    RF_TRY(f_conv3x3(c, cur, d, h->conv_out_w, h->prm(h->conv_out_b), p.pred, 4 * oc, H, W, 1, 2));
     const size_t npred = (size_t)B * oc * 4 * H * W;
     if (pred_out) RF_TRY(check_hip(hipMemcpyAsync(pred_out, p.pred, npred * 4, hipMemcpyDeviceToDevice, st), "copy pred"));
 
@@ -742,11 +694,14 @@ int rf_train_step(rf_handle* h, const float* in, const float* gt, float* grads, 
     RF_TRY(launch_pixel_unshuffle2(p.dpred, tA, B, oc, H, W, st));          // [B, 4 oc, H, W]
     RF_TRY(launch_pixel_unshuffle2(p.pred, tB, B, oc, H, W, st));
     RF_TRY(launch_ewise(tA, tB, tA, (size_t)B * 4 * oc * H * W, 2, 0.2f, st));
-    RF_TRY(b_conv3x3_dw(c, tA, 4 * oc, p.st[7].out, d, c.G("conv_out.weight"), c.G("conv_out.bias"), H, W));
-    GradNotifier note{h, st, h->flat_floats};
-    note.done("conv_out.");
+    RF_TRY(b_conv3x3_dw(c, tA, 4 * oc, p.st[7].out, d, c.G(h->conv_out_w), c.G(h->conv_out_b), H, W));
+    // announce range k of h->grad_ranges (plan_training lists the order): final on st from here on
+    auto ready = [&](int k) {
+        if (h->grad_ready) h->grad_ready(h->grad_ready_user, h->grad_ranges[k].offset, h->grad_ranges[k].count, (void*)st);
+    };
+    ready(0);                                                                                  // conv_out
     float* tE_src = p.tC;
-    RF_TRY(b_conv3x3_dx(c, tA, 4 * oc, P(h, "conv_out.weight"), d, tE_src, H, W));    // d(stage 7 out)
+    RF_TRY(b_conv3x3_dx(c, tA, 4 * oc, h->conv_out_w, d, tE_src, H, W));    // d(stage 7 out)
     for (int l = 0; l < 3; ++l) RF_TRY(check_hip(hipMemsetAsync(p.dskip[l], 0, ((size_t)B * (d << l) * (H >> l) * (W >> l)) * 4, st), "memset dskip"));
     // ga: gradient w.r.t. the output of the stage about to be processed; gb receives the gradient w.r.t. its input
     float *ga = p.ga, *gb = p.gb;
@@ -754,30 +709,25 @@ int rf_train_step(rf_handle* h, const float* in, const float* gt, float* grads, 
     // decoder, top-down
     for (int i = 3; i >= 1; --i) {
         const int lvl = 3 - i, C = d << lvl, hh = H >> lvl, ww = W >> lvl, Pn = hh * ww;
-        const std::string u = "up" + std::to_string(i), r = "channel_reduce" + std::to_string(i);
-        RF_TRY(stage_backward(c, wg, 4 + i, lvl, ga, gb, H, W));                                   // gb = d(catr_i)
-        note.done("conv_tran" + std::to_string(4 + i) + ".");
+        RF_TRY(stage_backward(c, wg, 4 + i, ga, gb, H, W));                                   // gb = d(catr_i)
+        ready(2 * (3 - i) + 1);                                                                // conv_tran<4 + i>
         // channel_reduce_i over cat[up, skip]
-        RF_TRY(b_conv1x1_dw(c, gb, C, p.up[i - 1], C, c.G(r + ".weight"), 2 * C, 0, c.G(r + ".bias"), hh, ww, 0, p.st[lvl + 1].out, C));
-        RF_TRY(b_conv1x1_dx(c, gb, C, P(h, r + ".weight"), 2 * C, p.tC, Pn));                 // tC = [dup ; dskip]
+        RF_TRY(b_conv1x1_dw(c, gb, C, p.up[i - 1], C, c.G(h->upcr_w[i - 1]), 2 * C, 0, c.G(h->upcr_b[i - 1]), hh, ww, 0, p.st[lvl + 1].out, C));
+        RF_TRY(b_conv1x1_dx(c, gb, C, h->upcr_w[i - 1], 2 * C, p.tC, Pn));                 // tC = [dup ; dskip]
         RF_TRY(launch_split_halves(p.tC, p.tA, p.dskip[lvl], B, C, Pn, st));
         // ConvTranspose2d(2C -> C): dX = conv1x1(unshuffle(dup), W as [2C][4C]);  dW = gram2(x, unshuffle(dup));  db = channel sums of dup
-        RF_TRY(launch_chan_sum(p.tA, (int64_t)C * Pn, c.G(u + ".bias"), p.part, B, C, Pn, 1, st));
+        RF_TRY(launch_chan_sum(p.tA, (int64_t)C * Pn, c.G(h->up_b[i - 1]), p.part, B, C, Pn, 1, st));
         RF_TRY(launch_pixel_unshuffle2(p.tA, p.tB, B, C, hh / 2, ww / 2, st));                 // [B, 4C, hh/2, ww/2]
         const float* xin = (i == 1) ? p.st[4].out : p.st[4 + i - 1].out;
-        RF_TRY(launch_gram2(xin, (int64_t)2 * C * (Pn / 4), 2 * C, p.tB, (int64_t)4 * C * (Pn / 4), 4 * C, c.G(u + ".weight"), 4 * C, p.part, p.part_floats, B, hh / 2, ww / 2,
+        RF_TRY(launch_gram2(xin, (int64_t)2 * C * (Pn / 4), 2 * C, p.tB, (int64_t)4 * C * (Pn / 4), 4 * C, c.G(h->up_w[i - 1]), 4 * C, p.part, p.part_floats, B, hh / 2, ww / 2,
                             1, 0, 0, 0, 0, 1, st));
-        const float* upb = c.pk(P(h, u + ".weight"), PF_CTB);
-        if (!upb) {
-            RF_TRY(pack_1x1(P(h, u + ".weight"), p.wt1, 2 * C, 4 * C, 4 * C, 1, st));
-            upb = p.wt1;
-        }
         Conv1x1Args a{};
-        a.x1 = p.tB; a.C1 = 4 * C; a.x1_bstride = (int64_t)4 * C * (Pn / 4); a.wp = upb;
-        if (upb != p.wt1) a.wp3 = c.pk(P(h, u + ".weight"), PF_CTB3);
+        RF_TRY(c.pk(h->up_w[i - 1], PF_CTB, &a.wp));
+        a.wp3 = c.pk(h->up_w[i - 1], PF_CTB3);
+        a.x1 = p.tB; a.C1 = 4 * C; a.x1_bstride = (int64_t)4 * C * (Pn / 4);
         a.out = ga; a.out_bstride = (int64_t)2 * C * (Pn / 4); a.Cout = 2 * C; a.B = B; a.P = Pn / 4; a.w = ww / 2;
         RF_TRY(launch_conv1x1(a, st));                                                         // ga = d(previous stage out) [B, 2C, Pn/4]
-        note.done(u + ".");                                                                    // up_i and channel_reduce_i
+        ready(2 * (3 - i) + 2);                                                                // up_i and channel_reduce_i
     }
     // bottleneck and encoder, bottom-up: ga = d(stage i out) on entry (for i <= 3 after the Downsample adjoint and the skip gradient)
     for (int i = 4; i >= 1; --i) {
@@ -785,18 +735,17 @@ int rf_train_step(rf_handle* h, const float* in, const float* gt, float* grads, 
         if (i <= 3) {
             // gb = d(down_i output) [B, 2C, Pn/4] = d(stage i+1 input)
             RF_TRY(launch_pixel_shuffle2(gb, p.tA, B, C / 2, hh / 2, ww / 2, st));             // [B, C/2, hh, ww]
-            RF_TRY(b_conv3x3_dw(c, p.tA, C / 2, p.st[i].out, C, c.G("down" + std::to_string(i) + ".body.0.weight"), nullptr, hh, ww));
-            RF_TRY(b_conv3x3_dx(c, p.tA, C / 2, P(h, "down" + std::to_string(i) + ".body.0.weight"), C, ga, hh, ww));
+            RF_TRY(b_conv3x3_dw(c, p.tA, C / 2, p.st[i].out, C, c.G(h->down_w[i - 1]), nullptr, hh, ww));
+            RF_TRY(b_conv3x3_dx(c, p.tA, C / 2, h->down_w[i - 1], C, ga, hh, ww));
             RF_TRY(launch_ewise(ga, p.dskip[lvl], ga, (size_t)B * C * Pn, 0, 0.f, st));
         }
-        RF_TRY(stage_backward(c, wg, i, lvl, ga, gb, H, W));                                       // gb = d(stage i input)
-        note.done("conv_tran" + std::to_string(i) + ".");                                      // and down_i, whose gradient came first
+        RF_TRY(stage_backward(c, wg, i, ga, gb, H, W));                                       // gb = d(stage i input)
+        ready(11 - i);                                                                         // conv_tran<i> and down_i, whose gradient came first
     }
     float* dcur = gb;
     // embedding
-    RF_TRY(b_conv3x3_dw(c, dcur, d, p.x4, 4, c.G("embedding.weight"), c.G("embedding.bias"), H, W));
-    note.done("embedding.");
-    if (note.watermark != 0 && h->grad_ready) h->grad_ready(h->grad_ready_user, 0, note.watermark, (void*)st);      // anything in front (never, by construction)
+    RF_TRY(b_conv3x3_dw(c, dcur, d, p.x4, 4, c.G(h->embedding_w), c.G(h->embedding_b), H, W));
+    ready(11);                                                                                 // embedding: the buffer's first float
     return RF_OK;
 }
 

@@ -78,3 +78,57 @@ def test_create_rejects_bad_configs():
     assert make(dim=32, heads=(8, 8, 8, 3))[0] == -22
     assert make(dim=32, variant=7)[0] == -22
     assert make(dim=1024, heads=(8, 8, 8, 8))[0] == -22      # head size > 64
+
+
+# rf_packed_bytes, rf_workspace_bytes(1, 64, 64) and rf_workspace_bytes(8, 512, 512) as the library returned them at e6a50e1,
+# before the handle recorded its registry indices at creation (heads 8 at every level, ffn_expansion 2, 3 output channels)
+PLAN_BYTES = {
+    ("plain", 32): (32372736, 14978304, 4072939776),
+    ("flca", 16): (5002496, 6881536, 2076578048),
+    ("flca", 32): (19781632, 14978304, 4072939776),
+    ("flca", 48): (44564992, 24349952, 6069498112),
+    ("flca", 64): (79006976, 35300608, 8098693376),
+    ("truecolor", 32): (22035456, 16032768, 4610732288),
+}
+GRAD_ORDER = ["conv_out.", "conv_tran7.", "up3.", "conv_tran6.", "up2.", "conv_tran5.", "up1.",
+              "conv_tran4.", "conv_tran3.", "conv_tran2.", "conv_tran1.", "embedding."]
+
+
+@pytest.mark.parametrize("variant,dim", list(PLAN_BYTES))
+def test_handle_plans_and_gradient_ranges(variant, dim):
+    lib = _lib.load()
+    rc, h = make(dim, {"flca": _lib.RF_VARIANT_FLCA, "plain": _lib.RF_VARIANT_PLAIN, "truecolor": _lib.RF_VARIANT_TRUECOLOR}[variant])
+    assert rc == 0
+    try:
+        got = []
+        sz = C.c_size_t()
+        assert lib.rf_packed_bytes(h, C.byref(sz)) == 0
+        got.append(sz.value)
+        for b, hh, ww in ((1, 64, 64), (8, 512, 512)):
+            assert lib.rf_workspace_bytes(h, b, hh, ww, C.byref(sz)) == 0
+            got.append(sz.value)
+        assert tuple(got) == PLAN_BYTES[(variant, dim)]
+        if variant == "truecolor":      # parameters in front of embedding. belong to no range: no tiling rule
+            return
+        # each range starts at the first flat float of the next module in grad_order and ends where the previous one began
+        name, off = C.c_char_p(), C.c_size_t()
+        first = {}
+        for i in range(lib.rf_param_count(h)):
+            assert lib.rf_param_info(h, i, C.byref(name), None, None) == 0
+            assert lib.rf_flat_offset(h, i, C.byref(off)) == 0
+            m = next((m for m in GRAD_ORDER if name.value.decode().startswith(m)), None)
+            if m is not None:
+                first[m] = min(first.get(m, off.value), off.value)
+        assert lib.rf_flat_param_floats(h, C.byref(sz)) == 0
+        end = sz.value
+        n = C.c_int()
+        assert lib.rf_grad_range_count(h, C.byref(n)) == 0 and n.value == len(GRAD_ORDER)
+        cnt = C.c_size_t()
+        for i, m in enumerate(GRAD_ORDER):
+            assert lib.rf_grad_range(h, i, C.byref(off), C.byref(cnt)) == 0
+            assert (off.value, off.value + cnt.value) == (first[m], end), m
+            end = off.value
+        assert end == 0
+        assert lib.rf_grad_range(h, n.value, C.byref(off), C.byref(cnt)) == -22
+    finally:
+        lib.rf_destroy(h)
