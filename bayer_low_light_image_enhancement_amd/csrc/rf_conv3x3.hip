@@ -42,7 +42,14 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 // its partial tile (after the output transform, before bias and activation) to scratch; the LAST one to arrive -- a ticket per
 // (image, tile, output group) -- adds the partials in split order (deterministic whatever the arrival order), applies bias /
 // activation / clamp and stores.  One 16 x 16 frame at level 3 is a chain of 32 chunk barriers on 4 workgroups otherwise.
-template <int NCO, int LOG2_RW, int RPW, int NWV, bool KS = false>
+//
+// L0 (wide level-0 launches with Cin <= 32, rows of whole aligned float4s; dispatched by launch_rw, nothing else changes):
+//   bit 0: the output group's complete Winograd weight set (Cin/4 k-sets x 18 taps x NCO x 64 floats, at most 72 KB) is loaded
+//          into LDS once per workgroup and stays there; the chunk loop stages input only.
+//   bit 1: the halo'd input tile is staged by row segments: the 64 interior floats of a (channel, row) as 16-byte loads,
+//          the two halo columns as dword loads (V4PT + 1 memory instructions per thread and chunk instead of EPT = 19 or 10,
+//          and a tile plan of the same length).  The LDS layout, and with it every MFMA operand, is the generic path's.
+template <int NCO, int LOG2_RW, int RPW, int NWV, bool KS = false, int L0 = 0>
 __global__ void __launch_bounds__(64 * NWV, (NWV >= 8 || NCO >= 3) ? 1 : 2) conv3x3_kernel(Conv3x3Args a, int ngroups, int tiles_x, int ntiles, int vec) {
     constexpr int NTHR = 64 * NWV;
     constexpr int TAPS = 18;                 // transformed taps per k-set (3 kernel rows x 6)
@@ -54,13 +61,20 @@ __global__ void __launch_bounds__(64 * NWV, (NWV >= 8 || NCO >= 3) ? 1 : 2) conv
     static_assert(RPW == 1 || RW == 1, "two row groups per wave only with one row per group");
     constexpr int RS = TW + 8;               // LDS row stride
     constexpr int PS = ((TH + 2) * RS + 63) / 64 * 64;   // LDS plane stride in floats (multiple of 64)
+    constexpr bool RESW = (L0 & 1) != 0, ROWS = (L0 & 2) != 0;
+    static_assert(L0 == 0 || (!KS && LOG2_RW == 0), "the level-0 path: wide tiles, no input-channel split");
     constexpr int NIN = KC * (TH + 2) * (TW + 2);       // staged input elements per chunk
-    constexpr int EPT = (NIN + NTHR - 1) / NTHR;        // ... per thread
-    constexpr int NW4 = 2 * TAPS * NCO * 16;            // staged weight float4 per chunk
-    constexpr int WPT = (NW4 + NTHR - 1) / NTHR;
-    constexpr int BUF = KC * PS + 2 * TAPS * NCO * 64;  // floats per LDS buffer
-    __shared__ __attribute__((aligned(16))) float lds[2 * BUF];
-    __shared__ float bias_l[NCO * 16];       // the epilogue must not read global memory: a load there is followed by
+    constexpr int NV4 = KC * (TH + 2) * (TW / 4);       // ROWS: interior float4 per chunk ...
+    constexpr int V4PT = ROWS ? (NV4 + NTHR - 1) / NTHR : 0;   // ... per thread; then one halo element per thread
+    static_assert(!ROWS || 2 * KC * (TH + 2) <= NTHR, "one halo element per thread");
+    constexpr int EPT = ROWS ? V4PT + 1 : (NIN + NTHR - 1) / NTHR;   // staged input items per thread
+    constexpr int WSL = 2 * TAPS * NCO * 64;            // floats of one chunk's weight slice
+    constexpr int NW4 = WSL / 4;                        // staged weight float4 per chunk
+    constexpr int WPT = RESW ? 0 : (NW4 + NTHR - 1) / NTHR;
+    constexpr int BUF = KC * PS + (RESW ? 0 : WSL);     // floats per LDS buffer
+    constexpr int MAXCH = 32 / KC;                      // RESW: chunks whose weights are resident (Cin <= 32)
+    __shared__ __attribute__((aligned(16))) float lds[2 * BUF + (RESW ? MAXCH * WSL : 0)];
+    __shared__ __attribute__((aligned(16))) float bias_l[NCO * 16];       // the epilogue must not read global memory: a load there is followed by
                                              // s_waitcnt vmcnt(0), one exposed round trip per bias value and tile
 
     const int tid = threadIdx.x;
@@ -91,18 +105,35 @@ __global__ void __launch_bounds__(64 * NWV, (NWV >= 8 || NCO >= 3) ? 1 : 2) conv
     int prc[EPT];             // (cl << 16) | (r << 8) | c, or -1 = no element
     short loff[EPT];          // LDS float offset inside a buffer ("no element" -> a spare slot in the plane padding,
                               // so the LDS writes need no predicate; 128 spare slots, 2 threads of different waves each)
-    static_assert(PS - (TH + 2) * RS >= 16, "plane padding holds the dummy slots");
-    const int dummy = (tid & 7) * PS + (TH + 2) * RS + ((tid >> 3) & 15);   // shared only by threads of different waves
+    static_assert(PS - (TH + 2) * RS >= (ROWS ? 32 : 16), "plane padding holds the dummy slots");
+    const int dummy = ROWS ? (tid & 7) * PS + (TH + 2) * RS + 4 * ((tid >> 3) & 7)    // four floats
+                           : (tid & 7) * PS + (TH + 2) * RS + ((tid >> 3) & 15);   // shared only by threads of different waves
+    if constexpr (ROWS) {
+        // item i < V4PT: float4 q of halo'd row (cl, r), columns 1 + 4q .. 4 + 4q; item V4PT: column 0 or TW + 1 of row tid / 2
 #pragma unroll
-    for (int i = 0; i < EPT; ++i) {
-        const int idx = tid + NTHR * i;
-        const int c = idx % (TW + 2);
-        const int r = (idx / (TW + 2)) % (TH + 2);
-        const int cl = idx / ((TW + 2) * (TH + 2));
-        prc[i] = idx < NIN ? (cl << 16) | (r << 8) | c : -1;
-        loff[i] = (short)(idx < NIN ? cl * PS + r * RS + c : dummy);
+        for (int i = 0; i < V4PT; ++i) {
+            const int idx = tid + NTHR * i;
+            const int c = 1 + 4 * (idx % (TW / 4));
+            const int r = (idx / (TW / 4)) % (TH + 2);
+            const int cl = idx / ((TW / 4) * (TH + 2));
+            prc[i] = idx < NV4 ? (cl << 16) | (r << 8) | c : -1;
+            loff[i] = (short)(idx < NV4 ? cl * PS + r * RS + c : dummy);
+        }
+        const int c = (tid & 1) * (TW + 1), r = (tid >> 1) % (TH + 2), cl = (tid >> 1) / (TH + 2);
+        prc[V4PT] = cl < KC ? (cl << 16) | (r << 8) | c : -1;
+        loff[V4PT] = (short)(cl < KC ? cl * PS + r * RS + c : dummy);
+    } else {
+#pragma unroll
+        for (int i = 0; i < EPT; ++i) {
+            const int idx = tid + NTHR * i;
+            const int c = idx % (TW + 2);
+            const int r = (idx / (TW + 2)) % (TH + 2);
+            const int cl = idx / ((TW + 2) * (TH + 2));
+            prc[i] = idx < NIN ? (cl << 16) | (r << 8) | c : -1;
+            loff[i] = (short)(idx < NIN ? cl * PS + r * RS + c : dummy);
+        }
     }
-    unsigned wvoff[WPT];      // weight byte offsets inside one chunk's packed slice
+    unsigned wvoff[WPT > 0 ? WPT : 1];      // weight byte offsets inside one chunk's packed slice
 #pragma unroll
     for (int i = 0; i < WPT; ++i) {
         const int idx = tid + NTHR * i;
@@ -134,8 +165,9 @@ __global__ void __launch_bounds__(64 * NWV, (NWV >= 8 || NCO >= 3) ? 1 : 2) conv
             voff[i] = ok ? (unsigned)(4 * (a.unshuffle_in ? off_m : off_p)) : OOB;
         }
     };
-    float xin[EPT];
-    float4 win[WPT];
+    float xin[ROWS ? 1 : EPT];
+    u32x4 xin4[ROWS ? V4PT : 1];          // ROWS: the interior float4s (xin[0] = the halo element)
+    float4 win[WPT > 0 ? WPT : 1];
     auto load_chunk = [&](int ch) {
         // planes of this chunk that exist: min(KC, Cin - ch*KC) channel planes (mosaic input: 4 channels = 1 plane of 4hw)
         const int cl_lim = min(KC, a.Cin - ch * KC);
@@ -144,8 +176,15 @@ __global__ void __launch_bounds__(64 * NWV, (NWV >= 8 || NCO >= 3) ? 1 : 2) conv
             const_cast<float*>(src), 0, (int)(a.unshuffle_in ? (size_t)(cl_lim / 4) * 4 * plane_bytes : (size_t)cl_lim * plane_bytes), 0x00020000);
         const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<float*>(a.wp) + (size_t)ch * (w_chunk_bytes / 4), 0, w_chunk_bytes, 0x00020000);
+        if constexpr (ROWS) {
+            // a float4 lies inside the image or outside it as a whole (w % 4 == 0, checked by the launcher), and so do the planes
 #pragma unroll
-        for (int i = 0; i < EPT; ++i) xin[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, (int)voff[i], 0, 0));
+            for (int i = 0; i < V4PT; ++i) xin4[i] = __builtin_amdgcn_raw_buffer_load_b128(rx, (int)voff[i], 0, 0);
+            xin[0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, (int)voff[V4PT], 0, 0));
+        } else {
+#pragma unroll
+            for (int i = 0; i < EPT; ++i) xin[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, (int)voff[i], 0, 0));
+        }
 #pragma unroll
         for (int i = 0; i < WPT; ++i) {
             const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rw, (int)wvoff[i], 0, 0);
@@ -155,11 +194,23 @@ __global__ void __launch_bounds__(64 * NWV, (NWV >= 8 || NCO >= 3) ? 1 : 2) conv
     auto store_chunk = [&](int buf) {
         float* li = lds + buf * BUF;
         float* lw = li + KC * PS;
+        if constexpr (ROWS) {
+            // the interior starts at column 1 (the halo column in front of it is what the B-operand reads expect): dword writes
 #pragma unroll
-        for (int i = 0; i < EPT; ++i) {
+            for (int i = 0; i < V4PT; ++i) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    float v = __uint_as_float(xin4[i][g]);
+                    if (a.clamp_in) v = fminf(fmaxf(v, 0.f), 1.f);
+                    li[loff[i] + g] = v;
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < (ROWS ? 1 : EPT); ++i) {
             float v = xin[i];
             if (a.clamp_in) v = fminf(fmaxf(v, 0.f), 1.f);      // uniform; only the clamp_io embedding conv
-            li[loff[i]] = v;
+            li[loff[ROWS ? V4PT : i]] = v;
         }
 #pragma unroll
         for (int i = 0; i < WPT; ++i) {
@@ -184,6 +235,17 @@ __global__ void __launch_bounds__(64 * NWV, (NWV >= 8 || NCO >= 3) ? 1 : 2) conv
     }
     plan_tile(tile);
     load_chunk(ch_lo);
+    if constexpr (RESW) {
+        // resident weights: chunk ch at lds + 2 BUF + ch WSL, laid out [kt][t][64] as the staged slice is
+        float* lw = lds + 2 * BUF;
+        const int n4 = nchunks_all * NW4;
+        for (int idx = tid; idx < n4; idx += NTHR) {
+            const int l4 = idx % 16, t = (idx / 16) % NCO, kt = idx / (16 * NCO);      // kt = (2 ch + ks) * TAPS + tap
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (t0 + t < NT) v = *reinterpret_cast<const float4*>(a.wp + ((size_t)(kt * NT + t0 + t) * 64 + l4 * 4));
+            *reinterpret_cast<float4*>(lw + idx * 4) = v;
+        }
+    }
     store_chunk(0);
     __syncthreads();
     int buf = 0;
@@ -203,7 +265,7 @@ __global__ void __launch_bounds__(64 * NWV, (NWV >= 8 || NCO >= 3) ? 1 : 2) conv
             if (last && more) plan_tile(tile + nwg);
             if (more) load_chunk(nch);                  // in flight during the MFMA block below
             const float* lds_in = lds + buf * BUF;
-            const float* lds_w = lds_in + KC * PS;
+            const float* lds_w = RESW ? lds + 2 * BUF + ch * WSL : lds_in + KC * PS;
             const int nks = (a.Cin - ch * KC > 4) ? 2 : 1;   // a 4-channel tail (the embedding conv) skips the empty k-set
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
@@ -258,21 +320,27 @@ __global__ void __launch_bounds__(64 * NWV, (NWV >= 8 || NCO >= 3) ? 1 : 2) conv
             u[r][3] = fmaf(8.f, d34, d12) + mm[5][r];
         }
     };
-    // bias, activation, clamp
+    // bias, activation, clamp.  The (uniform) choice of the activation is made once per 16 values: written per value it stayed
+    // a chain of six scalar branches around every one of them, and the bias a ds_read_b32 + lgkmcnt(0) per channel.
     auto finish = [&](int t, float (&v)[4][4]) {
+        const float4 b4 = *reinterpret_cast<const float4*>(bias_l + 16 * t + 4 * kq_);
+        const float bs[4] = {b4.x, b4.y, b4.z, b4.w};
+        auto each = [&](auto f) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float bs = bias_l[16 * t + 4 * kq_ + r];
+            for (int r = 0; r < 4; ++r)
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                float u = v[r][g] + bs;
-                if (a.act == 1) u = u > 0.f ? u : 0.2f * u;
-                else if (a.act == 2) u = fmaxf(u, 0.f);
-                else if (a.act == 3) u = gelu_fast(u);
-                else if (a.act == 4) u = 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * u));      // tanh
-                if (a.clamp_out) u = fminf(fmaxf(u, 0.f), 1.f);
-                v[r][g] = u;
-            }
+                for (int g = 0; g < 4; ++g) v[r][g] = f(v[r][g] + bs[r]);
+        };
+        if (a.act == 1) each([](float u) { return u > 0.f ? u : 0.2f * u; });
+        else if (a.act == 2) each([](float u) { return fmaxf(u, 0.f); });
+        else if (a.act == 3) each([](float u) { return gelu_fast(u); });
+        else if (a.act == 4) each([](float u) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * u)); });      // tanh
+        else each([](float u) { return u; });
+        if (a.clamp_out) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) v[r][g] = fminf(fmaxf(v[r][g], 0.f), 1.f);
         }
     };
     auto store_tile = [&](int t, int y, const float (&v)[4][4]) {
@@ -430,6 +498,14 @@ static int ksplit_for(const Conv3x3Args& a, int ntiles, int ngroups, int vec, co
     return S;
 }
 
+// Shapes of the level-0 path (template argument L0 of the kernel): a wide launch that is not small, all of Cin in at most four
+// chunks (resident weights), one or two output tiles per group (the instantiations that exist), and input rows made of whole,
+// 16-byte aligned float4s.  The mosaic input of the embedding conv is gathered element by element and stays on the generic path.
+static bool level0_path(const Conv3x3Args& a, int nco, bool small) {
+    return !small && nco <= 2 && a.w > 32 && a.h >= 16 && a.Cin <= 32 && !a.unshuffle_in && a.w % 4 == 0 && aligned16(a.x) &&
+           a.x_bstride % 4 == 0;
+}
+
 template <int NCO>
 static void launch_rw(const Conv3x3Args& a, int ngroups, int vec, bool small, hipStream_t st) {
     // Wide images (w > 32): 8 waves share one 18-tap weight slice, one workgroup per CU; a wave owns one pixel
@@ -454,9 +530,16 @@ static void launch_rw(const Conv3x3Args& a, int ngroups, int vec, bool small, hi
         // one output tile: 16 waves of one row each (103 registers, four waves per SIMD cover each other's LDS and
         // barrier waits) beat 8 waves of two rows by 7 %; with NCO = 2 the same shape spills at the 128-register cap
         const int txs = cdiv(a.w, 64), ntiles = txs * cdiv(a.h, 16);
-        conv3x3_kernel<1, 0, 1, 16><<<grid_for_tiles(ntiles), 1024, 0, st>>>(a, ngroups, txs, ntiles, vec);
+        if (level0_path(a, NCO, small)) conv3x3_kernel<1, 0, 1, 16, false, 3><<<grid_for_tiles(ntiles), 1024, 0, st>>>(a, ngroups, txs, ntiles, vec);
+        else conv3x3_kernel<1, 0, 1, 16><<<grid_for_tiles(ntiles), 1024, 0, st>>>(a, ngroups, txs, ntiles, vec);
     } else if (lrw == 0 && a.h >= 8 * RPWB) {
         const int txs = cdiv(a.w, 64), ntiles = txs * cdiv(a.h, 8 * RPWB);
+        if constexpr (NCO == 2) {
+            if (level0_path(a, NCO, small)) {
+                conv3x3_kernel<2, 0, 2, 8, false, 3><<<grid_for_tiles(ntiles), 512, 0, st>>>(a, ngroups, txs, ntiles, vec);
+                return;
+            }
+        }
         conv3x3_kernel<NCO, 0, RPWB, 8><<<grid_for_tiles(ntiles), 512, 0, st>>>(a, ngroups, txs, ntiles, vec);
     } else if (lrw == 0 && a.h >= 8) {
         const int txs = cdiv(a.w, 64), ntiles = txs * cdiv(a.h, 8);
@@ -506,6 +589,7 @@ int launch_conv3x3(const Conv3x3Args& a, hipStream_t st) {
         snprintf(key, sizeof(key), "conv3x3_kernel<%d, %d, %d, %d>", nco, lrw, (wide && a.h >= 8 * rpwb) ? rpwb : 1, wide ? 8 : 4);
         if (nco == 1 && lrw == 0 && a.h >= 16) snprintf(key, sizeof(key), "conv3x3_kernel<1, 0, 1, 16>");
         if (small) snprintf(key, sizeof(key), "conv3x3_kernel<%d, 0, 1, 4>", nco);
+        if (level0_path(a, nco, small)) snprintf(key, sizeof(key), "conv3x3_kernel<%d, 0, %d, %d, false, 3>", nco, nco == 1 ? 1 : 2, nco == 1 ? 16 : 8);
     }
     const double px = (double)a.B * a.h * a.w;
     ProfScope prof(st, key, 18.0 * a.Cin * a.Cout * px, 4.0 * px * (a.Cin + a.Cout));
