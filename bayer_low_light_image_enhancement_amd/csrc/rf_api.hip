@@ -235,16 +235,15 @@ static int attn_scratch(int B, int C, int heads, int h, int w, AttnScratch* s) {
         attn_mid_plan(h, w, &ns, &pf2, B, C);
         if (pf2 > pf) pf = pf2;
     }
-    size_t off = 0;
-    auto take = [&](size_t f) { const size_t o = off; off += align_up(f, 64); return o; };
-    s->wqkv = take(packed1x1_floats(C, 3 * C));
-    s->wqkv3 = take(packed1x1_b3_floats(C, 3 * C));
-    s->pre = take((size_t)B * 3 * C * P);
-    s->qkv = take((size_t)B * 3 * C * P);
-    s->partial = take(pf);
-    s->wfold = take((size_t)B * packed1x1_floats(C, C));
-    s->wfold3 = take((size_t)B * packed1x1_b3_floats(C, C));
-    s->total = off;
+    Bump b;
+    s->wqkv = b.off(packed1x1_floats(C, 3 * C));
+    s->wqkv3 = b.off(packed1x1_b3_floats(C, 3 * C));
+    s->pre = b.off((size_t)B * 3 * C * P);
+    s->qkv = b.off((size_t)B * 3 * C * P);
+    s->partial = b.off(pf);
+    s->wfold = b.off((size_t)B * packed1x1_floats(C, C));
+    s->wfold3 = b.off((size_t)B * packed1x1_b3_floats(C, C));
+    s->total = b.used;
     return RF_OK;
 }
 
@@ -262,59 +261,30 @@ int rf_chan_attn(const float* in, float* out, const float* qkv_w, const float* q
                  int B, int C, int heads, int h, int w, void* stream) {
     RF_CHECK_ARG(in && out && qkv_w && dw_w && temperature && proj_w && scratch && aligned16(scratch), "chan_attn: bad arguments");
     hipStream_t st = (hipStream_t)stream;
-    const int P = h * w;
     AttnScratch s;
     RF_TRY(attn_scratch(B, C, heads, h, w, &s));
     float* ws = (float*)scratch;
     RF_TRY(pack_1x1(qkv_w, ws + s.wqkv, 3 * C, C, C, 1, st));
     RF_TRY(pack_1x1_b3(qkv_w, ws + s.wqkv3, 3 * C, C, C, 1, st));
-    Conv1x1Args q{};
-    q.x1 = in; q.C1 = C; q.x1_bstride = (int64_t)C * P; q.wp = ws + s.wqkv; q.wp3 = ws + s.wqkv3; q.bias = qkv_b;
-    q.out = ws + s.pre; q.out_bstride = (int64_t)3 * C * P; q.Cout = 3 * C; q.B = B; q.P = P; q.w = w;
-    RF_TRY(launch_conv1x1(q, st));
-    Conv1x1Args av{};
-    int nslab = 0;
-    if (attn_mid_supported(C, heads, h, w)) {
-        // the forward's levels 1-2 kernel: depthwise 3x3 + Gram partials + v in one pass (rf_fused.hip)
-        size_t pf;
-        RF_TRY(attn_mid_plan(h, w, &nslab, &pf, B, C));
-        RF_TRY(launch_attn_mid(ws + s.pre, ws + s.qkv, ws + s.partial, nslab, dw_w, dw_b, B, C, h, w, st));
-        av.x1 = ws + s.qkv; av.x1_bstride = (int64_t)C * P;
-    } else {
-        DwConvArgs d{};
-        d.x = ws + s.pre; d.x_bstride = (int64_t)3 * C * P; d.out = ws + s.qkv; d.out_bstride = (int64_t)3 * C * P;
-        d.w = dw_w; d.bias = dw_b; d.B = B; d.C = 3 * C; d.h = h; d.w_ = w;
-        RF_TRY(launch_dwconv3x3(d, st));
-        GramArgs g{};
-        g.q = ws + s.qkv; g.k = ws + s.qkv + (size_t)C * P; g.bstride = (int64_t)3 * C * P;
-        g.B = B; g.C = C; g.heads = heads; g.P = P; g.partial = ws + s.partial;
-        size_t pf;
-        RF_TRY(gram_plan(B, C, heads, P, &g.nslab, &g.slab, &pf));
-        RF_TRY(launch_gram(g, st));
-        nslab = g.nslab;
-        av.x1 = ws + s.qkv + (size_t)2 * C * P; av.x1_bstride = (int64_t)3 * C * P;
-    }
-    RF_TRY(launch_attn_fold(ws + s.partial, nslab, temperature, proj_w, ws + s.wfold, ws + s.wfold3, B, C, heads, st));
-    av.C1 = C;
-    av.wp = ws + s.wfold; av.wp_bstride = (int64_t)packed1x1_floats(C, C); av.bias = proj_b;
-    av.wp3 = ws + s.wfold3; av.wp3_bstride = (int64_t)packed1x1_b3_floats(C, C);
-    av.out = out; av.out_bstride = (int64_t)C * P; av.Cout = C; av.B = B; av.P = P; av.w = w;
-    return launch_conv1x1(av, st);
+    // the block's attention schedule (rf_block.hip) without its LayerNorm and residual
+    TbParams p{};
+    p.qkv_wp = ws + s.wqkv; p.qkv_wp3 = ws + s.wqkv3; p.qkv_b = qkv_b; p.qkv_dw_w = dw_w; p.qkv_dw_b = dw_b;
+    p.temperature = temperature; p.proj_w = proj_w; p.proj_b = proj_b;
+    return run_chan_attn(p, in, out, false, AttnBufs{ws + s.pre, ws + s.qkv, ws + s.partial, ws + s.wfold, ws + s.wfold3}, B, C, heads, h, w, st);
 }
 
 // scratch layout of rf_transformer_block: packed qkv | packed pw1 | packed pw2 | run_transformer buffers
 struct TbScratch { size_t wqkv, w1, w2, wqkv3, w13, w23, bufs, total; TbBufOffsets o; };
 static void tb_scratch(int B, int C, int heads, int hc, int h, int w, TbScratch* s) {
-    size_t off = 0;
-    auto take = [&](size_t f) { const size_t r = off; off += align_up(f, 64); return r; };
-    s->wqkv = take(packed1x1_floats(C, 3 * C));
-    s->w1 = take(packed1x1_floats(C, hc));
-    s->w2 = take(packed1x1_floats(hc, C));
-    s->wqkv3 = take(packed1x1_b3_floats(C, 3 * C));
-    s->w13 = take(packed1x1_b3_floats(C, hc));
-    s->w23 = take(packed1x1_b3_floats(hc, C));
-    s->bufs = off;
-    s->total = off + transformer_scratch_floats(B, C, heads, hc, h, w, &s->o);
+    Bump b;
+    s->wqkv = b.off(packed1x1_floats(C, 3 * C));
+    s->w1 = b.off(packed1x1_floats(C, hc));
+    s->w2 = b.off(packed1x1_floats(hc, C));
+    s->wqkv3 = b.off(packed1x1_b3_floats(C, 3 * C));
+    s->w13 = b.off(packed1x1_b3_floats(C, hc));
+    s->w23 = b.off(packed1x1_b3_floats(hc, C));
+    s->bufs = b.used;
+    s->total = b.used + transformer_scratch_floats(B, C, heads, hc, h, w, &s->o);
 }
 
 int rf_transformer_block_scratch_bytes(int B, int C, int heads, int ffn_expansion, int h, int w, size_t* bytes) {
@@ -337,23 +307,38 @@ int rf_transformer_block(const float* in, float* out, const float* const* prm, v
     TbScratch s;
     tb_scratch(B, C, heads, hc, h, w, &s);
     float* ws = (float*)scratch;
-    // prm: norm1.w, norm1.b, temperature, qkv.w, qkv.b, qkv_dwconv.w, qkv_dwconv.b, project_out.w, project_out.b,
-    //      norm2.w, norm2.b, pointwise1.w, pointwise1.b, depthwise.w, depthwise.b, pointwise2.w, pointwise2.b
-    RF_TRY(pack_1x1(prm[3], ws + s.wqkv, 3 * C, C, C, 1, st));
-    RF_TRY(pack_1x1(prm[11], ws + s.w1, hc, C, C, 1, st));
-    RF_TRY(pack_1x1(prm[15], ws + s.w2, C, hc, hc, 1, st));
-    RF_TRY(pack_1x1_b3(prm[3], ws + s.wqkv3, 3 * C, C, C, 1, st));
-    RF_TRY(pack_1x1_b3(prm[11], ws + s.w13, hc, C, C, 1, st));
-    RF_TRY(pack_1x1_b3(prm[15], ws + s.w23, C, hc, hc, 1, st));
-    TbParams p{prm[0], prm[1], prm[2], ws + s.wqkv, prm[4], prm[5], prm[6], prm[7], prm[8],
-               prm[9], prm[10], ws + s.w1, prm[12], prm[13], prm[14], ws + s.w2, prm[16],
-               ws + s.wqkv3, ws + s.w13, ws + s.w23, 0};
+    // prm, in state_dict order; the three GEMM weights enter packed
+    TbParams p{};
+    p.ln1_w = prm[0]; p.ln1_b = prm[1]; p.temperature = prm[2];
+    const float* qkv_w = prm[3]; p.qkv_b = prm[4]; p.qkv_dw_w = prm[5]; p.qkv_dw_b = prm[6]; p.proj_w = prm[7]; p.proj_b = prm[8];
+    p.ln2_w = prm[9]; p.ln2_b = prm[10];
+    const float* pw1_w = prm[11]; p.pw1_b = prm[12]; p.dw_w = prm[13]; p.dw_b = prm[14];
+    const float* pw2_w = prm[15]; p.pw2_b = prm[16];
+    p.qkv_wp = ws + s.wqkv; p.pw1_wp = ws + s.w1; p.pw2_wp = ws + s.w2;
+    p.qkv_wp3 = ws + s.wqkv3; p.pw1_wp3 = ws + s.w13; p.pw2_wp3 = ws + s.w23;
+    RF_TRY(pack_1x1(qkv_w, ws + s.wqkv, 3 * C, C, C, 1, st));
+    RF_TRY(pack_1x1(pw1_w, ws + s.w1, hc, C, C, 1, st));
+    RF_TRY(pack_1x1(pw2_w, ws + s.w2, C, hc, hc, 1, st));
+    RF_TRY(pack_1x1_b3(qkv_w, ws + s.wqkv3, 3 * C, C, C, 1, st));
+    RF_TRY(pack_1x1_b3(pw1_w, ws + s.w13, hc, C, C, 1, st));
+    RF_TRY(pack_1x1_b3(pw2_w, ws + s.w23, C, hc, hc, 1, st));
     return run_transformer(p, in, out, ws + s.bufs, s.o, B, C, heads, hc, h, w, st);
+}
+
+// scratch layout of rf_flca: per-block channel sums | the gate [B][C]
+struct FlcaScratch { float *partial, *ch; size_t total; };
+static FlcaScratch flca_scratch(float* base, int B, int C, int h, int w) {
+    Bump b{base};
+    FlcaScratch s;
+    s.partial = b.take((size_t)B * flca_nblk(h, w) * C);
+    s.ch = b.take((size_t)B * C);
+    s.total = b.used;
+    return s;
 }
 
 int rf_flca_scratch_bytes(int B, int C, int h, int w, size_t* bytes) {
     RF_CHECK_ARG(bytes && B > 0 && C > 0 && h > 0 && w > 0, "flca_scratch_bytes: bad arguments");
-    *bytes = (align_up((size_t)B * flca_nblk(h, w) * C, 64) + align_up((size_t)B * C, 64)) * sizeof(float);
+    *bytes = flca_scratch(nullptr, B, C, h, w).total * sizeof(float);
     return RF_OK;
 }
 
@@ -362,17 +347,15 @@ int rf_flca(const float* feat, const float* guide, float* out, const float* cons
     RF_CHECK_ARG(feat && guide && out && prm && scratch && aligned16(scratch), "flca: bad arguments");
     for (int i = 0; i < 10; ++i) RF_CHECK_ARG(prm[i] != nullptr, "flca: parameter %d is null", i);
     hipStream_t st = (hipStream_t)stream;
-    float* partial = (float*)scratch;
-    float* ch = partial + align_up((size_t)B * flca_nblk(h, w) * C, 64);
-    // prm: alpha, beta, gamma, low_attn.0.w, high_attn.0.w, chroma_attn.0.w, se.1.w, se.1.b, se.3.w, se.3.b
+    const FlcaPrm p{prm[0], prm[1], prm[2], prm[3], prm[4], prm[5], {prm[6], prm[7], prm[8], prm[9]}};   // state_dict order = FlcaGroup's
+    const FlcaScratch s = flca_scratch((float*)scratch, B, C, h, w);
     FlcaSpatialArgs a{};
     a.feat = feat; a.xs = out; a.guide = guide;
-    a.alpha = prm[0]; a.beta = prm[1]; a.gamma = prm[2]; a.w_low = prm[3]; a.w_high = prm[4]; a.w_chr = prm[5];
-    a.partial = partial; a.B = B; a.C = C; a.h = h; a.w = w; a.nblk = flca_nblk(h, w);
+    a.set_params(p);
+    a.partial = s.partial; a.B = B; a.C = C; a.h = h; a.w = w; a.nblk = flca_nblk(h, w);
     RF_TRY(launch_flca_spatial(a, st));
-    const int hid = C / 8 > 8 ? C / 8 : 8;
-    RF_TRY(launch_flca_se(partial, a.nblk, h * w, prm[6], prm[7], prm[8], prm[9], hid, ch, B, C, st));
-    return launch_scale_channels(out, ch, B, C, h * w, st);
+    RF_TRY(launch_flca_se(s.partial, a.nblk, h * w, p.se, s.ch, B, C, st));
+    return launch_scale_channels(out, s.ch, B, C, h * w, st);
 }
 
 int rf_guidance_scratch_bytes(int B, int H, int W, size_t* bytes) {

@@ -8,21 +8,20 @@ namespace rf {
 
 size_t transformer_scratch_floats(int B, int C, int heads, int hc, int h, int w, TbBufOffsets* o) {
     const size_t P = (size_t)h * w;
-    size_t off = 0;
-    auto take = [&](size_t f) { const size_t r = off; off += align_up(f, 64); return r; };
+    Bump b;
     const size_t wide = (size_t)(3 * C > hc ? 3 * C : hc);
-    o->bufA = take((size_t)B * wide * P);
-    o->bufB = take((size_t)B * wide * P);
-    o->x1 = take((size_t)B * C * P);
+    o->bufA = b.off((size_t)B * wide * P);
+    o->bufB = b.off((size_t)B * wide * P);
+    o->x1 = b.off((size_t)B * C * P);
     int ns, sl;
     size_t pf = 0, pf2 = 0;
     if (gram_plan(B, C, heads, (int)P, &ns, &sl, &pf)) return 0;   // unsupported head layout: rf_last_error() says why
     if (fused_attn_supported(C, heads, h, w)) fused_attn_plan(h, w, &ns, &pf2, B, C);
     if (attn_mid_supported(C, heads, h, w)) attn_mid_plan(h, w, &ns, &pf2, B, C);
-    o->partial = take(pf > pf2 ? pf : pf2);
-    o->wfold = take((size_t)B * packed1x1_floats(C, C));
-    o->wfold3 = take((size_t)B * packed1x1_b3_floats(C, C));
-    return off;
+    o->partial = b.off(pf > pf2 ? pf : pf2);
+    o->wfold = b.off((size_t)B * packed1x1_floats(C, C));
+    o->wfold3 = b.off((size_t)B * packed1x1_b3_floats(C, C));
+    return b.used;
 }
 
 bool transformer_ffn_is_fused(const TbParams& p, int C, int hc, int hh, int ww) {
@@ -32,15 +31,72 @@ bool transformer_ffn_is_fused(const TbParams& p, int C, int hc, int hh, int ww) 
     return p.pw1_wp3 && fused_ffn_supported(C, hc, hh, ww);
 }
 
+int run_chan_attn(const TbParams& p, const float* in, float* out, bool residual, const AttnBufs& buf, int B, int C, int heads, int hh, int ww,
+                  hipStream_t st, bool no_fuse, bool no_fuse_attn) {
+    const int Pn = hh * ww;
+    float* const partial = buf.partial;
+    Conv1x1Args av{};
+    int nslab = 0;
+    size_t partial_floats = 0;
+    if (p.ln1_w && !no_fuse_attn && fused_attn_supported(C, heads, hh, ww)) {
+        // LN1 -> qkv 1x1 -> depthwise 3x3 -> {Gram partials, v} in one kernel: qkv never reaches HBM
+        RF_TRY(fused_attn_plan(hh, ww, &nslab, &partial_floats, B, C));
+        RF_TRY(launch_attn_front(in, buf.qkv, partial, nslab, p.ln1_w, p.ln1_b, p.qkv_wp3, p.qkv_b, p.qkv_dw_w, p.qkv_dw_b, B, C, hh, ww, st,
+                                 p.ylo, p.yhi));
+        av.x1 = buf.qkv; av.x1_bstride = (int64_t)C * Pn;
+    } else {
+        Conv1x1Args q{};
+        q.x1 = in; q.C1 = C; q.x1_bstride = (int64_t)C * Pn;
+        q.wp = p.qkv_wp; q.wp3 = p.qkv_wp3; q.bias = p.qkv_b;
+        q.ln_w = p.ln1_w; q.ln_b = p.ln1_b; q.ln_eps = 1e-5f;
+        q.out = buf.pre; q.out_bstride = (int64_t)3 * C * Pn; q.Cout = 3 * C; q.B = B; q.P = Pn; q.w = ww;
+        if (!conv1x1_ln_single_pass(q)) {      // LN1 as its own pass (buf.qkv is free until the depthwise kernel writes it)
+            RF_TRY(launch_layernorm2d(in, buf.qkv, p.ln1_w, p.ln1_b, 1e-5f, B, C, Pn, st));
+            q.x1 = buf.qkv; q.ln_w = nullptr; q.ln_b = nullptr;
+        }
+        RF_TRY(launch_conv1x1(q, st));
+
+        if (!no_fuse && attn_mid_supported(C, heads, hh, ww)) {
+            // depthwise 3x3 of q, k, v + Gram partials in one kernel: dw(q), dw(k) never reach HBM
+            RF_TRY(attn_mid_plan(hh, ww, &nslab, &partial_floats, B, C));
+            RF_TRY(launch_attn_mid(buf.pre, buf.qkv, partial, nslab, p.qkv_dw_w, p.qkv_dw_b, B, C, hh, ww, st, p.ylo, p.yhi));
+            av.x1 = buf.qkv; av.x1_bstride = (int64_t)C * Pn;
+        } else {
+            DwConvArgs d{};
+            d.x = buf.pre; d.x_bstride = (int64_t)3 * C * Pn; d.out = buf.qkv; d.out_bstride = (int64_t)3 * C * Pn;
+            d.w = p.qkv_dw_w; d.bias = p.qkv_dw_b;
+            d.B = B; d.C = 3 * C; d.h = hh; d.w_ = ww; d.gelu = 0;
+            RF_TRY(launch_dwconv3x3(d, st));
+
+            GramArgs g{};
+            g.q = buf.qkv; g.k = buf.qkv + (size_t)C * Pn; g.bstride = (int64_t)3 * C * Pn;
+            g.B = B; g.C = C; g.heads = heads; g.P = Pn; g.partial = partial;
+            RF_TRY(gram_plan(B, C, heads, Pn, &g.nslab, &g.slab, &partial_floats));
+            g.p_lo = p.ylo * ww; g.p_hi = p.yhi * ww;
+            RF_TRY(launch_gram(g, st));
+            nslab = g.nslab;
+            av.x1 = buf.qkv + (size_t)2 * C * Pn; av.x1_bstride = (int64_t)3 * C * Pn;
+        }
+    }
+    // spatial shard: every rank holds the same slab grid (equal local shapes), so the element-wise sum of the partial buffers is
+    // the partial buffer of the whole frame; the fold then sums the slabs as always
+    if (p.allreduce) p.allreduce(p.allreduce_user, partial, partial_floats, 0, (void*)st);
+    RF_TRY(launch_attn_fold(partial, nslab, p.temperature, p.proj_w, buf.wfold, buf.wfold3, B, C, heads, st, p.log_temperature));
+    av.C1 = C;
+    av.wp = buf.wfold; av.wp_bstride = (int64_t)packed1x1_floats(C, C);
+    av.wp3 = buf.wfold3; av.wp3_bstride = (int64_t)packed1x1_b3_floats(C, C);
+    av.bias = p.proj_b;
+    if (residual) { av.res = in; av.res_bstride = (int64_t)C * Pn; }
+    av.out = out; av.out_bstride = (int64_t)C * Pn; av.Cout = C; av.B = B; av.P = Pn; av.w = ww;
+    return launch_conv1x1(av, st);
+}
+
 int run_transformer(const TbParams& p, const float* in, float* out, float* ws, const TbBufOffsets& o,
                     int B, int C, int heads, int hc, int hh, int ww, hipStream_t st) {
     const int Pn = hh * ww;
     float* bufA = ws + o.bufA;
     float* bufB = ws + o.bufB;
     float* x1 = ws + o.x1;
-    float* partial = ws + o.partial;
-    float* wfold = ws + o.wfold;
-    float* wfold3 = ws + o.wfold3;
 #ifdef RF_DIAG   // diagnostic build only (build.py --diag): force the op-by-op path; the shipped library has no switch
     const bool no_fuse = getenv("RF_NO_FUSE") != nullptr;
     const bool no_fuse_attn = no_fuse || getenv("RF_NO_FUSE_ATTN") != nullptr;
@@ -49,66 +105,8 @@ int run_transformer(const TbParams& p, const float* in, float* out, float* ws, c
 #endif
 
     // x + attn(LN1(x)) ---------------------------------------------------------------------
-    Conv1x1Args av{};
-    int nslab = 0;
-    size_t partial_floats = 0;
-    if (!no_fuse_attn && fused_attn_supported(C, heads, hh, ww)) {
-        // LN1 -> qkv 1x1 -> depthwise 3x3 -> {Gram partials, v} in one kernel: qkv never reaches HBM
-        size_t pf;
-        RF_TRY(fused_attn_plan(hh, ww, &nslab, &pf, B, C));
-        RF_TRY(launch_attn_front(in, bufB, partial, nslab, p.ln1_w, p.ln1_b, p.qkv_wp3, p.qkv_b, p.qkv_dw_w, p.qkv_dw_b, B, C, hh, ww, st,
-                                 p.ylo, p.yhi));
-        partial_floats = pf;
-        av.x1 = bufB; av.x1_bstride = (int64_t)C * Pn;
-    } else {
-        Conv1x1Args q{};
-        q.x1 = in; q.C1 = C; q.x1_bstride = (int64_t)C * Pn;
-        q.wp = p.qkv_wp; q.wp3 = p.qkv_wp3; q.bias = p.qkv_b;
-        q.ln_w = p.ln1_w; q.ln_b = p.ln1_b; q.ln_eps = 1e-5f;
-        q.out = bufA; q.out_bstride = (int64_t)3 * C * Pn; q.Cout = 3 * C; q.B = B; q.P = Pn; q.w = ww;
-        if (!conv1x1_ln_single_pass(q)) {      // LN1 as its own pass (bufB is free until the depthwise kernel writes it)
-            RF_TRY(launch_layernorm2d(in, bufB, p.ln1_w, p.ln1_b, 1e-5f, B, C, Pn, st));
-            q.x1 = bufB; q.ln_w = nullptr; q.ln_b = nullptr;
-        }
-        RF_TRY(launch_conv1x1(q, st));
-
-        if (!no_fuse && attn_mid_supported(C, heads, hh, ww)) {
-            // depthwise 3x3 of q, k, v + Gram partials in one kernel: dw(q), dw(k) never reach HBM
-            size_t pf;
-            RF_TRY(attn_mid_plan(hh, ww, &nslab, &pf, B, C));
-            RF_TRY(launch_attn_mid(bufA, bufB, partial, nslab, p.qkv_dw_w, p.qkv_dw_b, B, C, hh, ww, st, p.ylo, p.yhi));
-            partial_floats = pf;
-            av.x1 = bufB; av.x1_bstride = (int64_t)C * Pn;
-        } else {
-        DwConvArgs d{};
-        d.x = bufA; d.x_bstride = (int64_t)3 * C * Pn; d.out = bufB; d.out_bstride = (int64_t)3 * C * Pn;
-        d.w = p.qkv_dw_w; d.bias = p.qkv_dw_b;
-        d.B = B; d.C = 3 * C; d.h = hh; d.w_ = ww; d.gelu = 0;
-        RF_TRY(launch_dwconv3x3(d, st));
-
-        GramArgs g{};
-        g.q = bufB; g.k = bufB + (size_t)C * Pn; g.bstride = (int64_t)3 * C * Pn;
-        g.B = B; g.C = C; g.heads = heads; g.P = Pn; g.partial = partial;
-        size_t pf;
-        RF_TRY(gram_plan(B, C, heads, Pn, &g.nslab, &g.slab, &pf));
-        g.p_lo = p.ylo * ww; g.p_hi = p.yhi * ww;
-        RF_TRY(launch_gram(g, st));
-        nslab = g.nslab;
-        partial_floats = pf;
-        av.x1 = bufB + (size_t)2 * C * Pn; av.x1_bstride = (int64_t)3 * C * Pn;
-        }
-    }
-    // spatial shard: every rank holds the same slab grid (equal local shapes), so the element-wise sum of the partial buffers is
-    // the partial buffer of the whole frame; the fold then sums the slabs as always
-    if (p.allreduce) p.allreduce(p.allreduce_user, partial, partial_floats, 0, (void*)st);
-    RF_TRY(launch_attn_fold(partial, nslab, p.temperature, p.proj_w, wfold, wfold3, B, C, heads, st, p.log_temperature));
-    av.C1 = C;
-    av.wp = wfold; av.wp_bstride = (int64_t)packed1x1_floats(C, C);
-    av.wp3 = wfold3; av.wp3_bstride = (int64_t)packed1x1_b3_floats(C, C);
-    av.bias = p.proj_b;
-    av.res = in; av.res_bstride = (int64_t)C * Pn;
-    av.out = x1; av.out_bstride = (int64_t)C * Pn; av.Cout = C; av.B = B; av.P = Pn; av.w = ww;
-    RF_TRY(launch_conv1x1(av, st));
+    RF_TRY(run_chan_attn(p, in, x1, true, AttnBufs{bufA, bufB, ws + o.partial, ws + o.wfold, ws + o.wfold3}, B, C, heads, hh, ww, st, no_fuse,
+                         no_fuse_attn));
 
     // x + ffn(LN2(x)) ----------------------------------------------------------------------
     if (transformer_ffn_is_fused(p, C, hc, hh, ww)) {

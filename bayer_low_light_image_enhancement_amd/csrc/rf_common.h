@@ -60,6 +60,16 @@ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// The one allocator behind every workspace / scratch layout: consecutive buffers, each rounded up to 64 floats (256-byte granules
+// keep every buffer 16-byte aligned).  off() is the offset form and take() the pointer form of the same step; with a null base
+// take() returns nullptr and `used` alone counts (the *_bytes entry points size their layouts that way).
+struct Bump {
+    float* base = nullptr;
+    size_t used = 0;
+    size_t off(size_t floats) { const size_t o = used; used += align_up(floats, 64); return o; }
+    float* take(size_t floats) { const size_t o = off(floats); return base ? base + o : nullptr; }
+};
+
 // ---------------------------------------------------------------------------------------------
 // MFMA operand packing.  All dense contractions use v_mfma_f32_16x16x4_f32:
 //   A (weights)   lane l holds A[i = l & 15][k = l >> 4]
@@ -222,6 +232,19 @@ int launch_conv3x3(const Conv3x3Args& a, hipStream_t st);
 size_t conv3x3_ksplit_floats(int B, int Cout, int h, int w);   // 0: launches of this size never split
 size_t conv3x3_ksplit_counter_bytes();
 
+// ---- named parameter groups: one struct per group, over the element type -- int: registry indices (rf_handle.h), const float*:
+// device pointers, float*: gradients.  Field order = registration order = the reference's state_dict order.
+template <class T> struct SeGroup { T se1_w, se1_b, se3_w, se3_b; };      // squeeze-excite: se.1 and se.3, weight and bias
+template <class T> struct FlcaGroup {                                     // FLCA branch of a stage
+    T alpha, beta, gamma;                 // scalars
+    T w_low, w_high, w_chr;               // low_attn.0 / high_attn.0 [C][1][3][3], chroma_attn.0 [C][2][3][3]
+    SeGroup<T> se;
+};
+typedef SeGroup<const float*> SePrm;
+typedef FlcaGroup<const float*> FlcaPrm;
+typedef FlcaGroup<float*> FlcaGrad;
+static inline int flca_hidden(int C) { return C / 8 > 8 ? C / 8 : 8; }   // width of the squeeze-excite hidden layer
+
 // ---- memory-bound ops (rf_pointwise.hip)
 int launch_layernorm2d(const float* in, float* out, const float* w, const float* b, float eps,
                        int B, int C, int P, hipStream_t st);
@@ -299,6 +322,17 @@ struct TbBufOffsets { size_t bufA, bufB, x1, partial, wfold, wfold3; };   // flo
 size_t transformer_scratch_floats(int B, int C, int heads, int hc, int h, int w, TbBufOffsets* o);
 int run_transformer(const TbParams& p, const float* in, float* out, float* ws, const TbBufOffsets& o,
                     int B, int C, int heads, int hc, int hh, int ww, hipStream_t st);
+// The attention half of the block, also the whole of rf_chan_attn:  out = [in +] W_out softmax(T q^ k^T) v + b  with
+// q, k, v = depthwise3x3(W_qkv [LN1](in)).  Reads the attention fields of `p`; p.ln1_w == nullptr: no LayerNorm (and never the
+// attn_front kernel, which has one built in).  The no_fuse switches are the diagnostic build's (run_transformer sets them).
+struct AttnBufs {
+    float *pre, *qkv;     // [B][3C][P] each: the qkv GEMM's output and the depthwise convolution's (or v alone, [B][C][P])
+    float *partial;       // Gram partials: the largest of gram_plan / fused_attn_plan / attn_mid_plan for the shape
+    float *wfold;         // [B] packed1x1_floats(C, C)
+    void* wfold3;         // [B] packed1x1_b3_floats(C, C)
+};
+int run_chan_attn(const TbParams& p, const float* in, float* out, bool residual, const AttnBufs& buf, int B, int C, int heads, int hh, int ww,
+                  hipStream_t st, bool no_fuse = false, bool no_fuse_attn = false);
 
 // ---- rfft2 / irfft2 with the polar maps of FEB (rf_fft.hip); cscratch: planes * h * (w/2 + 1) complex values
 int launch_rfft2_polar(const float* in, float* mag, float* pha, float2* cscratch, int planes, int h, int w, hipStream_t st);
@@ -321,11 +355,22 @@ int launch_tc_color_head(float* x, const float* const* prm, int B, size_t P, hip
 
 // ---- training kernels (rf_train.hip)
 size_t gram2_partial_floats(int B, int Ca, int Cb, int h, int w, int ntap);
-// partial_cap: floats available at partial (the launch needs gram2 slabs x (ntap Ca Cb + Ca when db); checked, never exceeded)
-int launch_gram2(const float* a, int64_t a_bstride, int Ca, const float* b, int64_t b_bstride, int Cb, float* out, int ld, float* partial,
-                 size_t partial_cap, int B, int h, int w, int ntap, int sy, int sx, int per_image, size_t out_istride, int accumulate, hipStream_t st,
-                 float* db = nullptr /* [Ca] (+)= row sums of a over all images and pixels: the bias gradient of the same layer */,
-                 const float* b2 = nullptr, int64_t b2_bstride = 0, int Cb2 = 0 /* input = cat(b, b2) along channels, read in place */);
+// out[(i * ld + j) * ntap + tap] (+)= sum over images and pixels of a[i][p] b[j][p + tap shift]: the weight gradient [Ca][ld >= Cb][ntap]
+// of a convolution with a = dOut and b = the layer's input
+struct Gram2Launch {
+    const float* a; int64_t a_bstride; int Ca;        // dOut  [B][Ca][h][w], floats between images
+    const float* b; int64_t b_bstride; int Cb;        // input [B][Cb][h][w]
+    const float* b2; int64_t b2_bstride; int Cb2;     // optional: the input is cat(b, b2) along channels, read in place (Cb2 = 0: none)
+    float* out; int ld;
+    size_t out_istride;                               // per_image: out[image * out_istride + ...]
+    float* partial; size_t partial_cap;               // slab partials, floats available there (slabs x (ntap Ca Cb + Ca when db): checked)
+    int B, h, w;
+    int ntap;                                         // 1, or 9 = the 3x3 window in (dy, dx) row-major order
+    bool per_image;                                   // no sum over images
+    bool accumulate;                                  // add to out (and db)
+    float* db;                                        // [Ca] (+)= row sums of a over all images and pixels: the bias gradient of the same layer; or nullptr
+};
+int launch_gram2(const Gram2Launch& g, hipStream_t st);
 int launch_reduce_rows(const float* partial, float* out, int nrows, size_t n, int accumulate, hipStream_t st);
 int chan_sum_nblk(int P);
 int launch_chan_sum(const float* x, int64_t bstride, float* out, float* partial, int B, int C, int P, int accumulate, hipStream_t st);
@@ -343,9 +388,23 @@ int launch_loss(const float* pred, const float* gt, float* grad, float* loss_out
 int launch_adam(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps, float wd, int decoupled,
                 int step, float gscale, hipStream_t st);
 
+// softmax of the forward's Gram partials and its adjoint, per (head, image): packed A and A^T, and unless fwd_only the packed M2
+// with d[q;k] = M2 [q;k] and the per-image dT partials (rf_trainstep.hip, header)
+struct AttnSmall {
+    const float* partial; int nslab;       // Gram partials of the forward (rf_attn.hip layout, kRowW = 66)
+    const float* temperature;
+    const float* dA; size_t dA_istride;    // [B][C][C]
+    float* m2; size_t m2_istride;          // packed [2C x 2C], zero-filled by the caller
+    float* at; float* ap; size_t a_istride;   // packed A^T and A [C x C], zero-filled by the caller
+    float* dT_part;                        // [B][heads]
+    int C, heads, fwd_only;
+};
+int launch_attn_small(const AttnSmall& a, int B, hipStream_t st);
+
 size_t flca_bwd_scratch_floats(int B, int C, int h, int w);
+// prm / grd: the FLCA parameters and their gradients (grd.se: four tensors adjacent in the flat gradient buffer, checked)
 int launch_flca_backward(const float* feat, const float* guide, const float* xs, const float* dz, int64_t dz_bstride, const float* ch,
-                         const float* pool_partial, int pool_nblk, const float* const* prm, float* const* grd, float* dfeat, int accumulate,
+                         const float* pool_partial, int pool_nblk, const FlcaPrm& prm, const FlcaGrad& grd, float* dfeat, int accumulate,
                          float* scratch, size_t scratch_floats, int B, int C, int h, int w, hipStream_t st);
 
 // ---- FLCA (rf_flca.hip)
@@ -361,19 +420,21 @@ struct FlcaSpatialArgs {
     float* partial;                                      // [B][nblk][C] per-block channel sums
     int B, C, h, w, nblk;
     int ylo = 0, yhi = 0;                                // rows [ylo, yhi) enter the channel sums (yhi = 0: all); see rf_set_shard
+    void set_params(const FlcaPrm& p) {                  // (the kernels take this struct by value: its layout is theirs)
+        w_low = p.w_low; w_high = p.w_high; w_chr = p.w_chr;
+        alpha = p.alpha; beta = p.beta; gamma = p.gamma;
+    }
 };
 int flca_nblk(int h, int w);
 int launch_flca_spatial(const FlcaSpatialArgs& a, hipStream_t st);
 // squeeze-excite gate only: ch_out[b][c]
-int launch_flca_se(const float* partial, int nblk, int P, const float* se1_w, const float* se1_b,
-                   const float* se3_w, const float* se3_b, int hidden, float* ch_out, int B, int C, hipStream_t st);
+int launch_flca_se(const float* partial, int nblk, int P, const SePrm& se, float* ch_out, int B, int C, hipStream_t st);
 // x[b][c][:] *= ch[b][c]   (operator-level FLCA output; the forward folds the gate into the next 1x1 instead)
 int launch_scale_channels(float* x, const float* ch, int B, int C, int P, hipStream_t st);
 int launch_scale_channels_to(const float* in, float* out, const float* ch, int B, int C, int P, hipStream_t st);   // out = in * ch (in == out allowed)
 // SE + fold into channel_reduce: wp_out[b] = pack([Wa * diag(ch_b) | Wb])
-int launch_flca_se_fold(const float* partial, int nblk, int P, const float* se1_w, const float* se1_b,
-                        const float* se3_w, const float* se3_b, int hidden, const float* w_cr,
-                        float* wp_out, void* wp3_out /* b3 form too, or nullptr */, float* ch_out, int B, int C, hipStream_t st,
+int launch_flca_se_fold(const float* partial, int nblk, int P, const SePrm& se, const float* w_cr, float* wp_out,
+                        void* wp3_out /* b3 form too, or nullptr */, float* ch_out, int B, int C, hipStream_t st,
                         const float* composed = nullptr /* pack_tail: emit [Wa diag(ch_b) | Wb | Wb W2] in b3 form only */, int hc = 0);
 // Composed stage tail (rf_model.hip run_stage): channel_reduce(cat(xs, x1 + W2 g + b2)) as ONE GEMM over [xs ; x1 ; g].
 // pack_tail writes Wb W2 ([C][hc]) and the composed bias ([C]) once per parameter load; launch_tail_fold the b3 weights.

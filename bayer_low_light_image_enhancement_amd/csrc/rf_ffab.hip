@@ -14,16 +14,6 @@ namespace rf {
 
 namespace {
 
-struct Bump {
-    float* base;
-    size_t off = 0;
-    float* take(size_t floats) {
-        float* p = base ? base + off : nullptr;
-        off += align_up(floats, 64);
-        return p;
-    }
-};
-
 // one nn.Conv2d(cin, cout, 1) on [B, cin, P] planes with raw weights (packed on the fly into `wpack`)
 int conv1x1_raw(const float* x, float* out, const float* w, const float* bias, const float* res, float* wpack, int B, int cin, int cout,
                 int P, int act, hipStream_t st) {
@@ -43,27 +33,33 @@ size_t feb_plan(Bump& b, FebBufs& f, int B, int nc, int h, int w) {
     f.mag = b.take(Uf); f.pha = b.take(Uf); f.t = b.take(Uf); f.mag2 = b.take(Uf); f.pha2 = b.take(Uf);
     f.cplx = reinterpret_cast<float2*>(b.take(2 * Uf));
     f.wpack = b.take(packed1x1_floats(nc, nc));
-    return b.off;
+    return b.used;
 }
 
-// prm: fpre.{w,b}, process1.0.{w,b}, process1.2.{w,b}, process2.0.{w,b}, process2.2.{w,b}
-int feb_forward(const float* x, float* out, const float* const* prm, const FebBufs& f, int B, int nc, int h, int w, hipStream_t st) {
+// the public entry points' `prm` arrays, unpacked once (state_dict order): FEB = fpre, process1.0 / .2 (magnitude), process2.0 / .2
+// (phase), weight and bias each; a ProcessBlock = its FEB, then cat
+struct FebPrm { const float *fpre_w, *fpre_b, *mag0_w, *mag0_b, *mag2_w, *mag2_b, *pha0_w, *pha0_b, *pha2_w, *pha2_b; };
+struct BlockPrm { FebPrm feb; const float *cat_w, *cat_b; };
+FebPrm feb_prm(const float* const* q) { return {q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8], q[9]}; }
+BlockPrm block_prm(const float* const* q) { return {feb_prm(q), q[10], q[11]}; }
+
+int feb_forward(const float* x, float* out, const FebPrm& p, const FebBufs& f, int B, int nc, int h, int w, hipStream_t st) {
     const int P = h * w, Pf = h * (w / 2 + 1);
     RF_TRY(launch_clamp(x, f.xc, (size_t)B * nc * P, -10.f, 10.f, st));
-    RF_TRY(conv1x1_raw(f.xc, f.y, prm[0], prm[1], nullptr, f.wpack, B, nc, nc, P, 0, st));
+    RF_TRY(conv1x1_raw(f.xc, f.y, p.fpre_w, p.fpre_b, nullptr, f.wpack, B, nc, nc, P, 0, st));
     RF_TRY(launch_rfft2_polar(f.y, f.mag, f.pha, f.cplx, B * nc, h, w, st));
-    RF_TRY(conv1x1_raw(f.mag, f.t, prm[2], prm[3], nullptr, f.wpack, B, nc, nc, Pf, 3, st));
-    RF_TRY(conv1x1_raw(f.t, f.mag2, prm[4], prm[5], nullptr, f.wpack, B, nc, nc, Pf, 4, st));
-    RF_TRY(conv1x1_raw(f.pha, f.t, prm[6], prm[7], nullptr, f.wpack, B, nc, nc, Pf, 3, st));
-    RF_TRY(conv1x1_raw(f.t, f.pha2, prm[8], prm[9], nullptr, f.wpack, B, nc, nc, Pf, 0, st));
+    RF_TRY(conv1x1_raw(f.mag, f.t, p.mag0_w, p.mag0_b, nullptr, f.wpack, B, nc, nc, Pf, 3, st));
+    RF_TRY(conv1x1_raw(f.t, f.mag2, p.mag2_w, p.mag2_b, nullptr, f.wpack, B, nc, nc, Pf, 4, st));
+    RF_TRY(conv1x1_raw(f.pha, f.t, p.pha0_w, p.pha0_b, nullptr, f.wpack, B, nc, nc, Pf, 3, st));
+    RF_TRY(conv1x1_raw(f.t, f.pha2, p.pha2_w, p.pha2_b, nullptr, f.wpack, B, nc, nc, Pf, 0, st));
     return launch_polar_irfft2(f.mag2, f.pha2, f.xc, out, f.cplx, B * nc, h, w, 10.f, st);
 }
 
-// prm: the 10 FEB tensors, then cat.{w,b};  out = cat(FEB(x)) + x   (out may not alias x)
-int process_block_forward(const float* x, float* out, const float* const* prm, const FebBufs& f, float* feb_out, int B, int nc, int h, int w,
+// out = cat(FEB(x)) + x   (out may not alias x)
+int process_block_forward(const float* x, float* out, const BlockPrm& p, const FebBufs& f, float* feb_out, int B, int nc, int h, int w,
                           hipStream_t st) {
-    RF_TRY(feb_forward(x, feb_out, prm, f, B, nc, h, w, st));
-    return conv1x1_raw(feb_out, out, prm[10], prm[11], x, f.wpack, B, nc, nc, h * w, 0, st);
+    RF_TRY(feb_forward(x, feb_out, p.feb, f, B, nc, h, w, st));
+    return conv1x1_raw(feb_out, out, p.cat_w, p.cat_b, x, f.wpack, B, nc, nc, h * w, 0, st);
 }
 
 int check_geometry(const char* what, int B, int nc, int h, int w) {
@@ -82,7 +78,7 @@ void ffab_plan(float* base, FfabPlan& p, int B, int nc, int h, int w) {
     p.wpack2 = b.take(packed1x1_floats(2 * nc, 2 * nc));
     feb_plan(b, p.f, B, 2 * nc, h, w);
     p.f.wpack = p.wpack2;
-    p.total = b.off;
+    p.total = b.used;
 }
 
 // torch.cat((a, b), dim=1) for [B, nc, P] planes
@@ -147,7 +143,7 @@ int rf_feb(const float* in, float* out, const float* const* prm, void* scratch, 
     Bump b{(float*)scratch};
     FebBufs f;
     feb_plan(b, f, B, nc, h, w);
-    return feb_forward(in, out, prm, f, B, nc, h, w, (hipStream_t)stream);
+    return feb_forward(in, out, feb_prm(prm), f, B, nc, h, w, (hipStream_t)stream);
 }
 
 int rf_affine_clamp_add(const float* in, const float* add, float* out, size_t n, float scale, float shift, float lo, float hi, void* stream) {
@@ -176,21 +172,25 @@ int rf_ffab(const float* in, float* out, const float* const* prm, void* scratch,
     const int P = h * w;
     const size_t per = (size_t)nc * P;
     // state_dict order: conv0.0.{w,b}, conv0.1.<12>, conv1.<12>, conv2.<12>, conv3.<12>, conv4.0.<12>, conv4.1.{w,b},
-    //                   conv5.0.<12>, conv5.1.{w,b}, convout.0.<12>, convout.1.{w,b}
-    const float* const* q = prm;
-    RF_TRY(conv1x1_raw(in, p.pb, q[0], q[1], nullptr, p.wpack2, B, nc, nc, P, 0, st));
-    RF_TRY(process_block_forward(p.pb, p.x, q + 2, p.f, p.feb_out, B, nc, h, w, st));
-    RF_TRY(process_block_forward(p.x, p.x1, q + 14, p.f, p.feb_out, B, nc, h, w, st));
-    RF_TRY(process_block_forward(p.x1, p.x2, q + 26, p.f, p.feb_out, B, nc, h, w, st));
-    RF_TRY(process_block_forward(p.x2, p.x3, q + 38, p.f, p.feb_out, B, nc, h, w, st));
-    auto tail = [&](const float* a, const float* b, const float* const* pp, float* dst) -> int {
+    //                   conv5.0.<12>, conv5.1.{w,b}, convout.0.<12>, convout.1.{w,b}     (<12> = one ProcessBlock)
+    struct Tail { BlockPrm block; const float *w, *b; };      // conv4 / conv5 / convout: ProcessBlock(2 nc), then 1x1 back to nc
+    auto tail_prm = [](const float* const* q) { return Tail{block_prm(q), q[12], q[13]}; };
+    const float *conv0_w = prm[0], *conv0_b = prm[1];
+    const BlockPrm conv0 = block_prm(prm + 2), conv1 = block_prm(prm + 14), conv2 = block_prm(prm + 26), conv3 = block_prm(prm + 38);
+    const Tail conv4 = tail_prm(prm + 50), conv5 = tail_prm(prm + 64), convout = tail_prm(prm + 78);
+    RF_TRY(conv1x1_raw(in, p.pb, conv0_w, conv0_b, nullptr, p.wpack2, B, nc, nc, P, 0, st));
+    RF_TRY(process_block_forward(p.pb, p.x, conv0, p.f, p.feb_out, B, nc, h, w, st));
+    RF_TRY(process_block_forward(p.x, p.x1, conv1, p.f, p.feb_out, B, nc, h, w, st));
+    RF_TRY(process_block_forward(p.x1, p.x2, conv2, p.f, p.feb_out, B, nc, h, w, st));
+    RF_TRY(process_block_forward(p.x2, p.x3, conv3, p.f, p.feb_out, B, nc, h, w, st));
+    auto tail = [&](const float* a, const float* b, const Tail& t, float* dst) -> int {
         RF_TRY(launch_cat2(a, b, p.cat, B, per, st));
-        RF_TRY(process_block_forward(p.cat, p.pb, pp, p.f, p.feb_out, B, 2 * nc, h, w, st));
-        return conv1x1_raw(p.pb, dst, pp[12], pp[13], nullptr, p.wpack2, B, 2 * nc, nc, P, 0, st);
+        RF_TRY(process_block_forward(p.cat, p.pb, t.block, p.f, p.feb_out, B, 2 * nc, h, w, st));
+        return conv1x1_raw(p.pb, dst, t.w, t.b, nullptr, p.wpack2, B, 2 * nc, nc, P, 0, st);
     };
-    RF_TRY(tail(p.x2, p.x3, q + 50, p.x4));
-    RF_TRY(tail(p.x1, p.x4, q + 64, p.x5));
-    return tail(p.x, p.x5, q + 78, out);
+    RF_TRY(tail(p.x2, p.x3, conv4, p.x4));
+    RF_TRY(tail(p.x1, p.x4, conv5, p.x5));
+    return tail(p.x, p.x5, convout, out);
 }
 
 }  // extern "C"

@@ -440,10 +440,10 @@ int launch_tail_fold(const float* w_cr, const float* ch, const float* composed, 
     return check_launch("tail_fold");
 }
 
-int launch_flca_se(const float* partial, int nblk, int P, const float* se1_w, const float* se1_b,
-                   const float* se3_w, const float* se3_b, int hidden, float* ch_out, int B, int C, hipStream_t st) {
+int launch_flca_se(const float* partial, int nblk, int P, const SePrm& se, float* ch_out, int B, int C, hipStream_t st) {
+    const int hidden = flca_hidden(C);
     RF_CHECK_ARG(C <= 512 && hidden <= 64 && C % 8 == 0 && ch_out, "flca_se: C=%d hidden=%d unsupported", C, hidden);
-    flca_se_kernel<<<B, 256, 0, st>>>(partial, nblk, P, se1_w, se1_b, se3_w, se3_b, hidden, ch_out, C);
+    flca_se_kernel<<<B, 256, 0, st>>>(partial, nblk, P, se.se1_w, se.se1_b, se.se3_w, se.se3_b, hidden, ch_out, C);
     return check_launch("flca_se");
 }
 
@@ -475,11 +475,10 @@ int launch_scale_channels_to(const float* in, float* out, const float* ch, int B
 }
 int launch_scale_channels(float* x, const float* ch, int B, int C, int P, hipStream_t st) { return launch_scale_channels_to(x, x, ch, B, C, P, st); }
 
-int launch_flca_se_fold(const float* partial, int nblk, int P, const float* se1_w, const float* se1_b,
-                        const float* se3_w, const float* se3_b, int hidden, const float* w_cr,
-                        float* wp_out, void* wp3_out, float* ch_out, int B, int C, hipStream_t st, const float* composed, int hc) {
+int launch_flca_se_fold(const float* partial, int nblk, int P, const SePrm& se, const float* w_cr, float* wp_out, void* wp3_out, float* ch_out,
+                        int B, int C, hipStream_t st, const float* composed, int hc) {
     ProfScope prof(st, "flca_se_kernel+flca_fold_kernel", 0.0, 0.0);
-    const int rc = launch_flca_se(partial, nblk, P, se1_w, se1_b, se3_w, se3_b, hidden, ch_out, B, C, st);
+    const int rc = launch_flca_se(partial, nblk, P, se, ch_out, B, C, st);
     if (rc) return rc;
     if (composed) return launch_tail_fold(w_cr, ch_out, composed, wp3_out, B, C, hc, st);
     flca_fold_kernel<<<dim3((unsigned)fold_grid(C, 2 * C), (unsigned)B), 256, 0, st>>>(w_cr, ch_out, nullptr, wp_out, (unsigned short*)wp3_out, C, 0);

@@ -81,88 +81,8 @@ __device__ __forceinline__ GroupGeom group_geom(int wave, int st, int j, int y0,
     return g;
 }
 
-// Input tile of one step: raw loads (issue early: the registers are dead between a tile's last
-// phase A and the next tile's first one, so the next tile is fetched behind the current phase B) ...
-template <int C>
-__device__ __forceinline__ void load_step(const float* __restrict__ xb, int P, int kq, const GroupGeom& g, float4 (&xh)[C / 4]) {
-    const unsigned voff = (unsigned)kq * (unsigned)P + (unsigned)g.goff;
-#pragma unroll
-    for (int s = 0; s < C / 4; ++s) xh[s] = *reinterpret_cast<const float4*>(xb + (size_t)(4 * s) * P + voff);
-}
-
-// ... and the exact two-pass LayerNorm over channels, in place: xh[s] = LN(x)[channel 4s + kq][4 px].
-template <int C>
-__device__ __forceinline__ void ln_step(int kq, const float* __restrict__ gam_l, const float* __restrict__ bet_l,
-                                        float eps, float4 (&xh)[C / 4]) {
-    constexpr int NS = C / 4;
-    float sum[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < NS; ++s) { sum[0] += xh[s].x; sum[1] += xh[s].y; sum[2] += xh[s].z; sum[3] += xh[s].w; }
-    float mu[4], var[4] = {0.f, 0.f, 0.f, 0.f}, rstd[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        sum[q] += __shfl_xor(sum[q], 16);
-        sum[q] += __shfl_xor(sum[q], 32);
-        mu[q] = sum[q] * (1.0f / C);
-    }
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        const float d0 = xh[s].x - mu[0], d1 = xh[s].y - mu[1], d2 = xh[s].z - mu[2], d3 = xh[s].w - mu[3];
-        var[0] = fmaf(d0, d0, var[0]); var[1] = fmaf(d1, d1, var[1]);
-        var[2] = fmaf(d2, d2, var[2]); var[3] = fmaf(d3, d3, var[3]);
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        var[q] += __shfl_xor(var[q], 16);
-        var[q] += __shfl_xor(var[q], 32);
-        rstd[q] = 1.0f / sqrtf(var[q] * (1.0f / C) + eps);
-    }
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        const float gk = gam_l[4 * s + kq], bk = bet_l[4 * s + kq];
-        xh[s].x = fmaf((xh[s].x - mu[0]) * rstd[0], gk, bk);
-        xh[s].y = fmaf((xh[s].y - mu[1]) * rstd[1], gk, bk);
-        xh[s].z = fmaf((xh[s].z - mu[2]) * rstd[2], gk, bk);
-        xh[s].w = fmaf((xh[s].w - mu[3]) * rstd[3], gk, bk);
-    }
-}
-
-// One phase-A step: 2 output tiles (32 intermediate channels) of the 1x1 GEMM, written to the LDS
-// plane array `mid` (plane stride PS) with bias; groups outside the image are written as zeros.
-template <int C, int WT>
-__device__ __forceinline__ void phase_a_step(const float4 (&xh)[C / 4], const float* __restrict__ wl /* [C/4][WT][64] + lane */,
-                                             int tile0, int tile1, const float* __restrict__ bias0, const float* __restrict__ bias1,
-                                             float* __restrict__ mid, int PS, int kq, const GroupGeom& g) {
-    f32x4 acc[2][4];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[t][q] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const float* w0 = wl + tile0 * 64;
-    const float* w1 = wl + tile1 * 64;
-#pragma unroll
-    for (int s = 0; s < C / 4; ++s) {
-        const float xb[4] = {xh[s].x, xh[s].y, xh[s].z, xh[s].w};
-        const float a0 = w0[s * WT * 64], a1 = w1[s * WT * 64];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[0][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, xb[q], acc[0][q], 0, 0, 0);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[1][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, xb[q], acc[1][q], 0, 0, 0);
-    }
-    if (g.lds_off >= 0) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float bs = (t ? bias1 : bias0)[4 * kq + r];
-                float4 v = make_float4(acc[t][0][r] + bs, acc[t][1][r] + bs, acc[t][2][r] + bs, acc[t][3][r] + bs);
-                if (!g.valid) v = make_float4(0.f, 0.f, 0.f, 0.f);
-                *reinterpret_cast<float4*>(mid + (16 * t + 4 * kq + r) * PS + g.lds_off) = v;
-            }
-    }
-}
-
-// ---- b3 forms of the phase-A helpers (rf_common.h): lane (j, kq) holds channels 32 kb + 8 kq + i, i = 0..7 ------------------
+// ---- phase-A helpers in b3 form (rf_common.h): lane (j, kq) holds channels 32 kb + 8 kq + i, i = 0..7 ------------------------
+// Input tile of one step: raw loads (issue early: the next tile is fetched behind the current phase B) ...
 template <int C>
 __device__ __forceinline__ void load_step_b3(const float* __restrict__ xb, int P, int kq, const GroupGeom& g, float4 (&xh)[C / 4]) {
     const unsigned voff = (unsigned)(8 * kq) * (unsigned)P + (unsigned)g.goff;
@@ -170,6 +90,7 @@ __device__ __forceinline__ void load_step_b3(const float* __restrict__ xb, int P
     for (int s = 0; s < C / 4; ++s) xh[s] = *reinterpret_cast<const float4*>(xb + (size_t)(32 * (s >> 3) + (s & 7)) * P + voff);
 }
 
+// ... and the exact two-pass LayerNorm over channels, in place.
 template <int C>
 __device__ __forceinline__ void ln_step_b3(int kq, const float* __restrict__ gam_l, const float* __restrict__ bet_l, float eps, float4 (&xh)[C / 4]) {
     constexpr int NS = C / 4;

@@ -1,7 +1,8 @@
 // The RawFormer handle (internal): parameter registry, packed-weight plans and the index table that the forward schedule
 // (rf_model.hip) and the training schedule (rf_trainstep.hip) read.  rf_create registers every tensor by name once (add_param)
 // and records its registry index where the schedules need it: per Conv_Transformer stage in `stage[1..7]`, per other module in
-// the fields below.  The schedules take pointers through those indices (prm / pk / pk3); names serve rf_set_param and
+// the fields below; a group of parameters that travels together (FLCA, the TrueColor modules) is one struct with a named field
+// per tensor.  The schedules take pointers through those indices (prm / pk / pk3 / flca_prm); names serve rf_set_param and
 // rf_param_info only.
 #pragma once
 #include <string>
@@ -42,6 +43,15 @@ struct CachePack {   // one weight form of the training pack cache: `d` without 
     rf::PackDesc d;
 };
 
+// registry indices of the TrueColor parameter groups, in registration order (the FLCA group and SeGroup: rf_common.h)
+struct TcIx {        // EnhancedFLCA branch of a stage: weight and bias of color_attention.0, low_attn.0, high_attn.0, se, res_proj.0 / .2
+    int col_w, col_b, low_w, low_b, high_w, high_b;
+    rf::SeGroup<int> se;
+    int res0_w, res0_b, res2_w, res2_b;
+};
+struct BayerProcIx { int wb_gains, color_matrix, dm0_w, dm0_b, dm2_w, dm2_b, ce0_w, ce0_b, ce2_w, ce2_b; };   // bayer_processor.*: demosaic_refine.0 / .2, chroma_extractor.0 / .2
+struct ColorCorrIx { int gamma, ct0_w, ct0_b, ct2_w, ct2_b, tone0_w, tone0_b, tone2_w, tone2_b; };             // color_correction.*: color_transform.0 / .2, tone_curve.0 / .2
+
 // registry indices of one Conv_Transformer stage (add_stage)
 struct StageIx {
     int lvl;         // U-Net level: channels dim << lvl, size H >> lvl
@@ -50,8 +60,8 @@ struct StageIx {
     int ln2_w, ln2_b, pw1_w, pw1_b, dw_w, dw_b, pw2_w, pw2_b;
     int cr_w, cr_b, out_w, out_b;     // channel_reduce, Conv_out
     int conv_w, conv_b;               // plain branch
-    int flca[10];    // FLCA branch, registry order = launch_flca_backward's: alpha, beta, gamma, low / high / chroma gate, se.1 w, b, se.3 w, b
-    int tc[14];      // TrueColor branch, registry order: weight and bias of color_attention, low_attn, high_attn, se.1, se.3, res_proj.0, .2
+    rf::FlcaGroup<int> flca;            // FLCA branch
+    TcIx tc;                          // TrueColor branch
     // composed tail (rf_flca.hip pack_tail), floats into the packed buffer of [Wb W2 | b'] (0 = not composed) and, plain variant
     // only, of the static b3 weights [Wa | Wb | Wb W2]
     size_t tail_offset = 0, tail3_offset = 0;
@@ -94,7 +104,8 @@ struct rf_handle {
     StageIx stage[8];                // 1..7
     int embedding_w, embedding_b, conv_out_w, conv_out_b;
     int down_w[3], up_w[3], up_b[3], upcr_w[3], upcr_b[3];   // down<i>, up<i>, channel_reduce<i> at [i - 1]
-    int bp[10], cc[9];               // TrueColor: bayer_processor.* and color_correction.*, registry order
+    BayerProcIx bp;                  // TrueColor: bayer_processor.*
+    ColorCorrIx cc;                  //            color_correction.*
     size_t upcat_offset[3] = {0, 0, 0};   // composed decoder-step weights (rf_upcat.hip), floats into the packed buffer
     // training (plan_training): float offset of every parameter in the flat parameter / gradient buffers; the gradient ranges in
     // the order the step announces them; the pack cache's forms in the order it writes them
@@ -118,6 +129,10 @@ struct rf_handle {
     const float* prm(int ix) const { return params[ix].ptr; }
     const float* pk(int ix) const { return packed + packs[params[ix].pack].offset; }
     const float* pk3(int ix) const { return packed + packs[params[ix].pack3].offset; }
+    rf::SePrm se_prm(const rf::SeGroup<int>& x) const { return {prm(x.se1_w), prm(x.se1_b), prm(x.se3_w), prm(x.se3_b)}; }
+    rf::FlcaPrm flca_prm(const rf::FlcaGroup<int>& x) const {
+        return {prm(x.alpha), prm(x.beta), prm(x.gamma), prm(x.w_low), prm(x.w_high), prm(x.w_chr), se_prm(x.se)};
+    }
 };
 
 // rf_trainstep.hip: lay out the flat buffers, the gradient ranges and the pack cache (rf_create, once the registry is complete)

@@ -57,38 +57,38 @@ void add_stage(rf_handle* h, int i, int lvl) {
     if (cfg.variant == RF_VARIANT_TRUECOLOR) {
         // EnhancedFLCA (BayerTORGBColorMultiLvl.py:192-231), state_dict order
         const std::string f = pre + "FLCA.";
-        const int hid = C / 8 > 8 ? C / 8 : 8;
-        s.tc[0] = add_param(h, f + "color_attention.0.weight", {C, 5, 3, 3});
-        s.tc[1] = add_param(h, f + "color_attention.0.bias", {C});
-        s.tc[2] = add_param(h, f + "low_attn.0.weight", {C, 1, 3, 3});
-        s.tc[3] = add_param(h, f + "low_attn.0.bias", {C});
-        s.tc[4] = add_param(h, f + "high_attn.0.weight", {C, 1, 3, 3});
-        s.tc[5] = add_param(h, f + "high_attn.0.bias", {C});
-        s.tc[6] = add_param(h, f + "se.1.weight", {hid, C, 1, 1});
-        s.tc[7] = add_param(h, f + "se.1.bias", {hid});
-        s.tc[8] = add_param(h, f + "se.3.weight", {C, hid, 1, 1});
-        s.tc[9] = add_param(h, f + "se.3.bias", {C});
-        s.tc[10] = add_param(h, f + "res_proj.0.weight", {C, C, 1, 1});
-        s.tc[11] = add_param(h, f + "res_proj.0.bias", {C});
-        s.tc[12] = add_param(h, f + "res_proj.2.weight", {C, C, 1, 1});
-        s.tc[13] = add_param(h, f + "res_proj.2.bias", {C});
-        for (int k : {10, 12}) {
-            add_pack(h, s.tc[k], PK_1x1);
-            add_pack(h, s.tc[k], PK_1x1_B3);
+        const int hid = flca_hidden(C);
+        s.tc.col_w = add_param(h, f + "color_attention.0.weight", {C, 5, 3, 3});
+        s.tc.col_b = add_param(h, f + "color_attention.0.bias", {C});
+        s.tc.low_w = add_param(h, f + "low_attn.0.weight", {C, 1, 3, 3});
+        s.tc.low_b = add_param(h, f + "low_attn.0.bias", {C});
+        s.tc.high_w = add_param(h, f + "high_attn.0.weight", {C, 1, 3, 3});
+        s.tc.high_b = add_param(h, f + "high_attn.0.bias", {C});
+        s.tc.se.se1_w = add_param(h, f + "se.1.weight", {hid, C, 1, 1});
+        s.tc.se.se1_b = add_param(h, f + "se.1.bias", {hid});
+        s.tc.se.se3_w = add_param(h, f + "se.3.weight", {C, hid, 1, 1});
+        s.tc.se.se3_b = add_param(h, f + "se.3.bias", {C});
+        s.tc.res0_w = add_param(h, f + "res_proj.0.weight", {C, C, 1, 1});
+        s.tc.res0_b = add_param(h, f + "res_proj.0.bias", {C});
+        s.tc.res2_w = add_param(h, f + "res_proj.2.weight", {C, C, 1, 1});
+        s.tc.res2_b = add_param(h, f + "res_proj.2.bias", {C});
+        for (int w : {s.tc.res0_w, s.tc.res2_w}) {
+            add_pack(h, w, PK_1x1);
+            add_pack(h, w, PK_1x1_B3);
         }
     } else if (cfg.variant == RF_VARIANT_FLCA) {
         const std::string f = pre + "FLCA.";
-        const int hid = C / 8 > 8 ? C / 8 : 8;
-        s.flca[0] = add_param(h, f + "alpha", {});
-        s.flca[1] = add_param(h, f + "beta", {});
-        s.flca[2] = add_param(h, f + "gamma", {});
-        s.flca[3] = add_param(h, f + "low_attn.0.weight", {C, 1, 3, 3});
-        s.flca[4] = add_param(h, f + "high_attn.0.weight", {C, 1, 3, 3});
-        s.flca[5] = add_param(h, f + "chroma_attn.0.weight", {C, 2, 3, 3});
-        s.flca[6] = add_param(h, f + "se.1.weight", {hid, C, 1, 1});
-        s.flca[7] = add_param(h, f + "se.1.bias", {hid});
-        s.flca[8] = add_param(h, f + "se.3.weight", {C, hid, 1, 1});
-        s.flca[9] = add_param(h, f + "se.3.bias", {C});
+        const int hid = flca_hidden(C);
+        s.flca.alpha = add_param(h, f + "alpha", {});
+        s.flca.beta = add_param(h, f + "beta", {});
+        s.flca.gamma = add_param(h, f + "gamma", {});
+        s.flca.w_low = add_param(h, f + "low_attn.0.weight", {C, 1, 3, 3});
+        s.flca.w_high = add_param(h, f + "high_attn.0.weight", {C, 1, 3, 3});
+        s.flca.w_chr = add_param(h, f + "chroma_attn.0.weight", {C, 2, 3, 3});
+        s.flca.se.se1_w = add_param(h, f + "se.1.weight", {hid, C, 1, 1});
+        s.flca.se.se1_b = add_param(h, f + "se.1.bias", {hid});
+        s.flca.se.se3_w = add_param(h, f + "se.3.weight", {C, hid, 1, 1});
+        s.flca.se.se3_b = add_param(h, f + "se.3.bias", {C});
     } else {
         s.conv_w = add_param(h, pre + "conv.weight", {C, C, 3, 3});
         s.conv_b = add_param(h, pre + "conv.bias", {C});
@@ -136,18 +136,12 @@ void add_stage(rf_handle* h, int i, int lvl) {
 
 // ---- workspace plan ---------------------------------------------------------------------
 struct Plan {
-    size_t total = 0;
+    size_t total;
     size_t gscratch, guide[4], skip[3], tA, tB, tU, bufA, bufB, x1, trans, xs, cr;
     size_t gram_partial, wfold_attn, wfold_cr, wfold_attn3, wfold_cr3, flca_partial, ch;
     size_t ks, ks_floats;       // scratch of the 3x3 convs' input-channel split (small frames only: ks_floats = 0 otherwise)
     int guide_planes;
 };
-
-size_t take(Plan& p, size_t floats) {
-    const size_t off = p.total;
-    p.total += align_up(floats, 64);   // 256-byte granules keep every buffer 16-byte aligned
-    return off;
-}
 
 int make_plan(const rf_handle* h, int B, int H, int W, Plan& p) {
     const rf_config& c = h->cfg;
@@ -155,20 +149,21 @@ int make_plan(const rf_handle* h, int B, int H, int W, Plan& p) {
     const bool tc = c.variant == RF_VARIANT_TRUECOLOR;
     const int levels = c.flca_levels > 0 ? c.flca_levels : 2;
     p.guide_planes = tc ? 7 : 4;
-    p.gscratch = take(p, tc ? tc_front_scratch_floats(B, H, W, levels) : guidance_scratch_floats(B, H, W));
-    for (int l = 0; l < 4; ++l) p.guide[l] = take(p, (size_t)B * p.guide_planes * (H >> l) * (W >> l));
-    for (int l = 0; l < 3; ++l) p.skip[l] = take(p, U0 >> l);
-    p.tA = take(p, U0);
-    p.tB = take(p, U0);
-    p.tU = take(p, U0);
+    Bump b;      // offsets into the caller's workspace
+    p.gscratch = b.off(tc ? tc_front_scratch_floats(B, H, W, levels) : guidance_scratch_floats(B, H, W));
+    for (int l = 0; l < 4; ++l) p.guide[l] = b.off((size_t)B * p.guide_planes * (H >> l) * (W >> l));
+    for (int l = 0; l < 3; ++l) p.skip[l] = b.off(U0 >> l);
+    p.tA = b.off(U0);
+    p.tB = b.off(U0);
+    p.tU = b.off(U0);
     // widest TransformerBlock intermediate: qkv (3C) or the FFN hidden tensor (ffn_expansion * C) on the op-by-op path
     const size_t wide = (size_t)(c.ffn_expansion > 3 ? c.ffn_expansion : 3);
-    p.bufA = take(p, wide * U0);
-    p.bufB = take(p, wide * U0);
-    p.x1 = take(p, U0);
-    p.trans = take(p, U0);
-    p.xs = take(p, U0);
-    p.cr = take(p, U0);
+    p.bufA = b.off(wide * U0);
+    p.bufB = b.off(wide * U0);
+    p.x1 = b.off(U0);
+    p.trans = b.off(U0);
+    p.xs = b.off(U0);
+    p.cr = b.off(U0);
     size_t gp = 0, wa = 0, wc = 0, fp = 0, wa3 = 0, wc3 = 0;
     for (int l = 0; l < 4; ++l) {
         const int C = c.dim << l, Pl = (H >> l) * (W >> l);
@@ -198,19 +193,20 @@ int make_plan(const rf_handle* h, int B, int H, int W, Plan& p) {
         const size_t f = (size_t)B * (tc ? tc_nblk(H >> l, W >> l) : flca_nblk(H >> l, W >> l)) * C;
         if (f > fp) fp = f;
     }
-    p.gram_partial = take(p, gp);
-    p.wfold_attn = take(p, wa);
-    p.wfold_cr = take(p, wc);
-    p.wfold_attn3 = take(p, wa3);
-    p.wfold_cr3 = take(p, wc3);
-    p.flca_partial = take(p, fp);
-    p.ch = take(p, (size_t)B * (c.dim << 3));
+    p.gram_partial = b.off(gp);
+    p.wfold_attn = b.off(wa);
+    p.wfold_cr = b.off(wc);
+    p.wfold_attn3 = b.off(wa3);
+    p.wfold_cr3 = b.off(wc3);
+    p.flca_partial = b.off(fp);
+    p.ch = b.off((size_t)B * (c.dim << 3));
     p.ks_floats = 0;
     for (int l = 0; l < 4; ++l) {
         const size_t f = conv3x3_ksplit_floats(B, c.dim << l, H >> l, W >> l);
         if (f > p.ks_floats) p.ks_floats = f;
     }
-    p.ks = take(p, p.ks_floats);
+    p.ks = b.off(p.ks_floats);
+    p.total = b.used;
     return RF_OK;
 }
 
@@ -266,36 +262,33 @@ int run_stage(rf_handle* h, int i, const float* in, float* out, float* ws, const
     if (cfg.variant == RF_VARIANT_TRUECOLOR) {
         // EnhancedFLCA (BayerTORGBColorMultiLvl.py:249-293): spatial gate -> x + 0.2 tanh(res_proj(x)) -> squeeze-excite (folded
         // into channel_reduce like the FLCA variant's)
-        const int* b = x.tc;   // registry order (StageIx)
-        RF_TRY(launch_tc_spatial(in, xs, ws + p.guide[lvl], h->prm(b[0]), h->prm(b[1]), h->prm(b[2]), h->prm(b[3]), h->prm(b[4]), h->prm(b[5]),
-                                 B, C, hh, ww, st));
+        const TcIx& t = x.tc;
+        RF_TRY(launch_tc_spatial(in, xs, ws + p.guide[lvl], h->prm(t.col_w), h->prm(t.col_b), h->prm(t.low_w), h->prm(t.low_b), h->prm(t.high_w),
+                                 h->prm(t.high_b), B, C, hh, ww, st));
         Conv1x1Args r0{};
-        r0.x1 = xs; r0.C1 = C; r0.x1_bstride = (int64_t)C * Pn; r0.wp = h->pk(b[10]); r0.wp3 = h->pk3(b[10]);
-        r0.bias = h->prm(b[11]); r0.out = crb; r0.out_bstride = (int64_t)C * Pn; r0.Cout = C; r0.B = B; r0.P = Pn; r0.w = ww; r0.act = 2;
+        r0.x1 = xs; r0.C1 = C; r0.x1_bstride = (int64_t)C * Pn; r0.wp = h->pk(t.res0_w); r0.wp3 = h->pk3(t.res0_w);
+        r0.bias = h->prm(t.res0_b); r0.out = crb; r0.out_bstride = (int64_t)C * Pn; r0.Cout = C; r0.B = B; r0.P = Pn; r0.w = ww; r0.act = 2;
         RF_TRY(launch_conv1x1(r0, st));
         Conv1x1Args r2 = r0;
-        r2.x1 = crb; r2.wp = h->pk(b[12]); r2.wp3 = h->pk3(b[12]); r2.bias = h->prm(b[13]);
+        r2.x1 = crb; r2.wp = h->pk(t.res2_w); r2.wp3 = h->pk3(t.res2_w); r2.bias = h->prm(t.res2_b);
         r2.out = ws + p.bufA; r2.act = 0;
         RF_TRY(launch_conv1x1(r2, st));
         RF_TRY(launch_tc_residual(xs, ws + p.bufA, xs, ws + p.flca_partial, B, C, hh, ww, st));
-        const int hid = C / 8 > 8 ? C / 8 : 8;
-        RF_TRY(launch_flca_se_fold(ws + p.flca_partial, tc_nblk(hh, ww), Pn, h->prm(b[6]), h->prm(b[7]), h->prm(b[8]), h->prm(b[9]), hid,
-                                   h->prm(x.cr_w), ws + p.wfold_cr, ws + p.wfold_cr3, ws + p.ch, B, C, st, composed, hc));
+        RF_TRY(launch_flca_se_fold(ws + p.flca_partial, tc_nblk(hh, ww), Pn, h->se_prm(t.se), h->prm(x.cr_w), ws + p.wfold_cr, ws + p.wfold_cr3,
+                                   ws + p.ch, B, C, st, composed, hc));
         r.wp = ws + p.wfold_cr; r.wp_bstride = (int64_t)packed1x1_floats(2 * C, C);
         r.wp3 = ws + p.wfold_cr3; r.wp3_bstride = (int64_t)packed1x1_b3_floats(compose ? 2 * C + hc : 2 * C, C);
     } else if (cfg.variant == RF_VARIANT_FLCA) {
-        const int* b = x.flca;   // registry order (StageIx)
+        const FlcaPrm fp = h->flca_prm(x.flca);
         FlcaSpatialArgs s{};
         s.feat = in; s.xs = xs; s.guide = ws + p.guide[lvl];
-        s.w_low = h->prm(b[3]); s.w_high = h->prm(b[4]); s.w_chr = h->prm(b[5]);
-        s.alpha = h->prm(b[0]); s.beta = h->prm(b[1]); s.gamma = h->prm(b[2]);
+        s.set_params(fp);
         s.partial = ws + p.flca_partial; s.B = B; s.C = C; s.h = hh; s.w = ww; s.nblk = flca_nblk(hh, ww);
         s.ylo = ylo; s.yhi = yhi;
         RF_TRY(launch_flca_spatial(s, side));
         if (sharded) h->shard_allreduce(h->shard_user, s.partial, (size_t)B * s.nblk * C, 0, (void*)side);
-        const int hid = C / 8 > 8 ? C / 8 : 8;
-        RF_TRY(launch_flca_se_fold(s.partial, s.nblk, P_pool, h->prm(b[6]), h->prm(b[7]), h->prm(b[8]), h->prm(b[9]), hid, h->prm(x.cr_w),
-                                   ws + p.wfold_cr, ws + p.wfold_cr3, ws + p.ch, B, C, side, composed, hc));
+        RF_TRY(launch_flca_se_fold(s.partial, s.nblk, P_pool, fp.se, h->prm(x.cr_w), ws + p.wfold_cr, ws + p.wfold_cr3, ws + p.ch, B, C, side,
+                                   composed, hc));
         r.wp = ws + p.wfold_cr; r.wp_bstride = (int64_t)packed1x1_floats(2 * C, C);
         r.wp3 = ws + p.wfold_cr3; r.wp3_bstride = (int64_t)packed1x1_b3_floats(compose ? 2 * C + hc : 2 * C, C);
     } else {
@@ -410,17 +403,17 @@ int rf_create(const rf_config* cfg, rf_handle** out) {
     h->cfg = *cfg;
     const int d = cfg->dim;
     if (cfg->variant == RF_VARIANT_TRUECOLOR) {   // EnhancedBayerProcessor (BayerTORGBColorMultiLvl.py:73-98), state_dict order
-        h->bp[0] = add_param(h, "bayer_processor.wb_gains", {4});
-        h->bp[1] = add_param(h, "bayer_processor.color_matrix", {3, 4});
-        h->bp[2] = add_param(h, "bayer_processor.demosaic_refine.0.weight", {32, 3, 3, 3});
-        h->bp[3] = add_param(h, "bayer_processor.demosaic_refine.0.bias", {32});
-        h->bp[4] = add_param(h, "bayer_processor.demosaic_refine.2.weight", {3, 32, 3, 3});
-        h->bp[5] = add_param(h, "bayer_processor.demosaic_refine.2.bias", {3});
-        h->bp[6] = add_param(h, "bayer_processor.chroma_extractor.0.weight", {16, 4, 3, 3});
-        h->bp[7] = add_param(h, "bayer_processor.chroma_extractor.0.bias", {16});
-        h->bp[8] = add_param(h, "bayer_processor.chroma_extractor.2.weight", {2, 16, 3, 3});
-        h->bp[9] = add_param(h, "bayer_processor.chroma_extractor.2.bias", {2});
-        for (int k : {2, 4, 6, 8}) add_pack(h, h->bp[k], PK_3x3);
+        h->bp.wb_gains = add_param(h, "bayer_processor.wb_gains", {4});
+        h->bp.color_matrix = add_param(h, "bayer_processor.color_matrix", {3, 4});
+        h->bp.dm0_w = add_param(h, "bayer_processor.demosaic_refine.0.weight", {32, 3, 3, 3});
+        h->bp.dm0_b = add_param(h, "bayer_processor.demosaic_refine.0.bias", {32});
+        h->bp.dm2_w = add_param(h, "bayer_processor.demosaic_refine.2.weight", {3, 32, 3, 3});
+        h->bp.dm2_b = add_param(h, "bayer_processor.demosaic_refine.2.bias", {3});
+        h->bp.ce0_w = add_param(h, "bayer_processor.chroma_extractor.0.weight", {16, 4, 3, 3});
+        h->bp.ce0_b = add_param(h, "bayer_processor.chroma_extractor.0.bias", {16});
+        h->bp.ce2_w = add_param(h, "bayer_processor.chroma_extractor.2.weight", {2, 16, 3, 3});
+        h->bp.ce2_b = add_param(h, "bayer_processor.chroma_extractor.2.bias", {2});
+        for (int w : {h->bp.dm0_w, h->bp.dm2_w, h->bp.ce0_w, h->bp.ce2_w}) add_pack(h, w, PK_3x3);
     }
     h->embedding_w = add_param(h, "embedding.weight", {d, 4 * cfg->inp_channels, 3, 3});
     h->embedding_b = add_param(h, "embedding.bias", {d});
@@ -449,15 +442,15 @@ int rf_create(const rf_config* cfg, rf_handle** out) {
     h->conv_out_b = add_param(h, "conv_out.bias", {4 * cfg->out_channels});
     add_pack(h, h->conv_out_w, PK_3x3);
     if (cfg->variant == RF_VARIANT_TRUECOLOR) {   // CameraAwareColorCorrection (BayerTORGBColorMultiLvl.py:139-158)
-        h->cc[0] = add_param(h, "color_correction.gamma_param", {});
-        h->cc[1] = add_param(h, "color_correction.color_transform.0.weight", {64, 3, 1, 1});
-        h->cc[2] = add_param(h, "color_correction.color_transform.0.bias", {64});
-        h->cc[3] = add_param(h, "color_correction.color_transform.2.weight", {3, 64, 1, 1});
-        h->cc[4] = add_param(h, "color_correction.color_transform.2.bias", {3});
-        h->cc[5] = add_param(h, "color_correction.tone_curve.0.weight", {32, 1, 1, 1});
-        h->cc[6] = add_param(h, "color_correction.tone_curve.0.bias", {32});
-        h->cc[7] = add_param(h, "color_correction.tone_curve.2.weight", {1, 32, 1, 1});
-        h->cc[8] = add_param(h, "color_correction.tone_curve.2.bias", {1});
+        h->cc.gamma = add_param(h, "color_correction.gamma_param", {});
+        h->cc.ct0_w = add_param(h, "color_correction.color_transform.0.weight", {64, 3, 1, 1});
+        h->cc.ct0_b = add_param(h, "color_correction.color_transform.0.bias", {64});
+        h->cc.ct2_w = add_param(h, "color_correction.color_transform.2.weight", {3, 64, 1, 1});
+        h->cc.ct2_b = add_param(h, "color_correction.color_transform.2.bias", {3});
+        h->cc.tone0_w = add_param(h, "color_correction.tone_curve.0.weight", {32, 1, 1, 1});
+        h->cc.tone0_b = add_param(h, "color_correction.tone_curve.0.bias", {32});
+        h->cc.tone2_w = add_param(h, "color_correction.tone_curve.2.weight", {1, 32, 1, 1});
+        h->cc.tone2_b = add_param(h, "color_correction.tone_curve.2.bias", {1});
     }
     plan_training(h);
     *out = h;
@@ -647,9 +640,9 @@ int rf_forward(rf_handle* h, const float* in, float* out, void* workspace, size_
         for (int l = 0; l < 4; ++l)
             RF_TRY(launch_guidance_level(ws + p.gscratch, ws + p.guide[l], B, H, W, H >> l, W >> l, side));
     } else if (cfg.variant == RF_VARIANT_TRUECOLOR) {
-        const int* bp = h->bp;   // wb_gains, color_matrix, demosaic_refine.0 / .2, chroma_extractor.0 / .2 (weight, bias each)
-        RF_TRY(launch_tc_front(in, mosaic, h->prm(bp[0]), h->prm(bp[1]), h->pk(bp[6]), h->prm(bp[7]), h->pk(bp[8]), h->prm(bp[9]),
-                               h->pk(bp[2]), h->prm(bp[3]), h->pk(bp[4]), h->prm(bp[5]),
+        const BayerProcIx& bp = h->bp;
+        RF_TRY(launch_tc_front(in, mosaic, h->prm(bp.wb_gains), h->prm(bp.color_matrix), h->pk(bp.ce0_w), h->prm(bp.ce0_b), h->pk(bp.ce2_w),
+                               h->prm(bp.ce2_b), h->pk(bp.dm0_w), h->prm(bp.dm0_b), h->pk(bp.dm2_w), h->prm(bp.dm2_b),
                                ws + p.gscratch, B, H, W, levels, st));
         for (int l = 0; l < 4; ++l)
             RF_TRY(launch_tc_guide_level(ws + p.gscratch, ws + p.guide[l], B, H, W, levels, H >> l, W >> l, st));
@@ -708,8 +701,9 @@ int rf_forward(rf_handle* h, const float* in, float* out, void* workspace, size_
     if (cfg.variant == RF_VARIANT_TRUECOLOR) o.act = 2;      // F.relu before the PixelShuffle (BayerTORGBColorMultiLvl.py:458)
     RF_TRY(launch_conv3x3(o, st));
     if (cfg.variant == RF_VARIANT_TRUECOLOR) {
-        const float* prm[9];
-        for (int k = 0; k < 9; ++k) prm[k] = h->prm(h->cc[k]);
+        const ColorCorrIx& cc = h->cc;
+        const float* prm[9] = {h->prm(cc.gamma),   h->prm(cc.ct0_w),   h->prm(cc.ct0_b),   h->prm(cc.ct2_w),  h->prm(cc.ct2_b),
+                               h->prm(cc.tone0_w), h->prm(cc.tone0_b), h->prm(cc.tone2_w), h->prm(cc.tone2_b)};
         RF_TRY(launch_tc_color_head(out, prm, B, (size_t)4 * H * W, st));
     }
     return RF_OK;

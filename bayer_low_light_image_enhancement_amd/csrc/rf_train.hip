@@ -683,6 +683,113 @@ int grid1d(size_t n, int cap = 4096) {
     return g < 1 ? 1 : g;
 }
 
+// ---- attention, small per-(head, image) kernel: softmax of the forward's Gram partials and its adjoint (AttnSmall, rf_common.h)
+// index of W[co][k] in a packed 1x1 weight matrix (rf_common.h)
+__device__ __forceinline__ size_t pk(int NT, int co, int k) { return ((size_t)(k >> 2) * NT + (co >> 4)) * 64 + (co & 15) + 16 * (k & 3); }
+
+__global__ void __launch_bounds__(256) attn_small_kernel(AttnSmall a) {
+    const int hd = blockIdx.x, b = blockIdx.y;
+    const int C = a.C, c = C / a.heads, NT = (C + 15) >> 4;
+    constexpr int kRowW = 66;
+    __shared__ float G[64][65], A[64][65], D[64][65];
+    __shared__ float nq[64], nk[64], srow[64], tcol[64];
+    const float* pb = a.partial + (size_t)b * a.nslab * NT * 16 * kRowW;
+    // 1. reduce the slab partials in slab order (same values as attn_fold_kernel's first step)
+    for (int v = threadIdx.x; v < c * c + 2 * c; v += 256) {
+        int qch, col;
+        if (v < c * c) {
+            const int ii = v / c, jj = v % c;
+            qch = hd * c + ii;
+            const int kch = hd * c + jj;
+            const int lo_ch = 16 * (qch >> 4);
+            const int tklo = ((lo_ch / c) * c) / 16;
+            col = ((kch >> 4) - tklo) * 16 + (kch & 15);
+        } else if (v < c * c + c) { qch = hd * c + (v - c * c); col = 64; }
+        else { qch = hd * c + (v - c * c - c); col = 65; }
+        const float* src = pb + ((size_t)(qch >> 4) * 16 + (qch & 15)) * kRowW + col;
+        float s = 0.f;
+        for (int sl = 0; sl < a.nslab; ++sl) s += src[(size_t)sl * NT * 16 * kRowW];
+        if (v < c * c) G[v / c][v % c] = s;
+        else if (v < c * c + c) nq[v - c * c] = s;
+        else nk[v - c * c - c] = s;
+    }
+    __syncthreads();
+    const float T = a.temperature[hd];
+    // 2. cosines, softmax
+    if (threadIdx.x < c) {
+        const int i = threadIdx.x;
+        const float rq = 1.0f / fmaxf(sqrtf(nq[i]), 1e-12f);
+        float m = -INFINITY;
+        for (int j = 0; j < c; ++j) {
+            const float cs = G[i][j] * rq * (1.0f / fmaxf(sqrtf(nk[j]), 1e-12f));
+            G[i][j] = cs;                       // G now holds the cosines c_ij
+            m = fmaxf(m, cs * T);
+        }
+        float sum = 0.f;
+        for (int j = 0; j < c; ++j) { const float e = expf(G[i][j] * T - m); A[i][j] = e; sum += e; }
+        const float inv = 1.0f / sum;
+        for (int j = 0; j < c; ++j) A[i][j] *= inv;
+    }
+    __syncthreads();
+    // packed A (o = blockdiag(A) v) and A^T (dv = blockdiag(A^T) do)
+    float* ap = a.ap + (size_t)b * a.a_istride;
+    float* at = a.at + (size_t)b * a.a_istride;
+    for (int v = threadIdx.x; v < c * c; v += 256) {
+        const int i = v / c, j = v % c;
+        ap[pk(NT, hd * c + i, hd * c + j)] = A[i][j];
+        at[pk(NT, hd * c + j, hd * c + i)] = A[i][j];
+    }
+    if (a.fwd_only) return;
+    // 3. dS = A (dA - rowsum(dA A));  dc = T dS
+    const float* dAb = a.dA + (size_t)b * a.dA_istride;
+    for (int v = threadIdx.x; v < c * c; v += 256) D[v / c][v % c] = dAb[(size_t)(hd * c + v / c) * C + hd * c + v % c];
+    __syncthreads();
+    if (threadIdx.x < c) {
+        const int i = threadIdx.x;
+        float dot = 0.f;
+        for (int j = 0; j < c; ++j) dot = fmaf(D[i][j], A[i][j], dot);
+        float dts = 0.f, sr = 0.f;
+        for (int j = 0; j < c; ++j) {
+            const float dS = A[i][j] * (D[i][j] - dot);
+            dts = fmaf(dS, G[i][j], dts);
+            const float dc = T * dS;
+            D[i][j] = dc;                       // D now holds dc_ij
+            sr = fmaf(dc, G[i][j], sr);
+        }
+        srow[i] = sr;
+        nq[i] = 1.0f / fmaxf(sqrtf(nq[i]), 1e-12f);      // nq, nk now hold rq, rk
+        tcol[i] = dts;                                   // (reused below as the per-row dT contribution)
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.f;
+        for (int i = 0; i < c; ++i) s += tcol[i];
+        a.dT_part[(size_t)b * a.heads + hd] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < c) {
+        const int j = threadIdx.x;
+        nk[j] = 1.0f / fmaxf(sqrtf(nk[j]), 1e-12f);
+        float tc = 0.f;
+        for (int i = 0; i < c; ++i) tc = fmaf(D[i][j], G[i][j], tc);
+        tcol[j] = tc;
+    }
+    __syncthreads();
+    // 4. M2: rows dq (0..C), dk (C..2C); columns q (0..C), k (C..2C)
+    float* m2 = a.m2 + (size_t)b * a.m2_istride;
+    const int NT2 = (2 * C + 15) >> 4;
+    for (int v = threadIdx.x; v < c * c; v += 256) {
+        const int i = v / c, j = v % c;
+        const float mqk = nq[i] * D[i][j] * nk[j];
+        m2[pk(NT2, hd * c + i, C + hd * c + j)] = mqk;            // dq_i += mqk k_j
+        m2[pk(NT2, C + hd * c + j, hd * c + i)] = mqk;            // dk_j += mqk q_i
+    }
+    for (int i = threadIdx.x; i < c; i += 256) {
+        m2[pk(NT2, hd * c + i, hd * c + i)] = -nq[i] * nq[i] * srow[i];
+        m2[pk(NT2, C + hd * c + i, C + hd * c + i)] = -nk[i] * nk[i] * tcol[i];
+    }
+}
+
 }  // namespace
 
 // ---- launchers (shared with the training schedule, rf_trainstep.hip) --------------------------------------------
@@ -716,21 +823,19 @@ size_t gram2_partial_floats(int B, int Ca, int Cb, int h, int w, int ntap) {
     return (size_t)B * per * ((size_t)ntap * Ca * Cb + Ca);      // + the row sums of A (bias gradient)
 }
 
-// out[(i * ld + j) * ntap + tap] = weight layout [Ca][ld >= Cb][taps] (ntap = 9: the 3x3 window in (dy, dx) row-major order;
-// ntap = 1: the single shift (sy, sx)); per_image: out[b * out_istride + ...] without the sum over images; accumulate adds
-int launch_gram2(const float* a, int64_t a_bstride, int Ca, const float* b, int64_t b_bstride, int Cb, float* out, int ld, float* partial,
-                 size_t partial_cap, int B, int h, int w, int ntap, int sy, int sx, int per_image, size_t out_istride, int accumulate, hipStream_t st, float* db,
-                 const float* b2, int64_t b2_bstride, int Cb2) {
-    RF_CHECK_ARG(w % 4 == 0 && aligned16(a) && aligned16(b) && a_bstride % 4 == 0 && b_bstride % 4 == 0,
+// (Gram2Launch, rf_common.h)  The single-tap form has no shift: the kernel struct's sy / sx stay 0, and the nine-tap form reads neither.
+int launch_gram2(const Gram2Launch& l, hipStream_t st) {
+    const int Ca = l.Ca, Cb1 = l.Cb, Cb2 = l.Cb2, B = l.B, h = l.h, w = l.w, ntap = l.ntap;
+    float *const partial = l.partial, *const db = l.db;
+    RF_CHECK_ARG(w % 4 == 0 && aligned16(l.a) && aligned16(l.b) && l.a_bstride % 4 == 0 && l.b_bstride % 4 == 0,
                  "gram2: width %d must be a multiple of 4 and the operands 16-byte aligned", w);
     RF_CHECK_ARG(ntap == 1 || ntap == 9, "gram2: ntap must be 1 or 9");
-    RF_CHECK_ARG(ntap == 9 || (sx == 0 && sy == 0), "gram2: the single-tap form takes no shift (sy = %d, sx = %d)", sy, sx);
-    RF_CHECK_ARG(Cb2 == 0 || Cb % 16 == 0, "gram2: a second input needs the first to hold a multiple of 16 channels (%d)", Cb);
-    RF_CHECK_ARG(!db || !per_image, "gram2: the bias gradient is a sum over all images");
-    RF_CHECK_ARG(Cb2 == 0 || (b2 && aligned16(b2) && b2_bstride % 4 == 0), "gram2: bad second input");
-    const int Cb1 = Cb;
-    Cb += Cb2;                                      // rows [Cb1, Cb1 + Cb2) of the input are b2's channels
-    Gram2Args g{a, a_bstride, Ca, b, b_bstride, Cb, Cb2 ? b2 : b, Cb2 ? b2_bstride : b_bstride, Cb1, partial, B, h, w, sy, sx, 0, 0, nullptr, 0, 0, 0};
+    RF_CHECK_ARG(Cb2 == 0 || Cb1 % 16 == 0, "gram2: a second input needs the first to hold a multiple of 16 channels (%d)", Cb1);
+    RF_CHECK_ARG(!db || !l.per_image, "gram2: the bias gradient is a sum over all images");
+    RF_CHECK_ARG(Cb2 == 0 || (l.b2 && aligned16(l.b2) && l.b2_bstride % 4 == 0), "gram2: bad second input");
+    const int Cb = Cb1 + Cb2;                       // rows [Cb1, Cb1 + Cb2) of the input are b2's channels
+    Gram2Args g{l.a, l.a_bstride, Ca, l.b, l.b_bstride, Cb, Cb2 ? l.b2 : l.b, Cb2 ? l.b2_bstride : l.b_bstride, Cb1, partial, B, h, w, 0, 0, 0, 0,
+                nullptr, 0, 0, 0};
     // P % 16 != 0 (no frame of the reference's pipeline): the masked single-tap instantiations exist for one A tile only
     const bool masked = ntap == 1 && ((h * w) & 15) != 0;
     const int na = masked ? 1 : gram2_na(Ca, ntap), tj = gram2_tj(Cb, ntap);
@@ -738,9 +843,9 @@ int launch_gram2(const float* a, int64_t a_bstride, int Ca, const float* b, int6
     const int nslab = B * g.slabs_per_image;
     g.nslab = nslab; g.nty = cdiv(Ca, 16 * na); g.ntz = cdiv(Cb, 16 * tj);
     const size_t n = (size_t)ntap * Ca * Cb;
-    RF_CHECK_ARG((size_t)nslab * (n + (db ? Ca : 0)) <= partial_cap,
+    RF_CHECK_ARG((size_t)nslab * (n + (db ? Ca : 0)) <= l.partial_cap,
                  "gram2: %d slabs x %zu partial floats (Ca = %d, Cb = %d, %d taps, %dx%d, B = %d) exceed the %zu-float partial buffer",
-                 nslab, n + (db ? Ca : 0), Ca, Cb, ntap, h, w, B, partial_cap);
+                 nslab, n + (db ? Ca : 0), Ca, Cb, ntap, h, w, B, l.partial_cap);
     if (db) g.bias_partial = partial + (size_t)nslab * n;
     ProfScope prof(st, ntap == 1 ? "gram2_kernel<1>" : "gram2_kernel<9>", 2.0 * ntap * Ca * Cb * (double)B * h * w, 4.0 * (double)B * h * w * (Ca + Cb));
     const dim3 grid1((unsigned)(cdiv(nslab, 8) * 8 * g.nty * g.ntz));
@@ -758,9 +863,14 @@ int launch_gram2(const float* a, int64_t a_bstride, int Ca, const float* b, int6
 #undef RF_G2_TJ
 #undef RF_G2
     const size_t n_pad = (n + kRedElems - 1) / kRedElems * kRedElems;
-    reduce_gram2_kernel<<<dim3((unsigned)red_grid(n_pad + (db ? Ca : 0)), per_image ? (unsigned)B : 1u), 256, 0, st>>>(
-        partial, out, per_image ? g.slabs_per_image : nslab, ntap, Ca, Cb, ld, out_istride, accumulate, g.bias_partial, db);
+    reduce_gram2_kernel<<<dim3((unsigned)red_grid(n_pad + (db ? Ca : 0)), l.per_image ? (unsigned)B : 1u), 256, 0, st>>>(
+        partial, l.out, l.per_image ? g.slabs_per_image : nslab, ntap, Ca, Cb, l.ld, l.out_istride, l.accumulate ? 1 : 0, g.bias_partial, db);
     return check_launch("gram2");
+}
+
+int launch_attn_small(const AttnSmall& a, int B, hipStream_t st) {
+    attn_small_kernel<<<dim3((unsigned)a.heads, (unsigned)B), 256, 0, st>>>(a);
+    return check_launch("attn_small");
 }
 
 // out[e] (+)= sum over rows of partial[row][e]
@@ -1225,18 +1335,17 @@ __global__ void __launch_bounds__(256) flca_abg_kernel(const float* __restrict__
 
 size_t flca_bwd_scratch_floats(int B, int C, int h, int w) {
     const int P = h * w;
-    const int hid = C / 8 > 8 ? C / 8 : 8;
+    const int hid = flca_hidden(C);
     return 3 * (size_t)B * C * P + (size_t)B * cdiv(P, 256) * 3 + (size_t)B * chan_sum_nblk(P) * C + 2 * (size_t)B * C + 256 +
            (size_t)B * (2 * C * hid + hid + C) + 64 +
            gram2_partial_floats(B, C, 2, h, w, 9) + gram2_partial_floats(B, C, 16, h, w, 1) * 3 + (size_t)C * 36 + 64;
 }
 
-// prm / grd: alpha, beta, gamma, low_attn.0.w, high_attn.0.w, chroma_attn.0.w, se.1.w, se.1.b, se.3.w, se.3.b (parameters / their gradients)
 int launch_flca_backward(const float* feat, const float* guide, const float* xs, const float* dz, int64_t dz_bstride, const float* ch,
-                         const float* pool_partial, int pool_nblk, const float* const* prm, float* const* grd, float* dfeat, int accumulate,
+                         const float* pool_partial, int pool_nblk, const FlcaPrm& prm, const FlcaGrad& grd, float* dfeat, int accumulate,
                          float* scratch, size_t scratch_floats, int B, int C, int h, int w, hipStream_t st) {
     RF_CHECK_ARG(C <= 512 && B <= 65535 && w % 4 == 0, "flca backward: C=%d, w=%d unsupported", C, w);
-    const int P = h * w, nblk = cdiv(P, 256), dnblk = chan_sum_nblk(P), hid = C / 8 > 8 ? C / 8 : 8;
+    const int P = h * w, nblk = cdiv(P, 256), dnblk = chan_sum_nblk(P), hid = flca_hidden(C);
     const size_t plane = (size_t)B * C * P;
     float* ds = scratch;
     float* abg = ds + 3 * plane;
@@ -1249,13 +1358,13 @@ int launch_flca_backward(const float* feat, const float* guide, const float* xs,
                  scratch_floats, (size_t)(gpart - scratch));
     const size_t gcap = scratch_floats - (size_t)(gpart - scratch);      // the slab partials of the tap gradients (gram2 / fused kernel)
     // the four squeeze-excite tensors follow each other in the flat gradient buffer (registry order, sizes multiples of 4)
-    RF_CHECK_ARG(grd[7] == grd[6] + (size_t)hid * C && grd[8] == grd[7] + hid && grd[9] == grd[8] + (size_t)C * hid,
+    RF_CHECK_ARG(grd.se.se1_b == grd.se.se1_w + (size_t)hid * C && grd.se.se3_w == grd.se.se1_b + hid && grd.se.se3_b == grd.se.se3_w + (size_t)C * hid,
                  "flca backward: the gradients of se.1.weight, se.1.bias, se.3.weight, se.3.bias must be contiguous");
     // squeeze-excite part: dch -> per-image MLP adjoint -> dm, the four se gradients
     auto se_part = [&]() -> int {
         flca_dch_kernel<<<dim3((unsigned)dnblk, (unsigned)C, (unsigned)B), 256, 0, st>>>(dz, dz_bstride, xs, dch_part, C, P, dnblk);
-        flca_se_bwd_kernel<<<B, 256, 0, st>>>(pool_partial, pool_nblk, dch_part, dnblk, prm[6], prm[7], prm[8], prm[9], dmP, se_contrib, C, hid, P);
-        reduce_partials_kernel<<<red_grid(n_se), 256, 0, st>>>(se_contrib, grd[6], B, n_se, 1);
+        flca_se_bwd_kernel<<<B, 256, 0, st>>>(pool_partial, pool_nblk, dch_part, dnblk, prm.se.se1_w, prm.se.se1_b, prm.se.se3_w, prm.se.se3_b, dmP, se_contrib, C, hid, P);
+        reduce_partials_kernel<<<red_grid(n_se), 256, 0, st>>>(se_contrib, grd.se.se1_w, B, n_se, 1);      // all four at once
         return check_launch("flca_backward (squeeze-excite)");
     };
     if (w % 4 == 0 && aligned16(dz) && dz_bstride % 4 == 0 && aligned16(feat) && aligned16(dfeat) && aligned16(guide)) {
@@ -1269,24 +1378,31 @@ int launch_flca_backward(const float* feat, const float* guide, const float* xs,
         float* abg2 = ds;
         ProfScope prof(st, "flca_backward(fused)", 2.0 * 36 * (double)B * C * P + 200.0 * B * C * P, 12.0 * (double)B * C * P + 8.0 * B * C * P);
         if (int rc = se_part()) return rc;
-        FlcaBwdArgs a{feat, guide, dz, dz_bstride, ch, dmP, prm[3], prm[4], prm[5], prm[0], prm[1], prm[2], dfeat, nullptr, abg2, B, C, h, w, nblk, accumulate};
+        FlcaBwdArgs a{feat, guide, dz, dz_bstride, ch, dmP, prm.w_low, prm.w_high, prm.w_chr, prm.alpha, prm.beta, prm.gamma, dfeat, nullptr, abg2, B, C, h, w, nblk, accumulate};
         flca_bwd_fused_kernel<<<dim3((unsigned)nslab, (unsigned)nti), 256, 0, st>>>(a, gpart, slab_px, per_image);
-        flca_abg_kernel<<<1, 256, 0, st>>>(abg2, nslab * nti, grd[0], grd[1], grd[2]);
+        flca_abg_kernel<<<1, 256, 0, st>>>(abg2, nslab * nti, grd.alpha, grd.beta, grd.gamma);
         reduce_partials_kernel<<<red_grid((size_t)C * 36), 256, 0, st>>>(gpart, sums, nslab, (size_t)C * 36, 0);
-        flca_taps_scatter_kernel<<<cdiv(C * 36, 256), 256, 0, st>>>(sums, grd[3], grd[4], grd[5], C);
+        flca_taps_scatter_kernel<<<cdiv(C * 36, 256), 256, 0, st>>>(sums, grd.w_low, grd.w_high, grd.w_chr, C);
         return check_launch("flca_backward (fused)");
     }
     {
         ProfScope prof(st, "flca_backward(elementwise)", 200.0 * B * C * P, 32.0 * B * C * P);
         if (int rc = se_part()) return rc;
-        FlcaBwdArgs a{feat, guide, dz, dz_bstride, ch, dmP, prm[3], prm[4], prm[5], prm[0], prm[1], prm[2], dfeat, ds, abg, B, C, h, w, nblk, accumulate};
+        FlcaBwdArgs a{feat, guide, dz, dz_bstride, ch, dmP, prm.w_low, prm.w_high, prm.w_chr, prm.alpha, prm.beta, prm.gamma, dfeat, ds, abg, B, C, h, w, nblk, accumulate};
         flca_spatial_bwd_kernel<<<dim3((unsigned)nblk, (unsigned)B), 256, 0, st>>>(a);
-        flca_abg_kernel<<<1, 256, 0, st>>>(abg, B * nblk, grd[0], grd[1], grd[2]);
+        flca_abg_kernel<<<1, 256, 0, st>>>(abg, B * nblk, grd.alpha, grd.beta, grd.gamma);
         if (int rc = check_launch("flca_backward")) return rc;
     }
-    if (int rc = launch_gram2(ds, (int64_t)C * P, C, guide, (int64_t)4 * P, 1, grd[3], 1, gpart, gcap, B, h, w, 9, 0, 0, 0, 0, 1, st)) return rc;
-    if (int rc = launch_gram2(ds + plane, (int64_t)C * P, C, guide + P, (int64_t)4 * P, 1, grd[4], 1, gpart, gcap, B, h, w, 9, 0, 0, 0, 0, 1, st)) return rc;
-    return launch_gram2(ds + 2 * plane, (int64_t)C * P, C, guide + 2 * (size_t)P, (int64_t)4 * P, 2, grd[5], 2, gpart, gcap, B, h, w, 9, 0, 0, 0, 0, 1, st);
+    // tap gradients of the three gates: each dS plane against the guidance planes it gates (low: plane 0, high: 1, chroma: 2-3)
+    Gram2Launch g{};
+    g.a_bstride = (int64_t)C * P; g.Ca = C; g.b_bstride = (int64_t)4 * P;
+    g.partial = gpart; g.partial_cap = gcap; g.B = B; g.h = h; g.w = w; g.ntap = 9; g.accumulate = true;
+    g.a = ds; g.b = guide; g.Cb = g.ld = 1; g.out = grd.w_low;
+    if (int rc = launch_gram2(g, st)) return rc;
+    g.a = ds + plane; g.b = guide + P; g.out = grd.w_high;
+    if (int rc = launch_gram2(g, st)) return rc;
+    g.a = ds + 2 * plane; g.b = guide + 2 * (size_t)P; g.Cb = g.ld = 2; g.out = grd.w_chr;
+    return launch_gram2(g, st);
 }
 
 }  // namespace rf

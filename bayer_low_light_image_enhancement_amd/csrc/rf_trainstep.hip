@@ -36,16 +36,6 @@ using namespace rf;
 
 namespace {
 
-struct Bump {
-    float* base;
-    size_t off = 0;
-    float* take(size_t n) {
-        float* p = base ? base + off : nullptr;
-        off += align_up(n, 64);
-        return p;
-    }
-};
-
 struct Stash {      // one Conv_Transformer stage
     const float* in;
     float *qkvp, *qkv, *partial, *x1, *f1, *f2, *g, *trans, *xs, *cr, *out;      // g = GELU(f2), written by the same kernel as f2
@@ -64,13 +54,34 @@ struct TrainPlan {
     float *part;                       // reduction partials
     float *part_wg;                    // ... of the kernels on the weight-gradient stream
     size_t part_floats;                // capacity of each of part / part_wg (launch_gram2 checks its slab partials against it)
-    float *sb[16];                     // stage_backward's temporaries, one buffer per tensor (see there)
-    float *small;                      // attention: per-image C x C matrices and packed per-image weights
+    // stage_backward's temporaries, one buffer per tensor (see there)
+    float *d_pre, *d_cr, *d_cat, *d_f2, *d_f1, *ln2, *d_ln2, *d_x1, *o, *d_o, *d_qkv, *d_qkvp, *ln1, *d_ln1, *d_xs, *d_tr;
+    float *small;                      // attention: per-image C x C matrices and packed per-image weights (SmallLayout)
     float *loss_part;
     size_t total;
 };
 
 size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
+
+// TrainPlan::small in a stage's backward.  Per image: dA [C][C] (from gram2; 3 C^2 floats kept for it), then the packed M2
+// (K = 2C, Cout = 2C), the packed A^T and the packed A (C x C each); after the B images the softmax adjoint's dT partials
+// [B][heads].  (The forward keeps its per-image folded projection at the start of the same buffer.)
+struct SmallLayout {
+    size_t m2, at, ap;        // float offsets inside an image's block (dA at 0)
+    size_t per, dT_part;      // floats per image = the image stride of all four; float offset of the dT partials
+    size_t cleared, floats;   // floats stage_backward zero-fills before the attention adjoint; floats reserved
+};
+SmallLayout small_layout(int B, int C) {
+    SmallLayout l;
+    l.m2 = 3 * (size_t)C * C;
+    l.at = l.m2 + packed1x1_floats(2 * C, 2 * C);
+    l.ap = l.at + packed1x1_floats(C, C);
+    l.per = l.ap + packed1x1_floats(C, C);
+    l.dT_part = (size_t)B * l.per;
+    l.cleared = (size_t)B * (l.per + 64);
+    l.floats = l.cleared + 64;
+    return l;
+}
 
 int make_train_plan(const rf_handle* h, float* base, int B, int H, int W, TrainPlan& p) {
     const rf_config& c = h->cfg;
@@ -105,7 +116,7 @@ int make_train_plan(const rf_handle* h, float* base, int B, int H, int W, TrainP
         part = max_sz(part, gram2_partial_floats(B, 2 * C, 4 * C, hh, ww, 1));
         part = max_sz(part, ln_bwd_partial_floats(B, C, hh * ww));
         part = max_sz(part, dw_wgrad_partial_floats(B, 3 * C > hc ? 3 * C : hc, hh * ww));
-        small = max_sz(small, (size_t)B * (3 * (size_t)C * C + packed1x1_floats(2 * C, 2 * C) + 2 * packed1x1_floats(C, C) + 64) + 64);
+        small = max_sz(small, small_layout(B, C).floats);
         return RF_OK;
     };
     for (int i = 1; i <= 4; ++i) {
@@ -128,16 +139,14 @@ int make_train_plan(const rf_handle* h, float* base, int B, int H, int W, TrainP
     p.part_floats = max_sz(part, (size_t)B * 64 * 512);
     p.part = b.take(p.part_floats);
     p.part_wg = b.take(p.part_floats);
-    {   // d_pre, d_cr, d_cat, d_f2, d_f1, ln2, d_ln2, d_x1, o, d_o, d_qkv, d_qkvp, ln1, d_ln1, d_xs, d_tr   (units of U0)
-        const size_t hx = (size_t)hcx;
-        const size_t units[16] = {1, 1, 2, hx, hx, 1, 1, 1, 1, 1, 3, 3, 1, 1, 1, 1};
-        for (int k = 0; k < 16; ++k) p.sb[k] = b.take(units[k] * U0);
-    }
+    p.d_pre = b.take(U0); p.d_cr = b.take(U0); p.d_cat = b.take(2 * U0); p.d_f2 = b.take(hcx * U0); p.d_f1 = b.take(hcx * U0);
+    p.ln2 = b.take(U0); p.d_ln2 = b.take(U0); p.d_x1 = b.take(U0); p.o = b.take(U0); p.d_o = b.take(U0);
+    p.d_qkv = b.take(3 * U0); p.d_qkvp = b.take(3 * U0); p.ln1 = b.take(U0); p.d_ln1 = b.take(U0); p.d_xs = b.take(U0); p.d_tr = b.take(U0);
     p.small = b.take(small);
     p.loss_part = b.take(4096);
     p.flca_scr = b.take(fscr);
     p.flca_scr_floats = fscr;
-    p.total = b.off;
+    p.total = b.used;
     return RF_OK;
 }
 
@@ -154,6 +163,9 @@ struct Ctx {
     bool forked() const { return wg != st; }
     float* dw_part() const { return forked() ? p->part_wg : p->part; }
     float* G(int ix) const { return grads + h->flat_offset[ix]; }
+    FlcaGrad flca_grad(const FlcaGroup<int>& x) const {
+        return {G(x.alpha), G(x.beta), G(x.gamma), G(x.w_low), G(x.w_high), G(x.w_chr), {G(x.se.se1_w), G(x.se.se1_b), G(x.se.se3_w), G(x.se.se3_b)}};
+    }
     // weight `ix` in pack-cache form `form`; the b3 forms are optional (nullptr: the f32 kernels), the others an error when missing
     const float* pk(int ix, int form) const {
         const size_t off = h->params[ix].cache[form];
@@ -212,21 +224,32 @@ int b_conv1x1_dx(const Ctx& c, const float* dy, int Cout, int w, int K, float* d
     return launch_conv1x1(a, c.st);
 }
 
-// dW [Cout][ld] columns [col0, col0 + Cx) += / = gram2(dy, x);  db = channel sums of dy, taken in the same pass
+// dW of a convolution layer, accumulated into the flat gradient buffer on the weight-gradient stream: out [Cout][ld][ntap] +=
+// gram2(dy, x) over all images; the caller adds db / a second input and launches on c.wg (after c.side->fork)
+Gram2Launch wgrad(const Ctx& c, const float* dy, int64_t dy_bstride, int Cout, const float* x, int Cx, float* dW, int ld, int hh, int ww, int ntap) {
+    Gram2Launch g{};
+    g.a = dy; g.a_bstride = dy_bstride; g.Ca = Cout;
+    g.b = x; g.b_bstride = (int64_t)Cx * hh * ww; g.Cb = Cx;
+    g.out = dW; g.ld = ld;
+    g.partial = c.dw_part(); g.partial_cap = c.p->part_floats;
+    g.B = c.B; g.h = hh; g.w = ww; g.ntap = ntap; g.accumulate = true;
+    return g;
+}
+
+// dW [Cout][ld] columns [col0, col0 + Cx) += gram2(dy, x);  db = channel sums of dy, taken in the same pass
 // (x2 / Cx2: the layer's input is cat(x, x2) along channels, read in place)
 int b_conv1x1_dw(const Ctx& c, const float* dy, int Cout, const float* x, int Cx, float* dW, int ld, int col0, float* db, int hh, int ww,
                  int64_t dy_bstride = 0, const float* x2 = nullptr, int Cx2 = 0) {
-    const int64_t dys = dy_bstride ? dy_bstride : (int64_t)Cout * hh * ww;
     RF_TRY(c.side->fork(c.st, c.wg));
-    const hipStream_t ws = c.wg;
-    float* part = c.dw_part();
+    Gram2Launch g = wgrad(c, dy, dy_bstride ? dy_bstride : (int64_t)Cout * hh * ww, Cout, x, Cx, dW + col0, ld, hh, ww, 1);
+    g.db = col0 == 0 ? db : nullptr;
     if (Cx2 && Cx % 16 != 0) {       // the two-source contraction cuts the inputs at a tile boundary: otherwise one pass per input
-        RF_TRY(launch_gram2(dy, dys, Cout, x, (int64_t)Cx * hh * ww, Cx, dW + col0, ld, part, c.p->part_floats, c.B, hh, ww, 1, 0, 0, 0, 0, 1, ws,
-                            col0 == 0 ? db : nullptr));
-        return launch_gram2(dy, dys, Cout, x2, (int64_t)Cx2 * hh * ww, Cx2, dW + col0 + Cx, ld, part, c.p->part_floats, c.B, hh, ww, 1, 0, 0, 0, 0, 1, ws);
+        RF_TRY(launch_gram2(g, c.wg));
+        g.b = x2; g.b_bstride = (int64_t)Cx2 * hh * ww; g.Cb = Cx2; g.out = dW + col0 + Cx; g.db = nullptr;
+    } else {
+        g.b2 = x2; g.b2_bstride = (int64_t)Cx2 * hh * ww; g.Cb2 = Cx2;
     }
-    return launch_gram2(dy, dys, Cout, x, (int64_t)Cx * hh * ww, Cx, dW + col0, ld, part, c.p->part_floats, c.B, hh, ww,
-                        1, 0, 0, 0, 0, 1, ws, col0 == 0 ? db : nullptr, x2, (int64_t)Cx2 * hh * ww, Cx2);
+    return launch_gram2(g, c.wg);
 }
 
 int b_conv3x3_dx(const Ctx& c, const float* dy, int Cout, int w, int Cin, float* dx, int hh, int ww) {
@@ -235,7 +258,9 @@ int b_conv3x3_dx(const Ctx& c, const float* dy, int Cout, int w, int Cin, float*
 
 int b_conv3x3_dw(const Ctx& c, const float* dy, int Cout, const float* x, int Cin, float* dW, float* db, int hh, int ww) {
     RF_TRY(c.side->fork(c.st, c.wg));
-    return launch_gram2(dy, (int64_t)Cout * hh * ww, Cout, x, (int64_t)Cin * hh * ww, Cin, dW, Cin, c.dw_part(), c.p->part_floats, c.B, hh, ww, 9, 0, 0, 0, 0, 1, c.wg, db);
+    Gram2Launch g = wgrad(c, dy, (int64_t)Cout * hh * ww, Cout, x, Cin, dW, Cin, hh, ww, 9);
+    g.db = db;
+    return launch_gram2(g, c.wg);
 }
 
 // depthwise 3x3 with weight `w`: dW, db on the weight-gradient stream, dX = the forward kernel on the flipped taps
@@ -247,137 +272,18 @@ int b_dw(const Ctx& c, const float* dy, const float* x, int w, float* dx, float*
     return f_dw(c, dy, wf, nullptr, dx, C, hh, ww);
 }
 
-// ---- attention, small per-(head, image) kernel ----------------------------------------------------------------------
-// layout of `small` per image: dA [C][C] (from gram2), then packed M2 (K = 2C, Cout = 2C), packed A^T (C, C), packed A (C, C)
-struct AttnSmall {
-    const float* partial; int nslab;       // Gram partials of the forward (rf_attn.hip layout, kRowW = 66)
-    const float* temperature;
-    const float* dA; size_t dA_istride;    // [B][C][C]
-    float* m2; size_t m2_istride;          // packed [2C x 2C], zero-filled by the caller
-    float* at; float* ap; size_t a_istride;   // packed A^T and A [C x C], zero-filled by the caller
-    float* dT_part;                        // [B][heads]
-    int C, heads, fwd_only;
-};
-
-__device__ __forceinline__ size_t pk(int NT, int co, int k) { return ((size_t)(k >> 2) * NT + (co >> 4)) * 64 + (co & 15) + 16 * (k & 3); }
-
-__global__ void __launch_bounds__(256) attn_small_kernel(AttnSmall a) {
-    const int hd = blockIdx.x, b = blockIdx.y;
-    const int C = a.C, c = C / a.heads, NT = (C + 15) >> 4;
-    constexpr int kRowW = 66;
-    __shared__ float G[64][65], A[64][65], D[64][65];
-    __shared__ float nq[64], nk[64], srow[64], tcol[64];
-    const float* pb = a.partial + (size_t)b * a.nslab * NT * 16 * kRowW;
-    // 1. reduce the slab partials in slab order (same values as attn_fold_kernel's first step)
-    for (int v = threadIdx.x; v < c * c + 2 * c; v += 256) {
-        int qch, col;
-        if (v < c * c) {
-            const int ii = v / c, jj = v % c;
-            qch = hd * c + ii;
-            const int kch = hd * c + jj;
-            const int lo_ch = 16 * (qch >> 4), hi_ch = (lo_ch + 15 < C - 1) ? lo_ch + 15 : C - 1;
-            const int tklo = ((lo_ch / c) * c) / 16;
-            (void)hi_ch;
-            col = ((kch >> 4) - tklo) * 16 + (kch & 15);
-        } else if (v < c * c + c) { qch = hd * c + (v - c * c); col = 64; }
-        else { qch = hd * c + (v - c * c - c); col = 65; }
-        const float* src = pb + ((size_t)(qch >> 4) * 16 + (qch & 15)) * kRowW + col;
-        float s = 0.f;
-        for (int sl = 0; sl < a.nslab; ++sl) s += src[(size_t)sl * NT * 16 * kRowW];
-        if (v < c * c) G[v / c][v % c] = s;
-        else if (v < c * c + c) nq[v - c * c] = s;
-        else nk[v - c * c - c] = s;
-    }
-    __syncthreads();
-    const float T = a.temperature[hd];
-    // 2. cosines, softmax
-    if (threadIdx.x < c) {
-        const int i = threadIdx.x;
-        const float rq = 1.0f / fmaxf(sqrtf(nq[i]), 1e-12f);
-        float m = -INFINITY;
-        for (int j = 0; j < c; ++j) {
-            const float cs = G[i][j] * rq * (1.0f / fmaxf(sqrtf(nk[j]), 1e-12f));
-            G[i][j] = cs;                       // G now holds the cosines c_ij
-            m = fmaxf(m, cs * T);
-        }
-        float sum = 0.f;
-        for (int j = 0; j < c; ++j) { const float e = expf(G[i][j] * T - m); A[i][j] = e; sum += e; }
-        const float inv = 1.0f / sum;
-        for (int j = 0; j < c; ++j) A[i][j] *= inv;
-    }
-    __syncthreads();
-    // packed A (o = blockdiag(A) v) and A^T (dv = blockdiag(A^T) do)
-    float* ap = a.ap + (size_t)b * a.a_istride;
-    float* at = a.at + (size_t)b * a.a_istride;
-    for (int v = threadIdx.x; v < c * c; v += 256) {
-        const int i = v / c, j = v % c;
-        ap[pk(NT, hd * c + i, hd * c + j)] = A[i][j];
-        at[pk(NT, hd * c + j, hd * c + i)] = A[i][j];
-    }
-    if (a.fwd_only) return;
-    // 3. dS = A (dA - rowsum(dA A));  dc = T dS
-    const float* dAb = a.dA + (size_t)b * a.dA_istride;
-    for (int v = threadIdx.x; v < c * c; v += 256) D[v / c][v % c] = dAb[(size_t)(hd * c + v / c) * C + hd * c + v % c];
-    __syncthreads();
-    if (threadIdx.x < c) {
-        const int i = threadIdx.x;
-        float dot = 0.f;
-        for (int j = 0; j < c; ++j) dot = fmaf(D[i][j], A[i][j], dot);
-        float dts = 0.f, sr = 0.f;
-        for (int j = 0; j < c; ++j) {
-            const float dS = A[i][j] * (D[i][j] - dot);
-            dts = fmaf(dS, G[i][j], dts);
-            const float dc = T * dS;
-            D[i][j] = dc;                       // D now holds dc_ij
-            sr = fmaf(dc, G[i][j], sr);
-        }
-        srow[i] = sr;
-        nq[i] = 1.0f / fmaxf(sqrtf(nq[i]), 1e-12f);      // nq, nk now hold rq, rk
-        tcol[i] = dts;                                   // (reused below as the per-row dT contribution)
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s = 0.f;
-        for (int i = 0; i < c; ++i) s += tcol[i];
-        a.dT_part[(size_t)b * a.heads + hd] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < c) {
-        const int j = threadIdx.x;
-        nk[j] = 1.0f / fmaxf(sqrtf(nk[j]), 1e-12f);
-        float tc = 0.f;
-        for (int i = 0; i < c; ++i) tc = fmaf(D[i][j], G[i][j], tc);
-        tcol[j] = tc;
-    }
-    __syncthreads();
-    // 4. M2: rows dq (0..C), dk (C..2C); columns q (0..C), k (C..2C)
-    float* m2 = a.m2 + (size_t)b * a.m2_istride;
-    const int NT2 = (2 * C + 15) >> 4;
-    for (int v = threadIdx.x; v < c * c; v += 256) {
-        const int i = v / c, j = v % c;
-        const float mqk = nq[i] * D[i][j] * nk[j];
-        m2[pk(NT2, hd * c + i, C + hd * c + j)] = mqk;            // dq_i += mqk k_j
-        m2[pk(NT2, C + hd * c + j, hd * c + i)] = mqk;            // dk_j += mqk q_i
-    }
-    for (int i = threadIdx.x; i < c; i += 256) {
-        m2[pk(NT2, hd * c + i, hd * c + i)] = -nq[i] * nq[i] * srow[i];
-        m2[pk(NT2, C + hd * c + i, C + hd * c + i)] = -nk[i] * nk[i] * tcol[i];
-    }
-}
-
+// ---- attention, small per-(head, image) kernel (rf_train.hip: launch_attn_small) --------------------------------------
 int attn_small(const Ctx& c, const Stash& s, const float* temperature, int C, int heads, int fwd_only, float* dT) {
-    const size_t CC = (size_t)C * C;
+    const SmallLayout l = small_layout(c.B, C);
     float* sm = c.p->small;
-    const size_t per = 3 * CC + packed1x1_floats(2 * C, 2 * C) + 2 * packed1x1_floats(C, C);
     AttnSmall a{};
     a.partial = s.partial; a.nslab = s.nslab; a.temperature = temperature;
-    a.dA = sm; a.dA_istride = per;
-    a.m2 = sm + 3 * CC; a.m2_istride = per;
-    a.at = a.m2 + packed1x1_floats(2 * C, 2 * C); a.ap = a.at + packed1x1_floats(C, C); a.a_istride = per;
-    a.dT_part = sm + (size_t)c.B * per;
+    a.dA = sm; a.dA_istride = l.per;
+    a.m2 = sm + l.m2; a.m2_istride = l.per;
+    a.at = sm + l.at; a.ap = sm + l.ap; a.a_istride = l.per;
+    a.dT_part = sm + l.dT_part;
     a.C = C; a.heads = heads; a.fwd_only = fwd_only;
-    attn_small_kernel<<<dim3((unsigned)heads, (unsigned)c.B), 256, 0, c.st>>>(a);
-    RF_TRY(check_launch("attn_small"));
+    RF_TRY(launch_attn_small(a, c.B, c.st));
     if (!fwd_only && dT) RF_TRY(launch_reduce_rows(a.dT_part, dT, c.B, (size_t)heads, 1, c.st));   // dT[h] += sum over images, in order
     return RF_OK;
 }
@@ -414,15 +320,13 @@ int stage_forward(const Ctx& c, int i, const float* in, int H, int W) {
     RF_TRY(f_dw(c, s.f1, h->prm(x.dw_w), h->prm(x.dw_b), s.f2, hc, hh, ww, s.g));   // f2 and g = gelu(f2)
     RF_TRY(f_conv1x1(c, s.g, hc, nullptr, 0, x.pw2_w, h->prm(x.pw2_b), nullptr, nullptr, s.x1, s.trans, C, Pn));
     if (cfg.variant == RF_VARIANT_FLCA) {
-        const int* b = x.flca;   // registry order (StageIx)
+        const FlcaPrm fp = h->flca_prm(x.flca);
         FlcaSpatialArgs sa{};
         sa.feat = in; sa.xs = s.xraw; sa.guide = c.p->guide[lvl];
-        sa.w_low = h->prm(b[3]); sa.w_high = h->prm(b[4]); sa.w_chr = h->prm(b[5]);
-        sa.alpha = h->prm(b[0]); sa.beta = h->prm(b[1]); sa.gamma = h->prm(b[2]);
+        sa.set_params(fp);
         sa.partial = s.pool; sa.B = c.B; sa.C = C; sa.h = hh; sa.w = ww; sa.nblk = flca_nblk(hh, ww);
         RF_TRY(launch_flca_spatial(sa, c.st));
-        const int hid = C / 8 > 8 ? C / 8 : 8;
-        RF_TRY(launch_flca_se(s.pool, sa.nblk, Pn, h->prm(b[6]), h->prm(b[7]), h->prm(b[8]), h->prm(b[9]), hid, s.ch, c.B, C, c.st));
+        RF_TRY(launch_flca_se(s.pool, sa.nblk, Pn, fp.se, s.ch, c.B, C, c.st));
         RF_TRY(launch_scale_channels_to(s.xraw, s.xs, s.ch, c.B, C, Pn, c.st));                         // xs = branch output z
     } else {
         RF_TRY(f_conv3x3(c, in, C, x.conv_w, h->prm(x.conv_b), s.xs, C, hh, ww, cfg.branch_lrelu ? 1 : 0, 0));
@@ -445,9 +349,9 @@ int stage_backward(const Ctx& outer, hipStream_t wg, int i, float* dout, float* 
     const size_t U = (size_t)c.B * C * Pn;
     // One buffer per tensor: the weight-gradient kernels read them from their own stream while the dX chain moves on, so nothing
     // is overwritten inside a stage; the stage ends with a join, after which the next stage reuses the buffers.
-    float* const* sb = c.p->sb;
-    float *d_pre = sb[0], *d_cr = sb[1], *d_cat = sb[2], *d_f2 = sb[3], *d_f1 = sb[4], *ln2 = sb[5], *d_ln2 = sb[6], *d_x1 = sb[7], *o = sb[8],
-          *d_o = sb[9], *d_qkv = sb[10], *d_qkvp = sb[11], *ln1 = sb[12], *d_ln1 = sb[13], *d_xs = sb[14], *d_tr = sb[15];
+    const TrainPlan& t = *c.p;
+    float *d_pre = t.d_pre, *d_cr = t.d_cr, *d_cat = t.d_cat, *d_f2 = t.d_f2, *d_f1 = t.d_f1, *ln2 = t.ln2, *d_ln2 = t.d_ln2, *d_x1 = t.d_x1, *o = t.o,
+          *d_o = t.d_o, *d_qkv = t.d_qkv, *d_qkvp = t.d_qkvp, *ln1 = t.ln1, *d_ln1 = t.d_ln1, *d_xs = t.d_xs, *d_tr = t.d_tr;
     // Conv_out + LeakyReLU
     RF_TRY(launch_ewise(dout, s.out, d_pre, U, 2, 0.2f, c.st));                                      // d(pre-activation)
     RF_TRY(b_conv3x3_dw(c, d_pre, C, s.cr, C, c.G(x.out_w), c.G(x.out_b), hh, ww));
@@ -465,11 +369,8 @@ int stage_backward(const Ctx& outer, hipStream_t wg, int i, float* dout, float* 
         dxs = d_xs; dtr = d_tr; half_bs = (int64_t)C * Pn;
     }
     if (cfg.variant == RF_VARIANT_FLCA) {
-        const float* prm[10];
-        float* grd[10];
-        for (int k = 0; k < 10; ++k) { prm[k] = h->prm(x.flca[k]); grd[k] = c.G(x.flca[k]); }
-        RF_TRY(launch_flca_backward(s.in, c.p->guide[lvl], s.xraw, dxs, half_bs, s.ch, s.pool, flca_nblk(hh, ww), prm, grd, din, 0,
-                                    c.p->flca_scr, c.p->flca_scr_floats, c.B, C, hh, ww, c.st));                             // din = branch part
+        RF_TRY(launch_flca_backward(s.in, c.p->guide[lvl], s.xraw, dxs, half_bs, s.ch, s.pool, flca_nblk(hh, ww), h->flca_prm(x.flca),
+                                    c.flca_grad(x.flca), din, 0, c.p->flca_scr, c.p->flca_scr_floats, c.B, C, hh, ww, c.st));   // din = branch part
     } else {
         // conv branch
         if (cfg.branch_lrelu) RF_TRY(launch_ewise(d_xs, s.xs, d_xs, U, 2, 0.2f, c.st));
@@ -487,32 +388,34 @@ int stage_backward(const Ctx& outer, hipStream_t wg, int i, float* dout, float* 
     // d_x1 = dtrans + (LayerNorm adjoint), dtrans read in place
     RF_TRY(launch_ln_bwd(s.x1, d_ln2, h->prm(x.ln2_w), d_x1, c.G(x.ln2_w), c.p->part, c.B, C, Pn, 1e-5f, 0, 1, c.st, dtr, half_bs));
     // attention:  x1 = in + W_out (A v) + b          (the residual din += dx1 rides on the last kernel of the stage)
-    const size_t CC = (size_t)C * C;
-    const size_t per = 3 * CC + packed1x1_floats(2 * C, 2 * C) + 2 * packed1x1_floats(C, C);
-    RF_TRY(check_hip(hipMemsetAsync(c.p->small, 0, (c.B * (per + 64)) * sizeof(float), c.st), "memset"));
+    const SmallLayout sl = small_layout(c.B, C);
+    RF_TRY(check_hip(hipMemsetAsync(c.p->small, 0, sl.cleared * sizeof(float), c.st), "memset"));
     RF_TRY(attn_small(c, s, h->prm(x.temperature), C, heads, 1, nullptr));                     // packed A, A^T
-    float* m2 = c.p->small + 3 * CC;
-    float* at = m2 + packed1x1_floats(2 * C, 2 * C);
-    float* ap = at + packed1x1_floats(C, C);
+    float *m2 = c.p->small + sl.m2, *at = c.p->small + sl.at, *ap = c.p->small + sl.ap;
     const float* v = s.qkv + (size_t)2 * C * Pn;
     {   // o = blockdiag(A) v
         Conv1x1Args a{};
-        a.x1 = v; a.C1 = C; a.x1_bstride = (int64_t)3 * C * Pn; a.wp = ap; a.wp_bstride = (int64_t)per;
+        a.x1 = v; a.C1 = C; a.x1_bstride = (int64_t)3 * C * Pn; a.wp = ap; a.wp_bstride = (int64_t)sl.per;
         a.out = o; a.out_bstride = (int64_t)C * Pn; a.Cout = C; a.B = c.B; a.P = Pn; a.w = ww;
         RF_TRY(launch_conv1x1(a, c.st));
     }
     RF_TRY(b_conv1x1_dw(c, d_x1, C, o, C, c.G(x.proj_w), C, 0, c.G(x.proj_b), hh, ww));
     RF_TRY(b_conv1x1_dx(c, d_x1, C, x.proj_w, C, d_o, Pn));
     // dA per image: on the dX chain (the softmax adjoint waits for it)
-    RF_TRY(launch_gram2(d_o, (int64_t)C * Pn, C, v, (int64_t)3 * C * Pn, C, c.p->small, C, c.p->part, c.p->part_floats, c.B, hh, ww, 1, 0, 0, 1, per, 0, c.st));
+    Gram2Launch dA{};
+    dA.a = d_o; dA.a_bstride = (int64_t)C * Pn; dA.Ca = C;
+    dA.b = v; dA.b_bstride = (int64_t)3 * C * Pn; dA.Cb = C;
+    dA.out = c.p->small; dA.ld = C; dA.per_image = true; dA.out_istride = sl.per;
+    dA.partial = c.p->part; dA.partial_cap = c.p->part_floats; dA.B = c.B; dA.h = hh; dA.w = ww; dA.ntap = 1;
+    RF_TRY(launch_gram2(dA, c.st));
     RF_TRY(attn_small(c, s, h->prm(x.temperature), C, heads, 0, c.G(x.temperature)));
     {   // d(qkv): [dq ; dk] = M2 [q ; k],  dv = blockdiag(A^T) do
         Conv1x1Args a{};
-        a.x1 = s.qkv; a.C1 = 2 * C; a.x1_bstride = (int64_t)3 * C * Pn; a.wp = m2; a.wp_bstride = (int64_t)per;
+        a.x1 = s.qkv; a.C1 = 2 * C; a.x1_bstride = (int64_t)3 * C * Pn; a.wp = m2; a.wp_bstride = (int64_t)sl.per;
         a.out = d_qkv; a.out_bstride = (int64_t)3 * C * Pn; a.Cout = 2 * C; a.B = c.B; a.P = Pn; a.w = ww;
         RF_TRY(launch_conv1x1(a, c.st));
         Conv1x1Args d{};
-        d.x1 = d_o; d.C1 = C; d.x1_bstride = (int64_t)C * Pn; d.wp = at; d.wp_bstride = (int64_t)per;
+        d.x1 = d_o; d.C1 = C; d.x1_bstride = (int64_t)C * Pn; d.wp = at; d.wp_bstride = (int64_t)sl.per;
         d.out = d_qkv + (size_t)2 * C * Pn; d.out_bstride = (int64_t)3 * C * Pn; d.Cout = C; d.B = c.B; d.P = Pn; d.w = ww;
         RF_TRY(launch_conv1x1(d, c.st));
     }
@@ -719,8 +622,12 @@ int rf_train_step(rf_handle* h, const float* in, const float* gt, float* grads, 
         RF_TRY(launch_chan_sum(p.tA, (int64_t)C * Pn, c.G(h->up_b[i - 1]), p.part, B, C, Pn, 1, st));
         RF_TRY(launch_pixel_unshuffle2(p.tA, p.tB, B, C, hh / 2, ww / 2, st));                 // [B, 4C, hh/2, ww/2]
         const float* xin = (i == 1) ? p.st[4].out : p.st[4 + i - 1].out;
-        RF_TRY(launch_gram2(xin, (int64_t)2 * C * (Pn / 4), 2 * C, p.tB, (int64_t)4 * C * (Pn / 4), 4 * C, c.G(h->up_w[i - 1]), 4 * C, p.part, p.part_floats, B, hh / 2, ww / 2,
-                            1, 0, 0, 0, 0, 1, st));
+        Gram2Launch g{};
+        g.a = xin; g.a_bstride = (int64_t)2 * C * (Pn / 4); g.Ca = 2 * C;
+        g.b = p.tB; g.b_bstride = (int64_t)4 * C * (Pn / 4); g.Cb = 4 * C;
+        g.out = c.G(h->up_w[i - 1]); g.ld = 4 * C; g.accumulate = true;
+        g.partial = p.part; g.partial_cap = p.part_floats; g.B = B; g.h = hh / 2; g.w = ww / 2; g.ntap = 1;
+        RF_TRY(launch_gram2(g, st));
         Conv1x1Args a{};
         RF_TRY(c.pk(h->up_w[i - 1], PF_CTB, &a.wp));
         a.wp3 = c.pk(h->up_w[i - 1], PF_CTB3);

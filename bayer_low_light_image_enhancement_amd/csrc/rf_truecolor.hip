@@ -322,17 +322,16 @@ struct TcFrontBufs { float *cin4, *lin3, *t16, *crcb, *t32, *d3, *rgb, *ll[3], *
 static TcFrontBufs tc_front_layout(float* s, int B, int H, int W, int levels) {
     const size_t hw = (size_t)H * W;
     TcFrontBufs f{};
-    size_t off = 0;
-    auto take = [&](size_t n) { float* p = s + off; off += align_up(n, 64); return p; };
-    f.cin4 = take(B * 4 * hw); f.lin3 = take(B * 3 * hw); f.t16 = take(B * 16 * hw); f.crcb = take(B * 2 * hw);
-    f.t32 = take(B * 32 * hw); f.d3 = take(B * 3 * hw); f.rgb = take(B * 3 * hw);
+    Bump b{s};
+    f.cin4 = b.take(B * 4 * hw); f.lin3 = b.take(B * 3 * hw); f.t16 = b.take(B * 16 * hw); f.crcb = b.take(B * 2 * hw);
+    f.t32 = b.take(B * 32 * hw); f.d3 = b.take(B * 3 * hw); f.rgb = b.take(B * 3 * hw);
     int h = H, w = W;
     for (int i = 0; i < levels; ++i) {
         h = (h + 1) / 2; w = (w + 1) / 2;
         f.lh[i] = h; f.lw[i] = w;
-        f.ll[i] = take((size_t)B * h * w); f.mag[i] = take((size_t)B * h * w);
+        f.ll[i] = b.take((size_t)B * h * w); f.mag[i] = b.take((size_t)B * h * w);
     }
-    f.amax = reinterpret_cast<int*>(take(B));
+    f.amax = reinterpret_cast<int*>(b.take(B));
     return f;
 }
 

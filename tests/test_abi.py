@@ -132,3 +132,51 @@ def test_handle_plans_and_gradient_ranges(variant, dim):
         assert lib.rf_grad_range(h, n.value, C.byref(off), C.byref(cnt)) == -22
     finally:
         lib.rf_destroy(h)
+
+
+# rf_train_workspace_bytes(1, 64, 64) and (4, 512, 512) as the library returned them at 78881de, before the schedules' seven
+# bump allocators became one (same handles as above)
+TRAIN_BYTES = {
+    ("plain", 32): (121401088, 14426197504),
+    ("flca", 16): (42835968, 7732380160),
+    ("flca", 32): (109422336, 15341869568),
+}
+
+
+@pytest.mark.parametrize("variant,dim", list(TRAIN_BYTES))
+def test_train_workspace_bytes(variant, dim):
+    lib = _lib.load()
+    rc, h = make(dim, {"flca": _lib.RF_VARIANT_FLCA, "plain": _lib.RF_VARIANT_PLAIN}[variant])
+    assert rc == 0
+    try:
+        sz = C.c_size_t()
+        got = []
+        for b, hh, ww in ((1, 64, 64), (4, 512, 512)):
+            assert lib.rf_train_workspace_bytes(h, b, hh, ww, C.byref(sz)) == 0
+            got.append(sz.value)
+        assert tuple(got) == TRAIN_BYTES[(variant, dim)]
+    finally:
+        lib.rf_destroy(h)
+
+
+# operator scratch sizes as the library returned them at 78881de: one small shape (2 images, 64 channels, 32 x 32: the
+# attn_mid path) and one of BASELINE config 2's size (8 images, 32 channels, 512 x 512) each; heads 8, ffn_expansion 2
+SCRATCH_BYTES = {
+    ("rf_chan_attn_scratch_bytes", (2, 64, 8, 32, 32)): 3620864,
+    ("rf_chan_attn_scratch_bytes", (8, 32, 8, 512, 512)): 1612888064,
+    ("rf_transformer_block_scratch_bytes", (2, 64, 8, 2, 32, 32)): 4308992,
+    ("rf_transformer_block_scratch_bytes", (8, 32, 8, 2, 512, 512)): 1896503296,
+    ("rf_flca_scratch_bytes", (2, 64, 32, 32)): 1024,
+    ("rf_flca_scratch_bytes", (8, 32, 512, 512)): 263168,
+    ("rf_feb_scratch_bytes", (2, 64, 32, 32)): 3014656,
+    ("rf_feb_scratch_bytes", (8, 32, 512, 512)): 1480069120,
+    ("rf_ffab_scratch_bytes", (2, 64, 32, 32)): 12419072,
+    ("rf_ffab_scratch_bytes", (8, 32, 512, 512)): 6181388288,
+}
+
+
+@pytest.mark.parametrize("fn,shape", list(SCRATCH_BYTES))
+def test_operator_scratch_bytes(fn, shape):
+    sz = C.c_size_t()
+    assert getattr(_lib.load(), fn)(*shape, C.byref(sz)) == 0
+    assert sz.value == SCRATCH_BYTES[(fn, shape)]
