@@ -46,6 +46,7 @@ SIGNATURES = {
     "rf_forward": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     "rf_forward_stage": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "rf_set_shard": (_i, [_vp, _i, _i, _i, ALLREDUCE_FN, _vp]),
+    "rf_set_shard_grid": (_i, [_vp, _i, _i, _i, _i, _i, _i, ALLREDUCE_FN, _vp]),
     "rf_flat_param_floats": (_i, [_vp, _psz]),
     "rf_flat_offset": (_i, [_vp, _i, _psz]),
     "rf_train_workspace_bytes": (_i, [_vp, _i, _i, _i, _psz]),

@@ -58,6 +58,10 @@ int gram_plan(int B, int C, int heads, int P, int* nslab, int* slab, size_t* par
     return RF_OK;
 }
 
+// XMASK: only columns [a.x_lo, a.x_hi) of the pixels in range enter the sums (a spatial shard on a grid of windows).  A column
+// range is not a range of the linear pixel index, so it is a per-pixel test on x = n mod w; the loads stay unconditional and
+// the VALUES are masked.  The instantiation without the mask is the kernel every other launch runs, instruction for instruction.
+template <bool XMASK>
 __global__ void __launch_bounds__(256) gram_kernel(GramArgs a, int vec) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = lane & 15, kq = lane >> 4;
@@ -100,14 +104,35 @@ __global__ void __launch_bounds__(256) gram_kernel(GramArgs a, int vec) {
     // a wave step covers 16 pixels: lane (i, kq) holds pixels n + 4kq .. 4kq+3 of channel row i.
     // The k rows of the diagonal tile (for |k|^2) are the band tile tq - tklo: no separate load.
     const int td = tq - tklo;
-    auto mfma_step = [&](const float4& qv, const float4 (&kv)[kMaxBand]) __attribute__((always_inline)) {
-        const float qa[4] = {qv.x, qv.y, qv.z, qv.w};
+    // bit m: pixel nn + m lies in the counted columns (a group of 4 may wrap into the next row when w % 4 != 0)
+    auto keep4 = [&](int nn) -> unsigned {
+        int x = nn % a.w;
+        unsigned keep = 0;
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            keep |= (x >= a.x_lo && x < a.x_hi ? 1u : 0u) << m;
+            if (++x == a.w) x = 0;
+        }
+        return keep;
+    };
+    auto mfma_step = [&](const float4& qv, const float4 (&kv)[kMaxBand], int nn) __attribute__((always_inline)) {
+        float qa[4] = {qv.x, qv.y, qv.z, qv.w};
+        unsigned keep = 15u;
+        if constexpr (XMASK) {
+            keep = keep4(nn);
+#pragma unroll
+            for (int m = 0; m < 4; ++m) qa[m] = (keep >> m & 1u) ? qa[m] : 0.f;
+        }
 #pragma unroll
         for (int m = 0; m < 4; ++m) nq = fmaf(qa[m], qa[m], nq);
 #pragma unroll
         for (int t = 0; t < kMaxBand; ++t) {
             if (t < nb) {
-                const float kt[4] = {kv[t].x, kv[t].y, kv[t].z, kv[t].w};
+                float kt[4] = {kv[t].x, kv[t].y, kv[t].z, kv[t].w};
+                if constexpr (XMASK) {
+#pragma unroll
+                    for (int m = 0; m < 4; ++m) kt[m] = (keep >> m & 1u) ? kt[m] : 0.f;
+                }
 #pragma unroll
                 for (int m = 0; m < 4; ++m) g[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(qa[m], kt[m], g[t], 0, 0, 0);
                 if (t == td) {
@@ -134,10 +159,10 @@ __global__ void __launch_bounds__(256) gram_kernel(GramArgs a, int vec) {
         for (; n < n_hi; n += 128) {
             const bool more1 = n + 64 < n_hi;
             load_step(more1 ? n + 64 : n, q1, k1);
-            mfma_step(q0, k0);
+            mfma_step(q0, k0, n + 4 * kq);
             if (!more1) break;
             load_step(n + 128 < n_hi ? n + 128 : n, q0, k0);
-            mfma_step(q1, k1);
+            mfma_step(q1, k1, n + 64 + 4 * kq);
         }
     } else {
         for (int n = n_lo + wave * 16; n < n_hi; n += 64) {
@@ -147,7 +172,7 @@ __global__ void __launch_bounds__(256) gram_kernel(GramArgs a, int vec) {
 #pragma unroll
             for (int t = 0; t < kMaxBand; ++t)
                 kv[t] = (t < nb) ? load4(kb, 16 * (tklo + t) + i, nn) : make_float4(0.f, 0.f, 0.f, 0.f);
-            mfma_step(qv, kv);
+            mfma_step(qv, kv, nn);
         }
     }
 
@@ -179,7 +204,10 @@ int launch_gram(const GramArgs& a, hipStream_t st) {
     dim3 grid((unsigned)a.nslab, (unsigned)cdiv(a.C, 16), (unsigned)a.B);
     const double c = (double)a.C / a.heads;
     ProfScope prof(st, "gram_kernel", 2.0 * a.C * c * a.P * a.B, 8.0 * a.C * (double)a.P * a.B);
-    gram_kernel<<<grid, 256, 0, st>>>(a, vec);
+    RF_CHECK_ARG(a.x_hi == 0 || (a.w > 0 && a.P % a.w == 0 && a.x_lo >= 0 && a.x_lo < a.x_hi && a.x_hi <= a.w),
+                 "gram: columns [%d, %d) outside the %d-wide image", a.x_lo, a.x_hi, a.w);
+    if (a.x_hi > 0) gram_kernel<true><<<grid, 256, 0, st>>>(a, vec);
+    else gram_kernel<false><<<grid, 256, 0, st>>>(a, vec);
     return check_launch("gram");
 }
 

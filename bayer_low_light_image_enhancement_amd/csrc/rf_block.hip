@@ -42,7 +42,7 @@ int run_chan_attn(const TbParams& p, const float* in, float* out, bool residual,
         // LN1 -> qkv 1x1 -> depthwise 3x3 -> {Gram partials, v} in one kernel: qkv never reaches HBM
         RF_TRY(fused_attn_plan(hh, ww, &nslab, &partial_floats, B, C));
         RF_TRY(launch_attn_front(in, buf.qkv, partial, nslab, p.ln1_w, p.ln1_b, p.qkv_wp3, p.qkv_b, p.qkv_dw_w, p.qkv_dw_b, B, C, hh, ww, st,
-                                 p.ylo, p.yhi));
+                                 p.ylo, p.yhi, p.xlo, p.xhi));
         av.x1 = buf.qkv; av.x1_bstride = (int64_t)C * Pn;
     } else {
         Conv1x1Args q{};
@@ -59,7 +59,7 @@ int run_chan_attn(const TbParams& p, const float* in, float* out, bool residual,
         if (!no_fuse && attn_mid_supported(C, heads, hh, ww)) {
             // depthwise 3x3 of q, k, v + Gram partials in one kernel: dw(q), dw(k) never reach HBM
             RF_TRY(attn_mid_plan(hh, ww, &nslab, &partial_floats, B, C));
-            RF_TRY(launch_attn_mid(buf.pre, buf.qkv, partial, nslab, p.qkv_dw_w, p.qkv_dw_b, B, C, hh, ww, st, p.ylo, p.yhi));
+            RF_TRY(launch_attn_mid(buf.pre, buf.qkv, partial, nslab, p.qkv_dw_w, p.qkv_dw_b, B, C, hh, ww, st, p.ylo, p.yhi, p.xlo, p.xhi));
             av.x1 = buf.qkv; av.x1_bstride = (int64_t)C * Pn;
         } else {
             DwConvArgs d{};
@@ -73,6 +73,7 @@ int run_chan_attn(const TbParams& p, const float* in, float* out, bool residual,
             g.B = B; g.C = C; g.heads = heads; g.P = Pn; g.partial = partial;
             RF_TRY(gram_plan(B, C, heads, Pn, &g.nslab, &g.slab, &partial_floats));
             g.p_lo = p.ylo * ww; g.p_hi = p.yhi * ww;
+            if (p.xhi > 0 && (p.xlo > 0 || p.xhi < ww)) { g.w = ww; g.x_lo = p.xlo; g.x_hi = p.xhi; }
             RF_TRY(launch_gram(g, st));
             nslab = g.nslab;
             av.x1 = buf.qkv + (size_t)2 * C * Pn; av.x1_bstride = (int64_t)3 * C * Pn;

@@ -276,6 +276,7 @@ struct GramArgs {
     float* partial;                   // [B][nslab][C][bandw + 2]  (see gram_partial_floats)
     int nslab, slab;
     int p_lo = 0, p_hi = 0;           // pixels [p_lo, p_hi) enter the statistics (p_hi = 0: all); see rf_set_shard
+    int w = 0, x_lo = 0, x_hi = 0;    // ... and of those only columns [x_lo, x_hi) of the w-wide image (x_hi = 0: all); rf_set_shard_grid
 };
 int gram_plan(int B, int C, int heads, int P, int* nslab, int* slab, size_t* partial_floats);
 int launch_gram(const GramArgs& a, hipStream_t st);
@@ -292,13 +293,14 @@ bool fused_attn_supported(int C, int heads, int h, int w);
 int fused_attn_plan(int h, int w, int* nslab, size_t* partial_floats, int B, int C);
 int launch_attn_front(const float* x, float* v, float* partial, int nslab, const float* ln_w, const float* ln_b,
                       const void* wp /* b3 */, const float* bq, const float* wd, const float* bd, int B, int C, int h, int w, hipStream_t st,
-                      int ylo = 0, int yhi = 0 /* rows [ylo, yhi) enter the Gram statistics; yhi = 0: all */);
+                      int ylo = 0, int yhi = 0 /* rows [ylo, yhi) enter the Gram statistics; yhi = 0: all */,
+                      int xlo = 0, int xhi = 0 /* ... and columns [xlo, xhi), multiples of 4 (xhi: or w); xhi = 0: all */);
 
 // qkv [B,3C,h,w] -> depthwise 3x3 -> Gram partials of (q,k) + v, for C = 64 / 128
 bool attn_mid_supported(int C, int heads, int h, int w);
 int attn_mid_plan(int h, int w, int* nslab, size_t* partial_floats, int B, int C);
 int launch_attn_mid(const float* qkv, float* v, float* partial, int nslab, const float* wd, const float* bd,
-                    int B, int C, int h, int w, hipStream_t st, int ylo = 0, int yhi = 0);
+                    int B, int C, int h, int w, hipStream_t st, int ylo = 0, int yhi = 0, int xlo = 0, int xhi = 0);
 
 // ---- TransformerBlock schedule (rf_block.hip)
 struct TbParams {
@@ -307,9 +309,10 @@ struct TbParams {
     const float *ln2_w, *ln2_b, *pw1_wp /* packed */, *pw1_b, *dw_w, *dw_b, *pw2_wp /* packed */, *pw2_b;
     const void *qkv_wp3, *pw1_wp3, *pw2_wp3;   // b3 forms of the three packed weights (nullptr: f32 kernels only)
     int log_temperature;                       // `temperature` holds log T (TrueColorRawFormer, BayerTORGBColorMultiLvl.py:331,344)
-    // spatial shard (rf_set_shard): rows [ylo, yhi) of this level enter the Gram statistics, and `allreduce` sums the
+    // spatial shard (rf_set_shard / rf_set_shard_grid): rows [ylo, yhi) and columns [xlo, xhi) (xhi = 0: all) of this level
+    // enter the Gram statistics, and `allreduce` sums the
     // slab partials over the ranks before the softmax (nullptr: single device)
-    int ylo = 0, yhi = 0;
+    int ylo = 0, yhi = 0, xlo = 0, xhi = 0;
     void (*allreduce)(void* user, float* buf, size_t n, int op, void* stream) = nullptr;
     void* allreduce_user = nullptr;
     // composed stage tail: on the op-by-op FFN path stop after depthwise 3x3 + GELU -- x + attn(..) stays in the x1 buffer, the
@@ -420,6 +423,7 @@ struct FlcaSpatialArgs {
     float* partial;                                      // [B][nblk][C] per-block channel sums
     int B, C, h, w, nblk;
     int ylo = 0, yhi = 0;                                // rows [ylo, yhi) enter the channel sums (yhi = 0: all); see rf_set_shard
+    int xlo = 0, xhi = 0;                                // ... and columns [xlo, xhi) of them (xhi = 0: all); see rf_set_shard_grid
     void set_params(const FlcaPrm& p) {                  // (the kernels take this struct by value: its layout is theirs)
         w_low = p.w_low; w_high = p.w_high; w_chr = p.w_chr;
         alpha = p.alpha; beta = p.beta; gamma = p.gamma;

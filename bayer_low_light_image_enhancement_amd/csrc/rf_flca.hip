@@ -185,7 +185,8 @@ __global__ void __launch_bounds__(256) flca_spatial_vec_kernel(FlcaSpatialArgs a
     const int p = (blk * 256 + threadIdx.x) * PX;
     const bool live = p < P;
     const int y = live ? p / w : 0, x = live ? p - (p / w) * w : 0;
-    const bool counted = y >= a.ylo && y < (a.yhi > 0 ? a.yhi : h);      // rows of the squeeze-excite pooling
+    // rows and columns of the squeeze-excite pooling (column bounds are multiples of PX or w: whole lane groups)
+    const bool counted = y >= a.ylo && y < (a.yhi > 0 ? a.yhi : h) && x >= a.xlo && x < (a.xhi > 0 ? a.xhi : w);
     float nb[4][3][PX + 2];
     const float* gb = a.guide + b * 4 * (size_t)P;
 #pragma unroll
@@ -269,7 +270,7 @@ __global__ void __launch_bounds__(256) flca_spatial_kernel(FlcaSpatialArgs a) {
     const int p = blk * 256 + threadIdx.x;
     const bool live = p < P;
     const int y = live ? p / w : 0, x = live ? p % w : 0;
-    const bool counted = y >= a.ylo && y < (a.yhi > 0 ? a.yhi : h);
+    const bool counted = y >= a.ylo && y < (a.yhi > 0 ? a.yhi : h) && x >= a.xlo && x < (a.xhi > 0 ? a.xhi : w);
     // 3x3 neighbourhoods of the four guidance planes, zero padded
     float nb[4][9];
     const float* gb = a.guide + b * 4 * (size_t)P;

@@ -639,6 +639,7 @@ struct AttnFrontArgs {
     const float* bd;       // [3C]
     int B, h, w, tiles_x, ntiles, nslab;
     int ylo, yhi;          // rows [ylo, yhi) enter the Gram statistics (a spatial shard's interior; the whole image otherwise)
+    int xlo, xhi;          // ... and columns [xlo, xhi) of them, both multiples of 4 or xhi = w: whole 4-pixel groups
 };
 
 template <int C>
@@ -714,7 +715,7 @@ __global__ void __launch_bounds__(256, 2) attn_front_kernel(AttnFrontArgs a) {
 #pragma unroll 1                                         // unrolled, the hoisted stencil loads push the kernel into scratch
             for (int st = 0; st < 4; ++st) {
                 const int xo = x0 + 16 * st + 4 * kq;
-                const bool ok = yo >= a.ylo && yo < a.yhi && xo < w;
+                const bool ok = yo >= a.ylo && yo < a.yhi && xo >= a.xlo && xo < a.xhi;
                 float qa[4], kb[4];
                 stencil4_wide(mid + j * PSG + wave * HC + 16 * st + 4 * kq + 4, wd_l + cq * 9, bd_l[cq], qa);
                 stencil4_wide(mid + (16 + j) * PSG + wave * HC + 16 * st + 4 * kq + 4, wd_l + ck * 9, bd_l[ck], kb);
@@ -805,10 +806,11 @@ int fused_attn_plan(int h, int w, int* nslab, size_t* partial_floats, int B, int
 
 int launch_attn_front(const float* x, float* v, float* partial, int nslab, const float* ln_w, const float* ln_b,
                       const void* wp, const float* bq, const float* wd, const float* bd, int B, int C, int h, int w, hipStream_t st,
-                      int ylo, int yhi) {
+                      int ylo, int yhi, int xlo, int xhi) {
     RF_CHECK_ARG(C == 32 && w % 4 == 0 && B <= 65535, "attn_front: unsupported shape C=%d %dx%d", C, h, w);
     RF_CHECK_ARG(aligned16(x) && aligned16(v), "attn_front: buffers must be 16-byte aligned");
-    AttnFrontArgs a{x, v, partial, ln_w, ln_b, wp, bq, wd, bd, B, h, w, cdiv(w, fused::TW), 0, nslab, ylo, (yhi > 0 && yhi < h) ? yhi : h};
+    AttnFrontArgs a{x, v, partial, ln_w, ln_b, wp, bq, wd, bd, B, h, w, cdiv(w, fused::TW), 0, nslab, ylo, (yhi > 0 && yhi < h) ? yhi : h,
+                    xlo, (xhi > 0 && xhi < w) ? xhi : w};
     a.ntiles = a.tiles_x * cdiv(h, fused::TH);
     const double px = (double)B * h * w;
     ProfScope prof(st, "attn_front_kernel<32>", px * (6.0 * C * C + 54.0 * C + 4.0 * C * 16), px * 8.0 * C);
@@ -834,6 +836,7 @@ struct AttnMidArgs {
     const float* bd;       // [3C]
     int B, h, w, tiles_x, ntiles, nslab;
     int ylo, yhi;          // as AttnFrontArgs
+    int xlo, xhi;
     int rgroups;           // gridDim.z: the rounds (Gram tiles, then v parts) are split over this many workgroups per slab
 };
 
@@ -968,7 +971,7 @@ __global__ void __launch_bounds__(256, 2) attn_mid_kernel(AttnMidArgs a) {
 #pragma unroll 1
                 for (int st = 0; st < 4; ++st) {
                     const int xo = x0 + 16 * st + 4 * kq;
-                    const bool ok = yo >= a.ylo && yo < a.yhi && xo < w;
+                    const bool ok = yo >= a.ylo && yo < a.yhi && xo >= a.xlo && xo < a.xhi;
                     float qa[4], kb[4];
                     stencil4_wide_r(mid + j * PSG + 16 * st + 4 * kq + 4, ro, wd_l + cq * 9, bd_l[cq], qa);
                     stencil4_wide_r(mid + (16 + j) * PSG + 16 * st + 4 * kq + 4, ro, wd_l + ck * 9, bd_l[ck], kb);
@@ -1040,10 +1043,11 @@ bool attn_mid_supported(int C, int heads, int h, int w) {
 }
 
 int launch_attn_mid(const float* qkv, float* v, float* partial, int nslab, const float* wd, const float* bd,
-                    int B, int C, int h, int w, hipStream_t st, int ylo, int yhi) {
+                    int B, int C, int h, int w, hipStream_t st, int ylo, int yhi, int xlo, int xhi) {
     RF_CHECK_ARG((C == 64 || C == 128) && w % 4 == 0 && B <= 65535, "attn_mid: unsupported shape C=%d %dx%d", C, h, w);
     RF_CHECK_ARG(aligned16(qkv) && aligned16(v), "attn_mid: buffers must be 16-byte aligned");
-    AttnMidArgs a{qkv, v, partial, wd, bd, B, h, w, cdiv(w, fused::TW), 0, nslab, ylo, (yhi > 0 && yhi < h) ? yhi : h, 1};
+    AttnMidArgs a{qkv, v, partial, wd, bd, B, h, w, cdiv(w, fused::TW), 0, nslab, ylo, (yhi > 0 && yhi < h) ? yhi : h,
+                  xlo, (xhi > 0 && xhi < w) ? xhi : w, 1};
     a.ntiles = a.tiles_x * cdiv(h, fused::TH);
     if ((long)nslab * B < 256) a.rgroups = 3;               // C / 16 + C / 32 rounds: 6 (C = 64) or 12 (C = 128)
     const double px = (double)B * h * w;

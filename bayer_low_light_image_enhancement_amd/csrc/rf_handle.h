@@ -115,9 +115,11 @@ struct rf_handle {
     std::vector<GradRange> grad_ranges;
     std::vector<CachePack> cache_packs;
     size_t cache_floats = 0;
-    // spatial shard of one frame (rf_set_shard): interior rows [y_lo, y_hi) of the local window and the frame's total rows, in
-    // packed (level-0) rows; `allreduce` sums a float buffer over the ranks on the given stream
+    // spatial shard of one frame (rf_set_shard / rf_set_shard_grid): interior rows [y_lo, y_hi) of the local window and the
+    // frame's total rows, in packed (level-0) rows, and the same for columns (x_hi = 0: all columns, total_cols = 0: the window's
+    // width -- a row shard); `allreduce` sums a float buffer over the ranks on the given stream
     int shard_y_lo = 0, shard_y_hi = 0, shard_total_rows = 0;
+    int shard_x_lo = 0, shard_x_hi = 0, shard_total_cols = 0;
     void (*shard_allreduce)(void* user, float* buf, size_t n, int op, void* stream) = nullptr;
     void* shard_user = nullptr;
     // second stream: the forward's branches and the training step's weight-gradient kernels run on it (SideStream above)

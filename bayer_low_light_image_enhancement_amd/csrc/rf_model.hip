@@ -233,11 +233,15 @@ int run_stage(rf_handle* h, int i, const float* in, float* out, float* ws, const
     tp.dw_w = h->prm(x.dw_w); tp.dw_b = h->prm(x.dw_b);
     tp.pw2_wp = h->pk(x.pw2_w); tp.pw2_b = h->prm(x.pw2_b);
     tp.qkv_wp3 = h->pk3(x.qkv_w); tp.pw1_wp3 = h->pk3(x.pw1_w); tp.pw2_wp3 = h->pk3(x.pw2_w);
-    // spatial shard: this level's interior rows and the frame's pixel count for the pooled mean
+    // spatial shard: this level's interior rows and columns, and the frame's pixel count for the pooled mean
     const bool sharded = h->shard_allreduce != nullptr;
     const int ylo = sharded ? h->shard_y_lo >> lvl : 0, yhi = sharded ? h->shard_y_hi >> lvl : 0;
-    const int P_pool = sharded ? (h->shard_total_rows >> lvl) * ww : Pn;
-    if (sharded) { tp.ylo = ylo; tp.yhi = yhi; tp.allreduce = h->shard_allreduce; tp.allreduce_user = h->shard_user; }
+    const int xlo = sharded ? h->shard_x_lo >> lvl : 0, xhi = sharded ? h->shard_x_hi >> lvl : 0;
+    const int P_pool = sharded ? (h->shard_total_rows >> lvl) * (h->shard_total_cols ? h->shard_total_cols >> lvl : ww) : Pn;
+    if (sharded) {
+        tp.ylo = ylo; tp.yhi = yhi; tp.xlo = xlo; tp.xhi = xhi;
+        tp.allreduce = h->shard_allreduce; tp.allreduce_user = h->shard_user;
+    }
     TbBufOffsets to{p.bufA, p.bufB, p.x1, p.gram_partial, p.wfold_attn, p.wfold_attn3};
     // Composed tail: where the FFN runs op by op, its last GEMM (x1 + W2 g + b2 -> trans, K = hidden) and channel_reduce
     // ([Wa' | Wb] [xs ; trans], K = 2C) become ONE GEMM over [xs ; x1 ; g] with [Wa' | Wb | Wb W2] (same MFMA count; `trans` --
@@ -284,7 +288,7 @@ int run_stage(rf_handle* h, int i, const float* in, float* out, float* ws, const
         s.feat = in; s.xs = xs; s.guide = ws + p.guide[lvl];
         s.set_params(fp);
         s.partial = ws + p.flca_partial; s.B = B; s.C = C; s.h = hh; s.w = ww; s.nblk = flca_nblk(hh, ww);
-        s.ylo = ylo; s.yhi = yhi;
+        s.ylo = ylo; s.yhi = yhi; s.xlo = xlo; s.xhi = xhi;
         RF_TRY(launch_flca_spatial(s, side));
         if (sharded) h->shard_allreduce(h->shard_user, s.partial, (size_t)B * s.nblk * C, 0, (void*)side);
         RF_TRY(launch_flca_se_fold(s.partial, s.nblk, P_pool, fp.se, h->prm(x.cr_w), ws + p.wfold_cr, ws + p.wfold_cr3, ws + p.ch, B, C, side,
@@ -550,19 +554,40 @@ int rf_workspace_bytes(const rf_handle* h, int B, int H, int W, size_t* bytes) {
     return RF_OK;
 }
 
-int rf_set_shard(rf_handle* h, int y_lo, int y_hi, int total_rows, rf_allreduce_fn allreduce, void* user) {
-    RF_CHECK_ARG(h, "rf_set_shard: null handle");
+// the one place that writes the shard state: rf_set_shard is the all-columns case (x_lo = x_hi = total_cols = 0)
+static int set_shard_state(rf_handle* h, const char* who, int y_lo, int y_hi, int total_rows, int x_lo, int x_hi, int total_cols,
+                           rf_allreduce_fn allreduce, void* user) {
+    RF_CHECK_ARG(h, "%s: null handle", who);
     if (!allreduce) {
         h->shard_y_lo = h->shard_y_hi = h->shard_total_rows = 0;
+        h->shard_x_lo = h->shard_x_hi = h->shard_total_cols = 0;
         h->shard_allreduce = nullptr; h->shard_user = nullptr;
         return RF_OK;
     }
-    RF_CHECK_ARG(h->cfg.variant != RF_VARIANT_TRUECOLOR, "rf_set_shard: variants flca and plain only");
+    RF_CHECK_ARG(h->cfg.variant != RF_VARIANT_TRUECOLOR, "%s: variants flca and plain only", who);
     RF_CHECK_ARG(y_lo >= 0 && y_hi > y_lo && y_lo % 8 == 0 && y_hi % 8 == 0 && total_rows >= y_hi - y_lo && total_rows % 8 == 0,
-                 "rf_set_shard: interior rows [%d, %d) of %d must be multiples of 8", y_lo, y_hi, total_rows);
+                 "%s: interior rows [%d, %d) of %d must be multiples of 8", who, y_lo, y_hi, total_rows);
+    // columns: cuts on multiples of 32 keep the bounds of every level (>> 3 at the coarsest) on the kernels' groups of 4 pixels;
+    // x_hi may instead be the window's width (the frame's right border), which rf_forward checks when it knows the width
+    RF_CHECK_ARG(x_lo >= 0 && x_lo % 32 == 0 && x_hi % 8 == 0 && (x_hi == 0 ? x_lo == 0 && total_cols == 0 : x_hi > x_lo) &&
+                     total_cols >= x_hi - x_lo && total_cols % 8 == 0,
+                 "%s: interior columns [%d, %d) of %d: x_lo must be a multiple of 32, x_hi of 32 or the window's width, the total of 8",
+                 who, x_lo, x_hi, total_cols);
     h->shard_y_lo = y_lo; h->shard_y_hi = y_hi; h->shard_total_rows = total_rows;
+    h->shard_x_lo = x_lo; h->shard_x_hi = x_hi; h->shard_total_cols = total_cols;
     h->shard_allreduce = allreduce; h->shard_user = user;
     return RF_OK;
+}
+
+int rf_set_shard(rf_handle* h, int y_lo, int y_hi, int total_rows, rf_allreduce_fn allreduce, void* user) {
+    return set_shard_state(h, "rf_set_shard", y_lo, y_hi, total_rows, 0, 0, 0, allreduce, user);
+}
+
+int rf_set_shard_grid(rf_handle* h, int y_lo, int y_hi, int total_rows, int x_lo, int x_hi, int total_cols,
+                      rf_allreduce_fn allreduce, void* user) {
+    RF_CHECK_ARG(!allreduce || (x_hi > 0 && total_cols > 0), "rf_set_shard_grid: interior columns [%d, %d) of %d must not be empty",
+                 x_lo, x_hi, total_cols);
+    return set_shard_state(h, "rf_set_shard_grid", y_lo, y_hi, total_rows, x_lo, x_hi, total_cols, allreduce, user);
 }
 
 int rf_forward_stage(rf_handle* h, int stage, const float* in, const float* packed, float* out, void* workspace,
@@ -600,13 +625,16 @@ int rf_forward(rf_handle* h, const float* in, float* out, void* workspace, size_
     RF_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0,
                  "rf_forward: packed size %dx%d must be positive multiples of 8 (mosaic divisible by 16)", H, W);
     RF_CHECK_ARG((size_t)H * W < (1u << 30), "rf_forward: frame too large");
+    RF_CHECK_ARG(!h->shard_allreduce || h->shard_y_hi <= H, "rf_forward: shard interior [%d, %d) outside the %d-row window",
+                 h->shard_y_lo, h->shard_y_hi, H);
+    RF_CHECK_ARG(!h->shard_allreduce || h->shard_x_hi == W || (h->shard_x_hi < W && h->shard_x_hi % 32 == 0),
+                 "rf_forward: shard interior columns [%d, %d) must end on a multiple of 32 inside the %d-column window or at its width",
+                 h->shard_x_lo, h->shard_x_hi, W);
     if (!h->packed) {
         set_error("rf_forward: parameters not packed (call rf_pack_params after rf_set_param)");
         return RF_E_MISSING;
     }
     RF_CHECK_ARG(aligned16(workspace) && aligned16(in) && aligned16(out), "rf_forward: buffers must be 16-byte aligned");
-    RF_CHECK_ARG(!h->shard_allreduce || h->shard_y_hi <= H, "rf_forward: shard interior [%d, %d) outside the %d-row window",
-                 h->shard_y_lo, h->shard_y_hi, H);
     Plan p;
     RF_TRY(make_plan(h, B, H, W, p));
     if (workspace_bytes < p.total * sizeof(float)) {

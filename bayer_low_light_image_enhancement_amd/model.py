@@ -339,14 +339,19 @@ class RawFormer(nn.Module):
                                       int(packed_input), stream), "rf_forward")
         return out
 
-    def forward_window(self, x: torch.Tensor, y_lo: int, y_hi: int, total_rows: int, group=None) -> torch.Tensor:
+    def forward_window(self, x: torch.Tensor, y_lo: int, y_hi: int, total_rows: int, group=None, *,
+                       x_lo: int = 0, x_hi: int = 0, total_cols: Optional[int] = None) -> torch.Tensor:
         """Forward of one rank's WINDOW of a spatially sharded frame (``tiling.forward_full_frame_exact``; C ABI
         ``rf_set_shard``).  ``x``: the window of the mosaic ``[B,1,2Hl,2Wl]``, the same shape on every rank of ``group``;
         ``[y_lo, y_hi)``: this rank's interior rows inside the window and ``total_rows`` the frame's height, in PACKED rows
         (mosaic rows / 2, multiples of 8).  The channel attention's Gram statistics and FLCA's squeeze-excite pooling are
         taken over interior rows and all-reduced over ``group`` (RCCL with the ``nccl`` backend), so interior rows of the
         result equal the whole-frame forward up to summation order when the window reaches ``tiling.HALO_ROWS`` rows beyond
-        the interior (or the frame border).  Rows outside the interior are meaningless."""
+        the interior (or the frame border).  Rows outside the interior are meaningless.
+
+        With ``total_cols`` the window is one of a rows x columns grid (``rf_set_shard_grid``): the interior is also cut to
+        columns ``[x_lo, x_hi)`` of the window, ``total_cols`` is the frame's packed width, ``x_lo`` a multiple of 32 and
+        ``x_hi`` a multiple of 32 or the window's width (``tiling.plan_grid_shards``)."""
         import torch.distributed as dist
 
         if self.variant == "truecolor":
@@ -374,7 +379,13 @@ class RawFormer(nn.Module):
             if st.workspace is None or st.workspace.numel() < sz.value:
                 st.workspace = None
                 st.workspace = torch.empty(sz.value, dtype=torch.uint8, device=x.device)
-            _lib.check(lib.rf_set_shard(st.handle, int(y_lo), int(y_hi), int(total_rows), cb, None), "rf_set_shard")
+            if total_cols is None:
+                if x_lo or x_hi:
+                    raise ValueError("forward_window: x_lo / x_hi need total_cols")
+                _lib.check(lib.rf_set_shard(st.handle, int(y_lo), int(y_hi), int(total_rows), cb, None), "rf_set_shard")
+            else:
+                _lib.check(lib.rf_set_shard_grid(st.handle, int(y_lo), int(y_hi), int(total_rows), int(x_lo), int(x_hi), int(total_cols),
+                                                 cb, None), "rf_set_shard_grid")
             try:
                 out = self._run(x, packed_input=False)
             finally:

@@ -12,7 +12,8 @@ everywhere (attention, squeeze-excite and the luma maximum reduce over ONE image
 
 ``forward_full_frame_exact`` is the exact alternative: row shards with ``HALO_ROWS`` rows of recomputed context whose global
 statistics are all-reduced inside the forward (``RawFormer.forward_window``, C ABI ``rf_set_shard``), so the stitched frame
-equals the whole-frame forward up to summation order.
+equals the whole-frame forward up to summation order.  With ``grid=(R, C)`` the shards are the windows of a rows x columns grid
+(``plan_grid_shards``, C ABI ``rf_set_shard_grid``): less recomputed context per rank than row strips once there are many ranks.
 
 ``forward_full_frame_sharded`` runs rank r's tiles on rank r and stitches the sRGB frame on
 every rank with ONE all-gather of fixed-size tile outputs (RCCL over xGMI with the ``nccl``
@@ -143,7 +144,10 @@ def forward_full_frame_sharded(forward: Callable[[torch.Tensor], torch.Tensor], 
 # convolution chain.  FLCA's gates sit in parallel with the TransformerBlock (3x3 of their level on guidance planes that are
 # Haar bands of the luma, bilinearly resampled to the stage: up to 2 more level-0 rows at level 0); interval propagation
 # through the whole U-Net from 8-aligned cuts gives 77.  HALO_ROWS = 80 = the next multiple of 8: a margin of 3 rows.
+# Every operator on that path is square (3 x 3 convolutions, 2 x 2 re-sampling), so the receptive field is the same along x and
+# HALO_ROWS is also the column halo of a grid of windows (plan_grid_shards).
 HALO_ROWS = 80
+COL_ALIGN = 32  # column cuts and window origins of a grid: 32 >> 3 = 4 pixels at the coarsest level, the kernels' lane-group width
 
 
 @dataclass(frozen=True)
@@ -179,12 +183,120 @@ def plan_row_shards(packed_rows: int, world: int, halo: int = HALO_ROWS) -> List
     return shards
 
 
-def forward_full_frame_exact(model, x: torch.Tensor, group=None, halo: int = HALO_ROWS) -> torch.Tensor:
-    """Row-sharded full-frame forward whose result equals the whole-frame forward (up to fp32 summation order): rank r runs
-    ``model.forward_window`` on its window of the mosaic ``x`` ``[B,1,h,w]`` (h divisible by 16), the statistics are
-    all-reduced inside the forward, and one all-gather of the interior strips stitches the sRGB frame on every rank."""
+@dataclass(frozen=True)
+class ColShard:
+    """The column half of a grid window, in PACKED columns (mosaic columns / 2): ``RowShard`` along x."""
+    start: int      # first column of the window
+    cols: int       # window width (equal on all ranks)
+    x_lo: int       # interior columns [x_lo, x_hi) inside the window ...
+    x_hi: int
+    dst: int        # ... which are columns [dst, dst + x_hi - x_lo) of the frame
+
+
+@dataclass(frozen=True)
+class GridShard:
+    """One rank's window of a rows x columns grid."""
+    row: RowShard
+    col: ColShard
+
+
+def plan_col_shards(packed_cols: int, parts: int, halo: int = HALO_ROWS) -> List[ColShard]:
+    """``plan_row_shards`` along x, with the alignment the kernels' interior masks need: cuts AND window origins are multiples
+    of ``COL_ALIGN`` = 32 packed columns, so that the local bounds are multiples of 4 pixels at every U-Net level.  The frame's
+    width need not be one (2128 = 66.5 x 32): the remainder goes to the last interior, whose ``x_hi`` is the window's width.
+    The last window ends at the frame border and starts on a multiple of 32, so the common window width is congruent to the
+    frame width modulo 32.  Every rank runs the same window, so the width is what costs: the plan takes the SMALLEST width for
+    which ``parts`` interiors with ``halo`` columns of context (or the frame border) on both sides cover the frame, and then
+    cuts as evenly as that width allows -- interiors at the frame border, which need context on one side only, come out wider
+    than an even cut would make them (2128 columns in 4: interiors of 544, 512, 512, 560 in windows of 688; the even 544, 544, 512, 528
+    need 720)."""
+    A = COL_ALIGN
+    if packed_cols % 8 or halo % 8 or halo < 0:
+        raise ValueError("packed columns and halo must be multiples of 8")
+    if parts < 1 or packed_cols // A < parts:
+        raise ValueError(f"{packed_cols} packed columns cannot be cut into {parts} shards of at least {A} columns")
+    last_cut = (packed_cols - 1) // A * A          # cut k lies in [A k, last_cut - A (parts - 1 - k)]: no interior is empty
+
+    def origin(cut: int, cols: int) -> int:        # as far right as the left context, the alignment and the border allow
+        return min(max(cut - halo, 0) // A * A, packed_cols - cols)
+
+    def reach(cut: int, cols: int) -> int:         # the furthest end of an interior that starts at `cut`
+        end = origin(cut, cols) + cols
+        return packed_cols if end >= packed_cols else (end - halo) // A * A
+
+    def cuts_for(cols: int):
+        lo = [0] * parts + [packed_cols]           # lo[k]: the leftmost cut k from which the rest of the frame can still be covered
+        for k in range(parts - 1, 0, -1):
+            fits = [c for c in range(A * k, last_cut - A * (parts - 1 - k) + 1, A) if reach(c, cols) >= lo[k + 1]]
+            if not fits:
+                return None
+            lo[k] = fits[0]
+        if reach(0, cols) < lo[1]:
+            return None
+        cuts = [0]
+        for k in range(1, parts):
+            even = int(round(k * packed_cols / parts / A)) * A
+            c = min(max(even, lo[k], cuts[-1] + A), reach(cuts[-1], cols), last_cut - A * (parts - 1 - k))
+            if c <= cuts[-1]:
+                return None
+            cuts.append(c)
+        return cuts + [packed_cols]
+
+    cols = packed_cols % A or A
+    while cols < packed_cols and cuts_for(cols) is None:
+        cols += A
+    cuts = cuts_for(cols)                           # cols == packed_cols: origin 0 for everyone, always a plan
+    return [ColShard(origin(cuts[k], cols), cols, cuts[k] - origin(cuts[k], cols), cuts[k + 1] - origin(cuts[k], cols), cuts[k])
+            for k in range(parts)]
+
+
+def plan_grid_shards(packed_rows: int, packed_cols: int, grid: Tuple[int, int], halo: int = HALO_ROWS) -> List[GridShard]:
+    """Windows of a ``grid = (R, C)`` cut of the packed frame, rank order row-major: the row plan is ``plan_row_shards``, the
+    column plan ``plan_col_shards``.  All windows have one shape."""
+    rows = plan_row_shards(packed_rows, grid[0], halo)
+    cols = plan_col_shards(packed_cols, grid[1], halo)
+    return [GridShard(r, c) for r in rows for c in cols]
+
+
+def _forward_grid_exact(model, x: torch.Tensor, group, halo: int, grid: Tuple[int, int]) -> torch.Tensor:
     import torch.distributed as dist
 
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    b, _, h, w = x.shape
+    if h % 16 or w % 16:
+        raise ValueError(f"mosaic size {h}x{w} must be divisible by 16")
+    if len(grid) != 2 or grid[0] * grid[1] != world:
+        raise ValueError(f"grid {tuple(grid)} does not have one window for each of the {world} ranks")
+    shards = plan_grid_shards(h // 2, w // 2, grid, halo)
+    me = shards[rank]
+    win = x[:, :, 2 * me.row.start: 2 * (me.row.start + me.row.rows), 2 * me.col.start: 2 * (me.col.start + me.col.cols)].contiguous()
+    o = model.forward_window(win, me.row.y_lo, me.row.y_hi, h // 2, group=group,
+                             x_lo=me.col.x_lo, x_hi=me.col.x_hi, total_cols=w // 2)
+    mh = max(s.row.y_hi - s.row.y_lo for s in shards)
+    mw = max(s.col.x_hi - s.col.x_lo for s in shards)
+    mine = o.new_zeros((b, o.shape[1], 2 * mh, 2 * mw))
+    mine[:, :, : 2 * (me.row.y_hi - me.row.y_lo), : 2 * (me.col.x_hi - me.col.x_lo)] = \
+        o[:, :, 2 * me.row.y_lo: 2 * me.row.y_hi, 2 * me.col.x_lo: 2 * me.col.x_hi]
+    gathered = o.new_empty((world,) + tuple(mine.shape))
+    dist.all_gather_into_tensor(gathered.view(world * b, o.shape[1], 2 * mh, 2 * mw), mine, group=group)
+    out = o.new_empty((b, o.shape[1], h, w))
+    for r, s in enumerate(shards):
+        n, m = 2 * (s.row.y_hi - s.row.y_lo), 2 * (s.col.x_hi - s.col.x_lo)
+        out[:, :, 2 * s.row.dst: 2 * s.row.dst + n, 2 * s.col.dst: 2 * s.col.dst + m] = gathered[r, :, :, :n, :m]
+    return out
+
+
+def forward_full_frame_exact(model, x: torch.Tensor, group=None, halo: int = HALO_ROWS, grid=None) -> torch.Tensor:
+    """Sharded full-frame forward whose result equals the whole-frame forward (up to fp32 summation order): rank r runs
+    ``model.forward_window`` on its window of the mosaic ``x`` ``[B,1,h,w]`` (h divisible by 16), the statistics are
+    all-reduced inside the forward, and one all-gather of the interior strips stitches the sRGB frame on every rank.
+
+    ``grid=None``: row shards, one per rank.  ``grid=(R, C)`` with ``R * C`` = the number of ranks: the windows of
+    ``plan_grid_shards`` (w divisible by 16 too), interiors padded to the largest one for the all-gather."""
+    import torch.distributed as dist
+
+    if grid is not None:
+        return _forward_grid_exact(model, x, group, halo, grid)
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     b, _, h, w = x.shape
     if h % 16:

@@ -96,6 +96,13 @@ int rf_forward(rf_handle* h, const float* in, float* out, void* workspace, size_
  * callback switch sharding off.  Variants flca and plain. */
 typedef void (*rf_allreduce_fn)(void* user, float* buf, size_t n, int op, void* stream);
 int rf_set_shard(rf_handle* h, int y_lo, int y_hi, int total_rows, rf_allreduce_fn allreduce, void* user);
+/* The same on a rows x columns grid of windows: the interior is the rectangle [y_lo, y_hi) x [x_lo, x_hi) of the local window,
+ * total_cols the frame's packed width.  x_lo is a multiple of 32 and x_hi a multiple of 32 or the window's width (the frame's
+ * right border; checked by rf_forward): at every U-Net level the bounds then fall on the kernels' groups of 4 pixels, which
+ * means that window origins are multiples of 32 packed columns too.  The receptive field is the same along both axes, so the
+ * halo is the same number of columns.  All ranks run the same window shape.  rf_set_shard is the all-columns case. */
+int rf_set_shard_grid(rf_handle* h, int y_lo, int y_hi, int total_rows, int x_lo, int x_hi, int total_cols,
+                      rf_allreduce_fn allreduce, void* user);
 
 /* One Conv_Transformer stage of the model, exactly as rf_forward schedules it (branch || TransformerBlock -> cat ->
  * 1x1 -> 3x3 -> LeakyReLU; FrequencyawareLumaChromaAttentionRAWFormer.py:257-278, RawFomer_WFB_FFAB/model.py:393-412,
