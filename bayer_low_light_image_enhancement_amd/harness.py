@@ -1,16 +1,22 @@
 """Evaluation-harness mirror of the reference's test loop (test.py:17-40 and 106-143).
 
 ``test.py`` post-processes every prediction on the host: ``clamp(0,1) * 255`` truncated to uint8,
-Bayer-order channel fix-ups, PSNR / SSIM from scikit-image, JPEG + CSV.  Here the conversion and
-the PSNR reduction run on the device with exact integer arithmetic (``csrc/rf_harness.hip``); the
-channel fix-ups keep the reference's function names and semantics.  SSIM is restated on the host
-from scikit-image's definition (7x7 uniform window, K1 = 0.01, K2 = 0.03, sample covariance,
-channel-wise mean) -- scikit-image is not installable here, so SSIM parity is unpinned.
+Bayer-order channel fix-ups, PSNR / SSIM from scikit-image, JPEG + CSV.  Here the conversion, the
+PSNR reduction and the SSIM run on the device with exact integer arithmetic (``csrc/rf_harness.hip``,
+``csrc/rf_ssim.hip``); the channel fix-ups keep the reference's function names and semantics;
+``evaluate_loader`` is the loop and ``write_metrics_csv`` its ``test_metrics.csv`` (no JPEG writing).
+
+SSIM is scikit-image's definition (7x7 uniform window, K1 = 0.01, K2 = 0.03, data range 255, sample
+covariance, mean over the fully covered window positions, channel-wise mean).  scikit-image itself is
+not available where this project is built and tested, so SSIM parity is NOT pinned against
+scikit-image: ``ssim_u8_device`` is tested against two independent float64 restatements of that
+definition -- ``ssim_u8`` below (scipy ``uniform_filter``) and the integral-image restatement in
+``tests/test_ssim.py`` (exact integer window sums).
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Tuple
+from typing import Dict, Tuple
 
 import numpy as np
 import torch
@@ -106,14 +112,61 @@ def ssim_u8(a: np.ndarray, b: np.ndarray) -> float:
     return float(np.mean(vals))
 
 
+def ssim_u8_channel_means(a: torch.Tensor, b: torch.Tensor) -> np.ndarray:
+    """Per-image, per-channel SSIM means of uint8 ``[B,H,W,C]`` device tensors (float64 ``[B,C]`` on the host): the window
+    sums are exact integers and the per-position values are added in a fixed order, so the result is bitwise reproducible
+    and the same for an image alone or in a batch (``csrc/rf_ssim.hip``)."""
+    if a.shape != b.shape or a.dtype != torch.uint8 or b.dtype != torch.uint8 or a.dim() != 4:
+        raise RuntimeError("ssim_u8_device expects two uint8 [B,H,W,C] tensors of the same shape")
+    if a.device.type != "cuda" or b.device != a.device:
+        raise RuntimeError("ssim_u8_device runs on the ROCm device only (ssim_u8 is the host restatement)")
+    a, b = a.contiguous(), b.contiguous()
+    n, h, w, c = a.shape
+    lib = _lib.load()
+    nbytes = C.c_size_t()
+    _lib.check(lib.rf_u8_ssim_scratch_bytes(n, c, h, w, C.byref(nbytes)), "rf_u8_ssim_scratch_bytes")
+    scratch = torch.empty((nbytes.value // 8,), dtype=torch.float64, device=a.device)
+    sums = torch.empty((n, c), dtype=torch.float64, device=a.device)
+    with torch.cuda.device(a.device):
+        _lib.check(lib.rf_u8_ssim(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), C.c_void_p(sums.data_ptr()),
+                                  C.c_void_p(scratch.data_ptr()), n, c, h, w, _stream(a)), "rf_u8_ssim")
+    return sums.cpu().numpy() / float((h - 6) * (w - 6))
+
+
+def ssim_u8_device(a: torch.Tensor, b: torch.Tensor) -> np.ndarray:
+    """``structural_similarity(a[i], b[i], channel_axis=-1)`` (test.py:124) for every image of two uint8 ``[B,H,W,C]`` device
+    tensors: float64 per image, the mean of ``ssim_u8_channel_means`` over the channels."""
+    return ssim_u8_channel_means(a, b).mean(axis=1)
+
+
 def evaluate(pred: torch.Tensor, gt: torch.Tensor, bayer_pattern: str = "RGGB", with_ssim: bool = False) -> Tuple[np.ndarray, np.ndarray]:
     """The body of test.py's loop (test.py:110-124) for a batch: uint8 conversion, Bayer fix-ups on both
-    images, PSNR (and optionally SSIM).  ``pred``/``gt`` are float32 ``[B,3,H,W]`` device tensors."""
+    images, PSNR (and optionally SSIM, on the device).  ``pred``/``gt`` are float32 ``[B,3,H,W]`` device tensors."""
     p8 = auto_correct_rb(correct_bayer_channels(to_uint8_hwc(torch.clamp(pred, 0, 1)), bayer_pattern).contiguous())
     g8 = auto_correct_rb(correct_bayer_channels(to_uint8_hwc(gt), bayer_pattern).contiguous())
     psnr = psnr_u8(p8, g8)
-    ssim = np.array([ssim_u8(p8[i].cpu().numpy(), g8[i].cpu().numpy()) for i in range(p8.shape[0])]) if with_ssim else np.array([])
+    ssim = ssim_u8_device(p8, g8) if with_ssim else np.array([])
     return psnr, ssim
+
+
+def evaluate_loader(model, batches, bayer_pattern: str = "RGGB") -> Dict[str, object]:
+    """test.py:106-137 without the image writing: for every ``(inp, gt)`` batch the forward under ``no_grad`` and the loop body
+    (``evaluate`` with SSIM) for each of its images.  Returns the per-image lists ``psnr`` and ``ssim`` in loader order and
+    their means ``psnr_average`` / ``ssim_average`` (test.py:136-137)."""
+    psnr_val_rgb, ssim_val_rgb = [], []
+    dev = next(model.parameters()).device
+    with torch.no_grad():
+        for inp, gt in batches:
+            psnr, ssim = evaluate(model(inp.to(dev)), gt.to(dev), bayer_pattern, with_ssim=True)
+            psnr_val_rgb.extend(float(v) for v in psnr)
+            ssim_val_rgb.extend(float(v) for v in ssim)
+    return {"psnr": psnr_val_rgb, "ssim": ssim_val_rgb,
+            "psnr_average": float(np.mean(psnr_val_rgb)), "ssim_average": float(np.mean(ssim_val_rgb))}
+
+
+def write_metrics_csv(path, psnr, ssim) -> None:
+    """``test_metrics.csv`` as test.py:141-143 writes it: one ``PSNR,SSIM`` row per image, four decimals."""
+    np.savetxt(path, np.column_stack((psnr, ssim)), delimiter=',', fmt='%.4f')
 
 
 _SID_MODES = {"loader": 0, "rgbg": 0, "rggb": 1, "unshuffle": 1, "mosaic": 2}

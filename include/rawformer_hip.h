@@ -248,6 +248,14 @@ int rf_to_uint8_hwc(const float* in, unsigned char* out, int B, int C, int h, in
 int rf_u8_sse(const unsigned char* a, const unsigned char* b, unsigned long long* sse, int B, size_t n_per_image, void* stream);
 /* per-image, per-channel sums of HWC uint8 images (auto_correct_rb compares channel means, test.py:31-40) */
 int rf_u8_channel_sums(const unsigned char* a, unsigned long long* sums, int B, int C, size_t hw, void* stream);
+/* SSIM (test.py:124, structural_similarity(a, b, channel_axis=-1)) of uint8 HWC images [B,h,w,C]: 7x7 uniform window, K1 0.01,
+ * K2 0.03, data range 255, sample covariance.  The five window sums are exact integers; ssim_sums[b*C + c] (float64) receives the
+ * sum of the per-position values over the (h-6)(w-6) fully covered window positions of channel c, added in a fixed order (bitwise
+ * reproducible, and the same for an image alone or in a batch); the caller divides by (h-6)(w-6) and averages the channels.
+ * scratch: rf_u8_ssim_scratch_bytes bytes, 8-byte aligned, no initialisation needed.  h, w >= 7; C in 1..4; B in 1..65535. */
+int rf_u8_ssim_scratch_bytes(int B, int C, int h, int w, size_t* bytes);
+int rf_u8_ssim(const unsigned char* a, const unsigned char* b, double* ssim_sums /* [B*C] */, void* scratch,
+               int B, int C, int h, int w, void* stream);
 
 /* ---- SID front-end: correctdataloader.py:58-72 (pack_raw), :86 (x ratio),
  * :103 (min 1) fused into one pass over the uint16 Bayer frame [B, 2h, 2w]:

@@ -5,7 +5,7 @@ Each case runs through the C ABI (ops.*) with the library's own HIP-event bracke
 (rf_profile_begin/end), so the figure is the kernel's time on its launch stream, without the
 weight-repack helper that the operator-level entry points run first.
 
-usage: python tools/kbench.py [conv1x1] [conv3x3] [dw] [attn] [flca] [dwt] [--dim 32] [--batch 8] [--size 512]
+usage: python tools/kbench.py [conv1x1] [conv3x3] [dw] [attn] [flca] [dwt] [ssim] [--dim 32] [--batch 8] [--size 512]
 """
 from __future__ import annotations
 
@@ -19,7 +19,7 @@ import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
-from bayer_low_light_image_enhancement_amd import _lib, ops  # noqa: E402
+from bayer_low_light_image_enhancement_amd import _lib, harness, ops  # noqa: E402
 
 
 def timed(fn, iters=10, warm=2):
@@ -89,6 +89,12 @@ def main():
             xx = r(bb, ci, sz, sz)
             report(f"c3 {ci}->{co} {sz}x{sz} B={bb}", timed(lambda: ops.conv3x3(xx, r(co, ci, 3, 3), r(co), act="lrelu")))
             del xx
+    if "ssim" in a.what:   # harness SSIM: a full SID frame and a batch of 8 x 1024 x 1024 (GB/s = the 2 B / element of algorithmic traffic)
+        for bb, hh, ww in ((1, 2848, 4256), (8, 1024, 1024)):
+            ia = torch.randint(0, 256, (bb, hh, ww, 3), dtype=torch.uint8, device=dev)
+            ib = (ia.to(torch.int16) + torch.randint(-9, 10, ia.shape, dtype=torch.int16, device=dev)).clamp(0, 255).to(torch.uint8)
+            report(f"ssim {bb}x{hh}x{ww}x3", timed(lambda: harness.ssim_u8_channel_means(ia, ib)))
+            del ia, ib
     if "dwt" in a.what:
         x = r(B, d, S, S)
         report("dwt_init", timed(lambda: ops.dwt_init(x)))
