@@ -41,8 +41,12 @@ int run_chan_attn(const TbParams& p, const float* in, float* out, bool residual,
     if (p.ln1_w && !no_fuse_attn && fused_attn_supported(C, heads, hh, ww)) {
         // LN1 -> qkv 1x1 -> depthwise 3x3 -> {Gram partials, v} in one kernel: qkv never reaches HBM
         RF_TRY(fused_attn_plan(hh, ww, &nslab, &partial_floats, B, C));
-        RF_TRY(launch_attn_front(in, buf.qkv, partial, nslab, p.ln1_w, p.ln1_b, p.qkv_wp3, p.qkv_b, p.qkv_dw_w, p.qkv_dw_b, B, C, hh, ww, st,
-                                 p.ylo, p.yhi, p.xlo, p.xhi));
+        AttnFrontArgs f{};
+        f.x = in; f.v = buf.qkv; f.partial = partial; f.nslab = nslab;
+        f.ln_w = p.ln1_w; f.ln_b = p.ln1_b; f.wp = p.qkv_wp3; f.bq = p.qkv_b; f.wd = p.qkv_dw_w; f.bd = p.qkv_dw_b;
+        f.B = B; f.h = hh; f.w = ww;
+        f.ylo = p.ylo; f.yhi = p.yhi; f.xlo = p.xlo; f.xhi = p.xhi;
+        RF_TRY(launch_attn_front(f, C, st));
         av.x1 = buf.qkv; av.x1_bstride = (int64_t)C * Pn;
     } else {
         Conv1x1Args q{};
@@ -59,7 +63,12 @@ int run_chan_attn(const TbParams& p, const float* in, float* out, bool residual,
         if (!no_fuse && attn_mid_supported(C, heads, hh, ww)) {
             // depthwise 3x3 of q, k, v + Gram partials in one kernel: dw(q), dw(k) never reach HBM
             RF_TRY(attn_mid_plan(hh, ww, &nslab, &partial_floats, B, C));
-            RF_TRY(launch_attn_mid(buf.pre, buf.qkv, partial, nslab, p.qkv_dw_w, p.qkv_dw_b, B, C, hh, ww, st, p.ylo, p.yhi, p.xlo, p.xhi));
+            AttnMidArgs m{};
+            m.qkv = buf.pre; m.v = buf.qkv; m.partial = partial; m.nslab = nslab;
+            m.wd = p.qkv_dw_w; m.bd = p.qkv_dw_b;
+            m.B = B; m.h = hh; m.w = ww;
+            m.ylo = p.ylo; m.yhi = p.yhi; m.xlo = p.xlo; m.xhi = p.xhi;
+            RF_TRY(launch_attn_mid(m, C, st));
             av.x1 = buf.qkv; av.x1_bstride = (int64_t)C * Pn;
         } else {
             DwConvArgs d{};
@@ -112,7 +121,11 @@ int run_transformer(const TbParams& p, const float* in, float* out, float* ws, c
     // x + ffn(LN2(x)) ----------------------------------------------------------------------
     if (transformer_ffn_is_fused(p, C, hc, hh, ww)) {
         // LN2 -> 1x1 -> depthwise 3x3 -> GELU -> 1x1 + residual in one kernel: the hidden tensor stays on chip
-        RF_TRY(launch_ffn_fused(x1, out, p.ln2_w, p.ln2_b, p.pw1_wp3, p.pw1_b, p.dw_w, p.dw_b, p.pw2_wp, p.pw2_b, B, C, hh, ww, st));
+        FfnArgs f{};
+        f.x = x1; f.out = out;
+        f.ln_w = p.ln2_w; f.ln_b = p.ln2_b; f.w1p = p.pw1_wp3; f.b1 = p.pw1_b; f.wd = p.dw_w; f.bd = p.dw_b; f.w2p = p.pw2_wp; f.b2 = p.pw2_b;
+        f.B = B; f.h = hh; f.w = ww;
+        RF_TRY(launch_ffn_fused(f, C, st));
     } else {
         Conv1x1Args f1{};
         f1.x1 = x1; f1.C1 = C; f1.x1_bstride = (int64_t)C * Pn;

@@ -285,22 +285,55 @@ int launch_attn_fold(const float* partial, int nslab, const float* temperature, 
                      float* wp_out, void* wp3_out /* b3 form too, or nullptr */, int B, int C, int heads, hipStream_t st,
                      int log_temperature = 0);
 
-// ---- fused transformer-block kernels for C = 32 / 64 (rf_fused.hip)
+// ---- fused transformer-block kernels (rf_fused.hip).  The kernels take these structs by value: their layout is the kernels'.
+// The caller fills the tensors, B / h / w, nslab (from the plan) and the shard window; the launcher fills tiles_x, ntiles and
+// rgroups and clamps yhi / xhi.
+struct FfnArgs {           // out = x + W2 gelu(dw3x3(W1 LN2(x) + b1) + bd) + b2, for C = 32 / 48
+    const float* x;        // [B][C][h][w] block input (also the residual)
+    float* out;            // [B][C][h][w]
+    const float* ln_w; const float* ln_b;
+    const void* w1p;       // b3-packed pw1 weight [C/32][2C/16][3][64] 16-byte elements
+    const float* b1;       // [2C]
+    const float* wd;       // [2C][9]
+    const float* bd;       // [2C]
+    const float* w2p;      // packed [2C/4][C/16][64]
+    const float* b2;       // [C]
+    int B, h, w, tiles_x, ntiles;
+};
 bool fused_ffn_supported(int C, int hidden, int h, int w);
-int launch_ffn_fused(const float* x, float* out, const float* ln_w, const float* ln_b, const void* w1p /* b3 */, const float* b1,
-                     const float* wd, const float* bd, const float* w2p, const float* b2, int B, int C, int h, int w, hipStream_t st);
+int launch_ffn_fused(FfnArgs a, int C, hipStream_t st);
+
+struct AttnFrontArgs {     // LN1 -> qkv 1x1 -> depthwise 3x3 -> Gram partials of (q, k) + v, for C = 32
+    const float* x;        // [B][C][h][w]
+    float* v;              // [B][C][h][w]  depthwise-convolved v
+    float* partial;        // [B][nslab][C/16][16][66]  (layout of rf_attn.hip: band of one k tile)
+    const float* ln_w; const float* ln_b;
+    const void* wp;        // b3-packed qkv weight [C/32][3C/16][3][64] 16-byte elements
+    const float* bq;       // [3C]
+    const float* wd;       // [3C][9]
+    const float* bd;       // [3C]
+    int B, h, w, tiles_x, ntiles, nslab;
+    int ylo, yhi;          // rows [ylo, yhi) enter the Gram statistics (a spatial shard's interior); yhi = 0: all
+    int xlo, xhi;          // ... and columns [xlo, xhi) of them, both multiples of 4 or xhi = w: whole 4-pixel groups; xhi = 0: all
+};
 bool fused_attn_supported(int C, int heads, int h, int w);
 int fused_attn_plan(int h, int w, int* nslab, size_t* partial_floats, int B, int C);
-int launch_attn_front(const float* x, float* v, float* partial, int nslab, const float* ln_w, const float* ln_b,
-                      const void* wp /* b3 */, const float* bq, const float* wd, const float* bd, int B, int C, int h, int w, hipStream_t st,
-                      int ylo = 0, int yhi = 0 /* rows [ylo, yhi) enter the Gram statistics; yhi = 0: all */,
-                      int xlo = 0, int xhi = 0 /* ... and columns [xlo, xhi), multiples of 4 (xhi: or w); xhi = 0: all */);
+int launch_attn_front(AttnFrontArgs a, int C, hipStream_t st);
 
-// qkv [B,3C,h,w] -> depthwise 3x3 -> Gram partials of (q,k) + v, for C = 64 / 128
+struct AttnMidArgs {       // qkv [B,3C,h,w] -> depthwise 3x3 -> Gram partials of (q, k) + v, for C = 64 / 128
+    const float* qkv;      // [B][3C][h][w]
+    float* v;              // [B][C][h][w]  depthwise-convolved v
+    float* partial;        // [B][nslab][C/16][16][66]  (layout of attn_front_kernel / rf_attn.hip)
+    const float* wd;       // [3C][9]
+    const float* bd;       // [3C]
+    int B, h, w, tiles_x, ntiles, nslab;
+    int ylo, yhi;          // as AttnFrontArgs
+    int xlo, xhi;
+    int rgroups;           // gridDim.z: the rounds (Gram tiles, then v parts) are split over this many workgroups per slab
+};
 bool attn_mid_supported(int C, int heads, int h, int w);
 int attn_mid_plan(int h, int w, int* nslab, size_t* partial_floats, int B, int C);
-int launch_attn_mid(const float* qkv, float* v, float* partial, int nslab, const float* wd, const float* bd,
-                    int B, int C, int h, int w, hipStream_t st, int ylo = 0, int yhi = 0, int xlo = 0, int xhi = 0);
+int launch_attn_mid(AttnMidArgs a, int C, hipStream_t st);
 
 // ---- TransformerBlock schedule (rf_block.hip)
 struct TbParams {

@@ -1,5 +1,9 @@
-// Fused transformer-block kernels for U-Net level 0 of RawFormer-S (C = 32 channels; the templates are written
-// for any C % 16 == 0, but C = 64 needs 400+ registers and lost to the op-by-op schedule, so only <32> is built).
+// Fused transformer-block kernels for U-Net levels 0-2.  Built: ffn_fused_kernel<32> and attn_front_kernel<32> (four waves,
+// level 0 of RawFormer-S), ffn_fused8_kernel<48> / <64> (eight waves; <64> is built and tested but never dispatched, see
+// fused_ffn_supported) and attn_mid_kernel<64> / <128> (levels 1-2, where the qkv 1x1 stays a separate GEMM).  The three
+// kernels with a phase A (both FFN kernels and attn_front) share group_geom, split_step, phase_a_step_b3 and tile_range; all
+// four share stencil4, and all but ffn_fused_kernel tile_origin.  Every helper is __forceinline__, and tools/isa_same.py shows whether an edit to one
+// of them left the compiled code alone.
 //
 // Un-fused, one TransformerBlock moves ~26 C floats per pixel through HBM (qkv 1x1: C in / 3C out,
 // depthwise 3x3: 3C/3C, Gram: 2C, ...; ffn: C/2C, 2C/2C, 2C+C/C).  Here the wide intermediates
@@ -53,6 +57,7 @@ constexpr int HR = TH + 2;              // halo'd rows
 constexpr int HC = 72;                  // halo'd columns held (18 groups of 4 px)
 constexpr int NG = HR * (HC / 4);       // 108 pixel groups per tile
 constexpr int GPW = NG / 4;             // 27 groups per wave in phase A (two MFMA steps: 16 + 11)
+constexpr int GPW8 = 14;                // ... of the eight-wave kernel: one step (8 x 14 = 112 >= 108)
 constexpr int PART = 32;                // intermediate channels per part
 // Plane stride of the Gram rounds, where lane (j, kq) reads 16 bytes at plane j, column 4 kq (+ 16 st): a ds_read_b128 is
 // served in four groups of 16 lanes, each holding every j once with two different kq (MI355X_MICROARCH.md, LDS), so the
@@ -62,23 +67,41 @@ constexpr int PSG = 456;
 }  // namespace fused
 
 // ---- shared phase-A machinery ------------------------------------------------------------------
-// The wave's two steps of halo'd pixel groups: geometry of step st for lane j.
+// A wave's share of the halo'd pixel groups, G of them in steps of 16 (G <= 16: step 0 only; the last wave's share may then run
+// past the tile): geometry of step st for lane j.
 struct GroupGeom {
     int lds_off;     // row * HC + 4 * cg
     int goff;        // y * w + x  (clamped to 0 when outside)
     bool valid;
 };
+template <int G>
 __device__ __forceinline__ GroupGeom group_geom(int wave, int st, int j, int y0, int x0, int h, int w) {
     using namespace fused;
     GroupGeom g;
-    const int gi = wave * GPW + st * 16 + j;
-    const bool in_step = (st == 0) || (j < GPW - 16);
+    const int gi = wave * G + st * 16 + j;
+    const bool in_step = j < G - st * 16 && (NG % G == 0 || gi < NG);
     const int row = gi / (HC / 4), cg = gi % (HC / 4);
     const int y = y0 - 1 + row, x = x0 - 4 + 4 * cg;
     g.valid = in_step && y >= 0 && y < h && x >= 0 && x < w;
     g.lds_off = in_step ? row * HC + 4 * cg : -1;
     g.goff = g.valid ? y * w + x : 0;
     return g;
+}
+
+// A persistent workgroup's tiles: CONSECUTIVE and numbered down the columns of the tile grid (ty fastest), so successive tiles
+// share two of their six halo'd rows, which are then still in L2 (strided tiles, numbered along x, re-fetched every halo row
+// from HBM).  `wg` of `nwg` workgroups owns [begin, end); WG keeps the caller's signedness of the product wg * per.
+struct TileRange { int tiles_y, begin, end; };
+template <typename WG>
+__device__ __forceinline__ TileRange tile_range(int ntiles, int tiles_x, int nwg, WG wg) {
+    const int tiles_y = ntiles / tiles_x;
+    const int per = (ntiles + nwg - 1) / nwg;
+    const int begin = wg * per, end = (begin + per < ntiles) ? begin + per : ntiles;
+    return {tiles_y, begin, end};
+}
+__device__ __forceinline__ int2 tile_origin(int tile, int tiles_y) {      // (x0, y0) of a tile
+    const int tx = tile / tiles_y, ty = tile % tiles_y;
+    return make_int2(tx * fused::TW, ty * fused::TH);
 }
 
 // ---- phase-A helpers in b3 form (rf_common.h): lane (j, kq) holds channels 32 kb + 8 kq + i, i = 0..7 ------------------------
@@ -177,14 +200,14 @@ __device__ __forceinline__ void phase_a_step_b3(const u32x4 (&bp)[C / 32][4][3],
     }
 }
 
-// 3x3 depthwise stencil for 4 consecutive pixels from an LDS plane: `p` points at the plane's
-// (row of the output pixel - 1, column of the first pixel), 16-byte aligned.  The two edge taps of
-// every row must not be scalar LDS reads (lanes 4 floats apart are a 4-way bank conflict on
-// ds_read_b32: measured 58 % of all LDS cycles), so:
-//   stencil4_dpp   lanes j-1 / j+1 of the same 16-lane row hold the neighbouring 4-pixel groups:
-//                  edges come over DPP row shifts; only lanes 0 and 15 read their outer tap.
-//   stencil4_wide  neighbouring groups are not in this wave's registers: three aligned
-//                  ds_read_b128 per row (conflict-free with the plane stride used there).
+// 3x3 depthwise stencil for 4 consecutive pixels from an LDS plane: `p` points at the plane's column of the first pixel,
+// 16-byte aligned, and the three rows (output row - 1 ..) lie at p + ro[dy]: {0, HC, 2 HC} in a contiguous tile, anything in
+// the circular row window of attn_mid_kernel.  The two edge taps of every row must not be scalar LDS reads (lanes 4 floats
+// apart are a 4-way bank conflict on ds_read_b32: measured 58 % of all LDS cycles), so:
+//   Edge::Dpp   lanes j-1 / j+1 of the same 16-lane row hold the neighbouring 4-pixel groups:
+//               edges come over DPP row shifts; only lanes 0 and 15 read their outer tap.
+//   Edge::Wide  neighbouring groups are not in this wave's registers: three aligned
+//               ds_read_b128 per row (conflict-free with the plane stride used there).
 __device__ __forceinline__ float dpp_row_shr1(float keep, float v) {   // lane i <- lane i-1 (i % 16 == 0 keeps `keep`)
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(keep), __float_as_int(v), 0x111, 0xf, 0xf, false));
 }
@@ -192,68 +215,31 @@ __device__ __forceinline__ float dpp_row_shl1(float keep, float v) {   // lane i
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(keep), __float_as_int(v), 0x101, 0xf, 0xf, false));
 }
 
-__device__ __forceinline__ void stencil4_dpp(const float* __restrict__ p, int j, const float* __restrict__ k9, float bias, float (&out)[4]) {
-    using namespace fused;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) out[q] = bias;
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy) {
-        const float* row = p + dy * HC;
-        const float4 m = *reinterpret_cast<const float4*>(row);
-        float el = 0.f, er = 0.f;
-        if (j == 0) el = row[-1];
-        if (j == 15) er = row[4];
-        const float v[6] = {dpp_row_shr1(el, m.w), m.x, m.y, m.z, m.w, dpp_row_shl1(er, m.x)};
-        const float k0 = k9[dy * 3], k1 = k9[dy * 3 + 1], k2 = k9[dy * 3 + 2];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) out[q] = fmaf(k2, v[q + 2], fmaf(k1, v[q + 1], fmaf(k0, v[q], out[q])));
-    }
-}
-
-// the same two stencils on rows at explicit offsets ro[dy] (a circular row window in LDS: attn_mid_kernel)
-__device__ __forceinline__ void stencil4_dpp_r(const float* __restrict__ p, const int (&ro)[3], int j, const float* __restrict__ k9, float bias, float (&out)[4]) {
+enum class Edge { Dpp, Wide };
+template <Edge E>
+__device__ __forceinline__ void stencil4(const float* __restrict__ p, const int (&ro)[3], int j, const float* __restrict__ k9, float bias, float (&out)[4]) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) out[q] = bias;
 #pragma unroll
     for (int dy = 0; dy < 3; ++dy) {
         const float* row = p + ro[dy];
-        const float4 m = *reinterpret_cast<const float4*>(row);
-        float el = 0.f, er = 0.f;
-        if (j == 0) el = row[-1];
-        if (j == 15) er = row[4];
-        const float v[6] = {dpp_row_shr1(el, m.w), m.x, m.y, m.z, m.w, dpp_row_shl1(er, m.x)};
-        const float k0 = k9[dy * 3], k1 = k9[dy * 3 + 1], k2 = k9[dy * 3 + 2];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) out[q] = fmaf(k2, v[q + 2], fmaf(k1, v[q + 1], fmaf(k0, v[q], out[q])));
-    }
-}
-__device__ __forceinline__ void stencil4_wide_r(const float* __restrict__ p, const int (&ro)[3], const float* __restrict__ k9, float bias, float (&out)[4]) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) out[q] = bias;
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy) {
-        const float* row = p + ro[dy];
-        const float4 lft = *reinterpret_cast<const float4*>(row - 4);
-        const float4 m = *reinterpret_cast<const float4*>(row);
-        const float4 rgt = *reinterpret_cast<const float4*>(row + 4);
-        const float v[6] = {lft.w, m.x, m.y, m.z, m.w, rgt.x};
-        const float k0 = k9[dy * 3], k1 = k9[dy * 3 + 1], k2 = k9[dy * 3 + 2];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) out[q] = fmaf(k2, v[q + 2], fmaf(k1, v[q + 1], fmaf(k0, v[q], out[q])));
-    }
-}
-
-__device__ __forceinline__ void stencil4_wide(const float* __restrict__ p, const float* __restrict__ k9, float bias, float (&out)[4]) {
-    using namespace fused;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) out[q] = bias;
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy) {
-        const float* row = p + dy * HC;
-        const float4 lft = *reinterpret_cast<const float4*>(row - 4);
-        const float4 m = *reinterpret_cast<const float4*>(row);
-        const float4 rgt = *reinterpret_cast<const float4*>(row + 4);
-        const float v[6] = {lft.w, m.x, m.y, m.z, m.w, rgt.x};
+        float4 m;
+        float vl, vr;                                    // the taps left and right of m
+        if constexpr (E == Edge::Dpp) {
+            m = *reinterpret_cast<const float4*>(row);
+            float el = 0.f, er = 0.f;
+            if (j == 0) el = row[-1];
+            if (j == 15) er = row[4];
+            vl = dpp_row_shr1(el, m.w);
+            vr = dpp_row_shl1(er, m.x);
+        } else {
+            const float4 lft = *reinterpret_cast<const float4*>(row - 4);
+            m = *reinterpret_cast<const float4*>(row);
+            const float4 rgt = *reinterpret_cast<const float4*>(row + 4);
+            vl = lft.w;
+            vr = rgt.x;
+        }
+        const float v[6] = {vl, m.x, m.y, m.z, m.w, vr};
         const float k0 = k9[dy * 3], k1 = k9[dy * 3 + 1], k2 = k9[dy * 3 + 2];
 #pragma unroll
         for (int q = 0; q < 4; ++q) out[q] = fmaf(k2, v[q + 2], fmaf(k1, v[q + 1], fmaf(k0, v[q], out[q])));
@@ -261,24 +247,12 @@ __device__ __forceinline__ void stencil4_wide(const float* __restrict__ p, const
 }
 
 // ================================================================================================
-// FFN:  out = x1 + W2 gelu(dw3x3(W1 LN2(x1) + b1) + bd) + b2
+// FFN:  out = x1 + W2 gelu(dw3x3(W1 LN2(x1) + b1) + bd) + b2          (FfnArgs: rf_common.h)
 // ================================================================================================
-struct FfnArgs {
-    const float* x;        // [B][C][h][w] block input (also the residual)
-    float* out;            // [B][C][h][w]
-    const float* ln_w; const float* ln_b;
-    const void* w1p;       // b3-packed pw1 weight [C/32][2C/16][3][64] 16-byte elements
-    const float* b1;       // [2C]
-    const float* wd;       // [2C][9]
-    const float* bd;       // [2C]
-    const float* w2p;      // packed [2C/4][C/16][64]
-    const float* b2;       // [C]
-    int B, h, w, tiles_x, ntiles;
-};
-
 template <int C>
 __global__ void __launch_bounds__(256, 2) ffn_fused_kernel(FfnArgs a) {
     using namespace fused;
+    const int ro[3] = {0, HC, 2 * HC};   // a tile's halo'd rows are contiguous in LDS
     constexpr int NS = C / 4;            // k-sets of the first GEMM
     constexpr int NT1 = 2 * C / 16;      // output tiles of the first GEMM (hidden)
     constexpr int NTO = C / 16;          // output tiles of the second GEMM
@@ -305,18 +279,14 @@ __global__ void __launch_bounds__(256, 2) ffn_fused_kernel(FfnArgs a) {
     __syncthreads();
     STAMP_DECL
 
-    // A workgroup's tiles are CONSECUTIVE and numbered down the columns of the tile grid (ty fastest): successive tiles share two
-    // of their six halo'd rows, which are then still in L2 (strided tiles, numbered along x, re-fetched every halo row from HBM)
-    const int tiles_y = a.ntiles / a.tiles_x;
-    const int per = (a.ntiles + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int t_begin = blockIdx.x * per, t_end = (t_begin + per < a.ntiles) ? t_begin + per : a.ntiles;
-    for (int tile = t_begin; tile < t_end; ++tile) {
-        const int tx = tile / tiles_y, ty = tile % tiles_y;
-        const int x0 = tx * TW, y0 = ty * TH;
+    const TileRange tr = tile_range(a.ntiles, a.tiles_x, (int)gridDim.x, blockIdx.x);
+    for (int tile = tr.begin; tile < tr.end; ++tile) {
+        const int tx = tile / tr.tiles_y, ty = tile % tr.tiles_y;      // tile_origin, spelled out: through the helper this kernel's
+        const int x0 = tx * TW, y0 = ty * TH;                          // prologue is scheduled differently (tools/isa_same.py)
         STAMP(0);
         // input tile, loaded here (see attn_front_kernel: the b3 pieces take the registers a tile in flight would need):
         // LayerNorm in registers, then the three-piece split that both parts of phase A reuse
-        const GroupGeom gw0 = group_geom(wave, 0, j, y0, x0, h, w), gw1 = group_geom(wave, 1, j, y0, x0, h, w);
+        const GroupGeom gw0 = group_geom<GPW>(wave, 0, j, y0, x0, h, w), gw1 = group_geom<GPW>(wave, 1, j, y0, x0, h, w);
         u32x4 bp0[C / 32][4][3], bp1[C / 32][4][3];
         {
             float4 xh0[NS], xh1[NS];
@@ -361,7 +331,7 @@ __global__ void __launch_bounds__(256, 2) ffn_fused_kernel(FfnArgs a) {
             for (int s = 0; s < PART / 4; ++s) {
                 const int hc = 4 * s + kq;
                 float v[4];
-                stencil4_dpp(mid + hc * PS + wave * HC + 4 * j + 4, j, wd_l + (part * PART + hc) * 9, bd_l[part * PART + hc], v);
+                stencil4<Edge::Dpp>(mid + hc * PS + wave * HC + 4 * j + 4, ro, j, wd_l + (part * PART + hc) * 9, bd_l[part * PART + hc], v);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[q] = gelu_fast(v[q]);
 #pragma unroll
@@ -401,23 +371,6 @@ __global__ void __launch_bounds__(256, 2) ffn_fused_kernel(FfnArgs a) {
 // is padded to a multiple of 32 with zero pieces (C = 48: the packed weight is zero-padded the same way).
 // LDS at C = 64: 64 KB mid / reduction + 48 KB W1 (b3) + 32 KB W2 + 6 KB of vectors = 150 KB.
 // ================================================================================================
-namespace fused8 {
-constexpr int GPW = 14;                 // pixel groups per wave in phase A (8 x 14 = 112 >= 108)
-}
-
-__device__ __forceinline__ GroupGeom group_geom8(int wave, int j, int y0, int x0, int h, int w) {
-    using namespace fused;
-    GroupGeom g;
-    const int gi = wave * fused8::GPW + j;
-    const bool in_step = j < fused8::GPW && gi < NG;
-    const int row = gi / (HC / 4), cg = gi % (HC / 4);
-    const int y = y0 - 1 + row, x = x0 - 4 + 4 * cg;
-    g.valid = in_step && y >= 0 && y < h && x >= 0 && x < w;
-    g.lds_off = in_step ? row * HC + 4 * cg : -1;
-    g.goff = g.valid ? y * w + x : 0;
-    return g;
-}
-
 // input of one step, K padded to KP: lane (j, kq) holds channels 32 kb + 8 kq + i; channels >= C are zeros (loaded from a
 // clamped address, selected away: the loads stay branch-free)
 template <int C, int KP>
@@ -474,6 +427,7 @@ __device__ __forceinline__ void ln_step_b3p(int kq, const float* __restrict__ ga
 template <int C>
 __global__ void __launch_bounds__(512, 1) ffn_fused8_kernel(FfnArgs a) {
     using namespace fused;
+    const int ro[3] = {0, HC, 2 * HC};   // a tile's halo'd rows are contiguous in LDS
     constexpr int KP = (C + 31) / 32 * 32; // K of the first GEMM, padded
     constexpr int NT1 = 2 * C / 16;      // output tiles of the first GEMM (hidden)
     constexpr int NTO = C / 16;          // output tiles of the second GEMM
@@ -499,18 +453,16 @@ __global__ void __launch_bounds__(512, 1) ffn_fused8_kernel(FfnArgs a) {
     for (int i = tid; i < C; i += 512) { gam_l[i] = a.ln_w[i]; bet_l[i] = a.ln_b[i]; b2_l[i] = a.b2[i]; }
     __syncthreads();
 
-    const int tiles_y = a.ntiles / a.tiles_x;
-    const int per = (a.ntiles + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int t_begin = blockIdx.x * per, t_end = (t_begin + per < a.ntiles) ? t_begin + per : a.ntiles;
+    const TileRange tr = tile_range(a.ntiles, a.tiles_x, (int)gridDim.x, blockIdx.x);
     const int j0 = lane & 15, kq0 = lane >> 4, lane0 = lane;
-    for (int tile = t_begin; tile < t_end; ++tile) {
-        const int tx = tile / tiles_y, ty = tile % tiles_y;
-        const int x0 = tx * TW, y0 = ty * TH;
+    for (int tile = tr.begin; tile < tr.end; ++tile) {
+        const int2 o = tile_origin(tile, tr.tiles_y);
+        const int x0 = o.x, y0 = o.y;
         // the lane coordinates are made opaque once per tile: everything derived from them (LDS plane / weight / stencil addresses)
         // would otherwise be hoisted out of the tile loop into long-lived registers and spilled (112 of them)
         int j = j0, kq = kq0, lane = lane0;
         asm volatile("" : "+v"(j), "+v"(kq), "+v"(lane));
-        const GroupGeom gw = group_geom8(wave, j, y0, x0, h, w);
+        const GroupGeom gw = group_geom<GPW8>(wave, 0, j, y0, x0, h, w);
         u32x4 bp[KP / 32][4][3];
         {
             float4 xh[KP / 4];
@@ -537,7 +489,7 @@ __global__ void __launch_bounds__(512, 1) ffn_fused8_kernel(FfnArgs a) {
             for (int s4 = 0; s4 < PART / 8; ++s4) {
                 const int s = 4 * hf + s4, hc = 4 * s + kq;
                 float v[4];
-                stencil4_dpp(mid + hc * PS + row * HC + 4 * j + 4, j, wd_l + (part * PART + hc) * 9, bd_l[part * PART + hc], v);
+                stencil4<Edge::Dpp>(mid + hc * PS + row * HC + 4 * j + 4, ro, j, wd_l + (part * PART + hc) * 9, bd_l[part * PART + hc], v);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[q] = gelu_fast(v[q]);
 #pragma unroll
@@ -593,18 +545,23 @@ __global__ void __launch_bounds__(512, 1) ffn_fused8_kernel(FfnArgs a) {
 // op-by-op chain there (RawFormer-L level 0, 3 M pixels: 1.98 ms against 1.85 ms; RawFormer-S level 1: 0.33 against 0.30 ms) --
 // at 64 channels the kernel is bound by MFMA + VALU issue (they do not overlap on this chip) where the chain is bound by HBM,
 // and both take the same time.  C = 48 (RawFormer-B level 0) gains 8 % of its FFN.
-bool fused_ffn_supported(int C, int hidden, int h, int w) {
-#ifdef RF_DIAG
-    if (C == 64 && getenv("RF_FFN8_64") && hidden == 2 * C && (w % 4 == 0) && ((double)C * h * w * 4.0 < 4.0e9)) return true;
-#endif
-    return (C == 32 || C == 48) && hidden == 2 * C && (w % 4 == 0) && ((double)C * h * w * 4.0 < 4.0e9);
+static bool ffn_shape_ok(int C, int hidden, int h, int w, bool diag64) {
+    return (C == 32 || C == 48 || (diag64 && C == 64)) && hidden == 2 * C && (w % 4 == 0) && ((double)C * h * w * 4.0 < 4.0e9);
 }
+static bool ffn_diag64() {
+#ifdef RF_DIAG
+    return getenv("RF_FFN8_64") != nullptr;
+#else
+    return false;
+#endif
+}
+bool fused_ffn_supported(int C, int hidden, int h, int w) { return ffn_shape_ok(C, hidden, h, w, ffn_diag64()); }
 
-int launch_ffn_fused(const float* x, float* out, const float* ln_w, const float* ln_b, const void* w1p, const float* b1,
-                     const float* wd, const float* bd, const float* w2p, const float* b2, int B, int C, int h, int w, hipStream_t st) {
-    RF_CHECK_ARG((C == 32 || C == 48 || C == 64) && w % 4 == 0 && (double)C * h * w * 4.0 < 4.0e9 && B <= 65535, "ffn_fused: unsupported shape C=%d %dx%d", C, h, w);
-    RF_CHECK_ARG(aligned16(x) && aligned16(out) && aligned16(w1p), "ffn_fused: buffers must be 16-byte aligned");
-    FfnArgs a{x, out, ln_w, ln_b, w1p, b1, wd, bd, w2p, b2, B, h, w, cdiv(w, fused::TW), 0};
+int launch_ffn_fused(FfnArgs a, int C, hipStream_t st) {
+    const int B = a.B, h = a.h, w = a.w;
+    RF_CHECK_ARG(ffn_shape_ok(C, 2 * C, h, w, ffn_diag64()) && B <= 65535, "ffn_fused: unsupported shape C=%d %dx%d", C, h, w);
+    RF_CHECK_ARG(aligned16(a.x) && aligned16(a.out) && aligned16(a.w1p), "ffn_fused: buffers must be 16-byte aligned");
+    a.tiles_x = cdiv(w, fused::TW);
     a.ntiles = a.tiles_x * cdiv(h, fused::TH);
     int wgs = cdiv(512, B);                       // persistent: two workgroups per CU over the whole batch
     if (wgs > a.ntiles) wgs = a.ntiles;
@@ -626,25 +583,12 @@ int launch_ffn_fused(const float* x, float* out, const float* ln_w, const float*
 }
 
 // ================================================================================================
-// Attention front:  qkv = dw3x3(Wqkv LN1(x) + b);  Gram partials of (q, k) per head;  v -> HBM
+// Attention front:  qkv = dw3x3(Wqkv LN1(x) + b);  Gram partials of (q, k) per head;  v -> HBM          (AttnFrontArgs: rf_common.h)
 // ================================================================================================
-struct AttnFrontArgs {
-    const float* x;        // [B][C][h][w]
-    float* v;              // [B][C][h][w]  depthwise-convolved v
-    float* partial;        // [B][nslab][C/16][16][66]  (layout of rf_attn.hip: band of one k tile)
-    const float* ln_w; const float* ln_b;
-    const void* wp;        // b3-packed qkv weight [C/32][3C/16][3][64] 16-byte elements
-    const float* bq;       // [3C]
-    const float* wd;       // [3C][9]
-    const float* bd;       // [3C]
-    int B, h, w, tiles_x, ntiles, nslab;
-    int ylo, yhi;          // rows [ylo, yhi) enter the Gram statistics (a spatial shard's interior; the whole image otherwise)
-    int xlo, xhi;          // ... and columns [xlo, xhi) of them, both multiples of 4 or xhi = w: whole 4-pixel groups
-};
-
 template <int C>
 __global__ void __launch_bounds__(256, 2) attn_front_kernel(AttnFrontArgs a) {
     using namespace fused;
+    const int ro[3] = {0, HC, 2 * HC};   // a tile's halo'd rows are contiguous in LDS
     constexpr int NS = C / 4;
     constexpr int NQT = C / 16;          // q (and k) tiles = Gram rounds
     constexpr int NVP = C / PART;        // v parts
@@ -676,17 +620,14 @@ __global__ void __launch_bounds__(256, 2) attn_front_kernel(AttnFrontArgs a) {
     for (int r = 0; r < NQT; ++r) { gq[r] = (f32x4){0.f, 0.f, 0.f, 0.f}; nq[r] = 0.f; nk[r] = 0.f; }
     STAMP_DECL
 
-    // consecutive tiles down the columns of the tile grid (see ffn_fused_kernel)
-    const int tiles_y = a.ntiles / a.tiles_x;
-    const int per = (a.ntiles + a.nslab - 1) / a.nslab;
-    const int t_begin = slab * per, t_end = (t_begin + per < a.ntiles) ? t_begin + per : a.ntiles;
-    for (int tile = t_begin; tile < t_end; ++tile) {
-        const int tx = tile / tiles_y, ty = tile % tiles_y;
-        const int x0 = tx * TW, y0 = ty * TH;
+    const TileRange tr = tile_range(a.ntiles, a.tiles_x, a.nslab, slab);
+    for (int tile = tr.begin; tile < tr.end; ++tile) {
+        const int2 o = tile_origin(tile, tr.tiles_y);
+        const int x0 = o.x, y0 = o.y;
         // The input tile is loaded here, not a tile ahead: the b3 pieces (96 registers) already fill the budget that the
         // f32 kernel of round 1 spent on the next tile's raw values.  The loads are issued before the barrier so that their
         // latency overlaps the wait (throw-away loads warming L2 for the next tile were measured: 3 % slower).
-        const GroupGeom g0 = group_geom(wave, 0, j, y0, x0, h, w), g1 = group_geom(wave, 1, j, y0, x0, h, w);
+        const GroupGeom g0 = group_geom<GPW>(wave, 0, j, y0, x0, h, w), g1 = group_geom<GPW>(wave, 1, j, y0, x0, h, w);
         float4 xh0[NS], xh1[NS];
         load_step_b3<C>(xb, P, kq, g0, xh0);
         load_step_b3<C>(xb, P, kq, g1, xh1);
@@ -717,8 +658,8 @@ __global__ void __launch_bounds__(256, 2) attn_front_kernel(AttnFrontArgs a) {
                 const int xo = x0 + 16 * st + 4 * kq;
                 const bool ok = yo >= a.ylo && yo < a.yhi && xo >= a.xlo && xo < a.xhi;
                 float qa[4], kb[4];
-                stencil4_wide(mid + j * PSG + wave * HC + 16 * st + 4 * kq + 4, wd_l + cq * 9, bd_l[cq], qa);
-                stencil4_wide(mid + (16 + j) * PSG + wave * HC + 16 * st + 4 * kq + 4, wd_l + ck * 9, bd_l[ck], kb);
+                stencil4<Edge::Wide>(mid + j * PSG + wave * HC + 16 * st + 4 * kq + 4, ro, j, wd_l + cq * 9, bd_l[cq], qa);
+                stencil4<Edge::Wide>(mid + (16 + j) * PSG + wave * HC + 16 * st + 4 * kq + 4, ro, j, wd_l + ck * 9, bd_l[ck], kb);
 #pragma unroll
                 for (int m = 0; m < 4; ++m) {
                     const float qv = ok ? qa[m] : 0.f, kv = ok ? kb[m] : 0.f;
@@ -746,7 +687,7 @@ __global__ void __launch_bounds__(256, 2) attn_front_kernel(AttnFrontArgs a) {
                 for (int s = 0; s < PART / 4; ++s) {
                     const int hc = 4 * s + kq, cv = 2 * C + vp * PART + hc;
                     float v[4];
-                    stencil4_dpp(mid + hc * PSV + wave * HC + 4 * j + 4, j, wd_l + cv * 9, bd_l[cv], v);
+                    stencil4<Edge::Dpp>(mid + hc * PSV + wave * HC + 4 * j + 4, ro, j, wd_l + cv * 9, bd_l[cv], v);
                     // uniform base + 32-bit lane offset (C P < 2^30 elements, checked by fused_attn_supported): no 64-bit per-lane pointer to keep
                     *reinterpret_cast<float4*>(vb + (unsigned)((vp * PART + hc) * P + yo * w + xo)) = make_float4(v[0], v[1], v[2], v[3]);
                 }
@@ -783,11 +724,13 @@ __global__ void __launch_bounds__(256, 2) attn_front_kernel(AttnFrontArgs a) {
     }
 }
 
-bool fused_attn_supported(int C, int heads, int h, int w) {
+// heads that never straddle a 16-channel tile
+static bool heads_fit_tiles(int C, int heads) {
     const int c = heads > 0 ? C / heads : 0;
-    return C == 32 && heads > 0 && C % heads == 0 && c <= 16 && 16 % c == 0 && (w % 4 == 0) &&
-           ((double)C * h * w * 4.0 < 4.0e9);
+    return heads > 0 && C % heads == 0 && c <= 16 && 16 % c == 0;
 }
+static bool attn_front_shape_ok(int C, int h, int w) { return C == 32 && (w % 4 == 0) && ((double)C * h * w * 4.0 < 4.0e9); }
+bool fused_attn_supported(int C, int heads, int h, int w) { return heads_fit_tiles(C, heads) && attn_front_shape_ok(C, h, w); }
 
 int fused_attn_plan(int h, int w, int* nslab, size_t* partial_floats, int B, int C) {
     const int ntiles = cdiv(w, fused::TW) * cdiv(h, fused::TH);
@@ -804,17 +747,17 @@ int fused_attn_plan(int h, int w, int* nslab, size_t* partial_floats, int B, int
     return RF_OK;
 }
 
-int launch_attn_front(const float* x, float* v, float* partial, int nslab, const float* ln_w, const float* ln_b,
-                      const void* wp, const float* bq, const float* wd, const float* bd, int B, int C, int h, int w, hipStream_t st,
-                      int ylo, int yhi, int xlo, int xhi) {
-    RF_CHECK_ARG(C == 32 && w % 4 == 0 && B <= 65535, "attn_front: unsupported shape C=%d %dx%d", C, h, w);
-    RF_CHECK_ARG(aligned16(x) && aligned16(v), "attn_front: buffers must be 16-byte aligned");
-    AttnFrontArgs a{x, v, partial, ln_w, ln_b, wp, bq, wd, bd, B, h, w, cdiv(w, fused::TW), 0, nslab, ylo, (yhi > 0 && yhi < h) ? yhi : h,
-                    xlo, (xhi > 0 && xhi < w) ? xhi : w};
+int launch_attn_front(AttnFrontArgs a, int C, hipStream_t st) {
+    const int B = a.B, h = a.h, w = a.w;
+    RF_CHECK_ARG(attn_front_shape_ok(C, h, w) && B <= 65535, "attn_front: unsupported shape C=%d %dx%d", C, h, w);
+    RF_CHECK_ARG(aligned16(a.x) && aligned16(a.v), "attn_front: buffers must be 16-byte aligned");
+    a.tiles_x = cdiv(w, fused::TW);
     a.ntiles = a.tiles_x * cdiv(h, fused::TH);
+    if (!(a.yhi > 0 && a.yhi < h)) a.yhi = h;
+    if (!(a.xhi > 0 && a.xhi < w)) a.xhi = w;
     const double px = (double)B * h * w;
     ProfScope prof(st, "attn_front_kernel<32>", px * (6.0 * C * C + 54.0 * C + 4.0 * C * 16), px * 8.0 * C);
-    const dim3 grid((unsigned)nslab, (unsigned)B);
+    const dim3 grid((unsigned)a.nslab, (unsigned)B);
     attn_front_kernel<32><<<grid, 256, 0, st>>>(a);
     return check_launch("attn_front");
 }
@@ -827,19 +770,8 @@ int launch_attn_front(const float* x, float* v, float* partial, int nslab, const
 // Round r stages q tile r (planes 0-15) and k tile r (planes 16-31) -- heads never straddle a 16-channel tile
 // here -- and the v rounds 32 channels each; a round's 14 x 16-byte loads per thread are issued before the
 // previous round's phase B and land in LDS after it (hardware zero fill outside the image, like rf_conv3x3.hip).
+// (AttnMidArgs: rf_common.h)
 // ================================================================================================
-struct AttnMidArgs {
-    const float* qkv;      // [B][3C][h][w]
-    float* v;              // [B][C][h][w]  depthwise-convolved v
-    float* partial;        // [B][nslab][C/16][16][66]  (layout of attn_front_kernel / rf_attn.hip)
-    const float* wd;       // [3C][9]
-    const float* bd;       // [3C]
-    int B, h, w, tiles_x, ntiles, nslab;
-    int ylo, yhi;          // as AttnFrontArgs
-    int xlo, xhi;
-    int rgroups;           // gridDim.z: the rounds (Gram tiles, then v parts) are split over this many workgroups per slab
-};
-
 template <int C>
 __global__ void __launch_bounds__(256, 2) attn_mid_kernel(AttnMidArgs a) {
     using namespace fused;
@@ -880,7 +812,8 @@ __global__ void __launch_bounds__(256, 2) attn_mid_kernel(AttnMidArgs a) {
     int pend_ys = 0;          // ... slot of its halo row 0
     bool pend_full = true;    // ... all six rows are staged (first tile of a round or of a column)
     auto plan_tile = [&](int tile, bool full) {
-        const int y0 = (tile % tiles_y) * TH, x0 = (tile / tiles_y) * TW;
+        const int2 o = tile_origin(tile, tiles_y);
+        const int x0 = o.x, y0 = o.y;
         pend_ys = y0 % HR; pend_full = full;
 #pragma unroll
         for (int i = 0; i < FPT; ++i) {
@@ -946,7 +879,8 @@ __global__ void __launch_bounds__(256, 2) attn_mid_kernel(AttnMidArgs a) {
     for (int rd = rd_lo; rd < rd_hi; ++rd) {
         for (int ti = 0; ti < ntw; ++ti) {
             const int tile = t_begin + ti;
-            const int x0 = (tile / tiles_y) * TW, y0 = (tile % tiles_y) * TH;
+            const int2 o = tile_origin(tile, tiles_y);
+            const int x0 = o.x, y0 = o.y;
             const int yo = y0 + wave;
             lds_barrier();                                // everyone is done reading the previous step
             store_round(rd);
@@ -973,8 +907,8 @@ __global__ void __launch_bounds__(256, 2) attn_mid_kernel(AttnMidArgs a) {
                     const int xo = x0 + 16 * st + 4 * kq;
                     const bool ok = yo >= a.ylo && yo < a.yhi && xo >= a.xlo && xo < a.xhi;
                     float qa[4], kb[4];
-                    stencil4_wide_r(mid + j * PSG + 16 * st + 4 * kq + 4, ro, wd_l + cq * 9, bd_l[cq], qa);
-                    stencil4_wide_r(mid + (16 + j) * PSG + 16 * st + 4 * kq + 4, ro, wd_l + ck * 9, bd_l[ck], kb);
+                    stencil4<Edge::Wide>(mid + j * PSG + 16 * st + 4 * kq + 4, ro, j, wd_l + cq * 9, bd_l[cq], qa);
+                    stencil4<Edge::Wide>(mid + (16 + j) * PSG + 16 * st + 4 * kq + 4, ro, j, wd_l + ck * 9, bd_l[ck], kb);
 #pragma unroll
                     for (int m = 0; m < 4; ++m) {
                         const float qv = ok ? qa[m] : 0.f, kv = ok ? kb[m] : 0.f;
@@ -990,7 +924,7 @@ __global__ void __launch_bounds__(256, 2) attn_mid_kernel(AttnMidArgs a) {
                     for (int s = 0; s < PART / 4; ++s) {
                         const int hc = 4 * s + kq, cv = 2 * C + vp * PART + hc;
                         float v[4];
-                        stencil4_dpp_r(mid + hc * PSV + 4 * j + 4, ro, j, wd_l + cv * 9, bd_l[cv], v);
+                        stencil4<Edge::Dpp>(mid + hc * PSV + 4 * j + 4, ro, j, wd_l + cv * 9, bd_l[cv], v);
                         *reinterpret_cast<float4*>(vb + (size_t)(vp * PART + hc) * P + (size_t)yo * w + xo) = make_float4(v[0], v[1], v[2], v[3]);
                     }
                 }
@@ -1036,23 +970,23 @@ int attn_mid_plan(int h, int w, int* nslab, size_t* partial_floats, int B, int C
     return RF_OK;
 }
 
-bool attn_mid_supported(int C, int heads, int h, int w) {
-    const int c = heads > 0 ? C / heads : 0;
-    return (C == 64 || C == 128) && heads > 0 && C % heads == 0 && c <= 16 && 16 % c == 0 && (w % 4 == 0) &&
-           ((double)(C + 16) * h * w * 4.0 < 2.0e9);      // byte offsets inside one round's buffer window stay below 2^31
+static bool attn_mid_shape_ok(int C, int h, int w) {
+    return (C == 64 || C == 128) && (w % 4 == 0) && ((double)(C + 16) * h * w * 4.0 < 2.0e9);      // byte offsets inside one round's buffer window stay below 2^31
 }
+bool attn_mid_supported(int C, int heads, int h, int w) { return heads_fit_tiles(C, heads) && attn_mid_shape_ok(C, h, w); }
 
-int launch_attn_mid(const float* qkv, float* v, float* partial, int nslab, const float* wd, const float* bd,
-                    int B, int C, int h, int w, hipStream_t st, int ylo, int yhi, int xlo, int xhi) {
-    RF_CHECK_ARG((C == 64 || C == 128) && w % 4 == 0 && B <= 65535, "attn_mid: unsupported shape C=%d %dx%d", C, h, w);
-    RF_CHECK_ARG(aligned16(qkv) && aligned16(v), "attn_mid: buffers must be 16-byte aligned");
-    AttnMidArgs a{qkv, v, partial, wd, bd, B, h, w, cdiv(w, fused::TW), 0, nslab, ylo, (yhi > 0 && yhi < h) ? yhi : h,
-                  xlo, (xhi > 0 && xhi < w) ? xhi : w, 1};
+int launch_attn_mid(AttnMidArgs a, int C, hipStream_t st) {
+    const int B = a.B, h = a.h, w = a.w;
+    RF_CHECK_ARG(attn_mid_shape_ok(C, h, w) && B <= 65535, "attn_mid: unsupported shape C=%d %dx%d", C, h, w);
+    RF_CHECK_ARG(aligned16(a.qkv) && aligned16(a.v), "attn_mid: buffers must be 16-byte aligned");
+    a.tiles_x = cdiv(w, fused::TW);
     a.ntiles = a.tiles_x * cdiv(h, fused::TH);
-    if ((long)nslab * B < 256) a.rgroups = 3;               // C / 16 + C / 32 rounds: 6 (C = 64) or 12 (C = 128)
+    if (!(a.yhi > 0 && a.yhi < h)) a.yhi = h;
+    if (!(a.xhi > 0 && a.xhi < w)) a.xhi = w;
+    a.rgroups = ((long)a.nslab * B < 256) ? 3 : 1;          // C / 16 + C / 32 rounds: 6 (C = 64) or 12 (C = 128)
     const double px = (double)B * h * w;
     ProfScope prof(st, C == 64 ? "attn_mid_kernel<64>" : "attn_mid_kernel<128>", px * (54.0 * C + 4.0 * C * 16), px * 16.0 * C);
-    const dim3 grid((unsigned)nslab, (unsigned)B, (unsigned)a.rgroups);
+    const dim3 grid((unsigned)a.nslab, (unsigned)B, (unsigned)a.rgroups);
     if (C == 64) attn_mid_kernel<64><<<grid, 256, 0, st>>>(a);
     else attn_mid_kernel<128><<<grid, 256, 0, st>>>(a);
     return check_launch("attn_mid");

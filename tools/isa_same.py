@@ -1,0 +1,41 @@
+#!/usr/bin/env python3
+"""Is the gfx950 code of one source the same as at an earlier revision?  The gate of a kernel refactor: identical instruction
+streams have identical results and identical speed.  Needs hipcc and git, no GPU.
+
+    isa_same.py <rev> <path.hip> [-DFOO ...]
+
+Compiles `git show <rev>:<path>` (next to that revision's headers) and the working-tree file with build.FLAGS to device assembly,
+drops the per-translation-unit __hip_cuid_* symbol and the source file name, and exits non-zero at the first difference.
+"""
+import os, re, subprocess, sys, tempfile
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+from bayer_low_light_image_enhancement_amd import build as B  # noqa: E402
+
+rev, path, flags = sys.argv[1], os.path.relpath(os.path.abspath(sys.argv[2]), REPO), sys.argv[3:]
+
+
+def listing(src):
+    r = subprocess.run([B._hipcc(), *B.FLAGS, *flags, "--cuda-device-only", "-S", src, "-o", "-"], capture_output=True, text=True)
+    if r.returncode:
+        sys.exit(r.stderr[-3000:])
+    return [ln for ln in r.stdout.splitlines() if "__hip_cuid_" not in ln and not ln.lstrip().startswith(".file")]
+
+
+with tempfile.TemporaryDirectory(prefix="isa_same_") as tmp:
+    tree = subprocess.check_output(["git", "ls-tree", "-r", "--name-only", rev], cwd=REPO, text=True).split("\n")
+    for f in (f for f in tree if f == path or f.endswith((".h", ".hpp"))):       # the source and every header of that revision
+        os.makedirs(os.path.dirname(os.path.join(tmp, f)), exist_ok=True)
+        with open(os.path.join(tmp, f), "wb") as out:
+            out.write(subprocess.check_output(["git", "show", f"{rev}:{f}"], cwd=REPO))
+    old, new = listing(os.path.join(tmp, path)), listing(os.path.join(REPO, path))
+what = f"{path} {' '.join(flags)}".strip()
+i = next((i for i, (a, b) in enumerate(zip(old, new)) if a != b), min(len(old), len(new)))
+if i == len(old) == len(new):
+    print(f"identical: {what}: {len(new)} lines of gfx950 assembly, {rev} and the working tree")
+    sys.exit(0)
+kernel = next((m.group(1) for ln in reversed(new[:i + 1]) if (m := re.match(r"^(\w+):", ln))), "(before the first function)")
+print(f"DIFFERENT: {what}: line {i + 1}, in {kernel}")
+for tag, text in ((f"--- {rev}", old), ("+++ working tree", new)):
+    print(tag, *text[max(i - 3, 0):i + 12], sep="\n")
+sys.exit(1)
