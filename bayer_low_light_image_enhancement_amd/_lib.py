@@ -51,6 +51,7 @@ SIGNATURES = {
     "rf_flat_offset": (_i, [_vp, _i, _psz]),
     "rf_train_workspace_bytes": (_i, [_vp, _i, _i, _i, _psz]),
     "rf_set_grad_ready": (_i, [_vp, GRAD_READY_FN, _vp]),
+    "rf_set_loss_clamp": (_i, [_vp, _i]),
     "rf_grad_range_count": (_i, [_vp, C.POINTER(_i)]),
     "rf_grad_range": (_i, [_vp, _i, _psz, _psz]),
     "rf_train_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _f, _vp]),
@@ -84,6 +85,8 @@ SIGNATURES = {
     "rf_u8_ssim_scratch_bytes": (_i, [_i, _i, _i, _i, _psz]),
     "rf_u8_ssim": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "rf_sid_pack": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.c_double, _i, _vp]),
+    "rf_sid_check_desc": (_i, [C.POINTER(C.c_int), _i, _i, _i, _i, _i, _i]),
+    "rf_sid_sample": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "rf_token_attn": (_i, [_vp, _vp, _vp, _vp, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _f, _vp]),
     "rf_bayer_luma_scratch_bytes": (_i, [_i, _i, _i, _psz]),
     "rf_bayer_luma": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),

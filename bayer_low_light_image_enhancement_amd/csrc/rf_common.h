@@ -420,7 +420,7 @@ int launch_dw_wgrad(const float* x, const float* dy, float* dw, float* db, float
 int launch_ewise(const float* a, const float* b, float* out, size_t n, int mode, float slope, hipStream_t st);
 int launch_split_halves(const float* src, float* a, float* b, int B, int C, int P, hipStream_t st);
 int loss_nblk();
-int launch_loss(const float* pred, const float* gt, float* grad, float* loss_out, float* partial, size_t n, int mode, float eps, hipStream_t st);
+int launch_loss(const float* pred, const float* gt, float* grad, float* loss_out, float* partial, size_t n, int mode, float eps, int clamp, hipStream_t st);
 int launch_adam(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps, float wd, int decoupled,
                 int step, float gscale, hipStream_t st);
 

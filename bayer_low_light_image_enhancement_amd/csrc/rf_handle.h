@@ -127,6 +127,8 @@ struct rf_handle {
     // training: notification that a range of the flat gradient buffer is final (rf_set_grad_ready)
     void (*grad_ready)(void* user, size_t offset, size_t count, void* stream) = nullptr;
     void* grad_ready_user = nullptr;
+    // training: the criterion sees clamp(pred, 0, 1) (rf_set_loss_clamp)
+    int loss_clamp = 0;
 
     const float* prm(int ix) const { return params[ix].ptr; }
     const float* pk(int ix) const { return packed + packs[params[ix].pack].offset; }

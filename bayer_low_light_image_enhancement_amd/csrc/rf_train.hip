@@ -607,13 +607,14 @@ __device__ __forceinline__ float gelu_grad(float v) {      // d/dv [ v Phi(v) ] 
     return cdf + v * 0.39894228040143267794f * expf(-0.5f * v * v);
 }
 // mode 0: out = a + b;  1: out = dy * gelu'(x) (a = dy, b = x);  2: out = dy * (y > 0 ? 1 : slope) (a = dy, b = y);
-// 3: out = gelu(a) (exact erf);  4: out += a;  5: out = a
+// 3: out = gelu(a) (exact erf);  4: out += a;  5: out = a;  6: out = clamp(a, 0, 1)
 __device__ __forceinline__ float ewise_op(float a, float b, float o, int mode, float slope) {
     if (mode == 0) return a + b;
     if (mode == 1) return a * gelu_grad(b);
     if (mode == 2) return a * (b > 0.f ? 1.0f : slope);
     if (mode == 3) return 0.5f * a * (1.0f + erff(a * 0.70710678118654752440f));
     if (mode == 5) return a;
+    if (mode == 6) return fminf(fmaxf(a, 0.f), 1.f);
     return o + a;
 }
 // VEC = 4: 16 bytes per lane and access (n % 4 == 0, 16-byte aligned operands); VEC = 1: any n
@@ -642,14 +643,18 @@ __global__ void __launch_bounds__(256) split_halves_kernel(const float4* __restr
     }
 }
 
-// loss (mode 0: L1 = mean |d|; 1: Charbonnier = mean sqrt(d^2 + eps^2), train.py:16-25) and its gradient w.r.t. pred
+// loss (mode 0: L1 = mean |d|; 1: Charbonnier = mean sqrt(d^2 + eps^2), train.py:16-25) and its gradient w.r.t. pred.
+// clamp: the loss of clamp(pred, 0, 1) (train.py:139); the gradient passes where 0 <= pred <= 1 (torch.clamp's subgradient)
 __global__ void __launch_bounds__(256) loss_kernel(const float* __restrict__ pred, const float* __restrict__ gt, float* __restrict__ grad,
-                                                   float* __restrict__ partial, size_t n, int mode, float eps, float inv_n) {
+                                                   float* __restrict__ partial, size_t n, int mode, float eps, float inv_n, int clamp) {
     float s = 0.f;
     for (size_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        const float d = pred[i] - gt[i];
-        if (mode == 0) { s += fabsf(d); grad[i] = (d > 0.f ? inv_n : d < 0.f ? -inv_n : 0.f); }
-        else { const float r = sqrtf(fmaf(d, d, eps * eps)); s += r; grad[i] = d / r * inv_n; }
+        float pr = pred[i];
+        const float pass = !clamp || (pr >= 0.f && pr <= 1.f) ? inv_n : 0.f;
+        if (clamp) pr = fminf(fmaxf(pr, 0.f), 1.f);
+        const float d = pr - gt[i];
+        if (mode == 0) { s += fabsf(d); grad[i] = (d > 0.f ? pass : d < 0.f ? -pass : 0.f); }
+        else { const float r = sqrtf(fmaf(d, d, eps * eps)); s += r; grad[i] = d / r * pass; }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
@@ -969,7 +974,7 @@ int launch_dw_wgrad(const float* x, const float* dy, float* dw, float* db, float
 }
 
 int launch_ewise(const float* a, const float* b, float* out, size_t n, int mode, float slope, hipStream_t st) {
-    ProfScope prof(st, "ewise_kernel", 0.0, (mode == 3 || mode == 5 ? 8.0 : 12.0) * n);
+    ProfScope prof(st, "ewise_kernel", 0.0, (mode == 3 || mode >= 5 ? 8.0 : 12.0) * n);
     if (n % 4 == 0 && aligned16(a) && aligned16(out) && (!b || aligned16(b))) ewise_kernel<4><<<grid1d(n / 4), 256, 0, st>>>(a, b, out, n, mode, slope);
     else ewise_kernel<1><<<grid1d(n), 256, 0, st>>>(a, b, out, n, mode, slope);
     return check_launch("ewise");
@@ -984,8 +989,8 @@ int launch_split_halves(const float* src, float* a, float* b, int B, int C, int 
 }
 
 int loss_nblk() { return 1024; }
-int launch_loss(const float* pred, const float* gt, float* grad, float* loss_out, float* partial, size_t n, int mode, float eps, hipStream_t st) {
-    loss_kernel<<<loss_nblk(), 256, 0, st>>>(pred, gt, grad, partial, n, mode, eps, 1.0f / (float)n);
+int launch_loss(const float* pred, const float* gt, float* grad, float* loss_out, float* partial, size_t n, int mode, float eps, int clamp, hipStream_t st) {
+    loss_kernel<<<loss_nblk(), 256, 0, st>>>(pred, gt, grad, partial, n, mode, eps, 1.0f / (float)n, clamp);
     reduce_partials_kernel<<<1, 256, 0, st>>>(partial, loss_out, loss_nblk(), 1, 0);
     return check_launch("loss");
 }

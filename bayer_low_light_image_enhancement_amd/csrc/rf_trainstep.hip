@@ -488,6 +488,12 @@ int rf_set_grad_ready(rf_handle* h, rf_grad_ready_fn ready, void* user) {
     return RF_OK;
 }
 
+int rf_set_loss_clamp(rf_handle* h, int on) {
+    RF_CHECK_ARG(h, "rf_set_loss_clamp: null handle");
+    h->loss_clamp = on != 0;
+    return RF_OK;
+}
+
 int rf_grad_range_count(const rf_handle* h, int* count) {
     RF_CHECK_ARG(h && count, "rf_grad_range_count: null argument");
     *count = (int)h->grad_ranges.size();
@@ -529,7 +535,10 @@ int rf_train_workspace_bytes(const rf_handle* h, int B, int H, int W, size_t* by
 int rf_train_step(rf_handle* h, const float* in, const float* gt, float* grads, float* loss_out, float* pred_out, void* workspace,
                   size_t workspace_bytes, int B, int H, int W, int loss_mode, float loss_eps, void* stream) {
     RF_CHECK_ARG(h && in && gt && grads && loss_out && workspace && aligned16(workspace) && aligned16(grads), "rf_train_step: bad arguments");
-    RF_CHECK_ARG((h->cfg.variant == RF_VARIANT_PLAIN || h->cfg.variant == RF_VARIANT_FLCA) && !h->cfg.clamp_io,
+    // clamp_io under the clamped criterion (rf_set_loss_clamp) is the criterion's own mask; the plain variant alone, whose input
+    // clamp feeds nothing but the embedding
+    const bool clamp_io = h->cfg.clamp_io && h->loss_clamp && h->cfg.variant == RF_VARIANT_PLAIN;
+    RF_CHECK_ARG((h->cfg.variant == RF_VARIANT_PLAIN || h->cfg.variant == RF_VARIANT_FLCA) && (!h->cfg.clamp_io || clamp_io),
                  "rf_train_step: variants 'plain' and 'flca' without clamp_io have their adjoint so far");
     RF_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0, "rf_train_step: B = %d, packed size %dx%d", B, H, W);
     RF_CHECK_ARG(H % 8 == 0, "rf_train_step: packed height %d is not a multiple of 8", H);
@@ -558,6 +567,7 @@ int rf_train_step(rf_handle* h, const float* in, const float* gt, float* grads, 
 
     // ------------------------------------------------------------------ forward
     RF_TRY(launch_pixel_unshuffle2(in, p.x4, B, 1, H, W, st));
+    if (clamp_io) RF_TRY(launch_ewise(p.x4, nullptr, p.x4, (size_t)B * 4 * H * W, 6, 0.f, st));      // model.py:475
     if (cfg.variant == RF_VARIANT_FLCA) {
         RF_TRY(launch_guidance_base(p.x4, 0, 0, p.gscratch, B, H, W, st));
         for (int l = 0; l < 4; ++l) RF_TRY(launch_guidance_level(p.gscratch, p.guide[l], B, H, W, H >> l, W >> l, st));
@@ -586,10 +596,11 @@ int rf_train_step(rf_handle* h, const float* in, const float* gt, float* grads, 
     }
     RF_TRY(f_conv3x3(c, cur, d, h->conv_out_w, h->prm(h->conv_out_b), p.pred, 4 * oc, H, W, 1, 2));
     const size_t npred = (size_t)B * oc * 4 * H * W;
-    if (pred_out) RF_TRY(check_hip(hipMemcpyAsync(pred_out, p.pred, npred * 4, hipMemcpyDeviceToDevice, st), "copy pred"));
+    if (pred_out && clamp_io) RF_TRY(launch_ewise(p.pred, nullptr, pred_out, npred, 6, 0.f, st));    // model.py:508
+    else if (pred_out) RF_TRY(check_hip(hipMemcpyAsync(pred_out, p.pred, npred * 4, hipMemcpyDeviceToDevice, st), "copy pred"));
 
     // ------------------------------------------------------------------ loss
-    RF_TRY(launch_loss(p.pred, gt, p.dpred, loss_out, p.loss_part, npred, loss_mode, loss_eps, st));
+    RF_TRY(launch_loss(p.pred, gt, p.dpred, loss_out, p.loss_part, npred, loss_mode, loss_eps, h->loss_clamp, st));
 
     // ------------------------------------------------------------------ backward
     float *tA = p.tA, *tB = p.tB;

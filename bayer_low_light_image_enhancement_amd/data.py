@@ -1,0 +1,134 @@
+"""Training batches from a device-resident SID set (RawFomer_WFB_FFAB/load_dataset.py:9-95).
+
+The reference keeps the decoded Sony split in host memory as uint16 arrays (``image_read_SID``, :9-31) and cuts, flips and
+normalises one patch per item in its loader workers (``load_data_SID.__getitem__``, :53-95).  Here the same arrays live in
+device memory (``ResidentSID``; the training split is about 16 GB), the host draws only the four random numbers of a patch
+(``PatchSampler``, the reference's draw order on a private ``random.Random``) and one kernel (``rf_sid_sample``,
+``csrc/rf_sampler.hip``) assembles the whole batch, bit for bit what ``__getitem__`` returns.
+
+As in the reference the flips are flips of the MOSAIC: a left-right flip of an even-aligned crop moves the CFA phase by one
+column, an up-down flip by one row.  That is the reference's augmentation and is reproduced, not corrected.
+
+Decoding the ARW files (rawpy) stays with the caller.  The MCR loader (``load_data_MCR``, :117-178, uint8 sources and a
+per-file exposure ratio) is out of scope.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import random
+from typing import Iterable, List, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+
+
+def amp_from_names(paths: Iterable[str]) -> List[float]:
+    """The amplification of every item from its LONG exposure's file name (:81-84): 300 where ``path[-7] == '3'``
+    (``..._30s.ARW`` beside a 0.1 s short exposure), 100 otherwise."""
+    return [300.0 if p[-7] == "3" else 100.0 for p in paths]
+
+
+def _device_tensor(a, dtype, what: str, device) -> torch.Tensor:
+    if isinstance(a, np.ndarray):
+        if dtype == torch.uint16 and a.dtype != np.uint16:
+            raise TypeError(f"ResidentSID: {what} must be uint16, got {a.dtype}")
+        a = torch.from_numpy(np.ascontiguousarray(a))
+    elif not isinstance(a, torch.Tensor):
+        a = torch.as_tensor(a)
+    if dtype == torch.uint16:
+        if a.dtype != torch.uint16:
+            raise TypeError(f"ResidentSID: {what} must be uint16, got {a.dtype}")
+    else:
+        a = a.to(dtype)
+    return a.to(device).contiguous()
+
+
+class ResidentSID:
+    """The decoded set in device memory: ``raw`` uint16 ``[N,H,W]`` (``raw_image_visible``), ``gt`` uint16 ``[N,H,W,3]``
+    (``postprocess(..., output_bps=16)``, HWC as rawpy returns it) and ``amp`` float32 ``[N]``.  numpy arrays and tensors
+    are accepted; host data is copied to ``device`` (default: the current ROCm device), device tensors are used in place."""
+
+    def __init__(self, raw_u16, gt_u16, amp, black: int = 512, white: int = 16383, device=None):
+        if device is None:
+            device = raw_u16.device if isinstance(raw_u16, torch.Tensor) and raw_u16.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("ResidentSID keeps the set on a ROCm device: there is no CPU path in this package")
+        self.raw = _device_tensor(raw_u16, torch.uint16, "raw", device)
+        self.gt = _device_tensor(gt_u16, torch.uint16, "gt", device)
+        self.amp = _device_tensor(amp, torch.float32, "amp", device)
+        if self.raw.dim() != 3:
+            raise ValueError(f"ResidentSID: raw must be [N,H,W], got {tuple(self.raw.shape)}")
+        n, h, w = self.raw.shape
+        if tuple(self.gt.shape) != (n, h, w, 3):
+            raise ValueError(f"ResidentSID: gt must be {(n, h, w, 3)} (HWC), got {tuple(self.gt.shape)}")
+        if tuple(self.amp.shape) != (n,):
+            raise ValueError(f"ResidentSID: amp must be {(n,)}, got {tuple(self.amp.shape)}")
+        if w % 2:
+            raise ValueError(f"ResidentSID: frame width {w} must be even")
+        if not 0 <= int(black) < int(white):
+            raise ValueError(f"ResidentSID: black level {black}, white level {white}")
+        self.n, self.h, self.w = n, h, w
+        self.black, self.white = int(black), int(white)
+        self.device = device
+
+    amp_from_names = staticmethod(amp_from_names)
+
+    def __len__(self) -> int:
+        return self.n
+
+
+class PatchSampler:
+    """``load_data_SID.__getitem__`` for a list of indices at once.  The descriptors (frame, i, j, flips) are drawn on the host
+    from a private ``random.Random(seed)`` in the reference's order per item -- ``randint(0, (H - P - 2) // 2) * 2`` for i, the same
+    for j, ``randint(0, 100) > 50`` (left-right), ``randint(0, 100) < 20`` (up-down) -- so the same seed and index list give the
+    patches the reference's dataset gives after ``random.seed(seed)``.  ``patch_size``: P (the reference's square patches) or
+    ``(ph, pw)``."""
+
+    def __init__(self, dataset: ResidentSID, patch_size=512, seed=None):
+        ph, pw = (int(v) for v in patch_size) if isinstance(patch_size, (tuple, list)) else (int(patch_size), int(patch_size))
+        if ph <= 0 or pw <= 0 or pw % 4:
+            raise ValueError(f"PatchSampler: patch size {patch_size}: the width must be a positive multiple of 4")
+        if dataset.h - ph - 2 < 0 or dataset.w - pw - 2 < 0:
+            raise ValueError(f"PatchSampler: frames of {dataset.h}x{dataset.w} are too small for patches of {ph}x{pw} (the reference draws from H - P - 2)")
+        self.dataset, self.patch_size, self.ph, self.pw = dataset, patch_size, ph, pw
+        self.rng = random.Random(seed)
+
+    def draw(self, indices: Sequence[int]) -> List[Tuple[int, int, int, int]]:
+        """The next descriptor ``(frame, i, j, flips)`` of every index; flips bit 0 = left-right, bit 1 = up-down."""
+        d, out = self.dataset, []
+        for idx in indices:
+            i = self.rng.randint(0, (d.h - self.ph - 2) // 2) * 2
+            j = self.rng.randint(0, (d.w - self.pw - 2) // 2) * 2
+            lr = self.rng.randint(0, 100) > 50
+            ud = self.rng.randint(0, 100) < 20
+            out.append((int(idx), i, j, int(lr) | int(ud) << 1))
+        return out
+
+    def gather(self, desc: Sequence[Sequence[int]], ph: int, pw: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The patches of an explicit descriptor table: ``x [B,1,ph,pw]``, ``gt [B,3,ph,pw]`` (float32, on the current stream)."""
+        d = self.dataset
+        b = len(desc)
+        table = np.ascontiguousarray(np.asarray(desc, dtype=np.int64).reshape(b, 4).astype(np.int32))
+        lib = _lib.load()
+        _lib.check(lib.rf_sid_check_desc(table.ctypes.data_as(C.POINTER(C.c_int)), d.n, d.h, d.w, b, ph, pw), "rf_sid_check_desc")
+        with torch.cuda.device(d.device):
+            dev_table = torch.from_numpy(table).to(d.device)
+            x = torch.empty((b, 1, ph, pw), dtype=torch.float32, device=d.device)
+            gt = torch.empty((b, 3, ph, pw), dtype=torch.float32, device=d.device)
+            stream = C.c_void_p(torch.cuda.current_stream(d.device).cuda_stream)
+            _lib.check(lib.rf_sid_sample(C.c_void_p(d.raw.data_ptr()), C.c_void_p(d.gt.data_ptr()), C.c_void_p(d.amp.data_ptr()),
+                                         C.c_void_p(dev_table.data_ptr()), C.c_void_p(x.data_ptr()), C.c_void_p(gt.data_ptr()),
+                                         d.n, d.h, d.w, b, ph, pw, d.black, d.white, stream), "rf_sid_sample")
+        return x, gt
+
+    def batch(self, indices: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Random patches of the items ``indices`` (``training=True``): ``x [B,1,P,P]``, ``gt [B,3,P,P]``."""
+        return self.gather(self.draw(indices), self.ph, self.pw)
+
+    def whole(self, indices: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The whole frames of the items ``indices`` (``training=False``, :77-79): no crop, no flip, no random draw."""
+        d = self.dataset
+        return self.gather([(int(i), 0, 0, 0) for i in indices], d.h, d.w)

@@ -1,19 +1,30 @@
 """Training step on the HIP path (SURVEY.md section 8 f3 / BASELINE configs[4]).
 
-Mirrors the reference's loop body (train.py:127-147; RawFomer_WFB_FFAB/train.py:124 for the L1 loss):
+Mirrors the reference's loop body (train.py:132-145; RawFomer_WFB_FFAB/train.py:124 for the L1 loss):
 
     pred = model(inp); loss = criterion(pred, gt); optimizer.zero_grad(); loss.backward(); optimizer.step()
 
-with torch.autograd replaced by the library's explicit adjoint schedule (``rf_train_step``) and ``nn.DataParallel``
+(``Trainer(clamp_pred=True)`` puts the reference's ``pred = torch.clamp(pred, 0, 1)`` of train.py:139 in front of the criterion;
+the default evaluates the criterion on the raw prediction) with torch.autograd replaced by the library's explicit adjoint schedule (``rf_train_step``) and ``nn.DataParallel``
 (train.py:108-111) by one process per GPU: every rank runs its own images, the flat gradient buffer is all-reduced in
 fixed-size buckets (RCCL with the ``nccl`` backend, ``gloo`` in the CPU tests), then ``rf_adam_step`` updates the flat
 parameter buffer.  PyTorch provides device memory, streams and the collective; no torch op computes anything.
+
+Around the step, ``fit`` is the reference's epoch loop (train.py:113-175): ``warmup_cosine_lr`` restates the learning rate its
+``GradualWarmupScheduler`` + ``CosineAnnealingLR`` pair leaves in the optimiser, batches come from a device-resident set
+(``data.PatchSampler``), validation is the uint8 PSNR of the evaluation harness, the best checkpoint has the reference's
+``{'epoch', 'state_dict', 'optimizer'}`` layout and the log its line format.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
+import os
+import random
+import time
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -86,7 +97,7 @@ class Trainer:
 
     def __init__(self, model: RawFormer, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  decoupled: bool = False, loss: str = "l1", charbonnier_eps: float = 1e-3, group=None, overlap_allreduce: bool = True,
-                 bucket_floats: int = 1 << 20):
+                 bucket_floats: int = 1 << 20, clamp_pred: bool = False):
         if model.variant not in ("plain", "flca"):
             raise RuntimeError("Trainer: the adjoint schedule exists for variants 'plain' and 'flca'")
         dev = next(model.parameters()).device
@@ -96,6 +107,7 @@ class Trainer:
         self.lr, self.betas, self.eps, self.wd, self.decoupled = float(lr), betas, float(eps), float(weight_decay), bool(decoupled)
         self.loss_mode = {"l1": LOSS_L1, "charbonnier": LOSS_CHARBONNIER}[loss]
         self.loss_eps = float(charbonnier_eps)
+        self.clamp_pred = bool(clamp_pred)       # the criterion sees clamp(pred, 0, 1): train.py:139
         lib = _lib.load()
         self.state = model._state_for(dev)
         n = C.c_size_t()
@@ -134,8 +146,9 @@ class Trainer:
         off, n = self.slices[key]
         return self.grads[off: off + n].view(dict(self.model.named_parameters())[key].shape)
 
-    def forward_backward(self, x: torch.Tensor, gt: torch.Tensor, want_pred: bool = False):
-        """Loss (device scalar) and, in ``self.grads``, this rank's gradient of the mean loss over ITS images."""
+    def forward_backward(self, x: torch.Tensor, gt: torch.Tensor, want_pred: bool = False, loss_out: Optional[torch.Tensor] = None):
+        """Loss (device scalar; written into ``loss_out``, one float32 on the device, when given) and, in ``self.grads``, this
+        rank's gradient of the mean loss over ITS images."""
         lib = _lib.load()
         x, gt = x.detach().float().contiguous(), gt.detach().float().contiguous()
         b, c, h, w = x.shape
@@ -156,14 +169,17 @@ class Trainer:
             import torch.distributed as dist
             overlapped = self.overlap and dist.is_initialized() and (dist.get_world_size(self.group) > 1 or self.overlap_always)
             _lib.check(lib.rf_set_grad_ready(self.state.handle, self._ready_cb if overlapped else _lib.GRAD_READY_FN(), None), "rf_set_grad_ready")
-            if overlapped:
-                self.reducer.begin()
+            self.reducer.begin()                # waits for a previous round's all-reduces: they write into self.grads
+            _lib.check(lib.rf_set_loss_clamp(self.state.handle, int(self.clamp_pred)), "rf_set_loss_clamp")
+            loss_dev = self.loss_dev if loss_out is None else loss_out
+            if loss_dev.dtype != torch.float32 or loss_dev.numel() != 1 or loss_dev.device != x.device:
+                raise RuntimeError("loss_out must be one float32 on the input's device")
             _lib.check(lib.rf_train_step(self.state.handle, C.c_void_p(x.data_ptr()), C.c_void_p(gt.data_ptr()), C.c_void_p(self.grads.data_ptr()),
-                                         C.c_void_p(self.loss_dev.data_ptr()), C.c_void_p(pred.data_ptr() if want_pred else None),
+                                         C.c_void_p(loss_dev.data_ptr()), C.c_void_p(pred.data_ptr() if want_pred else None),
                                          C.c_void_p(self.workspace.data_ptr()), self.workspace.numel(), b, H, W, self.loss_mode, self.loss_eps,
                                          stream), "rf_train_step")
             self._reduced = overlapped          # the buckets are on the wire (or done); optimizer_step waits for them
-        return (self.loss_dev, pred) if want_pred else self.loss_dev
+        return (loss_dev, pred) if want_pred else loss_dev
 
     def optimizer_step(self):
         import torch.distributed as dist
@@ -183,7 +199,130 @@ class Trainer:
                                         int(self.decoupled), self.step_no, 1.0 / world, stream), "rf_adam_step")
         self.model.invalidate_packed()          # the weights moved: packed copies are stale
 
-    def step(self, x: torch.Tensor, gt: torch.Tensor) -> torch.Tensor:
-        loss = self.forward_backward(x, gt)
+    def step(self, x: torch.Tensor, gt: torch.Tensor, loss_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        loss = self.forward_backward(x, gt, loss_out=loss_out)
         self.optimizer_step()
         return loss
+
+    def optimizer_state_dict(self) -> dict:
+        """``torch.optim.Adam(model.parameters()).state_dict()`` of this trainer: ``state[i] = {step, exp_avg, exp_avg_sq}`` in
+        ``model.parameters()`` order (host copies of the parameter's slices of the flat moment buffers) and one parameter group."""
+        step = torch.tensor(float(self.step_no))
+        state = {}
+        for i, (k, p) in enumerate(self.model.named_parameters()):
+            off, n = self.slices[k]
+            state[i] = {"step": step.clone(), "exp_avg": self.m[off: off + n].view(p.shape).cpu(), "exp_avg_sq": self.v[off: off + n].view(p.shape).cpu()}
+        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd, "amsgrad": False, "maximize": False,
+                 "foreach": None, "capturable": False, "differentiable": False, "fused": None, "decoupled_weight_decay": self.decoupled,
+                 "params": list(range(len(state)))}
+        return {"state": state, "param_groups": [group]}
+
+    def load_optimizer_state_dict(self, sd: dict) -> None:
+        """Resume from ``optimizer_state_dict()`` or from a real ``torch.optim.Adam.state_dict()`` over the same model."""
+        names = [k for k, _ in self.model.named_parameters()]
+        groups = sd["param_groups"]
+        if len(groups) != 1 or len(groups[0]["params"]) != len(names):
+            raise RuntimeError(f"optimizer state: expected one parameter group of {len(names)} tensors")
+        if groups[0].get("amsgrad"):
+            raise RuntimeError("optimizer state: amsgrad has no counterpart in rf_adam_step")
+        g = groups[0]
+        self.lr, self.betas, self.eps, self.wd = float(g["lr"]), tuple(float(b) for b in g["betas"]), float(g["eps"]), float(g["weight_decay"])
+        self.decoupled = bool(g.get("decoupled_weight_decay", self.decoupled))
+        state, steps = sd["state"], set()
+        self.m.zero_()
+        self.v.zero_()
+        for i, pid in enumerate(g["params"]):
+            st = state.get(pid)
+            if st is None:                     # torch creates a tensor's state at its first step
+                continue
+            off, n = self.slices[names[i]]
+            for buf, key in ((self.m, "exp_avg"), (self.v, "exp_avg_sq")):
+                t = st[key]
+                if t.numel() != n:
+                    raise RuntimeError(f"optimizer state: {key} of '{names[i]}' has {t.numel()} elements, expected {n}")
+                buf[off: off + n].copy_(t.reshape(-1))
+            steps.add(int(st["step"]))
+        if len(steps) > 1:
+            raise RuntimeError(f"optimizer state: the tensors disagree on the step count ({sorted(steps)})")
+        self.step_no = steps.pop() if steps else 0
+
+
+def warmup_cosine_lr(epoch: int, base_lr: float = 1e-4, epochs: int = 3000, warmup: int = 20, eta_min: float = 1e-5) -> float:
+    """The learning rate the reference's optimiser holds DURING epoch ``epoch`` (train.py:113-115, ``scheduler.step()`` at the
+    end of every epoch, :147): ``CosineAnnealingLR(optimizer, epochs, eta_min)`` behind ``GradualWarmupScheduler(multiplier=1,
+    total_epoch=warmup)``.  What that pair does, not a textbook schedule:
+
+    * epochs 0..warmup ramp ``base_lr * epoch / warmup``: epoch 0 trains at 0.0 and epoch ``warmup`` at ``base_lr``;
+    * epoch ``warmup + 1`` is the hand-over: the cosine scheduler, which has never stepped, is asked for its value at ITS epoch 0
+      and applies its recursive update ``(1 + cos(pi t / T)) / (1 + cos(pi (t - 1) / T))`` with t = 0 to the rate in the
+      optimiser, ``base_lr``: the rate rises ABOVE ``base_lr``, by the factor ``2 / (1 + cos(pi / T))`` on its part over ``eta_min``;
+    * the next epoch undoes that (``base_lr`` again) and from there the recursion telescopes: epoch ``e`` has
+      ``eta_min + (base_lr - eta_min) (1 + cos(pi t / T)) / (1 + cos(pi / T))`` with ``t = e - warmup - 1``: the cosine runs from
+      its own epoch 0 over ``T = epochs`` (not ``epochs - warmup``), one epoch late and scaled by that factor, so the last epoch
+      is still well above ``eta_min``.
+
+    The values were read from the real optimiser (tests/golden/lr_schedule.json); the reference's recursion and this closed form
+    differ by rounding only."""
+    if epoch <= warmup:
+        return base_lr * (float(epoch) / warmup)
+    t = epoch - warmup - 1
+    return eta_min + (base_lr - eta_min) * (1.0 + math.cos(math.pi * t / epochs)) / (1.0 + math.cos(math.pi / epochs))
+
+
+def validate(model: RawFormer, val_sampler) -> float:
+    """Mean uint8 PSNR (data range 255) of the whole validation frames, one frame at a time (train.py:150-164)."""
+    from . import harness
+    was_training = model.training
+    model.eval()
+    psnr_val_rgb = []
+    try:
+        with torch.no_grad():
+            for idx in range(len(val_sampler.dataset)):
+                x, gt = val_sampler.whole([idx])
+                psnr_val_rgb.extend(float(v) for v in harness.psnr_u8(harness.to_uint8_hwc(gt), harness.to_uint8_hwc(model(x))))
+    finally:
+        model.train(was_training)
+    return float(np.mean(psnr_val_rgb))
+
+
+def fit(trainer: Trainer, sampler, val_sampler, epochs: int, batch_size: int, out_dir: str, start_epoch: int = 0, shuffle_seed=None, *,
+        base_lr: Optional[float] = None, warmup: int = 20, eta_min: float = 1e-5, log_name: str = "train_log.txt"):
+    """The reference's epoch loop (train.py:127-176) on ``Trainer.step``.  Epochs ``start_epoch .. epochs`` INCLUSIVE, as there
+    (``range(start_epoch, epochs + 1)``).  Per epoch: the learning rate of ``warmup_cosine_lr`` (``base_lr``: the trainer's rate
+    at the call), one pass over a shuffled index list in batches of ``batch_size`` (the last one shorter, ``DataLoader``'s
+    default), the sum of the batch losses read from the device ONCE, validation (``validate``), ``model_best.pth`` =
+    ``{'epoch', 'state_dict', 'optimizer'}`` in ``out_dir`` on a new best PSNR (:165-172; host tensors) and one line of :175's
+    format appended to ``out_dir/log_name``.  No progress bar, no image writing.  To resume, load a checkpoint's ``state_dict``
+    into the model and its ``optimizer`` with ``Trainer.load_optimizer_state_dict``, then pass ``start_epoch = epoch + 1``.
+    Returns one dict per epoch: ``epoch``, ``lr``, ``loss``, ``psnr``, ``best_psnr``, ``best_epoch``."""
+    model = trainer.model
+    os.makedirs(out_dir, exist_ok=True)
+    base_lr = trainer.lr if base_lr is None else float(base_lr)
+    order_rng = random.Random(shuffle_seed)
+    n = len(sampler.dataset)
+    steps = (n + batch_size - 1) // batch_size
+    losses = torch.zeros(steps, dtype=torch.float32, device=trainer.flat.device)
+    best_psnr, best_epoch, history = 0, 0, []
+    with open(os.path.join(out_dir, log_name), "a") as log_f:
+        for epoch in range(start_epoch, epochs + 1):
+            start_time = time.time()
+            model.train()
+            trainer.lr = warmup_cosine_lr(epoch, base_lr, epochs, warmup, eta_min)
+            order = list(range(n))
+            order_rng.shuffle(order)
+            for k in range(steps):
+                x, gt = sampler.batch(order[k * batch_size: (k + 1) * batch_size])
+                trainer.step(x, gt, loss_out=losses[k: k + 1])
+            epoch_loss = 0
+            for v in losses.cpu().tolist():          # the epoch's one host read; added in step order, as `+= loss.item()`
+                epoch_loss += v
+            avg_psnr = validate(model, val_sampler)
+            if avg_psnr > best_psnr:
+                best_psnr, best_epoch = avg_psnr, epoch
+                torch.save({"epoch": epoch, "state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()},
+                            "optimizer": trainer.optimizer_state_dict()}, os.path.join(out_dir, "model_best.pth"))
+            epoch_time = time.time() - start_time
+            log_f.write(f"Epoch {epoch}/{epochs} | Time: {epoch_time:.2f}s | Loss: {epoch_loss:.4f} | Avg PSNR: {avg_psnr:.4f} | Best PSNR: {best_psnr:.4f} (Epoch {best_epoch})\n")
+            log_f.flush()
+            history.append({"epoch": epoch, "lr": trainer.lr, "loss": epoch_loss, "psnr": avg_psnr, "best_psnr": best_psnr, "best_epoch": best_epoch})
+    return history

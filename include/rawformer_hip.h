@@ -118,7 +118,12 @@ int rf_forward_stage(rf_handle* h, int stage, const float* in, const float* pack
  * parameter buffer, all-reduces the flat gradient buffer across ranks (RCCL) and calls rf_adam_step on the three buffers.
  * rf_train_step: in [B,1,2H,2W] mosaic, gt [B,3,2H,2W]; writes grads (flat), *loss_out (device float), optionally the prediction.
  * loss_mode 0: L1 (RawFomer_WFB_FFAB/train.py:124); 1: Charbonnier sqrt(d^2 + eps^2) (train.py:16-25).
- * Adjoint schedule for variants PLAIN and FLCA (no clamp_io); packed W must be a multiple of 32. */
+ * Adjoint schedule for variants PLAIN and FLCA (no clamp_io); packed W must be a multiple of 32.
+ * rf_set_loss_clamp(h, 1): the criterion of train.py:139, loss(clamp(pred, 0, 1), gt).  The seed gradient is multiplied by
+ * (0 <= pred <= 1), torch.clamp's subgradient, ends included; pred_out stays the model's output.  With it on, PLAIN models
+ * with clamp_io train too: their output clamp (model.py:508) under the criterion's is the same mask and their input clamp
+ * (:475) carries no parameter gradient; pred_out is then the clamped output, which is what such a model returns.  Default off. */
+int rf_set_loss_clamp(rf_handle* h, int on);
 int rf_flat_param_floats(const rf_handle* h, size_t* floats);
 int rf_flat_offset(const rf_handle* h, int index, size_t* offset);
 int rf_train_workspace_bytes(const rf_handle* h, int B, int H, int W, size_t* bytes);
@@ -264,6 +269,19 @@ int rf_u8_ssim(const unsigned char* a, const unsigned char* b, double* ssim_sums
  * (0,0) (0,1) (1,0) (1,1) (a1); mode 2: normalised mosaic [B,1,2h,2w] (RawFormer.forward's input).
  * black = min(black_level_per_channel); w % 4 == 0. */
 int rf_sid_pack(const unsigned short* raw, float* out, int B, int h, int w, int black, int white, double ratio, int mode, void* stream);
+
+/* ---- SID training batches from a device-resident set: load_data_SID.__getitem__, RawFomer_WFB_FFAB/load_dataset.py:53-95 ----
+ * raw [N,H,W] uint16 short exposures, gt [N,H,W,3] uint16 long exposures (HWC), amp [N] float (100 / 300, :81-84).  Patch b is
+ * rows i..i+ph, columns j..j+pw of frame desc[b][0], flipped left-right (flips bit 0) then up-down (bit 1) -- the mosaic itself
+ * is flipped, as in the reference, so the CFA phase changes -- and normalised:
+ *   x  = ((clip((float)raw, black, white) - black) / (float)(white - black + 1e-6)) * amp    in float32, each step rounded (:88-89)
+ *   gt = (float)((double)v / 65535.0)                                                        (:90, :93)
+ * x_out [B,1,ph,pw], gt_out [B,3,ph,pw].  pw % 4 == 0, W even, i and j even.  `desc` [B,4] = (frame, i, j, flips) is a DEVICE
+ * table: the host that built it checks it with rf_sid_check_desc (HOST pointer, no device work); a patch whose descriptor is out of range
+ * all the same is skipped by the kernel, which never reads or writes outside the buffers. */
+int rf_sid_check_desc(const int* desc_host, int N, int H, int W, int B, int ph, int pw);
+int rf_sid_sample(const unsigned short* raw, const unsigned short* gt, const float* amp, const int* desc, float* x_out, float* gt_out,
+                  int N, int H, int W, int B, int ph, int pw, int black, int white, void* stream);
 
 /* ---- luminance-aware token attention: Attenblock.py:161-220 -----------------
  * softmax(q_i . k_j * scale) v_j per (image, head), flash style (the N x N scores are never stored).

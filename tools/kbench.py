@@ -5,7 +5,7 @@ Each case runs through the C ABI (ops.*) with the library's own HIP-event bracke
 (rf_profile_begin/end), so the figure is the kernel's time on its launch stream, without the
 weight-repack helper that the operator-level entry points run first.
 
-usage: python tools/kbench.py [conv1x1] [conv3x3] [dw] [attn] [flca] [dwt] [ssim] [--dim 32] [--batch 8] [--size 512]
+usage: python tools/kbench.py [conv1x1] [conv3x3] [dw] [attn] [flca] [dwt] [ssim] [sampler] [--dim 32] [--batch 8] [--size 512]
 """
 from __future__ import annotations
 
@@ -95,6 +95,13 @@ def main():
             ib = (ia.to(torch.int16) + torch.randint(-9, 10, ia.shape, dtype=torch.int16, device=dev)).clamp(0, 255).to(torch.uint8)
             report(f"ssim {bb}x{hh}x{ww}x3", timed(lambda: harness.ssim_u8_channel_means(ia, ib)))
             del ia, ib
+    if "sampler" in a.what:   # training batch assembly: 16 patches of 512 x 512 out of 16 resident SID frames (GB/s = the 24 B / pixel of algorithmic traffic)
+        from bayer_low_light_image_enhancement_amd.data import PatchSampler, ResidentSID
+        nf, hh, ww = 16, 2848, 4256
+        u16 = lambda *s: torch.randint(-32768, 32768, s, dtype=torch.int16, device=dev).view(torch.uint16)  # noqa: E731
+        smp = PatchSampler(ResidentSID(u16(nf, hh, ww), u16(nf, hh, ww, 3), [100.0, 300.0] * (nf // 2)), patch_size=512, seed=0)
+        report(f"sid_sample 16x512x512 of {nf}x{hh}x{ww}", timed(lambda: smp.batch(list(range(16)))))
+        del smp
     if "dwt" in a.what:
         x = r(B, d, S, S)
         report("dwt_init", timed(lambda: ops.dwt_init(x)))
