@@ -103,10 +103,13 @@ int run_chan_attn(const TbParams& p, const float* in, float* out, bool residual,
 
 int run_transformer(const TbParams& p, const float* in, float* out, float* ws, const TbBufOffsets& o,
                     int B, int C, int heads, int hc, int hh, int ww, hipStream_t st) {
-    const int Pn = hh * ww;
-    float* bufA = ws + o.bufA;
-    float* bufB = ws + o.bufB;
-    float* x1 = ws + o.x1;
+    RF_TRY(run_transformer_attn(p, in, ws, o, B, C, heads, hh, ww, st));
+    return run_transformer_ffn(p, out, ws, o, B, C, hc, hh, ww, st);
+}
+
+// x + attn(LN1(x)) -> x1 ---------------------------------------------------------------------
+int run_transformer_attn(const TbParams& p, const float* in, float* ws, const TbBufOffsets& o, int B, int C, int heads, int hh, int ww,
+                         hipStream_t st) {
 #ifdef RF_DIAG   // diagnostic build only (build.py --diag): force the op-by-op path; the shipped library has no switch
     const bool no_fuse = getenv("RF_NO_FUSE") != nullptr;
     const bool no_fuse_attn = no_fuse || getenv("RF_NO_FUSE_ATTN") != nullptr;
@@ -114,18 +117,26 @@ int run_transformer(const TbParams& p, const float* in, float* out, float* ws, c
     constexpr bool no_fuse = false, no_fuse_attn = false;
 #endif
 
-    // x + attn(LN1(x)) ---------------------------------------------------------------------
-    RF_TRY(run_chan_attn(p, in, x1, true, AttnBufs{bufA, bufB, ws + o.partial, ws + o.wfold, ws + o.wfold3}, B, C, heads, hh, ww, st, no_fuse,
-                         no_fuse_attn));
+    return run_chan_attn(p, in, ws + o.x1, true, AttnBufs{ws + o.bufA, ws + o.bufB, ws + o.partial, ws + o.wfold, ws + o.wfold3}, B, C, heads,
+                         hh, ww, st, no_fuse, no_fuse_attn);
+}
 
-    // x + ffn(LN2(x)) ----------------------------------------------------------------------
-    if (transformer_ffn_is_fused(p, C, hc, hh, ww)) {
+// x1 + ffn(LN2(x1)) -> out -------------------------------------------------------------------
+int run_transformer_ffn(const TbParams& p, float* out, float* ws, const TbBufOffsets& o, int B, int C, int hc, int hh, int ww, hipStream_t st) {
+    const int Pn = hh * ww;
+    float* bufA = ws + o.bufA;
+    float* bufB = ws + o.bufB;
+    float* x1 = ws + o.x1;
+    const bool fused = transformer_ffn_is_fused(p, C, hc, hh, ww);
+    RF_CHECK_ARG(!p.tail.xs || (fused && fused_ffn_tail_supported(C)), "transformer: the stage tail needs the fused FFN kernel (C = %d)", C);
+    if (fused) {
         // LN2 -> 1x1 -> depthwise 3x3 -> GELU -> 1x1 + residual in one kernel: the hidden tensor stays on chip
         FfnArgs f{};
         f.x = x1; f.out = out;
         f.ln_w = p.ln2_w; f.ln_b = p.ln2_b; f.w1p = p.pw1_wp3; f.b1 = p.pw1_b; f.wd = p.dw_w; f.bd = p.dw_b; f.w2p = p.pw2_wp; f.b2 = p.pw2_b;
         f.B = B; f.h = hh; f.w = ww;
-        RF_TRY(launch_ffn_fused(f, C, st));
+        if (p.tail.xs) f.b2 = p.tail_bias;      // ... and the caller's channel_reduce on top
+        RF_TRY(launch_ffn_fused(f, C, st, p.tail));
     } else {
         Conv1x1Args f1{};
         f1.x1 = x1; f1.C1 = C; f1.x1_bstride = (int64_t)C * Pn;

@@ -300,8 +300,18 @@ struct FfnArgs {           // out = x + W2 gelu(dw3x3(W1 LN2(x) + b1) + bd) + b2
     const float* b2;       // [C]
     int B, h, w, tiles_x, ntiles;
 };
+// Stage tail (C = 32 only, fused_ffn_tail_supported): with one the kernel writes channel_reduce(cat(xs, x + ffn(x)))
+//   out = Wa'_b xs + Wb x + (Wb W2) g + (Wb b2 + b_cr)       (g = the GELU output; composition: rf_flca.hip pack_tail)
+// FfnArgs.b2 is then the composed bias and FfnArgs.w2p is not read: Wb W2 is the last 2C/4 k-sets of `wp`.
+struct FfnTail {
+    const float* xs;           // [B][C][h][w] branch output; nullptr: no tail
+    const float* wp;           // [Wa' | Wb | Wb W2] in f32 MFMA operand order [(2C + 2C)/4][C/16][64] (flca_fold_kernel's wp_out)
+    int64_t wp_bstride;        // floats between the images' sets (0: one static set)
+};
 bool fused_ffn_supported(int C, int hidden, int h, int w);
-int launch_ffn_fused(FfnArgs a, int C, hipStream_t st);
+bool fused_ffn_tail_supported(int C);
+int launch_ffn_fused(FfnArgs a, int C, hipStream_t st, FfnTail tail = FfnTail{nullptr, nullptr, 0});
+int launch_ffn_fused_tail32(const FfnArgs& a, const FfnTail& tail, dim3 grid, hipStream_t st);   // rf_fused_tail.hip; called by launch_ffn_fused
 
 struct AttnFrontArgs {     // LN1 -> qkv 1x1 -> depthwise 3x3 -> Gram partials of (q, k) + v, for C = 32
     const float* x;        // [B][C][h][w]
@@ -352,12 +362,21 @@ struct TbParams {
     // hidden tensor in bufB, `out` is not written; the caller's channel_reduce GEMM applies pointwise2 (transformer_ffn_is_fused
     // tells it which path runs)
     bool defer_pw2 = false;
+    // fused stage tail: on the fused FFN path (C = 32) the kernel applies the caller's channel_reduce too, `out` receives
+    // channel_reduce(cat(tail.xs, block output)); tail_bias = the composed bias
+    FfnTail tail{nullptr, nullptr, 0};
+    const float* tail_bias = nullptr;
 };
 bool transformer_ffn_is_fused(const TbParams& p, int C, int hc, int hh, int ww);
 struct TbBufOffsets { size_t bufA, bufB, x1, partial, wfold, wfold3; };   // float offsets into one scratch area
 size_t transformer_scratch_floats(int B, int C, int heads, int hc, int h, int w, TbBufOffsets* o);
 int run_transformer(const TbParams& p, const float* in, float* out, float* ws, const TbBufOffsets& o,
                     int B, int C, int heads, int hc, int hh, int ww, hipStream_t st);
+// its two halves: x1 = in + attn(LN1(in)) into the x1 buffer, then out = x1 + ffn(LN2(x1)) (a caller may order other work
+// between them: run_stage joins the branch there when the FFN kernel carries the stage tail)
+int run_transformer_attn(const TbParams& p, const float* in, float* ws, const TbBufOffsets& o, int B, int C, int heads, int hh, int ww,
+                         hipStream_t st);
+int run_transformer_ffn(const TbParams& p, float* out, float* ws, const TbBufOffsets& o, int B, int C, int hc, int hh, int ww, hipStream_t st);
 // The attention half of the block, also the whole of rf_chan_attn:  out = [in +] W_out softmax(T q^ k^T) v + b  with
 // q, k, v = depthwise3x3(W_qkv [LN1](in)).  Reads the attention fields of `p`; p.ln1_w == nullptr: no LayerNorm (and never the
 // attn_front kernel, which has one built in).  The no_fuse switches are the diagnostic build's (run_transformer sets them).
@@ -472,12 +491,15 @@ int launch_scale_channels_to(const float* in, float* out, const float* ch, int B
 // SE + fold into channel_reduce: wp_out[b] = pack([Wa * diag(ch_b) | Wb])
 int launch_flca_se_fold(const float* partial, int nblk, int P, const SePrm& se, const float* w_cr, float* wp_out,
                         void* wp3_out /* b3 form too, or nullptr */, float* ch_out, int B, int C, hipStream_t st,
-                        const float* composed = nullptr /* pack_tail: emit [Wa diag(ch_b) | Wb | Wb W2] in b3 form only */, int hc = 0);
+                        const float* composed = nullptr /* pack_tail: emit [Wa diag(ch_b) | Wb | Wb W2], in whichever of the two forms has
+                                                           a pointer (wp_out then holds packed1x1_floats(2C + hc, C) per image) */,
+                        int hc = 0);
 // Composed stage tail (rf_model.hip run_stage): channel_reduce(cat(xs, x1 + W2 g + b2)) as ONE GEMM over [xs ; x1 ; g].
-// pack_tail writes Wb W2 ([C][hc]) and the composed bias ([C]) once per parameter load; launch_tail_fold the b3 weights.
+// pack_tail writes Wb W2 ([C][hc]) and the composed bias ([C]) once per parameter load; launch_tail_fold the weights, in b3 form
+// (the GEMM of levels 1-3) and / or in f32 operand order (wp_out: the fused FFN kernel's tail at level 0).
 size_t tail_composed_floats(int C, int hc);
 int pack_tail(const float* w_cr, const float* b_cr, const float* w2, const float* b2, float* composed, int C, int hc, hipStream_t st);
 int launch_tail_fold(const float* w_cr, const float* ch /* [B][C] gate or nullptr */, const float* composed, void* wp3_out, int B, int C, int hc,
-                     hipStream_t st);
+                     hipStream_t st, float* wp_out = nullptr);
 
 }  // namespace rf

@@ -382,8 +382,9 @@ __global__ void __launch_bounds__(256) flca_se_kernel(const float* __restrict__ 
 
 // wp_out[b] = pack([W_a diag(ch_b) | W_b]) in MFMA operand order
 // (and, when wp3_out is given, the same matrix in b3 form for the bf16x3 GEMM: rf_common.h).
-// With `wc` (tail_compose_kernel below: W_b W_2, [C][hc]) the matrix is [W_a diag(ch_b) | W_b | W_b W_2], K = 2C + hc, written in
-// b3 form only: the weights of the composed stage tail (rf_model.hip, run_stage).  ch == nullptr: no gate (plain variant).
+// With `wc` (tail_compose_kernel below: W_b W_2, [C][hc]) the matrix is [W_a diag(ch_b) | W_b | W_b W_2], K = 2C + hc: the weights
+// of the composed stage tail (rf_model.hip, run_stage), in b3 form for the GEMM of levels 1-3 or in f32 operand order for the
+// fused FFN kernel of level 0 (whichever pointer is given).  ch == nullptr: no gate (plain variant).
 __global__ void __launch_bounds__(256) flca_fold_kernel(const float* __restrict__ w_cr, const float* __restrict__ ch, const float* __restrict__ wc,
                                                         float* __restrict__ wp_out, unsigned short* __restrict__ wp3_out, int C, int hc) {
     const size_t b = blockIdx.y;
@@ -434,10 +435,11 @@ static int fold_grid(int C, int K) {
     return gx < 1 ? 1 : gx;
 }
 
-// [W_a diag(ch_b) | W_b | W_b W_2] in b3 form for B images (ch == nullptr: B = 1 static set without a gate)
-int launch_tail_fold(const float* w_cr, const float* ch, const float* composed, void* wp3_out, int B, int C, int hc, hipStream_t st) {
-    RF_CHECK_ARG(w_cr && composed && wp3_out && C % 32 == 0 && hc % 32 == 0, "tail_fold: bad arguments (C = %d, hidden = %d)", C, hc);
-    flca_fold_kernel<<<dim3((unsigned)fold_grid(C, 2 * C + hc), (unsigned)B), 256, 0, st>>>(w_cr, ch, composed, nullptr, (unsigned short*)wp3_out, C, hc);
+// [W_a diag(ch_b) | W_b | W_b W_2] for B images, in b3 form (wp3_out) and / or f32 operand order (wp_out, packed1x1_floats(2C + hc, C)
+// per image); ch == nullptr: B = 1 static set without a gate
+int launch_tail_fold(const float* w_cr, const float* ch, const float* composed, void* wp3_out, int B, int C, int hc, hipStream_t st, float* wp_out) {
+    RF_CHECK_ARG(w_cr && composed && (wp3_out || wp_out) && C % 32 == 0 && hc % 32 == 0, "tail_fold: bad arguments (C = %d, hidden = %d)", C, hc);
+    flca_fold_kernel<<<dim3((unsigned)fold_grid(C, 2 * C + hc), (unsigned)B), 256, 0, st>>>(w_cr, ch, composed, wp_out, (unsigned short*)wp3_out, C, hc);
     return check_launch("tail_fold");
 }
 
@@ -481,7 +483,7 @@ int launch_flca_se_fold(const float* partial, int nblk, int P, const SePrm& se, 
     ProfScope prof(st, "flca_se_kernel+flca_fold_kernel", 0.0, 0.0);
     const int rc = launch_flca_se(partial, nblk, P, se, ch_out, B, C, st);
     if (rc) return rc;
-    if (composed) return launch_tail_fold(w_cr, ch_out, composed, wp3_out, B, C, hc, st);
+    if (composed) return launch_tail_fold(w_cr, ch_out, composed, wp3_out, B, C, hc, st, wp_out);
     flca_fold_kernel<<<dim3((unsigned)fold_grid(C, 2 * C), (unsigned)B), 256, 0, st>>>(w_cr, ch_out, nullptr, wp_out, (unsigned short*)wp3_out, C, 0);
     return check_launch("flca_se_fold");
 }

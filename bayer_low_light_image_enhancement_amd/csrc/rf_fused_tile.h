@@ -1,0 +1,394 @@
+// The tile machinery of the fused transformer-block kernels (rf_fused.hip has the overview) and ffn_fused_kernel itself, in a
+// header because the kernel is instantiated in two translation units: rf_fused.hip builds <32, false>, rf_fused_tail.hip
+// <32, true>.  hipcc compiles a translation unit's kernels together, and a second instantiation beside the first changed the
+// code of the first AND of attn_front_kernel / attn_mid_kernel (tools/isa_same.py); on its own each compiles as before.
+#pragma once
+#include "rf_common.h"
+
+namespace rf {
+
+#ifdef RF_STAMP
+// Diagnostic build only (python -m ...build --stamp): per-phase cycle sums of wave 0 lanes into g_stamp (rf_fused.hip), read back
+// with rf_debug_stamps().  Never compiled into the shipped library.
+#define STAMP_DECL unsigned long long st_prev = __builtin_amdgcn_s_memtime(), st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#define STAMP(i) do { __builtin_amdgcn_sched_barrier(0); unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[i] += t_ - st_prev; st_prev = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
+#define STAMP_FLUSH do { if ((threadIdx.x & 63) == 0) for (int i_ = 0; i_ < 8; ++i_) atomicAdd(&g_stamp[i_], st_acc[i_]); } while (0)
+#else
+#define STAMP_DECL
+#define STAMP(i)
+#define STAMP_FLUSH
+#endif
+
+// Workgroup barrier that orders LDS traffic only.  __syncthreads() makes hipcc drain vmcnt(0) first,
+// which would stall every wave on the next tile's prefetch loads that are deliberately in flight.
+__device__ __forceinline__ void lds_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+
+namespace fused {
+constexpr int TH = 4, TW = 64;          // output tile
+constexpr int HR = TH + 2;              // halo'd rows
+constexpr int HC = 72;                  // halo'd columns held (18 groups of 4 px)
+constexpr int NG = HR * (HC / 4);       // 108 pixel groups per tile
+constexpr int GPW = NG / 4;             // 27 groups per wave in phase A (two MFMA steps: 16 + 11)
+constexpr int GPW8 = 14;                // ... of the eight-wave kernel: one step (8 x 14 = 112 >= 108)
+constexpr int PART = 32;                // intermediate channels per part
+// Plane stride of the Gram rounds, where lane (j, kq) reads 16 bytes at plane j, column 4 kq (+ 16 st): a ds_read_b128 is
+// served in four groups of 16 lanes, each holding every j once with two different kq (MI355X_MICROARCH.md, LDS), so the
+// groups are conflict-free iff (PSG j + 4 kq) mod 64 are 16 distinct multiples of 4: PSG = 8 mod 64.  (452 = 4 mod 64 made
+// lanes (j, 1) and (j + 1, 0) collide: SQ_LDS_BANK_CONFLICT was 55 % of the LDS-active cycles of attn_front.)
+constexpr int PSG = 456;
+}  // namespace fused
+
+// ---- shared phase-A machinery ------------------------------------------------------------------
+// A wave's share of the halo'd pixel groups, G of them in steps of 16 (G <= 16: step 0 only; the last wave's share may then run
+// past the tile): geometry of step st for lane j.
+struct GroupGeom {
+    int lds_off;     // row * HC + 4 * cg
+    int goff;        // y * w + x  (clamped to 0 when outside)
+    bool valid;
+};
+template <int G>
+__device__ __forceinline__ GroupGeom group_geom(int wave, int st, int j, int y0, int x0, int h, int w) {
+    using namespace fused;
+    GroupGeom g;
+    const int gi = wave * G + st * 16 + j;
+    const bool in_step = j < G - st * 16 && (NG % G == 0 || gi < NG);
+    const int row = gi / (HC / 4), cg = gi % (HC / 4);
+    const int y = y0 - 1 + row, x = x0 - 4 + 4 * cg;
+    g.valid = in_step && y >= 0 && y < h && x >= 0 && x < w;
+    g.lds_off = in_step ? row * HC + 4 * cg : -1;
+    g.goff = g.valid ? y * w + x : 0;
+    return g;
+}
+
+// A persistent workgroup's tiles: CONSECUTIVE and numbered down the columns of the tile grid (ty fastest), so successive tiles
+// share two of their six halo'd rows, which are then still in L2 (strided tiles, numbered along x, re-fetched every halo row
+// from HBM).  `wg` of `nwg` workgroups owns [begin, end); WG keeps the caller's signedness of the product wg * per.
+struct TileRange { int tiles_y, begin, end; };
+template <typename WG>
+__device__ __forceinline__ TileRange tile_range(int ntiles, int tiles_x, int nwg, WG wg) {
+    const int tiles_y = ntiles / tiles_x;
+    const int per = (ntiles + nwg - 1) / nwg;
+    const int begin = wg * per, end = (begin + per < ntiles) ? begin + per : ntiles;
+    return {tiles_y, begin, end};
+}
+__device__ __forceinline__ int2 tile_origin(int tile, int tiles_y) {      // (x0, y0) of a tile
+    const int tx = tile / tiles_y, ty = tile % tiles_y;
+    return make_int2(tx * fused::TW, ty * fused::TH);
+}
+
+// ---- phase-A helpers in b3 form (rf_common.h): lane (j, kq) holds channels 32 kb + 8 kq + i, i = 0..7 ------------------------
+// Input tile of one step: raw loads (issue early: the next tile is fetched behind the current phase B) ...
+template <int C>
+__device__ __forceinline__ void load_step_b3(const float* __restrict__ xb, int P, int kq, const GroupGeom& g, float4 (&xh)[C / 4]) {
+    const unsigned voff = (unsigned)(8 * kq) * (unsigned)P + (unsigned)g.goff;
+#pragma unroll
+    for (int s = 0; s < C / 4; ++s) xh[s] = *reinterpret_cast<const float4*>(xb + (size_t)(32 * (s >> 3) + (s & 7)) * P + voff);
+}
+
+// ... and the exact two-pass LayerNorm over channels, in place.
+template <int C>
+__device__ __forceinline__ void ln_step_b3(int kq, const float* __restrict__ gam_l, const float* __restrict__ bet_l, float eps, float4 (&xh)[C / 4]) {
+    constexpr int NS = C / 4;
+    float sum[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < NS; ++s) { sum[0] += xh[s].x; sum[1] += xh[s].y; sum[2] += xh[s].z; sum[3] += xh[s].w; }
+    float mu[4], var[4] = {0.f, 0.f, 0.f, 0.f}, rstd[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        sum[q] += __shfl_xor(sum[q], 16);
+        sum[q] += __shfl_xor(sum[q], 32);
+        mu[q] = sum[q] * (1.0f / C);
+    }
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const float d0 = xh[s].x - mu[0], d1 = xh[s].y - mu[1], d2 = xh[s].z - mu[2], d3 = xh[s].w - mu[3];
+        var[0] = fmaf(d0, d0, var[0]); var[1] = fmaf(d1, d1, var[1]);
+        var[2] = fmaf(d2, d2, var[2]); var[3] = fmaf(d3, d3, var[3]);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        var[q] += __shfl_xor(var[q], 16);
+        var[q] += __shfl_xor(var[q], 32);
+        rstd[q] = 1.0f / sqrtf(var[q] * (1.0f / C) + eps);
+    }
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const int ch = 32 * (s >> 3) + 8 * kq + (s & 7);
+        const float gk = gam_l[ch], bk = bet_l[ch];
+        xh[s].x = fmaf((xh[s].x - mu[0]) * rstd[0], gk, bk);
+        xh[s].y = fmaf((xh[s].y - mu[1]) * rstd[1], gk, bk);
+        xh[s].z = fmaf((xh[s].z - mu[2]) * rstd[2], gk, bk);
+        xh[s].w = fmaf((xh[s].w - mu[3]) * rstd[3], gk, bk);
+    }
+}
+
+template <int C>
+__device__ __forceinline__ void split_step(const float4 (&xh)[C / 4], u32x4 (&bp)[C / 32][4][3]) {
+#pragma unroll
+    for (int kb = 0; kb < C / 32; ++kb)
+#pragma unroll
+        for (int hp = 0; hp < 4; ++hp) {
+            const float4 va = xh[8 * kb + 2 * hp], vb = xh[8 * kb + 2 * hp + 1];
+            const float xa[4] = {va.x, va.y, va.z, va.w}, xc[4] = {vb.x, vb.y, vb.z, vb.w};
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                unsigned a0, a1, a2, b0, b1, b2;
+                b3_split(xa[g], a0, a1, a2);
+                b3_split(xc[g], b0, b1, b2);
+                bp[kb][g][0][hp] = b3_pack(a0, b0);
+                bp[kb][g][1][hp] = b3_pack(a1, b1);
+                bp[kb][g][2][hp] = b3_pack(a2, b2);
+            }
+        }
+}
+
+template <int C, int WT>
+__device__ __forceinline__ void phase_a_step_b3(const u32x4 (&bp)[C / 32][4][3], const u32x4* __restrict__ wl,
+                                                int tile0, int tile1, const float* __restrict__ bias0, const float* __restrict__ bias1,
+                                                float* __restrict__ mid, int PS, int kq, const GroupGeom& g) {
+    f32x4 acc[2][4];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[t][q] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kb = 0; kb < C / 32; ++kb) {
+        const u32x4* w0 = wl + (size_t)(kb * WT + tile0) * 192;
+        const u32x4* w1 = wl + (size_t)(kb * WT + tile1) * 192;
+        const u32x4 a0[3] = {w0[0], w0[64], w0[128]}, a1[3] = {w1[0], w1[64], w1[128]};
+        b3_mfma4(a0, bp[kb], acc[0]);
+        b3_mfma4(a1, bp[kb], acc[1]);
+    }
+    if (g.lds_off >= 0) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float bs = (t ? bias1 : bias0)[4 * kq + r];
+                float4 v = make_float4(acc[t][0][r] + bs, acc[t][1][r] + bs, acc[t][2][r] + bs, acc[t][3][r] + bs);
+                if (!g.valid) v = make_float4(0.f, 0.f, 0.f, 0.f);
+                *reinterpret_cast<float4*>(mid + (16 * t + 4 * kq + r) * PS + g.lds_off) = v;
+            }
+    }
+}
+
+// 3x3 depthwise stencil for 4 consecutive pixels from an LDS plane: `p` points at the plane's column of the first pixel,
+// 16-byte aligned, and the three rows (output row - 1 ..) lie at p + ro[dy]: {0, HC, 2 HC} in a contiguous tile, anything in
+// the circular row window of attn_mid_kernel.  The two edge taps of every row must not be scalar LDS reads (lanes 4 floats
+// apart are a 4-way bank conflict on ds_read_b32: measured 58 % of all LDS cycles), so:
+//   Edge::Dpp   lanes j-1 / j+1 of the same 16-lane row hold the neighbouring 4-pixel groups:
+//               edges come over DPP row shifts; only lanes 0 and 15 read their outer tap.
+//   Edge::Wide  neighbouring groups are not in this wave's registers: three aligned
+//               ds_read_b128 per row (conflict-free with the plane stride used there).
+__device__ __forceinline__ float dpp_row_shr1(float keep, float v) {   // lane i <- lane i-1 (i % 16 == 0 keeps `keep`)
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(keep), __float_as_int(v), 0x111, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float dpp_row_shl1(float keep, float v) {   // lane i <- lane i+1 (i % 16 == 15 keeps `keep`)
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(keep), __float_as_int(v), 0x101, 0xf, 0xf, false));
+}
+
+enum class Edge { Dpp, Wide };
+template <Edge E>
+__device__ __forceinline__ void stencil4(const float* __restrict__ p, const int (&ro)[3], int j, const float* __restrict__ k9, float bias, float (&out)[4]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) out[q] = bias;
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy) {
+        const float* row = p + ro[dy];
+        float4 m;
+        float vl, vr;                                    // the taps left and right of m
+        if constexpr (E == Edge::Dpp) {
+            m = *reinterpret_cast<const float4*>(row);
+            float el = 0.f, er = 0.f;
+            if (j == 0) el = row[-1];
+            if (j == 15) er = row[4];
+            vl = dpp_row_shr1(el, m.w);
+            vr = dpp_row_shl1(er, m.x);
+        } else {
+            const float4 lft = *reinterpret_cast<const float4*>(row - 4);
+            m = *reinterpret_cast<const float4*>(row);
+            const float4 rgt = *reinterpret_cast<const float4*>(row + 4);
+            vl = lft.w;
+            vr = rgt.x;
+        }
+        const float v[6] = {vl, m.x, m.y, m.z, m.w, vr};
+        const float k0 = k9[dy * 3], k1 = k9[dy * 3 + 1], k2 = k9[dy * 3 + 2];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) out[q] = fmaf(k2, v[q + 2], fmaf(k1, v[q + 1], fmaf(k0, v[q], out[q])));
+    }
+}
+
+// ================================================================================================
+// FFN:  out = x1 + W2 gelu(dw3x3(W1 LN2(x1) + b1) + bd) + b2          (FfnArgs: rf_common.h)
+// TAIL: the stage's channel_reduce on top,  out = Wa'_b xs + Wb x1 + (Wb W2) g + (Wb b2 + b_cr)  with g = gelu(..): Wb W2 takes
+// the place of W2 in LDS (per image: a workgroup serves one), the composed bias that of b2, and x1 and xs enter as 16 more
+// k-steps of the second GEMM.  Their B operands are the interior 4 x 64 tile in the lane map of the 1x1 kernels (lane (j, kq):
+// one float4 of channel 4 s + kq), loaded where the tail-less kernel loads its residual rows -- behind the last phase A, when
+// the b3 pieces are dead, and ahead of the tile's stores -- together with their A operands, which come from L2 (no LDS left for
+// them); the MFMAs follow the last phase B.  No residual add: x1 arrives through Wb.
+// ================================================================================================
+template <int C, bool TAIL>
+__global__ void __launch_bounds__(256, 2) ffn_fused_kernel(FfnArgs a, FfnTail tl) {
+    using namespace fused;
+    const int ro[3] = {0, HC, 2 * HC};   // a tile's halo'd rows are contiguous in LDS
+    constexpr int NS = C / 4;            // k-sets of the first GEMM
+    constexpr int NT1 = 2 * C / 16;      // output tiles of the first GEMM (hidden)
+    constexpr int NTO = C / 16;          // output tiles of the second GEMM
+    constexpr int NPART = 2 * C / PART;  // parts of 32 hidden channels
+    constexpr int PS = 448;              // LDS plane stride (multiple of 64: kq planes on disjoint slots)
+    // all weights live in LDS for the lifetime of the (persistent) workgroup
+    __shared__ __attribute__((aligned(16))) float mid[PART * PS + 8];
+    __shared__ __attribute__((aligned(16))) u32x4 w1_l[(C / 32) * NT1 * 192];      // b3 form (phase A runs on the bf16 instruction)
+    __shared__ __attribute__((aligned(16))) float w2_l[(2 * C / 4) * NTO * 64];
+    __shared__ float wd_l[2 * C * 9], bd_l[2 * C], b1_l[2 * C], b2_l[C], gam_l[C], bet_l[C];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int j = lane & 15, kq = lane >> 4;
+    const int b = blockIdx.y;
+    const int h = a.h, w = a.w, P = h * w;
+    const float* xb = a.x + (size_t)b * C * P;
+    float* ob = a.out + (size_t)b * C * P;
+
+    for (int i = tid; i < (C / 32) * NT1 * 192; i += 256) w1_l[i] = reinterpret_cast<const u32x4*>(a.w1p)[i];
+    // TAIL: this image's [Wa' | Wb | Wb W2], k-sets [0, C/4) for xs, [C/4, 2C/4) for x1, the rest for g
+    const float* tw = TAIL ? tl.wp + (size_t)b * tl.wp_bstride : nullptr;
+    const float* w2src = TAIL ? tw + (2 * C / 4) * NTO * 64 : a.w2p;
+    for (int i = tid; i < (2 * C / 4) * NTO * 16; i += 256) *reinterpret_cast<float4*>(w2_l + i * 4) = *reinterpret_cast<const float4*>(w2src + i * 4);
+    for (int i = tid; i < 2 * C * 9; i += 256) wd_l[i] = a.wd[i];
+    for (int i = tid; i < 2 * C; i += 256) { bd_l[i] = a.bd[i]; b1_l[i] = a.b1[i]; }
+    for (int i = tid; i < C; i += 256) { gam_l[i] = a.ln_w[i]; bet_l[i] = a.ln_b[i]; b2_l[i] = a.b2[i]; }
+    __syncthreads();
+    STAMP_DECL
+    const float* xsb = TAIL ? tl.xs + (size_t)b * C * P : nullptr;
+
+    const TileRange tr = tile_range(a.ntiles, a.tiles_x, (int)gridDim.x, blockIdx.x);
+    for (int tile = tr.begin; tile < tr.end; ++tile) {
+        const int tx = tile / tr.tiles_y, ty = tile % tr.tiles_y;      // tile_origin, spelled out: through the helper this kernel's
+        const int x0 = tx * TW, y0 = ty * TH;                          // prologue is scheduled differently (tools/isa_same.py)
+        STAMP(0);
+        // input tile, loaded here (see attn_front_kernel: the b3 pieces take the registers a tile in flight would need):
+        // LayerNorm in registers, then the three-piece split that both parts of phase A reuse
+        const GroupGeom gw0 = group_geom<GPW>(wave, 0, j, y0, x0, h, w), gw1 = group_geom<GPW>(wave, 1, j, y0, x0, h, w);
+        u32x4 bp0[C / 32][4][3], bp1[C / 32][4][3];
+        {
+            float4 xh0[NS], xh1[NS];
+            load_step_b3<C>(xb, P, kq, gw0, xh0);
+            load_step_b3<C>(xb, P, kq, gw1, xh1);
+            ln_step_b3<C>(kq, gam_l, bet_l, 1e-5f, xh0);
+            ln_step_b3<C>(kq, gam_l, bet_l, 1e-5f, xh1);
+            split_step<C>(xh0, bp0);
+            split_step<C>(xh1, bp1);
+        }
+        STAMP(1);
+
+        const int yo = y0 + wave, xo = x0 + 4 * j;          // this lane's 4 output pixels
+        const bool live = yo < h && xo < w;
+        const unsigned voff = (unsigned)(4 * kq) * (unsigned)P + (unsigned)(live ? yo * w + xo : 0);
+        float4 resv[NTO * 4];
+        float4 tb[TAIL ? 2 * C / 4 : 1];                   // TAIL: B operands, k-steps of xs then of x1 ...
+        float ta[TAIL ? 2 * C / 4 : 1][NTO];               // ... and their A operands
+        f32x4 acc[NTO][4];
+#pragma unroll
+        for (int t = 0; t < NTO; ++t)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[t][q] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+#pragma unroll
+        for (int part = 0; part < NPART; ++part) {
+            lds_barrier();                                 // previous phase B is done with mid
+            STAMP(0);
+            // ---- phase A: hidden[32 of part][halo tile] = W1 x^ + b1 -> LDS
+            phase_a_step_b3<C, NT1>(bp0, w1_l + lane, 2 * part, 2 * part + 1, b1_l + part * PART, b1_l + part * PART + 16, mid, PS, kq, gw0);
+            phase_a_step_b3<C, NT1>(bp1, w1_l + lane, 2 * part, 2 * part + 1, b1_l + part * PART, b1_l + part * PART + 16, mid, PS, kq, gw1);
+            STAMP(2);
+            if (part == NPART - 1) {
+                if constexpr (TAIL) {
+                    // this tile's xs and x1 rows and their weights, behind the last phase B (issued before this tile's stores)
+                    const unsigned voffb = (unsigned)kq * (unsigned)P + (unsigned)(live ? yo * w + xo : 0);
+#pragma unroll
+                    for (int s = 0; s < C / 4; ++s) {
+                        tb[s] = *reinterpret_cast<const float4*>(xsb + (size_t)(4 * s) * P + voffb);
+                        tb[C / 4 + s] = *reinterpret_cast<const float4*>(xb + (size_t)(4 * s) * P + voffb);
+                    }
+                } else {
+                // this tile's residual rows, behind the last phase B (issued before this tile's stores)
+#pragma unroll
+                for (int t = 0; t < NTO; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) resv[t * 4 + r] = *reinterpret_cast<const float4*>(xb + (size_t)(16 * t + r) * P + voff);
+                }
+            }
+            lds_barrier();
+            STAMP(0);
+            // ---- phase B: depthwise 3x3 + GELU in registers, straight into the second GEMM
+#pragma unroll
+            for (int s = 0; s < PART / 4; ++s) {
+                const int hc = 4 * s + kq;
+                float v[4];
+                stencil4<Edge::Dpp>(mid + hc * PS + wave * HC + 4 * j + 4, ro, j, wd_l + (part * PART + hc) * 9, bd_l[part * PART + hc], v);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[q] = gelu_fast(v[q]);
+#pragma unroll
+                for (int t = 0; t < NTO; ++t) {
+                    const float av = w2_l[((part * (PART / 4) + s) * NTO + t) * 64 + lane];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) acc[t][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, v[q], acc[t][q], 0, 0, 0);
+                }
+            }
+            STAMP(3);
+        }
+        if constexpr (TAIL) {
+            // uniform base + 32-bit lane offset, the lane made opaque per tile: per-lane 64-bit pointers to the 8 KB of weights would
+            // be hoisted out of the tile loop and spilled
+            unsigned lo = (unsigned)lane;
+            asm volatile("" : "+v"(lo));
+#pragma unroll
+            for (int s = 0; s < 2 * C / 4; ++s)
+#pragma unroll
+                for (int t = 0; t < NTO; ++t) ta[s][t] = (tw + (s * NTO + t) * 64)[lo];
+            // ---- the stage tail's k-steps: [Wa' | Wb] [xs ; x1] (a dead lane's columns hold whatever offset 0 gave: never stored)
+#pragma unroll
+            for (int s = 0; s < 2 * C / 4; ++s) {
+                const float v[4] = {tb[s].x, tb[s].y, tb[s].z, tb[s].w};
+#pragma unroll
+                for (int t = 0; t < NTO; ++t)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) acc[t][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(ta[s][t], v[q], acc[t][q], 0, 0, 0);
+            }
+            // ---- epilogue: + composed bias
+            if (live) {
+#pragma unroll
+                for (int t = 0; t < NTO; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int cu = 16 * t + r;
+                        const float bs = b2_l[cu + 4 * kq];
+                        *reinterpret_cast<float4*>(ob + (size_t)cu * P + voff) =
+                            make_float4(acc[t][0][r] + bs, acc[t][1][r] + bs, acc[t][2][r] + bs, acc[t][3][r] + bs);
+                    }
+            }
+        } else {
+        // ---- epilogue: + b2 + residual
+        if (live) {
+#pragma unroll
+            for (int t = 0; t < NTO; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int cu = 16 * t + r;
+                    const float bs = b2_l[cu + 4 * kq];
+                    const float4 rv = resv[t * 4 + r];
+                    *reinterpret_cast<float4*>(ob + (size_t)cu * P + voff) =
+                        make_float4(acc[t][0][r] + bs + rv.x, acc[t][1][r] + bs + rv.y, acc[t][2][r] + bs + rv.z, acc[t][3][r] + bs + rv.w);
+                }
+        }
+        }
+        STAMP(4);
+    }
+    STAMP_FLUSH;
+}
+
+}  // namespace rf

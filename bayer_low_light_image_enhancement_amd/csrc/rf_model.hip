@@ -182,10 +182,12 @@ int make_plan(const rf_handle* h, int B, int H, int W, Plan& p) {
             attn_mid_plan(H >> l, W >> l, &ns, &pf2, B, C);
             if (pf2 > gp) gp = pf2;
         }
-        const size_t a = (size_t)B * packed1x1_floats(C, C), cr = (size_t)B * packed1x1_floats(2 * C, C);
+        const int hcl = C * c.ffn_expansion;
+        // the channel_reduce fold; at a level whose FFN kernel carries the stage tail, [Wa' | Wb | Wb W2] in the same slot
+        const bool tailf = !tc && fused_ffn_tail_supported(C) && tail_composable(C, hcl);
+        const size_t a = (size_t)B * packed1x1_floats(C, C), cr = (size_t)B * packed1x1_floats(tailf ? 2 * C + hcl : 2 * C, C);
         if (a > wa) wa = a;
         if (cr > wc) wc = cr;
-        const int hcl = C * c.ffn_expansion;
         const size_t a3 = (size_t)B * packed1x1_b3_floats(C, C),
                      cr3 = (size_t)B * packed1x1_b3_floats(tail_composable(C, hcl) ? 2 * C + hcl : 2 * C, C);
         if (a3 > wa3) wa3 = a3;
@@ -246,12 +248,21 @@ int run_stage(rf_handle* h, int i, const float* in, float* out, float* ws, const
     // Composed tail: where the FFN runs op by op, its last GEMM (x1 + W2 g + b2 -> trans, K = hidden) and channel_reduce
     // ([Wa' | Wb] [xs ; trans], K = 2C) become ONE GEMM over [xs ; x1 ; g] with [Wa' | Wb | Wb W2] (same MFMA count; `trans` --
     // C floats per pixel written and read back -- never exists).  The bias and Wb W2 are composed at parameter load.
-    bool compose = x.tail_offset != 0 && Pn % 4 == 0 && !transformer_ffn_is_fused(tp, C, hc, hh, ww);
+    const bool ffn_fused = transformer_ffn_is_fused(tp, C, hc, hh, ww);
+    bool compose = x.tail_offset != 0 && Pn % 4 == 0 && !ffn_fused;
+    // Fused tail: where the FFN is ffn_fused_kernel<32> (level 0), the same composition runs INSIDE it -- xs and x1 are 16 more
+    // k-steps of its second GEMM, Wb W2 replaces W2 -- so neither `trans` nor the channel_reduce launch exists.  The kernel reads
+    // the weights in f32 operand order from the fold slot of the workspace (per image: the FLCA gate; one set for the plain
+    // variant, folded per call: the packed buffer has no room for it).  Not TrueColor, whose branch runs after the block.
+    bool fuse_tail = x.tail_offset != 0 && ffn_fused && fused_ffn_tail_supported(C) && cfg.variant != RF_VARIANT_TRUECOLOR;
 #ifdef RF_DIAG   // diagnostic build only: the two-GEMM form
     if (getenv("RF_NO_COMPOSE") || getenv("RF_NO_B3")) compose = false;
+    if (getenv("RF_NO_COMPOSE")) fuse_tail = false;
 #endif
     tp.defer_pw2 = compose;
-    const float* composed = compose ? h->packed + x.tail_offset : nullptr;
+    const float* composed = compose || fuse_tail ? h->packed + x.tail_offset : nullptr;
+    float* const fold_wp = compose ? nullptr : ws + p.wfold_cr;          // the fold writes the form(s) the tail reads
+    float* const fold_wp3 = fuse_tail ? nullptr : ws + p.wfold_cr3;
     // the branch is launched first (on the branch stream when there is one), the block beside it; TrueColor's branch borrows
     // bufA and therefore follows the block on the same stream
     if (cfg.variant == RF_VARIANT_TRUECOLOR) RF_TRY(run_transformer(tp, in, trans, ws, to, B, C, heads, hc, hh, ww, st));
@@ -278,7 +289,7 @@ int run_stage(rf_handle* h, int i, const float* in, float* out, float* ws, const
         r2.out = ws + p.bufA; r2.act = 0;
         RF_TRY(launch_conv1x1(r2, st));
         RF_TRY(launch_tc_residual(xs, ws + p.bufA, xs, ws + p.flca_partial, B, C, hh, ww, st));
-        RF_TRY(launch_flca_se_fold(ws + p.flca_partial, tc_nblk(hh, ww), Pn, h->se_prm(t.se), h->prm(x.cr_w), ws + p.wfold_cr, ws + p.wfold_cr3,
+        RF_TRY(launch_flca_se_fold(ws + p.flca_partial, tc_nblk(hh, ww), Pn, h->se_prm(t.se), h->prm(x.cr_w), fold_wp, fold_wp3,
                                    ws + p.ch, B, C, st, composed, hc));
         r.wp = ws + p.wfold_cr; r.wp_bstride = (int64_t)packed1x1_floats(2 * C, C);
         r.wp3 = ws + p.wfold_cr3; r.wp3_bstride = (int64_t)packed1x1_b3_floats(compose ? 2 * C + hc : 2 * C, C);
@@ -291,8 +302,8 @@ int run_stage(rf_handle* h, int i, const float* in, float* out, float* ws, const
         s.ylo = ylo; s.yhi = yhi; s.xlo = xlo; s.xhi = xhi;
         RF_TRY(launch_flca_spatial(s, side));
         if (sharded) h->shard_allreduce(h->shard_user, s.partial, (size_t)B * s.nblk * C, 0, (void*)side);
-        RF_TRY(launch_flca_se_fold(s.partial, s.nblk, P_pool, fp.se, h->prm(x.cr_w), ws + p.wfold_cr, ws + p.wfold_cr3, ws + p.ch, B, C, side,
-                                   composed, hc));
+        RF_TRY(launch_flca_se_fold(s.partial, s.nblk, P_pool, fp.se, h->prm(x.cr_w), fold_wp, fold_wp3, ws + p.ch, B, C, side, composed, hc));
+        tp.tail.wp_bstride = (int64_t)packed1x1_floats(2 * C + hc, C);
         r.wp = ws + p.wfold_cr; r.wp_bstride = (int64_t)packed1x1_floats(2 * C, C);
         r.wp3 = ws + p.wfold_cr3; r.wp3_bstride = (int64_t)packed1x1_b3_floats(compose ? 2 * C + hc : 2 * C, C);
     } else {
@@ -301,10 +312,17 @@ int run_stage(rf_handle* h, int i, const float* in, float* out, float* ws, const
         cb.out = xs; cb.out_bstride = (int64_t)C * Pn; cb.B = B; cb.Cin = C; cb.Cout = C; cb.h = hh; cb.w = ww;
         cb.act = cfg.branch_lrelu ? 1 : 0;
         RF_TRY(launch_conv3x3(cb, side));
+        if (fuse_tail) RF_TRY(launch_tail_fold(h->prm(x.cr_w), nullptr, composed, nullptr, 1, C, hc, side, fold_wp));
         r.wp = h->pk(x.cr_w);
         r.wp3 = compose ? h->packed + x.tail3_offset : h->pk3(x.cr_w);
     }
-    if (cfg.variant != RF_VARIANT_TRUECOLOR) {
+    if (fuse_tail) {
+        // the FFN kernel reads the branch's output and weights: the join sits between the block's two halves
+        tp.tail.xs = xs; tp.tail.wp = fold_wp; tp.tail_bias = composed + (size_t)C * hc;
+        RF_TRY(run_transformer_attn(tp, in, ws, to, B, C, heads, hh, ww, st));
+        RF_TRY(h->side.join(st, side));
+        RF_TRY(run_transformer_ffn(tp, crb, ws, to, B, C, hc, hh, ww, st));
+    } else if (cfg.variant != RF_VARIANT_TRUECOLOR) {
         RF_TRY(run_transformer(tp, in, trans, ws, to, B, C, heads, hc, hh, ww, st));
         RF_TRY(h->side.join(st, side));
     }
@@ -314,7 +332,7 @@ int run_stage(rf_handle* h, int i, const float* in, float* out, float* ws, const
         r.x3 = ws + p.bufB; r.C3 = hc; r.x3_bstride = (int64_t)hc * Pn;
         r.bias = composed + (size_t)C * hc;
     }
-    RF_TRY(launch_conv1x1(r, st));
+    if (!fuse_tail) RF_TRY(launch_conv1x1(r, st));
 
     Conv3x3Args co{};
     co.x = crb; co.x_bstride = (int64_t)C * Pn; co.wp = h->pk(x.out_w); co.bias = h->prm(x.out_b);
