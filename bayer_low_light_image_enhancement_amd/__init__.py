@@ -8,6 +8,6 @@ raises if it has not been built (``python -m bayer_low_light_image_enhancement_a
 """
 from .model import RawFormer, canonical_key  # noqa: F401
 from . import ops, synth  # noqa: F401
-from .data import PatchSampler, ResidentSID, amp_from_names  # noqa: F401
+from .data import PatchSampler, ResidentMCR, ResidentSID, amp_from_names, mcr_amp_from_names  # noqa: F401
 
-__all__ = ["RawFormer", "canonical_key", "ops", "synth", "ResidentSID", "PatchSampler", "amp_from_names"]
+__all__ = ["RawFormer", "canonical_key", "ops", "synth", "ResidentSID", "ResidentMCR", "PatchSampler", "amp_from_names", "mcr_amp_from_names"]

@@ -87,6 +87,7 @@ SIGNATURES = {
     "rf_sid_pack": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.c_double, _i, _vp]),
     "rf_sid_check_desc": (_i, [C.POINTER(C.c_int), _i, _i, _i, _i, _i, _i]),
     "rf_sid_sample": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "rf_mcr_sample": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "rf_token_attn": (_i, [_vp, _vp, _vp, _vp, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _f, _vp]),
     "rf_bayer_luma_scratch_bytes": (_i, [_i, _i, _i, _psz]),
     "rf_bayer_luma": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),

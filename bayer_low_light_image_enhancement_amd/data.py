@@ -1,4 +1,4 @@
-"""Training batches from a device-resident SID set (RawFomer_WFB_FFAB/load_dataset.py:9-95).
+"""Training batches from a device-resident SID or MCR set (RawFomer_WFB_FFAB/load_dataset.py:9-179).
 
 The reference keeps the decoded Sony split in host memory as uint16 arrays (``image_read_SID``, :9-31) and cuts, flips and
 normalises one patch per item in its loader workers (``load_data_SID.__getitem__``, :53-95).  Here the same arrays live in
@@ -6,11 +6,15 @@ device memory (``ResidentSID``; the training split is about 16 GB), the host dra
 (``PatchSampler``, the reference's draw order on a private ``random.Random``) and one kernel (``rf_sid_sample``,
 ``csrc/rf_sampler.hip``) assembles the whole batch, bit for bit what ``__getitem__`` returns.
 
+The Mono-Colored-RAW set (``image_read_MCR`` / ``load_data_MCR``, :97-179) goes the same way: ``ResidentMCR`` holds the uint8
+colour-raw frames and RGB targets as ``imageio`` returns them and the float64 exposure ratio of every frame
+(``mcr_amp_from_names``, the reference's file-name slices), ``rf_mcr_sample`` restates ``(inp / 255 * amp).astype(float32)`` in
+float64 with one rounding, and the same ``PatchSampler`` serves both sets: the two ``__getitem__`` bodies draw identically.
+
 As in the reference the flips are flips of the MOSAIC: a left-right flip of an even-aligned crop moves the CFA phase by one
 column, an up-down flip by one row.  That is the reference's augmentation and is reproduced, not corrected.
 
-Decoding the ARW files (rawpy) stays with the caller.  The MCR loader (``load_data_MCR``, :117-178, uint8 sources and a
-per-file exposure ratio) is out of scope.
+Decoding the files (rawpy for SID's ARW, imageio for MCR's tif / jpg) stays with the caller.
 """
 from __future__ import annotations
 
@@ -30,16 +34,39 @@ def amp_from_names(paths: Iterable[str]) -> List[float]:
     return [300.0 if p[-7] == "3" else 100.0 for p in paths]
 
 
-def _device_tensor(a, dtype, what: str, device) -> torch.Tensor:
+def mcr_amp_from_names(paths: Iterable[str]) -> List[float]:
+    """The exposure ratio of every MCR item from its colour-raw file name (``load_data_MCR.__getitem__``, :141-149), e.g.
+    ``.../C00012_48mp_0x8_0x00ff.tif``: ``img_num = int(p[-23:-20])``, ``img_expo = int(p[-8:-4], 16)``, ``gt_expo`` 12287 below
+    image number 500 and 1023 from there on, ``amp = gt_expo / img_expo`` as a Python float (float64)."""
+    out = []
+    for p in paths:
+        try:
+            if len(p) < 23:
+                raise ValueError("shorter than the 23 characters the slices reach back")
+            img_num = int(p[-23:-20])
+            img_expo = int(p[-8:-4], 16)
+        except ValueError as e:
+            raise ValueError(f"mcr_amp_from_names: cannot parse {p!r}: {e}") from None
+        if img_expo == 0:
+            raise ValueError(f"mcr_amp_from_names: {p!r}: exposure 0")
+        out.append((12287 if img_num < 500 else 1023) / img_expo)
+    return out
+
+
+_EXACT = {torch.uint16: np.uint16, torch.uint8: np.uint8}          # the frames: no silent conversion
+
+
+def _device_tensor(a, dtype, what: str, device, who: str = "ResidentSID") -> torch.Tensor:
+    name = str(dtype).split(".")[1]
     if isinstance(a, np.ndarray):
-        if dtype == torch.uint16 and a.dtype != np.uint16:
-            raise TypeError(f"ResidentSID: {what} must be uint16, got {a.dtype}")
+        if dtype in _EXACT and a.dtype != _EXACT[dtype]:
+            raise TypeError(f"{who}: {what} must be {name}, got {a.dtype}")
         a = torch.from_numpy(np.ascontiguousarray(a))
     elif not isinstance(a, torch.Tensor):
-        a = torch.as_tensor(a)
-    if dtype == torch.uint16:
-        if a.dtype != torch.uint16:
-            raise TypeError(f"ResidentSID: {what} must be uint16, got {a.dtype}")
+        a = torch.as_tensor(a, dtype=None if dtype in _EXACT else dtype)
+    if dtype in _EXACT:
+        if a.dtype != dtype:
+            raise TypeError(f"{who}: {what} must be {name}, got {a.dtype}")
     else:
         a = a.to(dtype)
     return a.to(device).contiguous()
@@ -79,15 +106,58 @@ class ResidentSID:
     def __len__(self) -> int:
         return self.n
 
+    def _sample(self, lib, table: torch.Tensor, x: torch.Tensor, gt: torch.Tensor, b: int, ph: int, pw: int, stream) -> None:
+        _lib.check(lib.rf_sid_sample(C.c_void_p(self.raw.data_ptr()), C.c_void_p(self.gt.data_ptr()), C.c_void_p(self.amp.data_ptr()),
+                                     C.c_void_p(table.data_ptr()), C.c_void_p(x.data_ptr()), C.c_void_p(gt.data_ptr()),
+                                     self.n, self.h, self.w, b, ph, pw, self.black, self.white, stream), "rf_sid_sample")
+
+
+class ResidentMCR:
+    """The decoded Mono-Colored-RAW set in device memory: ``raw`` uint8 ``[N,H,W]`` (the colour-raw tif), ``gt`` uint8 ``[N,H,W,3]``
+    (the RGB target, HWC as imageio returns it) and ``amp`` float64 ``[N]`` (``mcr_amp_from_names``).  numpy arrays and tensors
+    are accepted; host data is copied to ``device`` (default: the current ROCm device), device tensors are used in place."""
+
+    def __init__(self, raw_u8, gt_u8, amp, device=None):
+        if device is None:
+            device = raw_u8.device if isinstance(raw_u8, torch.Tensor) and raw_u8.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("ResidentMCR keeps the set on a ROCm device: there is no CPU path in this package")
+        self.raw = _device_tensor(raw_u8, torch.uint8, "raw", device, "ResidentMCR")
+        self.gt = _device_tensor(gt_u8, torch.uint8, "gt", device, "ResidentMCR")
+        self.amp = _device_tensor(amp, torch.float64, "amp", device, "ResidentMCR")
+        if self.raw.dim() != 3:
+            raise ValueError(f"ResidentMCR: raw must be [N,H,W], got {tuple(self.raw.shape)}")
+        n, h, w = self.raw.shape
+        if tuple(self.gt.shape) != (n, h, w, 3):
+            raise ValueError(f"ResidentMCR: gt must be {(n, h, w, 3)} (HWC), got {tuple(self.gt.shape)}")
+        if tuple(self.amp.shape) != (n,):
+            raise ValueError(f"ResidentMCR: amp must be {(n,)}, got {tuple(self.amp.shape)}")
+        if w % 2:
+            raise ValueError(f"ResidentMCR: frame width {w} must be even")
+        self.n, self.h, self.w = n, h, w
+        self.device = device
+
+    amp_from_names = staticmethod(mcr_amp_from_names)
+
+    def __len__(self) -> int:
+        return self.n
+
+    def _sample(self, lib, table: torch.Tensor, x: torch.Tensor, gt: torch.Tensor, b: int, ph: int, pw: int, stream) -> None:
+        _lib.check(lib.rf_mcr_sample(C.c_void_p(self.raw.data_ptr()), C.c_void_p(self.gt.data_ptr()), C.c_void_p(self.amp.data_ptr()),
+                                     C.c_void_p(table.data_ptr()), C.c_void_p(x.data_ptr()), C.c_void_p(gt.data_ptr()),
+                                     self.n, self.h, self.w, b, ph, pw, stream), "rf_mcr_sample")
+
 
 class PatchSampler:
-    """``load_data_SID.__getitem__`` for a list of indices at once.  The descriptors (frame, i, j, flips) are drawn on the host
+    """``load_data_SID.__getitem__`` / ``load_data_MCR.__getitem__`` (``dataset``: a ``ResidentSID`` or a ``ResidentMCR``) for a list of
+    indices at once.  The descriptors (frame, i, j, flips) are drawn on the host
     from a private ``random.Random(seed)`` in the reference's order per item -- ``randint(0, (H - P - 2) // 2) * 2`` for i, the same
     for j, ``randint(0, 100) > 50`` (left-right), ``randint(0, 100) < 20`` (up-down) -- so the same seed and index list give the
     patches the reference's dataset gives after ``random.seed(seed)``.  ``patch_size``: P (the reference's square patches) or
     ``(ph, pw)``."""
 
-    def __init__(self, dataset: ResidentSID, patch_size=512, seed=None):
+    def __init__(self, dataset, patch_size=512, seed=None):
         ph, pw = (int(v) for v in patch_size) if isinstance(patch_size, (tuple, list)) else (int(patch_size), int(patch_size))
         if ph <= 0 or pw <= 0 or pw % 4:
             raise ValueError(f"PatchSampler: patch size {patch_size}: the width must be a positive multiple of 4")
@@ -119,9 +189,7 @@ class PatchSampler:
             x = torch.empty((b, 1, ph, pw), dtype=torch.float32, device=d.device)
             gt = torch.empty((b, 3, ph, pw), dtype=torch.float32, device=d.device)
             stream = C.c_void_p(torch.cuda.current_stream(d.device).cuda_stream)
-            _lib.check(lib.rf_sid_sample(C.c_void_p(d.raw.data_ptr()), C.c_void_p(d.gt.data_ptr()), C.c_void_p(d.amp.data_ptr()),
-                                         C.c_void_p(dev_table.data_ptr()), C.c_void_p(x.data_ptr()), C.c_void_p(gt.data_ptr()),
-                                         d.n, d.h, d.w, b, ph, pw, d.black, d.white, stream), "rf_sid_sample")
+            d._sample(lib, dev_table, x, gt, b, ph, pw, stream)
         return x, gt
 
     def batch(self, indices: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -283,6 +283,16 @@ int rf_sid_check_desc(const int* desc_host, int N, int H, int W, int B, int ph, 
 int rf_sid_sample(const unsigned short* raw, const unsigned short* gt, const float* amp, const int* desc, float* x_out, float* gt_out,
                   int N, int H, int W, int B, int ph, int pw, int black, int white, void* stream);
 
+/* ---- MCR training batches from a device-resident set: load_data_MCR.__getitem__, RawFomer_WFB_FFAB/load_dataset.py:136-179 ----
+ * raw [N,H,W] uint8 colour-raw frames, gt [N,H,W,3] uint8 RGB (HWC, as imageio returns it), amp [N] DOUBLE = gt_expo / img_expo
+ * (:141-149).  Patches, flips, outputs and the descriptor table are those of rf_sid_sample (same rules, same rf_sid_check_desc);
+ *   x  = (float)(((double)v / 255.0) * amp)     float64 quotient and product, rounded once (:151)
+ *   gt = (float)((double)v / 255.0)             (:152)
+ * raw and gt need 2-byte alignment only (the kernel reads aligned halfwords, and no byte outside the patches); amp 8, desc 4,
+ * the outputs 16.  pw % 4 == 0, W even, i and j even. */
+int rf_mcr_sample(const unsigned char* raw, const unsigned char* gt, const double* amp, const int* desc, float* x_out, float* gt_out,
+                  int N, int H, int W, int B, int ph, int pw, void* stream);
+
 /* ---- luminance-aware token attention: Attenblock.py:161-220 -----------------
  * softmax(q_i . k_j * scale) v_j per (image, head), flash style (the N x N scores are never stored).
  * q, k, v: [B, heads*d, N] with `bstride_qkv` floats between images (so they may be the three thirds of one

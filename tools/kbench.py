@@ -5,7 +5,7 @@ Each case runs through the C ABI (ops.*) with the library's own HIP-event bracke
 (rf_profile_begin/end), so the figure is the kernel's time on its launch stream, without the
 weight-repack helper that the operator-level entry points run first.
 
-usage: python tools/kbench.py [conv1x1] [conv3x3] [dw] [attn] [flca] [dwt] [ssim] [sampler] [--dim 32] [--batch 8] [--size 512]
+usage: python tools/kbench.py [conv1x1] [conv3x3] [dw] [attn] [flca] [dwt] [ssim] [sampler] [mcr_sampler] [--dim 32] [--batch 8] [--size 512]
 """
 from __future__ import annotations
 
@@ -101,6 +101,13 @@ def main():
         u16 = lambda *s: torch.randint(-32768, 32768, s, dtype=torch.int16, device=dev).view(torch.uint16)  # noqa: E731
         smp = PatchSampler(ResidentSID(u16(nf, hh, ww), u16(nf, hh, ww, 3), [100.0, 300.0] * (nf // 2)), patch_size=512, seed=0)
         report(f"sid_sample 16x512x512 of {nf}x{hh}x{ww}", timed(lambda: smp.batch(list(range(16)))))
+        del smp
+    if "mcr_sampler" in a.what:   # the same from 16 resident MCR frames (1024 x 1280 uint8; GB/s = the 20 B / pixel of algorithmic traffic)
+        from bayer_low_light_image_enhancement_amd.data import PatchSampler, ResidentMCR
+        nf, hh, ww = 16, 1024, 1280
+        u8 = lambda *s: torch.randint(0, 256, s, dtype=torch.uint8, device=dev)  # noqa: E731
+        smp = PatchSampler(ResidentMCR(u8(nf, hh, ww), u8(nf, hh, ww, 3), [12287 / 255, 1023 / 255] * (nf // 2)), patch_size=512, seed=0)
+        report(f"mcr_sample 16x512x512 of {nf}x{hh}x{ww}", timed(lambda: smp.batch(list(range(16)))))
         del smp
     if "dwt" in a.what:
         x = r(B, d, S, S)
