@@ -66,6 +66,8 @@ SIGNATURES = {
     "rf_layernorm2d": (_i, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp]),
     "rf_conv1x1_scratch_bytes": (_i, [_i, _i, _psz]),
     "rf_conv1x1": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "rf_conv1x1_group_grid": (_i, [_i, _i, C.POINTER(_i)]),
+    "rf_conv1x1_group_map": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "rf_dwconv3x3": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "rf_conv3x3_scratch_bytes": (_i, [_i, _i, _psz]),
     "rf_conv3x3": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),

@@ -159,6 +159,22 @@ int rf_conv1x1_scratch_bytes(int Cin_total, int Cout, size_t* bytes) {
     return RF_OK;
 }
 
+int rf_conv1x1_group_grid(int units, int ngroups, int* ids) {
+    RF_CHECK_ARG(ids && units > 0 && ngroups > 0 && (long)units * ngroups < (1L << 30), "conv1x1_group_grid: bad arguments");
+    *ids = (int)conv1x1_group_grid((unsigned)units, (unsigned)ngroups);
+    return RF_OK;
+}
+
+int rf_conv1x1_group_map(int units, int ngroups, int id, int* unit, int* group) {
+    RF_CHECK_ARG(unit && group && units > 0 && ngroups > 0 && (long)units * ngroups < (1L << 30) && id >= 0 &&
+                 (unsigned)id < conv1x1_group_grid((unsigned)units, (unsigned)ngroups), "conv1x1_group_map: bad arguments");
+    unsigned u, g;
+    const bool ok = conv1x1_group_map((unsigned)id, (unsigned)units, (unsigned)ngroups, &u, &g);
+    *unit = ok ? (int)u : -1;
+    *group = ok ? (int)g : -1;
+    return RF_OK;
+}
+
 int rf_conv1x1(const float* in, const float* in2, float* out, const float* weight, const float* bias,
                const float* ln_w, const float* ln_b, const float* res, void* scratch,
                int B, int C1, int C2, int Cout, int h, int w, void* stream) {

@@ -207,6 +207,20 @@ struct Conv1x1Args {
     int act;               // 0 none, 1 LeakyReLU(0.2), 2 ReLU, 3 LeakyReLU(0.1), 4 clamp to [0, 1e4] (FEB, blocks.py:14-30)
 };
 int launch_conv1x1(const Conv1x1Args& a, hipStream_t st);
+// Workgroup id -> (unit, grp) for `ngroups` workgroups per unit that read the same input (conv1x1_b3_kernel's paired form: a unit
+// is one pixel tile of one image, a group one pair of output groups).  The hardware deals consecutive ids round-robin over the 8
+// XCDs (one L2 each), so the groups of a unit get ids 8 apart: the same XCD, one after the other in its dispatch order, and the
+// L2 serves the re-reads.  Ids come in chunks of 8 units x ngroups; ids [0, units * ngroups) alone cannot do this when
+// units % 8 != 0 (one unit with two groups would own ids 0 and 1), so the grid is conv1x1_group_grid(units, ngroups) ids, the
+// last chunk padded to 8 units, and the ids of the missing units return false (at most 7 * ngroups of them).  The ids that
+// return true map one to one onto the (unit, grp) pairs.
+__host__ __device__ inline bool conv1x1_group_map(unsigned id, unsigned units, unsigned ngroups, unsigned* unit, unsigned* grp) {
+    const unsigned chunk = id / (8u * ngroups), r = id - chunk * 8u * ngroups;
+    *unit = 8u * chunk + (r & 7u);
+    *grp = r >> 3;
+    return *unit < units;
+}
+inline unsigned conv1x1_group_grid(unsigned units, unsigned ngroups) { return (units + 7u) / 8u * 8u * ngroups; }
 bool conv1x1_ln_single_pass(const Conv1x1Args& a);   // false: cheaper as layernorm2d + the plain GEMM (the prologue would re-read x per output group)
 
 // ---- conv3x3 (rf_conv3x3.hip)

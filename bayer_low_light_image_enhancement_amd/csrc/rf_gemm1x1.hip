@@ -465,29 +465,47 @@ __device__ __forceinline__ void b3_load_x_block(float4 (&xr)[8], const float* xb
     }
 }
 
-template <int NCO, bool LN>
-__global__ void __launch_bounds__(256, 2) conv1x1_b3_kernel(Conv1x1Args a, int ngroups) {
-    __shared__ __attribute__((aligned(16))) u32x4 lds_w[2][NCO * 3 * 64];
-    __shared__ float bias_l[NCO * 16];
+// PAIR (launch_conv1x1: no LayerNorm, more than one output group, a launch that still gives every CU a workgroup): the output
+// groups of a pixel tile share the x they fetch.  A workgroup is 512 threads = two halves of four waves; half h runs output group
+// 2 gp + h of the SAME 256 pixels with its own bias and double-buffered weight slice, so wave w and wave w + 4 issue the same x
+// loads at the same time and the second one is served on the CU.  The pairs gp of a pixel tile get workgroup ids 8 apart
+// (conv1x1_group_map, rf_common.h): they run back to back on one XCD and its L2 serves what the first pair fetched.  The grid
+// is flat (images x pixel tiles x pairs, padded to whole chunks; the padding exits at once).  An odd group count leaves the last
+// pair's second half without output tiles: it loads x, multiplies zero weights and stores nothing (at 3 groups a third more
+// matrix work per pixel tile than the unpaired form; no layer of RawFormer-S / B / L has an odd count).  Per output the k order, the
+// six-term chains and the epilogue are those of the unpaired form: same bits.
+template <int NCO, bool LN, bool PAIR = false>
+__global__ void __launch_bounds__(PAIR ? 512 : 256, 2) conv1x1_b3_kernel(Conv1x1Args a, int ngroups) {
+    static_assert(!(PAIR && LN), "the paired form has no LayerNorm prologue");
+    constexpr int NH = PAIR ? 2 : 1;
+    __shared__ __attribute__((aligned(16))) u32x4 lds_w[NH * 2][NCO * 3 * 64];   // [half][buffer]
+    __shared__ float bias_l[NH * NCO * 16];
     __shared__ float gam_l[LN ? kStreamLnMaxK : 4], bet_l[LN ? kStreamLnMaxK : 4];
     constexpr int WPT = (NCO * 3 * 64 + 255) / 256;   // 16-byte weight elements each thread moves per block
-    const int tid = threadIdx.x;
+    const int tid = PAIR ? threadIdx.x & 255 : threadIdx.x;       // inside the half
+    const int half = PAIR ? threadIdx.x >> 8 : 0;
     const int lane = tid & 63, wave = tid >> 6;
     const int j = lane & 15, kq = lane >> 4;
-    const int grp = blockIdx.x % ngroups;
-    const int tile = blockIdx.x / ngroups;
-    const int b = blockIdx.y;
+    unsigned unit = 0, gp = 0, utiles = 1;
+    if constexpr (PAIR) {
+        utiles = (unsigned)(a.P + 255) >> 8;
+        if (!conv1x1_group_map(blockIdx.x, (unsigned)a.B * utiles, (unsigned)(ngroups + 1) >> 1, &unit, &gp)) return;   // (whole workgroup)
+    }
+    const int grp = PAIR ? 2 * (int)gp + half : blockIdx.x % ngroups;
+    const int tile = PAIR ? unit % utiles : blockIdx.x / ngroups;
+    const int b = PAIR ? unit / utiles : blockIdx.y;
     const int P = a.P;
     const int K = a.C1 + a.C2 + a.C3;
     const int NB = (K + 31) >> 5;
     const int NT = (a.Cout + 15) >> 4;
-    const int t0 = grp * NCO;
-    const int tcnt = (NT - t0 < NCO) ? NT - t0 : NCO;
+    const bool idle = PAIR && grp >= ngroups;           // the second half of the last pair of an odd group count: reads tile 0, writes nothing
+    const int t0 = idle ? 0 : grp * NCO;
+    const int tcnt = idle ? 0 : (NT - t0 < NCO) ? NT - t0 : NCO;
     const int p0 = (tile * 4 + wave) * 64 + 4 * j;
     const bool live = p0 < P;
     const unsigned pl = (unsigned)(live ? p0 : 0);
     const u32x4* wp3 = reinterpret_cast<const u32x4*>(reinterpret_cast<const float*>(a.wp3) + (size_t)b * a.wp3_bstride);
-    stage_bias(a, bias_l, t0, NCO, tid);
+    stage_bias(a, bias_l + half * NCO * 16, t0, NCO, tid);
     if constexpr (LN) {
         for (int i = tid; i < 32 * NB; i += 256) {
             gam_l[i] = i < K ? a.ln_w[i] : 0.f;
@@ -564,7 +582,7 @@ __global__ void __launch_bounds__(256, 2) conv1x1_b3_kernel(Conv1x1Args a, int n
     auto store_w_block = [&](int buf) {
 #pragma unroll
         for (int i = 0; i < WPT; ++i)
-            if (tid + 256 * i < NCO * 192) lds_w[buf][tid + 256 * i] = wr[i];
+            if (tid + 256 * i < NCO * 192) lds_w[2 * half + buf][tid + 256 * i] = wr[i];
     };
 
     load_x_block(0);
@@ -601,7 +619,7 @@ __global__ void __launch_bounds__(256, 2) conv1x1_b3_kernel(Conv1x1Args a, int n
             load_x_block(c + 1);
             load_w_block(c + 1);
         }
-        const u32x4* wl = &lds_w[c & 1][lane];
+        const u32x4* wl = &lds_w[2 * half + (c & 1)][lane];
 #pragma unroll
         for (int t = 0; t < NCO; ++t) {
             const u32x4 ap[3] = {wl[(t * 3 + 0) * 64], wl[(t * 3 + 1) * 64], wl[(t * 3 + 2) * 64]};
@@ -610,7 +628,7 @@ __global__ void __launch_bounds__(256, 2) conv1x1_b3_kernel(Conv1x1Args a, int n
         if (c + 1 < NB) store_w_block((c + 1) & 1);
         __syncthreads();
     }
-    epilogue<NCO, false>(a, acc, t0, tcnt, bias_l, nullptr, b, p0, kq, live);
+    epilogue<NCO, false>(a, acc, t0, tcnt, bias_l + half * NCO * 16, nullptr, b, p0, kq, live);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -929,13 +947,31 @@ int launch_conv1x1(const Conv1x1Args& a, hipStream_t st) {
         // 6 tiles per workgroup where that divides the output evenly; never with the LayerNorm prologue (that instantiation
         // needs 2 registers more than the 256 a wave has at two waves per SIMD)
         int nco = (!a.ln_w && (NT % 6 == 0 || (NT % 4 != 0 && NT > 8))) ? 6 : 4;
+        // Paired form (two output groups per 512-thread workgroup, the pairs of a pixel tile on one XCD): x is fetched once per
+        // pixel tile instead of once per group.  It halves the workgroup count, so it is taken where every CU still gets one;
+        // smaller launches keep the unpaired form and the rule below.
+        const long units = (long)cdiv(a.P, 256) * a.B;
+        bool pair = !a.ln_w && cdiv(NT, nco) > 1 && units * cdiv(cdiv(NT, nco), 2) >= 256;
+#ifdef RF_DIAG   // diagnostic build only: RF_B3_PAIR=1 takes the paired form at any launch size, RF_B3_PAIR=0 never
+        if (const char* e = getenv("RF_B3_PAIR")) pair = !a.ln_w && cdiv(NT, nco) > 1 && e[0] != '0';
+#endif
         // one frame at levels 2-3: fewer than 256 workgroups -- two output tiles per workgroup instead of four fills more CUs
-        if (!a.ln_w && nco == 4 && NT % 2 == 0 && (long)cdiv(a.P, 256) * cdiv(NT, 4) * a.B < 256) nco = 2;
+        if (!pair && !a.ln_w && nco == 4 && NT % 2 == 0 && units * cdiv(NT, 4) < 256) nco = 2;
         const int ngroups = cdiv(NT, nco);
         dim3 grid((unsigned)(cdiv(a.P, 256) * ngroups), (unsigned)a.B, 1);
-        snprintf(key, sizeof(key), "conv1x1_b3_kernel<%d, %s>", nco, a.ln_w ? "true" : "false");
+        // the flat grid of the paired form: whole chunks of 8 units x pairs (conv1x1_group_grid), as one 32-bit workgroup id
+        const long pair_ids = (units + 7) / 8 * 8 * cdiv(ngroups, 2);
+        RF_CHECK_ARG(!pair || pair_ids < (1L << 31), "conv1x1: %ld pixel tiles x %d output groups is too large a grid", units, ngroups);
+        // the unpaired key names the family by its first two arguments (bench.py's lookup covers <.., false, false> with it);
+        // the paired form has a key of its own, so a profile shows which form a launch took
+        if (pair) snprintf(key, sizeof(key), "conv1x1_b3_kernel<%d, false, true>", nco);
+        else snprintf(key, sizeof(key), "conv1x1_b3_kernel<%d, %s>", nco, a.ln_w ? "true" : "false");
         ProfScope prof(st, key, work_flops, work_bytes);
-        if (nco == 6) {
+        if (pair) {
+            const unsigned gx = conv1x1_group_grid((unsigned)units, (unsigned)cdiv(ngroups, 2));
+            if (nco == 6) conv1x1_b3_kernel<6, false, true><<<gx, 512, 0, st>>>(a, ngroups);
+            else conv1x1_b3_kernel<4, false, true><<<gx, 512, 0, st>>>(a, ngroups);
+        } else if (nco == 6) {
             conv1x1_b3_kernel<6, false><<<grid, 256, 0, st>>>(a, ngroups);
         } else if (nco == 2) {
             conv1x1_b3_kernel<2, false><<<grid, 256, 0, st>>>(a, ngroups);

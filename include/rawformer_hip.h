@@ -176,6 +176,11 @@ int rf_conv1x1_scratch_bytes(int Cin_total, int Cout, size_t* bytes);
 int rf_conv1x1(const float* in, const float* in2, float* out, const float* weight, const float* bias,
                const float* ln_w, const float* ln_b, const float* res, void* scratch,
                int B, int C1, int C2, int Cout, int h, int w, void* stream);
+/* Host only, no launch: the workgroup order of the 1x1 GEMM whose output groups share their input.  A launch of `units`
+ * pixel tiles x `ngroups` groups has *ids workgroups (whole chunks of 8 units); workgroup `id` works on (*unit, *group), or on
+ * nothing (*unit = *group = -1: padding of the last chunk).  All groups of a unit have ids 8 apart. */
+int rf_conv1x1_group_grid(int units, int ngroups, int* ids);
+int rf_conv1x1_group_map(int units, int ngroups, int id, int* unit, int* group);
 /* nn.Conv2d(C, C, 3, padding=1, groups=C) (+bias), optional exact GELU: conv_ffn middle
  * (RawFomer_WFB_FFAB/model.py:326-334). */
 int rf_dwconv3x3(const float* in, float* out, const float* weight, const float* bias, int gelu,
