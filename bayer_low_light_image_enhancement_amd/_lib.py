@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("RF_LIB_PATH") or os.path.join(_HERE, "csrc", "librawf
 RF_VARIANT_FLCA = 0
 RF_VARIANT_PLAIN = 1
 RF_VARIANT_TRUECOLOR = 2
+RF_VARIANT_MULTILVL = 3
 
 
 class RfConfig(C.Structure):

@@ -421,6 +421,22 @@ int launch_tc_spatial(const float* feat, float* xs, const float* guide, const fl
                       const float* b_low, const float* w_high, const float* b_high, int B, int C, int h, int w, hipStream_t st);
 int launch_tc_residual(const float* xs, const float* r, float* x2, float* partial, int B, int C, int h, int w, hipStream_t st);
 int launch_tc_color_head(float* x, const float* const* prm, int B, size_t P, hipStream_t st);
+int launch_tc_pyramid(const float* src, float* ll, float* mag, int B, int hs, int ws, hipStream_t st);
+
+// ---- multi-level FLCA RawFormer extras (rf_multilvl.hip): guidance pyramid, per-stage planes and pooled means, the gated
+// modulation of one residual step (step = pyramid level, or `levels` for the chroma form), the output corrections
+size_t ml_scratch_floats(int B, int H, int W, int levels);
+int launch_ml_guidance(const float* in, int mosaic, float* scratch, int B, int H, int W, int levels, hipStream_t st);
+int launch_ml_guide_level(float* scratch, float* guide, int lvl, int B, int H, int W, int levels, int hf, int wf, hipStream_t st);
+const float* ml_level_means(const float* scratch, int lvl, int B, int H, int W, int levels);
+int launch_ml_modulate(const float* x, float* out, const float* guide, const float* means, int step, int levels, const float* w_a,
+                       const float* w_b, const float* gate_w, const float* gate_b, int B, int C, int h, int w, hipStream_t st);
+int launch_ml_residual(const float* x, const float* r, float* out, int B, int C, int h, int w, hipStream_t st);
+bool ml_step_fused_supported(int C, int h, int w);
+int launch_ml_step_fused(const float* x, float* out, const float* guide, const float* means, int step, int levels, const float* w_a,
+                         const float* w_b, const float* gate_w, const float* gate_b, const float* w0, const float* b0, const float* w2,
+                         const float* b2, float* partial, int B, int C, int h, int w, hipStream_t st);
+int launch_ml_tail(float* out, const float* in, int mosaic, float* scratch, int B, int H, int W, int levels, hipStream_t st);
 
 // ---- training kernels (rf_train.hip)
 size_t gram2_partial_floats(int B, int Ca, int Cb, int h, int w, int ntap);
@@ -482,6 +498,7 @@ size_t guidance_scratch_floats(int B, int H, int W);
 int launch_guidance_base(const float* in, int mosaic, int clamp_in, float* scratch, int B, int H, int W, hipStream_t st,
                          void (*allreduce)(void*, float*, size_t, int, void*) = nullptr, void* allreduce_user = nullptr);
 int launch_guidance_level(const float* scratch, float* guide, int B, int H, int W, int hf, int wf, hipStream_t st);
+void guidance_planes(float* scratch, int B, int H, int W, float** y, float** cr, float** cb, float** ll, float** mag);
 struct FlcaSpatialArgs {
     const float* feat; float* xs; const float* guide;   // feat/xs [B][C][P], guide [B][4][h][w]
     const float* w_low; const float* w_high; const float* w_chr;   // [C][1][3][3], [C][1][3][3], [C][2][3][3]

@@ -32,6 +32,12 @@ __host__ __device__ static inline GuideLayout guide_layout(float* s, int B, int 
     return g;
 }
 
+// the planes launch_guidance_base leaves in its scratch, for a schedule that resizes them itself (rf_multilvl.hip)
+void guidance_planes(float* scratch, int B, int H, int W, float** y, float** cr, float** cb, float** ll, float** mag) {
+    const GuideLayout g = guide_layout(scratch, B, H, W);
+    *y = g.y; *cr = g.cr; *cb = g.cb; *ll = g.ll; *mag = g.mag;
+}
+
 __device__ __forceinline__ void atomic_max_float(int* addr, float v) {
     if (v >= 0.f) atomicMax(addr, __float_as_int(v));
     else atomicMin(reinterpret_cast<unsigned int*>(addr), __float_as_uint(v));

@@ -49,6 +49,12 @@ struct TcIx {        // EnhancedFLCA branch of a stage: weight and bias of color
     rf::SeGroup<int> se;
     int res0_w, res0_b, res2_w, res2_b;
 };
+struct MlIx {        // FLCA_Pyramid branch of a stage: low_attn.<l>.0 / high_attn.<l>.0 weights, freq_gate_head.<l>, chroma_attn.0, chroma_gate, se, res_proj.0 / .2
+    int low_w[3], high_w[3], gate_w[3], gate_b[3];
+    int chr_w, cgate_w, cgate_b;
+    rf::SeGroup<int> se;
+    int res0_w, res0_b, res2_w, res2_b;
+};
 struct BayerProcIx { int wb_gains, color_matrix, dm0_w, dm0_b, dm2_w, dm2_b, ce0_w, ce0_b, ce2_w, ce2_b; };   // bayer_processor.*: demosaic_refine.0 / .2, chroma_extractor.0 / .2
 struct ColorCorrIx { int gamma, ct0_w, ct0_b, ct2_w, ct2_b, tone0_w, tone0_b, tone2_w, tone2_b; };             // color_correction.*: color_transform.0 / .2, tone_curve.0 / .2
 
@@ -62,6 +68,7 @@ struct StageIx {
     int conv_w, conv_b;               // plain branch
     rf::FlcaGroup<int> flca;            // FLCA branch
     TcIx tc;                          // TrueColor branch
+    MlIx ml;                          // multi-level FLCA branch
     // composed tail (rf_flca.hip pack_tail), floats into the packed buffer of [Wb W2 | b'] (0 = not composed) and, plain variant
     // only, of the static b3 weights [Wa | Wb | Wb W2]
     size_t tail_offset = 0, tail3_offset = 0;

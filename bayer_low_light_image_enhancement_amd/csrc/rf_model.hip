@@ -76,6 +76,32 @@ void add_stage(rf_handle* h, int i, int lvl) {
             add_pack(h, w, PK_1x1);
             add_pack(h, w, PK_1x1_B3);
         }
+    } else if (cfg.variant == RF_VARIANT_MULTILVL) {
+        // FLCA_Pyramid (MultiLvlFrequencyawareLumaChromaAttentionRAWFormer.py:90-116), state_dict order
+        const std::string f = pre + "FLCA.";
+        const int hid = flca_hidden(C), L = cfg.flca_levels > 0 ? cfg.flca_levels : 2;
+        MlIx& m = s.ml;
+        for (int l = 0; l < L; ++l) m.low_w[l] = add_param(h, f + "low_attn." + std::to_string(l) + ".0.weight", {C, 1, 3, 3});
+        for (int l = 0; l < L; ++l) m.high_w[l] = add_param(h, f + "high_attn." + std::to_string(l) + ".0.weight", {C, 1, 3, 3});
+        for (int l = 0; l < L; ++l) {
+            m.gate_w[l] = add_param(h, f + "freq_gate_head." + std::to_string(l) + ".weight", {2, 2, 1, 1});
+            m.gate_b[l] = add_param(h, f + "freq_gate_head." + std::to_string(l) + ".bias", {2});
+        }
+        m.chr_w = add_param(h, f + "chroma_attn.0.weight", {C, 2, 3, 3});
+        m.cgate_w = add_param(h, f + "chroma_gate.weight", {1, 1, 1, 1});
+        m.cgate_b = add_param(h, f + "chroma_gate.bias", {1});
+        m.se.se1_w = add_param(h, f + "se.1.weight", {hid, C, 1, 1});
+        m.se.se1_b = add_param(h, f + "se.1.bias", {hid});
+        m.se.se3_w = add_param(h, f + "se.3.weight", {C, hid, 1, 1});
+        m.se.se3_b = add_param(h, f + "se.3.bias", {C});
+        m.res0_w = add_param(h, f + "res_proj.0.weight", {C, C, 1, 1});
+        m.res0_b = add_param(h, f + "res_proj.0.bias", {C});
+        m.res2_w = add_param(h, f + "res_proj.2.weight", {C, C, 1, 1});
+        m.res2_b = add_param(h, f + "res_proj.2.bias", {C});
+        for (int w : {m.res0_w, m.res2_w}) {
+            add_pack(h, w, PK_1x1);
+            add_pack(h, w, PK_1x1_B3);
+        }
     } else if (cfg.variant == RF_VARIANT_FLCA) {
         const std::string f = pre + "FLCA.";
         const int hid = flca_hidden(C);
@@ -146,11 +172,12 @@ struct Plan {
 int make_plan(const rf_handle* h, int B, int H, int W, Plan& p) {
     const rf_config& c = h->cfg;
     const size_t U0 = (size_t)B * c.dim * H * W;   // floats of a level-0 activation
-    const bool tc = c.variant == RF_VARIANT_TRUECOLOR;
+    const bool ml = c.variant == RF_VARIANT_MULTILVL;
+    const bool tc = c.variant == RF_VARIANT_TRUECOLOR || ml;      // the branch follows the block on one stream and pools with tc_residual
     const int levels = c.flca_levels > 0 ? c.flca_levels : 2;
-    p.guide_planes = tc ? 7 : 4;
+    p.guide_planes = ml ? 2 * levels + 2 : tc ? 7 : 4;
     Bump b;      // offsets into the caller's workspace
-    p.gscratch = b.off(tc ? tc_front_scratch_floats(B, H, W, levels) : guidance_scratch_floats(B, H, W));
+    p.gscratch = b.off(ml ? ml_scratch_floats(B, H, W, levels) : tc ? tc_front_scratch_floats(B, H, W, levels) : guidance_scratch_floats(B, H, W));
     for (int l = 0; l < 4; ++l) p.guide[l] = b.off((size_t)B * p.guide_planes * (H >> l) * (W >> l));
     for (int l = 0; l < 3; ++l) p.skip[l] = b.off(U0 >> l);
     p.tA = b.off(U0);
@@ -254,7 +281,8 @@ int run_stage(rf_handle* h, int i, const float* in, float* out, float* ws, const
     // k-steps of its second GEMM, Wb W2 replaces W2 -- so neither `trans` nor the channel_reduce launch exists.  The kernel reads
     // the weights in f32 operand order from the fold slot of the workspace (per image: the FLCA gate; one set for the plain
     // variant, folded per call: the packed buffer has no room for it).  Not TrueColor, whose branch runs after the block.
-    bool fuse_tail = x.tail_offset != 0 && ffn_fused && fused_ffn_tail_supported(C) && cfg.variant != RF_VARIANT_TRUECOLOR;
+    const bool branch_after = cfg.variant == RF_VARIANT_TRUECOLOR || cfg.variant == RF_VARIANT_MULTILVL;
+    bool fuse_tail = x.tail_offset != 0 && ffn_fused && fused_ffn_tail_supported(C) && !branch_after;
 #ifdef RF_DIAG   // diagnostic build only: the two-GEMM form
     if (getenv("RF_NO_COMPOSE") || getenv("RF_NO_B3")) compose = false;
     if (getenv("RF_NO_COMPOSE")) fuse_tail = false;
@@ -263,9 +291,9 @@ int run_stage(rf_handle* h, int i, const float* in, float* out, float* ws, const
     const float* composed = compose || fuse_tail ? h->packed + x.tail_offset : nullptr;
     float* const fold_wp = compose ? nullptr : ws + p.wfold_cr;          // the fold writes the form(s) the tail reads
     float* const fold_wp3 = fuse_tail ? nullptr : ws + p.wfold_cr3;
-    // the branch is launched first (on the branch stream when there is one), the block beside it; TrueColor's branch borrows
-    // bufA and therefore follows the block on the same stream
-    if (cfg.variant == RF_VARIANT_TRUECOLOR) RF_TRY(run_transformer(tp, in, trans, ws, to, B, C, heads, hc, hh, ww, st));
+    // the branch is launched first (on the branch stream when there is one), the block beside it; the TrueColor and multi-level
+    // branches borrow bufA and therefore follow the block on the same stream
+    if (branch_after) RF_TRY(run_transformer(tp, in, trans, ws, to, B, C, heads, hc, hh, ww, st));
     else RF_TRY(h->side.fork(st, side));
 
     // branch, cat, channel_reduce -------------------------------------------------------------
@@ -290,6 +318,48 @@ int run_stage(rf_handle* h, int i, const float* in, float* out, float* ws, const
         RF_TRY(launch_conv1x1(r2, st));
         RF_TRY(launch_tc_residual(xs, ws + p.bufA, xs, ws + p.flca_partial, B, C, hh, ww, st));
         RF_TRY(launch_flca_se_fold(ws + p.flca_partial, tc_nblk(hh, ww), Pn, h->se_prm(t.se), h->prm(x.cr_w), fold_wp, fold_wp3,
+                                   ws + p.ch, B, C, st, composed, hc));
+        r.wp = ws + p.wfold_cr; r.wp_bstride = (int64_t)packed1x1_floats(2 * C, C);
+        r.wp3 = ws + p.wfold_cr3; r.wp3_bstride = (int64_t)packed1x1_b3_floats(compose ? 2 * C + hc : 2 * C, C);
+    } else if (cfg.variant == RF_VARIANT_MULTILVL) {
+        // FLCA_Pyramid (MultiLvlFrequencyawareLumaChromaAttentionRAWFormer.py:132-183): for every pyramid level and then for the
+        // chroma planes  x <- x + 0.2 tanh(res_proj(x * gated spatial attention)),  one res_proj for all steps; squeeze-excite
+        // folded into channel_reduce.  A composed step is modulate -> 1x1 (ReLU) -> 1x1 -> residual; the last one leaves the pooling sums.
+        const MlIx& m = x.ml;
+        const int L = cfg.flca_levels > 0 ? cfg.flca_levels : 2;
+        const float* means = ml_level_means(ws + p.gscratch, lvl, B, H, W, L);
+        float* t1 = ws + p.bufA;
+        float* t2 = t1 + (size_t)B * C * Pn;
+        Conv1x1Args r0{};
+        r0.x1 = crb; r0.C1 = C; r0.x1_bstride = (int64_t)C * Pn; r0.wp = h->pk(m.res0_w); r0.wp3 = h->pk3(m.res0_w);
+        r0.bias = h->prm(m.res0_b); r0.out = t1; r0.out_bstride = (int64_t)C * Pn; r0.Cout = C; r0.B = B; r0.P = Pn; r0.w = ww; r0.act = 2;
+        Conv1x1Args r2 = r0;
+        r2.x1 = t1; r2.wp = h->pk(m.res2_w); r2.wp3 = h->pk3(m.res2_w); r2.bias = h->prm(m.res2_b); r2.out = t2; r2.act = 0;
+        // level 0 (C = dim <= 64, the largest tensor): one kernel per step, nothing but x and the result in HBM
+        bool fused_step = ml_step_fused_supported(C, hh, ww);
+#ifdef RF_DIAG   // diagnostic build only: the composed steps everywhere
+        if (getenv("RF_NO_ML_FUSED")) fused_step = false;
+#endif
+        const float* cur = in;
+        for (int s = 0; s <= L; ++s) {
+            const bool chroma = s == L;
+            const float* w_a = h->prm(chroma ? m.chr_w : m.low_w[s]);
+            const float* w_b = chroma ? nullptr : h->prm(m.high_w[s]);
+            const float* g_w = h->prm(chroma ? m.cgate_w : m.gate_w[s]);
+            const float* g_b = h->prm(chroma ? m.cgate_b : m.gate_b[s]);
+            if (fused_step) {
+                RF_TRY(launch_ml_step_fused(cur, xs, ws + p.guide[lvl], means, s, L, w_a, w_b, g_w, g_b, h->prm(m.res0_w), h->prm(m.res0_b),
+                                            h->prm(m.res2_w), h->prm(m.res2_b), chroma ? ws + p.flca_partial : nullptr, B, C, hh, ww, st));
+            } else {
+                RF_TRY(launch_ml_modulate(cur, crb, ws + p.guide[lvl], means, s, L, w_a, w_b, g_w, g_b, B, C, hh, ww, st));
+                RF_TRY(launch_conv1x1(r0, st));
+                RF_TRY(launch_conv1x1(r2, st));
+                if (chroma) RF_TRY(launch_tc_residual(cur, t2, xs, ws + p.flca_partial, B, C, hh, ww, st));   // the last step: + pooling sums
+                else RF_TRY(launch_ml_residual(cur, t2, xs, B, C, hh, ww, st));
+            }
+            cur = xs;
+        }
+        RF_TRY(launch_flca_se_fold(ws + p.flca_partial, tc_nblk(hh, ww), Pn, h->se_prm(m.se), h->prm(x.cr_w), fold_wp, fold_wp3,
                                    ws + p.ch, B, C, st, composed, hc));
         r.wp = ws + p.wfold_cr; r.wp_bstride = (int64_t)packed1x1_floats(2 * C, C);
         r.wp3 = ws + p.wfold_cr3; r.wp3_bstride = (int64_t)packed1x1_b3_floats(compose ? 2 * C + hc : 2 * C, C);
@@ -322,7 +392,7 @@ int run_stage(rf_handle* h, int i, const float* in, float* out, float* ws, const
         RF_TRY(run_transformer_attn(tp, in, ws, to, B, C, heads, hh, ww, st));
         RF_TRY(h->side.join(st, side));
         RF_TRY(run_transformer_ffn(tp, crb, ws, to, B, C, hc, hh, ww, st));
-    } else if (cfg.variant != RF_VARIANT_TRUECOLOR) {
+    } else if (!branch_after) {
         RF_TRY(run_transformer(tp, in, trans, ws, to, B, C, heads, hc, hh, ww, st));
         RF_TRY(h->side.join(st, side));
     }
@@ -409,10 +479,13 @@ int rf_create(const rf_config* cfg, rf_handle** out) {
     RF_CHECK_ARG(cfg->dim > 0 && cfg->dim % 8 == 0, "rf_create: dim=%d must be a positive multiple of 8", cfg->dim);
     RF_CHECK_ARG(cfg->inp_channels == 1, "rf_create: inp_channels=%d (only the 1-channel Bayer mosaic is supported)", cfg->inp_channels);
     RF_CHECK_ARG(cfg->out_channels > 0 && cfg->ffn_expansion > 0, "rf_create: bad out_channels / ffn_expansion");
-    RF_CHECK_ARG(cfg->variant == RF_VARIANT_FLCA || cfg->variant == RF_VARIANT_PLAIN || cfg->variant == RF_VARIANT_TRUECOLOR,
+    RF_CHECK_ARG(cfg->variant == RF_VARIANT_FLCA || cfg->variant == RF_VARIANT_PLAIN || cfg->variant == RF_VARIANT_TRUECOLOR ||
+                     cfg->variant == RF_VARIANT_MULTILVL,
                  "rf_create: unknown variant %d", cfg->variant);
     RF_CHECK_ARG(cfg->flca_levels >= 0 && cfg->flca_levels <= 3, "rf_create: flca_levels=%d (1..3, 0 = default 2)", cfg->flca_levels);
     RF_CHECK_ARG(cfg->variant != RF_VARIANT_TRUECOLOR || cfg->out_channels == 3, "rf_create: the TrueColor colour head is defined for 3 output channels");
+    RF_CHECK_ARG(cfg->variant != RF_VARIANT_MULTILVL || (cfg->out_channels == 3 && !cfg->clamp_io),
+                 "rf_create: the multilvl output corrections are defined for 3 output channels and no clamp_io");
     for (int l = 0; l < 4; ++l) {
         const int C = cfg->dim << l;
         RF_CHECK_ARG(cfg->heads[l] > 0 && C % cfg->heads[l] == 0 && C / cfg->heads[l] <= 64,
@@ -443,7 +516,8 @@ int rf_create(const rf_config* cfg, rf_handle** out) {
     for (int i = 1; i <= 3; ++i) {
         const int C = d << (i - 1);
         add_stage(h, i, i - 1);
-        h->down_w[i - 1] = add_param(h, "down" + std::to_string(i) + ".body.0.weight", {C / 2, C, 3, 3});
+        // (the multi-level file's down<i> is a bare nn.Sequential: no `body`)
+        h->down_w[i - 1] = add_param(h, "down" + std::to_string(i) + (cfg->variant == RF_VARIANT_MULTILVL ? ".0.weight" : ".body.0.weight"), {C / 2, C, 3, 3});
         add_pack(h, h->down_w[i - 1], PK_3x3);
     }
     add_stage(h, 4, 3);
@@ -582,7 +656,7 @@ static int set_shard_state(rf_handle* h, const char* who, int y_lo, int y_hi, in
         h->shard_allreduce = nullptr; h->shard_user = nullptr;
         return RF_OK;
     }
-    RF_CHECK_ARG(h->cfg.variant != RF_VARIANT_TRUECOLOR, "%s: variants flca and plain only", who);
+    RF_CHECK_ARG(h->cfg.variant == RF_VARIANT_FLCA || h->cfg.variant == RF_VARIANT_PLAIN, "%s: variants flca and plain only", who);
     RF_CHECK_ARG(y_lo >= 0 && y_hi > y_lo && y_lo % 8 == 0 && y_hi % 8 == 0 && total_rows >= y_hi - y_lo && total_rows % 8 == 0,
                  "%s: interior rows [%d, %d) of %d must be multiples of 8", who, y_lo, y_hi, total_rows);
     // columns: cuts on multiples of 32 keep the bounds of every level (>> 3 at the coarsest) on the kernels' groups of 4 pixels;
@@ -613,7 +687,8 @@ int rf_forward_stage(rf_handle* h, int stage, const float* in, const float* pack
     RF_CHECK_ARG(h && in && out && workspace && stage >= 1 && stage <= 7, "rf_forward_stage: bad arguments (stage 1..7)");
     RF_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0,
                  "rf_forward_stage: packed size %dx%d must be positive multiples of 8", H, W);
-    RF_CHECK_ARG(h->cfg.variant != RF_VARIANT_FLCA || packed, "rf_forward_stage: the FLCA branch needs the packed frame for its guidance");
+    RF_CHECK_ARG((h->cfg.variant != RF_VARIANT_FLCA && h->cfg.variant != RF_VARIANT_MULTILVL) || packed,
+                 "rf_forward_stage: the FLCA branch needs the packed frame for its guidance");
     RF_CHECK_ARG(h->cfg.variant != RF_VARIANT_TRUECOLOR, "rf_forward_stage: not available for the TrueColor variant");
     if (!h->packed) {
         set_error("rf_forward_stage: parameters not packed (call rf_pack_params after rf_set_param)");
@@ -632,6 +707,11 @@ int rf_forward_stage(rf_handle* h, int stage, const float* in, const float* pack
     if (h->cfg.variant == RF_VARIANT_FLCA) {
         RF_TRY(launch_guidance_base(packed, 0, h->cfg.clamp_io, ws + p.gscratch, B, H, W, st));
         RF_TRY(launch_guidance_level(ws + p.gscratch, ws + p.guide[lvl], B, H, W, H >> lvl, W >> lvl, st));
+    } else if (h->cfg.variant == RF_VARIANT_MULTILVL) {
+        const int levels = h->cfg.flca_levels > 0 ? h->cfg.flca_levels : 2;
+        RF_CHECK_ARG(aligned16(packed), "rf_forward_stage: buffers must be 16-byte aligned");
+        RF_TRY(launch_ml_guidance(packed, 0, ws + p.gscratch, B, H, W, levels, st));
+        RF_TRY(launch_ml_guide_level(ws + p.gscratch, ws + p.guide[lvl], lvl, B, H, W, levels, H >> lvl, W >> lvl, st));
     }
     if (p.ks_floats) RF_TRY(check_hip(hipMemsetAsync(ws + p.ks, 0, conv3x3_ksplit_counter_bytes(), st), "rf_forward_stage: memset"));
     return run_stage(h, stage, in, out, ws, p, B, H, W, st, st);
@@ -672,7 +752,7 @@ int rf_forward(rf_handle* h, const float* in, float* out, void* workspace, size_
     // both chains is a few dozen microseconds of mostly latency, so the branch runs on the handle's second stream, forked
     // before it and joined before channel_reduce.  Not for a spatial shard (its collectives stay on the caller's stream) nor
     // for TrueColor (its branch shares bufA with the block).
-    bool use_side = !h->shard_allreduce && cfg.variant != RF_VARIANT_TRUECOLOR;
+    bool use_side = !h->shard_allreduce && cfg.variant != RF_VARIANT_TRUECOLOR && cfg.variant != RF_VARIANT_MULTILVL;
 #ifdef RF_DIAG   // diagnostic build only: everything on the caller's stream
     if (getenv("RF_NO_SIDE")) use_side = false;
 #endif
@@ -692,6 +772,10 @@ int rf_forward(rf_handle* h, const float* in, float* out, void* workspace, size_
                                ws + p.gscratch, B, H, W, levels, st));
         for (int l = 0; l < 4; ++l)
             RF_TRY(launch_tc_guide_level(ws + p.gscratch, ws + p.guide[l], B, H, W, levels, H >> l, W >> l, st));
+    } else if (cfg.variant == RF_VARIANT_MULTILVL) {
+        RF_TRY(launch_ml_guidance(in, mosaic, ws + p.gscratch, B, H, W, levels, st));
+        for (int l = 0; l < 4; ++l)
+            RF_TRY(launch_ml_guide_level(ws + p.gscratch, ws + p.guide[l], l, B, H, W, levels, H >> l, W >> l, st));
     }
     // embedding (reads the mosaic through the Bayer pack)
     Conv3x3Args e{};
@@ -752,6 +836,8 @@ int rf_forward(rf_handle* h, const float* in, float* out, void* workspace, size_
                                h->prm(cc.tone0_w), h->prm(cc.tone0_b), h->prm(cc.tone2_w), h->prm(cc.tone2_b)};
         RF_TRY(launch_tc_color_head(out, prm, B, (size_t)4 * H * W, st));
     }
+    // colour anchor and luminance nudge (MultiLvlFrequencyawareLumaChromaAttentionRAWFormer.py:403-414)
+    if (cfg.variant == RF_VARIANT_MULTILVL) RF_TRY(launch_ml_tail(out, in, mosaic, ws + p.gscratch, B, H, W, levels, st));
     return RF_OK;
 }
 

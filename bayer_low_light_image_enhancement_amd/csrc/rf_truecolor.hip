@@ -364,6 +364,15 @@ int launch_tc_front(const float* in, int mosaic, const float* wb_gains, const fl
     return check_launch("tc_front");
 }
 
+// one more pyramid level: Haar LL and high-band magnitude of `src` [B][hs][ws] (the multi-level FLCA variant builds its own pyramid)
+int launch_tc_pyramid(const float* src, float* ll, float* mag, int B, int hs, int ws, hipStream_t st) {
+    RF_CHECK_ARG(B <= 65535 && hs >= 2 && ws >= 2, "pyramid level of a %dx%d plane", hs, ws);
+    const size_t n = (size_t)((hs + 1) / 2) * ((ws + 1) / 2);
+    ProfScope prof(st, "tc_pyramid_kernel", 0.0, 4.0 * B * n * 6);
+    tc_pyramid_kernel<<<dim3((unsigned)grid_for(n, 1024), (unsigned)B), 256, 0, st>>>(src, ll, mag, hs, ws);
+    return check_launch("tc_pyramid");
+}
+
 int launch_tc_guide_level(const float* scratch, float* guide, int B, int H, int W, int levels, int hf, int wf, hipStream_t st) {
     const TcFrontBufs f = tc_front_layout(const_cast<float*>(scratch), B, H, W, levels);
     TcGuideSrc s{};

@@ -16,7 +16,9 @@ front end, colour-aware pyramid FLCA, ``exp(log_temperature)`` attention, colour
 ``flca_levels`` as in its constructor); ``variant='plain'`` replaces the FLCA
 branch by the 3x3 conv branch of RawFomer_WFB_FFAB/model.py:393-412 (``branch_lrelu=True``)
 or model.py:94-108 (``False``) and, with ``clamp_io=True``, adds the I/O clamps of
-RawFomer_WFB_FFAB/model.py:475,508.
+RawFomer_WFB_FFAB/model.py:475,508.  ``variant='multilvl'`` is the ``RawFormer`` of
+MultiLvlFrequencyawareLumaChromaAttentionRAWFormer.py:313-416 (``FLCA_Pyramid`` branches with ``flca_levels`` pyramid
+levels, per-channel colour anchor and luminance nudge on the output); forward and evaluation only.
 
 The module owns ordinary ``nn.Parameter`` objects; the HIP library borrows their device
 pointers.  There is no PyTorch fallback: on a CPU tensor ``forward`` raises.
@@ -83,6 +85,10 @@ def canonical_key(key: str) -> str:
     return stage + rest
 
 
+_VARIANTS = {"flca": _lib.RF_VARIANT_FLCA, "plain": _lib.RF_VARIANT_PLAIN, "truecolor": _lib.RF_VARIANT_TRUECOLOR,
+             "multilvl": _lib.RF_VARIANT_MULTILVL}
+
+
 class _Node(nn.Module):
     """Name-only container so parameters get the reference's dotted state_dict keys."""
 
@@ -110,8 +116,8 @@ class RawFormer(nn.Module):
         out_channels = out_ch if out_ch is not None else out_channels
         num_heads = list(heads if heads is not None else num_heads)
         ffn_expansion_factor = ffn_exp if ffn_exp is not None else ffn_expansion_factor
-        if variant not in ("flca", "plain", "truecolor"):
-            raise ValueError(f"variant must be 'flca', 'plain' or 'truecolor', got {variant!r}")
+        if variant not in _VARIANTS:
+            raise ValueError(f"variant must be 'flca', 'plain', 'truecolor' or 'multilvl', got {variant!r}")
         if len(num_heads) != 4:
             raise ValueError("num_heads must have 4 entries")
         self.dim, self.inp_channels, self.out_channels = int(dim), int(inp_channels), int(out_channels)
@@ -133,9 +139,9 @@ class RawFormer(nn.Module):
                 self._register(key, nn.Parameter(torch.empty(tuple(shape[: ndim.value]), dtype=torch.float32)))
         finally:
             lib.rf_destroy(probe)
-        if variant in ("flca", "truecolor"):
+        if variant in ("flca", "truecolor", "multilvl"):
             # fixed buffers the reference keeps in its state_dict (values are constants in the kernels)
-            if variant == "flca":
+            if variant in ("flca", "multilvl"):
                 for k, v in (("r_w", 0.299), ("g_w", 0.587), ("b_w", 0.114)):
                     self._register_buffer("luma_chroma." + k, torch.tensor(v, dtype=torch.float32))
             else:
@@ -145,6 +151,8 @@ class RawFormer(nn.Module):
             filt = torch.stack([torch.outer(hv, hv), torch.outer(hv, gv), torch.outer(gv, hv), torch.outer(gv, gv)]).unsqueeze(1)
             for i in range(1, 8):
                 self._register_buffer(f"conv_tran{i}.FLCA.dwt.filt", filt.clone())
+            if variant == "multilvl":
+                self._register_buffer("haar.filt", filt.clone())
         self.reset_parameters()
         self._rt: Dict[int, _DeviceState] = {}
         self._rt_lock = threading.Lock()
@@ -154,7 +162,7 @@ class RawFormer(nn.Module):
     def _config(self) -> _lib.RfConfig:
         return _lib.RfConfig(self.dim, (C.c_int32 * 4)(*self.num_heads), self.inp_channels, self.out_channels,
                              self.ffn_expansion_factor,
-                             {"flca": _lib.RF_VARIANT_FLCA, "plain": _lib.RF_VARIANT_PLAIN, "truecolor": _lib.RF_VARIANT_TRUECOLOR}[self.variant],
+                             _VARIANTS[self.variant],
                              int(self.branch_lrelu), int(self.clamp_io), self.flca_levels)
 
     def _node(self, path: List[str]) -> nn.Module:
@@ -354,8 +362,8 @@ class RawFormer(nn.Module):
         ``x_hi`` a multiple of 32 or the window's width (``tiling.plan_grid_shards``)."""
         import torch.distributed as dist
 
-        if self.variant == "truecolor":
-            raise RuntimeError("forward_window: variants 'flca' and 'plain' only")
+        if self.variant not in ("flca", "plain"):
+            raise RuntimeError(f"forward_window: variants 'flca' and 'plain' only, not {self.variant!r}")
         lib = _lib.load()
         failure: List[BaseException] = []
 
@@ -405,7 +413,7 @@ class RawFormer(nn.Module):
     def forward_stage(self, stage: int, x: torch.Tensor, packed: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One ``conv_tran<stage>`` (``Conv_Transformer``) exactly as ``forward`` schedules it.  ``x``: the stage input
         ``[B, dim*2^l, H>>l, W>>l]``; ``packed``: the packed frame ``[B,4,H,W]`` the FLCA guidance is derived from
-        (``variant='flca'``; for ``'plain'`` pass ``None`` and H, W are taken from ``x``)."""
+        (``variant='flca'`` and ``'multilvl'``; for ``'plain'`` pass ``None`` and H, W are taken from ``x``)."""
         if x.device.type != "cuda":
             raise RuntimeError("RawFormer (HIP) needs a ROCm device tensor: there is no CPU path in this package")
         lvl = stage - 1 if stage <= 4 else 7 - stage

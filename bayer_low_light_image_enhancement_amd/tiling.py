@@ -295,6 +295,8 @@ def forward_full_frame_exact(model, x: torch.Tensor, group=None, halo: int = HAL
     ``plan_grid_shards`` (w divisible by 16 too), interiors padded to the largest one for the all-gather."""
     import torch.distributed as dist
 
+    if getattr(model, "variant", None) not in (None, "flca", "plain"):
+        raise RuntimeError(f"forward_full_frame_exact: variants 'flca' and 'plain' only, not {model.variant!r}")
     if grid is not None:
         return _forward_grid_exact(model, x, group, halo, grid)
     world, rank = dist.get_world_size(group), dist.get_rank(group)

@@ -99,7 +99,7 @@ class Trainer:
                  decoupled: bool = False, loss: str = "l1", charbonnier_eps: float = 1e-3, group=None, overlap_allreduce: bool = True,
                  bucket_floats: int = 1 << 20, clamp_pred: bool = False):
         if model.variant not in ("plain", "flca"):
-            raise RuntimeError("Trainer: the adjoint schedule exists for variants 'plain' and 'flca'")
+            raise RuntimeError(f"Trainer: the adjoint schedule exists for variants 'plain' and 'flca', not {model.variant!r}")
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("Trainer needs the model on a ROCm device: there is no CPU path in this package")

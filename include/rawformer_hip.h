@@ -40,6 +40,9 @@ extern "C" {
 #define RF_VARIANT_TRUECOLOR 2 /* TrueColorRawFormer, BayerTORGBColorMultiLvl.py:387-462: learned Bayer front end
                                   (EnhancedBayerProcessor), EnhancedFLCA branch, exp(log_temperature) attention, ReLU before
                                   the PixelShuffle, CameraAwareColorCorrection head */
+#define RF_VARIANT_MULTILVL 3  /* MultiLvlFrequencyawareLumaChromaAttentionRAWFormer.py:313-416: FLCA_Pyramid branch (gated
+                                  progressive residuals over the Haar pyramid of the luma), per-channel colour anchor and
+                                  luminance nudge towards the 2-level LL after the PixelShuffle; forward only */
 
 typedef struct rf_handle rf_handle;
 
@@ -52,7 +55,7 @@ typedef struct rf_config {
     int32_t variant;          /* RF_VARIANT_*                                         */
     int32_t branch_lrelu;     /* plain variant: LeakyReLU on the conv branch (WFB) or not (model.py) */
     int32_t clamp_io;         /* clamp input and output to [0,1]: RawFomer_WFB_FFAB/model.py:475,508 */
-    int32_t flca_levels;      /* TRUECOLOR: wavelet pyramid depth of EnhancedFLCA (reference default 2; 0 = 2) */
+    int32_t flca_levels;      /* TRUECOLOR, MULTILVL: wavelet pyramid depth of the FLCA branch, 1..3 (reference default 2; 0 = 2) */
 } rf_config;
 
 const char* rf_last_error(void);

@@ -1,0 +1,277 @@
+"""``RawFormer(variant='multilvl')``: the reference's MultiLvlFrequencyawareLumaChromaAttentionRAWFormer.RawFormer.
+
+Fixtures (tools/make_golden_multilvl.py ran the reference on the CPU): tests/golden/multilvl.npz, multilvl_state_dict_keys.json,
+PINNING_multilvl.txt.  tests/multilvl_ref.py is the CPU restatement used where no fixture exists.
+
+Tolerance: TOL = 5e-5 max-abs, the whole-model bound of the flca variant (tests/test_gpu_model.py).  PINNING_multilvl.txt has the
+reference's own float32-against-float64 floor at 1.9e-6 .. 2.4e-6 on every case, below the 1.2e-5 above which the bound would
+become 4 x floor, so it stays 5e-5 (outputs reach |out| = 1.9).  Channel means: 2e-5, as in tests/test_truecolor.py (a mean of
+per-pixel errors, each under TOL).  Output corrections against the closed form: 5e-6 -- every output is at most ten float32
+operations on values below 2 (10 x 2^-24 x 2 = 1.2e-6), the bilinear sample of LL2 as many again, and the two means enter with
+0.12 times a relative error of a few 2^-24 of their pairwise sums."""
+import ctypes
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import cases
+import multilvl_ref
+from cases import golden
+from bayer_low_light_image_enhancement_amd import RawFormer, _lib, synth
+from oracle import rawformer_ref as R
+
+# tag, dim, flca_levels, batch, mosaic height, width, input seed (tools/make_golden_multilvl.py)
+CASES = (("ml_d16_b2_32x48", 16, 2, 2, 32, 48, 91), ("ml_d32_b1_64x64", 32, 2, 1, 64, 64, 92), ("ml_d16_l3_b1_64x64", 16, 3, 1, 64, 64, 93))
+TOL = 5e-5
+_STATE = {}
+_REF = {}
+
+
+def state(dim, levels=2):
+    """What the fixture tool gave the reference: synth values by name for every parameter; the constant buffers keep theirs."""
+    if (dim, levels) not in _STATE:
+        sd = RawFormer(dim=dim, variant="multilvl", flca_levels=levels).state_dict()
+        synth.fill_state_dict(sd, 5000 + dim)
+        _STATE[dim, levels] = sd
+    return {k: v.clone() for k, v in _STATE[dim, levels].items()}
+
+
+def model(dim, device, levels=2, sd=None):
+    m = RawFormer(dim=dim, variant="multilvl", flca_levels=levels)
+    m.load_state_dict(sd if sd is not None else state(dim, levels), strict=True)
+    return m.to(device).eval()
+
+
+def restated(dim, seed, b, hh, ww):
+    """The CPU restatement's output for a shape without a fixture, computed once."""
+    key = (dim, seed, b, hh, ww)
+    if key not in _REF:
+        x = torch.from_numpy(synth.bayer_mosaic(seed, b, hh, ww))
+        with torch.no_grad():
+            _REF[key] = (x, multilvl_ref.forward(state(dim), x, dim))
+    return _REF[key]
+
+
+def launches(fn):
+    """Kernel launches of ``fn()`` by kernel class, from the library's own per-launch brackets."""
+    lib = _lib.load()
+    torch.cuda.synchronize()
+    lib.rf_profile_begin()
+    try:
+        out = fn()
+        torch.cuda.synchronize()
+    finally:
+        buf = ctypes.create_string_buffer(1 << 16)
+        _lib.check(lib.rf_profile_end(buf, len(buf)), "rf_profile_end")
+    return out, {r["kernel"]: r["launches"] for r in json.loads(buf.value.decode())}
+
+
+# ------------------------------------------------------------------------------------------------ no GPU
+def test_state_dict_is_the_reference_one():
+    ref = json.load(open(os.path.join(cases.GOLDEN, "multilvl_state_dict_keys.json")))
+    for dim in (16, 32):
+        sd = RawFormer(dim=dim, variant="multilvl").state_dict()
+        assert {k: list(v.shape) for k, v in sd.items()} == {k: s for k, s in ref[str(dim)]}
+        assert len(sd) == len(ref[str(dim)])
+
+
+@pytest.mark.parametrize("tag,dim,levels,b,hh,ww,seed", CASES)
+def test_restatement_matches_the_reference(tag, dim, levels, b, hh, ww, seed):
+    x = torch.from_numpy(synth.bayer_mosaic(seed, b, hh, ww))
+    with torch.no_grad():
+        out = multilvl_ref.forward(state(dim, levels), x, dim, levels=levels)
+    g = golden("multilvl")
+    floor = float(np.abs(g[f"{tag}.out"].astype(np.float64) - g[f"{tag}.out_fp64"]).max())     # the reference's own float32 error
+    err = float((out - torch.from_numpy(g[f"{tag}.out"])).abs().max())
+    print(f"{tag}: restatement vs reference {err:.3e}, floor {floor:.3e}")
+    assert err <= max(5e-5, 4 * floor)
+
+
+def test_upsampled_mean_is_the_plain_mean():
+    """float64: with align_corners=False and an exact factor 2 every source pixel carries a total weight of 4, so the colour
+    anchor's in_mean (mean of the x2 bilinear upsample) is the mean of the packed plane: the kernels compute the latter."""
+    for i, (h, w) in enumerate(((16, 24), (8, 8), (5, 7), (32, 32))):
+        x = torch.from_numpy(synth.uniform(96 + i, "ml.mean", (2, 3, h, w), 0.0, 1.0)).double()
+        up = F.interpolate(x, size=(2 * h, 2 * w), mode="bilinear", align_corners=False)
+        assert float((up.mean(dim=(2, 3)) - x.mean(dim=(2, 3))).abs().max()) <= 1e-14
+        assert float((R.bilinear_resize(x, (2 * h, 2 * w)).mean(dim=(2, 3)) - x.mean(dim=(2, 3))).abs().max()) <= 1e-14
+
+
+def test_refusals_name_the_variant():
+    from bayer_low_light_image_enhancement_amd import tiling
+    from bayer_low_light_image_enhancement_amd.train import Trainer
+
+    m = RawFormer(dim=16, variant="multilvl")
+    x = torch.zeros(1, 1, 32, 32)
+    with pytest.raises(RuntimeError, match="multilvl"):
+        m.forward_window(x, 0, 16, 16)
+    with pytest.raises(RuntimeError, match="multilvl"):
+        Trainer(m)
+    with pytest.raises(RuntimeError, match="multilvl"):
+        tiling.forward_full_frame_exact(m, x)
+    with pytest.raises(RuntimeError, match="flca_levels"):
+        RawFormer(dim=16, variant="multilvl", flca_levels=4)
+
+
+# ------------------------------------------------------------------------------------------------ GPU
+@pytest.mark.gpu
+@pytest.mark.parametrize("tag,dim,levels,b,hh,ww,seed", CASES)
+def test_forward_matches_the_reference(device, tag, dim, levels, b, hh, ww, seed):
+    m = model(dim, device, levels)
+    x = torch.from_numpy(synth.bayer_mosaic(seed, b, hh, ww)).to(device)
+    with torch.no_grad():
+        out = m(x).cpu()
+    ref = torch.from_numpy(golden("multilvl")[f"{tag}.out"])
+    assert out.shape == ref.shape
+    err = float((out - ref).abs().max())
+    print(f"{tag}: max-abs error {err:.3e}")
+    assert err <= TOL, err
+
+
+@pytest.mark.gpu
+def test_forward_packed_equals_forward(device):
+    m = model(16, device)
+    x = torch.from_numpy(synth.bayer_mosaic(91, 2, 32, 48)).to(device)
+    with torch.no_grad():
+        assert torch.equal(m(x), m.forward_packed(R.pixel_unshuffle2(x).contiguous()))
+    assert m.workspace_bytes(2, 16, 24) > 0
+
+
+@pytest.mark.gpu
+def test_sampled_points_of_a_256_frame(device):
+    g = golden("multilvl")
+    m = model(32, device)
+    x = torch.from_numpy(synth.random_mosaic(94, 1, 256, 256)).to(device)
+    with torch.no_grad():
+        out = m(x)
+        again = m(x)
+    assert torch.equal(out, again)
+    got = out.reshape(-1)[torch.from_numpy(g["cfg1.idx"]).to(device)].cpu()
+    err = float((got - torch.from_numpy(g["cfg1.samples"])).abs().max())
+    merr = float((out.double().mean(dim=(0, 2, 3)).cpu().float() - torch.from_numpy(g["cfg1.chan_mean"])).abs().max())
+    print(f"cfg1: samples {err:.3e}, channel means {merr:.3e}")
+    assert err <= TOL
+    assert merr <= 2e-5
+
+
+@pytest.mark.gpu
+def test_larger_frame_fused_level0_and_composed_levels(device):
+    """dim 32, 2 x 1 x 256 x 384: several tiles per kernel and every U-Net level wider than one tile.  The fused step runs wherever
+    C <= 64: level 0 (C = 32, 128 x 192, stages 1 and 7) and level 1 (C = 64, stages 2 and 6), one launch per step.  Levels 2 and 3
+    (C = 128, 256; stages 3, 4, 5) run the composed path, here in its float4 form (widths 48 and 24)."""
+    x, ref = restated(32, 97, 2, 256, 384)
+    m = model(32, device)
+    with torch.no_grad():
+        out, n = launches(lambda: m(x.to(device)))
+    err = float((out.cpu() - ref).abs().max())
+    print(f"2x1x256x384: max-abs error {err:.3e}; launches {n.get('ml_step_fused_kernel')} fused, {n.get('ml_modulate_kernel')} modulate")
+    assert n.get("ml_step_fused_kernel") == 4 * 3 and n.get("ml_modulate_kernel") == 3 * 3     # stages 1, 2, 6, 7 | stages 3, 4, 5
+    assert n.get("tc_residual_kernel") == 3 and n.get("ml_residual_kernel") == 3 * 2            # pooling sums in a block's last step only
+    assert err <= TOL
+
+
+@pytest.mark.gpu
+def test_width_that_leaves_the_vector_path_at_level_2(device):
+    """Packed width 8 k with k odd (40): w % 4 == 0 at levels 0 and 1 (40, 20), not at levels 2 and 3 (10, 5).  One forward runs
+    the fused step at levels 0 and 1 (C = 32 and 64) and the composed path in its scalar form at levels 2 and 3."""
+    x, ref = restated(32, 98, 1, 64, 80)
+    m = model(32, device)
+    with torch.no_grad():
+        out, n = launches(lambda: m(x.to(device)))
+    err = float((out.cpu() - ref).abs().max())
+    print(f"1x1x64x80: max-abs error {err:.3e}; launches {n.get('ml_step_fused_kernel')} fused, {n.get('ml_modulate_kernel')} modulate")
+    assert n.get("ml_step_fused_kernel") == 4 * 3 and n.get("ml_modulate_kernel") == 3 * 3
+    assert err <= TOL
+
+
+# one forward, with whichever library RF_LIB_PATH names
+CODE = r'''
+import sys, numpy as np, torch
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
+from bayer_low_light_image_enhancement_amd import RawFormer, synth
+dim, seed, b, hm, wm = (int(v) for v in sys.argv[3:8])
+m = RawFormer(dim=dim, variant="multilvl")
+sd = m.state_dict()
+synth.fill_state_dict(sd, 5000 + dim)
+m.load_state_dict(sd, strict=True)
+m = m.to("cuda:0").eval()
+with torch.no_grad():
+    y = m(torch.from_numpy(synth.bayer_mosaic(seed, b, hm, wm)).to("cuda:0")).cpu().numpy()
+np.save(sys.argv[2], y)
+'''
+
+
+@pytest.mark.gpu
+def test_fused_step_against_the_composed_path_on_the_same_input(device, tmp_path):
+    """The same 2 x 1 x 256 x 384 forward with the shipped library (fused step at levels 0 and 1) and with the diagnostic twin
+    under RF_NO_ML_FUSED=1 (composed steps everywhere): each within TOL of the restatement, and not the same bits (the switch
+    took effect).  Between the two only the f32 summation order of the two 1x1 contractions differs: TOL again."""
+    from bayer_low_light_image_enhancement_amd import build
+
+    _, ref = restated(32, 97, 2, 256, 384)
+    got = {}
+    for tag, env in (("fused", {}), ("composed", {"RF_LIB_PATH": build.build_diag_library(), "RF_NO_ML_FUSED": "1"})):
+        e = dict(os.environ)
+        e.pop("RF_LIB_PATH", None)
+        e.update(env)
+        path = str(tmp_path / f"{tag}.npy")
+        r = subprocess.run([sys.executable, "-c", CODE, cases.REPO, path, "32", "97", "2", "256", "384"], env=e, capture_output=True,
+                           text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        got[tag] = torch.from_numpy(np.load(path))
+    e = {"fused vs restatement": float((got["fused"] - ref).abs().max()), "composed vs restatement": float((got["composed"] - ref).abs().max()),
+         "fused vs composed": float((got["fused"] - got["composed"]).abs().max())}
+    print(e)
+    assert max(e.values()) <= TOL, e
+    assert not torch.equal(got["fused"], got["composed"]), "the switch changed nothing"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("stage", (1, 4))
+def test_forward_stage(device, stage):
+    """One Conv_Transformer at U-Net level 0 (stage 1: C = 16, the fused step) and level 3 (stage 4: C = 128, composed, scalar) of a
+    32 x 48 packed frame: at level 3 the gate means are taken over 4 x 6 resized planes, not over the guidance size."""
+    dim, lvl = 16, stage - 1
+    sd = state(dim)
+    x4 = R.pixel_unshuffle2(torch.from_numpy(synth.bayer_mosaic(99, 2, 64, 96)))
+    xin = torch.from_numpy(synth.uniform(100 + stage, "ml.stage.x", (2, dim << lvl, 32 >> lvl, 48 >> lvl), -1.0, 1.0))
+    with torch.no_grad():
+        ref = multilvl_ref.stage(xin, R.bayer_luma_chroma(x4), sd, f"conv_tran{stage}.", 8)
+        out = model(dim, device, sd=sd).forward_stage(stage, xin.to(device), x4.to(device)).cpu()
+    err = float((out - ref).abs().max())
+    print(f"stage {stage}: max-abs error {err:.3e}")
+    assert err <= TOL
+
+
+@pytest.mark.gpu
+def test_output_corrections_closed_form(device):
+    """conv_out with zero weights and a constant bias: the output before the corrections is a known constant per channel, and the
+    result must be the colour anchor plus the luminance nudge computed on the host from the input alone (float64).  A wrong
+    out_mean or a wrong phase of the x8 bilinear sample of LL2 shows here at full size."""
+    dim, b, hh, ww = 16, 2, 64, 96
+    sd = state(dim)
+    bias = torch.tensor([0.3, -0.5, 0.2])
+    sd["conv_out.weight"].zero_()
+    sd["conv_out.bias"].copy_(bias.repeat_interleave(4))
+    x = torch.from_numpy(synth.bayer_mosaic(101, b, hh, ww))
+    with torch.no_grad():
+        out = model(dim, device, sd=sd)(x.to(device)).cpu().double()
+    x4 = R.pixel_unshuffle2(x).double()
+    const = F.leaky_relu(bias.double(), 0.2).view(1, 3, 1, 1)
+    rgb = torch.cat([x4[:, 0:1], 0.5 * (x4[:, 1:2] + x4[:, 2:3]), x4[:, 3:4]], dim=1)
+    in_mean = F.interpolate(rgb, size=(hh, ww), mode="bilinear", align_corners=False).mean(dim=(2, 3), keepdim=True)
+    anchored = const + 0.12 * (in_mean - const)                                   # [B,3,1,1]: out_mean is the constant itself
+    y = 0.299 * x4[:, 0:1] + 0.587 * 0.5 * (x4[:, 1:2] + x4[:, 2:3]) + 0.114 * x4[:, 3:4]
+    y = y / y.amax(dim=(2, 3), keepdim=True).clamp_min(1e-6)
+    ll2 = 4.0 * F.avg_pool2d(y, 4)                                                # two orthonormal Haar LL steps = (sum over 4x4) / 4
+    out_y = 0.299 * anchored[:, 0:1] + 0.587 * anchored[:, 1:2] + 0.114 * anchored[:, 2:3]
+    want = anchored + 0.03 * (F.interpolate(ll2, size=(hh, ww), mode="bilinear", align_corners=False) - out_y)
+    err = float((out - want).abs().max())
+    print(f"output corrections: max-abs error {err:.3e}")
+    assert err <= 5e-6
