@@ -108,6 +108,11 @@ SIGNATURES = {
     "rf_affine_clamp_add": (_i, [_vp, _vp, _vp, _sz, _f, _f, _f, _f, _vp]),
     "rf_upcat_scratch_bytes": (_i, [_i, _psz]),
     "rf_upcat": (_i, [_vp] * 8 + [_i, _i, _i, _i, _vp]),
+    "rf_mamba_chunk_len": (_i, []),
+    "rf_mamba_workspace_bytes": (C.c_longlong, [_i, _i, _i, _i, _i, _i]),
+    "rf_mamba_forward": (_i, [_vp, _vp, C.POINTER(_vp), _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "rf_wm_workspace_bytes": (C.c_longlong, [_i, _i, _i, _i]),
+    "rf_wm_forward": (_i, [_vp, _vp, C.POINTER(_vp), _vp, _sz, _i, _i, _i, _i, _vp]),
 }
 
 _lib = None

@@ -624,3 +624,85 @@ def wmb_ll_branch(x: torch.Tensor, params, prefix: str = "", high=None) -> torch
     with torch.cuda.device(x.device):
         _lib.check(_lib.load().rf_affine_clamp_add(_ptr(y), _ptr(t), _ptr(out), t.numel(), 0.5, 0.5, 0.0, 1.0, _stream(x)), "rf_affine_clamp_add")
     return out
+
+
+# ------------------------------------------------------------------------------------------ Mamba / WM / WMB
+_MAMBA_KEYS = ("in_proj.weight", "conv1d.weight", "conv1d.bias", "x_proj.weight", "dt_proj.weight", "dt_proj.bias", "A_log", "D",
+               "out_proj.weight")
+_WM_KEYS = (("convb.0.weight", "convb.0.bias", "convb.2.weight", "convb.2.bias", "ln.weight", "ln.bias")
+            + tuple("model1." + k for k in _MAMBA_KEYS) + ("smooth.weight", "smooth.bias"))
+
+
+def mamba_param_shapes(d_model: int, d_state: int = 32, d_conv: int = 4, expand: int = 2):
+    """state_dict names and shapes of ``mamba_ssm.modules.mamba_simple.Mamba(d_model, d_state, d_conv, expand)`` with the
+    module's defaults (``dt_rank='auto'`` = ceil(d_model / 16), no projection biases, conv1d bias)."""
+    di, r = expand * d_model, -(-d_model // 16)
+    return {"in_proj.weight": (2 * di, d_model), "conv1d.weight": (di, 1, d_conv), "conv1d.bias": (di,),
+            "x_proj.weight": (r + 2 * d_state, di), "dt_proj.weight": (di, r), "dt_proj.bias": (di,),
+            "A_log": (di, d_state), "D": (di,), "out_proj.weight": (d_model, di)}
+
+
+def _shaped(params, prefix, keys, shapes, what):
+    ts = []
+    for k in keys:
+        t = _chk(params[prefix + k], prefix + k)
+        if k in shapes and tuple(t.shape) != tuple(shapes[k]):
+            raise RuntimeError(f"{what}: {prefix + k} has shape {tuple(t.shape)}, expected {tuple(shapes[k])}")
+        ts.append(t)
+    return ts
+
+
+def _workspace(nbytes: int, what: str, like: torch.Tensor) -> torch.Tensor:
+    if nbytes < 0:
+        _lib.check(nbytes, what)
+    return _scratch(nbytes, like)
+
+
+def mamba(u: torch.Tensor, params, prefix: str = "", d_state: int = 32, d_conv: int = 4, expand: int = 2,
+          channel_major: bool = False) -> torch.Tensor:
+    """``Mamba(d_model, d_state, d_conv, expand)(u)`` (mamba_ssm, as RawFomer_WFB_FFAB/model.py:146-152 builds it), inference:
+    ``u`` and the result are ``[B, L, d_model]``, or ``[B, d_model, L]`` with ``channel_major=True`` (the layout of the other
+    operators here).  ``params`` maps the module's state_dict keys (``mamba_param_shapes``) to device tensors."""
+    u = _chk(u, "u")
+    if u.dim() != 3:
+        raise RuntimeError(f"mamba: expected a 3-D tensor, got {tuple(u.shape)}")
+    b, l, d = (u.shape[0], u.shape[2], u.shape[1]) if channel_major else tuple(u.shape)
+    ts = _shaped(params, prefix, _MAMBA_KEYS, mamba_param_shapes(d, d_state, d_conv, expand), "mamba")
+    lib = _lib.load()
+    ws = _workspace(lib.rf_mamba_workspace_bytes(b, l, d, d_state, d_conv, expand), "rf_mamba_workspace_bytes", u)
+    out = torch.empty_like(u)
+    with torch.cuda.device(u.device):
+        _lib.check(lib.rf_mamba_forward(_ptr(u), _ptr(out), _ptr_array(ts), _ptr(ws), ws.numel(), b, l, d, d_state, d_conv, expand,
+                                        int(channel_major), _stream(u)), "rf_mamba_forward")
+    return out
+
+
+def wm(x: torch.Tensor, params, prefix: str = "") -> torch.Tensor:
+    """``WM(c)(x)`` (RawFomer_WFB_FFAB/model.py:138-172) on ``[n, c, h, w]``: ``convb`` + residual, LayerNorm over the runs of ``c``
+    floats of the NCHW memory (the reference's raw ``reshape(b, -1, c)``), ``model1`` = ``Mamba(c, 32, 4, 2)``, ``smooth``.  Reads
+    ``convb.0/2.*``, ``ln.*``, ``model1.*``, ``smooth.*``; ``model2`` is constructed by the reference but never called."""
+    x = _chk(x, "x")
+    n, c, h, w = x.shape
+    shapes = {"model1." + k: v for k, v in mamba_param_shapes(c).items()}
+    shapes.update({"convb.0.weight": (2 * c, c, 3, 3), "convb.0.bias": (2 * c,), "convb.2.weight": (c, 2 * c, 3, 3), "convb.2.bias": (c,),
+                   "ln.weight": (c,), "ln.bias": (c,), "smooth.weight": (c, c, 3, 3), "smooth.bias": (c,)})
+    ts = _shaped(params, prefix, _WM_KEYS, shapes, "wm")
+    lib = _lib.load()
+    ws = _workspace(lib.rf_wm_workspace_bytes(n, c, h, w), "rf_wm_workspace_bytes", x)
+    out = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.rf_wm_forward(_ptr(x), _ptr(out), _ptr_array(ts), _ptr(ws), ws.numel(), n, c, h, w, _stream(x)), "rf_wm_forward")
+    return out
+
+
+def wmb(x: torch.Tensor, params, prefix: str = "") -> torch.Tensor:
+    """``WMB(dim)(x)`` (RawFomer_WFB_FFAB/model.py:203-245), eval mode: the wavelet branch with ``mb`` = ``WM`` on the three high
+    bands, then ``x + ffn(norm2(x))``."""
+    t = wmb_ll_branch(x, params, prefix, high=lambda hi: wm(hi, params, prefix + "mb."))
+    y = layernorm2d(t, params[prefix + "norm2.body.weight"], params.get(prefix + "norm2.body.bias"))
+    hid = wfb_feed_forward(y, params, prefix + "ffn.")          # ffn(y) + y: the operator carries FeedForward's own identity
+    out = torch.empty_like(t)
+    with torch.cuda.device(t.device):                           # out = t + hid (an unbounded clamp is the identity)
+        _lib.check(_lib.load().rf_affine_clamp_add(_ptr(hid), _ptr(t), _ptr(out), t.numel(), 1.0, 0.0, float("-inf"), float("inf"), _stream(t)),
+                   "rf_affine_clamp_add")
+    return out

@@ -326,6 +326,31 @@ int rf_dwgate3x3(const float* in, float* out, const float* wa, const float* ba, 
 /* nn.Conv2d(C, C, 5, padding=2, groups=C) (+bias): Illumination_Estimator.depth_conv (model.py:182-183) */
 int rf_dwconv5x5(const float* in, float* out, const float* weight, const float* bias, int B, int C, int h, int w, void* stream);
 
+/* ---- Mamba selective scan and the WM block (RawFomer_WFB_FFAB/model.py:138-172), inference only -------------------
+ * mamba_ssm.modules.mamba_simple.Mamba(d_model, d_state, d_conv, expand).forward with the module's defaults
+ * (dt_rank = ceil(d_model / 16), no projection biases, conv1d bias).  Di = expand * d_model, R = dt_rank.
+ * prm = HOST array of 9 device pointers: in_proj.weight [2Di,D], conv1d.weight [Di,1,4], conv1d.bias [Di],
+ * x_proj.weight [R+2N,Di], dt_proj.weight [Di,R], dt_proj.bias [Di], A_log [Di,N], D [Di], out_proj.weight [D,Di].
+ * Supported: d_state 32, d_conv 4, expand >= 1, d_model % 4 == 0, d_model <= 512, Di <= 4096, any B >= 1 and L >= 1;
+ * anything else is refused with a message (rf_last_error) before any launch.
+ * The scan over L runs in chunks of rf_mamba_chunk_len() tokens: every chunk's end state from a zero start in parallel,
+ * a short pass over the chunks in order, every chunk again from its incoming state.  No float atomics: two runs of one
+ * input give the same bits.
+ * rf_mamba_workspace_bytes: the workspace size in bytes (> 0), or a negative rf error code.
+ * rf_mamba_forward: channel_major = 0: in and out are [B,L,D] (the module's own layout); 1: [B,D,L], L contiguous (the
+ * layout of every other operator here).  in is not written; in, out and workspace are 16-byte aligned. */
+int rf_mamba_chunk_len(void);
+long long rf_mamba_workspace_bytes(int B, int L, int d_model, int d_state, int d_conv, int expand);
+int rf_mamba_forward(const float* in, float* out, const float* const* prm, void* workspace, size_t workspace_bytes,
+                     int B, int L, int d_model, int d_state, int d_conv, int expand, int channel_major, void* stream);
+/* WM.forward (model.py:165-172): x = convb(x) + x; tokens = LayerNorm_c(x.reshape(n, -1, c)) -- a RAW reshape of the NCHW
+ * memory: token i is the run flat[i c : (i + 1) c] of an image; y = Mamba(c, 32, 4, 2)(tokens), stored channel-major, which
+ * IS permute(0,2,1).reshape(n,c,h,w); out = smooth(y).  in, out [n,c,h,w].  prm = HOST array of 17 device pointers:
+ * convb.0.{weight,bias}, convb.2.{weight,bias}, ln.{weight,bias}, model1.<the 9 above>, smooth.{weight,bias}. */
+long long rf_wm_workspace_bytes(int n, int c, int h, int w);
+int rf_wm_forward(const float* in, float* out, const float* const* prm, void* workspace, size_t workspace_bytes,
+                  int n, int c, int h, int w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,7 @@ Each case runs through the C ABI (ops.*) with the library's own HIP-event bracke
 (rf_profile_begin/end), so the figure is the kernel's time on its launch stream, without the
 weight-repack helper that the operator-level entry points run first.
 
-usage: python tools/kbench.py [conv1x1] [conv3x3] [dw] [attn] [flca] [dwt] [ssim] [sampler] [mcr_sampler] [--dim 32] [--batch 8] [--size 512]
+usage: python tools/kbench.py [conv1x1] [conv3x3] [dw] [attn] [flca] [dwt] [ssim] [sampler] [mcr_sampler] [mamba] [--dim 32] [--batch 8] [--size 512]
 """
 from __future__ import annotations
 
@@ -109,6 +109,23 @@ def main():
         smp = PatchSampler(ResidentMCR(u8(nf, hh, ww), u8(nf, hh, ww, 3), [12287 / 255, 1023 / 255] * (nf // 2)), patch_size=512, seed=0)
         report(f"mcr_sample 16x512x512 of {nf}x{hh}x{ww}", timed(lambda: smp.batch(list(range(16)))))
         del smp
+    if "mamba" in a.what:   # ops.wm on the high bands of the headline batch (n = 3 x 8) at level 0 and level 3 of the WFB U-Net.  The scan rows'
+        # GB/s are algorithmic HBM bytes: mamba_scan_kernel<true> reads delta, x, z, Bm, Cm and writes y.  The chunk length is a build-time
+        # constant: compare libraries built with -DRF_MAMBA_LC=<n> through RF_LIB_PATH (the figure in use is printed).
+        print(f"rf_mamba_chunk_len() = {_lib.load().rf_mamba_chunk_len()}", flush=True)
+        for n, c, hw in ((24, 32, 256), (24, 256, 32)):
+            xw = r(n, c, hw, hw)
+            shapes = {"convb.0.weight": (2 * c, c, 3, 3), "convb.0.bias": (2 * c,), "convb.2.weight": (c, 2 * c, 3, 3), "convb.2.bias": (c,),
+                      "ln.weight": (c,), "ln.bias": (c,), "smooth.weight": (c, c, 3, 3), "smooth.bias": (c,)}
+            shapes.update({"model1." + k: v for k, v in ops.mamba_param_shapes(c).items()})
+            pw = {k: 0.1 * r(*v) for k, v in shapes.items()}
+            pw["model1.A_log"] = torch.log(torch.arange(1, 33, device=dev, dtype=torch.float32)).repeat(2 * c, 1).contiguous()
+            pw["model1.dt_proj.bias"] = torch.full((2 * c,), -4.0, device=dev)      # delta around 0.02
+            recs = timed(lambda: ops.wm(xw, pw))
+            report(f"wm n={n} c={c} {hw}x{hw}", recs)
+            print(f"wm n={n} c={c} {hw}x{hw}: {sum(q['ms'] for q in recs) / 10:.3f} ms per call "
+                  f"(sum of its kernels)", flush=True)
+            del xw, pw
     if "dwt" in a.what:
         x = r(B, d, S, S)
         report("dwt_init", timed(lambda: ops.dwt_init(x)))
