@@ -15,6 +15,9 @@ RF_VARIANT_FLCA = 0
 RF_VARIANT_PLAIN = 1
 RF_VARIANT_TRUECOLOR = 2
 RF_VARIANT_MULTILVL = 3
+RF_VARIANT_WFB = 4
+RF_PARAM_BUFFER = 1
+RF_PARAM_UNUSED = 2
 
 
 class RfConfig(C.Structure):
@@ -40,6 +43,7 @@ SIGNATURES = {
     "rf_destroy": (None, [_vp]),
     "rf_param_count": (_i, [_vp]),
     "rf_param_info": (_i, [_vp, _i, C.POINTER(C.c_char_p), C.POINTER(C.c_int64 * 4), C.POINTER(_i)]),
+    "rf_param_flags": (_i, [_vp, _i, C.POINTER(_i)]),
     "rf_set_param": (_i, [_vp, C.c_char_p, _vp, C.POINTER(C.c_int64), _i]),
     "rf_packed_bytes": (_i, [_vp, _psz]),
     "rf_pack_params": (_i, [_vp, _vp, _sz, _vp]),
@@ -113,6 +117,9 @@ SIGNATURES = {
     "rf_mamba_forward": (_i, [_vp, _vp, C.POINTER(_vp), _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "rf_wm_workspace_bytes": (C.c_longlong, [_i, _i, _i, _i]),
     "rf_wm_forward": (_i, [_vp, _vp, C.POINTER(_vp), _vp, _sz, _i, _i, _i, _i, _vp]),
+    "rf_wmb_front": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "rf_wmb_back": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "rf_wmb_ffn_sum": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
 }
 
 _lib = None

@@ -533,4 +533,28 @@ int pack_tail(const float* w_cr, const float* b_cr, const float* w2, const float
 int launch_tail_fold(const float* w_cr, const float* ch /* [B][C] gate or nullptr */, const float* composed, void* wp3_out, int B, int C, int hc,
                      hipStream_t st, float* wp_out = nullptr);
 
+// ---- FFAB and WM as the WFB handle calls them (rf_ffab.hip, rf_mamba.hip): the schedules of rf_ffab / rf_wm_forward.
+// prepacked: every 1x1 / 3x3 / projection weight pointer of `prm` already is the packed form (rf_pack_params), nothing is packed
+// per call.  WM's three projections need both forms, so those travel in WmPacked (prm keeps the raw pointers, unused then).
+size_t ffab_scratch_floats(int B, int nc, int h, int w);
+int ffab_forward(const float* in, float* out, const float* const* prm, bool prepacked, float* scratch, int B, int nc, int h, int w,
+                 hipStream_t st);
+struct WmPacked { const float *convb0, *convb2, *smooth, *in_proj, *x_proj, *out_proj; const void *in_proj3, *x_proj3, *out_proj3; };
+int wm_workspace_floats(const char* who, int n, int c, int h, int w, size_t* floats);
+int wm_forward(const float* in, float* out, const float* const* prm, const WmPacked* pk, float* ws, int n, int c, int h, int w,
+               hipStream_t st);
+int launch_dwgate3x3(const float* in, float* out, const float* wa, const float* ba, const float* wb, const float* bb, int B, int C, int h,
+                     int w, hipStream_t st);
+int launch_dwconv5x5(const float* in, float* out, const float* weight, const float* bias, int B, int C, int h, int w, hipStream_t st);
+
+// ---- the WMB block's own kernels and pack-time folds (rf_wmb.hip)
+int launch_wmb_front(const float* x, float* t, float* bands, const float* w2, const float* b2, int B, int C, int h, int w, hipStream_t st);
+int launch_wmb_back(const float* bands, const float* t, float* out, int B, int C, int h, int w, hipStream_t st);
+int launch_wmb_ffn_tail(const float* t, const float* y, float* out, const float* ln_w, const float* ln_b, int B, int C, int h, int w,
+                        hipStream_t st);
+// folds of one block, written once per parameter load: [2 w | 2 b - 1] of norm1 (2C floats); rep_conv1 + BN, rep_conv2 + BN and
+// the identity as one depthwise 3x3 weight [hid][9] and bias [hid]; illu.conv1 with the channel mean folded in, [C][C] row-major
+int launch_wmb_fold(const float* ln_w, const float* ln_b, float* ln2, const float* rep1_w, const float* const* bn1, const float* rep2_w,
+                    const float* const* bn2, float* rep_w, float* rep_b, const float* illu_w, float* illu_fold, int C, int hid, hipStream_t st);
+
 }  // namespace rf

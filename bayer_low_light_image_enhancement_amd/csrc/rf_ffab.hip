@@ -14,13 +14,14 @@ namespace rf {
 
 namespace {
 
-// one nn.Conv2d(cin, cout, 1) on [B, cin, P] planes with raw weights (packed on the fly into `wpack`)
+// one nn.Conv2d(cin, cout, 1) on [B, cin, P] planes with raw weights (packed on the fly into `wpack`); wpack == nullptr: `w`
+// already is the packed form (the WFB handle packs every weight once, rf_pack_params)
 int conv1x1_raw(const float* x, float* out, const float* w, const float* bias, const float* res, float* wpack, int B, int cin, int cout,
                 int P, int act, hipStream_t st) {
-    RF_TRY(pack_1x1(w, wpack, cout, cin, cin, 1, st));
+    if (wpack) RF_TRY(pack_1x1(w, wpack, cout, cin, cin, 1, st));
     Conv1x1Args a{};
     a.x1 = x; a.C1 = cin; a.x1_bstride = (int64_t)cin * P;
-    a.wp = wpack; a.bias = bias; a.res = res; a.res_bstride = (int64_t)cout * P;
+    a.wp = wpack ? wpack : w; a.bias = bias; a.res = res; a.res_bstride = (int64_t)cout * P;
     a.out = out; a.out_bstride = (int64_t)cout * P; a.Cout = cout; a.B = B; a.P = P; a.w = P; a.act = act;
     return launch_conv1x1(a, st);
 }
@@ -166,9 +167,25 @@ int rf_ffab(const float* in, float* out, const float* const* prm, void* scratch,
     RF_CHECK_ARG(in && out && prm && scratch && aligned16(scratch), "ffab: bad arguments");
     RF_TRY(check_geometry("ffab", B, nc, h, w));
     for (int i = 0; i < 92; ++i) RF_CHECK_ARG(prm[i] != nullptr, "ffab: parameter %d is null", i);
-    hipStream_t st = (hipStream_t)stream;
+    return ffab_forward(in, out, prm, false, (float*)scratch, B, nc, h, w, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+namespace rf {
+
+size_t ffab_scratch_floats(int B, int nc, int h, int w) {
     FfabPlan p;
-    ffab_plan((float*)scratch, p, B, nc, h, w);
+    ffab_plan(nullptr, p, B, nc, h, w);
+    return p.total;
+}
+
+int ffab_forward(const float* in, float* out, const float* const* prm, bool prepacked, float* scratch, int B, int nc, int h, int w,
+                 hipStream_t st) {
+    RF_TRY(check_geometry("ffab", B, nc, h, w));
+    FfabPlan p;
+    ffab_plan(scratch, p, B, nc, h, w);
+    if (prepacked) p.wpack2 = p.f.wpack = nullptr;
     const int P = h * w;
     const size_t per = (size_t)nc * P;
     // state_dict order: conv0.0.{w,b}, conv0.1.<12>, conv1.<12>, conv2.<12>, conv3.<12>, conv4.0.<12>, conv4.1.{w,b},
@@ -193,4 +210,4 @@ int rf_ffab(const float* in, float* out, const float* const* prm, void* scratch,
     return tail(p.x, p.x5, convout, out);
 }
 
-}  // extern "C"
+}  // namespace rf

@@ -20,6 +20,7 @@ struct Param {
     int64_t shape[4];
     int ndim;
     const float* ptr;
+    int flags = 0;                    // RF_PARAM_BUFFER | RF_PARAM_UNUSED (rawformer_hip.h)
     int pack = -1, pack3 = -1;        // packs[] entries of its packed and its b3 form (rf_pack_params), -1: none
     size_t cache[PF_COUNT];           // floats into the training pack cache per PackForm, kNotCached: not held
     size_t numel() const {
@@ -58,6 +59,16 @@ struct MlIx {        // FLCA_Pyramid branch of a stage: low_attn.<l>.0 / high_at
 struct BayerProcIx { int wb_gains, color_matrix, dm0_w, dm0_b, dm2_w, dm2_b, ce0_w, ce0_b, ce2_w, ce2_b; };   // bayer_processor.*: demosaic_refine.0 / .2, chroma_extractor.0 / .2
 struct ColorCorrIx { int gamma, ct0_w, ct0_b, ct2_w, ct2_b, tone0_w, tone0_b, tone2_w, tone2_b; };             // color_correction.*: color_transform.0 / .2, tone_curve.0 / .2
 
+// registry indices of a WMB block (RF_VARIANT_WFB, RawFomer_WFB_FFAB/model.py:203-245); bn = weight, bias, running_mean, running_var
+struct WmbIx {
+    int ln1_w, ln1_b, illu1_w, illu1_b, illu_dw_w, illu_dw_b;
+    int ffab[92];                     // rf_ffab's order (= state_dict order)
+    int ln2_w, ln2_b, rep1_w, bn1[4], rep2_w, bn2[4], pin_w, pin_b, dw_w, dw_b, pout_w, pout_b;
+    int wm[17];                       // rf_wm_forward's order: convb.0, convb.2, ln, model1.<9>, smooth
+    int hid;                          // FeedForward's hidden width
+    size_t fold = 0, illu_pk = 0;     // floats into the packed buffer: launch_wmb_fold's outputs [ln2 | rep_w | rep_b | illu_fold], packed illu.conv1
+};
+
 // registry indices of one Conv_Transformer stage (add_stage)
 struct StageIx {
     int lvl;         // U-Net level: channels dim << lvl, size H >> lvl
@@ -69,6 +80,7 @@ struct StageIx {
     rf::FlcaGroup<int> flca;            // FLCA branch
     TcIx tc;                          // TrueColor branch
     MlIx ml;                          // multi-level FLCA branch
+    WmbIx wmb;                        // WFB: the WMB block in place of the TransformerBlock
     // composed tail (rf_flca.hip pack_tail), floats into the packed buffer of [Wb W2 | b'] (0 = not composed) and, plain variant
     // only, of the static b3 weights [Wa | Wb | Wb W2]
     size_t tail_offset = 0, tail3_offset = 0;
@@ -145,6 +157,16 @@ struct rf_handle {
         return {prm(x.alpha), prm(x.beta), prm(x.gamma), prm(x.w_low), prm(x.w_high), prm(x.w_chr), se_prm(x.se)};
     }
 };
+
+// rf_wmb.hip: one WMB block of the WFB variant.  Buffers (U = B C h w floats of the stage's activation, f = ffn_expansion):
+// t U, bands U, illu and fea U / 4 each, hid and gated f U each, ffab / wm = ffab_scratch_floats / wm_workspace_floats of the
+// half-resolution bands.  pack_wmb writes the block's folds (wmb_fold_floats at WmbIx::fold) and the packed illu.conv1.
+namespace rf {
+struct WmbBufs { float *t, *bands, *illu, *fea, *hid, *gated, *ffab, *wm; };
+size_t wmb_fold_floats(int C, int hid);
+int pack_wmb(rf_handle* h, int stage, float* base, hipStream_t st);
+int run_wmb(const rf_handle* h, int stage, const float* in, float* out, const WmbBufs& b, int B, int hh, int ww, hipStream_t st);
+}  // namespace rf
 
 // rf_trainstep.hip: lay out the flat buffers, the gradient ranges and the pack cache (rf_create, once the registry is complete)
 void plan_training(rf_handle* h);

@@ -327,9 +327,12 @@ static int mamba_plan(const char* who, int B, int L, int D, int N, int K, int E,
     return RF_OK;
 }
 
+// w == nullptr: wp and wp3 already hold the packed forms (the WFB handle's, rf_pack_params) and are only read
 static int mamba_gemm(const float* x, int K, const float* w, float* wp, float* wp3, float* out, int Cout, int B, int L, hipStream_t st) {
-    RF_TRY(pack_1x1(w, wp, Cout, K, K, 1, st));
-    RF_TRY(pack_1x1_b3(w, wp3, Cout, K, K, 1, st));
+    if (w) {
+        RF_TRY(pack_1x1(w, wp, Cout, K, K, 1, st));
+        RF_TRY(pack_1x1_b3(w, wp3, Cout, K, K, 1, st));
+    }
     Conv1x1Args a{};
     a.x1 = x; a.C1 = K; a.x1_bstride = (int64_t)K * L; a.wp = wp; a.wp3 = wp3; a.ln_eps = 1e-5f;
     a.out = out; a.out_bstride = (int64_t)Cout * L; a.Cout = Cout; a.B = B; a.P = L; a.w = L;
@@ -347,12 +350,17 @@ static int launch_tok_transpose(const float* in, const float* add, float* out, c
 }
 
 // channel-major Mamba: u, out [B][D][L]; ws = the plan's buffers.  prm: the nine tensors in the header's order.
-static int run_mamba(const MambaPlan& p, const float* u, float* out, const float* const* prm, float* ws, int B, int L, hipStream_t st) {
+static int run_mamba(const MambaPlan& p, const float* u, float* out, const float* const* prm, float* ws, int B, int L, hipStream_t st,
+                     const WmPacked* pk = nullptr) {
     const float *w_in = prm[0], *w_conv = prm[1], *b_conv = prm[2], *w_x = prm[3], *w_dt = prm[4], *b_dt = prm[5], *A_log = prm[6], *Dp = prm[7],
                 *w_out = prm[8];
     const int D = p.D, Di = p.Di;
     float *xz = ws + p.xz, *xc = ws + p.xc, *dbc = ws + p.dbc, *delta = ws + p.delta;
-    RF_TRY(mamba_gemm(u, D, w_in, ws + p.w_in, ws + p.w_in3, xz, 2 * Di, B, L, st));
+    auto gemm = [&](const float* x, int K, const float* w, size_t o, size_t o3, const float* pw, const void* pw3, float* dst, int Cout) {
+        if (pk) return mamba_gemm(x, K, nullptr, const_cast<float*>(pw), static_cast<float*>(const_cast<void*>(pw3)), dst, Cout, B, L, st);
+        return mamba_gemm(x, K, w, ws + o, ws + o3, dst, Cout, B, L, st);
+    };
+    RF_TRY(gemm(u, D, w_in, p.w_in, p.w_in3, pk ? pk->in_proj : nullptr, pk ? pk->in_proj3 : nullptr, xz, 2 * Di));
     const double el = (double)B * Di * L;
     {
         const size_t total = (size_t)B * Di * L;
@@ -362,7 +370,7 @@ static int run_mamba(const MambaPlan& p, const float* u, float* out, const float
         mamba_conv_kernel<<<dim3((unsigned)gx), 256, 0, st>>>(xz, xc, w_conv, b_conv, Di, L, total);
         RF_TRY(check_launch("mamba_conv"));
     }
-    RF_TRY(mamba_gemm(xc, Di, w_x, ws + p.w_x, ws + p.w_x3, dbc, p.NR, B, L, st));
+    RF_TRY(gemm(xc, Di, w_x, p.w_x, p.w_x3, pk ? pk->x_proj : nullptr, pk ? pk->x_proj3 : nullptr, dbc, p.NR));
     {
         ProfScope prof(st, "mamba_delta_kernel", 2.0 * p.R * el, 4.0 * el + 4.0 * B * p.R * (double)L);
         mamba_delta_kernel<<<dim3((unsigned)cdiv(L, 256), (unsigned)(Di / 4), (unsigned)B), 256, 0, st>>>(dbc, delta, w_dt, b_dt, Di, p.R, p.NR, L);
@@ -390,7 +398,7 @@ static int run_mamba(const MambaPlan& p, const float* u, float* out, const float
         mamba_scan_kernel<true><<<dim3((unsigned)p.nchunk, (unsigned)cdiv(Di, 64), (unsigned)B), 64, 0, st>>>(a);
         RF_TRY(check_launch("mamba_scan<true>"));
     }
-    return mamba_gemm(delta, Di, w_out, ws + p.w_out, ws + p.w_out3, out, D, B, L, st);
+    return gemm(delta, Di, w_out, p.w_out, p.w_out3, pk ? pk->out_proj : nullptr, pk ? pk->out_proj3 : nullptr, out, D);
 }
 
 struct WmPlan {
@@ -415,9 +423,10 @@ static int wm_plan(const char* who, int n, int c, int h, int w, WmPlan* p) {
     return RF_OK;
 }
 
-static int wm_conv(const float* x, const float* wgt, float* wp, const float* bias, float* out, int act, int n, int cin, int cout, int h, int w,
+// wgt == nullptr: wp already holds the packed weight
+static int wm_conv(const float* x, const float* wgt, const float* wp, const float* bias, float* out, int act, int n, int cin, int cout, int h, int w,
                    hipStream_t st) {
-    RF_TRY(pack_3x3(wgt, wp, cout, cin, st));
+    if (wgt) RF_TRY(pack_3x3(wgt, const_cast<float*>(wp), cout, cin, st));
     Conv3x3Args a{};
     a.x = x; a.x_bstride = (int64_t)cin * h * w; a.wp = wp; a.bias = bias; a.out = out; a.out_bstride = (int64_t)cout * h * w;
     a.B = n; a.Cin = cin; a.Cout = cout; a.h = h; a.w = w; a.act = act;
@@ -479,16 +488,32 @@ int rf_wm_forward(const float* in, float* out, const float* const* prm, void* wo
         return RF_E_NOMEM;
     }
     for (int i = 0; i < 17; ++i) RF_CHECK_ARG(prm[i] != nullptr, "rf_wm_forward: parameter %d is null", i);
-    hipStream_t st = (hipStream_t)stream;
-    float* ws = (float*)workspace;
-    float *t1 = ws + p.t1, *t2 = ws + p.t2;
-    const int L = h * w;
-    RF_TRY(wm_conv(in, prm[0], ws + p.w0, prm[1], t1, 2 /* ReLU */, n, c, 2 * c, h, w, st));
-    RF_TRY(wm_conv(t1, prm[2], ws + p.w2, prm[3], t2, 0, n, 2 * c, c, h, w, st));
-    // tokens = LayerNorm((convb(x) + x) as runs of c floats), stored channel-major over t1, which is dead by now
-    RF_TRY(launch_tok_transpose(t2, in, t1, prm[4], prm[5], n, L, c, st));
-    RF_TRY(run_mamba(p.m, t1, t2, prm + 6, ws, n, L, st));           // [n][c][L] = permute(0,2,1).reshape(n,c,h,w)
-    return wm_conv(t2, prm[15], ws + p.ws_, prm[16], out, 0, n, c, c, h, w, st);
+    return wm_forward(in, out, prm, nullptr, (float*)workspace, n, c, h, w, (hipStream_t)stream);
 }
 
 }  // extern "C"
+
+namespace rf {
+
+int wm_workspace_floats(const char* who, int n, int c, int h, int w, size_t* floats) {
+    WmPlan p;
+    RF_TRY(wm_plan(who, n, c, h, w, &p));
+    *floats = p.floats;
+    return RF_OK;
+}
+
+int wm_forward(const float* in, float* out, const float* const* prm, const WmPacked* pk, float* ws, int n, int c, int h, int w,
+               hipStream_t st) {
+    WmPlan p;
+    RF_TRY(wm_plan("wm_forward", n, c, h, w, &p));
+    float *t1 = ws + p.t1, *t2 = ws + p.t2;
+    const int L = h * w;
+    RF_TRY(wm_conv(in, pk ? nullptr : prm[0], pk ? pk->convb0 : ws + p.w0, prm[1], t1, 2 /* ReLU */, n, c, 2 * c, h, w, st));
+    RF_TRY(wm_conv(t1, pk ? nullptr : prm[2], pk ? pk->convb2 : ws + p.w2, prm[3], t2, 0, n, 2 * c, c, h, w, st));
+    // tokens = LayerNorm((convb(x) + x) as runs of c floats), stored channel-major over t1, which is dead by now
+    RF_TRY(launch_tok_transpose(t2, in, t1, prm[4], prm[5], n, L, c, st));
+    RF_TRY(run_mamba(p.m, t1, t2, prm + 6, ws, n, L, st, pk));       // [n][c][L] = permute(0,2,1).reshape(n,c,h,w)
+    return wm_conv(t2, pk ? nullptr : prm[15], pk ? pk->smooth : ws + p.ws_, prm[16], out, 0, n, c, c, h, w, st);
+}
+
+}  // namespace rf

@@ -47,8 +47,122 @@ void add_pack(rf_handle* h, int pi, PackKind kind) {
 // (run_stage decides per call: the fused kernel takes only some image sizes).
 bool tail_composable(int C, int hc) { return C % 32 == 0 && hc % 32 == 0 && hc > 0; }
 
+int add_flagged(rf_handle* h, const std::string& name, std::initializer_list<int64_t> shape, int flags) {
+    const int ix = add_param(h, name, shape);
+    h->params[ix].flags = flags;
+    return ix;
+}
+
+// mamba_ssm's Mamba(d, 32, 4, expand) in the order of rf_mamba_forward's pointer array (ops.mamba_param_shapes); the package is
+// not available to pin the order of these keys inside the module's state_dict
+void add_mamba(rf_handle* h, const std::string& q, int d, int expand, int flags, int* ix) {
+    const int di = expand * d, r = cdiv(d, 16);
+    ix[0] = add_flagged(h, q + "in_proj.weight", {2 * di, d}, flags);
+    ix[1] = add_flagged(h, q + "conv1d.weight", {di, 1, 4}, flags);
+    ix[2] = add_flagged(h, q + "conv1d.bias", {di}, flags);
+    ix[3] = add_flagged(h, q + "x_proj.weight", {r + 64, di}, flags);
+    ix[4] = add_flagged(h, q + "dt_proj.weight", {di, r}, flags);
+    ix[5] = add_flagged(h, q + "dt_proj.bias", {di}, flags);
+    ix[6] = add_flagged(h, q + "A_log", {di, 32}, flags);
+    ix[7] = add_flagged(h, q + "D", {di}, flags);
+    ix[8] = add_flagged(h, q + "out_proj.weight", {d, di}, flags);
+}
+
+// Conv_Transformer of RawFomer_WFB_FFAB/model.py:414-433 with WMB (model.py:203-245) as its Transformer, state_dict order.  Every
+// GEMM and 3x3 weight is packed once (rf_pack_params); illu.conv2 and mb.model2 are registered and never read.
+void add_stage_wfb(rf_handle* h, int i, int lvl) {
+    const rf_config& cfg = h->cfg;
+    const int C = cfg.dim << lvl, hid = C * cfg.ffn_expansion;
+    StageIx& s = h->stage[i];
+    s.lvl = lvl;
+    s.first = (int)h->params.size();
+    const std::string pre = "conv_tran" + std::to_string(i) + ".", t = pre + "Transformer.";
+    WmbIx& m = s.wmb;
+    m.hid = hid;
+    s.conv_w = add_param(h, pre + "conv.weight", {C, C, 3, 3});
+    s.conv_b = add_param(h, pre + "conv.bias", {C});
+    add_pack(h, s.conv_w, PK_3x3);
+    m.ln1_w = add_param(h, t + "norm1.body.weight", {C});
+    m.ln1_b = add_param(h, t + "norm1.body.bias", {C});
+    m.illu1_w = add_param(h, t + "illu.conv1.weight", {C, C + 1, 1, 1});
+    m.illu1_b = add_param(h, t + "illu.conv1.bias", {C});
+    m.illu_dw_w = add_param(h, t + "illu.depth_conv.weight", {C, 1, 5, 5});
+    m.illu_dw_b = add_param(h, t + "illu.depth_conv.bias", {C});
+    add_flagged(h, t + "illu.conv2.weight", {C, C, 1, 1}, RF_PARAM_UNUSED);
+    add_flagged(h, t + "illu.conv2.bias", {C}, RF_PARAM_UNUSED);
+    int* f = m.ffab;
+    auto conv = [&](const std::string& q, int cout, int cin) {
+        *f = add_param(h, q + ".weight", {cout, cin, 1, 1});
+        add_pack(h, *f++, PK_1x1);
+        *f++ = add_param(h, q + ".bias", {cout});
+    };
+    auto block = [&](const std::string& q, int n) {      // ProcessBlock(n): FEB, then cat
+        for (const char* name : {"frequency_process.fpre", "frequency_process.process1.0", "frequency_process.process1.2",
+                                 "frequency_process.process2.0", "frequency_process.process2.2", "cat"})
+            conv(q + name, n, n);
+    };
+    const std::string fb = t + "ffab.";
+    conv(fb + "conv0.0", C, C);
+    block(fb + "conv0.1.", C);
+    for (const char* name : {"conv1.", "conv2.", "conv3."}) block(fb + name, C);
+    for (const char* name : {"conv4", "conv5", "convout"}) {
+        block(fb + name + ".0.", 2 * C);
+        conv(fb + name + ".1", C, 2 * C);
+    }
+    m.ln2_w = add_param(h, t + "norm2.body.weight", {C});
+    m.ln2_b = add_param(h, t + "norm2.body.bias", {C});
+    auto conv_bn = [&](const std::string& q, int k, int& w, int* bn) {
+        w = add_param(h, q + "c.weight", {hid, 1, k, k});
+        bn[0] = add_param(h, q + "bn.weight", {hid});
+        bn[1] = add_param(h, q + "bn.bias", {hid});
+        bn[2] = add_flagged(h, q + "bn.running_mean", {hid}, RF_PARAM_BUFFER);
+        bn[3] = add_flagged(h, q + "bn.running_var", {hid}, RF_PARAM_BUFFER);
+    };
+    conv_bn(t + "ffn.rep_conv1.", 3, m.rep1_w, m.bn1);
+    conv_bn(t + "ffn.rep_conv2.", 1, m.rep2_w, m.bn2);
+    m.pin_w = add_param(h, t + "ffn.project_in.weight", {hid, C, 1, 1});
+    m.pin_b = add_param(h, t + "ffn.project_in.bias", {hid});
+    m.dw_w = add_param(h, t + "ffn.dwconv.weight", {hid, 1, 3, 3});
+    m.dw_b = add_param(h, t + "ffn.dwconv.bias", {hid});
+    m.pout_w = add_param(h, t + "ffn.project_out.weight", {C, hid, 1, 1});
+    m.pout_b = add_param(h, t + "ffn.project_out.bias", {C});
+    for (int w : {m.pin_w, m.pout_w}) {
+        add_pack(h, w, PK_1x1);
+        add_pack(h, w, PK_1x1_B3);
+    }
+    const std::string mb = t + "mb.";
+    m.wm[0] = add_param(h, mb + "convb.0.weight", {2 * C, C, 3, 3});
+    m.wm[1] = add_param(h, mb + "convb.0.bias", {2 * C});
+    m.wm[2] = add_param(h, mb + "convb.2.weight", {C, 2 * C, 3, 3});
+    m.wm[3] = add_param(h, mb + "convb.2.bias", {C});
+    add_mamba(h, mb + "model1.", C, 2, 0, m.wm + 6);
+    int unused[9];
+    add_mamba(h, mb + "model2.", C, 9, RF_PARAM_UNUSED, unused);
+    m.wm[15] = add_param(h, mb + "smooth.weight", {C, C, 3, 3});
+    m.wm[16] = add_param(h, mb + "smooth.bias", {C});
+    m.wm[4] = add_param(h, mb + "ln.weight", {C});
+    m.wm[5] = add_param(h, mb + "ln.bias", {C});
+    for (int w : {m.wm[0], m.wm[2], m.wm[15]}) add_pack(h, w, PK_3x3);
+    for (int w : {m.wm[6], m.wm[9], m.wm[14]}) {
+        add_pack(h, w, PK_1x1);
+        add_pack(h, w, PK_1x1_B3);
+    }
+    m.fold = h->packed_floats;
+    h->packed_floats += wmb_fold_floats(C, hid);
+    m.illu_pk = h->packed_floats;
+    h->packed_floats += align_up(packed1x1_floats(C, C), 64);
+    s.cr_w = add_param(h, pre + "channel_reduce.weight", {C, 2 * C, 1, 1});
+    s.cr_b = add_param(h, pre + "channel_reduce.bias", {C});
+    s.out_w = add_param(h, pre + "Conv_out.weight", {C, C, 3, 3});
+    s.out_b = add_param(h, pre + "Conv_out.bias", {C});
+    add_pack(h, s.cr_w, PK_1x1);
+    add_pack(h, s.cr_w, PK_1x1_B3);
+    add_pack(h, s.out_w, PK_3x3);
+}
+
 void add_stage(rf_handle* h, int i, int lvl) {
     const rf_config& cfg = h->cfg;
+    if (cfg.variant == RF_VARIANT_WFB) return add_stage_wfb(h, i, lvl);
     const int C = cfg.dim << lvl;
     StageIx& s = h->stage[i];
     s.lvl = lvl;
@@ -165,6 +279,7 @@ struct Plan {
     size_t total;
     size_t gscratch, guide[4], skip[3], tA, tB, tU, bufA, bufB, x1, trans, xs, cr;
     size_t gram_partial, wfold_attn, wfold_cr, wfold_attn3, wfold_cr3, flca_partial, ch;
+    size_t ffab, wm;            // WFB: FFAB scratch and WM workspace at their largest level, shared by the stages
     size_t ks, ks_floats;       // scratch of the 3x3 convs' input-channel split (small frames only: ks_floats = 0 otherwise)
     int guide_planes;
 };
@@ -192,7 +307,22 @@ int make_plan(const rf_handle* h, int B, int H, int W, Plan& p) {
     p.xs = b.off(U0);
     p.cr = b.off(U0);
     size_t gp = 0, wa = 0, wc = 0, fp = 0, wa3 = 0, wc3 = 0;
-    for (int l = 0; l < 4; ++l) {
+    const bool wfb = c.variant == RF_VARIANT_WFB;      // no channel attention and no fold: `heads` is not read
+    p.ffab = p.wm = 0;
+    if (wfb) {
+        size_t ff = 0, wf = 0;
+        for (int l = 0; l < 4; ++l) {
+            const int C = c.dim << l, h2 = (H >> l) / 2, w2 = (W >> l) / 2;
+            size_t f;
+            RF_TRY(wm_workspace_floats("rf_workspace_bytes", 3 * B, C, h2, w2, &f));
+            if (f > wf) wf = f;
+            f = ffab_scratch_floats(B, C, h2, w2);
+            if (f > ff) ff = f;
+        }
+        p.ffab = b.off(ff);
+        p.wm = b.off(wf);
+    }
+    for (int l = 0; l < 4 && !wfb; ++l) {
         const int C = c.dim << l, Pl = (H >> l) * (W >> l);
         int ns, sl;
         size_t pf;
@@ -239,10 +369,56 @@ int make_plan(const rf_handle* h, int B, int H, int W, Plan& p) {
     return RF_OK;
 }
 
+// one Conv_Transformer stage of the WFB variant: the plain variant's wiring around a WMB block (rf_wmb.hip)
+int run_stage_wfb(rf_handle* h, int i, const float* in, float* out, float* ws, const Plan& p, int B, int H, int W, hipStream_t st,
+                  hipStream_t side) {
+    const StageIx& x = h->stage[i];
+    const int lvl = x.lvl, C = h->cfg.dim << lvl, hh = H >> lvl, ww = W >> lvl, Pn = hh * ww;
+    const size_t U = (size_t)B * C * Pn;
+    float *trans = ws + p.trans, *xs = ws + p.xs, *crb = ws + p.cr;
+    RF_TRY(h->side.fork(st, side));
+    Conv3x3Args cb{};
+    cb.x = in; cb.x_bstride = (int64_t)C * Pn; cb.wp = h->pk(x.conv_w); cb.bias = h->prm(x.conv_b);
+    cb.out = xs; cb.out_bstride = (int64_t)C * Pn; cb.B = B; cb.Cin = C; cb.Cout = C; cb.h = hh; cb.w = ww; cb.act = 1;
+    RF_TRY(launch_conv3x3(cb, side));
+    // t in the x1 slot, the bands in tU (idle inside a stage), the quarter-size illumination tensors at the head of bufA until
+    // project_in writes the hidden tensor there
+    const WmbBufs wb{ws + p.x1, ws + p.tU, ws + p.bufA, ws + p.bufA + U, ws + p.bufA, ws + p.bufB, ws + p.ffab, ws + p.wm};
+    RF_TRY(run_wmb(h, i, in, trans, wb, B, hh, ww, st));
+    RF_TRY(h->side.join(st, side));
+    Conv1x1Args r{};
+    r.x1 = xs; r.C1 = C; r.x1_bstride = (int64_t)C * Pn;
+    r.x2 = trans; r.C2 = C; r.x2_bstride = (int64_t)C * Pn;
+    r.wp = h->pk(x.cr_w); r.wp3 = h->pk3(x.cr_w); r.bias = h->prm(x.cr_b);
+    r.out = crb; r.out_bstride = (int64_t)C * Pn; r.Cout = C; r.B = B; r.P = Pn; r.w = ww;
+    RF_TRY(launch_conv1x1(r, st));
+    Conv3x3Args co{};
+    co.x = crb; co.x_bstride = (int64_t)C * Pn; co.wp = h->pk(x.out_w); co.bias = h->prm(x.out_b);
+    co.out = out; co.out_bstride = (int64_t)C * Pn; co.B = B; co.Cin = C; co.Cout = C; co.h = hh; co.w = ww; co.act = 1;
+    if (p.ks_floats) { co.ks_scratch = ws + p.ks; co.ks_floats = p.ks_floats; }
+    return launch_conv3x3(co, st);
+}
+
+// Sizes the WFB variant admits (packed H x W), checked before any launch.  Level 3 works on H/8 x W/8 and its LL band on
+// H/16 x W/16: the DWT needs even sizes there, FFAB at least 2 rows and an even width, the vector kernels widths in multiples of 4.
+// The FFT of the level-0 LL band (H/2 x W/2) has rf_fft.hip's line limits; every lower level halves them.
+int wfb_check_size(const char* who, int H, int W) {
+    RF_CHECK_ARG(H % 16 == 0, "%s: variant wfb: packed height %d must be a multiple of 16 (the Haar DWT at U-Net level 3)", who, H);
+    RF_CHECK_ARG(H >= 32, "%s: variant wfb: packed height %d must be at least 32 (FFAB needs 2 rows of the level-3 LL band)", who, H);
+    RF_CHECK_ARG(W % 32 == 0, "%s: variant wfb: packed width %d must be a multiple of 32 (an even level-3 LL band for FFAB's rfft2)", who, W);
+    for (int n : {H / 2, W / 2}) {
+        RF_CHECK_ARG(n <= 4096, "%s: variant wfb: a line of %d samples in the level-0 LL band exceeds the FFT's 4096", who, n);
+        RF_CHECK_ARG((n & (n - 1)) == 0 || n <= 2048, "%s: variant wfb: a line of %d samples in the level-0 LL band is no power of two and exceeds 2048",
+                     who, n);
+    }
+    return RF_OK;
+}
+
 // one Conv_Transformer stage
 int run_stage(rf_handle* h, int i, const float* in, float* out, float* ws, const Plan& p,
               int B, int H, int W, hipStream_t st, hipStream_t side) {
     const rf_config& cfg = h->cfg;
+    if (cfg.variant == RF_VARIANT_WFB) return run_stage_wfb(h, i, in, out, ws, p, B, H, W, st, side);
     const StageIx& x = h->stage[i];
     const int lvl = x.lvl, C = cfg.dim << lvl, hh = H >> lvl, ww = W >> lvl, Pn = hh * ww, heads = cfg.heads[lvl];
     const int hc = C * cfg.ffn_expansion;
@@ -480,13 +656,18 @@ int rf_create(const rf_config* cfg, rf_handle** out) {
     RF_CHECK_ARG(cfg->inp_channels == 1, "rf_create: inp_channels=%d (only the 1-channel Bayer mosaic is supported)", cfg->inp_channels);
     RF_CHECK_ARG(cfg->out_channels > 0 && cfg->ffn_expansion > 0, "rf_create: bad out_channels / ffn_expansion");
     RF_CHECK_ARG(cfg->variant == RF_VARIANT_FLCA || cfg->variant == RF_VARIANT_PLAIN || cfg->variant == RF_VARIANT_TRUECOLOR ||
-                     cfg->variant == RF_VARIANT_MULTILVL,
+                     cfg->variant == RF_VARIANT_MULTILVL || cfg->variant == RF_VARIANT_WFB,
                  "rf_create: unknown variant %d", cfg->variant);
+    const bool wfb = cfg->variant == RF_VARIANT_WFB;
+    RF_CHECK_ARG(!wfb || (cfg->clamp_io && cfg->branch_lrelu), "rf_create: variant wfb always clamps its input and output and applies the "
+                 "LeakyReLU on the conv branch (clamp_io = branch_lrelu = 1)");
+    RF_CHECK_ARG(!wfb || cfg->dim * 8 <= 512, "rf_create: variant wfb: dim * 8 = %d channels at level 3 exceed the 512 of the Mamba token LayerNorm",
+                 cfg->dim * 8);
     RF_CHECK_ARG(cfg->flca_levels >= 0 && cfg->flca_levels <= 3, "rf_create: flca_levels=%d (1..3, 0 = default 2)", cfg->flca_levels);
     RF_CHECK_ARG(cfg->variant != RF_VARIANT_TRUECOLOR || cfg->out_channels == 3, "rf_create: the TrueColor colour head is defined for 3 output channels");
     RF_CHECK_ARG(cfg->variant != RF_VARIANT_MULTILVL || (cfg->out_channels == 3 && !cfg->clamp_io),
                  "rf_create: the multilvl output corrections are defined for 3 output channels and no clamp_io");
-    for (int l = 0; l < 4; ++l) {
+    for (int l = 0; l < 4 && !wfb; ++l) {
         const int C = cfg->dim << l;
         RF_CHECK_ARG(cfg->heads[l] > 0 && C % cfg->heads[l] == 0 && C / cfg->heads[l] <= 64,
                      "rf_create: heads[%d]=%d incompatible with %d channels (head size must divide and be <= 64)", l, cfg->heads[l], C);
@@ -570,6 +751,12 @@ int rf_param_info(const rf_handle* h, int index, const char** name, int64_t shap
     return RF_OK;
 }
 
+int rf_param_flags(const rf_handle* h, int index, int* flags) {
+    RF_CHECK_ARG(h && flags && index >= 0 && index < (int)h->params.size(), "rf_param_flags: index %d out of range", index);
+    *flags = h->params[index].flags;
+    return RF_OK;
+}
+
 int rf_set_param(rf_handle* h, const char* name, const float* dev_ptr, const int64_t* shape, int ndim) {
     RF_CHECK_ARG(h && name && dev_ptr, "rf_set_param: null argument");
     auto it = h->index.find(name);
@@ -578,6 +765,7 @@ int rf_set_param(rf_handle* h, const char* name, const float* dev_ptr, const int
         return RF_E_MISSING;
     }
     Param& p = h->params[it->second];
+    RF_CHECK_ARG(!(p.flags & RF_PARAM_UNUSED), "rf_set_param: %s is never read by the forward and takes no pointer", name);
     size_t n = 1;
     for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
     bool same = n == p.numel();
@@ -607,7 +795,7 @@ int rf_pack_params(rf_handle* h, void* packed_dev, size_t bytes, void* stream) {
         return RF_E_NOMEM;
     }
     for (const Param& p : h->params)
-        if (!p.ptr) {
+        if (!p.ptr && !(p.flags & RF_PARAM_UNUSED)) {
             set_error("rf_pack_params: missing key '%s'", p.name.c_str());
             return RF_E_MISSING;
         }
@@ -634,12 +822,19 @@ int rf_pack_params(rf_handle* h, void* packed_dev, size_t bytes, void* stream) {
         if (x.tail3_offset) RF_TRY(launch_tail_fold(h->prm(x.cr_w), nullptr, composed, base + x.tail3_offset, 1, C, hc, st));
     }
     h->packed = base;
+    if (h->cfg.variant == RF_VARIANT_WFB)
+        for (int i = 1; i <= 7; ++i)
+            if (int rc = pack_wmb(h, i, base, st)) {
+                h->packed = nullptr;
+                return rc;
+            }
     return RF_OK;
 }
 
 int rf_workspace_bytes(const rf_handle* h, int B, int H, int W, size_t* bytes) {
     RF_CHECK_ARG(h && bytes, "rf_workspace_bytes: null argument");
     RF_CHECK_ARG(B > 0 && H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0, "packed size %dx%d must be positive multiples of 8 (mosaic divisible by 16)", H, W);
+    if (h->cfg.variant == RF_VARIANT_WFB) RF_TRY(wfb_check_size("rf_workspace_bytes", H, W));
     Plan p;
     RF_TRY(make_plan(h, B, H, W, p));
     *bytes = p.total * sizeof(float);
@@ -690,6 +885,7 @@ int rf_forward_stage(rf_handle* h, int stage, const float* in, const float* pack
     RF_CHECK_ARG((h->cfg.variant != RF_VARIANT_FLCA && h->cfg.variant != RF_VARIANT_MULTILVL) || packed,
                  "rf_forward_stage: the FLCA branch needs the packed frame for its guidance");
     RF_CHECK_ARG(h->cfg.variant != RF_VARIANT_TRUECOLOR, "rf_forward_stage: not available for the TrueColor variant");
+    if (h->cfg.variant == RF_VARIANT_WFB) RF_TRY(wfb_check_size("rf_forward_stage", H, W));
     if (!h->packed) {
         set_error("rf_forward_stage: parameters not packed (call rf_pack_params after rf_set_param)");
         return RF_E_MISSING;
@@ -723,6 +919,7 @@ int rf_forward(rf_handle* h, const float* in, float* out, void* workspace, size_
     RF_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0,
                  "rf_forward: packed size %dx%d must be positive multiples of 8 (mosaic divisible by 16)", H, W);
     RF_CHECK_ARG((size_t)H * W < (1u << 30), "rf_forward: frame too large");
+    if (h->cfg.variant == RF_VARIANT_WFB) RF_TRY(wfb_check_size("rf_forward", H, W));
     RF_CHECK_ARG(!h->shard_allreduce || h->shard_y_hi <= H, "rf_forward: shard interior [%d, %d) outside the %d-row window",
                  h->shard_y_lo, h->shard_y_hi, H);
     RF_CHECK_ARG(!h->shard_allreduce || h->shard_x_hi == W || (h->shard_x_hi < W && h->shard_x_hi % 32 == 0),

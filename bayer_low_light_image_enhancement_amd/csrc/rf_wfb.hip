@@ -143,16 +143,9 @@ __global__ void __launch_bounds__(kBlk) dwconv5x5_kernel(const float* __restrict
     }
 }
 
-}  // namespace rf
-
-using namespace rf;
-
-extern "C" {
-
-int rf_dwgate3x3(const float* in, float* out, const float* wa, const float* ba, const float* wb, const float* bb,
-                 int B, int C, int h, int w, void* stream) {
+int launch_dwgate3x3(const float* in, float* out, const float* wa, const float* ba, const float* wb, const float* bb, int B, int C, int h,
+                     int w, hipStream_t st) {
     RF_CHECK_ARG(in && out && wa && wb && B > 0 && C > 0 && h > 0 && w > 0, "dwgate3x3: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
     const int vec = (w % 4 == 0) && aligned16(in) && aligned16(out);
     const size_t items = (size_t)B * C * cdiv(h, 4) * cdiv(w, 4);
     size_t gx = (items + kBlk - 1) / kBlk;
@@ -163,9 +156,8 @@ int rf_dwgate3x3(const float* in, float* out, const float* wa, const float* ba, 
     return check_launch("dwgate3x3");
 }
 
-int rf_dwconv5x5(const float* in, float* out, const float* weight, const float* bias, int B, int C, int h, int w, void* stream) {
+int launch_dwconv5x5(const float* in, float* out, const float* weight, const float* bias, int B, int C, int h, int w, hipStream_t st) {
     RF_CHECK_ARG(in && out && weight && B > 0 && C > 0 && h > 0 && w > 0, "dwconv5x5: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
     const size_t items = (size_t)B * C * cdiv(h, 2) * cdiv(w, 4);
     size_t gx = (items + kBlk - 1) / kBlk;
     if (gx > 8192) gx = 8192;
@@ -173,6 +165,21 @@ int rf_dwconv5x5(const float* in, float* out, const float* weight, const float* 
     ProfScope prof(st, "dwconv5x5_kernel", 50.0 * el, 8.0 * el);
     dwconv5x5_kernel<<<dim3((unsigned)gx), kBlk, 0, st>>>(in, out, weight, bias, B, C, h, w);
     return check_launch("dwconv5x5");
+}
+
+}  // namespace rf
+
+using namespace rf;
+
+extern "C" {
+
+int rf_dwgate3x3(const float* in, float* out, const float* wa, const float* ba, const float* wb, const float* bb,
+                 int B, int C, int h, int w, void* stream) {
+    return launch_dwgate3x3(in, out, wa, ba, wb, bb, B, C, h, w, (hipStream_t)stream);
+}
+
+int rf_dwconv5x5(const float* in, float* out, const float* weight, const float* bias, int B, int C, int h, int w, void* stream) {
+    return launch_dwconv5x5(in, out, weight, bias, B, C, h, w, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -19,6 +19,9 @@ or model.py:94-108 (``False``) and, with ``clamp_io=True``, adds the I/O clamps 
 RawFomer_WFB_FFAB/model.py:475,508.  ``variant='multilvl'`` is the ``RawFormer`` of
 MultiLvlFrequencyawareLumaChromaAttentionRAWFormer.py:313-416 (``FLCA_Pyramid`` branches with ``flca_levels`` pyramid
 levels, per-channel colour anchor and luminance nudge on the output); forward and evaluation only.
+``variant='wfb'`` is the whole ``RawFormer`` of RawFomer_WFB_FFAB/model.py:437-508: the plain stage wiring (conv branch with
+LeakyReLU, I/O clamps) around a ``WMB`` block per stage (LayerNorm, Haar DWT, ``Illumination_Estimator`` + ``FFAB`` on the LL band,
+``WM`` / Mamba on the high bands, IWT, gated ``FeedForward`` with BatchNorm); eval mode, forward and evaluation only.
 
 The module owns ordinary ``nn.Parameter`` objects; the HIP library borrows their device
 pointers.  There is no PyTorch fallback: on a CPU tensor ``forward`` raises.
@@ -86,7 +89,7 @@ def canonical_key(key: str) -> str:
 
 
 _VARIANTS = {"flca": _lib.RF_VARIANT_FLCA, "plain": _lib.RF_VARIANT_PLAIN, "truecolor": _lib.RF_VARIANT_TRUECOLOR,
-             "multilvl": _lib.RF_VARIANT_MULTILVL}
+             "multilvl": _lib.RF_VARIANT_MULTILVL, "wfb": _lib.RF_VARIANT_WFB}
 
 
 class _Node(nn.Module):
@@ -108,7 +111,7 @@ class _DeviceState:
 class RawFormer(nn.Module):
     def __init__(self, inp_channels: int = 1, out_channels: int = 3, dim: int = 48,
                  num_heads: Sequence[int] = (8, 8, 8, 8), ffn_expansion_factor: int = 2, *,
-                 variant: str = "flca", branch_lrelu: bool = True, clamp_io: bool = False, flca_levels: int = 2,
+                 variant: str = "flca", branch_lrelu: bool = True, clamp_io: Optional[bool] = None, flca_levels: int = 2,
                  in_ch: Optional[int] = None, out_ch: Optional[int] = None,
                  heads: Optional[Sequence[int]] = None, ffn_exp: Optional[int] = None):
         super().__init__()
@@ -117,9 +120,18 @@ class RawFormer(nn.Module):
         num_heads = list(heads if heads is not None else num_heads)
         ffn_expansion_factor = ffn_exp if ffn_exp is not None else ffn_expansion_factor
         if variant not in _VARIANTS:
-            raise ValueError(f"variant must be 'flca', 'plain', 'truecolor' or 'multilvl', got {variant!r}")
+            raise ValueError(f"variant must be 'flca', 'plain', 'truecolor', 'multilvl' or 'wfb', got {variant!r}")
         if len(num_heads) != 4:
             raise ValueError("num_heads must have 4 entries")
+        if variant == "wfb":
+            # the reference model clamps its input and output and applies the LeakyReLU unconditionally (model.py:428,475,508)
+            if clamp_io is False or not branch_lrelu:
+                raise ValueError("variant='wfb' always applies the input / output clamps and the LeakyReLU on the conv branch: "
+                                 "clamp_io=False and branch_lrelu=False are not available")
+            if int(ffn_expansion_factor) != ffn_expansion_factor:
+                raise ValueError(f"variant='wfb': ffn_expansion_factor must be a whole number, got {ffn_expansion_factor!r}")
+            clamp_io = True
+        clamp_io = bool(clamp_io)
         self.dim, self.inp_channels, self.out_channels = int(dim), int(inp_channels), int(out_channels)
         self.num_heads, self.ffn_expansion_factor = [int(h) for h in num_heads], int(ffn_expansion_factor)
         self.variant, self.branch_lrelu, self.clamp_io = variant, bool(branch_lrelu), bool(clamp_io)
@@ -130,13 +142,25 @@ class RawFormer(nn.Module):
         probe = C.c_void_p()
         _lib.check(lib.rf_create(C.byref(cfg), C.byref(probe)), "rf_create")
         try:
+            # _param_names: every tensor the handle borrows (parameters and, for 'wfb', the BatchNorm statistics, which are
+            # module buffers); entries the reference registers and its forward never reads stay out of it
             self._param_names: List[str] = []
-            name, shape, ndim = C.c_char_p(), (C.c_int64 * 4)(), C.c_int()
+            self._buffer_names: List[str] = []
+            name, shape, ndim, flags = C.c_char_p(), (C.c_int64 * 4)(), C.c_int(), C.c_int()
             for i in range(lib.rf_param_count(probe)):
                 _lib.check(lib.rf_param_info(probe, i, C.byref(name), C.byref(shape), C.byref(ndim)), "rf_param_info")
-                key = name.value.decode()
-                self._param_names.append(key)
-                self._register(key, nn.Parameter(torch.empty(tuple(shape[: ndim.value]), dtype=torch.float32)))
+                _lib.check(lib.rf_param_flags(probe, i, C.byref(flags)), "rf_param_flags")
+                key, shp = name.value.decode(), tuple(shape[: ndim.value])
+                if flags.value & _lib.RF_PARAM_BUFFER:
+                    self._param_names.append(key)
+                    self._buffer_names.append(key)
+                    self._register_buffer(key, torch.ones(shp) if key.endswith("running_var") else torch.zeros(shp))
+                    if key.endswith("running_var"):      # nn.BatchNorm2d's third buffer follows it in the state_dict
+                        self._register_buffer(key[: -len("running_var")] + "num_batches_tracked", torch.tensor(0, dtype=torch.int64))
+                    continue
+                if not flags.value & _lib.RF_PARAM_UNUSED:
+                    self._param_names.append(key)
+                self._register(key, nn.Parameter(torch.empty(shp, dtype=torch.float32)))
         finally:
             lib.rf_destroy(probe)
         if variant in ("flca", "truecolor", "multilvl"):
@@ -197,6 +221,12 @@ class RawFormer(nn.Module):
                 p.copy_(torch.eye(3, 4))
             elif leaf == "gamma_param":
                 p.fill_(2.2)
+            elif leaf == "A_log":                              # mamba_ssm's initial values: A = 1 .. d_state per row, D = 1
+                p.copy_(torch.log(torch.arange(1, p.shape[1] + 1, dtype=torch.float32)).repeat(p.shape[0], 1))
+            elif leaf == "D":
+                p.fill_(1.0)
+            elif key.endswith((".bn.bias", ".ln.bias")):       # BatchNorm2d / nn.LayerNorm shifts
+                p.zero_()
             elif p.dim() == 1:
                 if leaf == "weight":
                     p.fill_(1.0)                      # LayerNorm scale
@@ -273,6 +303,9 @@ class RawFormer(nn.Module):
         needs the pointers -- registered once as long as they do not move -- and leaves the packed copies stale (the next
         inference forward repacks: ``signature`` stays ``None``)."""
         params = dict(self.named_parameters())
+        if self._buffer_names:      # 'wfb': the BatchNorm running statistics take part in the fold, so also in the signature
+            buffers = dict(self.named_buffers())
+            params.update({k: buffers[k] for k in self._buffer_names if k in buffers})
         if len(params) < len(self._param_names):
             # nn.DataParallel replicas carry their weights as plain tensors, not Parameters (train.py:108-111 is the
             # reference's only multi-device construct); this package shards across PROCESSES instead (tiling.py)
@@ -313,6 +346,7 @@ class RawFormer(nn.Module):
             raise RuntimeError("RawFormer.forward (HIP) is the inference path and builds no autograd graph: call model.eval() or wrap "
                                "in torch.no_grad(); to train use bayer_low_light_image_enhancement_amd.train.Trainer(model).step(x, gt) "
                                "(rf_train_step: forward, loss, explicit backward, Adam / AdamW)")
+        self._refuse_training_mode()
         x = x.detach()
         if x.dtype != torch.float32:
             x = x.float()
@@ -346,6 +380,11 @@ class RawFormer(nn.Module):
                                       C.c_void_p(st.workspace.data_ptr()), st.workspace.numel(), b, H, W,
                                       int(packed_input), stream), "rf_forward")
         return out
+
+    def _refuse_training_mode(self) -> None:
+        if self.variant == "wfb" and self.training:
+            raise RuntimeError("RawFormer(variant='wfb') is inference only: in training mode its BatchNorm layers are a different "
+                               "function (batch statistics); call model.eval()")
 
     def forward_window(self, x: torch.Tensor, y_lo: int, y_hi: int, total_rows: int, group=None, *,
                        x_lo: int = 0, x_hi: int = 0, total_cols: Optional[int] = None) -> torch.Tensor:
@@ -416,6 +455,7 @@ class RawFormer(nn.Module):
         (``variant='flca'`` and ``'multilvl'``; for ``'plain'`` pass ``None`` and H, W are taken from ``x``)."""
         if x.device.type != "cuda":
             raise RuntimeError("RawFormer (HIP) needs a ROCm device tensor: there is no CPU path in this package")
+        self._refuse_training_mode()
         lvl = stage - 1 if stage <= 4 else 7 - stage
         x = x.detach().float().contiguous()
         b, c, hh, ww = x.shape

@@ -706,3 +706,44 @@ def wmb(x: torch.Tensor, params, prefix: str = "") -> torch.Tensor:
         _lib.check(_lib.load().rf_affine_clamp_add(_ptr(hid), _ptr(t), _ptr(out), t.numel(), 1.0, 0.0, float("-inf"), float("inf"), _stream(t)),
                    "rf_affine_clamp_add")
     return out
+
+
+# ------------------------------------------------------------------------------------------ the fused passes of the WFB handle's WMB block
+def wmb_front(x: torch.Tensor, weight2: torch.Tensor, bias2: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``t = LayerNorm_c(x) * weight2 + bias2`` per pixel and ``dwt_init(t)`` in one pass (csrc/rf_wmb.hip); with ``weight2 = 2 w``,
+    ``bias2 = 2 b - 1`` that is ``data_transform(norm1(x))`` and its four bands (WMB.forward, model.py:221-225).
+    ``x`` [B,C,2h,2w] with 2w % 4 == 0 -> (t [B,C,2h,2w], bands [4B,C,h,w])."""
+    x, weight2, bias2 = _chk(x, "x"), _chk(weight2, "weight2"), _chk(bias2, "bias2")
+    b, c, h2, w2 = x.shape
+    if h2 % 2 or w2 % 4 or weight2.numel() != c or bias2.numel() != c:
+        raise RuntimeError(f"wmb_front: needs an even height, a width in multiples of 4 and {c} LayerNorm weights (got {h2}x{w2})")
+    t, bands = torch.empty_like(x), torch.empty((4 * b, c, h2 // 2, w2 // 2), dtype=x.dtype, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().rf_wmb_front(_ptr(x), _ptr(t), _ptr(bands), _ptr(weight2), _ptr(bias2), b, c, h2 // 2, w2 // 2, _stream(x)),
+                   "rf_wmb_front")
+    return t, bands
+
+
+def wmb_back(bands: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+    """``t + clamp((iwt_init(bands) + 1) / 2, 0, 1)`` in one pass (WMB.forward, model.py:239-243)."""
+    bands, t = _chk(bands, "bands"), _chk(t, "t")
+    b4, c, h, w = bands.shape
+    if b4 % 4 or w % 2 or tuple(t.shape) != (b4 // 4, c, 2 * h, 2 * w):
+        raise RuntimeError(f"wmb_back: bands {tuple(bands.shape)} and t {tuple(t.shape)} do not belong together (band width must be even)")
+    out = torch.empty_like(t)
+    with torch.cuda.device(t.device):
+        _lib.check(_lib.load().rf_wmb_back(_ptr(bands), _ptr(t), _ptr(out), b4 // 4, c, h, w, _stream(t)), "rf_wmb_back")
+    return out
+
+
+def wmb_ffn_tail(t: torch.Tensor, y: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """``t + y + LayerNorm_c(t)``: the end of ``x + ffn(norm2(x))`` with ``y = project_out(..)``, FeedForward's identity
+    ``norm2(x)`` recomputed per pixel instead of stored (model.py:58-65, 244)."""
+    t, y, weight, bias = _chk(t, "t"), _chk(y, "y"), _chk(weight, "weight"), _chk(bias, "bias")
+    b, c, h, w = t.shape
+    if w % 4 or tuple(y.shape) != tuple(t.shape) or weight.numel() != c or bias.numel() != c:
+        raise RuntimeError(f"wmb_ffn_tail: t {tuple(t.shape)}, y {tuple(y.shape)}: equal shapes and a width in multiples of 4 are needed")
+    out = torch.empty_like(t)
+    with torch.cuda.device(t.device):
+        _lib.check(_lib.load().rf_wmb_ffn_sum(_ptr(t), _ptr(y), _ptr(out), _ptr(weight), _ptr(bias), b, c, h, w, _stream(t)), "rf_wmb_ffn_sum")
+    return out

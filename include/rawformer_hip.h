@@ -43,6 +43,11 @@ extern "C" {
 #define RF_VARIANT_MULTILVL 3  /* MultiLvlFrequencyawareLumaChromaAttentionRAWFormer.py:313-416: FLCA_Pyramid branch (gated
                                   progressive residuals over the Haar pyramid of the luma), per-channel colour anchor and
                                   luminance nudge towards the 2-level LL after the PixelShuffle; forward only */
+#define RF_VARIANT_WFB 4       /* RawFomer_WFB_FFAB/model.py:437-508: the plain variant's stage (conv branch + LeakyReLU, I/O
+                                  clamps) with WMB (model.py:203-245) as its Transformer: LayerNorm, Haar DWT,
+                                  Illumination_Estimator + FFAB on the LL band, WM / Mamba on the high bands, IWT, gated
+                                  FeedForward with BatchNorm (eval mode).  `heads` is not read; hidden = dim * ffn_expansion.
+                                  Packed H % 16 == 0, H >= 32, W % 32 == 0, dim * 8 <= 512; forward only */
 
 typedef struct rf_handle rf_handle;
 
@@ -76,6 +81,12 @@ void rf_destroy(rf_handle* h);
 int rf_param_count(const rf_handle* h);
 int rf_param_info(const rf_handle* h, int index, const char** name, int64_t shape[4], int* ndim);
 int rf_set_param(rf_handle* h, const char* name, const float* dev_ptr, const int64_t* shape, int ndim);
+/* What kind of state_dict entry a registry slot is: RF_PARAM_BUFFER = a float32 module buffer (BatchNorm running statistics),
+ * not an nn.Parameter; RF_PARAM_UNUSED = the reference registers the tensor and its forward never reads it (RF_VARIANT_WFB:
+ * illu.conv2.*, mb.model2.*): it keeps its place in the key order, takes no pointer and rf_set_param refuses it. */
+#define RF_PARAM_BUFFER 1
+#define RF_PARAM_UNUSED 2
+int rf_param_flags(const rf_handle* h, int index, int* flags);
 /* Repack the registered weights into MFMA operand order inside caller memory.  Call again
  * whenever a parameter tensor changed. */
 int rf_packed_bytes(const rf_handle* h, size_t* bytes);
@@ -350,6 +361,19 @@ int rf_mamba_forward(const float* in, float* out, const float* const* prm, void*
 long long rf_wm_workspace_bytes(int n, int c, int h, int w);
 int rf_wm_forward(const float* in, float* out, const float* const* prm, void* workspace, size_t workspace_bytes,
                   int n, int c, int h, int w, void* stream);
+
+
+/* ---- the three fused element-wise kernels of a WMB block as RF_VARIANT_WFB schedules it (csrc/rf_wmb.hip) ----------
+ * All tensors NCHW float32, 16-byte aligned, the full-resolution width a multiple of 4 and the height even; 4 <= C <= 512.
+ * rf_wmb_front: t = (x - mean_c) * rstd_c * w2[c] + b2[c] per pixel (w2 = 2 norm1.weight, b2 = 2 norm1.bias - 1, i.e.
+ * data_transform(norm1(x))) and bands = dwt_init(t) in dwt_init's own expression order: x, t [B,C,2h,2w], bands [4B,C,h,w].
+ * rf_wmb_back: out = t + clamp((iwt_init(bands) + 1) / 2, 0, 1).
+ * rf_wmb_ffn_sum: out = t + y + LayerNorm_c(t; ln_w, ln_b), the tail of x + ffn(norm2(x)) with y = project_out(..):
+ * t, y, out [B,C,h,w] (w % 4 == 0). */
+int rf_wmb_front(const float* x, float* t, float* bands, const float* w2, const float* b2, int B, int C, int h, int w, void* stream);
+int rf_wmb_back(const float* bands, const float* t, float* out, int B, int C, int h, int w, void* stream);
+int rf_wmb_ffn_sum(const float* t, const float* y, float* out, const float* ln_w, const float* ln_b, int B, int C, int h, int w,
+                    void* stream);
 
 #ifdef __cplusplus
 }

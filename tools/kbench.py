@@ -5,7 +5,7 @@ Each case runs through the C ABI (ops.*) with the library's own HIP-event bracke
 (rf_profile_begin/end), so the figure is the kernel's time on its launch stream, without the
 weight-repack helper that the operator-level entry points run first.
 
-usage: python tools/kbench.py [conv1x1] [conv3x3] [dw] [attn] [flca] [dwt] [ssim] [sampler] [mcr_sampler] [mamba] [--dim 32] [--batch 8] [--size 512]
+usage: python tools/kbench.py [conv1x1] [conv3x3] [dw] [attn] [flca] [dwt] [ssim] [sampler] [mcr_sampler] [mamba] [wfb] [--dim 32] [--batch 8] [--size 512]
 """
 from __future__ import annotations
 
@@ -126,6 +126,56 @@ def main():
             print(f"wm n={n} c={c} {hw}x{hw}: {sum(q['ms'] for q in recs) / 10:.3f} ms per call "
                   f"(sum of its kernels)", flush=True)
             del xw, pw
+    if "wfb" in a.what:   # one forward of RawFormer(variant='wfb') at --dim on a --size mosaic, batch 1 and --batch: the handle (weights folded
+        # and packed once, fused front / back / tail passes) against the same forward composed from ops.* (every call folds and packs
+        # its own weights).  HIP-event brackets around `iters` forwards, both orders in one visit; then the handle's per-kernel table
+        # (one stream while profiling) and the share of WM's 3x3 convolutions, from ops.wm at every level's shape.
+        sys.path.insert(0, os.path.join(REPO, "tests"))
+        import wfb_ref
+        from bayer_low_light_image_enhancement_amd import RawFormer
+        m = RawFormer(dim=d, variant="wfb").to(dev).eval()
+        pw = {k: v for k, v in m.state_dict().items() if v.dtype.is_floating_point}
+
+        def event_ms(fn, iters=10, warm=2):
+            for _ in range(warm):
+                fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / iters
+
+        for bb in (1, B):
+            xm = torch.rand(bb, 1, S, S, device=dev)
+            with torch.no_grad():
+                handle, composed = (lambda: m(xm)), (lambda: wfb_ref.ops_forward(pw, xm))
+                t = [event_ms(handle), event_ms(composed), event_ms(composed), event_ms(handle)]
+                print(f"wfb dim {d} mosaic {bb}x{S}x{S}: handle {t[0]:.3f} / {t[3]:.3f} ms, composed from ops.* {t[1]:.3f} / {t[2]:.3f} ms per forward "
+                      f"(order: handle, composed, composed, handle); handle / composed = {(t[0] + t[3]) / (t[1] + t[2]):.3f}", flush=True)
+                recs = timed(handle)
+            total = sum(q["ms"] for q in recs)
+            print(f"wfb handle {bb}x{S}x{S}: {sum(q['launches'] for q in recs) // 10} kernel launches per forward", flush=True)
+            for q in sorted(recs, key=lambda q: -q["ms"]):      # per forward: launches, total time and share, then the per-launch figures
+                print(f"wfb handle {bb}x{S}x{S}  {q['kernel']:40s} {q['launches'] // 10:5d} launches {q['ms'] / 10:8.3f} ms {100 * q['ms'] / total:5.1f} %  "
+                      f"{q['ms'] / q['launches'] * 1e3:8.1f} us each  {q['bytes'] / max(q['ms'], 1e-9) / 1e6:8.1f} GB/s", flush=True)
+            print(f"wfb handle {bb}x{S}x{S}: {total / 10:.3f} ms per forward as the sum of its kernels on one stream", flush=True)
+            wm_ms, wm_conv = 0.0, 0.0
+            for lvl in range(4):
+                c, hw = d << lvl, (S // 2 >> lvl) // 2
+                pre = f"conv_tran{lvl + 1}.Transformer.mb."
+                sub = {k[len(pre):]: v for k, v in pw.items() if k.startswith(pre)}
+                xw = r(3 * bb, c, hw, hw)
+                rw = timed(lambda: ops.wm(xw, sub))
+                ms, cv = sum(q["ms"] for q in rw) / 10, sum(q["ms"] for q in rw if "conv3x3" in q["kernel"]) / 10
+                n_stage = 1 if lvl == 3 else 2
+                wm_ms, wm_conv = wm_ms + n_stage * ms, wm_conv + n_stage * cv
+                print(f"  wm level {lvl} n={3 * bb} c={c} {hw}x{hw}: {ms:.3f} ms, 3x3 convolutions {cv:.3f} ms ({100 * cv / ms:.0f} %)", flush=True)
+            print(f"wfb {bb}x{S}x{S}: WM over the 7 stages {wm_ms:.3f} ms = {100 * wm_ms / (total / 10):.0f} % of the forward's kernel time; "
+                  f"its 3x3 convolutions {wm_conv:.3f} ms = {100 * wm_conv / wm_ms:.0f} % of WM", flush=True)
+            del xm
     if "dwt" in a.what:
         x = r(B, d, S, S)
         report("dwt_init", timed(lambda: ops.dwt_init(x)))
