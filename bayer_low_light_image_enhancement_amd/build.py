@@ -21,7 +21,7 @@ LIB = os.path.join(CSRC, "librawformer_hip.so")
 # The shipped library has no such switch.  Selected with RF_LIB_PATH (see _lib.py).
 DIAG_LIB = os.path.join(CSRC, "librawformer_hip_diag.so")
 DIAG_SOURCES = ["rf_block.hip", "rf_model.hip", "rf_gemm1x1.hip", "rf_fused.hip"]
-SOURCES = ["rf_api.hip", "rf_model.hip", "rf_pack.hip", "rf_pointwise.hip", "rf_gemm1x1.hip",
+SOURCES = ["rf_api.hip", "rf_registry.hip", "rf_model.hip", "rf_pack.hip", "rf_pointwise.hip", "rf_gemm1x1.hip",
            "rf_conv3x3.hip", "rf_attn.hip", "rf_flca.hip", "rf_fused.hip", "rf_fused_tail.hip", "rf_block.hip", "rf_harness.hip", "rf_ssim.hip", "rf_tokattn.hip", "rf_wfb.hip", "rf_upcat.hip", "rf_fft.hip", "rf_ffab.hip", "rf_truecolor.hip", "rf_multilvl.hip", "rf_train.hip", "rf_trainstep.hip", "rf_sampler.hip", "rf_mamba.hip", "rf_wmb.hip"]
 # every header a source may include: ONE list for the product and the diagnostic objects (a stale *_diag.o linked with fresh
 # product objects would disagree on struct rf_handle)

@@ -207,6 +207,13 @@ struct Conv1x1Args {
     int act;               // 0 none, 1 LeakyReLU(0.2), 2 ReLU, 3 LeakyReLU(0.1), 4 clamp to [0, 1e4] (FEB, blocks.py:14-30)
 };
 int launch_conv1x1(const Conv1x1Args& a, hipStream_t st);
+// one dense NCHW source and a dense destination (batch strides C1 P / Cout P); everything else zero
+inline Conv1x1Args conv1x1_dense(const float* x1, int C1, const float* wp, const void* wp3, const float* bias, float* out, int Cout, int B, int P, int w) {
+    Conv1x1Args a{};
+    a.x1 = x1; a.C1 = C1; a.x1_bstride = (int64_t)C1 * P; a.wp = wp; a.wp3 = wp3; a.bias = bias;
+    a.out = out; a.out_bstride = (int64_t)Cout * P; a.Cout = Cout; a.B = B; a.P = P; a.w = w;
+    return a;
+}
 // Workgroup id -> (unit, grp) for `ngroups` workgroups per unit that read the same input (conv1x1_b3_kernel's paired form: a unit
 // is one pixel tile of one image, a group one pair of output groups).  The hardware deals consecutive ids round-robin over the 8
 // XCDs (one L2 each), so the groups of a unit get ids 8 apart: the same XCD, one after the other in its dispatch order, and the
@@ -243,6 +250,13 @@ struct Conv3x3Args {
     size_t ks_floats = 0;
 };
 int launch_conv3x3(const Conv3x3Args& a, hipStream_t st);
+// dense NCHW source and destination (batch strides Cin h w / Cout h w, also through a pixel (un)shuffle); everything else zero
+inline Conv3x3Args conv3x3_dense(const float* x, const float* wp, const float* bias, float* out, int B, int Cin, int Cout, int h, int w, int act) {
+    Conv3x3Args a{};
+    a.x = x; a.x_bstride = (int64_t)Cin * h * w; a.wp = wp; a.bias = bias; a.out = out; a.out_bstride = (int64_t)Cout * h * w;
+    a.B = B; a.Cin = Cin; a.Cout = Cout; a.h = h; a.w = w; a.act = act;
+    return a;
+}
 size_t conv3x3_ksplit_floats(int B, int Cout, int h, int w);   // 0: launches of this size never split
 size_t conv3x3_ksplit_counter_bytes();
 

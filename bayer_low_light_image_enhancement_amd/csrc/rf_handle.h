@@ -1,9 +1,9 @@
-// The RawFormer handle (internal): parameter registry, packed-weight plans and the index table that the forward schedule
-// (rf_model.hip) and the training schedule (rf_trainstep.hip) read.  rf_create registers every tensor by name once (add_param)
+// The RawFormer handle (internal): parameter registry, packed-weight plans, the variant's traits and the index table.  The
+// registry (rf_registry.hip) fills all of it before the first forward: rf_create registers every tensor by name once (add_param)
 // and records its registry index where the schedules need it: per Conv_Transformer stage in `stage[1..7]`, per other module in
 // the fields below; a group of parameters that travels together (FLCA, the TrueColor modules) is one struct with a named field
-// per tensor.  The schedules take pointers through those indices (prm / pk / pk3 / flca_prm); names serve rf_set_param and
-// rf_param_info only.
+// per tensor.  The forward schedule (rf_model.hip) and the training schedule (rf_trainstep.hip) only read: pointers through those
+// indices (prm / pk / pk3 / flca_prm), model facts through `vt`; names serve rf_set_param and rf_param_info only.
 #pragma once
 #include <string>
 #include <unordered_map>
@@ -69,6 +69,11 @@ struct WmbIx {
     size_t fold = 0, illu_pk = 0;     // floats into the packed buffer: launch_wmb_fold's outputs [ln2 | rep_w | rep_b | illu_fold], packed illu.conv1
 };
 
+// Stage tail  channel_reduce(cat(branch, x1 + pointwise2(g)))  as one bf16x3 GEMM over [branch ; x1 ; g] (K = 2C + hidden):
+// K blocks of 32 channels must not straddle the sources.  Level 0 of RawFormer-S / -B runs the fused FFN kernel instead
+// (run_stage decides per call: the fused kernel takes only some image sizes).
+inline bool tail_composable(int C, int hc) { return C % 32 == 0 && hc % 32 == 0 && hc > 0; }
+
 // registry indices of one Conv_Transformer stage (add_stage)
 struct StageIx {
     int lvl;         // U-Net level: channels dim << lvl, size H >> lvl
@@ -112,8 +117,22 @@ struct SideJoinGuard {
     ~SideJoinGuard() { s.join_pending(st); }
 };
 
+// What the schedules need to know about cfg.variant: plain data, set once by rf_create and read in its place.
+enum BranchKind { BR_CONV, BR_FLCA, BR_TC, BR_ML };   // a stage's branch: 3x3 conv (plain, wfb), FLCA, EnhancedFLCA (TrueColor), FLCA_Pyramid (multilvl)
+struct VariantTraits {
+    BranchKind branch;
+    bool wmb_block;                  // the stage's block is WMB (rf_wmb.hip), not the TransformerBlock
+    bool branch_after;               // BR_TC, BR_ML: the branch borrows bufA and pools with tc_residual, so it follows the block on the caller's stream
+    int levels;                      // flca_levels, resolved (0 = the default 2)
+    int guide_planes;                // planes of the guidance pyramid at every U-Net level
+    bool log_temperature;            // the attention's `temperature` holds log T
+    bool shardable;                  // rf_set_shard / rf_set_shard_grid accept it
+    bool stage_needs_packed_frame;   // rf_forward_stage derives the branch's guidance from the packed frame
+};
+
 struct rf_handle {
     rf_config cfg;
+    VariantTraits vt;
     std::vector<Param> params;
     std::unordered_map<std::string, int> index;   // name -> params[] (rf_set_param)
     std::vector<PackItem> packs;

@@ -90,7 +90,7 @@ int make_train_plan(const rf_handle* h, float* base, int B, int H, int W, TrainP
     const int hcx = c.ffn_expansion;
     p.x4 = b.take((size_t)B * 4 * H * W);
     p.e = b.take(U0);
-    const bool flca = c.variant == RF_VARIANT_FLCA;
+    const bool flca = h->vt.branch == BR_FLCA;
     if (flca) {
         p.gscratch = b.take(guidance_scratch_floats(B, H, W));
         for (int l = 0; l < 4; ++l) p.guide[l] = b.take((size_t)B * 4 * (H >> l) * (W >> l));
@@ -319,7 +319,7 @@ int stage_forward(const Ctx& c, int i, const float* in, int H, int W) {
     RF_TRY(f_conv1x1(c, s.x1, C, nullptr, 0, x.pw1_w, h->prm(x.pw1_b), h->prm(x.ln2_w), h->prm(x.ln2_b), nullptr, s.f1, hc, Pn));
     RF_TRY(f_dw(c, s.f1, h->prm(x.dw_w), h->prm(x.dw_b), s.f2, hc, hh, ww, s.g));   // f2 and g = gelu(f2)
     RF_TRY(f_conv1x1(c, s.g, hc, nullptr, 0, x.pw2_w, h->prm(x.pw2_b), nullptr, nullptr, s.x1, s.trans, C, Pn));
-    if (cfg.variant == RF_VARIANT_FLCA) {
+    if (h->vt.branch == BR_FLCA) {
         const FlcaPrm fp = h->flca_prm(x.flca);
         FlcaSpatialArgs sa{};
         sa.feat = in; sa.xs = s.xraw; sa.guide = c.p->guide[lvl];
@@ -364,11 +364,11 @@ int stage_backward(const Ctx& outer, hipStream_t wg, int i, float* dout, float* 
     const float* dxs = d_cat;
     const float* dtr = d_cat + (size_t)C * Pn;
     int64_t half_bs = (int64_t)2 * C * Pn;
-    if (cfg.variant != RF_VARIANT_FLCA || !ln_bwd_fused_shape(C, Pn)) {
+    if (h->vt.branch != BR_FLCA || !ln_bwd_fused_shape(C, Pn)) {
         RF_TRY(launch_split_halves(d_cat, d_xs, d_tr, c.B, C, Pn, c.st));
         dxs = d_xs; dtr = d_tr; half_bs = (int64_t)C * Pn;
     }
-    if (cfg.variant == RF_VARIANT_FLCA) {
+    if (h->vt.branch == BR_FLCA) {
         RF_TRY(launch_flca_backward(s.in, c.p->guide[lvl], s.xraw, dxs, half_bs, s.ch, s.pool, flca_nblk(hh, ww), h->flca_prm(x.flca),
                                     c.flca_grad(x.flca), din, 0, c.p->flca_scr, c.p->flca_scr_floats, c.B, C, hh, ww, c.st));   // din = branch part
     } else {
@@ -568,7 +568,7 @@ int rf_train_step(rf_handle* h, const float* in, const float* gt, float* grads, 
     // ------------------------------------------------------------------ forward
     RF_TRY(launch_pixel_unshuffle2(in, p.x4, B, 1, H, W, st));
     if (clamp_io) RF_TRY(launch_ewise(p.x4, nullptr, p.x4, (size_t)B * 4 * H * W, 6, 0.f, st));      // model.py:475
-    if (cfg.variant == RF_VARIANT_FLCA) {
+    if (h->vt.branch == BR_FLCA) {
         RF_TRY(launch_guidance_base(p.x4, 0, 0, p.gscratch, B, H, W, st));
         for (int l = 0; l < 4; ++l) RF_TRY(launch_guidance_level(p.gscratch, p.guide[l], B, H, W, H >> l, W >> l, st));
     }

@@ -255,9 +255,7 @@ int run_wmb(const rf_handle* h, int stage, const float* in, float* out, const Wm
     RF_TRY(launch_wmb_front(in, b.t, b.bands, ln2, ln2 + C, B, C, h2, w2, st));
     // 2. Illumination_Estimator on the LL band: conv1 with the channel mean folded in, depthwise 5x5 (conv2's illu_map is discarded
     //    by WMB.forward and not computed)
-    Conv1x1Args c1{};
-    c1.x1 = b.bands; c1.C1 = C; c1.x1_bstride = (int64_t)C * P2; c1.wp = h->packed + m.illu_pk; c1.bias = h->prm(m.illu1_b);
-    c1.out = b.illu; c1.out_bstride = (int64_t)C * P2; c1.Cout = C; c1.B = B; c1.P = P2; c1.w = w2;
+    const Conv1x1Args c1 = conv1x1_dense(b.bands, C, h->packed + m.illu_pk, nullptr, h->prm(m.illu1_b), b.illu, C, B, P2, w2);
     RF_TRY(launch_conv1x1(c1, st));
     RF_TRY(launch_dwconv5x5(b.illu, b.fea, h->prm(m.illu_dw_w), h->prm(m.illu_dw_b), B, C, h2, w2, st));
     // 3. FFAB into the LL slot, 4. WM on the three high bands, in place (its first convolution and its token pass are the only
@@ -273,10 +271,8 @@ int run_wmb(const rf_handle* h, int stage, const float* in, float* out, const Wm
     // 5. u = t + clamp((IWT + 1) / 2, 0, 1), over t
     RF_TRY(launch_wmb_back(b.bands, b.t, b.t, B, C, h2, w2, st));
     // 6. project_in(LN2(u)) with the LayerNorm in the GEMM's prologue where that reads u once
-    Conv1x1Args pi{};
-    pi.x1 = b.t; pi.C1 = C; pi.x1_bstride = (int64_t)C * Pn; pi.wp = h->pk(m.pin_w); pi.wp3 = h->pk3(m.pin_w); pi.bias = h->prm(m.pin_b);
+    Conv1x1Args pi = conv1x1_dense(b.t, C, h->pk(m.pin_w), h->pk3(m.pin_w), h->prm(m.pin_b), b.hid, hid, B, Pn, ww);
     pi.ln_w = h->prm(m.ln2_w); pi.ln_b = h->prm(m.ln2_b); pi.ln_eps = 1e-5f;
-    pi.out = b.hid; pi.out_bstride = (int64_t)hid * Pn; pi.Cout = hid; pi.B = B; pi.P = Pn; pi.w = ww;
     if (!conv1x1_ln_single_pass(pi)) {
         RF_TRY(launch_layernorm2d(b.t, b.gated, pi.ln_w, pi.ln_b, 1e-5f, B, C, Pn, st));
         pi.x1 = b.gated; pi.ln_w = nullptr; pi.ln_b = nullptr;
@@ -284,9 +280,7 @@ int run_wmb(const rf_handle* h, int stage, const float* in, float* out, const Wm
     RF_TRY(launch_conv1x1(pi, st));
     // 7. the gate on the folded rep-conv weights, 8. project_out, 9. out = u + y + LN2(u)
     RF_TRY(launch_dwgate3x3(b.hid, b.gated, rep_w, rep_b, h->prm(m.dw_w), h->prm(m.dw_b), B, hid, hh, ww, st));
-    Conv1x1Args po{};
-    po.x1 = b.gated; po.C1 = hid; po.x1_bstride = (int64_t)hid * Pn; po.wp = h->pk(m.pout_w); po.wp3 = h->pk3(m.pout_w); po.bias = h->prm(m.pout_b);
-    po.out = b.hid; po.out_bstride = (int64_t)C * Pn; po.Cout = C; po.B = B; po.P = Pn; po.w = ww;
+    const Conv1x1Args po = conv1x1_dense(b.gated, hid, h->pk(m.pout_w), h->pk3(m.pout_w), h->prm(m.pout_b), b.hid, C, B, Pn, ww);
     RF_TRY(launch_conv1x1(po, st));
     return launch_wmb_ffn_tail(b.t, b.hid, out, h->prm(m.ln2_w), h->prm(m.ln2_b), B, C, hh, ww, st);
 }

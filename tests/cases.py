@@ -161,3 +161,118 @@ def atten_tb_inputs(tag, dim, heads, b, h, w):
     x = rnd(f"atten.tb.{tag}.x", (b, dim, h, w), seed=43)
     luma = rnd(f"atten.tb.{tag}.luma", (b, 1, h, w), 0.0, 1.0, seed=44)
     return x, luma, params(atten_tb_spec(dim, heads), seed=750 + dim)
+
+
+# ---- handle layout and launch census: tools/make_handle_layout.py records, test_handle_layout.py / test_forward_launches.py compare
+VARIANT_IDS = {"flca": 0, "plain": 1, "truecolor": 2, "multilvl": 3, "wfb": 4}
+# tag: (variant, dim, ffn_expansion, branch_lrelu, clamp_io, flca_levels); heads 8 at every level, 3 output channels
+HANDLE_CONFIGS = {
+    "flca_d32": ("flca", 32, 2, 1, 0, 0), "flca_d48": ("flca", 48, 2, 1, 0, 0),
+    "plain_d16_lrelu0": ("plain", 16, 2, 0, 0, 0), "plain_d16_lrelu1": ("plain", 16, 2, 1, 0, 0), "plain_d32_clamp": ("plain", 32, 2, 1, 1, 0),
+    "truecolor_d32_l2": ("truecolor", 32, 2, 1, 0, 2), "truecolor_d32_l3": ("truecolor", 32, 2, 1, 0, 3),
+    **{f"multilvl_d{d}_l{l}": ("multilvl", d, 2, 1, 0, l) for d in (16, 32) for l in (0, 1, 3)},
+    **{f"wfb_d{d}_f{f}": ("wfb", d, f, 1, 1, 0) for d in (16, 32) for f in (2, 3)},
+}
+LAYOUT_FRAMES = ((1, 32, 32), (2, 64, 96), (1, 40, 72), (8, 512, 512), (1, 712, 1064))      # B, packed H, W
+
+
+def handle_params(tag):
+    """``(name, shape, flags)`` of every registered tensor of HANDLE_CONFIGS[tag], in registry order, and the handle's plans:
+    rf_packed_bytes and, per LAYOUT_FRAMES entry, rf_workspace_bytes or its (negative) error code.  No device is needed."""
+    import ctypes as C
+    from bayer_low_light_image_enhancement_amd import _lib
+    variant, dim, ffn, lrelu, clamp, levels = HANDLE_CONFIGS[tag]
+    lib = _lib.load()
+    cfg = _lib.RfConfig(dim, (C.c_int32 * 4)(8, 8, 8, 8), 1, 3, ffn, VARIANT_IDS[variant], lrelu, clamp, levels)
+    h = C.c_void_p()
+    _lib.check(lib.rf_create(C.byref(cfg), C.byref(h)), "rf_create")
+    try:
+        name, shape, ndim, flags, sz = C.c_char_p(), (C.c_int64 * 4)(), C.c_int(), C.c_int(), C.c_size_t()
+        rows = []
+        for i in range(lib.rf_param_count(h)):
+            _lib.check(lib.rf_param_info(h, i, C.byref(name), C.byref(shape), C.byref(ndim)), "rf_param_info")
+            _lib.check(lib.rf_param_flags(h, i, C.byref(flags)), "rf_param_flags")
+            rows.append((name.value.decode(), list(shape[: ndim.value]), flags.value))
+        _lib.check(lib.rf_packed_bytes(h, C.byref(sz)), "rf_packed_bytes")
+        plans = {"packed_bytes": sz.value, "workspace_bytes": []}
+        for b, hh, ww in LAYOUT_FRAMES:
+            rc = lib.rf_workspace_bytes(h, b, hh, ww, C.byref(sz))
+            plans["workspace_bytes"].append(sz.value if rc == 0 else rc)
+    finally:
+        lib.rf_destroy(h)
+    return rows, plans
+
+
+def params_digest(rows):
+    import hashlib
+    return hashlib.sha256("\n".join(f"{n} {s} {f}" for n, s, f in rows).encode()).hexdigest()
+
+
+def census(fn):
+    """``fn()`` between rf_profile_begin and rf_profile_end: its result and ``{kernel: [launches, flops, bytes]}``, the library's
+    per-launch brackets summed by kernel class (the times left out)."""
+    import ctypes
+    import json
+    from bayer_low_light_image_enhancement_amd import _lib
+    lib = _lib.load()
+    torch.cuda.synchronize()
+    lib.rf_profile_begin()
+    try:
+        out = fn()
+        torch.cuda.synchronize()
+    finally:
+        buf = ctypes.create_string_buffer(1 << 16)
+        _lib.check(lib.rf_profile_end(buf, len(buf)), "rf_profile_end")
+    return out, {r["kernel"]: [r["launches"], r["flops"], r["bytes"]] for r in json.loads(buf.value.decode())}
+
+
+def launches(fn):
+    """Kernel launches of ``fn()`` by kernel class, from the library's own per-launch brackets."""
+    out, c = census(fn)
+    return out, {k: v[0] for k, v in c.items()}
+
+
+# Launch census cases: tag -> (variant, dim, constructor keywords, B, packed H, W, stage or None = the whole forward).  Small
+# frames; between them every decision of the host schedule takes both values (the kernel named is what shows it in the census):
+#   fuse_tail   dim 32 level 0 / dim 16 level 1 at a width % 4 == 0 (ffn_fused tail) | every other level
+#   compose     C % 32 == 0 off the fused FFN (dim 32 levels 1-3) | dim 16 level 0, and level 3 of 40 x 72 (5 x 9 pixels, not % 4)
+#   fuse_up     level-3 width 4 (packed width 32: upcat_kernel) | 9 (packed width 72: the ConvTranspose2d GEMM + channel_reduce)
+#   ks_floats   > 0 (every small frame) | 0: 1032 x 1024, whose level 3 has more than 16384 pixels
+#   ml_step_fused_supported   C <= 64 (levels 0-1) | levels 2-3;   conv1x1_ln_single_pass   C <= 64 or 128 / 256 | dim 24 levels 2-3 (C = 96, 192)
+LAUNCH_CASES = {
+    "flca_d16_b2_32x32": ("flca", 16, {}, 2, 32, 32, None),
+    "flca_d32_b2_64x64": ("flca", 32, {}, 2, 64, 64, None),
+    "flca_d32_b1_40x72": ("flca", 32, {}, 1, 40, 72, None),
+    "plain_d16_b1_32x48": ("plain", 16, {"branch_lrelu": False}, 1, 32, 48, None),
+    "plain_d32_b1_32x32": ("plain", 32, {"clamp_io": True}, 1, 32, 32, None),
+    "plain_d16_b1_1032x1024": ("plain", 16, {}, 1, 1032, 1024, None),
+    "truecolor_d32_b1_32x32": ("truecolor", 32, {}, 1, 32, 32, None),
+    "truecolor_d32_l3_b1_40x72": ("truecolor", 32, {"flca_levels": 3}, 1, 40, 72, None),
+    "multilvl_d16_b2_32x48": ("multilvl", 16, {}, 2, 32, 48, None),
+    "multilvl_d32_l3_b1_40x72": ("multilvl", 32, {"flca_levels": 3}, 1, 40, 72, None),
+    "wfb_d16_b1_32x32": ("wfb", 16, {}, 1, 32, 32, None),
+    "wfb_d32_f3_b2_64x96": ("wfb", 32, {"ffn_expansion_factor": 3}, 2, 64, 96, None),
+    "wfb_d24_b1_32x32": ("wfb", 24, {}, 1, 32, 32, None),
+    **{f"{v}_d{d}_stage{s}": (v, d, {}, 1, 32, 32, s) for v, d in (("flca", 32), ("plain", 16), ("multilvl", 16), ("wfb", 16)) for s in (1, 4)},
+}
+_LAUNCH_MODELS = {}
+
+
+def launch_case(tag, device):
+    """The model (PyTorch's default initialisers under a fixed seed, built once per configuration) and a closure that runs the
+    case's one call on fixed random inputs."""
+    from bayer_low_light_image_enhancement_amd import RawFormer
+    variant, dim, kw, b, hh, ww, stage = LAUNCH_CASES[tag]
+    key = (variant, dim, tuple(sorted(kw.items())))
+    if key not in _LAUNCH_MODELS:
+        torch.manual_seed(1234)
+        _LAUNCH_MODELS[key] = RawFormer(dim=dim, variant=variant, **kw).to(device).eval()
+    m = _LAUNCH_MODELS[key]
+    g = torch.Generator().manual_seed(len(tag) + 7 * b + hh + ww)
+    if stage is None:
+        x = torch.rand((b, 1, 2 * hh, 2 * ww), generator=g).to(device)
+        return m, lambda: m(x)
+    lvl = stage - 1
+    x = (2 * torch.rand((b, dim << lvl, hh >> lvl, ww >> lvl), generator=g) - 1).to(device)
+    packed = torch.rand((b, 4, hh, ww), generator=g).to(device) if variant in ("flca", "multilvl") else None
+    return m, lambda: m.forward_stage(stage, x, packed)

@@ -9,7 +9,6 @@ become 4 x floor, so it stays 5e-5 (outputs reach |out| = 1.9).  Channel means: 
 per-pixel errors, each under TOL).  Output corrections against the closed form: 5e-6 -- every output is at most ten float32
 operations on values below 2 (10 x 2^-24 x 2 = 1.2e-6), the bilinear sample of LL2 as many again, and the two means enter with
 0.12 times a relative error of a few 2^-24 of their pairwise sums."""
-import ctypes
 import json
 import os
 import subprocess
@@ -22,8 +21,8 @@ import torch.nn.functional as F
 
 import cases
 import multilvl_ref
-from cases import golden
-from bayer_low_light_image_enhancement_amd import RawFormer, _lib, synth
+from cases import golden, launches
+from bayer_low_light_image_enhancement_amd import RawFormer, synth
 from oracle import rawformer_ref as R
 
 # tag, dim, flca_levels, batch, mosaic height, width, input seed (tools/make_golden_multilvl.py)
@@ -56,20 +55,6 @@ def restated(dim, seed, b, hh, ww):
         with torch.no_grad():
             _REF[key] = (x, multilvl_ref.forward(state(dim), x, dim))
     return _REF[key]
-
-
-def launches(fn):
-    """Kernel launches of ``fn()`` by kernel class, from the library's own per-launch brackets."""
-    lib = _lib.load()
-    torch.cuda.synchronize()
-    lib.rf_profile_begin()
-    try:
-        out = fn()
-        torch.cuda.synchronize()
-    finally:
-        buf = ctypes.create_string_buffer(1 << 16)
-        _lib.check(lib.rf_profile_end(buf, len(buf)), "rf_profile_end")
-    return out, {r["kernel"]: r["launches"] for r in json.loads(buf.value.decode())}
 
 
 # ------------------------------------------------------------------------------------------------ no GPU

@@ -1,4 +1,4 @@
-"""``RawFormer(variant='wfb')``: the whole RawFomer_WFB_FFAB model on one handle (csrc/rf_wmb.hip, rf_model.hip).
+"""``RawFormer(variant='wfb')``: the whole RawFomer_WFB_FFAB model on one handle (csrc/rf_wmb.hip, rf_registry.hip, rf_model.hip).
 
 Fixtures (tools/make_golden_wfb.py ran the reference's classes on the CPU, eval mode, with the restated Mamba bound to
 ``mamba_ssm.Mamba``): tests/golden/wfb.npz, wfb_state_dict_keys.json, PINNING_wfb.txt.  tests/wfb_ref.py is the plain-torch
