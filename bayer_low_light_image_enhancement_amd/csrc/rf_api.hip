@@ -175,6 +175,18 @@ int rf_conv1x1_group_map(int units, int ngroups, int id, int* unit, int* group) 
     return RF_OK;
 }
 
+// the GEMM of rf_conv1x1 on packed weights wp / wp3
+static Conv1x1Args conv1x1_api_args(const float* in, const float* in2, float* out, const float* wp, const void* wp3, const float* bias,
+                                    const float* ln_w, const float* ln_b, const float* res, int B, int C1, int C2, int Cout, int h, int w) {
+    Conv1x1Args a{};
+    a.x1 = in; a.C1 = C1; a.x1_bstride = (int64_t)C1 * h * w;
+    a.x2 = C2 ? in2 : nullptr; a.C2 = C2; a.x2_bstride = (int64_t)C2 * h * w;
+    a.wp = wp; a.wp3 = wp3; a.bias = bias; a.ln_w = ln_w; a.ln_b = ln_b; a.ln_eps = 1e-5f;
+    a.res = res; a.res_bstride = (int64_t)Cout * h * w;
+    a.out = out; a.out_bstride = (int64_t)Cout * h * w; a.Cout = Cout; a.B = B; a.P = h * w; a.w = w;
+    return a;
+}
+
 int rf_conv1x1(const float* in, const float* in2, float* out, const float* weight, const float* bias,
                const float* ln_w, const float* ln_b, const float* res, void* scratch,
                int B, int C1, int C2, int Cout, int h, int w, void* stream) {
@@ -184,13 +196,7 @@ int rf_conv1x1(const float* in, const float* in2, float* out, const float* weigh
     RF_TRY(pack_1x1(weight, (float*)scratch, Cout, K, K, 1, st));
     float* w3 = (float*)scratch + align_up(packed1x1_floats(K, Cout), 64);
     RF_TRY(pack_1x1_b3(weight, w3, Cout, K, K, 1, st));
-    Conv1x1Args a{};
-    a.x1 = in; a.C1 = C1; a.x1_bstride = (int64_t)C1 * h * w;
-    a.x2 = C2 ? in2 : nullptr; a.C2 = C2; a.x2_bstride = (int64_t)C2 * h * w;
-    a.wp = (const float*)scratch; a.wp3 = w3; a.bias = bias; a.ln_w = ln_w; a.ln_b = ln_b; a.ln_eps = 1e-5f;
-    a.res = res; a.res_bstride = (int64_t)Cout * h * w;
-    a.out = out; a.out_bstride = (int64_t)Cout * h * w; a.Cout = Cout; a.B = B; a.P = h * w; a.w = w;
-    return launch_conv1x1(a, st);
+    return launch_conv1x1(conv1x1_api_args(in, in2, out, (const float*)scratch, w3, bias, ln_w, ln_b, res, B, C1, C2, Cout, h, w), st);
 }
 
 int rf_dwconv3x3(const float* in, float* out, const float* weight, const float* bias, int gelu,
@@ -226,15 +232,38 @@ int rf_convT2x2_scratch_bytes(int Cin, int Cout, size_t* bytes) {
     return RF_OK;
 }
 
+// the GEMM of rf_convT2x2 on packed weights wp
+static Conv1x1Args convT2x2_api_args(const float* in, float* out, const float* wp, const float* bias, int B, int Cin, int Cout, int h, int w) {
+    Conv1x1Args a{};
+    a.x1 = in; a.C1 = Cin; a.x1_bstride = (int64_t)Cin * h * w; a.wp = wp; a.bias = bias;
+    a.out = out; a.out_bstride = (int64_t)Cout * 4 * h * w; a.Cout = 4 * Cout; a.B = B; a.P = h * w; a.w = w; a.mode = 1;
+    return a;
+}
+
 int rf_convT2x2(const float* in, float* out, const float* weight, const float* bias, void* scratch,
                 int B, int Cin, int Cout, int h, int w, void* stream) {
     RF_CHECK_ARG(in && out && weight && scratch && aligned16(scratch), "convT2x2: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     RF_TRY(pack_convT(weight, (float*)scratch, Cin, Cout, st));
-    Conv1x1Args a{};
-    a.x1 = in; a.C1 = Cin; a.x1_bstride = (int64_t)Cin * h * w; a.wp = (const float*)scratch; a.bias = bias;
-    a.out = out; a.out_bstride = (int64_t)Cout * 4 * h * w; a.Cout = 4 * Cout; a.B = B; a.P = h * w; a.w = w; a.mode = 1;
-    return launch_conv1x1(a, st);
+    return launch_conv1x1(convT2x2_api_args(in, out, (const float*)scratch, bias, B, Cin, Cout, h, w), st);
+}
+
+int rf_conv1x1_plan(int B, int C1, int C2, int Cout, int h, int w, int ln, int res, int transposed, int b3_weights,
+                    char* key, size_t key_len, int* grid, int* block, size_t* lds_bytes, int* ln_single_pass) {
+    RF_CHECK_ARG(key && key_len > 0 && grid && block && lds_bytes && ln_single_pass, "conv1x1_plan: bad arguments");
+    RF_CHECK_ARG(!transposed || (!ln && !res && C2 == 0 && !b3_weights), "conv1x1_plan: rf_convT2x2 has one source, no LayerNorm, no residual and no b3 weights");
+    alignas(16) static float any[4];      // stands for every operand: a plan looks at presence and alignment only
+    const Conv1x1Args a = transposed ? convT2x2_api_args(any, any, any, any, B, C1, Cout, h, w)
+                                     : conv1x1_api_args(any, any, any, any, b3_weights ? any : nullptr, any, ln ? any : nullptr, ln ? any : nullptr,
+                                                        res ? any : nullptr, B, C1, C2, Cout, h, w);
+    Conv1x1Plan p;
+    RF_TRY(plan_conv1x1(a, &p));
+    snprintf(key, key_len, "%s", p.key);
+    grid[0] = (int)p.grid[0]; grid[1] = (int)p.grid[1]; grid[2] = (int)p.grid[2];
+    *block = (int)p.block;
+    *lds_bytes = p.lds;
+    *ln_single_pass = p.ln_single_pass;
+    return RF_OK;
 }
 
 // scratch layout of rf_chan_attn: packed qkv weights | qkv_pre | qkv | gram partials | folded weights

@@ -178,7 +178,7 @@ int pack_upcat(const float* up_w, const float* up_b, const float* cr_w, const fl
 bool upcat_supported(int C, int h, int w, const void* x, const void* skip, const void* out);
 int launch_upcat(const float* x, const float* skip, float* out, const float* packed, int B, int C, int h, int w, hipStream_t st);
 
-// ---- conv1x1 (rf_conv1x1.hip)
+// ---- conv1x1 (rf_gemm1x1.hip)
 struct Conv1x1Args {
     const float* x1;       // first source, channel 0 of image 0
     const float* x2;       // second source or nullptr
@@ -206,6 +206,18 @@ struct Conv1x1Args {
     int mode;              // 0: out[co][p]; 1: ConvTranspose2d 2x2 scatter, row co = 4*o + 2*i + j
     int act;               // 0 none, 1 LeakyReLU(0.2), 2 ReLU, 3 LeakyReLU(0.1), 4 clamp to [0, 1e4] (FEB, blocks.py:14-30)
 };
+// What launch_conv1x1 will launch for `a`, decided on the host alone (no HIP call): plan_conv1x1 in rf_gemm1x1.hip is the single
+// statement of the selection rule.
+struct Conv1x1Plan {
+    int inst;              // row of rf_gemm1x1.hip's instantiation table: the kernel and its template arguments
+    const char* key;       // that row's name: the profiler key, and the kernel name a trace shows
+    unsigned grid[3], block;
+    size_t lds;            // dynamic LDS bytes
+    int karg[2];           // the kernel's integer arguments: (ntw, ngroups) resident-input | (ngroups) streaming, b3 | (tpw) b3_ln
+    double flops, bytes;   // of the whole launch, for ProfScope
+    bool ln_single_pass;   // the LayerNorm prologue (if any) reads x once: see conv1x1_ln_single_pass
+};
+int plan_conv1x1(const Conv1x1Args& a, Conv1x1Plan* p);    // RF_E_INVALID (and the error text) for arguments launch_conv1x1 refuses
 int launch_conv1x1(const Conv1x1Args& a, hipStream_t st);
 // one dense NCHW source and a dense destination (batch strides C1 P / Cout P); everything else zero
 inline Conv1x1Args conv1x1_dense(const float* x1, int C1, const float* wp, const void* wp3, const float* bias, float* out, int Cout, int B, int P, int w) {

@@ -17,16 +17,25 @@
 // (clamped addresses instead of predicates, so the compiler emits counted waits), and read all
 // small operands (bias, gamma, beta, weights) from LDS, which has its own counter.
 //
-//   conv1x1_res_kernel    K <= 128 (U-Net levels 0-1, HBM-bound): persistent workgroups; a wave
-//                         keeps its whole [K x 64 px] input tile in registers, computes exact
-//                         two-pass LayerNorm statistics on it, then sweeps ALL output-channel
-//                         groups over the resident tile (x is read from HBM once whatever Cout
-//                         is) while the next tile's loads are already in flight (K <= 64).
-//   conv1x1_stream_kernel K  > 128 (levels 2-3, MFMA-bound): accumulators resident, K streamed
-//                         in chunks; the next chunk's x (registers) and weights (registers ->
-//                         LDS double buffer) are fetched while the current one is in the matrix
-//                         pipe; one barrier per chunk.
-//   conv1x1_scalar_kernel any ragged shape (P % 4 != 0 or unaligned): plain FMA loop.
+// Five kernels.  plan_conv1x1 (at the end of this file) is the single statement of the rule that picks between them and of
+// their template arguments and grids; it applies the rule in this order:
+//   1. conv1x1_scalar_kernel  any ragged shape (P % 4 != 0, unaligned operands, odd width in ConvTranspose mode), a residual
+//                             with Cout % 16 != 0: plain FMA loop, correctness only.
+//   2. conv1x1_b3_ln_kernel   b3 weights present, LayerNorm, K = 64 / 128 / 256, Cout % 64 == 0, one source, no residual
+//                             (qkv and pw1 of levels 1-3): bf16 matrix pipe with three-piece operands; a workgroup normalises
+//                             and splits its 64 pixels ONCE and its waves split the output tiles.
+//   3. conv1x1_b3_kernel      b3 weights present, K >= 128, sources cut at multiples of 32 channels (up to three): the
+//                             streaming form on the bf16 pipe, accumulators resident, K in blocks of 32; LayerNorm prologue
+//                             (K = 512) at 4 tiles per workgroup only; without LayerNorm two output groups may share a
+//                             512-thread workgroup and the x it fetches (PAIR) where the launch still fills the CUs.
+//   4. conv1x1_res_kernel     K <= 64, or K <= 128 without LayerNorm and residual (U-Net levels 0-1, HBM-bound): persistent
+//                             workgroups; a wave keeps its whole [K x 64 px] input tile in registers, computes exact two-pass
+//                             LayerNorm statistics on it, then sweeps ALL output-channel groups over the resident tile (x is
+//                             read from HBM once whatever Cout is) while the next tile's loads are already in flight (K <= 64).
+//   5. conv1x1_stream_kernel  everything else (K = 96 .. 128 with LayerNorm or a residual, K > 128 without b3 weights or
+//                             with sources not cut at 8 / 32 channels): f32 MFMA, accumulators resident, K streamed in chunks;
+//                             the next chunk's x (registers) and weights (registers -> LDS double buffer) are fetched while the
+//                             current one is in the matrix pipe; one barrier per chunk.
 // Fused: LayerNorm prologue (a4), second source (torch.cat without the copy), bias, residual,
 // LeakyReLU, ConvTranspose2d(k=2,s=2) scatter (a9), per-image weights (wp_bstride != 0) for the
 // attention / squeeze-excite matrices folded into the projection.
@@ -47,6 +56,26 @@ __device__ __forceinline__ const float* kset_base(const Conv1x1Args& a, int b, i
 
 __device__ __forceinline__ float4 ldv(const float* __restrict__ base, unsigned off) {
     return *reinterpret_cast<const float4*>(base + off);
+}
+
+// ---- pieces the kernels share (operands by value or by reference-to-array: see the note at b3_load_x_block's call site)
+template <int NCO>
+__device__ __forceinline__ void zero_acc(f32x4 (&acc)[NCO][4]) {
+#pragma unroll
+    for (int t = 0; t < NCO; ++t)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) acc[t][g] = (f32x4){0.f, 0.f, 0.f, 0.f};
+}
+
+// channel pair (2 hp, 2 hp + 1) of pixel g -> dword hp of the three bf16 pieces of that pixel's B operand, bp[g][piece][hp]
+template <class BP>
+__device__ __forceinline__ void b3_split_pair(float xa, float xb, BP& bp, int g, int hp) {
+    unsigned a0, a1, a2, b0, b1, b2;
+    b3_split(xa, a0, a1, a2);
+    b3_split(xb, b0, b1, b2);
+    bp[g][0][hp] = b3_pack(a0, b0);
+    bp[g][1][hp] = b3_pack(a1, b1);
+    bp[g][2][hp] = b3_pack(a2, b2);
 }
 
 // Store NCO accumulator tiles.  bias_l: LDS bias of the first tile; res: prefetched residual rows
@@ -253,10 +282,7 @@ __global__ void __launch_bounds__(256, (KS <= 8 ? 3 : 2)) conv1x1_res_kernel(Con
         // ---- sweep the output-channel groups over the resident tile
         auto do_group = [&](int tg, const float4* resp) {
             f32x4 acc[NCO][4];
-#pragma unroll
-            for (int t = 0; t < NCO; ++t)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) acc[t][g] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            zero_acc(acc);
             const float* wl = lds_w + (size_t)tg * 64 + lane;
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
@@ -329,13 +355,11 @@ __global__ void __launch_bounds__(256, 2) conv1x1_stream_kernel(Conv1x1Args a, i
     // The residual initialises the accumulators: its loads travel with the first chunk's (one exposed
     // round trip instead of two) and the epilogue stays store-only.
     f32x4 acc[NCO][4];
-#pragma unroll
-    for (int t = 0; t < NCO; ++t)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc[t][g] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
     if (a.res && a.mode == 0) {   // (wave-uniform)
         // branch-free: a conditional block around each load would be closed with s_waitcnt vmcnt(0), i.e. 32
         // serialised round trips to HBM; rows that do not exist read row 0 of the image and are masked to zero
+        // (conv1x1_b3_kernel has the same loop: as a shared function it changes that kernel's code)
         const float* resb = a.res + (size_t)b * a.res_bstride;
         const unsigned vo = (unsigned)(live ? p0 : 0);
 #pragma unroll
@@ -515,7 +539,7 @@ __global__ void __launch_bounds__(PAIR ? 512 : 256, 2) conv1x1_b3_kernel(Conv1x1
 
     f32x4 acc[NCO][4];
 #pragma unroll
-    for (int t = 0; t < NCO; ++t)
+    for (int t = 0; t < NCO; ++t)      // (zero_acc here moves the zeroing ahead of the branch below)
 #pragma unroll
         for (int g = 0; g < 4; ++g) acc[t][g] = (f32x4){0.f, 0.f, 0.f, 0.f};
     if (a.res && a.mode == 0) {   // the residual initialises the accumulators (branch-free loads, see conv1x1_stream_kernel)
@@ -606,14 +630,7 @@ __global__ void __launch_bounds__(PAIR ? 512 : 256, 2) conv1x1_b3_kernel(Conv1x1
                 }
             }
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                unsigned a0, a1, a2, b0, b1, b2;
-                b3_split(xa[g], a0, a1, a2);
-                b3_split(xb[g], b0, b1, b2);
-                bp[g][0][hp] = b3_pack(a0, b0);
-                bp[g][1][hp] = b3_pack(a1, b1);
-                bp[g][2][hp] = b3_pack(a2, b2);
-            }
+            for (int g = 0; g < 4; ++g) b3_split_pair(xa[g], xb[g], bp, g, hp);
         }
         if (c + 1 < NB) {   // next block in flight while this one is in the matrix pipe (x into the registers just vacated)
             load_x_block(c + 1);
@@ -728,13 +745,7 @@ __global__ void __launch_bounds__(256, KB <= 4 ? 2 : 1) conv1x1_b3_ln_kernel(Con
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const float mu = a.ln_b ? mean[g] : 0.f;     // BiasFree_LayerNorm scales x, not x - mean
-                const float ya = fmaf((xa[g] - mu) * rstd[g], ga, ba), yb = fmaf((xc[g] - mu) * rstd[g], gb, bb);
-                unsigned a0, a1, a2, b0, b1, b2;
-                b3_split(ya, a0, a1, a2);
-                b3_split(yb, b0, b1, b2);
-                bpd[g][0][hp] = b3_pack(a0, b0);
-                bpd[g][1][hp] = b3_pack(a1, b1);
-                bpd[g][2][hp] = b3_pack(a2, b2);
+                b3_split_pair(fmaf((xa[g] - mu) * rstd[g], ga, ba), fmaf((xc[g] - mu) * rstd[g], gb, bb), bpd, g, hp);
             }
         }
 #pragma unroll
@@ -788,17 +799,6 @@ __global__ void __launch_bounds__(256, KB <= 4 ? 2 : 1) conv1x1_b3_ln_kernel(Con
     }   // pixel tiles (the first barrier of the next tile's statistics also frees Bl)
 }
 
-static bool b3_ln_supported(const Conv1x1Args& a, int* nco) {
-    const int K = a.C1 + a.C2;
-    if (!(a.ln_w && a.wp3 && a.C2 == 0 && (K == 64 || K == 128 || K == 256) && a.mode == 0 && !a.res && a.Cout % 64 == 0 && a.Cout <= 1024 &&
-          aligned16(a.wp3) && a.wp3_bstride % 4 == 0))
-        return false;
-    const int tpw = a.Cout / 64;
-    // K = 128 runs two workgroups per CU (256 registers): 4 tiles at once plus the next pixel tile in flight would spill
-    *nco = (K == 256 && tpw % 4 == 0) ? 4 : tpw % 3 == 0 ? 3 : tpw % 2 == 0 ? 2 : 0;
-    return *nco != 0;
-}
-
 // ---------------------------------------------------------------------------------------------
 // Ragged shapes (P % 4 != 0, unaligned views): one thread per output pixel and channel, plain
 // FMA over K with a two-pass LayerNorm.  Correctness path only: tiny odd test frames (a RawFormer level always has
@@ -847,22 +847,61 @@ __global__ void __launch_bounds__(256) conv1x1_scalar_kernel(Conv1x1Args a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-template <int KS, int RT>
-static void launch_res_rt(const Conv1x1Args& a, int ntw, int ngroups, dim3 grid, size_t lds, hipStream_t st) {
-    constexpr bool DBUF = KS <= 16 && !(KS > 8 && RT == 4);
-    if (a.ln_w) conv1x1_res_kernel<KS, true, RT, DBUF><<<grid, 256, lds, st>>>(a, ntw, ngroups);
-    else conv1x1_res_kernel<KS, false, RT, DBUF><<<grid, 256, lds, st>>>(a, ntw, ngroups);
+// Host side.  Every instantiation that can be launched is one row of kInst: the row's text is both the launch and the
+// profiler key (= the kernel name a trace shows), so the two cannot drift apart.
+enum { kScalar, kRes, kStream, kB3, kB3Ln };
+struct Conv1x1Inst {
+    const char* key;
+    int family, targ[4];     // the template arguments as integers, in order (absent ones zero)
+    unsigned block;
+    void (*launch)(const Conv1x1Args&, const Conv1x1Plan&, hipStream_t);
+};
+#define RF_GRID dim3(p.grid[0], p.grid[1], p.grid[2]), p.block, p.lds, st
+#define RF_INST(FAMILY, BLOCK, KERNEL, KARGS, ...)                                      \
+    {#KERNEL "<" #__VA_ARGS__ ">", FAMILY, {__VA_ARGS__}, BLOCK,                        \
+     [](const Conv1x1Args& a, const Conv1x1Plan& p, hipStream_t st) { KERNEL<__VA_ARGS__><<<RF_GRID>>> KARGS; }}
+#define RF_RES(...) RF_INST(kRes, 256, conv1x1_res_kernel, (a, p.karg[0], p.karg[1]), __VA_ARGS__)          // <KS, LN, RT, DBUF>(ntw, ngroups)
+#define RF_RES6(KS, DBUF4) /* K <= 64: LayerNorm or not, 0 / 2 / 4 residual tiles in registers */             \
+    RF_RES(KS, true, 4, DBUF4), RF_RES(KS, false, 4, DBUF4), RF_RES(KS, true, 2, true), RF_RES(KS, false, 2, true), RF_RES(KS, true, 0, true), RF_RES(KS, false, 0, true)
+#define RF_STREAM(...) RF_INST(kStream, 256, conv1x1_stream_kernel, (a, p.karg[0]), __VA_ARGS__)            // <NCO, KCH, LN>(ngroups)
+#define RF_B3(BLOCK, ...) RF_INST(kB3, BLOCK, conv1x1_b3_kernel, (a, p.karg[0]), __VA_ARGS__)               // <NCO, LN[, PAIR]>(ngroups)
+#define RF_B3LN(...) RF_INST(kB3Ln, 256, conv1x1_b3_ln_kernel, (a, p.karg[0]), __VA_ARGS__)                 // <KB, NCO>(tpw)
+// (rows in the order the code object has always held its kernels)
+static const Conv1x1Inst kInst[] = {
+    {"conv1x1_scalar_kernel", kScalar, {}, 256, [](const Conv1x1Args& a, const Conv1x1Plan& p, hipStream_t st) { conv1x1_scalar_kernel<<<RF_GRID>>>(a); }},
+    RF_B3LN(2, 3), RF_B3LN(2, 2), RF_B3LN(4, 3), RF_B3LN(4, 2), RF_B3LN(8, 4), RF_B3LN(8, 3), RF_B3LN(8, 2),
+    // the unpaired key names the family by its first two arguments (bench.py's lookup covers <.., false, false> with it); the
+    // paired form has a key of its own, so a profile shows which form a launch took
+    RF_B3(512, 6, false, true), RF_B3(512, 4, false, true), RF_B3(256, 6, false), RF_B3(256, 2, false), RF_B3(256, 4, true), RF_B3(256, 4, false),
+    // four residual tiles next to a whole [K x 64 px] tile in flight do not fit at K > 32: those load the next tile late (no
+    // DBUF).  With K <= 32 or a LayerNorm prologue the four-tile forms spill and plan_conv1x1 never asks for them; they stay
+    // in the table (and in the code object) as they were.
+    RF_RES6(4, true), RF_RES6(8, true), RF_RES6(12, false), RF_RES6(16, false),
+    RF_RES(24, false, 0, false), RF_RES(32, false, 0, false),
+    RF_STREAM(8, 4, true), RF_STREAM(8, 4, false), RF_STREAM(4, 8, true), RF_STREAM(4, 8, false),
+};
+#undef RF_GRID
+
+// the row of `family` whose first template arguments are t0, t1, t2 (-1: any); a kernel that is not there is an error
+static int find_inst(int family, int t0, int t1, int t2, Conv1x1Plan* p) {
+    const int want[3] = {t0, t1, t2};
+    for (const Conv1x1Inst& r : kInst) {
+        bool ok = r.family == family;
+        for (int k = 0; k < 3; ++k) ok = ok && (want[k] < 0 || want[k] == r.targ[k]);
+        if (ok) { p->inst = (int)(&r - kInst); p->key = r.key; p->block = r.block; return RF_OK; }
+    }
+    RF_CHECK_ARG(false, "conv1x1: no kernel instantiation for family %d <%d, %d, %d>", family, t0, t1, t2);
 }
 
-template <int KS>
-static void launch_res(const Conv1x1Args& a, int ntw, int ngroups, dim3 grid, size_t lds, hipStream_t st) {
-    if constexpr (KS <= 16) {
-        if (a.res && ntw > 2) launch_res_rt<KS, 4>(a, ntw, ngroups, grid, lds, st);
-        else if (a.res) launch_res_rt<KS, 2>(a, ntw, ngroups, grid, lds, st);
-        else launch_res_rt<KS, 0>(a, ntw, ngroups, grid, lds, st);
-    } else {
-        conv1x1_res_kernel<KS, false, 0, false><<<grid, 256, lds, st>>>(a, ntw, ngroups);
-    }
+static bool b3_ln_supported(const Conv1x1Args& a, int* nco) {
+    const int K = a.C1 + a.C2;
+    if (!(a.ln_w && a.wp3 && a.C2 == 0 && (K == 64 || K == 128 || K == 256) && a.mode == 0 && !a.res && a.Cout % 64 == 0 && a.Cout <= 1024 &&
+          aligned16(a.wp3) && a.wp3_bstride % 4 == 0))
+        return false;
+    const int tpw = a.Cout / 64;
+    // K = 128 runs two workgroups per CU (256 registers): 4 tiles at once plus the next pixel tile in flight would spill
+    *nco = (K == 256 && tpw % 4 == 0) ? 4 : tpw % 3 == 0 ? 3 : tpw % 2 == 0 ? 2 : 0;
+    return *nco != 0;
 }
 
 // shapes the b3 kernel takes: K-blocks of 32 channels must not straddle the two sources; K < 128 stays on the resident-input
@@ -874,16 +913,16 @@ static bool b3_supported(const Conv1x1Args& a) {
            (a.C3 == 0 || a.C2 % 32 == 0) && (!a.ln_w || (K <= kStreamLnMaxK && a.C3 == 0)) && aligned16(a.wp3) && (a.wp3_bstride % 4 == 0);
 }
 
-// Does the LayerNorm prologue of this GEMM read x once?  Yes on the split-once bf16x3 kernel (K = 64 / 128 / 256) and on the
-// resident-input kernels (K <= 64).  The streaming kernels re-read and re-normalise their pixels once per group of 64-96 output
-// channels (RawFormer-L level 3, K = 512 -> 1536: 24 passes, 0.77 ms for a 0.2 ms product; every level of RawFormer-B, K = 96 /
-// 192 / 384): their callers run layernorm2d first and the plain GEMM on its output (rf_block.hip).
-bool conv1x1_ln_single_pass(const Conv1x1Args& a) {
-    int nco = 0;
-    return !a.ln_w || a.C1 + a.C2 <= 64 || (a.wp3 != nullptr && b3_ln_supported(a, &nco));
-}
-
-int launch_conv1x1(const Conv1x1Args& a, hipStream_t st) {
+// THE selection rule (summary at the top of this file): argument checks, then the family in the order scalar, b3_ln, b3, res,
+// stream, and inside a family the template arguments and the grid.  No HIP call, no launch; a plan exists only for arguments
+// launch_conv1x1 accepts.
+int plan_conv1x1(const Conv1x1Args& a, Conv1x1Plan* p) {
+    bool b3_ok = a.wp3 != nullptr;
+    int force_pair = -1;      // -1: by launch size
+#ifdef RF_DIAG   // diagnostic build only (build.py --diag): RF_NO_B3 forces the f32 MFMA kernels; RF_B3_PAIR=1 takes the paired form at any launch size, =0 never
+    if (getenv("RF_NO_B3")) b3_ok = false;
+    if (const char* e = getenv("RF_B3_PAIR")) force_pair = e[0] != '0';
+#endif
     RF_CHECK_ARG(a.B > 0 && a.P > 0 && a.C1 > 0 && a.C2 >= 0 && a.Cout > 0, "conv1x1: bad sizes B=%d P=%d C1=%d C2=%d Cout=%d",
                  a.B, a.P, a.C1, a.C2, a.Cout);
     RF_CHECK_ARG(a.C1 % 4 == 0 && a.C2 % 4 == 0, "conv1x1: input channel counts (%d, %d) must be multiples of 4", a.C1, a.C2);
@@ -893,27 +932,34 @@ int launch_conv1x1(const Conv1x1Args& a, hipStream_t st) {
     RF_CHECK_ARG(a.B <= 65535 && (double)a.P * 4.0 * 16.0 < 4.0e9, "conv1x1: batch %d / plane %d too large", a.B, a.P);
     const int K = a.C1 + a.C2 + a.C3;
     const int NS = K / 4, NT = cdiv(a.Cout, 16);
+    const int ptiles = cdiv(a.P, 256);                    // 256-pixel tiles of an image
+    const long units = (long)ptiles * a.B;
     bool vec = (a.P % 4 == 0) && aligned16(a.x1) && aligned16(a.out) && (a.x1_bstride % 4 == 0) && (a.out_bstride % 4 == 0);
     if (a.x2) vec = vec && aligned16(a.x2) && (a.x2_bstride % 4 == 0);
     if (a.C3) vec = vec && aligned16(a.x3) && (a.x3_bstride % 4 == 0);
     if (a.res) vec = vec && aligned16(a.res) && (a.res_bstride % 4 == 0);
     if (a.mode == 1) vec = vec && (a.w % 2 == 0);
+    const bool ln = a.ln_w != nullptr;
     const double px = (double)a.B * a.P;
-    const double work_flops = 2.0 * K * a.Cout * px, work_bytes = 4.0 * px * (K + a.Cout + (a.res ? a.Cout : 0));
-    char key[64];
-    bool b3_ok = a.wp3 != nullptr;
-#ifdef RF_DIAG   // diagnostic build only (build.py --diag): force the f32 MFMA kernels
-    if (getenv("RF_NO_B3")) b3_ok = false;
-#endif
+    *p = Conv1x1Plan{};
+    p->flops = 2.0 * K * a.Cout * px;
+    p->bytes = 4.0 * px * (K + a.Cout + (a.res ? a.Cout : 0));
+    p->grid[1] = (unsigned)a.B; p->grid[2] = 1;
+    int nco_ln = 0;
+    const bool ln_once = b3_ln_supported(a, &nco_ln);      // the split-once bf16x3 kernel takes this shape
+    // Does the LayerNorm prologue read x once?  Yes on the split-once bf16x3 kernel and on the resident-input kernels (K <= 64).
+    // The streaming kernels re-read and re-normalise their pixels once per group of 64-96 output channels (RawFormer-L level 3,
+    // K = 512 -> 1536: 24 passes, 0.77 ms for a 0.2 ms product; every level of RawFormer-B): their callers run layernorm2d first
+    // and the plain GEMM on its output (rf_block.hip).  A property of the shape: the same on ragged frames and under RF_NO_B3.
+    p->ln_single_pass = !ln || a.C1 + a.C2 <= 64 || ln_once;
     const bool use_b3 = b3_ok && b3_supported(a);
     // three sources exist for the bf16x3 streaming kernel only (its caller checks the shape; there is no slower form to fall to)
     RF_CHECK_ARG(a.C3 == 0 || (use_b3 && vec && !a.ln_w && !(a.res && a.Cout % 16 != 0)), "conv1x1: three sources need the bf16x3 kernel (K = %d, P = %d)", K, a.P);
-    if (!vec || (a.res && a.Cout % 16 != 0) || (a.ln_w && K > kStreamLnMaxK)) {
-        ProfScope prof(st, "conv1x1_scalar_kernel", work_flops, work_bytes);
-        int gx = cdiv(a.P, 256);
-        if (gx > 4096) gx = 4096;
-        conv1x1_scalar_kernel<<<dim3((unsigned)gx, (unsigned)a.B), 256, 0, st>>>(a);
-    } else if (int nco_ln = 0; b3_ok && b3_ln_supported(a, &nco_ln)) {
+    if (!vec || (a.res && a.Cout % 16 != 0) || (ln && K > kStreamLnMaxK)) {
+        p->grid[0] = (unsigned)(cdiv(a.P, 256) < 4096 ? cdiv(a.P, 256) : 4096);
+        return find_inst(kScalar, -1, -1, -1, p);
+    }
+    if (b3_ok && ln_once) {
         const int kb = K / 32;
         int tpw = a.Cout / 64;
         const int slots = (kb <= 4 ? 2 : 1) * 256;                // resident workgroups (LDS: 31 / 55 / 104 KB; registers: 2 per CU)
@@ -927,59 +973,30 @@ int launch_conv1x1(const Conv1x1Args& a, hipStream_t st) {
         if ((long)gx * a.B < 128)
             for (int z = tpw / nco_ln; z > 1; --z)
                 if ((tpw / nco_ln) % z == 0 && (long)gx * a.B * z <= 512) { zs = z; break; }
-        tpw /= zs;
-        dim3 grid((unsigned)gx, (unsigned)a.B, (unsigned)zs);
-        snprintf(key, sizeof(key), "conv1x1_b3_ln_kernel<%d, %d>", kb, nco_ln);
-        ProfScope prof(st, key, work_flops, work_bytes);
-        if (kb == 2) {
-            if (nco_ln == 3) conv1x1_b3_ln_kernel<2, 3><<<grid, 256, 0, st>>>(a, tpw);
-            else conv1x1_b3_ln_kernel<2, 2><<<grid, 256, 0, st>>>(a, tpw);
-        } else if (kb == 4) {
-            if (nco_ln == 3) conv1x1_b3_ln_kernel<4, 3><<<grid, 256, 0, st>>>(a, tpw);
-            else conv1x1_b3_ln_kernel<4, 2><<<grid, 256, 0, st>>>(a, tpw);
-        } else {
-            if (nco_ln == 4) conv1x1_b3_ln_kernel<8, 4><<<grid, 256, 0, st>>>(a, tpw);
-            else if (nco_ln == 3) conv1x1_b3_ln_kernel<8, 3><<<grid, 256, 0, st>>>(a, tpw);
-            else conv1x1_b3_ln_kernel<8, 2><<<grid, 256, 0, st>>>(a, tpw);
-        }
-    } else if (use_b3) {
-        // bf16x3 streaming kernel (K > 32: below that the resident-input f32 kernels are HBM-bound anyway)
+        p->grid[0] = (unsigned)gx; p->grid[2] = (unsigned)zs;
+        p->karg[0] = tpw / zs;
+        return find_inst(kB3Ln, kb, nco_ln, -1, p);
+    }
+    if (use_b3) {
         // 6 tiles per workgroup where that divides the output evenly; never with the LayerNorm prologue (that instantiation
         // needs 2 registers more than the 256 a wave has at two waves per SIMD)
-        int nco = (!a.ln_w && (NT % 6 == 0 || (NT % 4 != 0 && NT > 8))) ? 6 : 4;
+        int nco = (!ln && (NT % 6 == 0 || (NT % 4 != 0 && NT > 8))) ? 6 : 4;
         // Paired form (two output groups per 512-thread workgroup, the pairs of a pixel tile on one XCD): x is fetched once per
         // pixel tile instead of once per group.  It halves the workgroup count, so it is taken where every CU still gets one;
         // smaller launches keep the unpaired form and the rule below.
-        const long units = (long)cdiv(a.P, 256) * a.B;
-        bool pair = !a.ln_w && cdiv(NT, nco) > 1 && units * cdiv(cdiv(NT, nco), 2) >= 256;
-#ifdef RF_DIAG   // diagnostic build only: RF_B3_PAIR=1 takes the paired form at any launch size, RF_B3_PAIR=0 never
-        if (const char* e = getenv("RF_B3_PAIR")) pair = !a.ln_w && cdiv(NT, nco) > 1 && e[0] != '0';
-#endif
+        const bool pair = !ln && cdiv(NT, nco) > 1 && (force_pair >= 0 ? force_pair != 0 : units * cdiv(cdiv(NT, nco), 2) >= 256);
         // one frame at levels 2-3: fewer than 256 workgroups -- two output tiles per workgroup instead of four fills more CUs
-        if (!pair && !a.ln_w && nco == 4 && NT % 2 == 0 && units * cdiv(NT, 4) < 256) nco = 2;
+        if (!pair && !ln && nco == 4 && NT % 2 == 0 && units * cdiv(NT, 4) < 256) nco = 2;
         const int ngroups = cdiv(NT, nco);
-        dim3 grid((unsigned)(cdiv(a.P, 256) * ngroups), (unsigned)a.B, 1);
         // the flat grid of the paired form: whole chunks of 8 units x pairs (conv1x1_group_grid), as one 32-bit workgroup id
         const long pair_ids = (units + 7) / 8 * 8 * cdiv(ngroups, 2);
         RF_CHECK_ARG(!pair || pair_ids < (1L << 31), "conv1x1: %ld pixel tiles x %d output groups is too large a grid", units, ngroups);
-        // the unpaired key names the family by its first two arguments (bench.py's lookup covers <.., false, false> with it);
-        // the paired form has a key of its own, so a profile shows which form a launch took
-        if (pair) snprintf(key, sizeof(key), "conv1x1_b3_kernel<%d, false, true>", nco);
-        else snprintf(key, sizeof(key), "conv1x1_b3_kernel<%d, %s>", nco, a.ln_w ? "true" : "false");
-        ProfScope prof(st, key, work_flops, work_bytes);
-        if (pair) {
-            const unsigned gx = conv1x1_group_grid((unsigned)units, (unsigned)cdiv(ngroups, 2));
-            if (nco == 6) conv1x1_b3_kernel<6, false, true><<<gx, 512, 0, st>>>(a, ngroups);
-            else conv1x1_b3_kernel<4, false, true><<<gx, 512, 0, st>>>(a, ngroups);
-        } else if (nco == 6) {
-            conv1x1_b3_kernel<6, false><<<grid, 256, 0, st>>>(a, ngroups);
-        } else if (nco == 2) {
-            conv1x1_b3_kernel<2, false><<<grid, 256, 0, st>>>(a, ngroups);
-        } else {
-            if (a.ln_w) conv1x1_b3_kernel<4, true><<<grid, 256, 0, st>>>(a, ngroups);
-            else conv1x1_b3_kernel<4, false><<<grid, 256, 0, st>>>(a, ngroups);
-        }
-    } else if (NS <= 16 || (NS <= 32 && !a.ln_w && !a.res)) {
+        p->karg[0] = ngroups;
+        if (pair) { p->grid[0] = conv1x1_group_grid((unsigned)units, (unsigned)cdiv(ngroups, 2)); p->grid[1] = 1; }
+        else p->grid[0] = (unsigned)(ptiles * ngroups);
+        return find_inst(kB3, nco, ln, pair, p);
+    }
+    if (NS <= 16 || (NS <= 32 && !ln && !a.res)) {
         const int ks = NS <= 4 ? 4 : NS <= 8 ? 8 : NS <= 12 ? 12 : NS <= 16 ? 16 : NS <= 24 ? 24 : 32;
         // output tiles per workgroup: weight slice <= ~60 KB, and <= 8 tiles when the residual rows
         // are prefetched into registers
@@ -987,50 +1004,43 @@ int launch_conv1x1(const Conv1x1Args& a, hipStream_t st) {
         if (a.res && cap > 4) cap = 4;
         // the four-residual-tile instantiations with K <= 32 or a LayerNorm prologue spill (28-296 bytes of scratch) next to
         // their prefetched loads: such shapes (no layer of RawFormer; reachable through rf_conv1x1) take two tiles per workgroup
-        if (a.res && (ks <= 8 || a.ln_w) && cap > 2) cap = 2;
-        int ntw = NT < cap ? NT : cap;
+        if (a.res && (ks <= 8 || ln) && cap > 2) cap = 2;
+        const int ntw = NT < cap ? NT : cap;
         const int ngroups = cdiv(NT, ntw);
         const int tpad = cdiv(ntw, 2) * 2;
-        const size_t lds = ((size_t)ks * tpad * 64 + tpad * 16 + 8 * ks) * sizeof(float);
+        p->lds = ((size_t)ks * tpad * 64 + tpad * 16 + 8 * ks) * sizeof(float);
         // persistent workgroups: enough to fill every CU at this kernel's occupancy, split over the images
         const int slots = 256 * (ks <= 8 ? 3 : 2);
         int wgs = cdiv(slots, a.B * ngroups);
-        if (wgs > cdiv(a.P, 256)) wgs = cdiv(a.P, 256);
-        dim3 grid((unsigned)(wgs * ngroups), (unsigned)a.B, 1);
-        // the key is the instantiation launch_res picks (= the kernel name rocprofv3 reports): <KS, LN, RT, DBUF>
-        const int rt = ks <= 16 ? (a.res ? (ntw > 2 ? 4 : 2) : 0) : 0;
-        const bool dbuf = ks <= 16 && !(ks > 8 && rt == 4);
-        snprintf(key, sizeof(key), "conv1x1_res_kernel<%d, %s, %d, %s>", ks, (ks <= 16 && a.ln_w) ? "true" : "false", rt, dbuf ? "true" : "false");
-        ProfScope prof(st, key, work_flops, work_bytes);
-        switch (ks) {
-            case 4: launch_res<4>(a, ntw, ngroups, grid, lds, st); break;
-            case 8: launch_res<8>(a, ntw, ngroups, grid, lds, st); break;
-            case 12: launch_res<12>(a, ntw, ngroups, grid, lds, st); break;
-            case 16: launch_res<16>(a, ntw, ngroups, grid, lds, st); break;
-            case 24: launch_res<24>(a, ntw, ngroups, grid, lds, st); break;
-            default: launch_res<32>(a, ntw, ngroups, grid, lds, st); break;
-        }
-    } else {
-        // accumulator tiles per workgroup: 8 (128 channels) unless that would be mostly padding -- or unless the grid
-        // would fill the 512 resident workgroup slots badly (level 3 of config 2: 256 or 768 workgroups = half-empty
-        // rounds); 4 tiles per workgroup double the grid.  The k order per output is the same either way (same bits).
-        int nco = (NT % 8 == 0 || NT > 12) ? 8 : 4;
-        if (nco == 8) {
-            const long units = (long)cdiv(a.P, 256) * a.B;
-            const long cost8 = ((units * cdiv(NT, 8) + 511) / 512) * 8, cost4 = ((units * cdiv(NT, 4) + 511) / 512) * 4;
-            if (cost4 < cost8) nco = 4;
-        }
-        const int ngroups = cdiv(NT, nco);
-        dim3 grid((unsigned)(cdiv(a.P, 256) * ngroups), (unsigned)a.B, 1);
-        snprintf(key, sizeof(key), "conv1x1_stream_kernel<%d, %d, %s>", nco, nco == 8 ? 4 : 8, a.ln_w ? "true" : "false");
-        ProfScope prof(st, key, work_flops, work_bytes);
-        if (nco == 8) {
-            if (a.ln_w) conv1x1_stream_kernel<8, 4, true><<<grid, 256, 0, st>>>(a, ngroups);
-            else conv1x1_stream_kernel<8, 4, false><<<grid, 256, 0, st>>>(a, ngroups);
-        } else {
-            if (a.ln_w) conv1x1_stream_kernel<4, 8, true><<<grid, 256, 0, st>>>(a, ngroups);
-            else conv1x1_stream_kernel<4, 8, false><<<grid, 256, 0, st>>>(a, ngroups);
-        }
+        if (wgs > ptiles) wgs = ptiles;
+        p->grid[0] = (unsigned)(wgs * ngroups);
+        p->karg[0] = ntw; p->karg[1] = ngroups;
+        return find_inst(kRes, ks, ln, a.res ? (ntw > 2 ? 4 : 2) : 0, p);      // residual tiles held in registers
+    }
+    // accumulator tiles per workgroup: 8 (128 channels) unless that would be mostly padding -- or unless the grid
+    // would fill the 512 resident workgroup slots badly (level 3 of config 2: 256 or 768 workgroups = half-empty
+    // rounds); 4 tiles per workgroup double the grid.  The k order per output is the same either way (same bits).
+    int nco = (NT % 8 == 0 || NT > 12) ? 8 : 4;
+    if (nco == 8) {
+        const long cost8 = ((units * cdiv(NT, 8) + 511) / 512) * 8, cost4 = ((units * cdiv(NT, 4) + 511) / 512) * 4;
+        if (cost4 < cost8) nco = 4;
+    }
+    p->karg[0] = cdiv(NT, nco);
+    p->grid[0] = (unsigned)(ptiles * p->karg[0]);
+    return find_inst(kStream, nco, -1, ln, p);
+}
+
+bool conv1x1_ln_single_pass(const Conv1x1Args& a) {
+    Conv1x1Plan p;
+    return plan_conv1x1(a, &p) != RF_OK || p.ln_single_pass;      // arguments without a plan: launch_conv1x1 reports them
+}
+
+int launch_conv1x1(const Conv1x1Args& a, hipStream_t st) {
+    Conv1x1Plan p;
+    RF_TRY(plan_conv1x1(a, &p));
+    {
+        ProfScope prof(st, p.key, p.flops, p.bytes);
+        kInst[p.inst].launch(a, p, st);
     }
     return check_launch("conv1x1");
 }

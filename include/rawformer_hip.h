@@ -210,6 +210,13 @@ int rf_conv3x3(const float* in, float* out, const float* weight, const float* bi
 int rf_convT2x2_scratch_bytes(int Cin, int Cout, size_t* bytes);
 int rf_convT2x2(const float* in, float* out, const float* weight, const float* bias, void* scratch,
                 int B, int Cin, int Cout, int h, int w, void* stream);
+/* Host only, no launch, no GPU needed: what rf_conv1x1 (transposed == 0: b3_weights = 1) or rf_convT2x2 (transposed != 0: C1 = Cin,
+ * C2 = ln = res = b3_weights = 0) launches for these sizes with 16-byte aligned dense operands; ln / res: a LayerNorm prologue /
+ * a residual is present; b3_weights = 0 plans as the internal callers without bf16x3 weights do.  key: the kernel instantiation
+ * (= its profiler key), grid[3], block and dynamic LDS bytes of the launch; *ln_single_pass: the LayerNorm prologue would read the
+ * input once (the schedules run LayerNorm as its own pass where it would not). */
+int rf_conv1x1_plan(int B, int C1, int C2, int Cout, int h, int w, int ln, int res, int transposed, int b3_weights,
+                    char* key, size_t key_len, int* grid, int* block, size_t* lds_bytes, int* ln_single_pass);
 /* Attention.forward: FrequencyawareLumaChromaAttentionRAWFormer.py:212-235.
  * Takes the 6 raw parameter tensors; scratch from rf_chan_attn_scratch_bytes. */
 int rf_chan_attn_scratch_bytes(int B, int C, int heads, int h, int w, size_t* bytes);

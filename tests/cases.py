@@ -276,3 +276,81 @@ def launch_case(tag, device):
     x = (2 * torch.rand((b, dim << lvl, hh >> lvl, ww >> lvl), generator=g) - 1).to(device)
     packed = torch.rand((b, 4, hh, ww), generator=g).to(device) if variant in ("flca", "multilvl") else None
     return m, lambda: m.forward_stage(stage, x, packed)
+
+
+# ---- 1x1 GEMM selection: tools/make_conv1x1_keys.py records, test_conv1x1_plan.py compares.
+# tag -> (C1, C2, Cout, B, h, w, flags); flags: "ln" LayerNorm prologue, "res" residual (no bias), "T" ConvTranspose2d(C1, Cout, 2, 2)
+# through ops.conv_transpose2x2 (GEMM rows 4 Cout, no bf16x3 weights).  Derived from the ladders of plan_conv1x1 (rf_gemm1x1.hip),
+# in its order, at the smallest frame that reaches each instantiation (K = C1 + C2, NT = Cout / 16, units = pixel tiles x images):
+#   scalar      P % 4 != 0 | a residual with Cout % 16 != 0
+#   b3_ln       LayerNorm, K = 64 / 128 / 256 (KB = 2 / 4 / 8), Cout % 64 == 0, no residual; NCO 4 at K = 256 and Cout % 256 == 0,
+#               else 3 at Cout % 192 == 0, else 2; the blockIdx.z split at fewer than 128 workgroups and more than one chunk per wave
+#   b3          K >= 128 otherwise: NCO 6 at NT % 6 == 0, 2 below 256 workgroups at an even NT, else 4; LayerNorm (K = 512, or K = 128
+#               with a residual) only at 4; paired from units x pairs >= 256
+#   res         K <= 64, or K <= 128 without LayerNorm and residual: KS = 4, 8, 12, 16, 24, 32; RT 2 with a residual, 4 at KS 12 / 16
+#               without LayerNorm and Cout >= 48; one case with two output groups (K = 64 -> 256)
+#   stream      the rest (K = 96 with LayerNorm or a residual, K = 132): NCO 4 | 8 where 8 tiles fill the 512 slots no worse (129 units, NT 16)
+CONV1X1_CASES = {
+    "scalar_p35": (24, 0, 80, 1, 5, 7, "res"),
+    "scalar_cout24_res": (16, 0, 24, 1, 8, 8, "res"),
+    **{f"res_k{k}_o{o}{'_' + f.replace(' ', '_') if f else ''}": (k, 0, o, 1, 16, 16, f)
+       for k, o in ((16, 32), (32, 48)) for f in ("", "ln", "res", "ln res")},
+    **{f"res_k{k}_o{o}{'_' + f.replace(' ', '_') if f else ''}": (k, 0, o, 2, 12, 20, f)
+       for k, o, fs in ((48, 64, ("", "ln", "res", "ln res")), (48, 32, ("res",)), (64, 48, ("", "ln", "res", "ln res")), (64, 32, ("res",)))
+       for f in fs},
+    "res_k32_32_o48_res": (32, 32, 48, 1, 16, 16, "res"),
+    "res_k64_o256_two_groups": (64, 0, 256, 1, 16, 16, ""),
+    "res_k96_o48": (96, 0, 48, 1, 16, 16, ""),
+    "res_k112_o48": (112, 0, 48, 1, 16, 16, ""),
+    "stream_k96_o96_res": (96, 0, 96, 1, 16, 16, "res"),
+    "stream_k96_o96_ln": (96, 0, 96, 1, 16, 16, "ln"),
+    "stream_k132_o64": (132, 0, 64, 1, 8, 8, ""),
+    "stream8_k96_o256_res": (96, 0, 256, 1, 129, 256, "res"),
+    "stream8_k96_o256_ln": (96, 0, 256, 1, 129, 256, "ln"),
+    "b3_k128_o128": (128, 0, 128, 1, 16, 16, ""),
+    "b3_k128_o80": (128, 0, 80, 1, 16, 16, ""),
+    "b3_k64_64_o80_res": (64, 64, 80, 1, 12, 20, "res"),
+    "b3_k128_o96_res": (128, 0, 96, 1, 16, 16, "res"),
+    "b3_k512_o64_ln": (512, 0, 64, 1, 8, 8, "ln"),
+    "b3_k128_o64_ln_res": (128, 0, 64, 1, 16, 16, "ln res"),
+    "b3_pair_k128_o512": (128, 0, 512, 1, 128, 128, ""),
+    "b3_pair_k128_o768": (128, 0, 768, 1, 128, 128, ""),
+    "b3ln_k64_o128": (64, 0, 128, 1, 16, 16, "ln"),
+    "b3ln_k64_o192": (64, 0, 192, 1, 9, 20, "ln"),
+    "b3ln_k128_o256_zsplit": (128, 0, 256, 1, 16, 16, "ln"),
+    "b3ln_k128_o256_b8_no_split": (128, 0, 256, 8, 32, 32, "ln"),
+    "b3ln_k128_o192": (128, 0, 192, 1, 16, 16, "ln"),
+    "b3ln_k256_o128": (256, 0, 128, 1, 16, 16, "ln"),
+    "b3ln_k256_o384_zsplit": (256, 0, 384, 1, 16, 16, "ln"),
+    "b3ln_k256_o256": (256, 0, 256, 1, 12, 20, "ln"),
+    "convT_k32_o16": (32, 0, 16, 2, 8, 8, "T"),
+    "convT_k128_o64": (128, 0, 64, 1, 8, 8, "T"),
+    "convT_k256_o128": (256, 0, 128, 1, 4, 6, "T"),
+}
+
+
+def conv1x1_case(tag):
+    """Inputs of CONV1X1_CASES[tag] (ranges and weight scaling of test_conv1x1_groups.inputs; the LayerNorm input and affine of
+    test_gpu_ops.test_conv1x1) and ``run(ops, device)``, the case's one call."""
+    c1, c2, cout, b, h, w, flags = CONV1X1_CASES[tag]
+    k = c1 + c2
+    t = {"x": rnd("g.x", (b, c1, h, w)), "bias": rnd("g.b", (cout,))}
+    if "T" in flags:
+        t["w"] = rnd("g.w", (k, cout, 2, 2)) / np.sqrt(k)
+    else:
+        t["w"] = rnd("g.w", (cout, k, 1, 1)) / np.sqrt(k)
+    if c2:
+        t["x2"] = rnd("g.x2", (b, c2, h, w))
+    if "ln" in flags:
+        t["x"] = t["x"] * 2.0 + 0.7
+        t["ln_w"], t["ln_b"] = rnd("g.lw", (k,), 0.5, 1.5), rnd("g.lb", (k,))
+    if "res" in flags:
+        t["res"] = rnd("g.res", (b, cout, h, w))
+
+    def run(ops, device):
+        d = {n: v.to(device) for n, v in t.items()}
+        if "T" in flags:
+            return ops.conv_transpose2x2(d["x"], d["w"], d["bias"])
+        return ops.conv1x1(d["x"], d["w"], None if "res" in flags else d["bias"], x2=d.get("x2"), ln_weight=d.get("ln_w"),
+                           ln_bias=d.get("ln_b"), residual=d.get("res"))
+    return t, run
