@@ -106,6 +106,7 @@ SIGNATURES = {
     "rf_rfft2_polar_scratch_bytes": (_i, [_i, _i, _i, _psz]),
     "rf_rfft2_polar": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "rf_polar_irfft2": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "rf_fft_plan": (_i, [_i, _i, _i, C.POINTER(_i)]),
     "rf_feb_scratch_bytes": (_i, [_i, _i, _i, _i, _psz]),
     "rf_feb": (_i, [_vp, _vp, C.POINTER(_vp), _vp, _i, _i, _i, _i, _vp]),
     "rf_ffab_scratch_bytes": (_i, [_i, _i, _i, _i, _psz]),

@@ -266,6 +266,16 @@ int rf_conv1x1_plan(int B, int C1, int C2, int Cout, int h, int w, int ln, int r
     return RF_OK;
 }
 
+int rf_fft_plan(int planes, int h, int w, int out[10]) {
+    RF_CHECK_ARG(out, "fft_plan: bad arguments");
+    FftPlan p;
+    RF_TRY(plan_fft("fft_plan", planes, h, w, &p));
+    const int plan[10] = {p.log2w, p.log2h, p.L, p.TC, (int)p.gx, (int)p.gy, cdiv(cdiv(p.rows, p.L), (int)p.gx), cdiv(p.units, (int)p.gy),
+                          (int)p.lds_rows, (int)p.lds_cols};
+    for (int i = 0; i < 10; ++i) out[i] = plan[i];
+    return RF_OK;
+}
+
 // scratch layout of rf_chan_attn: packed qkv weights | qkv_pre | qkv | gram partials | folded weights
 struct AttnScratch {
     size_t wqkv, wqkv3, pre, qkv, partial, wfold, wfold3, total;

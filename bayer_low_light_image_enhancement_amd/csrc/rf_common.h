@@ -430,6 +430,16 @@ int run_chan_attn(const TbParams& p, const float* in, float* out, bool residual,
                   hipStream_t st, bool no_fuse = false, bool no_fuse_attn = false);
 
 // ---- rfft2 / irfft2 with the polar maps of FEB (rf_fft.hip); cscratch: planes * h * (w/2 + 1) complex values
+// What both launchers launch for [planes][h][w], decided on the host alone (no HIP call): plan_fft is the single statement of the
+// geometry and of the argument checks.  A row workgroup takes L rows at a time and a column workgroup TC columns of one plane.
+struct FftPlan {
+    int log2w, log2h;          // per axis: log2 of the line length (radix 2), or -1 (direct DFT)
+    int L, TC;
+    int wf, rows, units;       // w/2 + 1;  planes * h lines for the row kernels;  planes * ceil(wf / TC) column tiles
+    unsigned gx, gy;           // grids of the row and the column kernel: row groups / column tiles, capped (persistent loops)
+    size_t lds_rows, lds_cols; // dynamic LDS bytes
+};
+int plan_fft(const char* what, int planes, int h, int w, FftPlan* p);    // RF_E_INVALID (and the error text) for sizes the launchers refuse
 int launch_rfft2_polar(const float* in, float* mag, float* pha, float2* cscratch, int planes, int h, int w, hipStream_t st);
 int launch_polar_irfft2(const float* mag, const float* pha, const float* res, float* out, float2* cscratch, int planes, int h, int w,
                         float lim, hipStream_t st);

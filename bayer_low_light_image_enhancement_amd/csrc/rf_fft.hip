@@ -12,15 +12,18 @@
 //                          does); epilogue: + clamp(x, -10, 10), clamp(-10, 10)
 //
 // A line of length n lives in LDS as n complex values.  n = 2^k: radix-2 decimation in time (bit-reversed load, k
-// in-place stages, one barrier each).  Any other n (e.g. 712 x 1064 = the LL band of a 1424 x 2128 frame): direct O(n^2)
-// DFT out of the same LDS line with an exact twiddle index (j k mod n) -- a correctness path, ~n/log2(n) times the work.
-// Twiddles come from sincospif (argument exact in float for n <= 2^23), so the error growth matches a table-driven host
-// FFT (pocketfft in the reference: O(1e-7 log n) relative).
+// in-place stages, one barrier each).  Any other n (e.g. 712 x 1072 = the LL band of a packed 1424 x 2144 frame, a SID frame
+// padded to the multiple of 32 variant='wfb' asks of the width): direct O(n^2) DFT out of the same LDS line with an exact
+// twiddle index (j k mod n) -- a correctness path, ~n/log2(n) times the work.
+// Twiddles come from sincospif.  Its argument 2 k / n is exact in float only for a power of two n, where the error
+// growth matches a table-driven host FFT (pocketfft in the reference: O(1e-7 log n) relative); for any other n the quotient is
+// rounded once, a phase error of at most 2^-24 * 2 pi per twiddle (tests/test_fft_lines.py measures what the n terms add up to).
 //
 // The four bins of a real 2-D transform that are real by symmetry -- (0|h/2, 0|w/2) -- get Im = +0 exactly, as the
 // reference produces them: angle() of a negative real must be +pi, not -pi (it feeds a 1x1 MLP, i.e. is NOT 2 pi
 // periodic downstream).  Elsewhere a phase within rounding of the +-pi cut is ill-conditioned in the reference too;
 // tests state their tolerance accordingly.
+#include <climits>
 #include "rf_common.h"
 
 namespace rf {
@@ -220,41 +223,48 @@ static int fft_geometry(int n, const char* what, int* log2n) {
     return RF_OK;
 }
 
+int plan_fft(const char* what, int planes, int h, int w, FftPlan* p) {
+    RF_CHECK_ARG(w % 2 == 0, "%s: width %d must be even (irfft2 with s=(H,W) inverts rfft2 only then)", what, w);
+    if (int rc = fft_geometry(w, what, &p->log2w)) return rc;
+    if (int rc = fft_geometry(h, what, &p->log2h)) return rc;
+    p->wf = w / 2 + 1;
+    // the kernels count lines and column tiles in int, and step past the last one by up to a grid of them
+    RF_CHECK_ARG(planes >= 1 && (int64_t)planes * h <= INT_MAX / 2 && (int64_t)planes * p->wf <= INT_MAX / 2,
+                 "%s: %d planes of %d x %d: more than 2^30 lines", what, planes, h, w);
+    p->rows = planes * h;
+    p->L = 2048 / w; if (p->L < 1) p->L = 1;
+    p->TC = 2048 / h; if (p->TC < 1) p->TC = 1; if (p->TC > 16) p->TC = 16;
+    p->units = planes * cdiv(p->wf, p->TC);
+    const int groups = cdiv(p->rows, p->L);
+    p->gx = groups > 4096 ? 4096 : groups;
+    p->gy = p->units > 4096 ? 4096 : p->units;
+    // the line and the direct path's `tmp` line of the same size: 64 KB at n = 4096, the most a launch gets without opting in
+    p->lds_rows = (size_t)2 * p->L * w * sizeof(float2);
+    p->lds_cols = (size_t)2 * p->TC * h * sizeof(float2);
+    return RF_OK;
+}
+
 // rfft2 (ortho) of [planes][h][w] followed by |.| + 1e-6 and angle: mag / pha are [planes][h][w/2 + 1]; `cscratch` holds
 // planes * h * (w/2 + 1) complex values
 int launch_rfft2_polar(const float* in, float* mag, float* pha, float2* cscratch, int planes, int h, int w, hipStream_t st) {
-    RF_CHECK_ARG(w % 2 == 0, "rfft2: width %d must be even (irfft2 with s=(H,W) needs it to invert)", w);
-    int l2w, l2h;
-    if (int rc = fft_geometry(w, "rfft2", &l2w)) return rc;
-    if (int rc = fft_geometry(h, "rfft2", &l2h)) return rc;
-    const int wf = w / 2 + 1, rows = planes * h;
-    int L = 2048 / w; if (L < 1) L = 1;
-    int gx = cdiv(rows, L); if (gx > 4096) gx = 4096;
-    ProfScope prof(st, "rfft2_polar(2 kernels)", 0.0, 4.0 * planes * ((double)h * w + 6.0 * h * wf));
-    fft_rows_r2c_kernel<<<gx, 256, (size_t)2 * L * w * sizeof(float2), st>>>(in, cscratch, rows, w, l2w, L, 1.0f / sqrtf((float)w));
-    int TC = 2048 / h; if (TC < 1) TC = 1; if (TC > 16) TC = 16;
-    int gy = planes * cdiv(wf, TC); if (gy > 4096) gy = 4096;
-    fft_cols_kernel<false><<<gy, 256, (size_t)2 * TC * h * sizeof(float2), st>>>(cscratch, nullptr, nullptr, nullptr, mag, pha, planes, h, wf,
-                                                                                  w / 2, l2h, TC, 1.0f / sqrtf((float)h));
+    FftPlan p;
+    RF_TRY(plan_fft("rfft2", planes, h, w, &p));
+    ProfScope prof(st, "rfft2_polar(2 kernels)", 0.0, 4.0 * planes * ((double)h * w + 6.0 * h * p.wf));
+    fft_rows_r2c_kernel<<<p.gx, 256, p.lds_rows, st>>>(in, cscratch, p.rows, w, p.log2w, p.L, 1.0f / sqrtf((float)w));
+    fft_cols_kernel<false><<<p.gy, 256, p.lds_cols, st>>>(cscratch, nullptr, nullptr, nullptr, mag, pha, planes, h, p.wf, w / 2, p.log2h, p.TC,
+                                                          1.0f / sqrtf((float)h));
     return check_launch("rfft2_polar");
 }
 
 // irfft2 (ortho, s = (h, w)) of mag * exp(i pha), then out = clamp(. + clamp(res, +-lim), +-lim)   (res may be null)
 int launch_polar_irfft2(const float* mag, const float* pha, const float* res, float* out, float2* cscratch, int planes, int h, int w,
                         float lim, hipStream_t st) {
-    RF_CHECK_ARG(w % 2 == 0, "irfft2: width %d must be even", w);
-    int l2w, l2h;
-    if (int rc = fft_geometry(w, "irfft2", &l2w)) return rc;
-    if (int rc = fft_geometry(h, "irfft2", &l2h)) return rc;
-    const int wf = w / 2 + 1, rows = planes * h;
-    ProfScope prof(st, "polar_irfft2(2 kernels)", 0.0, 4.0 * planes * (2.0 * h * w + 6.0 * h * wf));
-    int TC = 2048 / h; if (TC < 1) TC = 1; if (TC > 16) TC = 16;
-    int gy = planes * cdiv(wf, TC); if (gy > 4096) gy = 4096;
-    fft_cols_kernel<true><<<gy, 256, (size_t)2 * TC * h * sizeof(float2), st>>>(nullptr, cscratch, mag, pha, nullptr, nullptr, planes, h, wf,
-                                                                                 w / 2, l2h, TC, 1.0f / sqrtf((float)h));
-    int L = 2048 / w; if (L < 1) L = 1;
-    int gx = cdiv(rows, L); if (gx > 4096) gx = 4096;
-    fft_rows_c2r_kernel<<<gx, 256, (size_t)2 * L * w * sizeof(float2), st>>>(cscratch, res, out, rows, w, l2w, L, 1.0f / sqrtf((float)w), lim);
+    FftPlan p;
+    RF_TRY(plan_fft("irfft2", planes, h, w, &p));
+    ProfScope prof(st, "polar_irfft2(2 kernels)", 0.0, 4.0 * planes * (2.0 * h * w + 6.0 * h * p.wf));
+    fft_cols_kernel<true><<<p.gy, 256, p.lds_cols, st>>>(nullptr, cscratch, mag, pha, nullptr, nullptr, planes, h, p.wf, w / 2, p.log2h, p.TC,
+                                                         1.0f / sqrtf((float)h));
+    fft_rows_c2r_kernel<<<p.gx, 256, p.lds_rows, st>>>(cscratch, res, out, p.rows, w, p.log2w, p.L, 1.0f / sqrtf((float)w), lim);
     return check_launch("polar_irfft2");
 }
 

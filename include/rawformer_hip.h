@@ -253,6 +253,11 @@ int rf_flca_guidance(const float* packed, float* guide, void* scratch, int B, in
 int rf_rfft2_polar_scratch_bytes(int planes, int h, int w, size_t* bytes);
 int rf_rfft2_polar(const float* in, float* mag, float* pha, void* scratch, int planes, int h, int w, void* stream);
 int rf_polar_irfft2(const float* mag, const float* pha, float* out, void* scratch, int planes, int h, int w, void* stream);
+/* Host only, no launch, no GPU needed: what rf_rfft2_polar and rf_polar_irfft2 launch for [planes,h,w], or the error they return.
+ * out = { log2 w, log2 h (-1: that axis takes the direct DFT),  L (rows per row workgroup), TC (columns per column workgroup),
+ *         grid of the row kernel, grid of the column kernel,  most trips of a row / of a column workgroup through its persistent
+ *         loop,  dynamic LDS bytes of the row / of the column kernel }. */
+int rf_fft_plan(int planes, int h, int w, int out[10]);
 /* FEB.forward (blocks.py:23-39).  prm = HOST array of 10 device pointers in state_dict order:
  * fpre.{w,b}, process1.0.{w,b}, process1.2.{w,b}, process2.0.{w,b}, process2.2.{w,b}.  [B,nc,h,w] -> same. */
 int rf_feb_scratch_bytes(int B, int nc, int h, int w, size_t* bytes);

@@ -508,20 +508,24 @@ def feb(x: Tensor, p: Dict[str, Tensor], pre: str, exact_symmetric_bins: bool = 
     return (out + x).clamp(-10.0, 10.0)
 
 
-def process_block(x: Tensor, p: Dict[str, Tensor], pre: str) -> Tensor:
+def process_block(x: Tensor, p: Dict[str, Tensor], pre: str, exact_symmetric_bins: bool = False) -> Tensor:
     """ProcessBlock.forward (blocks.py:48-55): ``cat(FEB(x)) + x`` with ``cat`` a 1x1 conv."""
-    return F.conv2d(feb(x, p, pre + "frequency_process."), p[pre + "cat.weight"], p[pre + "cat.bias"]) + x
+    return F.conv2d(feb(x, p, pre + "frequency_process.", exact_symmetric_bins), p[pre + "cat.weight"], p[pre + "cat.bias"]) + x
 
 
-def ffab(x: Tensor, p: Dict[str, Tensor], pre: str) -> Tensor:
-    """FFAB.forward (blocks.py:83-92): seven ProcessBlocks with dense concatenations."""
-    x = process_block(F.conv2d(x, p[pre + "conv0.0.weight"], p[pre + "conv0.0.bias"]), p, pre + "conv0.1.")
-    x1 = process_block(x, p, pre + "conv1.")
-    x2 = process_block(x1, p, pre + "conv2.")
-    x3 = process_block(x2, p, pre + "conv3.")
+def ffab(x: Tensor, p: Dict[str, Tensor], pre: str, exact_symmetric_bins: bool = False, cat=torch.cat) -> Tensor:
+    """FFAB.forward (blocks.py:83-92): seven ProcessBlocks with dense concatenations.  ``exact_symmetric_bins``: see ``feb``;
+    ``cat``: the concatenation (a test replaces it to measure what a wrong one would cost)."""
+    def pb(t, name):
+        return process_block(t, p, pre + name, exact_symmetric_bins)
+
+    x = pb(F.conv2d(x, p[pre + "conv0.0.weight"], p[pre + "conv0.0.bias"]), "conv0.1.")
+    x1 = pb(x, "conv1.")
+    x2 = pb(x1, "conv2.")
+    x3 = pb(x2, "conv3.")
 
     def tail(a, b, name):
-        t = process_block(torch.cat((a, b), dim=1), p, pre + name + ".0.")
+        t = pb(cat((a, b), dim=1), name + ".0.")
         return F.conv2d(t, p[pre + name + ".1.weight"], p[pre + name + ".1.bias"])
 
     x4 = tail(x2, x3, "conv4")

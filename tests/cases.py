@@ -354,3 +354,40 @@ def conv1x1_case(tag):
         return ops.conv1x1(d["x"], d["w"], None if "res" in flags else d["bias"], x2=d.get("x2"), ln_weight=d.get("ln_w"),
                            ln_bias=d.get("ln_b"), residual=d.get("res"))
     return t, run
+
+
+# ---- FFT lines: test_fft_lines.py.  tag -> ((planes, h, w), the regime the case is there for, as rf_fft_plan states it:
+# log2 w / log2 h (-1: direct DFT), L rows per row workgroup, TC columns per column workgroup, most trips of a row / of a column
+# workgroup through its persistent loop).  The shapes follow the plan's constants (rf_fft.hip, plan_fft: a line budget of 2048 values
+# per workgroup, TC <= 16, grids capped at 4096, lines <= 4096, direct lines <= 2048); if those change, these change with them.
+FFT_LINE_CASES = {
+    # long radix-2 lines: 12 stages and the largest LDS request; wf = 2049 = 128 * 16 + 1, so the last column tile holds one column
+    "r2_row4096": ((2, 64, 4096), dict(log2w=12, log2h=6, L=1, TC=16, trips=(1, 1))),
+    "r2_col4096": ((2, 4096, 64), dict(log2w=6, log2h=12, L=32, TC=1, trips=(1, 1))),
+    "r2_512x1024": ((1, 512, 1024), dict(log2w=10, log2h=9, L=2, TC=4, trips=(1, 1))),
+    # long direct lines: the LL band of a padded SID frame (packed 1424 x 2144); the longest direct row; the longest direct column, odd
+    "direct_712x1072": ((1, 712, 1072), dict(log2w=-1, log2h=-1, L=1, TC=2, trips=(1, 1))),
+    "direct_row2046": ((1, 90, 2046), dict(log2w=-1, log2h=-1, L=1, TC=16, trips=(1, 1))),
+    "direct_col2047": ((1, 2047, 6), dict(log2w=-1, log2h=-1, L=341, TC=1, trips=(1, 1))),
+    "mixed_256x288": ((1, 256, 288), dict(log2w=-1, log2h=8, L=7, TC=8, trips=(1, 1))),
+    # second trips: 5120 row groups on a grid of 4096 (some workgroups take two lines, some one); 460 * 9 = 4140 column tiles on a
+    # grid of 4096; 16 405 rows in groups of 4, so that the last group (of the second trip) has one live line, with direct columns
+    "row_trip2": ((5, 1024, 2048), dict(log2w=11, log2h=10, L=1, TC=2, trips=(2, 1))),
+    "col_trip2": ((460, 2048, 16), dict(log2w=4, log2h=11, L=128, TC=1, trips=(2, 2))),
+    "ragged_trip2": ((17, 965, 512), dict(log2w=9, log2h=-1, L=4, TC=2, trips=(2, 1))),
+    # small edges: all four bins real; an odd height of 3 (no 2 y == h bins); odd direct height; a height of 2 under the longest row
+    "edge_2x2": ((3, 2, 2), dict(log2w=1, log2h=1, L=1024, TC=16, trips=(1, 1))),
+    "edge_3x4": ((2, 3, 4), dict(log2w=2, log2h=-1, L=512, TC=16, trips=(1, 1))),
+    "edge_15x22": ((1, 15, 22), dict(log2w=-1, log2h=-1, L=93, TC=16, trips=(1, 1))),
+    "edge_2x4096": ((1, 2, 4096), dict(log2w=12, log2h=1, L=1, TC=16, trips=(1, 1))),
+}
+
+
+def fft_plan(planes, h, w):
+    """rf_fft_plan as a dict (include/rawformer_hip.h); raises RuntimeError with the library's message for refused sizes."""
+    import ctypes as C
+    from bayer_low_light_image_enhancement_amd import _lib
+    out = (C.c_int * 10)()
+    _lib.check(_lib.load().rf_fft_plan(planes, h, w, out), "rf_fft_plan")
+    l2w, l2h, L, tc, gx, gy, trips_r, trips_c, lds_r, lds_c = out
+    return dict(log2w=l2w, log2h=l2h, L=L, TC=tc, grid=(gx, gy), trips=(trips_r, trips_c), lds=(lds_r, lds_c))

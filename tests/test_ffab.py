@@ -6,7 +6,13 @@ Tolerances.  Transforms: 2e-6 on |F| (values of O(1)); the phase is compared as 
 magnitude (|F| e^{i angle}), because angle() is ill-conditioned where |F| -> 0 and 2 pi-periodic at the +-pi cut, where the
 reference itself flips with rounding; the four bins that are real by symmetry must reproduce the reference's +pi / 0
 exactly.  FEB <= 2e-5, FFAB <= 2e-4 max-abs on outputs of magnitude up to ~30 (the reference's own float32-vs-float64
-difference on these cases is 1e-6 / 1e-5: tools in oracle/make_golden.py log it)."""
+difference on these cases is 1e-6 / 1e-5: tools in oracle/make_golden.py log it).
+
+The element-wise kernels (clamp, cat2, affine_clamp_add) run a grid of at most 4096 x 256 lanes and stride over the rest:
+``big_ffab`` and test_affine_clamp_add_strides are the cases with more elements than that; their bounds are stated there."""
+import ctypes as C
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -85,6 +91,42 @@ def test_oracle_wmb_wavelet_branch_matches_the_reference_modules():
     assert maxabs(R.wmb_ll_branch(rnd("wmb.wmb16.x", (2, 16, 16, 24), seed=62), wmb_params(16), ""), g["wmb16.out"]) <= 2e-5
 
 
+# ---- FFAB with more than 4096 x 256 elements per element-wise launch: nc = 8 at 1 x 8 x 256 x 288 (cat2 and FEB(16)'s clamp see
+# 16 * 256 * 288 = 1 179 648 elements; the FFT runs radix-2 columns and direct rows of 288).
+# At this size ~1e6 bins have a negative real part, and some lie within float32's reach of the branch cut of FEB's ``angle``: the
+# block as it stands has no single float32 answer (tests/test_wfb_model.py met that at 1e5 bins).  So ``process2.2.weight`` of every
+# FEB is zero and its bias kept: the phase fed to the inverse transform is a non-zero constant per channel and the output is
+# continuous in the input, with clamp, cat, both transforms, the magnitude MLP, the residual epilogue and the 2 nc tails all live
+# (tests/test_fft_lines.py holds the forward phase).  Bound: e64 <= 8 e32 + 2e-6 max|ref_f64| (tests/test_mamba.py), the reference
+# R.ffab in float64 with exact self-conjugate bins, e32 from the same in float32.
+BIG_NC, BIG_SHAPE = 8, (1, 8, 256, 288)
+RATIO, FLOOR = 8.0, 2e-6
+
+
+@functools.lru_cache(maxsize=None)
+def big_ffab():
+    p = params(ffab_spec(BIG_NC), 2100 + BIG_NC)
+    zeroed = [k for k in p if k.endswith("process2.2.weight")]
+    assert len(zeroed) == 7
+    for k in zeroed:
+        p[k] = torch.zeros_like(p[k])
+    x = rnd("ffab.big.x", BIG_SHAPE, seed=64)
+    ref64 = R.ffab(x.double(), f64(p), "", exact_symmetric_bins=True)
+    e32 = maxabs(R.ffab(x, p, "", exact_symmetric_bins=True), ref64)
+    mx = float(ref64.abs().max())
+    return {"x": x, "p": p, "ref64": ref64, "e32": e32, "max": mx, "bound": RATIO * e32 + FLOOR * mx}
+
+
+def test_big_ffab_case_is_well_conditioned_and_sees_the_second_half_of_cat():
+    c = big_ffab()
+    assert BIG_NC * 2 * BIG_SHAPE[2] * BIG_SHAPE[3] > 4096 * 256, "cat2 and FEB(2 nc)'s clamp take a second trip of their stride loop"
+    assert all(float(c["p"][k].abs().min()) > 0 for k in c["p"] if k.endswith("process2.2.bias")), "a non-zero phase per channel"
+    print(f"big ffab: e32 {c['e32']:.3e} max|ref| {c['max']:.3e} bound {c['bound']:.3e}")
+    assert c["e32"] < 1e-4 * c["max"], c
+    dropped = R.ffab(c["x"].double(), f64(c["p"]), "", exact_symmetric_bins=True, cat=lambda ts, dim: torch.cat((ts[0], torch.zeros_like(ts[1])), dim))
+    assert maxabs(dropped, c["ref64"]) > 10 * c["bound"], (maxabs(dropped, c["ref64"]), c["bound"])
+
+
 # ------------------------------------------------------------------------------------------ GPU
 def _dev(d, device):
     return {k: v.to(device) for k, v in d.items()}
@@ -147,3 +189,33 @@ def test_wmb_wavelet_branch(device):
     g = golden("ffab")
     out = ops.wmb_ll_branch(rnd("wmb.wmb16.x", (2, 16, 16, 24), seed=62).to(device), _dev(wmb_params(16), device))
     assert maxabs(out, g["wmb16.out"]) <= 2e-4
+
+
+@pytest.mark.gpu
+def test_big_ffab_strides_the_elementwise_kernels(device):
+    from bayer_low_light_image_enhancement_amd import ops
+    c = big_ffab()
+    out = ops.ffab(c["x"].to(device), _dev(c["p"], device)).cpu()
+    assert bool(torch.isfinite(out).all())
+    e64 = maxabs(out, c["ref64"])
+    msg = f"big ffab: e64 {e64:.3e} e32 {c['e32']:.3e} max|ref| {c['max']:.3e} | bound {c['bound']:.3e} ({e64 / c['bound']:.3f} of it)"
+    print(msg)
+    assert e64 <= c["bound"], msg
+
+
+@pytest.mark.gpu
+def test_affine_clamp_add_strides(device):
+    """n = 4096 * 256 + 257: a second trip of the stride loop for one full workgroup and one lane of the next.  Against float64 at
+    1e-6: one fused multiply-add and one addition in float32 on values below 2 are within 2 ulp(2) = 4.8e-7."""
+    from bayer_low_light_image_enhancement_amd import _lib
+    n = 4096 * 256 + 257
+    x, add = rnd("aca.x", (n,), -2.0, 2.0, seed=65).to(device), rnd("aca.add", (n,), seed=65).to(device)
+    out = torch.full((n + 256,), float("nan"), device=device)
+    with torch.cuda.device(device):
+        _lib.check(_lib.load().rf_affine_clamp_add(C.c_void_p(x.data_ptr()), C.c_void_p(add.data_ptr()), C.c_void_p(out.data_ptr()), n, 0.5, 0.5,
+                                                   0.0, 1.0, C.c_void_p(torch.cuda.current_stream().cuda_stream)), "rf_affine_clamp_add")
+    torch.cuda.synchronize()
+    inner = x.cpu().double() * 0.5 + 0.5
+    assert float((inner < 0).double().mean()) > 0.2 and float((inner > 1).double().mean()) > 0.2, "both clamp ends are reached"
+    assert maxabs(out[:n], add.cpu().double() + inner.clamp(0.0, 1.0)) <= 1e-6
+    assert bool(torch.isnan(out[n:]).all()), "written past n"
