@@ -18,20 +18,9 @@
 // broadcast reads) and the sum over n is a chain of FMAs in the lane, no cross-lane step.  A wave handles 64 channels of one
 // chunk; delta, x, z tiles of 64 channels x kT tokens go through LDS so that global accesses run along L.  No atomics, fixed
 // summation orders: two runs give the same bits.
-#include "rf_common.h"
+#include "rf_mamba.h"
 
 namespace rf {
-
-static constexpr int kN = 32;     // d_state
-static constexpr int kDc = 4;     // d_conv
-#ifndef RF_MAMBA_LC               // build-time only: tools/kbench.py compares libraries built with other values
-#define RF_MAMBA_LC 128
-#endif
-static constexpr int kLc = RF_MAMBA_LC;   // tokens per chunk
-static constexpr int kT = 16;             // tokens per LDS tile
-static constexpr int kBrow = kN + 4;      // floats per token row of the Bm / Cm tiles: 16-byte aligned rows, writes 2-way at worst
-static_assert(kLc % kT == 0 && kLc > kDc, "a chunk is a whole number of tiles and longer than the convolution");
-static constexpr float kLog2e = 1.44269504088896340736f;
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // in [rows][cols] (+ add, same layout) -> out [cols][rows] per image, with an optional LayerNorm along cols (cols <= 512).
@@ -291,14 +280,8 @@ __global__ void __launch_bounds__(256) mamba_carry_kernel(float* __restrict__ st
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-struct MambaPlan {
-    int D, Di, R, NR, nchunk;
-    size_t xz, xc, dbc, delta, state, sdelta, w_in, w_in3, w_x, w_x3, w_out, w_out3;   // float offsets
-    size_t floats;
-};
-
 // every refusal names the argument; nothing is launched or dereferenced before this returns RF_OK
-static int mamba_plan(const char* who, int B, int L, int D, int N, int K, int E, MambaPlan* p, Bump* bump) {
+int mamba_plan(const char* who, int B, int L, int D, int N, int K, int E, MambaPlan* p, Bump* bump) {
     RF_CHECK_ARG(N == kN, "%s: d_state %d is not supported (d_state must be %d)", who, N, kN);
     RF_CHECK_ARG(K == kDc, "%s: d_conv %d is not supported (d_conv must be %d)", who, K, kDc);
     RF_CHECK_ARG(D > 0 && D % 4 == 0 && D <= 512, "%s: d_model %d must be a positive multiple of 4, at most 512", who, D);
@@ -328,7 +311,7 @@ static int mamba_plan(const char* who, int B, int L, int D, int N, int K, int E,
 }
 
 // w == nullptr: wp and wp3 already hold the packed forms (the WFB handle's, rf_pack_params) and are only read
-static int mamba_gemm(const float* x, int K, const float* w, float* wp, float* wp3, float* out, int Cout, int B, int L, hipStream_t st) {
+int mamba_gemm(const float* x, int K, const float* w, float* wp, float* wp3, float* out, int Cout, int B, int L, hipStream_t st) {
     if (w) {
         RF_TRY(pack_1x1(w, wp, Cout, K, K, 1, st));
         RF_TRY(pack_1x1_b3(w, wp3, Cout, K, K, 1, st));
@@ -339,8 +322,8 @@ static int mamba_gemm(const float* x, int K, const float* w, float* wp, float* w
     return launch_conv1x1(a, st);
 }
 
-static int launch_tok_transpose(const float* in, const float* add, float* out, const float* lw, const float* lb, int B, int rows, int cols,
-                                hipStream_t st) {
+int launch_tok_transpose(const float* in, const float* add, float* out, const float* lw, const float* lb, int B, int rows, int cols,
+                         hipStream_t st) {
     const dim3 grid((unsigned)cdiv(rows, 32), (unsigned)B);
     const double el = (double)B * rows * cols;
     ProfScope prof(st, lw ? "tok_transpose_kernel<true>" : "tok_transpose_kernel<false>", 0.0, (add ? 12.0 : 8.0) * el);
@@ -349,16 +332,28 @@ static int launch_tok_transpose(const float* in, const float* add, float* out, c
     return check_launch("tok_transpose");
 }
 
-// channel-major Mamba: u, out [B][D][L]; ws = the plan's buffers.  prm: the nine tensors in the header's order.
-static int run_mamba(const MambaPlan& p, const float* u, float* out, const float* const* prm, float* ws, int B, int L, hipStream_t st,
-                     const WmPacked* pk = nullptr) {
-    const float *w_in = prm[0], *w_conv = prm[1], *b_conv = prm[2], *w_x = prm[3], *w_dt = prm[4], *b_dt = prm[5], *A_log = prm[6], *Dp = prm[7],
-                *w_out = prm[8];
+static ScanArgs scan_args(const MambaPlan& p, const float* const* prm, float* ws, int L) {
+    float *xz = ws + p.xz, *dbc = ws + p.dbc, *delta = ws + p.delta;
+    ScanArgs a{};
+    a.delta = delta; a.x = ws + p.xc; a.z = xz + (size_t)p.Di * L; a.z_bstride = (int64_t)2 * p.Di * L;
+    a.bm = dbc + (size_t)p.R * L; a.bc_bstride = (int64_t)p.NR * L; a.A_log = prm[6]; a.Dp = prm[7];
+    a.y = delta; a.state = ws + p.state; a.sdelta = ws + p.sdelta; a.Di = p.Di; a.L = L; a.nchunk = p.nchunk;
+    return a;
+}
+
+// one of the module's three projections: packed per call into the plan's buffers, or read from the handle's packed forms
+static int mamba_proj(const MambaPlan& p, const float* x, int K, const float* w, size_t o, size_t o3, const float* pw, const void* pw3, bool packed,
+                      float* dst, int Cout, float* ws, int B, int L, hipStream_t st) {
+    if (packed) return mamba_gemm(x, K, nullptr, const_cast<float*>(pw), static_cast<float*>(const_cast<void*>(pw3)), dst, Cout, B, L, st);
+    return mamba_gemm(x, K, w, ws + o, ws + o3, dst, Cout, B, L, st);
+}
+
+int mamba_forward_front(const MambaPlan& p, const float* u, const float* const* prm, float* ws, int B, int L, hipStream_t st, const WmPacked* pk) {
+    const float *w_in = prm[0], *w_conv = prm[1], *b_conv = prm[2], *w_x = prm[3], *w_dt = prm[4], *b_dt = prm[5], *A_log = prm[6];
     const int D = p.D, Di = p.Di;
     float *xz = ws + p.xz, *xc = ws + p.xc, *dbc = ws + p.dbc, *delta = ws + p.delta;
     auto gemm = [&](const float* x, int K, const float* w, size_t o, size_t o3, const float* pw, const void* pw3, float* dst, int Cout) {
-        if (pk) return mamba_gemm(x, K, nullptr, const_cast<float*>(pw), static_cast<float*>(const_cast<void*>(pw3)), dst, Cout, B, L, st);
-        return mamba_gemm(x, K, w, ws + o, ws + o3, dst, Cout, B, L, st);
+        return mamba_proj(p, x, K, w, o, o3, pw, pw3, pk != nullptr, dst, Cout, ws, B, L, st);
     };
     RF_TRY(gemm(u, D, w_in, p.w_in, p.w_in3, pk ? pk->in_proj : nullptr, pk ? pk->in_proj3 : nullptr, xz, 2 * Di));
     const double el = (double)B * Di * L;
@@ -376,10 +371,7 @@ static int run_mamba(const MambaPlan& p, const float* u, float* out, const float
         mamba_delta_kernel<<<dim3((unsigned)cdiv(L, 256), (unsigned)(Di / 4), (unsigned)B), 256, 0, st>>>(dbc, delta, w_dt, b_dt, Di, p.R, p.NR, L);
         RF_TRY(check_launch("mamba_delta"));
     }
-    ScanArgs a{};
-    a.delta = delta; a.x = xc; a.z = xz + (size_t)Di * L; a.z_bstride = (int64_t)2 * Di * L;
-    a.bm = dbc + (size_t)p.R * L; a.bc_bstride = (int64_t)p.NR * L; a.A_log = A_log; a.Dp = Dp;
-    a.y = delta; a.state = ws + p.state; a.sdelta = ws + p.sdelta; a.Di = Di; a.L = L; a.nchunk = p.nchunk;
+    const ScanArgs a = scan_args(p, prm, ws, L);
     const int ns = p.nchunk - 1;
     const double bc = 4.0 * B * kN * (double)L;
     if (ns > 0) {
@@ -392,13 +384,24 @@ static int run_mamba(const MambaPlan& p, const float* u, float* out, const float
         mamba_carry_kernel<<<dim3((unsigned)cdiv(Di * kN, 256), (unsigned)B), 256, 0, st>>>(a.state, a.sdelta, A_log, Di, ns);
         RF_TRY(check_launch("mamba_carry"));
     }
+    return RF_OK;
+}
+
+// channel-major Mamba: u, out [B][D][L]; ws = the plan's buffers.  prm: the nine tensors in the header's order.
+static int run_mamba(const MambaPlan& p, const float* u, float* out, const float* const* prm, float* ws, int B, int L, hipStream_t st,
+                     const WmPacked* pk = nullptr) {
+    RF_TRY(mamba_forward_front(p, u, prm, ws, B, L, st, pk));
+    const int Di = p.Di;
+    const ScanArgs a = scan_args(p, prm, ws, L);
+    const double el = (double)B * Di * L, bc = 4.0 * B * kN * (double)L;
     {
         // algorithmic HBM bytes of the scan: read delta, x, z, Bm, Cm, write y
         ProfScope prof(st, "mamba_scan_kernel<true>", 6.0 * kN * el, 16.0 * el + 2.0 * bc);
         mamba_scan_kernel<true><<<dim3((unsigned)p.nchunk, (unsigned)cdiv(Di, 64), (unsigned)B), 64, 0, st>>>(a);
         RF_TRY(check_launch("mamba_scan<true>"));
     }
-    return gemm(delta, Di, w_out, p.w_out, p.w_out3, pk ? pk->out_proj : nullptr, pk ? pk->out_proj3 : nullptr, out, D);
+    return mamba_proj(p, ws + p.delta, Di, prm[8], p.w_out, p.w_out3, pk ? pk->out_proj : nullptr, pk ? pk->out_proj3 : nullptr, pk != nullptr, out,
+                      p.D, ws, B, L, st);
 }
 
 struct WmPlan {

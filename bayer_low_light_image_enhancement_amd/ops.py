@@ -677,6 +677,34 @@ def mamba(u: torch.Tensor, params, prefix: str = "", d_state: int = 32, d_conv: 
     return out
 
 
+def mamba_backward(u: torch.Tensor, params, grad_out: torch.Tensor, prefix: str = "", d_state: int = 32, d_conv: int = 4, expand: int = 2,
+                   channel_major: bool = False, grads=None):
+    """The gradient of ``mamba``: ``(grad_u, grads)`` for ``grad_out`` = dL/d ``mamba(u, params)``, in ``u``'s layout.  ``grads`` maps
+    the module's state_dict keys (``prefix`` included) to the parameter gradients, with the shapes of ``mamba_param_shapes``
+    (``conv1d.weight``: ``[Di, 1, 4]``).  Passing the ``grads`` of an earlier call ADDS to its tensors (a training step sums
+    several modules' calls); ``grad_u`` is always a new tensor.  The forward intermediates are recomputed: nothing is kept from
+    a ``mamba`` call, and ``u`` and ``grad_out`` are not written."""
+    u, grad_out = _chk(u, "u"), _chk(grad_out, "grad_out")
+    if u.dim() != 3 or tuple(grad_out.shape) != tuple(u.shape):
+        raise RuntimeError(f"mamba_backward: expected 3-D u and grad_out of one shape, got {tuple(u.shape)} and {tuple(grad_out.shape)}")
+    b, l, d = (u.shape[0], u.shape[2], u.shape[1]) if channel_major else tuple(u.shape)
+    shapes = mamba_param_shapes(d, d_state, d_conv, expand)
+    ts = _shaped(params, prefix, _MAMBA_KEYS, shapes, "mamba_backward")
+    accumulate = grads is not None
+    if grads is None:
+        grads = {prefix + k: torch.empty_like(t) for k, t in zip(_MAMBA_KEYS, ts)}
+    gs = _shaped(grads, prefix, _MAMBA_KEYS, shapes, "mamba_backward (grads)")
+    if any(t.data_ptr() != grads[prefix + k].data_ptr() for k, t in zip(_MAMBA_KEYS, gs)):
+        raise RuntimeError("mamba_backward: the tensors of grads must be contiguous (they are written in place)")
+    lib = _lib.load()
+    ws = _workspace(lib.rf_mamba_backward_workspace_bytes(b, l, d, d_state, d_conv, expand), "rf_mamba_backward_workspace_bytes", u)
+    grad_u = torch.empty_like(u)
+    with torch.cuda.device(u.device):
+        _lib.check(lib.rf_mamba_backward(_ptr(u), _ptr(grad_out), _ptr(grad_u), _ptr_array(ts), _ptr_array(gs), _ptr(ws), ws.numel(), b, l, d,
+                                         d_state, d_conv, expand, int(channel_major), int(accumulate), _stream(u)), "rf_mamba_backward")
+    return grad_u, grads
+
+
 def wm(x: torch.Tensor, params, prefix: str = "") -> torch.Tensor:
     """``WM(c)(x)`` (RawFomer_WFB_FFAB/model.py:138-172) on ``[n, c, h, w]``: ``convb`` + residual, LayerNorm over the runs of ``c``
     floats of the NCHW memory (the reference's raw ``reshape(b, -1, c)``), ``model1`` = ``Mamba(c, 32, 4, 2)``, ``smooth``.  Reads

@@ -349,7 +349,7 @@ int rf_dwgate3x3(const float* in, float* out, const float* wa, const float* ba, 
 /* nn.Conv2d(C, C, 5, padding=2, groups=C) (+bias): Illumination_Estimator.depth_conv (model.py:182-183) */
 int rf_dwconv5x5(const float* in, float* out, const float* weight, const float* bias, int B, int C, int h, int w, void* stream);
 
-/* ---- Mamba selective scan and the WM block (RawFomer_WFB_FFAB/model.py:138-172), inference only -------------------
+/* ---- Mamba selective scan and the WM block (RawFomer_WFB_FFAB/model.py:138-172): inference, and Mamba's gradient -------------------
  * mamba_ssm.modules.mamba_simple.Mamba(d_model, d_state, d_conv, expand).forward with the module's defaults
  * (dt_rank = ceil(d_model / 16), no projection biases, conv1d bias).  Di = expand * d_model, R = dt_rank.
  * prm = HOST array of 9 device pointers: in_proj.weight [2Di,D], conv1d.weight [Di,1,4], conv1d.bias [Di],
@@ -366,6 +366,17 @@ int rf_mamba_chunk_len(void);
 long long rf_mamba_workspace_bytes(int B, int L, int d_model, int d_state, int d_conv, int expand);
 int rf_mamba_forward(const float* in, float* out, const float* const* prm, void* workspace, size_t workspace_bytes,
                      int B, int L, int d_model, int d_state, int d_conv, int expand, int channel_major, void* stream);
+/* The module's gradient: (in, grad_out = dL/d out, prm) -> grad_in = dL/d in and grad_prm, a HOST array of 9 device pointers
+ * with prm's order and shapes (conv1d.weight's gradient is [Di,1,4]).  Nothing is kept from a forward call: the intermediates
+ * are recomputed.  The limits and refusals are rf_mamba_forward's; in, grad_out, grad_in and workspace are 16-byte aligned and
+ * in, grad_out, grad_in may not alias each other; in and grad_out are not written.  grad_in is always overwritten;
+ * accumulate != 0 ADDS to the nine grad_prm tensors (a training step sums several modules' calls), 0 overwrites them.
+ * The adjoint recurrence runs in the forward's chunks, last to first, with every sum in a fixed order (no float atomics): two
+ * runs give the same bits.  A workspace smaller than rf_mamba_backward_workspace_bytes is refused with -12. */
+long long rf_mamba_backward_workspace_bytes(int B, int L, int d_model, int d_state, int d_conv, int expand);
+int rf_mamba_backward(const float* in, const float* grad_out, float* grad_in, const float* const* prm, float* const* grad_prm,
+                      void* workspace, size_t workspace_bytes, int B, int L, int d_model, int d_state, int d_conv, int expand,
+                      int channel_major, int accumulate, void* stream);
 /* WM.forward (model.py:165-172): x = convb(x) + x; tokens = LayerNorm_c(x.reshape(n, -1, c)) -- a RAW reshape of the NCHW
  * memory: token i is the run flat[i c : (i + 1) c] of an image; y = Mamba(c, 32, 4, 2)(tokens), stored channel-major, which
  * IS permute(0,2,1).reshape(n,c,h,w); out = smooth(y).  in, out [n,c,h,w].  prm = HOST array of 17 device pointers:
