@@ -211,11 +211,18 @@ int launch_gram(const GramArgs& a, hipStream_t st) {
     return check_launch("gram");
 }
 
-// one workgroup per (head, image)
-__global__ void __launch_bounds__(256) attn_fold_kernel(const float* __restrict__ partial, int nslab,
-                                                        const float* __restrict__ temperature,
-                                                        const float* __restrict__ w_out, float* __restrict__ wp_out,
-                                                        unsigned short* __restrict__ wp3_out, int C, int heads, int log_temperature) {
+// one workgroup per (head, image): fold_threads() threads and fold_stage() + that many floats of dynamic LDS
+constexpr int kFoldThreads = 1024;
+constexpr int kFoldStage = 8192;      // floats of w_out staged at a time in step 3 (32 KB)
+// 256 threads while step 1 fits one pass of them (c <= 8), 1024 from there on.  Not 1024 throughout: the level-0 fold of the
+// encoder runs beside the branch stream's kernels, and a 16-wave workgroup with 54 KB of LDS waited for a whole free CU
+// (44 -> 87 us between its first and last workgroup at cfg2)
+static int fold_threads(int c) { return c * c + 2 * c > 256 ? kFoldThreads : 256; }
+__host__ __device__ static inline int fold_stage(int NT, int c) { return NT * 16 * c < kFoldStage ? NT * 16 * c : kFoldStage; }
+__global__ void __launch_bounds__(kFoldThreads) attn_fold_kernel(const float* __restrict__ partial, int nslab,
+                                                                 const float* __restrict__ temperature,
+                                                                 const float* __restrict__ w_out, float* __restrict__ wp_out,
+                                                                 unsigned short* __restrict__ wp3_out, int C, int heads, int log_temperature) {
     const int hd = blockIdx.x, b = blockIdx.y;
     const int c = C / heads;
     const int NT = (C + 15) >> 4;
@@ -223,16 +230,23 @@ __global__ void __launch_bounds__(256) attn_fold_kernel(const float* __restrict_
     __shared__ float nq[64], nk[64];
     const float* pb = partial + (size_t)b * nslab * NT * 16 * kRowW;
     // 1. reduce the slab partials: value v is summed by RS threads over interleaved slabs, then the RS
-    //    sub-sums are combined in a fixed order (deterministic, and parallel when c*c + 2c < 256)
-    __shared__ float sub[256];
+    //    sub-sums are combined in a fixed order (deterministic, and parallel when c*c + 2c < 256).  RS, a function of c alone,
+    //    and the order of the adds decide the bits and stay; what runs side by side is the values: blockDim.x / RS of them per
+    //    pass (c = 16: all 288 in one pass, c = 32: 1088 in two; with 256 threads they took two and five, each pass a serial
+    //    walk over the slabs), and a thread has 16 loads in flight.
+    extern __shared__ float fold_dyn[];
+    const int nthr = (int)blockDim.x;
+    float* sub = fold_dyn;                  // [nthr]
     const int nval = c * c + 2 * c;
     int RS = 256 / nval;
     if (RS < 1) RS = 1;
     if (RS > 16) RS = 16;
-    for (int base = 0; base < nval; base += 256 / RS) {
+    const int vpp = nthr / RS;              // values per pass
+    for (int base = 0; base < nval; base += vpp) {
         const int vi = base + threadIdx.x / RS, rs = threadIdx.x % RS;
+        const bool mine = vi < nval && (int)threadIdx.x / RS < vpp;
         float s = 0.f;
-        if (vi < nval && threadIdx.x / RS < 256 / RS) {
+        if (mine) {
             int qch, col;
             if (vi < c * c) {
                 const int ii = vi / c, jj = vi % c;
@@ -249,20 +263,28 @@ __global__ void __launch_bounds__(256) attn_fold_kernel(const float* __restrict_
                 col = kMaxBand * 16 + 1;
             }
             const float* src = pb + ((size_t)(qch >> 4) * 16 + (qch & 15)) * kRowW + col;
-            // loads of 8 slabs in flight, summed in slab order (same result, one exposed round trip per 8 instead of per slab)
+            const size_t sstride = (size_t)NT * 16 * kRowW;
+            // loads of 16 (then 4) slabs in flight, summed in slab order (same result, one exposed round trip per 16 instead of per slab)
             int sl = rs;
-            for (; sl + 7 * RS < nslab; sl += 8 * RS) {
-                float t[8];
+            for (; sl + 15 * RS < nslab; sl += 16 * RS) {
+                float t[16];
 #pragma unroll
-                for (int u = 0; u < 8; ++u) t[u] = src[(size_t)(sl + u * RS) * NT * 16 * kRowW];
+                for (int u = 0; u < 16; ++u) t[u] = src[(size_t)(sl + u * RS) * sstride];
 #pragma unroll
-                for (int u = 0; u < 8; ++u) s += t[u];
+                for (int u = 0; u < 16; ++u) s += t[u];
             }
-            for (; sl < nslab; sl += RS) s += src[(size_t)sl * NT * 16 * kRowW];
+            for (; sl + 3 * RS < nslab; sl += 4 * RS) {
+                float t[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) t[u] = src[(size_t)(sl + u * RS) * sstride];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) s += t[u];
+            }
+            for (; sl < nslab; sl += RS) s += src[(size_t)sl * sstride];
         }
         sub[threadIdx.x] = s;
         __syncthreads();
-        if (rs == 0 && vi < nval && threadIdx.x / RS < 256 / RS) {
+        if (rs == 0 && mine) {
             float t = 0.f;
             for (int q = 0; q < RS; ++q) t += sub[threadIdx.x + q];
             if (vi < c * c) S[vi / c][vi % c] = t;
@@ -296,20 +318,33 @@ __global__ void __launch_bounds__(256) attn_fold_kernel(const float* __restrict_
     float* dst = wp_out + (size_t)b * NT * (C / 4) * 64;
     const int NB = (C + 31) >> 5;
     unsigned short* dst3 = wp3_out ? wp3_out + (size_t)b * NT * NB * 1536 : nullptr;   // b3 form of the same matrix (rf_common.h)
-    for (int idx = threadIdx.x; idx < NT * 16 * c; idx += 256) {
-        const int co = idx / c, jj = idx % c;
-        float s = 0.f;
-        if (co < C) {
-            const float* wr = w_out + (size_t)co * C + hd * c;
-            for (int ii = 0; ii < c; ++ii) s = fmaf(wr[ii], S[ii][jj], s);
+    // the head's slice of w_out, [co][hd*c .. hd*c + c), goes through LDS a block of rows at a time (each element was read from
+    // global memory c times, inside the sum); the sum itself is the same fmaf chain over i
+    float* wl = fold_dyn + nthr;            // [fold_stage(NT, c)]
+    const int rows = fold_stage(NT, c) / c;
+    for (int co0 = 0; co0 < NT * 16; co0 += rows) {
+        const int nrow = NT * 16 - co0 < rows ? NT * 16 - co0 : rows;
+        __syncthreads();
+        for (int idx = threadIdx.x; idx < nrow * c; idx += nthr) {
+            const int co = co0 + idx / c;
+            wl[idx] = co < C ? w_out[(size_t)co * C + hd * c + idx % c] : 0.f;
         }
-        const int k = hd * c + jj;
-        dst[((size_t)(k >> 2) * NT + (co >> 4)) * 64 + (co & 15) + 16 * (k & 3)] = s;
-        if (dst3) b3_store(dst3, NT, co, k, s);
+        __syncthreads();
+        for (int idx = threadIdx.x; idx < nrow * c; idx += nthr) {
+            const int co = co0 + idx / c, jj = idx % c;
+            float s = 0.f;
+            if (co < C) {
+                const float* wr = wl + (idx - jj);
+                for (int ii = 0; ii < c; ++ii) s = fmaf(wr[ii], S[ii][jj], s);
+            }
+            const int k = hd * c + jj;
+            dst[((size_t)(k >> 2) * NT + (co >> 4)) * 64 + (co & 15) + 16 * (k & 3)] = s;
+            if (dst3) b3_store(dst3, NT, co, k, s);
+        }
     }
     // columns C .. 32 NB - 1 of the padded b3 matrix (C not a multiple of 32): zero, written by the last head's workgroup
     if (dst3 && hd == heads - 1)
-        for (int idx = threadIdx.x; idx < NT * 16 * (32 * NB - C); idx += 256)
+        for (int idx = threadIdx.x; idx < NT * 16 * (32 * NB - C); idx += nthr)
             b3_store(dst3, NT, idx / (32 * NB - C), C + idx % (32 * NB - C), 0.f);
 }
 
@@ -317,7 +352,8 @@ int launch_attn_fold(const float* partial, int nslab, const float* temperature, 
                      float* wp_out, void* wp3_out, int B, int C, int heads, hipStream_t st, int log_temperature) {
     RF_CHECK_ARG(C % heads == 0 && C / heads <= 64 && C % 4 == 0, "attn_fold: unsupported C=%d heads=%d", C, heads);
     ProfScope prof(st, "attn_fold_kernel", 0.0, 0.0);
-    attn_fold_kernel<<<dim3((unsigned)heads, (unsigned)B), 256, 0, st>>>(partial, nslab, temperature, w_out, wp_out, (unsigned short*)wp3_out, C, heads, log_temperature);
+    const int c = C / heads, nthr = fold_threads(c);
+    attn_fold_kernel<<<dim3((unsigned)heads, (unsigned)B), nthr, (size_t)(nthr + fold_stage((C + 15) >> 4, c)) * sizeof(float), st>>>(partial, nslab, temperature, w_out, wp_out, (unsigned short*)wp3_out, C, heads, log_temperature);
     return check_launch("attn_fold");
 }
 

@@ -1,8 +1,8 @@
 // Fused transformer-block kernels for U-Net levels 0-2.  Built: ffn_fused_kernel<32, false> and attn_front_kernel<32> (four
 // waves, level 0 of RawFormer-S), ffn_fused8_kernel<48> / <64> (eight waves; <64> is built and tested but never dispatched, see
-// fused_ffn_supported) and attn_mid_kernel<64> / <128> (levels 1-2, where the qkv 1x1 stays a separate GEMM).  The three
-// kernels with a phase A (both FFN kernels and attn_front) share group_geom, split_step, phase_a_step_b3 and tile_range; all
-// four share stencil4, and all but ffn_fused_kernel tile_origin.  Every helper is __forceinline__, and tools/isa_same.py shows whether an edit to one
+// fused_ffn_supported); attn_mid_kernel<64> / <128> (levels 1-2, where the qkv 1x1 stays a separate GEMM) is built by
+// rf_attn_mid.hip.  The three kernels with a phase A (both FFN kernels and attn_front) share group_geom, split_step,
+// phase_a_step_b3 and tile_range; all four share stencil4, and ffn_fused8_kernel and attn_front_kernel tile_origin.  Every helper is __forceinline__, and tools/isa_same.py shows whether an edit to one
 // of them left the compiled code alone.  The helpers and ffn_fused_kernel live in rf_fused_tile.h: rf_fused_tail.hip builds the
 // second instantiation, ffn_fused_kernel<32, true>, which a whole-model stage uses at level 0 -- the FFN with the stage's
 // channel_reduce on top (FfnTail, rf_common.h), launched from here by launch_ffn_fused.
@@ -407,11 +407,6 @@ __global__ void __launch_bounds__(256, 2) attn_front_kernel(AttnFrontArgs a) {
     }
 }
 
-// heads that never straddle a 16-channel tile
-static bool heads_fit_tiles(int C, int heads) {
-    const int c = heads > 0 ? C / heads : 0;
-    return heads > 0 && C % heads == 0 && c <= 16 && 16 % c == 0;
-}
 static bool attn_front_shape_ok(int C, int h, int w) { return C == 32 && (w % 4 == 0) && ((double)C * h * w * 4.0 < 4.0e9); }
 bool fused_attn_supported(int C, int heads, int h, int w) { return heads_fit_tiles(C, heads) && attn_front_shape_ok(C, h, w); }
 
@@ -443,236 +438,6 @@ int launch_attn_front(AttnFrontArgs a, int C, hipStream_t st) {
     const dim3 grid((unsigned)a.nslab, (unsigned)B);
     attn_front_kernel<32><<<grid, 256, 0, st>>>(a);
     return check_launch("attn_front");
-}
-
-// ================================================================================================
-// Attention middle for levels where the qkv 1x1 stays a separate GEMM (C = 64, 128):
-//   qkv [B,3C,h,w] (HBM) -> depthwise 3x3 -> { Gram partials of (q, k) per head ; v -> HBM }
-// i.e. attn_front_kernel with phase A replaced by staging halo'd qkv tiles from HBM: the depthwise-convolved
-// q and k never exist in memory (un-fused: dwconv writes 3C and the Gram kernel reads 2C of it back).
-// Round r stages q tile r (planes 0-15) and k tile r (planes 16-31) -- heads never straddle a 16-channel tile
-// here -- and the v rounds 32 channels each; a round's 14 x 16-byte loads per thread are issued before the
-// previous round's phase B and land in LDS after it (hardware zero fill outside the image, like rf_conv3x3.hip).
-// (AttnMidArgs: rf_common.h)
-// ================================================================================================
-template <int C>
-__global__ void __launch_bounds__(256, 2) attn_mid_kernel(AttnMidArgs a) {
-    using namespace fused;
-    constexpr int NQT = C / 16;          // Gram rounds
-    constexpr int NVP = C / PART;        // v rounds
-    constexpr int NR = NQT + NVP;
-    constexpr int PSG = fused::PSG, PSV = 448, ROWW = 4 * 16 + 2;
-    constexpr int NF4 = PART * HR * (HC / 4);            // 16-byte elements of one staged round (32 planes x 6 x 18)
-    constexpr int FPT = (NF4 + 255) / 256;
-    constexpr unsigned OOB = 0x80000000u;
-    __shared__ __attribute__((aligned(16))) float mid[PART * PSG + 8];
-    __shared__ float wd_l[3 * C * 9], bd_l[3 * C];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int j = lane & 15, kq = lane >> 4;
-    const int slab = blockIdx.x, b = blockIdx.y;
-    const int h = a.h, w = a.w, P = h * w;
-    const float* qb = a.qkv + (size_t)b * 3 * C * P;
-    float* vb = a.v + (size_t)b * C * P;
-    for (int i = tid; i < 3 * C * 9; i += 256) wd_l[i] = a.wd[i];
-    for (int i = tid; i < 3 * C; i += 256) bd_l[i] = a.bd[i];
-
-    // element e = tid + 256 i of a round = (plane p, halo row, 4-pixel group g)
-    int pk[FPT];
-#pragma unroll
-    for (int i = 0; i < FPT; ++i) {
-        const int e = tid + 256 * i;
-        const int pl = e / (HR * (HC / 4)), rem = e % (HR * (HC / 4));
-        pk[i] = e < NF4 ? (pl << 16) | ((rem / (HC / 4)) << 8) | (rem % (HC / 4)) : -1;
-    }
-    // A workgroup's tiles are consecutive and run DOWN a column of the tile grid, and the six halo'd rows of a plane live in a
-    // circular window of LDS rows (image row y in slot (y + 1) mod 6): a tile directly below the previous one of the same round
-    // finds its first two rows already there and stages only the four new ones -- 4.5 instead of 6.75 floats read per pixel
-    // and channel (the measured HBM traffic of this kernel had been 2.1-2.3 x its algorithmic bytes).
-    const int tiles_y = a.ntiles / a.tiles_x;
-    const int per = (a.ntiles + a.nslab - 1) / a.nslab;
-    unsigned voff[FPT];       // pending tile: byte offset of (row, group) inside a plane, OOB outside the image / already in LDS
-    int pend_ys = 0;          // ... slot of its halo row 0
-    bool pend_full = true;    // ... all six rows are staged (first tile of a round or of a column)
-    auto plan_tile = [&](int tile, bool full) {
-        const int2 o = tile_origin(tile, tiles_y);
-        const int x0 = o.x, y0 = o.y;
-        pend_ys = y0 % HR; pend_full = full;
-#pragma unroll
-        for (int i = 0; i < FPT; ++i) {
-            int e = pk[i];
-            asm volatile("" : "+v"(e));
-            const int r = (e >> 8) & 255;
-            const int y = y0 - 1 + r, x = x0 - 4 + 4 * (e & 255);
-            const bool ok = e >= 0 && (full || r >= 2) && (unsigned)y < (unsigned)h && (unsigned)x < (unsigned)w;      // w % 4 == 0: whole groups
-            voff[i] = ok ? (unsigned)((y * w + x) * 4) : OOB;
-        }
-    };
-    float4 stg[FPT];
-    // round rd < NQT: q tile rd | k tile rd;  rd >= NQT: v channels 32 (rd - NQT) ..
-    auto load_round = [&](int rd) {
-        const bool gram = rd < NQT;
-        const size_t base = gram ? (size_t)16 * rd * P : (size_t)(2 * C + PART * (rd - NQT)) * P;
-        // num_records = the planes this round touches (q tile + k tile, C planes apart; or 32 v planes), never the rest of the
-        // tensor: it must stay below the OOB offset 2^31 for the zero fill to work on large frames (3C planes of a 1424x2128
-        // level are 2.3 GB)
-        const size_t span = (gram ? (size_t)(C + 16) : (size_t)PART) * P, rest = (size_t)3 * C * P - base;
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>(qb) + base, 0, (int)((span < rest ? span : rest) * 4), 0x00020000);
-        const unsigned kjump = gram ? (unsigned)((C - 16) * P) * 4u : 0u;      // planes 16-31 of a Gram round are the k tile
-#pragma unroll
-        for (int i = 0; i < FPT; ++i) {
-            const int pl = pk[i] >> 16;
-            const unsigned off = voff[i] + (unsigned)pl * (unsigned)P * 4u + (pl >= 16 ? kjump : 0u);   // OOB stays >= 2^31
-            typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-            const u32x4_t v4 = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, 0);
-            stg[i] = make_float4(__uint_as_float(v4.x), __uint_as_float(v4.y), __uint_as_float(v4.z), __uint_as_float(v4.w));
-        }
-    };
-    auto store_round = [&](int rd) {      // the pending tile's rows into their slots (rows 0-1 of a sliding tile are already there)
-        const int PSX = rd < NQT ? PSG : PSV;
-#pragma unroll
-        for (int i = 0; i < FPT; ++i) {
-            int e = pk[i];
-            asm volatile("" : "+v"(e));       // opaque: nothing derived from the element id is hoisted out of the step loop (and spilled)
-            const int r = (e >> 8) & 255;
-            const int slot = pend_ys + r - (pend_ys + r >= HR ? HR : 0);
-            if (e >= 0 && (pend_full || r >= 2)) *reinterpret_cast<float4*>(mid + (e >> 16) * PSX + slot * HC + 4 * (e & 255)) = stg[i];
-        }
-    };
-
-    // Rounds are the OUTER loop and this workgroup's tiles the inner one, so one register set holds the Gram tile of the
-    // round across all tiles (a round index into a register array would go to scratch); (round, tile) is one flattened
-    // pipeline: the next step's loads are issued before this step's phase B.
-    const int t_begin = slab * per;
-    if (t_begin >= a.ntiles) {                             // (whole workgroup) no tiles: its Gram partials are zero
-        if ((int)blockIdx.z == 0)
-            for (int i = tid; i < NQT * 16 * ROWW; i += 256) a.partial[((size_t)b * a.nslab + slab) * NQT * 16 * ROWW + i] = 0.f;
-        return;
-    }
-    const int ntw = (t_begin + per < a.ntiles) ? per : a.ntiles - t_begin;      // tiles of this workgroup: t_begin, t_begin + 1, ...
-    f32x4 gq = {0.f, 0.f, 0.f, 0.f};
-    float nq = 0.f, nk = 0.f;                              // sums of squares on the VALU (see attn_front_kernel)
-    // rounds of this workgroup: every round is independent (its own Gram partial or its own v channels), so a launch with few
-    // slabs (one frame) spreads them over gridDim.z workgroups per slab -- same partials, same results
-    const int rd_lo = (int)blockIdx.z * NR / a.rgroups, rd_hi = ((int)blockIdx.z + 1) * NR / a.rgroups;
-    plan_tile(t_begin, true);
-    load_round(rd_lo);
-    __syncthreads();                                      // wd_l / bd_l visible
-    for (int rd = rd_lo; rd < rd_hi; ++rd) {
-        for (int ti = 0; ti < ntw; ++ti) {
-            const int tile = t_begin + ti;
-            const int2 o = tile_origin(tile, tiles_y);
-            const int x0 = o.x, y0 = o.y;
-            const int yo = y0 + wave;
-            lds_barrier();                                // everyone is done reading the previous step
-            store_round(rd);
-            // LDS row offsets of this wave's three stencil rows (halo rows wave .. wave + 2 of this tile)
-            int ro[3];
-#pragma unroll
-            for (int dy = 0; dy < 3; ++dy) {
-                const int sl = pend_ys + wave + dy;
-                ro[dy] = (sl - (sl >= HR ? HR : 0)) * HC;
-            }
-            if (ti + 1 < ntw) {                           // next step: same round, next tile / next round, first tile
-                plan_tile(tile + 1, (tile + 1) % tiles_y == 0);      // a new column starts with a full window
-                load_round(rd);
-            } else if (rd + 1 < rd_hi) {
-                plan_tile(t_begin, true);
-                load_round(rd + 1);
-            }
-            lds_barrier();
-            if (rd < NQT) {
-                // Gram: lane (i = j, kq) owns channel j of the q tile and of the k tile at pixels x0 + 16 st + 4 kq + m
-                const int cq = 16 * rd + j, ck = C + 16 * rd + j;
-#pragma unroll 1
-                for (int st = 0; st < 4; ++st) {
-                    const int xo = x0 + 16 * st + 4 * kq;
-                    const bool ok = yo >= a.ylo && yo < a.yhi && xo >= a.xlo && xo < a.xhi;
-                    float qa[4], kb[4];
-                    stencil4<Edge::Wide>(mid + j * PSG + 16 * st + 4 * kq + 4, ro, j, wd_l + cq * 9, bd_l[cq], qa);
-                    stencil4<Edge::Wide>(mid + (16 + j) * PSG + 16 * st + 4 * kq + 4, ro, j, wd_l + ck * 9, bd_l[ck], kb);
-#pragma unroll
-                    for (int m = 0; m < 4; ++m) {
-                        const float qv = ok ? qa[m] : 0.f, kv = ok ? kb[m] : 0.f;
-                        gq = __builtin_amdgcn_mfma_f32_16x16x4f32(qv, kv, gq, 0, 0, 0);
-                        nq = fmaf(qv, qv, nq);
-                        nk = fmaf(kv, kv, nk);
-                    }
-                }
-            } else {
-                const int vp = rd - NQT, xo = x0 + 4 * j;
-                if (yo < h && xo < w) {
-#pragma unroll
-                    for (int s = 0; s < PART / 4; ++s) {
-                        const int hc = 4 * s + kq, cv = 2 * C + vp * PART + hc;
-                        float v[4];
-                        stencil4<Edge::Dpp>(mid + hc * PSV + 4 * j + 4, ro, j, wd_l + cv * 9, bd_l[cv], v);
-                        *reinterpret_cast<float4*>(vb + (size_t)(vp * PART + hc) * P + (size_t)yo * w + xo) = make_float4(v[0], v[1], v[2], v[3]);
-                    }
-                }
-            }
-        }
-        if (rd < NQT) {
-            // ---- cross-wave reduction of this round's Gram tile in a fixed order, one partial per workgroup
-            // (the next step's data is still in registers: mid is free between the two barriers)
-            __syncthreads();
-            float* red = mid;
-            for (int i = tid; i < 64 * 48; i += 256) red[(i / 48) * ROWW + 16 + i % 48] = 0.f;      // zero key tiles: see attn_front_kernel
-            int kq_ = kq;                     // opaque here: the row addresses below were hoisted out of the round loop and SPILLED
-            asm volatile("" : "+v"(kq_));     // (scratch traffic next to the prefetched loads of the next round)
-            float nqt = nq, nkt = nk;         // channel j's sums of squares over the four kq lanes
-            nqt += __shfl_xor(nqt, 16); nqt += __shfl_xor(nqt, 32);
-            nkt += __shfl_xor(nkt, 16); nkt += __shfl_xor(nkt, 32);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int row = 4 * kq_ + q;
-                float* rr = red + (wave * 16 + row) * ROWW;
-                rr[j] = gq[q];
-                if (row == j) { rr[64] = nqt; rr[65] = nkt; }
-            }
-            __syncthreads();
-            float* dst = a.partial + (((size_t)b * a.nslab + slab) * NQT + rd) * 16 * ROWW;
-            for (int i = tid; i < 16 * ROWW; i += 256)
-                dst[i] = ((red[i] + red[16 * ROWW + i]) + red[2 * 16 * ROWW + i]) + red[3 * 16 * ROWW + i];
-            gq = (f32x4){0.f, 0.f, 0.f, 0.f}; nq = 0.f; nk = 0.f;
-        }
-    }
-}
-
-// slabs of the image (= workgroups per image): enough of them to fill the chip at a batch of 8, at most 8 tiles each;
-// a function of the image only (batch-invariant reduction order)
-int attn_mid_plan(int h, int w, int* nslab, size_t* partial_floats, int B, int C) {
-    const int ntiles = cdiv(w, fused::TW) * cdiv(h, fused::TH);
-    int per = ntiles / 64;                      // (finer slabs -- ntiles / 128 -- are 40 % faster for ONE frame and 9 % slower for a
-                                                // batch of 8: the tile loop is what hides this kernel's load latency)
-    if (per < 1) per = 1;
-    if (per > 8) per = 8;
-    *nslab = cdiv(ntiles, per);
-    *partial_floats = (size_t)B * *nslab * (C / 16) * 16 * 66;
-    return RF_OK;
-}
-
-static bool attn_mid_shape_ok(int C, int h, int w) {
-    return (C == 64 || C == 128) && (w % 4 == 0) && ((double)(C + 16) * h * w * 4.0 < 2.0e9);      // byte offsets inside one round's buffer window stay below 2^31
-}
-bool attn_mid_supported(int C, int heads, int h, int w) { return heads_fit_tiles(C, heads) && attn_mid_shape_ok(C, h, w); }
-
-int launch_attn_mid(AttnMidArgs a, int C, hipStream_t st) {
-    const int B = a.B, h = a.h, w = a.w;
-    RF_CHECK_ARG(attn_mid_shape_ok(C, h, w) && B <= 65535, "attn_mid: unsupported shape C=%d %dx%d", C, h, w);
-    RF_CHECK_ARG(aligned16(a.qkv) && aligned16(a.v), "attn_mid: buffers must be 16-byte aligned");
-    a.tiles_x = cdiv(w, fused::TW);
-    a.ntiles = a.tiles_x * cdiv(h, fused::TH);
-    if (!(a.yhi > 0 && a.yhi < h)) a.yhi = h;
-    if (!(a.xhi > 0 && a.xhi < w)) a.xhi = w;
-    a.rgroups = ((long)a.nslab * B < 256) ? 3 : 1;          // C / 16 + C / 32 rounds: 6 (C = 64) or 12 (C = 128)
-    const double px = (double)B * h * w;
-    ProfScope prof(st, C == 64 ? "attn_mid_kernel<64>" : "attn_mid_kernel<128>", px * (54.0 * C + 4.0 * C * 16), px * 16.0 * C);
-    const dim3 grid((unsigned)a.nslab, (unsigned)B, (unsigned)a.rgroups);
-    if (C == 64) attn_mid_kernel<64><<<grid, 256, 0, st>>>(a);
-    else attn_mid_kernel<128><<<grid, 256, 0, st>>>(a);
-    return check_launch("attn_mid");
 }
 
 #ifdef RF_STAMP

@@ -27,6 +27,12 @@ __device__ __forceinline__ void lds_barrier() {
     asm volatile("" ::: "memory");
 }
 
+// heads that never straddle a 16-channel tile: what attn_front_kernel (rf_fused.hip) and attn_mid_kernel (rf_attn_mid.hip) need
+static inline bool heads_fit_tiles(int C, int heads) {
+    const int c = heads > 0 ? C / heads : 0;
+    return c > 0 && C % heads == 0 && c <= 16 && 16 % c == 0;
+}
+
 namespace fused {
 constexpr int TH = 4, TW = 64;          // output tile
 constexpr int HR = TH + 2;              // halo'd rows

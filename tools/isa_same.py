@@ -2,24 +2,59 @@
 """Is the gfx950 code of one source the same as at an earlier revision?  The gate of a kernel refactor: identical instruction
 streams have identical results and identical speed.  Needs hipcc and git, no GPU.
 
-    isa_same.py <rev> <path.hip> [-DFOO ...]
+    isa_same.py <rev> <path.hip> [--kernel NAME ...] [-DFOO ...]
 
 Compiles `git show <rev>:<path>` (next to that revision's headers) and the working-tree file with build.FLAGS to device assembly,
 drops the per-translation-unit __hip_cuid_* symbol and the source file name, and exits non-zero at the first difference.
+With --kernel (repeatable) only the kernels whose mangled name contains NAME are compared -- their instruction streams and
+their .amdhsa_kernel descriptors -- which is the question when a kernel has moved OUT of the file: did the ones that stayed change?
 """
 import os, re, subprocess, sys, tempfile
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 from bayer_low_light_image_enhancement_amd import build as B  # noqa: E402
 
-rev, path, flags = sys.argv[1], os.path.relpath(os.path.abspath(sys.argv[2]), REPO), sys.argv[3:]
+rev, path, flags, kernels = sys.argv[1], os.path.relpath(os.path.abspath(sys.argv[2]), REPO), [], []
+rest = sys.argv[3:]
+while rest:
+    a = rest.pop(0)
+    if a == "--kernel":
+        kernels.append(rest.pop(0))
+    else:
+        flags.append(a)
+
+
+def only_kernels(lines):
+    """The bodies (label .. .Lfunc_end) and descriptors (.amdhsa_kernel .. .end_amdhsa_kernel) of the chosen kernels; the
+    numbers of local labels and of .Lfunc_end belong to the whole file and are normalised per kernel."""
+    out, keep, names = [], False, []
+    for ln in lines:
+        m = re.match(r"^(\w+):", ln) or re.match(r"^\s*\.amdhsa_kernel\s+(\w+)", ln)
+        if m and any(k in m.group(1) for k in kernels):
+            keep, first = True, None
+            names.append(m.group(1))
+        if keep:
+            def renum(mm):
+                nonlocal first
+                first = int(mm.group(2)) if first is None else first
+                return f"{mm.group(1)}{int(mm.group(2)) - first}_"
+            out.append(re.sub(r"(\.LBB|\.Lfunc_end|\.Lfunc_begin)(\d+)_?", renum, ln) if ".L" in ln else ln)
+        if keep and (ln.startswith(".Lfunc_end") or ".end_amdhsa_kernel" in ln):
+            keep = False
+    return out, sorted(set(names))
 
 
 def listing(src):
     r = subprocess.run([B._hipcc(), *B.FLAGS, *flags, "--cuda-device-only", "-S", src, "-o", "-"], capture_output=True, text=True)
     if r.returncode:
         sys.exit(r.stderr[-3000:])
-    return [ln for ln in r.stdout.splitlines() if "__hip_cuid_" not in ln and not ln.lstrip().startswith(".file")]
+    lines = [ln for ln in r.stdout.splitlines() if "__hip_cuid_" not in ln and not ln.lstrip().startswith(".file")]
+    if kernels:
+        lines, names = only_kernels(lines)
+        if not names:
+            sys.exit(f"no kernel of {src} matches {kernels}")
+        print(f"{src}: {len(names)} kernel(s): " + " ".join(names))
+    return lines
 
 
 with tempfile.TemporaryDirectory(prefix="isa_same_") as tmp:
@@ -29,7 +64,7 @@ with tempfile.TemporaryDirectory(prefix="isa_same_") as tmp:
         with open(os.path.join(tmp, f), "wb") as out:
             out.write(subprocess.check_output(["git", "show", f"{rev}:{f}"], cwd=REPO))
     old, new = listing(os.path.join(tmp, path)), listing(os.path.join(REPO, path))
-what = f"{path} {' '.join(flags)}".strip()
+what = f"{path} {' '.join(flags)}".strip() + (f" [{', '.join(kernels)}]" if kernels else "")
 i = next((i for i, (a, b) in enumerate(zip(old, new)) if a != b), min(len(old), len(new)))
 if i == len(old) == len(new):
     print(f"identical: {what}: {len(new)} lines of gfx950 assembly, {rev} and the working tree")
