@@ -121,6 +121,8 @@ SIGNATURES = {
     "rf_mamba_backward": (_i, [_vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "rf_wm_workspace_bytes": (C.c_longlong, [_i, _i, _i, _i]),
     "rf_wm_forward": (_i, [_vp, _vp, C.POINTER(_vp), _vp, _sz, _i, _i, _i, _i, _vp]),
+    "rf_wm_backward_workspace_bytes": (C.c_longlong, [_i, _i, _i, _i]),
+    "rf_wm_backward": (_i, [_vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _sz, _i, _i, _i, _i, _i, _vp]),
     "rf_wmb_front": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "rf_wmb_back": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "rf_wmb_ffn_sum": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

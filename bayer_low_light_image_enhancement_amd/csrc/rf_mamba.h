@@ -34,4 +34,35 @@ int launch_tok_transpose(const float* in, const float* add, float* out, const fl
 int mamba_forward_front(const MambaPlan& p, const float* u, const float* const* prm, float* ws, int B, int L, hipStream_t st,
                         const WmPacked* pk = nullptr);
 
+// ---- the adjoint schedule of rf_mamba_bwd.hip, as rf_mamba_backward and the WM backward (rf_wm_bwd.hip) call it
+struct MambaBwdPlan {
+    MambaPlan m;
+    int NRp, nct;
+    size_t u, g, gu, yg, dpre, dx, dxc, dxz, ddbc, slab, adj, adj_s, dA, dD, cw, cb, csum, wpart, wpart_cap;   // float offsets
+    size_t t_in, t_in3, t_x, t_x3, t_dt, t_dt3, t_out, t_out3;                                                 // transposed packs
+};
+// the forward plan first (same offsets as mamba_plan on a fresh Bump), then the adjoint's buffers
+int mamba_bwd_plan(const char* who, int B, int L, int D, int N, int K, int E, MambaBwdPlan* p, Bump* b);
+// channel-major: u, g, du [B][D][L]; grd: the nine gradients in the order of prm, written or (acc) added to.  The plan's u, g and
+// gu buffers are not touched: they are the caller's (rf_mamba_backward's token-major copies, WM's tok / g_y / g_tok).
+int run_mamba_backward(const MambaBwdPlan& p, const float* u, const float* g, float* du, const float* const* prm, float* const* grd,
+                       float* ws, int B, int L, int acc, hipStream_t st);
+
+// ---- WM (rf_mamba.hip): what rf_wm_forward and the WM backward share
+int wm_check_shape(const char* who, int n, int c, int h, int w);      // the refusals of rf_wm_forward, each naming its argument
+struct WmFrontBufs {
+    float *w0, *w2;            // packed convb.0 / convb.2 weights, written here unless the caller passes WmPacked
+    float *a1;                 // [n][2c][P]  relu(convb.0(x))
+    float *r;                  // [n][c][P]   convb.2(a1), WITHOUT the skip: the transposition pass adds x on the fly
+    float *tok;                // [n][c][L]   LayerNorm(rows of r + x), channel-major (may be a1: dead by then)
+    float *y;                  // [n][c][L]   mamba(tok) (may be r)
+    // optional scratch of launch_conv3x3's input-channel split (Conv3x3Args::ks_scratch: its counters zero on entry).  The forward
+    // passes none and keeps its bits; the backward's small launches run a chain 1/S as long and add the S partial tiles in order
+    float *ks = nullptr;
+    size_t ks_floats = 0;
+};
+// WM's forward up to `smooth`, on the forward's own launchers in the forward's order; ws: the buffers of the Mamba plan `m`
+int wm_forward_front(const MambaPlan& m, const float* in, const float* const* prm, const WmPacked* pk, float* ws, const WmFrontBufs& b, int n,
+                     int c, int h, int w, hipStream_t st);
+
 }  // namespace rf

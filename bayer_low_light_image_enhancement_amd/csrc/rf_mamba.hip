@@ -410,11 +410,16 @@ struct WmPlan {
     size_t floats;
 };
 
-static int wm_plan(const char* who, int n, int c, int h, int w, WmPlan* p) {
+int wm_check_shape(const char* who, int n, int c, int h, int w) {
     RF_CHECK_ARG(h >= 1 && w >= 1 && (double)h * w <= (double)(1 << 24), "%s: h x w = %d x %d must be between 1 and 2^24 pixels", who, h, w);
     RF_CHECK_ARG(c > 0 && c % 4 == 0 && c <= 512, "%s: c %d must be a positive multiple of 4, at most 512", who, c);
     RF_CHECK_ARG(n >= 1 && n <= 65535, "%s: n %d must be between 1 and 65535", who, n);
     RF_CHECK_ARG(8.0 * c * h * w < 2.0e9, "%s: an image of 2c x h x w = %d x %d x %d floats is too large for the 3x3 convolutions", who, 2 * c, h, w);
+    return RF_OK;
+}
+
+static int wm_plan(const char* who, int n, int c, int h, int w, WmPlan* p) {
+    RF_TRY(wm_check_shape(who, n, c, h, w));
     Bump b;
     RF_TRY(mamba_plan(who, n, h * w, c, kN, kDc, 2, &p->m, &b));
     p->w0 = b.off(packed3x3_floats(c, 2 * c));
@@ -428,11 +433,11 @@ static int wm_plan(const char* who, int n, int c, int h, int w, WmPlan* p) {
 
 // wgt == nullptr: wp already holds the packed weight
 static int wm_conv(const float* x, const float* wgt, const float* wp, const float* bias, float* out, int act, int n, int cin, int cout, int h, int w,
-                   hipStream_t st) {
+                   hipStream_t st, float* ks = nullptr, size_t ks_floats = 0) {
     if (wgt) RF_TRY(pack_3x3(wgt, const_cast<float*>(wp), cout, cin, st));
     Conv3x3Args a{};
     a.x = x; a.x_bstride = (int64_t)cin * h * w; a.wp = wp; a.bias = bias; a.out = out; a.out_bstride = (int64_t)cout * h * w;
-    a.B = n; a.Cin = cin; a.Cout = cout; a.h = h; a.w = w; a.act = act;
+    a.B = n; a.Cin = cin; a.Cout = cout; a.h = h; a.w = w; a.act = act; a.ks_scratch = ks; a.ks_floats = ks_floats;
     return launch_conv3x3(a, st);
 }
 
@@ -505,17 +510,24 @@ int wm_workspace_floats(const char* who, int n, int c, int h, int w, size_t* flo
     return RF_OK;
 }
 
+int wm_forward_front(const MambaPlan& m, const float* in, const float* const* prm, const WmPacked* pk, float* ws, const WmFrontBufs& b, int n,
+                     int c, int h, int w, hipStream_t st) {
+    const int L = h * w;
+    RF_TRY(wm_conv(in, pk ? nullptr : prm[0], pk ? pk->convb0 : b.w0, prm[1], b.a1, 2 /* ReLU */, n, c, 2 * c, h, w, st, b.ks, b.ks_floats));
+    RF_TRY(wm_conv(b.a1, pk ? nullptr : prm[2], pk ? pk->convb2 : b.w2, prm[3], b.r, 0, n, 2 * c, c, h, w, st, b.ks, b.ks_floats));
+    // tokens = LayerNorm((convb(x) + x) as runs of c floats), stored channel-major
+    RF_TRY(launch_tok_transpose(b.r, in, b.tok, prm[4], prm[5], n, L, c, st));
+    return run_mamba(m, b.tok, b.y, prm + 6, ws, n, L, st, pk);      // [n][c][L] = permute(0,2,1).reshape(n,c,h,w)
+}
+
 int wm_forward(const float* in, float* out, const float* const* prm, const WmPacked* pk, float* ws, int n, int c, int h, int w,
                hipStream_t st) {
     WmPlan p;
     RF_TRY(wm_plan("wm_forward", n, c, h, w, &p));
     float *t1 = ws + p.t1, *t2 = ws + p.t2;
-    const int L = h * w;
-    RF_TRY(wm_conv(in, pk ? nullptr : prm[0], pk ? pk->convb0 : ws + p.w0, prm[1], t1, 2 /* ReLU */, n, c, 2 * c, h, w, st));
-    RF_TRY(wm_conv(t1, pk ? nullptr : prm[2], pk ? pk->convb2 : ws + p.w2, prm[3], t2, 0, n, 2 * c, c, h, w, st));
-    // tokens = LayerNorm((convb(x) + x) as runs of c floats), stored channel-major over t1, which is dead by now
-    RF_TRY(launch_tok_transpose(t2, in, t1, prm[4], prm[5], n, L, c, st));
-    RF_TRY(run_mamba(p.m, t1, t2, prm + 6, ws, n, L, st, pk));       // [n][c][L] = permute(0,2,1).reshape(n,c,h,w)
+    // the tokens go over t1, which is dead by then, and Mamba's output over t2
+    const WmFrontBufs b{ws + p.w0, ws + p.w2, t1, t2, t1, t2};
+    RF_TRY(wm_forward_front(p.m, in, prm, pk, ws, b, n, c, h, w, st));
     return wm_conv(t2, pk ? nullptr : prm[15], pk ? pk->smooth : ws + p.ws_, prm[16], out, 0, n, c, c, h, w, st);
 }
 

@@ -473,14 +473,7 @@ static int mamba_dgrad(const float* x, int K, int Kp, int64_t x_bstride, const f
     return launch_conv1x1(a, st);
 }
 
-struct MambaBwdPlan {
-    MambaPlan m;
-    int NRp, nct;
-    size_t u, g, gu, yg, dpre, dx, dxc, dxz, ddbc, slab, adj, adj_s, dA, dD, cw, cb, csum, wpart, wpart_cap;   // float offsets
-    size_t t_in, t_in3, t_x, t_x3, t_dt, t_dt3, t_out, t_out3;                                                 // transposed packs
-};
-
-static int mamba_bwd_plan(const char* who, int B, int L, int D, int N, int K, int E, MambaBwdPlan* p, Bump* b) {
+int mamba_bwd_plan(const char* who, int B, int L, int D, int N, int K, int E, MambaBwdPlan* p, Bump* b) {
     RF_TRY(mamba_plan(who, B, L, D, N, K, E, &p->m, b));
     const int Di = p->m.Di, R = p->m.R, NR = p->m.NR, nchunk = p->m.nchunk;
     p->NRp = (NR + 3) / 4 * 4;
@@ -522,7 +515,7 @@ static int mamba_bwd_plan(const char* who, int B, int L, int D, int N, int K, in
 }
 
 // channel-major: u, g, du [B][D][L]
-static int run_mamba_backward(const MambaBwdPlan& p, const float* u, const float* g, float* du, const float* const* prm, float* const* grd,
+int run_mamba_backward(const MambaBwdPlan& p, const float* u, const float* g, float* du, const float* const* prm, float* const* grd,
                               float* ws, int B, int L, int acc, hipStream_t st) {
     const MambaPlan& m = p.m;
     const int D = m.D, Di = m.Di, R = m.R, NR = m.NR, NRp = p.NRp, nchunk = m.nchunk, ns = nchunk - 1;

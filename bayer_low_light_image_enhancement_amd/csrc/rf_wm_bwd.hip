@@ -1,0 +1,367 @@
+// Adjoint of the WM block of rf_mamba.hip (RawFomer_WFB_FFAB/model.py:138-172): (x, dL/dout, parameters) -> dL/dx and the 17
+// parameter gradients.  With
+//   a1 = relu(convb.0(x)),  r = convb.2(a1) + x,  tok = LN(rows of r) stored channel-major [n][c][L],  y = mamba(tok),  out = smooth(y)
+// nothing is kept from a forward call: wm_forward_front (rf_mamba.hip) recomputes a1, convb.2(a1), tok and y; then, with g = dL/dout:
+//
+//   smooth    dW, db = wgrad(g, y);            g_y  = conv3x3(g, smooth^T with flipped taps)
+//   Mamba     g_tok, nine gradients            run_mamba_backward (rf_mamba_bwd.hip) on (tok, g_y), channel-major
+//   LN        g_r, d ln.weight, d ln.bias      wm_ln_bwd_kernel (below): the adjoint of tok_transpose_kernel<true>
+//   convb.2   dW, db = wgrad(g_r, a1);         g_a1 = conv3x3(g_r, W2^T flipped) masked by a1 > 0
+//   convb.0   dW, db = wgrad(g_a1, x);         dL/dx = g_r + conv3x3(g_a1, W0^T flipped)
+//
+// wgrad = launch_gram2 with nine taps where w % 4 == 0, else conv3x3_wgrad_kernel (below).  The three transposed, tap-flipped
+// packs are written by one launch_pack_batch.  Every sum over pixels or rows goes to per-workgroup slabs that a second kernel adds
+// in a fixed order: no atomics, two runs give the same bits.
+#include "rf_mamba.h"
+
+namespace rf {
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Adjoint of tok_transpose_kernel<true>.  in (+ add) [rows][cols] per image is the LayerNorm input, row i a run of cols floats;
+// g [cols][rows] the gradient at the kernel's channel-major output.  Per row, with mean and rstd recomputed as the forward does,
+// xh = (v - mean) rstd and dyh[k] = g[k] gamma[k]:
+//   dx[k] = rstd (dyh[k] - mean_k(dyh) - xh[k] mean_k(dyh xh))
+// and per column  dgamma[k] = sum_rows g xh,  dbeta[k] = sum_rows g.
+// As in the forward a workgroup owns 32 rows at a time: its four waves reduce 8 rows each for mean / rstd, then g is read in
+// 32 x 32 tiles that turn round in LDS (both global sides move 128-byte runs) twice: once for the two row means, once more (L2)
+// for dx.  The row sums end in shuffles over the 32 lanes of a row, in a fixed order.  Thread (ty, tx) alone owns the column
+// sums acc[.][ty][k = tx mod 32]; they stay in LDS over all the row groups the workgroup walks and leave as one slab per
+// workgroup, summed over ty in order (launch_reduce_rows adds the slabs).
+__global__ void __launch_bounds__(256) wm_ln_bwd_kernel(const float* __restrict__ in, const float* __restrict__ add, const float* __restrict__ g,
+                                                        const float* __restrict__ lw, float* __restrict__ dx, float* __restrict__ dgam,
+                                                        float* __restrict__ dbet, float eps, int rows, int cols) {
+    __shared__ float tile[32][33];
+    __shared__ float smean[32], srstd[32], sm1[32], sm2[32];
+    __shared__ float acc[2][8][512];
+    const size_t img = (size_t)blockIdx.y * rows * cols;
+    in += img;
+    add += img;
+    g += img;
+    dx += img;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    for (int k = tx; k < cols; k += 32) {
+        acc[0][ty][k] = 0.f;
+        acc[1][ty][k] = 0.f;
+    }
+    const float inv = 1.0f / (float)cols;
+    const int ngroups = (rows + 31) / 32;
+    for (int rg = blockIdx.x; rg < ngroups; rg += gridDim.x) {
+        const int r0 = rg * 32;
+        for (int i = 0; i < 8; ++i) {                          // mean and rstd: the forward's arithmetic
+            const int r = r0 + wave * 8 + i;
+            float v[8], s = 0.f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int k = lane + 64 * j;
+                v[j] = 0.f;
+                if (r < rows && k < cols) {
+                    const size_t o = (size_t)r * cols + k;
+                    v[j] = in[o] + add[o];
+                }
+                s += v[j];
+            }
+#pragma unroll
+            for (int m = 32; m > 0; m >>= 1) s += __shfl_xor(s, m, 64);
+            const float mean = s / (float)cols;
+            float q = 0.f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float dv = lane + 64 * j < cols ? v[j] - mean : 0.f;
+                q = fmaf(dv, dv, q);
+            }
+#pragma unroll
+            for (int m = 32; m > 0; m >>= 1) q += __shfl_xor(q, m, 64);
+            if (lane == 0) {
+                smean[wave * 8 + i] = mean;
+                srstd[wave * 8 + i] = 1.0f / sqrtf(q / (float)cols + eps);
+            }
+        }
+        __syncthreads();
+        float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int c0 = 0; c0 < cols; c0 += 32) {                // pass 1: row means of dyh and dyh xh, column sums
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int kk = ty + 8 * i, k = c0 + kk, r = r0 + tx;
+                tile[kk][tx] = (k < cols && r < rows) ? g[(size_t)k * rows + r] : 0.f;
+            }
+            __syncthreads();
+            const int k = c0 + tx;
+            if (k < cols) {
+                const float gam = lw[k];
+                float cg = 0.f, cb = 0.f;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int rr = ty + 8 * i, r = r0 + rr;
+                    if (r < rows) {
+                        const size_t o = (size_t)r * cols + k;
+                        const float xh = (in[o] + add[o] - smean[rr]) * srstd[rr], gt = tile[tx][rr], dy = gt * gam;
+                        s1[i] += dy;
+                        s2[i] = fmaf(dy, xh, s2[i]);
+                        cg = fmaf(gt, xh, cg);
+                        cb += gt;
+                    }
+                }
+                acc[0][ty][k] += cg;
+                acc[1][ty][k] += cb;
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+#pragma unroll
+            for (int m = 16; m > 0; m >>= 1) {
+                s1[i] += __shfl_xor(s1[i], m, 64);
+                s2[i] += __shfl_xor(s2[i], m, 64);
+            }
+            if (tx == 0) {
+                sm1[ty + 8 * i] = s1[i] * inv;
+                sm2[ty + 8 * i] = s2[i] * inv;
+            }
+        }
+        __syncthreads();
+        for (int c0 = 0; c0 < cols; c0 += 32) {                // pass 2: dx
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int kk = ty + 8 * i, k = c0 + kk, r = r0 + tx;
+                tile[kk][tx] = (k < cols && r < rows) ? g[(size_t)k * rows + r] : 0.f;
+            }
+            __syncthreads();
+            const int k = c0 + tx;
+            if (k < cols) {
+                const float gam = lw[k];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int rr = ty + 8 * i, r = r0 + rr;
+                    if (r < rows) {
+                        const size_t o = (size_t)r * cols + k;
+                        const float xh = (in[o] + add[o] - smean[rr]) * srstd[rr], dy = tile[tx][rr] * gam;
+                        dx[o] = srstd[rr] * (dy - sm1[rr] - xh * sm2[rr]);
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+    const size_t slab = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * cols;
+    for (int k = threadIdx.x; k < cols; k += 256) {
+        float a = 0.f, b = 0.f;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            a += acc[0][t][k];
+            b += acc[1][t][k];
+        }
+        dgam[slab + k] = a;
+        dbet[slab + k] = b;
+    }
+}
+
+// workgroups per image: one per 32 rows up to about 2048 in all (a workgroup walks the row groups it owns in order)
+static int wm_ln_bwd_nblk(int B, int rows) {
+    const int ng = cdiv(rows, 32), cap = cdiv(2048, B);
+    return ng < cap ? ng : cap;
+}
+
+// launch_reduce_rows inside a profiler bracket
+static int reduce_rows(const float* partial, float* out, int nrows, size_t n, int accumulate, hipStream_t st) {
+    ProfScope prof(st, "reduce_partials_kernel", (double)nrows * n, 4.0 * (nrows + 1.0) * n);
+    return launch_reduce_rows(partial, out, nrows, n, accumulate, st);
+}
+
+// partial: 2 B nblk cols floats
+static int launch_wm_ln_bwd(const float* in, const float* add, const float* g, const float* lw, float* dx, float* dlw, float* dlb, float* partial,
+                            int B, int rows, int cols, int accumulate, hipStream_t st) {
+    const int nblk = wm_ln_bwd_nblk(B, rows);
+    float *dgam = partial, *dbet = partial + (size_t)B * nblk * cols;
+    {
+        const double el = (double)B * rows * cols;
+        ProfScope prof(st, "wm_ln_bwd_kernel", 20.0 * el, 12.0 * el);
+        wm_ln_bwd_kernel<<<dim3((unsigned)nblk, (unsigned)B), 256, 0, st>>>(in, add, g, lw, dx, dgam, dbet, 1e-5f, rows, cols);
+        RF_TRY(check_launch("wm_ln_bwd"));
+    }
+    RF_TRY(reduce_rows(dgam, dlw, B * nblk, (size_t)cols, accumulate, st));
+    return reduce_rows(dbet, dlb, B * nblk, (size_t)cols, accumulate, st);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// 3x3 weight and bias gradient for the widths launch_gram2 does not take (w % 4 != 0: the small bands of the deep levels):
+//   dW[co][ci][dy][dx] = sum over images and pixels of a[co][y][x] b[ci][y + dy - 1][x + dx - 1],   db[co] = sum of a[co]
+// A thread owns one (ci, tap) of one output channel and one slab of `slab_px` consecutive pixels of the batch (images laid end
+// to end) and adds them in order; every thread of the workgroup reads the same a value (one broadcast load).  The partials have
+// the layout of the result, [slab][Ca][Cb][9] and [slab][Ca].
+__global__ void __launch_bounds__(256) conv3x3_wgrad_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ partial,
+                                                            float* __restrict__ bias_partial, int Ca, int Cb, int h, int w, long long total,
+                                                            long long slab_px) {
+    const int co = blockIdx.x, e = blockIdx.y * 256 + threadIdx.x;
+    if (e >= Cb * 9) return;
+    const int ci = e / 9, tap = e - 9 * ci, sy = tap / 3 - 1, sx = tap % 3 - 1;
+    const int P = h * w;
+    const long long q0 = (long long)blockIdx.z * slab_px, q1 = q0 + slab_px < total ? q0 + slab_px : total;
+    long long img = q0 / P;
+    int p = (int)(q0 - img * P);
+    float s = 0.f, sb = 0.f;
+    for (long long q = q0; q < q1; ++q) {
+        const float av = a[((size_t)img * Ca + co) * P + p];
+        const int y = p / w, x = p - y * w, yy = y + sy, xx = x + sx;
+        if (yy >= 0 && yy < h && xx >= 0 && xx < w) s = fmaf(av, b[((size_t)img * Cb + ci) * P + yy * w + xx], s);
+        sb += av;
+        if (++p == P) {
+            p = 0;
+            ++img;
+        }
+    }
+    partial[((size_t)blockIdx.z * Ca + co) * Cb * 9 + e] = s;
+    if (e == 0) bias_partial[(size_t)blockIdx.z * Ca + co] = sb;
+}
+
+static int wgrad3x3_slabs(int B, int P, long long* slab_px) {
+    const long long total = (long long)B * P;
+    long long px = (total + 32767) / 32768;
+    if (px < 4096) px = 4096;
+    *slab_px = px;
+    return (int)((total + px - 1) / px);
+}
+
+static size_t wgrad3x3_partial_floats(int B, int Ca, int Cb, int h, int w) {
+    if (w % 4 == 0) return gram2_partial_floats(B, Ca, Cb, h, w, 9);
+    long long px;
+    return (size_t)wgrad3x3_slabs(B, h * w, &px) * ((size_t)9 * Ca * Cb + Ca);
+}
+
+// dW [Ca][Cb][3][3] and db [Ca] (+)= the gradient of a 3x3 convolution with output gradient a [B][Ca][h][w] and input b [B][Cb][h][w]
+static int wm_wgrad3x3(const float* a, int Ca, const float* b, int Cb, float* dW, float* db, float* partial, size_t partial_cap, int B, int h,
+                       int w, int accumulate, hipStream_t st) {
+    if (w % 4 == 0) {
+        Gram2Launch g{};
+        g.a = a; g.a_bstride = (int64_t)Ca * h * w; g.Ca = Ca; g.b = b; g.b_bstride = (int64_t)Cb * h * w; g.Cb = Cb;
+        g.out = dW; g.ld = Cb; g.partial = partial; g.partial_cap = partial_cap; g.B = B; g.h = h; g.w = w; g.ntap = 9;
+        g.accumulate = accumulate != 0; g.db = db;
+        return launch_gram2(g, st);
+    }
+    long long px;
+    const int nslab = wgrad3x3_slabs(B, h * w, &px);
+    const size_t n = (size_t)9 * Ca * Cb;
+    RF_CHECK_ARG((size_t)nslab * (n + Ca) <= partial_cap, "rf_wm_backward: the weight-gradient partials exceed their buffer");
+    float* bias_partial = partial + (size_t)nslab * n;
+    {
+        const double px_all = (double)B * h * w;
+        ProfScope prof(st, "conv3x3_wgrad_kernel", 18.0 * Ca * Cb * px_all, 4.0 * px_all * (Ca + Cb));
+        conv3x3_wgrad_kernel<<<dim3((unsigned)Ca, (unsigned)cdiv(Cb * 9, 256), (unsigned)nslab), 256, 0, st>>>(a, b, partial, bias_partial, Ca, Cb, h,
+                                                                                                               w, (long long)B * h * w, px);
+        RF_TRY(check_launch("conv3x3_wgrad"));
+    }
+    RF_TRY(reduce_rows(partial, dW, nslab, n, accumulate, st));
+    return reduce_rows(bias_partial, db, nslab, (size_t)Ca, accumulate, st);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+struct WmBwdPlan {
+    MambaBwdPlan mb;                      // its u, g and gu buffers hold tok, g_y and g_tok
+    size_t w0, w2;                        // packed convb.0 / convb.2 (forward)
+    size_t t0, t2, ts;                    // transposed, tap-flipped packs of convb.0, convb.2, smooth
+    size_t a1, r, y, ga1;                 // [n][2c][P], [n][c][P] (convb.2's output without the skip), [n][c][P] (y, then g_r), [n][2c][P]
+    size_t lnp, wpart, wpart_cap;         // LayerNorm slabs; weight-gradient partials and their capacity
+    size_t ks, ks_floats;                 // scratch of the 3x3 convolutions' input-channel split (small launches only, else 0 floats)
+};
+
+static int wm_bwd_plan(const char* who, int n, int c, int h, int w, WmBwdPlan* p, Bump* b) {
+    RF_TRY(wm_check_shape(who, n, c, h, w));
+    RF_TRY(mamba_bwd_plan(who, n, h * w, c, kN, kDc, 2, &p->mb, b));
+    const size_t plane = (size_t)n * h * w;
+    p->w0 = b->off(packed3x3_floats(c, 2 * c));
+    p->w2 = b->off(packed3x3_floats(2 * c, c));
+    p->t0 = b->off(packed3x3_floats(2 * c, c));
+    p->t2 = b->off(packed3x3_floats(c, 2 * c));
+    p->ts = b->off(packed3x3_floats(c, c));
+    p->a1 = b->off(plane * 2 * c);
+    p->r = b->off(plane * c);
+    p->y = b->off(plane * c);
+    p->ga1 = b->off(plane * 2 * c);
+    p->lnp = b->off((size_t)2 * n * wm_ln_bwd_nblk(n, h * w) * c);
+    size_t cap = wgrad3x3_partial_floats(n, 2 * c, c, h, w);             // convb.0
+    const size_t c2 = wgrad3x3_partial_floats(n, c, 2 * c, h, w), c3 = wgrad3x3_partial_floats(n, c, c, h, w);
+    cap = cap > c2 ? cap : c2;
+    cap = cap > c3 ? cap : c3;
+    p->wpart_cap = cap;
+    p->wpart = b->off(cap);
+    p->ks_floats = conv3x3_ksplit_floats(n, 2 * c, h, w);                // the widest output of the five convolutions
+    p->ks = b->off(p->ks_floats);
+    return RF_OK;
+}
+
+static int wm_dgrad3x3(const float* dy, const float* wp, float* dx, float* ks, size_t ks_floats, int n, int cout, int cin, int h, int w,
+                       hipStream_t st) {
+    Conv3x3Args a = conv3x3_dense(dy, wp, nullptr, dx, n, cout, cin, h, w, 0);
+    a.ks_scratch = ks; a.ks_floats = ks_floats;
+    return launch_conv3x3(a, st);
+}
+
+static int run_wm_backward(const WmBwdPlan& p, const float* x, const float* g, float* dx, const float* const* prm, float* const* grd, float* ws,
+                           int n, int c, int h, int w, int acc, hipStream_t st) {
+    const int L = h * w;
+    const size_t el = (size_t)n * c * L;
+    float *a1 = ws + p.a1, *r = ws + p.r, *y = ws + p.y, *ga1 = ws + p.ga1, *tok = ws + p.mb.u, *gy = ws + p.mb.g, *gtok = ws + p.mb.gu,
+          *wpart = ws + p.wpart;
+    float* gr = y;                                                          // y is dead once smooth's weight gradient is taken
+    // dX weights of a 3x3 convolution [Cout][Cin][3][3]: rows and columns exchanged, taps flipped
+    const PackDesc packs[3] = {{prm[0], ws + p.t0, 1, c, 2 * c, 9, (int64_t)c * 9, 1},
+                               {prm[2], ws + p.t2, 1, 2 * c, c, 9, (int64_t)2 * c * 9, 1},
+                               {prm[15], ws + p.ts, 1, c, c, 9, (int64_t)c * 9, 1}};
+    RF_TRY(launch_pack_batch(packs, 3, st));
+    // Launches of at most 64 workgroups (single frames of the deep levels) split their input channels over up to eight workgroups:
+    // a chain of 64 chunk barriers becomes eight of 8, and the accumulation runs over an eighth of the 9 Cin products before the
+    // partial tiles are added in split order, which also shortens the rounding chain ("WM backward").  Deterministic.
+    float* ks = p.ks_floats ? ws + p.ks : nullptr;
+    if (ks) RF_TRY(check_hip(hipMemsetAsync(ks, 0, conv3x3_ksplit_counter_bytes(), st), "rf_wm_backward: memset"));
+    WmFrontBufs fb{ws + p.w0, ws + p.w2, a1, r, tok, y};
+    fb.ks = ks; fb.ks_floats = p.ks_floats;
+    RF_TRY(wm_forward_front(p.mb.m, x, prm, nullptr, ws, fb, n, c, h, w, st));
+    // smooth
+    RF_TRY(wm_wgrad3x3(g, c, y, c, grd[15], grd[16], wpart, p.wpart_cap, n, h, w, acc, st));
+    RF_TRY(wm_dgrad3x3(g, ws + p.ts, gy, ks, p.ks_floats, n, c, c, h, w, st));
+    // Mamba, channel-major
+    RF_TRY(run_mamba_backward(p.mb, tok, gy, gtok, prm + 6, grd + 6, ws, n, L, acc, st));
+    // LayerNorm over the runs of c floats + the transposition
+    RF_TRY(launch_wm_ln_bwd(r, x, gtok, prm[4], gr, grd[4], grd[5], ws + p.lnp, n, L, c, acc, st));
+    // convb.2
+    RF_TRY(wm_wgrad3x3(gr, c, a1, 2 * c, grd[2], grd[3], wpart, p.wpart_cap, n, h, w, acc, st));
+    RF_TRY(wm_dgrad3x3(gr, ws + p.t2, ga1, ks, p.ks_floats, n, c, 2 * c, h, w, st));
+    RF_TRY(launch_ewise(ga1, a1, ga1, 2 * el, 2, 0.f, st));                 // ReLU: g_a1 where a1 > 0, else 0
+    // convb.0 and the skip
+    RF_TRY(wm_wgrad3x3(ga1, 2 * c, x, c, grd[0], grd[1], wpart, p.wpart_cap, n, h, w, acc, st));
+    RF_TRY(wm_dgrad3x3(ga1, ws + p.t0, dx, ks, p.ks_floats, n, 2 * c, c, h, w, st));
+    return launch_ewise(dx, gr, dx, el, 0, 0.f, st);
+}
+
+}  // namespace rf
+
+using namespace rf;
+
+extern "C" {
+
+long long rf_wm_backward_workspace_bytes(int n, int c, int h, int w) {
+    WmBwdPlan p;
+    Bump b;
+    const int rc = wm_bwd_plan("rf_wm_backward_workspace_bytes", n, c, h, w, &p, &b);
+    return rc ? rc : (long long)(b.used * sizeof(float));
+}
+
+int rf_wm_backward(const float* in, const float* grad_out, float* grad_in, const float* const* prm, float* const* grad_prm, void* workspace,
+                   size_t workspace_bytes, int n, int c, int h, int w, int accumulate, void* stream) {
+    WmBwdPlan p;
+    Bump b;
+    RF_TRY(wm_bwd_plan("rf_wm_backward", n, c, h, w, &p, &b));
+    RF_CHECK_ARG(in && grad_out && grad_in && prm && grad_prm && workspace && aligned16(in) && aligned16(grad_out) && aligned16(grad_in) &&
+                     aligned16(workspace),
+                 "rf_wm_backward: in, grad_out, grad_in, prm, grad_prm and workspace must be non-null and 16-byte aligned");
+    if (workspace_bytes < b.used * sizeof(float)) {
+        set_error("rf_wm_backward: workspace of %zu bytes, %zu needed", workspace_bytes, b.used * sizeof(float));
+        return RF_E_NOMEM;
+    }
+    RF_CHECK_ARG(in != grad_out && in != grad_in && grad_out != grad_in, "rf_wm_backward: in, grad_out and grad_in may not alias each other");
+    for (int i = 0; i < 17; ++i) RF_CHECK_ARG(prm[i] != nullptr && grad_prm[i] != nullptr, "rf_wm_backward: parameter or gradient %d is null", i);
+    return run_wm_backward(p, in, grad_out, grad_in, prm, grad_prm, (float*)workspace, n, c, h, w, accumulate, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -705,6 +705,15 @@ def mamba_backward(u: torch.Tensor, params, grad_out: torch.Tensor, prefix: str 
     return grad_u, grads
 
 
+def wm_param_shapes(c: int):
+    """Names and shapes of the 17 tensors ``wm`` reads, in the order of the C ABI's pointer array."""
+    shapes = {"convb.0.weight": (2 * c, c, 3, 3), "convb.0.bias": (2 * c,), "convb.2.weight": (c, 2 * c, 3, 3), "convb.2.bias": (c,),
+              "ln.weight": (c,), "ln.bias": (c,)}
+    shapes.update({"model1." + k: v for k, v in mamba_param_shapes(c).items()})
+    shapes.update({"smooth.weight": (c, c, 3, 3), "smooth.bias": (c,)})
+    return shapes
+
+
 def wm(x: torch.Tensor, params, prefix: str = "") -> torch.Tensor:
     """``WM(c)(x)`` (RawFomer_WFB_FFAB/model.py:138-172) on ``[n, c, h, w]``: ``convb`` + residual, LayerNorm over the runs of ``c``
     floats of the NCHW memory (the reference's raw ``reshape(b, -1, c)``), ``model1`` = ``Mamba(c, 32, 4, 2)``, ``smooth``.  Reads
@@ -721,6 +730,33 @@ def wm(x: torch.Tensor, params, prefix: str = "") -> torch.Tensor:
     with torch.cuda.device(x.device):
         _lib.check(lib.rf_wm_forward(_ptr(x), _ptr(out), _ptr_array(ts), _ptr(ws), ws.numel(), n, c, h, w, _stream(x)), "rf_wm_forward")
     return out
+
+
+def wm_backward(x: torch.Tensor, params, grad_out: torch.Tensor, prefix: str = "", grads=None):
+    """The gradient of ``wm``: ``(grad_x, grads)`` for ``grad_out`` = dL/d ``wm(x, params)``.  ``grads`` maps the 17 keys ``wm`` reads
+    (``prefix`` included) to gradients of the parameters' shapes (``wm_param_shapes``; ``model1.conv1d.weight``: ``[Di, 1, 4]``);
+    ``model2`` and ``softmax`` are never called by the reference and have none.  Passing the ``grads`` of an earlier call ADDS to its
+    tensors; ``grad_x`` is always a new tensor.  The forward intermediates are recomputed: nothing is kept from a ``wm`` call, and
+    ``x``, ``grad_out`` and ``params`` are not written."""
+    x, grad_out = _chk(x, "x"), _chk(grad_out, "grad_out")
+    if x.dim() != 4 or tuple(grad_out.shape) != tuple(x.shape):
+        raise RuntimeError(f"wm_backward: expected 4-D x and grad_out of one shape, got {tuple(x.shape)} and {tuple(grad_out.shape)}")
+    n, c, h, w = x.shape
+    shapes = wm_param_shapes(c)
+    ts = _shaped(params, prefix, _WM_KEYS, shapes, "wm_backward")
+    accumulate = grads is not None
+    if grads is None:
+        grads = {prefix + k: torch.empty_like(t) for k, t in zip(_WM_KEYS, ts)}
+    gs = _shaped(grads, prefix, _WM_KEYS, shapes, "wm_backward (grads)")
+    if any(t.data_ptr() != grads[prefix + k].data_ptr() for k, t in zip(_WM_KEYS, gs)):
+        raise RuntimeError("wm_backward: the tensors of grads must be contiguous (they are written in place)")
+    lib = _lib.load()
+    ws = _workspace(lib.rf_wm_backward_workspace_bytes(n, c, h, w), "rf_wm_backward_workspace_bytes", x)
+    grad_x = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.rf_wm_backward(_ptr(x), _ptr(grad_out), _ptr(grad_x), _ptr_array(ts), _ptr_array(gs), _ptr(ws), ws.numel(), n, c, h, w,
+                                      int(accumulate), _stream(x)), "rf_wm_backward")
+    return grad_x, grads
 
 
 def wmb(x: torch.Tensor, params, prefix: str = "") -> torch.Tensor:

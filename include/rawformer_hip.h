@@ -384,6 +384,16 @@ int rf_mamba_backward(const float* in, const float* grad_out, float* grad_in, co
 long long rf_wm_workspace_bytes(int n, int c, int h, int w);
 int rf_wm_forward(const float* in, float* out, const float* const* prm, void* workspace, size_t workspace_bytes,
                   int n, int c, int h, int w, void* stream);
+/* WM's gradient: (in, grad_out = dL/d out, prm) -> grad_in = dL/d in and grad_prm, a HOST array of 17 device pointers with
+ * prm's order and shapes.  Nothing is kept from a forward call: the intermediates are recomputed with the forward's own kernels.
+ * Every shape rf_wm_forward accepts is accepted (widths that are no multiple of 4 take a plain 3x3 weight-gradient kernel).
+ * in, grad_out, grad_in and workspace are 16-byte aligned; in, grad_out, grad_in may not alias each other; in, grad_out and
+ * the parameters are not written.  grad_in is always overwritten; accumulate != 0 ADDS to the 17 grad_prm tensors, 0 overwrites
+ * them.  Every sum runs in a fixed order (no float atomics): two runs give the same bits.  A workspace smaller than
+ * rf_wm_backward_workspace_bytes is refused with -12. */
+long long rf_wm_backward_workspace_bytes(int n, int c, int h, int w);
+int rf_wm_backward(const float* in, const float* grad_out, float* grad_in, const float* const* prm, float* const* grad_prm,
+                   void* workspace, size_t workspace_bytes, int n, int c, int h, int w, int accumulate, void* stream);
 
 
 /* ---- the three fused element-wise kernels of a WMB block as RF_VARIANT_WFB schedules it (csrc/rf_wmb.hip) ----------
