@@ -50,6 +50,7 @@ SIGNATURES = {
     "rf_workspace_bytes": (_i, [_vp, _i, _i, _i, _psz]),
     "rf_forward": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     "rf_forward_stage": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
+    "rf_tc_guidance": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "rf_set_shard": (_i, [_vp, _i, _i, _i, ALLREDUCE_FN, _vp]),
     "rf_set_shard_grid": (_i, [_vp, _i, _i, _i, _i, _i, _i, ALLREDUCE_FN, _vp]),
     "rf_flat_param_floats": (_i, [_vp, _psz]),
@@ -126,6 +127,11 @@ SIGNATURES = {
     "rf_wmb_front": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "rf_wmb_back": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "rf_wmb_ffn_sum": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "rf_tc_spatial": (_i, [_vp] * 9 + [_i, _i, _i, _i, _vp]),
+    "rf_tc_nblk": (_i, [_i, _i]),
+    "rf_tc_residual": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "rf_tc_color_head": (_i, [_vp] * 10 + [_i, _sz, _vp]),
+    "rf_tc_pyramid": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
 }
 
 _lib = None

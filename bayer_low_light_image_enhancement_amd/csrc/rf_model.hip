@@ -519,7 +519,6 @@ int rf_forward_stage(rf_handle* h, int stage, const float* in, const float* pack
     RF_CHECK_ARG(h && in && out && workspace && stage >= 1 && stage <= 7, "rf_forward_stage: bad arguments (stage 1..7)");
     const VariantTraits& vt = h->vt;
     RF_CHECK_ARG(!vt.stage_needs_packed_frame || packed, "rf_forward_stage: the FLCA branch needs the packed frame for its guidance");
-    RF_CHECK_ARG(vt.branch != BR_TC, "rf_forward_stage: not available for the TrueColor variant");
     Plan p;
     RF_TRY(check_call("rf_forward_stage", h, in, out, workspace, workspace_bytes, B, H, W, p));
     RF_CHECK_ARG(vt.branch != BR_ML || aligned16(packed), "rf_forward_stage: buffers must be 16-byte aligned");
@@ -528,6 +527,28 @@ int rf_forward_stage(rf_handle* h, int stage, const float* in, const float* pack
     RF_TRY(run_guidance(h, packed, 0, h->stage[stage].lvl, ws, p, B, H, W, st, st));
     if (p.ks_floats) RF_TRY(check_hip(hipMemsetAsync(ws + p.ks, 0, conv3x3_ksplit_counter_bytes(), st), "rf_forward_stage: memset"));
     return run_stage(h, stage, in, out, ws, p, B, H, W, st, st);
+}
+
+int rf_tc_guidance(rf_handle* h, const float* packed, int level, float* y, float* crcb, float* rgb, float* guide, void* workspace,
+                   size_t workspace_bytes, int B, int H, int W, void* stream) {
+    RF_CHECK_ARG(h && packed && y && crcb && rgb && guide && workspace, "rf_tc_guidance: null argument");
+    RF_CHECK_ARG(h->vt.branch == BR_TC, "rf_tc_guidance: the TrueColor variant only");
+    RF_CHECK_ARG(level >= 0 && level <= 3, "rf_tc_guidance: U-Net level %d (0..3)", level);
+    Plan p;
+    RF_TRY(check_call("rf_tc_guidance", h, packed, guide, workspace, workspace_bytes, B, H, W, p));
+    RF_CHECK_ARG(aligned16(y) && aligned16(crcb) && aligned16(rgb), "rf_tc_guidance: buffers must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    float* ws = (float*)workspace;
+    RF_TRY(run_guidance(h, packed, 0, level, ws, p, B, H, W, st, st));
+    const float *sy, *scrcb, *srgb;
+    RF_TRY(tc_front_outputs(ws + p.gscratch, &sy, &scrcb, &srgb, B, H, W, h->vt.levels));
+    const size_t hw = (size_t)H * W, f = sizeof(float);
+    // y is plane 3 of cin4 [B,4,H,W]: one row of hw floats per image, 4 hw apart
+    RF_TRY(check_hip(hipMemcpy2DAsync(y, hw * f, sy, 4 * hw * f, hw * f, (size_t)B, hipMemcpyDeviceToDevice, st), "rf_tc_guidance: copy y"));
+    RF_TRY(check_hip(hipMemcpyAsync(crcb, scrcb, (size_t)B * 2 * hw * f, hipMemcpyDeviceToDevice, st), "rf_tc_guidance: copy crcb"));
+    RF_TRY(check_hip(hipMemcpyAsync(rgb, srgb, (size_t)B * 3 * hw * f, hipMemcpyDeviceToDevice, st), "rf_tc_guidance: copy rgb"));
+    return check_hip(hipMemcpyAsync(guide, ws + p.guide[level], (size_t)B * 7 * (H >> level) * (W >> level) * f, hipMemcpyDeviceToDevice, st),
+                     "rf_tc_guidance: copy guide");
 }
 
 int rf_forward(rf_handle* h, const float* in, float* out, void* workspace, size_t workspace_bytes,

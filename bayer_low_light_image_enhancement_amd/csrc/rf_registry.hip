@@ -277,7 +277,7 @@ int rf_create(const rf_config* cfg, rf_handle** out) {
     vt.guide_planes = vt.branch == BR_ML ? 2 * vt.levels + 2 : vt.branch == BR_TC ? 7 : 4;
     vt.log_temperature = vt.branch == BR_TC;
     vt.shardable = v == RF_VARIANT_FLCA || v == RF_VARIANT_PLAIN;
-    vt.stage_needs_packed_frame = vt.branch == BR_FLCA || vt.branch == BR_ML;
+    vt.stage_needs_packed_frame = vt.branch == BR_FLCA || vt.branch == BR_ML || vt.branch == BR_TC;
     if (vt.branch == BR_TC) add_bayer_processor(h);
     add_wb(h, "embedding", {d, 4 * cfg->inp_channels, 3, 3}, h->embedding_w, h->embedding_b);
     add_pack(h, h->embedding_w, PK_3x3);

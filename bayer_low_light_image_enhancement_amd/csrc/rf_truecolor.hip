@@ -424,3 +424,62 @@ int launch_tc_color_head(float* x, const float* const* prm /* gamma, ct.0.w, ct.
 }
 
 }  // namespace rf
+
+using namespace rf;
+
+// ---- the kernels one by one (include/rawformer_hip.h): argument checks, then the launch functions above ----------------------
+namespace {
+
+bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+
+// what the spatial and residual kernels index with int: B in the grid, h * w pixels
+int tc_check_shape(const char* who, int B, int C, int h, int w) {
+    RF_CHECK_ARG(B >= 1 && B <= 65535 && C >= 1 && h >= 1 && w >= 1, "%s: B=%d C=%d h=%d w=%d: every size must be positive and B <= 65535", who, B, C, h, w);
+    RF_CHECK_ARG(C <= 512, "%s: C=%d > 512 not supported", who, C);
+    RF_CHECK_ARG((size_t)h * w <= (1u << 28), "%s: a %dx%d plane exceeds 2^28 pixels", who, h, w);
+    return RF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rf_tc_spatial(const float* feat, const float* guide, const float* w_col, const float* b_col, const float* w_low, const float* b_low,
+                  const float* w_high, const float* b_high, float* xs, int B, int C, int h, int w, void* stream) {
+    RF_CHECK_ARG(feat && guide && w_col && b_col && w_low && b_low && w_high && b_high && xs, "rf_tc_spatial: null argument");
+    RF_TRY(tc_check_shape("rf_tc_spatial", B, C, h, w));
+    RF_CHECK_ARG(aligned4(feat) && aligned4(guide) && aligned4(xs) && aligned4(w_col) && aligned4(b_col) && aligned4(w_low) && aligned4(b_low) &&
+                     aligned4(w_high) && aligned4(b_high), "rf_tc_spatial: buffers must be 4-byte aligned");
+    return launch_tc_spatial(feat, xs, guide, w_col, b_col, w_low, b_low, w_high, b_high, B, C, h, w, (hipStream_t)stream);
+}
+
+int rf_tc_nblk(int h, int w) {
+    RF_CHECK_ARG(h >= 1 && w >= 1 && (size_t)h * w <= (1u << 28), "rf_tc_nblk: a %dx%d plane", h, w);
+    return tc_nblk(h, w);
+}
+
+int rf_tc_residual(const float* xs, const float* r, float* x2, float* partial, int B, int C, int h, int w, void* stream) {
+    RF_CHECK_ARG(xs && r && x2 && partial, "rf_tc_residual: null argument");
+    RF_TRY(tc_check_shape("rf_tc_residual", B, C, h, w));
+    RF_CHECK_ARG(aligned4(xs) && aligned4(r) && aligned4(x2) && aligned4(partial), "rf_tc_residual: buffers must be 4-byte aligned");
+    RF_CHECK_ARG(w % 4 != 0 || (aligned16(xs) && aligned16(r) && aligned16(x2)),
+                 "rf_tc_residual: buffers must be 16-byte aligned where the width is a multiple of 4");
+    return launch_tc_residual(xs, r, x2, partial, B, C, h, w, (hipStream_t)stream);
+}
+
+int rf_tc_color_head(float* x, const float* gamma, const float* ct0_w, const float* ct0_b, const float* ct2_w, const float* ct2_b,
+                     const float* tone0_w, const float* tone0_b, const float* tone2_w, const float* tone2_b, int B, size_t P, void* stream) {
+    const float* prm[9] = {gamma, ct0_w, ct0_b, ct2_w, ct2_b, tone0_w, tone0_b, tone2_w, tone2_b};
+    RF_CHECK_ARG(x && aligned4(x), "rf_tc_color_head: the image is null or not 4-byte aligned");
+    for (const float* p : prm) RF_CHECK_ARG(p && aligned4(p), "rf_tc_color_head: a parameter pointer is null or not 4-byte aligned");
+    RF_CHECK_ARG(B >= 1 && B <= 65535 && P >= 1 && P <= ((size_t)1 << 40), "rf_tc_color_head: B=%d P=%zu: B in 1..65535, P in 1..2^40", B, P);
+    return launch_tc_color_head(x, prm, B, P, (hipStream_t)stream);
+}
+
+int rf_tc_pyramid(const float* src, float* ll, float* mag, int B, int hs, int ws, void* stream) {
+    RF_CHECK_ARG(src && ll && mag && aligned4(src) && aligned4(ll) && aligned4(mag), "rf_tc_pyramid: a buffer is null or not 4-byte aligned");
+    RF_CHECK_ARG(B >= 1 && (size_t)(hs > 0 ? hs : 0) * (ws > 0 ? ws : 0) <= (1u << 30), "rf_tc_pyramid: B=%d, a %dx%d plane", B, hs, ws);
+    return launch_tc_pyramid(src, ll, mag, B, hs, ws, (hipStream_t)stream);
+}
+
+}  // extern "C"

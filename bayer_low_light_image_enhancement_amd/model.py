@@ -451,8 +451,9 @@ class RawFormer(nn.Module):
 
     def forward_stage(self, stage: int, x: torch.Tensor, packed: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One ``conv_tran<stage>`` (``Conv_Transformer``) exactly as ``forward`` schedules it.  ``x``: the stage input
-        ``[B, dim*2^l, H>>l, W>>l]``; ``packed``: the packed frame ``[B,4,H,W]`` the FLCA guidance is derived from
-        (``variant='flca'`` and ``'multilvl'``; for ``'plain'`` pass ``None`` and H, W are taken from ``x``)."""
+        ``[B, dim*2^l, H>>l, W>>l]``; ``packed``: the packed frame ``[B,4,H,W]`` the branch's guidance is derived from
+        (``variant='flca'``, ``'multilvl'`` and ``'truecolor'``, whose front end -- ``EnhancedBayerProcessor`` with the model's
+        own parameters -- runs on it first; for ``'plain'`` and ``'wfb'`` pass ``None`` and H, W are taken from ``x``)."""
         if x.device.type != "cuda":
             raise RuntimeError("RawFormer (HIP) needs a ROCm device tensor: there is no CPU path in this package")
         self._refuse_training_mode()
@@ -482,6 +483,36 @@ class RawFormer(nn.Module):
                                             C.c_void_p(out.data_ptr()), C.c_void_p(st.workspace.data_ptr()),
                                             st.workspace.numel(), b, H, W, stream), "rf_forward_stage")
         return out
+
+    def tc_guidance(self, packed: torch.Tensor, level: int):
+        """``variant='truecolor'``: the front end on a packed frame ``[B,4,H,W]`` exactly as ``forward`` runs it, and the seven
+        guidance planes an ``EnhancedFLCA`` block sees at U-Net level ``level`` (0..3).  Returns ``(y [B,1,H,W], crcb [B,2,H,W],
+        rgb [B,3,H,W], guide [B,7,H>>level,W>>level])``: ``EnhancedBayerProcessor``'s outputs (BayerTORGBColorMultiLvl.py:100-134)
+        and ``[y, cr, cb, R, G, y_low, y_high]`` (:255-275)."""
+        if packed.device.type != "cuda":
+            raise RuntimeError("RawFormer (HIP) needs a ROCm device tensor: there is no CPU path in this package")
+        if self.variant != "truecolor":
+            raise RuntimeError(f"tc_guidance: variant 'truecolor' only, not {self.variant!r}")
+        packed = packed.detach().float().contiguous()
+        if packed.dim() != 4 or packed.shape[1] != 4:
+            raise RuntimeError(f"expected a packed frame [B,4,H,W], got {tuple(packed.shape)}")
+        b, _, H, W = packed.shape
+        lib = _lib.load()
+        with torch.cuda.device(packed.device):
+            st = self._state_for(packed.device)
+            self._sync_params(st, packed.device)
+            sz = C.c_size_t()
+            _lib.check(lib.rf_workspace_bytes(st.handle, b, H, W, C.byref(sz)), "rf_workspace_bytes")
+            if st.workspace is None or st.workspace.numel() < sz.value:
+                st.workspace = None
+                st.workspace = torch.empty(sz.value, dtype=torch.uint8, device=packed.device)
+            new = lambda c, hh, ww: torch.empty((b, c, hh, ww), dtype=torch.float32, device=packed.device)      # noqa: E731
+            y, crcb, rgb, guide = new(1, H, W), new(2, H, W), new(3, H, W), new(7, H >> max(level, 0), W >> max(level, 0))
+            stream = C.c_void_p(torch.cuda.current_stream(packed.device).cuda_stream)
+            _lib.check(lib.rf_tc_guidance(st.handle, C.c_void_p(packed.data_ptr()), int(level), C.c_void_p(y.data_ptr()),
+                                          C.c_void_p(crcb.data_ptr()), C.c_void_p(rgb.data_ptr()), C.c_void_p(guide.data_ptr()),
+                                          C.c_void_p(st.workspace.data_ptr()), st.workspace.numel(), b, H, W, stream), "rf_tc_guidance")
+        return y, crcb, rgb, guide
 
     def workspace_bytes(self, batch: int, H: int, W: int) -> int:
         probe, sz = C.c_void_p(), C.c_size_t()

@@ -811,3 +811,90 @@ def wmb_ffn_tail(t: torch.Tensor, y: torch.Tensor, weight: torch.Tensor, bias: t
     with torch.cuda.device(t.device):
         _lib.check(_lib.load().rf_wmb_ffn_sum(_ptr(t), _ptr(y), _ptr(out), _ptr(weight), _ptr(bias), b, c, h, w, _stream(t)), "rf_wmb_ffn_sum")
     return out
+
+
+# ------------------------------------------------------------------------------------------ the TrueColor variant's kernels one by one
+def tc_spatial(feat: torch.Tensor, guide: torch.Tensor, params, prefix: str = "", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The spatial gate of ``EnhancedFLCA.forward`` (BayerTORGBColorMultiLvl.py:277-283) given the seven guidance planes
+    ``guide`` [B,7,h,w] at the feature size: ``feat * (1 + sigmoid(color_attention(guide[:, 0:5])) + tanh(sigmoid(low_attn(guide[:, 5:6]))
+    + tanh(high_attn(guide[:, 6:7]))))``.  ``params``: the block's ``state_dict`` (``color_attention.0.*``, ``low_attn.0.*``,
+    ``high_attn.0.*``).  ``out``: where to write (default: a new tensor)."""
+    feat, guide = _chk(feat, "feat"), _chk(guide, "guide")
+    b, c, h, w = feat.shape
+    if tuple(guide.shape) != (b, 7, h, w):
+        raise RuntimeError(f"tc_spatial: guide must be {(b, 7, h, w)}, got {tuple(guide.shape)}")
+    prm = []
+    for key, shape in (("color_attention.0.weight", (c, 5, 3, 3)), ("color_attention.0.bias", (c,)), ("low_attn.0.weight", (c, 1, 3, 3)),
+                       ("low_attn.0.bias", (c,)), ("high_attn.0.weight", (c, 1, 3, 3)), ("high_attn.0.bias", (c,))):
+        t = _chk(params[prefix + key], key)
+        if tuple(t.shape) != shape:
+            raise RuntimeError(f"tc_spatial: {key} must be {shape}, got {tuple(t.shape)}")
+        prm.append(t)
+    out = torch.empty_like(feat) if out is None else out
+    if tuple(out.shape) != tuple(feat.shape) or not out.is_contiguous() or out.dtype != torch.float32 or out.device != feat.device:
+        raise RuntimeError("tc_spatial: out must be a contiguous float32 tensor of feat's shape on its device")
+    with torch.cuda.device(feat.device):
+        _lib.check(_lib.load().rf_tc_spatial(_ptr(feat), _ptr(guide), *[_ptr(t) for t in prm], _ptr(out), b, c, h, w, _stream(feat)),
+                   "rf_tc_spatial")
+    return out
+
+
+def tc_nblk(h: int, w: int) -> int:
+    """Blocks per image of ``tc_residual``'s pooling sums: 1024 consecutive pixels each where ``w % 4 == 0``, else 256."""
+    n = _lib.load().rf_tc_nblk(int(h), int(w))
+    _lib.check(min(n, 0), "rf_tc_nblk")
+    return n
+
+
+def tc_residual(xs: torch.Tensor, r: torch.Tensor, out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``x2 = xs + 0.2 tanh(r)`` (EnhancedFLCA.forward, BayerTORGBColorMultiLvl.py:285-288; ``r = res_proj(xs)``) and the
+    squeeze-excite pooling sums ``partial`` [B, tc_nblk(h, w), C]: entry ``[b, k, c]`` is the sum of ``x2[b, c]`` over block ``k`` of
+    the flattened plane.  ``out`` may be ``xs`` itself (the forward writes in place)."""
+    xs, r = _chk(xs, "xs"), _chk(r, "r")
+    b, c, h, w = xs.shape
+    if tuple(r.shape) != tuple(xs.shape):
+        raise RuntimeError(f"tc_residual: xs {tuple(xs.shape)} and r {tuple(r.shape)} differ")
+    out = torch.empty_like(xs) if out is None else out
+    if tuple(out.shape) != tuple(xs.shape) or not out.is_contiguous() or out.dtype != torch.float32 or out.device != xs.device:
+        raise RuntimeError("tc_residual: out must be a contiguous float32 tensor of xs's shape on its device")
+    if c > 512:
+        raise RuntimeError(f"tc_residual: C={c} > 512 not supported")
+    partial = torch.empty((b, tc_nblk(h, w), c), dtype=torch.float32, device=xs.device)
+    with torch.cuda.device(xs.device):
+        _lib.check(_lib.load().rf_tc_residual(_ptr(xs), _ptr(r), _ptr(out), _ptr(partial), b, c, h, w, _stream(xs)), "rf_tc_residual")
+    return out, partial
+
+
+def tc_color_head(x: torch.Tensor, params, prefix: str = "") -> torch.Tensor:
+    """``CameraAwareColorCorrection()(x)`` (BayerTORGBColorMultiLvl.py:160-176) on ``x`` [B,3,...]: clamp, ``pow(1 / gamma)``, the
+    3 -> 64 -> 3 colour transform, the per-channel tone curve, clamp.  ``params``: the module's ``state_dict``.  A new tensor."""
+    x = _chk(x, "x")
+    if x.dim() < 3 or x.shape[1] != 3:
+        raise RuntimeError(f"tc_color_head: expected [B,3,...], got {tuple(x.shape)}")
+    prm = []
+    for key, n in (("gamma_param", 1), ("color_transform.0.weight", 192), ("color_transform.0.bias", 64), ("color_transform.2.weight", 192),
+                   ("color_transform.2.bias", 3), ("tone_curve.0.weight", 32), ("tone_curve.0.bias", 32), ("tone_curve.2.weight", 32),
+                   ("tone_curve.2.bias", 1)):
+        t = _chk(params[prefix + key], key)
+        if t.numel() != n:
+            raise RuntimeError(f"tc_color_head: {key} must have {n} elements, got {t.numel()}")
+        prm.append(t)
+    out = x.clone()
+    b = x.shape[0]
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().rf_tc_color_head(_ptr(out), *[_ptr(t) for t in prm], b, x[0, 0].numel(), _stream(x)), "rf_tc_color_head")
+    return out
+
+
+def tc_pyramid(src: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One level of ``EnhancedFLCA._pyramid_y`` (BayerTORGBColorMultiLvl.py:236-247) on planes ``src`` [B,1,h,w]: the Haar LL band and
+    the high-band magnitude ``sqrt(LH^2 + HL^2 + HH^2 + 1e-8)``, each [B,1,ceil(h/2),ceil(w/2)]; an odd side is reflect-padded."""
+    src = _chk(src, "src")
+    if src.dim() != 4 or src.shape[1] != 1:
+        raise RuntimeError(f"tc_pyramid: expected [B,1,h,w], got {tuple(src.shape)}")
+    b, _, h, w = src.shape
+    ll = torch.empty((b, 1, (h + 1) // 2, (w + 1) // 2), dtype=torch.float32, device=src.device)
+    mag = torch.empty_like(ll)
+    with torch.cuda.device(src.device):
+        _lib.check(_lib.load().rf_tc_pyramid(_ptr(src), _ptr(ll), _ptr(mag), b, h, w, _stream(src)), "rf_tc_pyramid")
+    return ll, mag

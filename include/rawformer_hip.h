@@ -122,9 +122,16 @@ int rf_set_shard_grid(rf_handle* h, int y_lo, int y_hi, int total_rows, int x_lo
  * 1x1 -> 3x3 -> LeakyReLU; FrequencyawareLumaChromaAttentionRAWFormer.py:257-278, RawFomer_WFB_FFAB/model.py:393-412,
  * model.py:94-108), including the squeeze-excite fold into channel_reduce.  stage = 1..7 (conv_tran<stage>), at U-Net
  * level l = stage-1 (encoder) or 7-stage (decoder): in/out [B, dim*2^l, H>>l, W>>l]; packed [B,4,H,W] feeds the FLCA
- * guidance (may be NULL for the plain variant).  Workspace as for rf_forward(B, H, W). */
+ * guidance, and for RF_VARIANT_TRUECOLOR its front end (EnhancedBayerProcessor with the handle's parameters), which runs first
+ * (may be NULL for the plain and wfb variants).  Workspace as for rf_forward(B, H, W). */
 int rf_forward_stage(rf_handle* h, int stage, const float* in, const float* packed, float* out, void* workspace,
                      size_t workspace_bytes, int B, int H, int W, void* stream);
+/* RF_VARIANT_TRUECOLOR, diagnostic: the front end (EnhancedBayerProcessor, BayerTORGBColorMultiLvl.py:100-134, and the Haar pyramid
+ * of its luma) on a packed frame [B,4,H,W] with the handle's parameters, and the seven guidance planes an EnhancedFLCA block sees
+ * at U-Net level `level` (0..3), exactly as rf_forward runs them.  Copies out y [B,1,H,W], crcb [B,2,H,W], rgb [B,3,H,W] (the
+ * refined rgb) and guide [B,7,H>>level,W>>level] = (y, cr, cb, R, G, y_low, y_high).  Workspace as for rf_forward(B, H, W). */
+int rf_tc_guidance(rf_handle* h, const float* packed, int level, float* y, float* crcb, float* rgb, float* guide, void* workspace,
+                   size_t workspace_bytes, int B, int H, int W, void* stream);
 
 /* ---- training step (reference train.py:127-147: forward, loss, backward; optimiser train.py:113) ----
  * Parameters, gradients and the Adam moments live in FLAT float buffers: parameter i of the registry sits at float offset
@@ -407,6 +414,26 @@ int rf_wmb_front(const float* x, float* t, float* bands, const float* w2, const 
 int rf_wmb_back(const float* bands, const float* t, float* out, int B, int C, int h, int w, void* stream);
 int rf_wmb_ffn_sum(const float* t, const float* y, float* out, const float* ln_w, const float* ln_b, int B, int C, int h, int w,
                     void* stream);
+
+/* ---- the element-wise kernels of RF_VARIANT_TRUECOLOR one by one (csrc/rf_truecolor.hip; BayerTORGBColorMultiLvl.py) ----------
+ * No handle: the caller passes the raw parameter tensors.  Every argument is checked before any launch (RF_E_INVALID).
+ * rf_tc_spatial: xs = feat * (1 + sigmoid(conv3x3(guide[0:5]; w_col, b_col)) + tanh(sigmoid(conv3x3(guide[5]; w_low, b_low)) +
+ * tanh(conv3x3(guide[6]; w_high, b_high)))) (EnhancedFLCA.forward, :277-283).  feat, xs [B,C,h,w]; guide [B,7,h,w]; w_col [C,5,3,3],
+ * w_low, w_high [C,1,3,3], the biases [C]; C <= 512.  16 bytes per lane where w % 4 == 0 and feat, xs are 16-byte aligned.
+ * rf_tc_residual: x2 = xs + 0.2 tanh(r) (:285-288) and partial[b][blk][c] = the sum of x2 over the pixels of block blk, the
+ * squeeze-excite pooling sums (:289); a block is 1024 consecutive pixels where w % 4 == 0 (then xs, r, x2 must be 16-byte
+ * aligned), else 256; rf_tc_nblk(h, w) blocks per image.  x2 may be xs.  C <= 512.  Fixed summation order, no atomics.
+ * rf_tc_color_head: CameraAwareColorCorrection.forward (:160-176) in place on x [B,3,P]; gamma [1], ct0_w [64,3], ct0_b [64],
+ * ct2_w [3,64], ct2_b [3], tone0_w [32], tone0_b [32], tone2_w [32], tone2_b [1].
+ * rf_tc_pyramid: one more level of EnhancedFLCA._pyramid_y (:236-247): ll = Haar LL of src, mag = sqrt(LH^2 + HL^2 + HH^2 + 1e-8);
+ * src [B,hs,ws] with hs, ws >= 2 (an odd side is reflect-padded as HaarDWT does), ll, mag [B,ceil(hs/2),ceil(ws/2)]. */
+int rf_tc_spatial(const float* feat, const float* guide, const float* w_col, const float* b_col, const float* w_low, const float* b_low,
+                  const float* w_high, const float* b_high, float* xs, int B, int C, int h, int w, void* stream);
+int rf_tc_nblk(int h, int w);
+int rf_tc_residual(const float* xs, const float* r, float* x2, float* partial, int B, int C, int h, int w, void* stream);
+int rf_tc_color_head(float* x, const float* gamma, const float* ct0_w, const float* ct0_b, const float* ct2_w, const float* ct2_b,
+                     const float* tone0_w, const float* tone0_b, const float* tone2_w, const float* tone2_b, int B, size_t P, void* stream);
+int rf_tc_pyramid(const float* src, float* ll, float* mag, int B, int hs, int ws, void* stream);
 
 #ifdef __cplusplus
 }
