@@ -51,6 +51,8 @@ SIGNATURES = {
     "rf_forward": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     "rf_forward_stage": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "rf_tc_guidance": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
+    "rf_ml_guidance": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
+    "rf_ml_tail": (_i, [_vp, _vp, _vp, _i, _vp, _sz, _i, _i, _i, _vp]),
     "rf_set_shard": (_i, [_vp, _i, _i, _i, ALLREDUCE_FN, _vp]),
     "rf_set_shard_grid": (_i, [_vp, _i, _i, _i, _i, _i, _i, ALLREDUCE_FN, _vp]),
     "rf_flat_param_floats": (_i, [_vp, _psz]),
@@ -132,6 +134,9 @@ SIGNATURES = {
     "rf_tc_residual": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "rf_tc_color_head": (_i, [_vp] * 10 + [_i, _sz, _vp]),
     "rf_tc_pyramid": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "rf_ml_modulate": (_i, [_vp, _vp, _vp, _i, _i] + [_vp] * 5 + [_i, _i, _i, _i, _vp]),
+    "rf_ml_step_fused": (_i, [_vp, _vp, _vp, _i, _i] + [_vp] * 10 + [_i, _i, _i, _i, _vp]),
+    "rf_ml_residual": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
 }
 
 _lib = None

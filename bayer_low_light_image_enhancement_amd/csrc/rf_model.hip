@@ -551,6 +551,39 @@ int rf_tc_guidance(rf_handle* h, const float* packed, int level, float* y, float
                      "rf_tc_guidance: copy guide");
 }
 
+int rf_ml_guidance(rf_handle* h, const float* packed, int level, float* guide, float* means, void* workspace, size_t workspace_bytes,
+                   int B, int H, int W, void* stream) {
+    RF_CHECK_ARG(h && packed && guide && means && workspace, "rf_ml_guidance: null argument");
+    RF_CHECK_ARG(h->vt.branch == BR_ML, "rf_ml_guidance: the multi-level variant only");
+    RF_CHECK_ARG(level >= 0 && level <= 3, "rf_ml_guidance: U-Net level %d (0..3)", level);
+    Plan p;
+    RF_TRY(check_call("rf_ml_guidance", h, packed, guide, workspace, workspace_bytes, B, H, W, p));
+    RF_CHECK_ARG(aligned16(means), "rf_ml_guidance: buffers must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    float* ws = (float*)workspace;
+    const int L = h->vt.levels;
+    RF_TRY(run_guidance(h, packed, 0, level, ws, p, B, H, W, st, st));
+    const size_t f = sizeof(float);
+    RF_TRY(check_hip(hipMemcpyAsync(guide, ws + p.guide[level], (size_t)B * (2 * L + 2) * (H >> level) * (W >> level) * f, hipMemcpyDeviceToDevice, st),
+                     "rf_ml_guidance: copy guide"));
+    return check_hip(hipMemcpyAsync(means, ml_level_means(ws + p.gscratch, level, B, H, W, L), (size_t)B * 8 * f, hipMemcpyDeviceToDevice, st),
+                     "rf_ml_guidance: copy means");
+}
+
+int rf_ml_tail(rf_handle* h, float* image, const float* in, int packed_input, void* workspace, size_t workspace_bytes, int B, int H, int W,
+               void* stream) {
+    RF_CHECK_ARG(h && image && in && workspace, "rf_ml_tail: null argument");
+    RF_CHECK_ARG(h->vt.branch == BR_ML, "rf_ml_tail: the multi-level variant only");
+    RF_CHECK_ARG((size_t)H * W < (1u << 30), "rf_ml_tail: frame too large");
+    Plan p;
+    RF_TRY(check_call("rf_ml_tail", h, in, image, workspace, workspace_bytes, B, H, W, p));
+    hipStream_t st = (hipStream_t)stream;
+    float* gs = (float*)workspace + p.gscratch;
+    const int mosaic = packed_input ? 0 : 1;
+    RF_TRY(launch_ml_guidance(in, mosaic, gs, B, H, W, h->vt.levels, st));
+    return launch_ml_tail(image, in, mosaic, gs, B, H, W, h->vt.levels, st);
+}
+
 int rf_forward(rf_handle* h, const float* in, float* out, void* workspace, size_t workspace_bytes,
                int B, int H, int W, int packed_input, void* stream) {
     RF_CHECK_ARG(h && in && out && workspace, "rf_forward: null argument");

@@ -548,3 +548,57 @@ int launch_ml_tail(float* out, const float* in, int mosaic, float* scratch, int 
 }
 
 }  // namespace rf
+
+using namespace rf;
+
+// ---- the kernels one by one (include/rawformer_hip.h): argument checks, then the launch functions above ----------------------
+namespace {
+
+// what the modulation and the fused step index with int: B and the channel groups in the grid, h * w pixels
+int ml_check_step(const char* who, int B, int C, int h, int w, int step, int levels) {
+    RF_CHECK_ARG(B >= 1 && B <= 65535 && C >= 1 && h >= 1 && w >= 1, "%s: B=%d C=%d h=%d w=%d: every size must be positive and B <= 65535", who, B, C, h, w);
+    RF_CHECK_ARG(C <= 512, "%s: C=%d > 512 not supported", who, C);
+    RF_CHECK_ARG((size_t)h * w <= (1u << 28), "%s: a %dx%d plane exceeds 2^28 pixels", who, h, w);
+    RF_CHECK_ARG(levels >= 1 && levels <= 3, "%s: levels=%d (1..3)", who, levels);
+    RF_CHECK_ARG(step >= 0 && step <= levels, "%s: step=%d (0..levels-1: a pyramid level; levels = %d: the chroma form)", who, step, levels);
+    return RF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rf_ml_modulate(const float* x, const float* guide, const float* means, int step, int levels, const float* w_a, const float* w_b,
+                   const float* gate_w, const float* gate_b, float* out, int B, int C, int h, int w, void* stream) {
+    RF_TRY(ml_check_step("rf_ml_modulate", B, C, h, w, step, levels));
+    RF_CHECK_ARG(x && guide && means && w_a && (w_b || step == levels) && gate_w && gate_b && out, "rf_ml_modulate: null argument");
+    RF_CHECK_ARG(aligned4(x) && aligned4(guide) && aligned4(means) && aligned4(w_a) && aligned4(w_b) && aligned4(gate_w) &&
+                     aligned4(gate_b) && aligned4(out), "rf_ml_modulate: buffers must be 4-byte aligned");
+    return launch_ml_modulate(x, out, guide, means, step, levels, w_a, w_b, gate_w, gate_b, B, C, h, w, (hipStream_t)stream);
+}
+
+int rf_ml_step_fused(const float* x, const float* guide, const float* means, int step, int levels, const float* w_a, const float* w_b,
+                     const float* gate_w, const float* gate_b, const float* w0, const float* b0, const float* w2, const float* b2,
+                     float* out, float* partial, int B, int C, int h, int w, void* stream) {
+    RF_TRY(ml_check_step("rf_ml_step_fused", B, C, h, w, step, levels));
+    RF_CHECK_ARG(ml_step_fused_supported(C, h, w),
+                 "rf_ml_step_fused: C=%d at %dx%d: the fused step needs C = 16, 32, 48 or 64, w %% 4 == 0 and h * w %% 64 == 0", C, h, w);
+    RF_CHECK_ARG(x && guide && means && w_a && (w_b || step == levels) && gate_w && gate_b && w0 && b0 && w2 && b2 && out,
+                 "rf_ml_step_fused: null argument");
+    for (const void* p : {(const void*)x, (const void*)guide, (const void*)means, (const void*)w_a, (const void*)w_b, (const void*)gate_w,
+                          (const void*)gate_b, (const void*)w0, (const void*)b0, (const void*)w2, (const void*)b2, (const void*)out,
+                          (const void*)partial})
+        RF_CHECK_ARG(aligned4(p), "rf_ml_step_fused: buffers must be 4-byte aligned");
+    return launch_ml_step_fused(x, out, guide, means, step, levels, w_a, w_b, gate_w, gate_b, w0, b0, w2, b2, partial, B, C, h, w,
+                                (hipStream_t)stream);
+}
+
+int rf_ml_residual(const float* x, const float* r, float* out, int B, int C, int h, int w, void* stream) {
+    RF_CHECK_ARG(x && r && out, "rf_ml_residual: null argument");
+    RF_CHECK_ARG(B >= 1 && C >= 1 && h >= 1 && w >= 1, "rf_ml_residual: B=%d C=%d h=%d w=%d: every size must be positive", B, C, h, w);
+    RF_CHECK_ARG((double)B * C * h * w <= (double)((size_t)1 << 38), "rf_ml_residual: B=%d C=%d h=%d w=%d exceeds 2^38 elements", B, C, h, w);
+    RF_CHECK_ARG(aligned4(x) && aligned4(r) && aligned4(out), "rf_ml_residual: buffers must be 4-byte aligned");
+    return launch_ml_residual(x, r, out, B, C, h, w, (hipStream_t)stream);
+}
+
+}  // extern "C"

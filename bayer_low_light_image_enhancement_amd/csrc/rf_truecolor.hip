@@ -430,8 +430,6 @@ using namespace rf;
 // ---- the kernels one by one (include/rawformer_hip.h): argument checks, then the launch functions above ----------------------
 namespace {
 
-bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-
 // what the spatial and residual kernels index with int: B in the grid, h * w pixels
 int tc_check_shape(const char* who, int B, int C, int h, int w) {
     RF_CHECK_ARG(B >= 1 && B <= 65535 && C >= 1 && h >= 1 && w >= 1, "%s: B=%d C=%d h=%d w=%d: every size must be positive and B <= 65535", who, B, C, h, w);

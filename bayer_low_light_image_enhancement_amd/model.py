@@ -514,6 +514,61 @@ class RawFormer(nn.Module):
                                           C.c_void_p(st.workspace.data_ptr()), st.workspace.numel(), b, H, W, stream), "rf_tc_guidance")
         return y, crcb, rgb, guide
 
+    def _ml_call(self, who: str, frame: torch.Tensor, H: int, W: int):
+        """``variant='multilvl'`` diagnostics: the device state with parameters in place and a workspace for ``(B, H, W)``."""
+        if frame.device.type != "cuda":
+            raise RuntimeError("RawFormer (HIP) needs a ROCm device tensor: there is no CPU path in this package")
+        if self.variant != "multilvl":
+            raise RuntimeError(f"{who}: variant 'multilvl' only, not {self.variant!r}")
+        st = self._state_for(frame.device)
+        self._sync_params(st, frame.device)
+        sz = C.c_size_t()
+        _lib.check(_lib.load().rf_workspace_bytes(st.handle, frame.shape[0], H, W, C.byref(sz)), "rf_workspace_bytes")
+        if st.workspace is None or st.workspace.numel() < sz.value:
+            st.workspace = None
+            st.workspace = torch.empty(sz.value, dtype=torch.uint8, device=frame.device)
+        return st
+
+    def ml_guidance(self, packed: torch.Tensor, level: int):
+        """``variant='multilvl'``: the guidance an ``FLCA_Pyramid`` block sees at U-Net level ``level`` (0..3) of a packed frame
+        ``[B,4,H,W]``, exactly as ``forward`` computes it.  Returns ``(guide [B,2L+2,H>>level,W>>level], means [B,8])``: the planes
+        ``[y_low_0, y_high_0, .., y_low_{L-1}, y_high_{L-1}, cr, cb]`` (MultiLvlFrequencyawareLumaChromaAttentionRAWFormer.py:143-145,
+        :168-169; L = ``flca_levels``) and the table the kernels read their pooled gates from: ``means[:, 2l]``, ``means[:, 2l+1]`` the
+        means of ``y_low_l``, ``y_high_l`` at this size (:151-152), ``means[:, 6]`` that of ``sqrt(cr^2 + cb^2 + eps)`` (:171-172)."""
+        packed = packed.detach().float().contiguous()
+        if packed.dim() != 4 or packed.shape[1] != 4:
+            raise RuntimeError(f"expected a packed frame [B,4,H,W], got {tuple(packed.shape)}")
+        b, _, H, W = packed.shape
+        with torch.cuda.device(packed.device):
+            st = self._ml_call("ml_guidance", packed, H, W)
+            guide = torch.empty((b, 2 * self.flca_levels + 2, H >> max(level, 0), W >> max(level, 0)), dtype=torch.float32, device=packed.device)
+            means = torch.zeros((b, 8), dtype=torch.float32, device=packed.device)
+            stream = C.c_void_p(torch.cuda.current_stream(packed.device).cuda_stream)
+            _lib.check(_lib.load().rf_ml_guidance(st.handle, C.c_void_p(packed.data_ptr()), int(level), C.c_void_p(guide.data_ptr()),
+                                                  C.c_void_p(means.data_ptr()), C.c_void_p(st.workspace.data_ptr()), st.workspace.numel(),
+                                                  b, H, W, stream), "rf_ml_guidance")
+        return guide, means
+
+    def ml_tail(self, image: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+        """``variant='multilvl'``: the colour anchor and the luminance nudge of ``RawFormer.forward``
+        (MultiLvlFrequencyawareLumaChromaAttentionRAWFormer.py:403-414) applied to ``image`` [B,3,2H,2W] for the model input ``x``, a
+        mosaic ``[B,1,2H,2W]`` or a packed frame ``[B,4,H,W]``, as ``forward`` applies them to its own output.  A new tensor."""
+        x = x.detach().float().contiguous()
+        if x.dim() != 4 or x.shape[1] not in (1, 4):
+            raise RuntimeError(f"expected a mosaic [B,1,2H,2W] or a packed frame [B,4,H,W], got {tuple(x.shape)}")
+        packed_input = x.shape[1] == 4
+        b = x.shape[0]
+        H, W = (x.shape[2], x.shape[3]) if packed_input else (x.shape[2] // 2, x.shape[3] // 2)
+        if tuple(image.shape) != (b, 3, 2 * H, 2 * W) or image.device != x.device:
+            raise RuntimeError(f"image must be {(b, 3, 2 * H, 2 * W)} on {x.device}, got {tuple(image.shape)} on {image.device}")
+        out = image.detach().float().clone(memory_format=torch.contiguous_format)
+        with torch.cuda.device(x.device):
+            st = self._ml_call("ml_tail", x, H, W)
+            stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+            _lib.check(_lib.load().rf_ml_tail(st.handle, C.c_void_p(out.data_ptr()), C.c_void_p(x.data_ptr()), int(packed_input),
+                                              C.c_void_p(st.workspace.data_ptr()), st.workspace.numel(), b, H, W, stream), "rf_ml_tail")
+        return out
+
     def workspace_bytes(self, batch: int, H: int, W: int) -> int:
         probe, sz = C.c_void_p(), C.c_size_t()
         cfg = self._config()

@@ -898,3 +898,100 @@ def tc_pyramid(src: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     with torch.cuda.device(src.device):
         _lib.check(_lib.load().rf_tc_pyramid(_ptr(src), _ptr(ll), _ptr(mag), b, h, w, _stream(src)), "rf_tc_pyramid")
     return ll, mag
+
+
+# ------------------------------------------------------------------------------------------ the multi-level variant's kernels one by one
+def _ml_step_params(params, prefix: str, step: int, levels: int, c: int, who: str):
+    """The weights of one residual step of ``FLCA_Pyramid`` from the block's ``state_dict``: ``(w_a, w_b, gate_w, gate_b)``."""
+    if step == levels:
+        spec = (("chroma_attn.0.weight", (c, 2, 3, 3)), None, ("chroma_gate.weight", (1, 1, 1, 1)), ("chroma_gate.bias", (1,)))
+    else:
+        spec = ((f"low_attn.{step}.0.weight", (c, 1, 3, 3)), (f"high_attn.{step}.0.weight", (c, 1, 3, 3)),
+                (f"freq_gate_head.{step}.weight", (2, 2, 1, 1)), (f"freq_gate_head.{step}.bias", (2,)))
+    out = []
+    for item in spec:
+        if item is None:
+            out.append(None)
+            continue
+        key, shape = item
+        t = _chk(params[prefix + key], key)
+        if tuple(t.shape) != shape:
+            raise RuntimeError(f"{who}: {key} must be {shape}, got {tuple(t.shape)}")
+        out.append(t)
+    return out
+
+
+def _ml_step_inputs(x, guide, means, step, levels, who):
+    x, guide, means = _chk(x, "x"), _chk(guide, "guide"), _chk(means, "means")
+    if x.dim() != 4:
+        raise RuntimeError(f"{who}: expected x [B,C,h,w], got {tuple(x.shape)}")
+    b, c, h, w = x.shape
+    step, levels = int(step), int(levels)
+    if not 1 <= levels <= 3 or not 0 <= step <= levels:
+        raise RuntimeError(f"{who}: levels={levels} must be 1..3 and step={step} 0..levels")
+    if tuple(guide.shape) != (b, 2 * levels + 2, h, w):
+        raise RuntimeError(f"{who}: guide must be {(b, 2 * levels + 2, h, w)}, got {tuple(guide.shape)}")
+    if tuple(means.shape) != (b, 8):
+        raise RuntimeError(f"{who}: means must be {(b, 8)}, got {tuple(means.shape)}")
+    return x, guide, means, step, levels
+
+
+def _ml_out(out, x, who):
+    out = torch.empty_like(x) if out is None else out
+    if tuple(out.shape) != tuple(x.shape) or not out.is_contiguous() or out.dtype != torch.float32 or out.device != x.device:
+        raise RuntimeError(f"{who}: out must be a contiguous float32 tensor of x's shape on its device")
+    return out
+
+
+def ml_modulate(x: torch.Tensor, guide: torch.Tensor, means: torch.Tensor, step: int, levels: int, params, prefix: str = "",
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The gated spatial attention of one step of ``FLCA_Pyramid.forward`` (MultiLvlFrequencyawareLumaChromaAttentionRAWFormer.py
+    :147-162, :170-173) applied to ``x`` [B,C,h,w].  ``guide`` [B,2 levels+2,h,w] and ``means`` [B,8] as ``RawFormer.ml_guidance``
+    returns them; ``step`` < ``levels`` is that pyramid level, ``step == levels`` the chroma form.  ``params``: the block's
+    ``state_dict``.  ``out``: where to write (default: a new tensor)."""
+    x, guide, means, step, levels = _ml_step_inputs(x, guide, means, step, levels, "ml_modulate")
+    b, c, h, w = x.shape
+    prm = _ml_step_params(params, prefix, step, levels, c, "ml_modulate")
+    out = _ml_out(out, x, "ml_modulate")
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().rf_ml_modulate(_ptr(x), _ptr(guide), _ptr(means), step, levels, *[_ptr(t) for t in prm], _ptr(out), b, c, h, w,
+                                              _stream(x)), "rf_ml_modulate")
+    return out
+
+
+def ml_step_fused(x: torch.Tensor, guide: torch.Tensor, means: torch.Tensor, step: int, levels: int, params, prefix: str = "",
+                  out: Optional[torch.Tensor] = None, sums: bool = False):
+    """One whole residual step of ``FLCA_Pyramid.forward`` in one kernel: ``x + 0.2 tanh(res_proj(ml_modulate(x, ...)))`` for
+    C = 16, 32, 48 or 64, ``w % 4 == 0`` and ``h * w % 64 == 0`` (anything else raises).  Arguments as ``ml_modulate``; ``params``
+    also holds ``res_proj.0.*`` and ``res_proj.2.*``.  ``out`` may be ``x``.  With ``sums`` returns ``(out, partial)``, ``partial``
+    [B, tc_nblk(h, w), C] the sums of ``out`` over each block of 1024 consecutive pixels (``tc_residual``'s layout)."""
+    x, guide, means, step, levels = _ml_step_inputs(x, guide, means, step, levels, "ml_step_fused")
+    b, c, h, w = x.shape
+    prm = _ml_step_params(params, prefix, step, levels, c, "ml_step_fused")
+    for key, shape in (("res_proj.0.weight", (c, c, 1, 1)), ("res_proj.0.bias", (c,)), ("res_proj.2.weight", (c, c, 1, 1)), ("res_proj.2.bias", (c,))):
+        t = _chk(params[prefix + key], key)
+        if tuple(t.shape) != shape:
+            raise RuntimeError(f"ml_step_fused: {key} must be {shape}, got {tuple(t.shape)}")
+        prm.append(t)
+    out = _ml_out(out, x, "ml_step_fused")
+    # the library refuses an unsupported shape before it reads `partial`: one block of 1024 pixels is the most any shape needs there
+    partial = torch.empty((b, -(-h * w // 1024), c), dtype=torch.float32, device=x.device) if sums else None
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().rf_ml_step_fused(_ptr(x), _ptr(guide), _ptr(means), step, levels, *[_ptr(t) for t in prm], _ptr(out),
+                                                _ptr(partial), b, c, h, w, _stream(x)), "rf_ml_step_fused")
+    return (out, partial) if sums else out
+
+
+def ml_residual(x: torch.Tensor, r: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``x + 0.2 tanh(r)`` (FLCA_Pyramid.forward, :162-165; ``r = res_proj(x * attention)``), tensors of any one shape.  ``out`` may
+    be ``x`` itself (the forward writes in place)."""
+    x, r = _chk(x, "x"), _chk(r, "r")
+    if tuple(r.shape) != tuple(x.shape):
+        raise RuntimeError(f"ml_residual: x {tuple(x.shape)} and r {tuple(r.shape)} differ")
+    if x.numel() == 0:
+        raise RuntimeError("ml_residual: empty tensor")
+    out = _ml_out(out, x, "ml_residual")
+    b, c, h, w = x.shape if x.dim() == 4 else (1, 1, 1, x.numel())
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().rf_ml_residual(_ptr(x), _ptr(r), _ptr(out), b, c, h, w, _stream(x)), "rf_ml_residual")
+    return out

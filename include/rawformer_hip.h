@@ -132,6 +132,18 @@ int rf_forward_stage(rf_handle* h, int stage, const float* in, const float* pack
  * refined rgb) and guide [B,7,H>>level,W>>level] = (y, cr, cb, R, G, y_low, y_high).  Workspace as for rf_forward(B, H, W). */
 int rf_tc_guidance(rf_handle* h, const float* packed, int level, float* y, float* crcb, float* rgb, float* guide, void* workspace,
                    size_t workspace_bytes, int B, int H, int W, void* stream);
+/* RF_VARIANT_MULTILVL, diagnostic.  rf_ml_guidance: y / cr / cb and the Haar pyramid of a packed frame [B,4,H,W], then the
+ * guidance an FLCA_Pyramid block sees at U-Net level `level` (0..3), exactly as rf_forward runs them.  Copies out guide
+ * [B,2L+2,H>>level,W>>level] = (y_low_0, y_high_0, .., y_low_{L-1}, y_high_{L-1}, cr, cb) (L = flca_levels) and that level's means
+ * table [B,8] as the kernels lay it out: entries 2l and 2l+1 are the means of y_low_l and y_high_l at this size, entry 6 the mean of
+ * sqrt(cr^2 + cb^2 + 1e-8); the other entries are not used.
+ * rf_ml_tail: the colour anchor and the luminance nudge (MultiLvlFrequencyawareLumaChromaAttentionRAWFormer.py:403-414) in place on
+ * image [B,3,2H,2W], from the model input `in` (the mosaic [B,1,2H,2W], or with packed_input the packed frame [B,4,H,W]): the front
+ * end on `in`, then the tail as rf_forward runs it.  Both: workspace as for rf_forward(B, H, W), buffers 16-byte aligned. */
+int rf_ml_guidance(rf_handle* h, const float* packed, int level, float* guide, float* means, void* workspace, size_t workspace_bytes,
+                   int B, int H, int W, void* stream);
+int rf_ml_tail(rf_handle* h, float* image, const float* in, int packed_input, void* workspace, size_t workspace_bytes, int B, int H, int W,
+               void* stream);
 
 /* ---- training step (reference train.py:127-147: forward, loss, backward; optimiser train.py:113) ----
  * Parameters, gradients and the Adam moments live in FLAT float buffers: parameter i of the registry sits at float offset
@@ -434,6 +446,28 @@ int rf_tc_residual(const float* xs, const float* r, float* x2, float* partial, i
 int rf_tc_color_head(float* x, const float* gamma, const float* ct0_w, const float* ct0_b, const float* ct2_w, const float* ct2_b,
                      const float* tone0_w, const float* tone0_b, const float* tone2_w, const float* tone2_b, int B, size_t P, void* stream);
 int rf_tc_pyramid(const float* src, float* ll, float* mag, int B, int hs, int ws, void* stream);
+
+/* ---- the element-wise kernels of RF_VARIANT_MULTILVL one by one (csrc/rf_multilvl.hip; FLCA_Pyramid.forward,
+ * MultiLvlFrequencyawareLumaChromaAttentionRAWFormer.py:132-183) ----------
+ * No handle: the caller passes the raw parameter tensors.  Every argument is checked before any launch (RF_E_INVALID): nulls, 4-byte
+ * alignment, B <= 65535, C <= 512, levels in 1..3, step in 0..levels.  guide [B,2 levels+2,h,w] and means [B,8] as rf_ml_guidance
+ * leaves them.  step < levels is pyramid level `step`: w_a = low_attn[step] [C,1,3,3], w_b = high_attn[step] [C,1,3,3], gate_w / gate_b
+ * = freq_gate_head[step] [2,2], [2]; step == levels is the chroma form: w_a = chroma_attn [C,2,3,3], w_b unused (may be NULL),
+ * gate_w / gate_b = chroma_gate [1], [1].
+ * rf_ml_modulate: out = x * (g0 sigmoid(conv3x3(y_low; w_a)) + g1 tanh(conv3x3(y_high; w_b))), (g0, g1) = sigmoid(gate_w (mean y_low,
+ * mean y_high) + gate_b) (:147-162), or out = x * sigmoid(gate_w mean|c| + gate_b) sigmoid(conv3x3([cr, cb]; w_a)) (:170-173).
+ * x, out [B,C,h,w]; 16 bytes per lane where w % 4 == 0 and x, out are 16-byte aligned.
+ * rf_ml_step_fused: out = x + 0.2 tanh(W2 relu(W0 m + b0) + b2) with m = rf_ml_modulate's result, in one kernel; w0, w2 [C,C], b0, b2
+ * [C] (res_proj.0 / .2).  C = 16, 32, 48 or 64, w % 4 == 0, h * w % 64 == 0.  partial: NULL, or [B,rf_tc_nblk(h, w),C], the sums of
+ * out over each block of 1024 consecutive pixels (rf_tc_residual's layout).  out may be x.
+ * rf_ml_residual: out = x + 0.2 tanh(r) over B C h w elements; 16 bytes per lane where that count is a multiple of 4 and all three
+ * are 16-byte aligned.  out may be x. */
+int rf_ml_modulate(const float* x, const float* guide, const float* means, int step, int levels, const float* w_a, const float* w_b,
+                   const float* gate_w, const float* gate_b, float* out, int B, int C, int h, int w, void* stream);
+int rf_ml_step_fused(const float* x, const float* guide, const float* means, int step, int levels, const float* w_a, const float* w_b,
+                     const float* gate_w, const float* gate_b, const float* w0, const float* b0, const float* w2, const float* b2,
+                     float* out, float* partial, int B, int C, int h, int w, void* stream);
+int rf_ml_residual(const float* x, const float* r, float* out, int B, int C, int h, int w, void* stream);
 
 #ifdef __cplusplus
 }

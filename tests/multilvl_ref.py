@@ -31,23 +31,30 @@ def res_step(x: Tensor, spatial: Tensor, p: Dict[str, Tensor], pre: str) -> Tens
     return x + 0.2 * torch.tanh(F.conv2d(t, p[pre + "res_proj.2.weight"], p[pre + "res_proj.2.bias"]))
 
 
+def step_gate(a: Tensor, b: Tensor, p: Dict[str, Tensor], pre: str, step: int, levels: int, eps: float = 1e-8) -> Tensor:
+    """The gated spatial attention of residual step ``step`` of FLCA_Pyramid from its two planes at the feature size:
+    ``step < levels``: (y_low, y_high) of pyramid level ``step`` -> ``g0 sigmoid(conv3(y_low)) + g1 tanh(conv3(y_high))`` with
+    ``(g0, g1) = sigmoid(freq_gate_head(mean y_low, mean y_high))``; ``step == levels``: (cr, cb) ->
+    ``sigmoid(chroma_gate(mean sqrt(cr^2 + cb^2 + eps))) sigmoid(conv3([cr, cb]))``.  The means are those of the planes given."""
+    if step == levels:
+        a_chr = torch.sigmoid(F.conv2d(torch.cat([a, b], dim=1), p[pre + "chroma_attn.0.weight"], padding=1))
+        mag = torch.sqrt(a * a + b * b + eps).mean(dim=(2, 3), keepdim=True)
+        return torch.sigmoid(F.conv2d(mag, p[pre + "chroma_gate.weight"], p[pre + "chroma_gate.bias"])) * a_chr
+    a_low = torch.sigmoid(F.conv2d(a, p[f"{pre}low_attn.{step}.0.weight"], padding=1))
+    a_high = torch.tanh(F.conv2d(b, p[f"{pre}high_attn.{step}.0.weight"], padding=1))
+    pooled = torch.cat([a.mean(dim=(2, 3), keepdim=True), b.mean(dim=(2, 3), keepdim=True)], dim=1)      # means at THIS size
+    gates = torch.sigmoid(F.conv2d(pooled, p[f"{pre}freq_gate_head.{step}.weight"], p[f"{pre}freq_gate_head.{step}.bias"]))
+    return gates[:, 0:1] * a_low + gates[:, 1:2] * a_high
+
+
 def flca_pyramid(feat: Tensor, guide, p: Dict[str, Tensor], pre: str, levels: int, eps: float = 1e-8) -> Tensor:
     y, cr, cb = guide
     size = feat.shape[-2:]
     lows, highs = pyramid(y, levels, eps)
     x = feat
     for l in range(levels):
-        lo, hi = R.bilinear_resize(lows[l], size), R.bilinear_resize(highs[l], size)
-        a_low = torch.sigmoid(F.conv2d(lo, p[f"{pre}low_attn.{l}.0.weight"], padding=1))
-        a_high = torch.tanh(F.conv2d(hi, p[f"{pre}high_attn.{l}.0.weight"], padding=1))
-        pooled = torch.cat([lo.mean(dim=(2, 3), keepdim=True), hi.mean(dim=(2, 3), keepdim=True)], dim=1)      # means at THIS size
-        gates = torch.sigmoid(F.conv2d(pooled, p[f"{pre}freq_gate_head.{l}.weight"], p[f"{pre}freq_gate_head.{l}.bias"]))
-        x = res_step(x, gates[:, 0:1] * a_low + gates[:, 1:2] * a_high, p, pre)
-    cr_r, cb_r = R.bilinear_resize(cr, size), R.bilinear_resize(cb, size)
-    a_chr = torch.sigmoid(F.conv2d(torch.cat([cr_r, cb_r], dim=1), p[pre + "chroma_attn.0.weight"], padding=1))
-    mag = torch.sqrt(cr_r * cr_r + cb_r * cb_r + eps).mean(dim=(2, 3), keepdim=True)
-    gamma = torch.sigmoid(F.conv2d(mag, p[pre + "chroma_gate.weight"], p[pre + "chroma_gate.bias"]))
-    x = res_step(x, gamma * a_chr, p, pre)
+        x = res_step(x, step_gate(R.bilinear_resize(lows[l], size), R.bilinear_resize(highs[l], size), p, pre, l, levels, eps), p, pre)
+    x = res_step(x, step_gate(R.bilinear_resize(cr, size), R.bilinear_resize(cb, size), p, pre, levels, levels, eps), p, pre)
     pooled = x.mean(dim=(2, 3), keepdim=True)
     hid = torch.relu(F.conv2d(pooled, p[pre + "se.1.weight"], p[pre + "se.1.bias"]))
     return x * torch.sigmoid(F.conv2d(hid, p[pre + "se.3.weight"], p[pre + "se.3.bias"]))
@@ -61,14 +68,15 @@ def stage(x: Tensor, guide, p: Dict[str, Tensor], pre: str, heads: int, levels: 
     return F.leaky_relu(F.conv2d(t, p[pre + "Conv_out.weight"], p[pre + "Conv_out.bias"], padding=1), 0.2)
 
 
-def corrections(out: Tensor, x4: Tensor, y: Tensor) -> Tensor:
-    """Colour anchor ``out += 0.12 (in_mean - out_mean)`` then the nudge ``out += 0.03 (up(LL2) - luma(out))``."""
+def corrections(out: Tensor, x4: Tensor, y: Tensor, resize=R.bilinear_resize, anchor_level: int = 2) -> Tensor:
+    """Colour anchor ``out += 0.12 (in_mean - out_mean)`` then the nudge ``out += 0.03 (up(LL2) - luma(out))``.  ``resize`` and
+    ``anchor_level`` are the model's (bilinear, align_corners=False; LL2); tests that inject a defect pass others."""
     rgb = torch.cat([x4[:, 0:1], 0.5 * (x4[:, 1:2] + x4[:, 2:3]), x4[:, 3:4]], dim=1)
-    in_mean = R.bilinear_resize(rgb, out.shape[-2:]).mean(dim=(2, 3), keepdim=True)
+    in_mean = resize(rgb, out.shape[-2:]).mean(dim=(2, 3), keepdim=True)
     out = out + 0.12 * (in_mean - out.mean(dim=(2, 3), keepdim=True))
-    ll2 = pyramid(y, 2)[0][1]
+    ll2 = pyramid(y, anchor_level)[0][anchor_level - 1]
     out_y = 0.299 * out[:, 0:1] + 0.587 * out[:, 1:2] + 0.114 * out[:, 2:3]
-    return out + 0.03 * (R.bilinear_resize(ll2, out.shape[-2:]) - out_y)
+    return out + 0.03 * (resize(ll2, out.shape[-2:]) - out_y)
 
 
 def forward(p: Dict[str, Tensor], x: Tensor, dim: int, heads=(8, 8, 8, 8), levels: int = 2, packed: bool = False) -> Tensor:
