@@ -126,6 +126,14 @@ SIGNATURES = {
     "rf_wm_forward": (_i, [_vp, _vp, C.POINTER(_vp), _vp, _sz, _i, _i, _i, _i, _vp]),
     "rf_wm_backward_workspace_bytes": (C.c_longlong, [_i, _i, _i, _i]),
     "rf_wm_backward": (_i, [_vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _sz, _i, _i, _i, _i, _i, _vp]),
+    "rf_rfft2_polar_backward_scratch_bytes": (C.c_longlong, [_i, _i, _i]),
+    "rf_rfft2_polar_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "rf_polar_irfft2_backward_scratch_bytes": (C.c_longlong, [_i, _i, _i]),
+    "rf_polar_irfft2_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "rf_feb_backward_workspace_bytes": (C.c_longlong, [_i, _i, _i, _i]),
+    "rf_feb_backward": (_i, [_vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _sz, _i, _i, _i, _i, _i, _vp]),
+    "rf_ffab_backward_workspace_bytes": (C.c_longlong, [_i, _i, _i, _i]),
+    "rf_ffab_backward": (_i, [_vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _sz, _i, _i, _i, _i, _i, _vp]),
     "rf_wmb_front": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "rf_wmb_back": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "rf_wmb_ffn_sum": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

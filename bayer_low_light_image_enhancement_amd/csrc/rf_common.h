@@ -445,6 +445,12 @@ int launch_rfft2_polar(const float* in, float* mag, float* pha, float2* cscratch
 int launch_polar_irfft2(const float* mag, const float* pha, const float* res, float* out, float2* cscratch, int planes, int h, int w,
                         float lim, hipStream_t st);
 int launch_clamp(const float* in, float* out, size_t n, float lo, float hi, hipStream_t st);
+int launch_rfft_rows(const float* in, float2* cscratch, int planes, int h, int w, hipStream_t st);   // the row pass of launch_rfft2_polar alone
+// their adjoints (rf_ffab_bwd.hip): (mag, pha, dL/dout) -> (dL/dmag, dL/dpha);  (in, dL/dmag, dL/dpha) -> dL/din, the spectrum recomputed
+int launch_polar_irfft2_backward(const float* mag, const float* pha, const float* gout, float* gmag, float* gpha, float2* cscratch, int planes,
+                                 int h, int w, hipStream_t st);
+int launch_rfft2_polar_backward(const float* in, const float* gmag, const float* gpha, float* gin, float2* cscratch, int planes, int h, int w,
+                                hipStream_t st);
 
 // ---- TrueColorRawFormer extras (rf_truecolor.hip)
 size_t tc_front_scratch_floats(int B, int H, int W, int levels);
@@ -574,6 +580,11 @@ int launch_tail_fold(const float* w_cr, const float* ch /* [B][C] gate or nullpt
 // prepacked: every 1x1 / 3x3 / projection weight pointer of `prm` already is the packed form (rf_pack_params), nothing is packed
 // per call.  WM's three projections need both forms, so those travel in WmPacked (prm keeps the raw pointers, unused then).
 size_t ffab_scratch_floats(int B, int nc, int h, int w);
+int ffab_check_geometry(const char* what, int B, int nc, int h, int w);
+// one nn.Conv2d(cin, cout, 1) on [B, cin, P] planes, the raw weight packed into `wpack` first (nullptr: `w` is the packed form)
+int conv1x1_raw(const float* x, float* out, const float* w, const float* bias, const float* res, float* wpack, int B, int cin, int cout,
+                int P, int act, hipStream_t st);
+int launch_cat2(const float* a, const float* b, float* out, int B, size_t per_image, hipStream_t st);   // torch.cat((a, b), dim=1), per_image floats each
 int ffab_forward(const float* in, float* out, const float* const* prm, bool prepacked, float* scratch, int B, int nc, int h, int w,
                  hipStream_t st);
 struct WmPacked { const float *convb0, *convb2, *smooth, *in_proj, *x_proj, *out_proj; const void *in_proj3, *x_proj3, *out_proj3; };

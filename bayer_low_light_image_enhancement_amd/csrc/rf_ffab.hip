@@ -12,8 +12,6 @@
 
 namespace rf {
 
-namespace {
-
 // one nn.Conv2d(cin, cout, 1) on [B, cin, P] planes with raw weights (packed on the fly into `wpack`); wpack == nullptr: `w`
 // already is the packed form (the WFB handle packs every weight once, rf_pack_params)
 int conv1x1_raw(const float* x, float* out, const float* w, const float* bias, const float* res, float* wpack, int B, int cin, int cout,
@@ -25,6 +23,8 @@ int conv1x1_raw(const float* x, float* out, const float* w, const float* bias, c
     a.out = out; a.out_bstride = (int64_t)cout * P; a.Cout = cout; a.B = B; a.P = P; a.w = P; a.act = act;
     return launch_conv1x1(a, st);
 }
+
+namespace {
 
 struct FebBufs { float *xc, *y, *mag, *pha, *t, *mag2, *pha2, *wpack; float2* cplx; };
 
@@ -63,11 +63,15 @@ int process_block_forward(const float* x, float* out, const BlockPrm& p, const F
     return conv1x1_raw(feb_out, out, p.cat_w, p.cat_b, x, f.wpack, B, nc, nc, h * w, 0, st);
 }
 
-int check_geometry(const char* what, int B, int nc, int h, int w) {
+}  // namespace
+
+int ffab_check_geometry(const char* what, int B, int nc, int h, int w) {
     RF_CHECK_ARG(B > 0 && nc > 0 && nc % 4 == 0 && h >= 2 && w >= 2 && w % 2 == 0, "%s: needs channels %% 4 == 0 and an even width (B=%d nc=%d %dx%d)",
                  what, B, nc, h, w);
     return RF_OK;
 }
+
+namespace {
 
 struct FfabPlan { float *x, *x1, *x2, *x3, *x4, *x5, *cat, *pb, *feb_out, *wpack2; FebBufs f; size_t total; };
 
@@ -90,12 +94,16 @@ __global__ void __launch_bounds__(256) cat2_kernel(const float* __restrict__ a, 
     }
 }
 
+}  // namespace
+
 int launch_cat2(const float* a, const float* b, float* out, int B, size_t per_image, hipStream_t st) {
     const size_t total = 2 * per_image * B;
     int gx = (int)((total + 255) / 256); if (gx > 4096) gx = 4096;
     cat2_kernel<<<gx, 256, 0, st>>>(a, b, out, per_image, total);
     return check_launch("cat2");
 }
+
+namespace {
 
 // out = add + clamp(in * scale + shift, lo, hi): the tail of the wavelet branch of WMB (inverse_data_transform + residual,
 // RawFomer_WFB_FFAB/model.py:13-15, 241-243)
@@ -130,7 +138,7 @@ int rf_polar_irfft2(const float* mag, const float* pha, float* out, void* scratc
 
 int rf_feb_scratch_bytes(int B, int nc, int h, int w, size_t* bytes) {
     RF_CHECK_ARG(bytes, "feb_scratch_bytes: null argument");
-    RF_TRY(check_geometry("feb", B, nc, h, w));
+    RF_TRY(ffab_check_geometry("feb", B, nc, h, w));
     Bump b{nullptr};
     FebBufs f;
     *bytes = feb_plan(b, f, B, nc, h, w) * sizeof(float);
@@ -139,7 +147,7 @@ int rf_feb_scratch_bytes(int B, int nc, int h, int w, size_t* bytes) {
 
 int rf_feb(const float* in, float* out, const float* const* prm, void* scratch, int B, int nc, int h, int w, void* stream) {
     RF_CHECK_ARG(in && out && prm && scratch && aligned16(scratch) && in != out, "feb: bad arguments");
-    RF_TRY(check_geometry("feb", B, nc, h, w));
+    RF_TRY(ffab_check_geometry("feb", B, nc, h, w));
     for (int i = 0; i < 10; ++i) RF_CHECK_ARG(prm[i] != nullptr, "feb: parameter %d is null", i);
     Bump b{(float*)scratch};
     FebBufs f;
@@ -156,7 +164,7 @@ int rf_affine_clamp_add(const float* in, const float* add, float* out, size_t n,
 
 int rf_ffab_scratch_bytes(int B, int nc, int h, int w, size_t* bytes) {
     RF_CHECK_ARG(bytes, "ffab_scratch_bytes: null argument");
-    RF_TRY(check_geometry("ffab", B, nc, h, w));
+    RF_TRY(ffab_check_geometry("ffab", B, nc, h, w));
     FfabPlan p;
     ffab_plan(nullptr, p, B, nc, h, w);
     *bytes = p.total * sizeof(float);
@@ -165,7 +173,7 @@ int rf_ffab_scratch_bytes(int B, int nc, int h, int w, size_t* bytes) {
 
 int rf_ffab(const float* in, float* out, const float* const* prm, void* scratch, int B, int nc, int h, int w, void* stream) {
     RF_CHECK_ARG(in && out && prm && scratch && aligned16(scratch), "ffab: bad arguments");
-    RF_TRY(check_geometry("ffab", B, nc, h, w));
+    RF_TRY(ffab_check_geometry("ffab", B, nc, h, w));
     for (int i = 0; i < 92; ++i) RF_CHECK_ARG(prm[i] != nullptr, "ffab: parameter %d is null", i);
     return ffab_forward(in, out, prm, false, (float*)scratch, B, nc, h, w, (hipStream_t)stream);
 }
@@ -182,7 +190,7 @@ size_t ffab_scratch_floats(int B, int nc, int h, int w) {
 
 int ffab_forward(const float* in, float* out, const float* const* prm, bool prepacked, float* scratch, int B, int nc, int h, int w,
                  hipStream_t st) {
-    RF_TRY(check_geometry("ffab", B, nc, h, w));
+    RF_TRY(ffab_check_geometry("ffab", B, nc, h, w));
     FfabPlan p;
     ffab_plan(scratch, p, B, nc, h, w);
     if (prepacked) p.wpack2 = p.f.wpack = nullptr;

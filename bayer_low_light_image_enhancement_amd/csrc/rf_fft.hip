@@ -11,6 +11,7 @@
 //            [row pass]    Hermitian half spectrum -> real row (Im of the DC / Nyquist bins ignored, as pocketfft's c2r
 //                          does); epilogue: + clamp(x, -10, 10), clamp(-10, 10)
 //
+// (lds_fft_lines lives in rf_fft_lines.h, shared with the adjoints of rf_ffab_bwd.hip.)
 // A line of length n lives in LDS as n complex values.  n = 2^k: radix-2 decimation in time (bit-reversed load, k
 // in-place stages, one barrier each).  Any other n (e.g. 712 x 1072 = the LL band of a packed 1424 x 2144 frame, a SID frame
 // padded to the multiple of 32 variant='wfb' asks of the width): direct O(n^2) DFT out of the same LDS line with an exact
@@ -24,73 +25,11 @@
 // periodic downstream).  Elsewhere a phase within rounding of the +-pi cut is ill-conditioned in the reference too;
 // tests state their tolerance accordingly.
 #include <climits>
-#include "rf_common.h"
+#include "rf_fft_lines.h"
 
 namespace rf {
 
 namespace {
-
-constexpr int kMaxLine = 4096;          // longest line held in LDS (32 KB as float2)
-
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-
-__device__ __forceinline__ float2 twiddle(int k, int n, bool inverse) {   // exp(-+ 2 pi i k / n)
-    float s, c;
-    sincospif(2.0f * (float)k / (float)n, &s, &c);
-    return make_float2(c, inverse ? s : -s);
-}
-
-// In-place transform of L independent lines of length n held in `buf` (line l at buf + l * n); `tmp` (same size) is
-// only used by the generic path.  All 256 threads take part; ends with a barrier.  Unscaled.
-__device__ void lds_fft_lines(float2* __restrict__ buf, float2* __restrict__ tmp, int n, int log2n, int L, bool inverse) {
-    const int tid = threadIdx.x;
-    if (log2n >= 0) {
-        // bit reversal (in place: swap pairs once)
-        for (int i = tid; i < L * n; i += 256) {
-            const int l = i / n, k = i - l * n;
-            const int r = (int)(__brev((unsigned)k) >> (32 - log2n));
-            if (log2n > 0 && r > k) {
-                float2* b = buf + l * n;
-                const float2 t = b[k];
-                b[k] = b[r];
-                b[r] = t;
-            }
-        }
-        __syncthreads();
-        for (int s = 0; s < log2n; ++s) {
-            const int half = 1 << s;
-            for (int i = tid; i < L * (n >> 1); i += 256) {
-                const int l = i / (n >> 1), q = i - l * (n >> 1);
-                const int j = q & (half - 1), base = ((q >> s) << (s + 1)) + j;
-                float2* b = buf + l * n;
-                const float2 w = twiddle(j << (log2n - 1 - s), n, inverse);   // exp(-+2 pi i j / (2 half))
-                const float2 u = b[base], v = cmul(b[base + half], w);
-                b[base] = make_float2(u.x + v.x, u.y + v.y);
-                b[base + half] = make_float2(u.x - v.x, u.y - v.y);
-            }
-            __syncthreads();
-        }
-    } else {
-        for (int i = tid; i < L * n; i += 256) {
-            const int l = i / n, k = i - l * n;
-            const float2* b = buf + l * n;
-            float2 acc = make_float2(0.f, 0.f);
-            int jk = 0;                                   // j * k mod n, exact
-            for (int j = 0; j < n; ++j) {
-                const float2 w = twiddle(jk, n, inverse);
-                const float2 v = b[j];
-                acc.x = fmaf(v.x, w.x, fmaf(-v.y, w.y, acc.x));
-                acc.y = fmaf(v.x, w.y, fmaf(v.y, w.x, acc.y));
-                jk += k;
-                if (jk >= n) jk -= n;
-            }
-            tmp[i] = acc;
-        }
-        __syncthreads();
-        for (int i = tid; i < L * n; i += 256) buf[i] = tmp[i];
-        __syncthreads();
-    }
-}
 
 static int ilog2_exact(int n) {
     int l = 0;
@@ -254,6 +193,16 @@ int launch_rfft2_polar(const float* in, float* mag, float* pha, float2* cscratch
     fft_cols_kernel<false><<<p.gy, 256, p.lds_cols, st>>>(cscratch, nullptr, nullptr, nullptr, mag, pha, planes, h, p.wf, w / 2, p.log2h, p.TC,
                                                           1.0f / sqrtf((float)h));
     return check_launch("rfft2_polar");
+}
+
+// the row pass of launch_rfft2_polar alone: the half spectrum of every row, scaled 1/sqrt(w), into `cscratch` (the backward's
+// column kernel transforms it again, rf_ffab_bwd.hip)
+int launch_rfft_rows(const float* in, float2* cscratch, int planes, int h, int w, hipStream_t st) {
+    FftPlan p;
+    RF_TRY(plan_fft("rfft2", planes, h, w, &p));
+    ProfScope prof(st, "rfft_rows", 0.0, 4.0 * planes * ((double)h * w + 2.0 * h * p.wf));
+    fft_rows_r2c_kernel<<<p.gx, 256, p.lds_rows, st>>>(in, cscratch, p.rows, w, p.log2w, p.L, 1.0f / sqrtf((float)w));
+    return check_launch("rfft_rows");
 }
 
 // irfft2 (ortho, s = (h, w)) of mag * exp(i pha), then out = clamp(. + clamp(res, +-lim), +-lim)   (res may be null)

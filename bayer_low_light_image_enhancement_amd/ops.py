@@ -759,6 +759,99 @@ def wm_backward(x: torch.Tensor, params, grad_out: torch.Tensor, prefix: str = "
     return grad_x, grads
 
 
+def feb_param_shapes(nc: int):
+    """Names and shapes of the 10 tensors ``feb`` reads, in the order of the C ABI's pointer array."""
+    return {k: ((nc, nc, 1, 1) if k.endswith("weight") else (nc,)) for k in _FEB_KEYS}
+
+
+def ffab_param_shapes(nc: int):
+    """Names and shapes of the 92 tensors ``ffab`` reads, in the order of the C ABI's pointer array: the four ``nc`` ProcessBlocks,
+    then ``conv4`` / ``conv5`` / ``convout``, each a ``2 nc`` ProcessBlock and a 1x1 back to ``nc``."""
+    shapes = {}
+    for k in _FFAB_KEYS:
+        head = k.split(".")[0]
+        if head in ("conv4", "conv5", "convout"):
+            c = 2 * nc
+            shapes[k] = ((nc, c, 1, 1) if k.endswith("weight") else (nc,)) if k.split(".")[1] == "1" else ((c, c, 1, 1) if k.endswith("weight") else (c,))
+        else:
+            shapes[k] = (nc, nc, 1, 1) if k.endswith("weight") else (nc,)
+    return shapes
+
+
+def rfft2_polar_backward(x: torch.Tensor, grad_mag: torch.Tensor, grad_pha: torch.Tensor) -> torch.Tensor:
+    """The gradient of ``rfft2_polar``: ``grad_x`` for ``grad_mag`` = dL/d ``mag`` and ``grad_pha`` = dL/d ``pha``.  The spectrum of
+    ``x`` is recomputed; where it is exactly 0 both maps pass no gradient (torch's ``abs`` / ``angle`` backward)."""
+    x, grad_mag, grad_pha = _chk(x, "x"), _chk(grad_mag, "grad_mag"), _chk(grad_pha, "grad_pha")
+    if x.dim() != 4:
+        raise RuntimeError(f"rfft2_polar_backward: expected a 4-D x, got {tuple(x.shape)}")
+    b, c, h, w = x.shape
+    if tuple(grad_mag.shape) != (b, c, h, w // 2 + 1) or tuple(grad_pha.shape) != tuple(grad_mag.shape):
+        raise RuntimeError(f"rfft2_polar_backward: grad_mag / grad_pha must be {(b, c, h, w // 2 + 1)}, got {tuple(grad_mag.shape)} and "
+                           f"{tuple(grad_pha.shape)}")
+    lib = _lib.load()
+    scratch = _workspace(lib.rf_rfft2_polar_backward_scratch_bytes(b * c, h, w), "rf_rfft2_polar_backward_scratch_bytes", x)
+    grad_x = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.rf_rfft2_polar_backward(_ptr(x), _ptr(grad_mag), _ptr(grad_pha), _ptr(grad_x), _ptr(scratch), b * c, h, w, _stream(x)),
+                   "rf_rfft2_polar_backward")
+    return grad_x
+
+
+def polar_irfft2_backward(mag: torch.Tensor, pha: torch.Tensor, grad_out: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The gradient of ``polar_irfft2``: ``(grad_mag, grad_pha)`` for ``grad_out`` = dL/d ``polar_irfft2(mag, pha, grad_out.shape[-1])``."""
+    mag, pha, grad_out = _chk(mag, "mag"), _chk(pha, "pha"), _chk(grad_out, "grad_out")
+    if grad_out.dim() != 4:
+        raise RuntimeError(f"polar_irfft2_backward: expected a 4-D grad_out, got {tuple(grad_out.shape)}")
+    b, c, h, w = grad_out.shape
+    if tuple(mag.shape) != (b, c, h, w // 2 + 1) or tuple(pha.shape) != tuple(mag.shape):
+        raise RuntimeError(f"polar_irfft2_backward: mag / pha must be {(b, c, h, w // 2 + 1)}, got {tuple(mag.shape)} and {tuple(pha.shape)}")
+    lib = _lib.load()
+    scratch = _workspace(lib.rf_polar_irfft2_backward_scratch_bytes(b * c, h, w), "rf_polar_irfft2_backward_scratch_bytes", mag)
+    grad_mag, grad_pha = torch.empty_like(mag), torch.empty_like(mag)
+    with torch.cuda.device(mag.device):
+        _lib.check(lib.rf_polar_irfft2_backward(_ptr(mag), _ptr(pha), _ptr(grad_out), _ptr(grad_mag), _ptr(grad_pha), _ptr(scratch), b * c, h, w,
+                                                _stream(mag)), "rf_polar_irfft2_backward")
+    return grad_mag, grad_pha
+
+
+def _block_backward(name, keys, shapes_of, x, params, grad_out, prefix, grads):
+    x, grad_out = _chk(x, "x"), _chk(grad_out, "grad_out")
+    if x.dim() != 4 or tuple(grad_out.shape) != tuple(x.shape):
+        raise RuntimeError(f"{name}_backward: expected 4-D x and grad_out of one shape, got {tuple(x.shape)} and {tuple(grad_out.shape)}")
+    b, c, h, w = x.shape
+    shapes = shapes_of(c)
+    ts = _shaped(params, prefix, keys, shapes, f"{name}_backward")
+    accumulate = grads is not None
+    if grads is None:
+        grads = {prefix + k: torch.empty_like(t) for k, t in zip(keys, ts)}
+    gs = _shaped(grads, prefix, keys, shapes, f"{name}_backward (grads)")
+    if any(t.data_ptr() != grads[prefix + k].data_ptr() for k, t in zip(keys, gs)):
+        raise RuntimeError(f"{name}_backward: the tensors of grads must be contiguous (they are written in place)")
+    lib = _lib.load()
+    query, call = getattr(lib, f"rf_{name}_backward_workspace_bytes"), getattr(lib, f"rf_{name}_backward")
+    ws = _workspace(query(b, c, h, w), f"rf_{name}_backward_workspace_bytes", x)
+    grad_x = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _lib.check(call(_ptr(x), _ptr(grad_out), _ptr(grad_x), _ptr_array(ts), _ptr_array(gs), _ptr(ws), ws.numel(), b, c, h, w, int(accumulate),
+                        _stream(x)), f"rf_{name}_backward")
+    return grad_x, grads
+
+
+def feb_backward(x: torch.Tensor, params, grad_out: torch.Tensor, prefix: str = "", grads=None):
+    """The gradient of ``feb``: ``(grad_x, grads)`` for ``grad_out`` = dL/d ``feb(x, params)``.  ``grads`` maps the 10 keys ``feb`` reads
+    (``prefix`` included) to gradients of the parameters' shapes (``feb_param_shapes``).  Passing the ``grads`` of an earlier call ADDS
+    to its tensors; ``grad_x`` is always a new tensor.  The forward intermediates are recomputed: nothing is kept from a ``feb``
+    call, and ``x``, ``grad_out`` and ``params`` are not written.  The three clamps follow ``torch.clamp``'s backward (the gradient
+    passes where ``lo <= v <= hi`` at the value before the clamp)."""
+    return _block_backward("feb", _FEB_KEYS, feb_param_shapes, x, params, grad_out, prefix, grads)
+
+
+def ffab_backward(x: torch.Tensor, params, grad_out: torch.Tensor, prefix: str = "", grads=None):
+    """The gradient of ``ffab``: ``(grad_x, grads)`` for ``grad_out`` = dL/d ``ffab(x, params)``, with ``feb_backward``'s contract and
+    the 92 keys of ``ffab_param_shapes``."""
+    return _block_backward("ffab", _FFAB_KEYS, ffab_param_shapes, x, params, grad_out, prefix, grads)
+
+
 def wmb(x: torch.Tensor, params, prefix: str = "") -> torch.Tensor:
     """``WMB(dim)(x)`` (RawFomer_WFB_FFAB/model.py:203-245), eval mode: the wavelet branch with ``mb`` = ``WM`` on the three high
     bands, then ``x + ffn(norm2(x))``."""

@@ -285,6 +285,33 @@ int rf_feb(const float* in, float* out, const float* const* prm, void* scratch, 
  * (conv0.0.{w,b}, conv0.1.<ProcessBlock: 10 FEB tensors, cat.{w,b}>, conv1..conv3, conv4.0.<PB>, conv4.1.{w,b}, conv5.*, convout.*). */
 int rf_ffab_scratch_bytes(int B, int nc, int h, int w, size_t* bytes);
 int rf_ffab(const float* in, float* out, const float* const* prm, void* scratch, int B, int nc, int h, int w, void* stream);
+/* The gradients of the four operators above.  Conventions of rf_wm_backward: a *_bytes query returns a negative error code for a
+ * geometry the operator refuses (the forward's: nc % 4 == 0, even w; and the transforms': lengths 2 .. 4096, a length that is no
+ * power of two at most 2048); every tensor pointer is 16-byte aligned; outputs and scratch may not alias an input or each other
+ * (-22 with an rf_last_error message otherwise; rf_feb_backward / rf_ffab_backward check the byte ranges of in, grad_out, grad_in,
+ * every parameter, every gradient and the workspace, inputs alone may overlap one another); inputs and parameters are not written; every sum runs in a fixed order (no float
+ * atomics): two runs give the same bits.
+ * rf_rfft2_polar_backward: (in [planes,h,w], dL/dmag, dL/dpha [planes,h,w/2+1]) -> grad_in = dL/din.  The spectrum F of `in` is
+ *   recomputed; G = dL/dmag F/|F| + dL/dpha (-Im F, Re F)/|F|^2, and 0 where F = 0 (torch's abs / angle backward).
+ * rf_polar_irfft2_backward: (mag, pha, grad_out = dL/d irfft2(mag e^{i pha}) [planes,h,w]) -> dL/dmag, dL/dpha.
+ * Both take planes * h * (w/2+1) complex values of scratch (the queries return that in bytes). */
+long long rf_rfft2_polar_backward_scratch_bytes(int planes, int h, int w);
+int rf_rfft2_polar_backward(const float* in, const float* grad_mag, const float* grad_pha, float* grad_in, void* scratch, int planes, int h, int w,
+                            void* stream);
+long long rf_polar_irfft2_backward_scratch_bytes(int planes, int h, int w);
+int rf_polar_irfft2_backward(const float* mag, const float* pha, const float* grad_out, float* grad_mag, float* grad_pha, void* scratch,
+                             int planes, int h, int w, void* stream);
+/* rf_feb_backward / rf_ffab_backward: (in, grad_out = dL/d out, prm) -> grad_in = dL/d in and grad_prm, a HOST array of 10 / 92
+ * device pointers with prm's order and shapes.  Nothing is kept from a forward call: the intermediates are recomputed with the
+ * forward's own kernels.  Every shape rf_feb / rf_ffab accept is accepted, within the transforms' length limits.  grad_in is always
+ * overwritten; accumulate != 0 ADDS to the grad_prm tensors, 0 overwrites them.  A workspace smaller than the query's answer is
+ * refused with -12. */
+long long rf_feb_backward_workspace_bytes(int B, int nc, int h, int w);
+int rf_feb_backward(const float* in, const float* grad_out, float* grad_in, const float* const* prm, float* const* grad_prm, void* workspace,
+                    size_t workspace_bytes, int B, int nc, int h, int w, int accumulate, void* stream);
+long long rf_ffab_backward_workspace_bytes(int B, int nc, int h, int w);
+int rf_ffab_backward(const float* in, const float* grad_out, float* grad_in, const float* const* prm, float* const* grad_prm, void* workspace,
+                     size_t workspace_bytes, int B, int nc, int h, int w, int accumulate, void* stream);
 /* out = add + clamp(in * scale + shift, lo, hi): inverse_data_transform + residual of WMB (model.py:13-15, 241-243). */
 int rf_affine_clamp_add(const float* in, const float* add, float* out, size_t n, float scale, float shift, float lo, float hi, void* stream);
 

@@ -5,7 +5,7 @@ Each case runs through the C ABI (ops.*) with the library's own HIP-event bracke
 (rf_profile_begin/end), so the figure is the kernel's time on its launch stream, without the
 weight-repack helper that the operator-level entry points run first.
 
-usage: python tools/kbench.py [conv1x1] [conv3x3] [dw] [attn] [flca] [dwt] [ssim] [sampler] [mcr_sampler] [mamba] [wfb] [--dim 32] [--batch 8] [--size 512]
+usage: python tools/kbench.py [conv1x1] [conv3x3] [dw] [attn] [flca] [dwt] [ssim] [sampler] [mcr_sampler] [mamba] [wfb] [ffab_bwd] [--dim 32] [--batch 8] [--size 512]
 """
 from __future__ import annotations
 
@@ -176,6 +176,38 @@ def main():
             print(f"wfb {bb}x{S}x{S}: WM over the 7 stages {wm_ms:.3f} ms = {100 * wm_ms / (total / 10):.0f} % of the forward's kernel time; "
                   f"its 3x3 convolutions {wm_conv:.3f} ms = {100 * wm_conv / wm_ms:.0f} % of WM", flush=True)
             del xm
+    if "ffab_bwd" in a.what:   # ops.ffab_backward against ops.ffab on the LL band of four 512 x 512 patches at level 0 and level 3 of RawFormer-S:
+        # HIP events around `iters` calls, both orders in one visit (workspace allocation and the per-call weight packs included, for
+        # both); then the backward's per-kernel table on one stream and the share of the four transform-adjoint kernels
+        def event_ms(fn, iters=10, warm=2):
+            for _ in range(warm):
+                fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / iters
+
+        for bb, c, hw in ((4, 32, 128), (4, 256, 16)):
+            xf, gf = torch.rand(bb, c, hw, hw, device=dev) * 2 - 1, r(bb, c, hw, hw)
+            pf = {k: (torch.rand(*v, device=dev) * 2 - 1) / (v[1] if len(v) == 4 else v[0]) ** 0.5 for k, v in ops.ffab_param_shapes(c).items()}
+            fwd, bwd = (lambda: ops.ffab(xf, pf)), (lambda: ops.ffab_backward(xf, pf, gf))
+            t = [event_ms(fwd), event_ms(bwd), event_ms(bwd), event_ms(fwd)]
+            print(f"ffab ({bb},{c},{hw},{hw}): forward {t[0]:.3f} / {t[3]:.3f} ms, backward {t[1]:.3f} / {t[2]:.3f} ms per call (order: forward, "
+                  f"backward, backward, forward); backward / forward = {(t[1] + t[2]) / (t[0] + t[3]):.2f}", flush=True)
+            for tag, fn in (("forward", fwd), ("backward", bwd)):
+                recs = timed(fn)
+                total = sum(q["ms"] for q in recs)
+                for q in sorted(recs, key=lambda q: -q["ms"]):
+                    print(f"ffab {tag} ({bb},{c},{hw},{hw})  {q['kernel']:40s} {q['launches'] // 10:5d} launches {q['ms'] / 10:8.3f} ms {100 * q['ms'] / total:5.1f} %  "
+                          f"{q['ms'] / q['launches'] * 1e3:8.1f} us each  {q['bytes'] / max(q['ms'], 1e-9) / 1e6:8.1f} GB/s", flush=True)
+                adj = sum(q["ms"] for q in recs if q["kernel"].endswith("_backward(2 kernels)"))
+                print(f"ffab {tag} ({bb},{c},{hw},{hw}): {total / 10:.3f} ms per call as the sum of its bracketed kernels on one stream"
+                      + (f"; the four transform-adjoint kernels {adj / 10:.3f} ms = {100 * adj / total:.1f} %" if tag == "backward" else ""), flush=True)
+            del xf, gf, pf
     if "dwt" in a.what:
         x = r(B, d, S, S)
         report("dwt_init", timed(lambda: ops.dwt_init(x)))
