@@ -60,6 +60,11 @@ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+// workgroups of 256 threads for a grid-stride loop over n elements: at least one, at most cap
+static inline int grid1d(size_t n, int cap = 4096) {
+    const size_t g = (n + 255) / 256;
+    return g > (size_t)cap ? cap : g < 1 ? 1 : (int)g;
+}
 
 // The one allocator behind every workspace / scratch layout: consecutive buffers, each rounded up to 64 floats (256-byte granules
 // keep every buffer 16-byte aligned).  off() is the offset form and take() the pointer form of the same step; with a null base

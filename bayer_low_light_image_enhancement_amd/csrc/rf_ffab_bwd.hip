@@ -16,9 +16,10 @@
 //   gy        = adjoint of rfft2 + polar at F of (gmag, gpha)           launch_rfft_rows, adj_cols_rfft_kernel, adj_rows_c2r_kernel
 //   fpre      dW, db = wgrad(gy, xc);  gx = (W^T gy + gs) where -10 <= x <= 10
 //
-// wgrad = launch_gram2 with one tap where the plane's pixel count is a multiple of 4, else plain_wgrad_kernel (below); W^T g =
-// launch_conv1x1 on a transposed pack.  Both transforms are norm='ortho' and linear, so their adjoints are transforms of the other
-// direction over the same lines in LDS (rf_fft_lines.h); what differs from irfft2 / rfft2 is the treatment of the half spectrum:
+// wgrad = wgrad1x1 (rf_grad.hip): launch_gram2 with one tap where the plane's pixel count is a multiple of 4, else wgrad1x1_kernel;
+// W^T g = dgrad1x1: launch_conv1x1 on a transposed pack.  Both transforms are norm='ortho' and linear, so their adjoints are
+// transforms of the other direction over the same lines in LDS (rf_fft_lines.h); what differs from irfft2 / rfft2 is the treatment
+// of the half spectrum:
 //
 //   adjoint of rfft2:   the half spectrum G (wf = w/2 + 1 columns) is zero-extended, NOT Hermitian-extended, and nothing is
 //                       doubled:  gy[x] = Re sum_{k < wf} G_k e^{+2 pi i k x / w} / sqrt(w)
@@ -28,6 +29,7 @@
 // Every sum over pixels goes to per-workgroup slabs that a second kernel adds in a fixed order: no atomics, two runs give the same bits.
 #include <cmath>
 #include "rf_fft_lines.h"
+#include "rf_grad.h"
 
 namespace rf {
 
@@ -179,43 +181,6 @@ __global__ void __launch_bounds__(256) mask_range_kernel(const float* g, const f
     }
 }
 
-// Weight and bias gradient of a 1x1 convolution for planes launch_gram2 does not take (P % 4 != 0: rows that are not 16-byte aligned):
-// partial[(image, slab)][i][j] = sum over the slab's pixels of a[i][t] b[j][t], bias_partial[(image, slab)][i] = sum of a[i][t];
-// a workgroup owns a 16 x 16 tile of (i, j) and adds its pixels in order.
-__global__ void __launch_bounds__(256) plain_wgrad_kernel(const float* __restrict__ a, int Ca, const float* __restrict__ b, int Cb,
-                                                          float* __restrict__ partial, float* __restrict__ bias_partial, int P, int slab_len, int ntj) {
-    __shared__ float sa[16][65], sb[16][65];
-    const int i0 = ((int)blockIdx.x / ntj) * 16, j0 = ((int)blockIdx.x % ntj) * 16, ti = threadIdx.x >> 4, tj = threadIdx.x & 15;
-    const float* ag = a + (size_t)blockIdx.z * Ca * P;
-    const float* bg = b + (size_t)blockIdx.z * Cb * P;
-    const int lo = blockIdx.y * slab_len, hi = min(P, lo + slab_len);
-    float acc = 0.f, accb = 0.f;
-    for (int t0 = lo; t0 < hi; t0 += 64) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int idx = threadIdx.x + 256 * q, r = idx >> 6, c = idx & 63;
-            const bool ok = t0 + c < hi;
-            sa[r][c] = (ok && i0 + r < Ca) ? ag[(size_t)(i0 + r) * P + t0 + c] : 0.f;
-            sb[r][c] = (ok && j0 + r < Cb) ? bg[(size_t)(j0 + r) * P + t0 + c] : 0.f;
-        }
-        __syncthreads();
-#pragma unroll 16
-        for (int c = 0; c < 64; ++c) {
-            acc = fmaf(sa[ti][c], sb[tj][c], acc);
-            accb += sa[ti][c];
-        }
-        __syncthreads();
-    }
-    const size_t slab = (size_t)blockIdx.z * gridDim.y + blockIdx.y;
-    if (i0 + ti < Ca && j0 + tj < Cb) partial[(slab * Ca + i0 + ti) * Cb + j0 + tj] = acc;
-    if (j0 == 0 && tj == 0 && i0 + ti < Ca) bias_partial[slab * Ca + i0 + ti] = accb;
-}
-
-int grid1d(size_t n) {
-    const size_t g = (n + 255) / 256;
-    return g > 4096 ? 4096 : g < 1 ? 1 : (int)g;
-}
-
 int launch_mask_range(const float* g, const float* v, const float* add, float* out, size_t n, float lo, float hi, hipStream_t st) {
     ProfScope prof(st, "mask_range_kernel", 0.0, (add ? 16.0 : 12.0) * n);
     mask_range_kernel<<<grid1d(n), 256, 0, st>>>(g, v, add, out, n, lo, hi);
@@ -249,60 +214,6 @@ int launch_rfft2_polar_backward(const float* in, const float* gmag, const float*
 
 namespace {
 
-// ---- 1x1 convolution gradients on [B][C][P] planes
-int plain_wgrad_slabs(int P, int* slab_len) {
-    int len = cdiv(cdiv(P, 16), 64) * 64;
-    if (len < 1024) len = 1024;
-    *slab_len = len;
-    return cdiv(P, len);
-}
-
-size_t wgrad_partial_floats(int B, int Ca, int Cb, int P) {
-    if (P % 4 == 0) return gram2_partial_floats(B, Ca, Cb, 1, P, 1);
-    int len;
-    return (size_t)B * plain_wgrad_slabs(P, &len) * ((size_t)Ca * Cb + Ca);
-}
-
-int reduce_rows(const float* partial, float* out, int nrows, size_t n, int accumulate, hipStream_t st) {
-    ProfScope prof(st, "reduce_partials_kernel", (double)nrows * n, 4.0 * (nrows + 1.0) * n);
-    return launch_reduce_rows(partial, out, nrows, n, accumulate, st);
-}
-
-struct Wgrad { float* partial; size_t cap; int B, P, acc; hipStream_t st; };
-
-// dW [Ca][Cb] and db [Ca] (+)= the gradient of a 1x1 convolution with output gradient a [B][Ca][P] and input b [B][Cb][P]
-int wgrad1x1(const Wgrad& q, const float* a, int Ca, const float* b, int Cb, float* dW, float* db) {
-    const int B = q.B, P = q.P;
-    if (P % 4 == 0) {
-        Gram2Launch g{};
-        g.a = a; g.a_bstride = (int64_t)Ca * P; g.Ca = Ca; g.b = b; g.b_bstride = (int64_t)Cb * P; g.Cb = Cb;
-        g.out = dW; g.ld = Cb; g.partial = q.partial; g.partial_cap = q.cap; g.B = B; g.h = 1; g.w = P; g.ntap = 1;
-        g.accumulate = q.acc != 0; g.db = db;
-        return launch_gram2(g, q.st);
-    }
-    int len;
-    const int nslab = plain_wgrad_slabs(P, &len), ntj = cdiv(Cb, 16);
-    const size_t n = (size_t)Ca * Cb;
-    RF_CHECK_ARG((size_t)B * nslab * (n + Ca) <= q.cap, "ffab backward: the weight-gradient partials exceed their buffer");
-    float* bias_partial = q.partial + (size_t)B * nslab * n;
-    {
-        ProfScope prof(q.st, "plain_wgrad_kernel", 2.0 * Ca * Cb * (double)B * P, 4.0 * (double)B * P * (Ca + Cb));
-        plain_wgrad_kernel<<<dim3((unsigned)(cdiv(Ca, 16) * ntj), (unsigned)nslab, (unsigned)B), 256, 0, q.st>>>(a, Ca, b, Cb, q.partial, bias_partial,
-                                                                                                                   P, len, ntj);
-        RF_TRY(check_launch("plain_wgrad"));
-    }
-    RF_TRY(reduce_rows(q.partial, dW, B * nslab, n, q.acc, q.st));
-    return reduce_rows(bias_partial, db, B * nslab, (size_t)Ca, q.acc, q.st);
-}
-
-// out [B][cin][P] = W^T g (+ res) for the layer's weight W [cout][cin] and output gradient g [B][cout][P]
-int dgrad1x1(const float* g, int cout, const float* w, int cin, float* wpack, const float* res, float* out, int B, int P, hipStream_t st) {
-    RF_TRY(pack_1x1(w, wpack, cin, cout, 1, cin, st));
-    Conv1x1Args a = conv1x1_dense(g, cout, wpack, nullptr, nullptr, out, cin, B, P, P);
-    a.res = res; a.res_bstride = (int64_t)cin * P;
-    return launch_conv1x1(a, st);
-}
-
 // ---- one FEB
 struct FebBwdBufs {
     float *xc, *y, *s, *gy;                                              // [B][nc][P]
@@ -319,7 +230,7 @@ void feb_bwd_plan(Bump& b, FebBwdBufs& f, int B, int nc, int h, int w, size_t wp
     f.gm = b.take(Uf); f.gp = b.take(Uf); f.gt = b.take(Uf); f.gmag = b.take(Uf); f.gpha = b.take(Uf);
     f.cplx = reinterpret_cast<float2*>(b.take(2 * Uf));
     f.wpack = b.take(packed1x1_floats(nc, nc));
-    const size_t c1 = wgrad_partial_floats(B, nc, nc, h * w), c2 = wgrad_partial_floats(B, nc, nc, h * (w / 2 + 1));
+    const size_t c1 = wgrad1x1_partial_floats(B, nc, nc, h * w, true), c2 = wgrad1x1_partial_floats(B, nc, nc, h * (w / 2 + 1), true);
     f.wpart_cap = wpart_cap > c1 ? wpart_cap : c1;
     if (f.wpart_cap < c2) f.wpart_cap = c2;
     f.wpart = b.take(f.wpart_cap);
@@ -344,7 +255,7 @@ int feb_adjoint(const float* x, const float* g, const float* add, float* gx, con
                 int nc, int h, int w, int acc, hipStream_t st) {
     const int P = h * w, Pf = h * (w / 2 + 1);
     const size_t U = (size_t)B * nc * P, Uf = (size_t)B * nc * Pf;
-    const Wgrad wp{f.wpart, f.wpart_cap, B, P, acc, st}, wf{f.wpart, f.wpart_cap, B, Pf, acc, st};
+    const Wgrad wp{"ffab backward", f.wpart, f.wpart_cap, B, P, acc, st}, wf{"ffab backward", f.wpart, f.wpart_cap, B, Pf, acc, st};
     float* gs = f.s;
     RF_TRY(launch_mask_range(g, f.s, nullptr, gs, U, -10.f, 10.f, st));
     RF_TRY(launch_polar_irfft2_backward(f.m, f.p, gs, f.gm, f.gp, f.cplx, B * nc, h, w, st));
@@ -382,7 +293,7 @@ int block_backward(const float* x, const float* g, float* gx, const float* const
                    int B, int nc, int h, int w, int acc, hipStream_t st) {
     const int P = h * w;
     RF_TRY(block_recompute(x, nullptr, p, f, k, B, nc, h, w, st));
-    RF_TRY(wgrad1x1(Wgrad{f.wpart, f.wpart_cap, B, P, acc, st}, g, nc, k.feb_out, nc, d[10], d[11]));
+    RF_TRY(wgrad1x1(Wgrad{"ffab backward", f.wpart, f.wpart_cap, B, P, acc, st}, g, nc, k.feb_out, nc, d[10], d[11]));
     RF_TRY(dgrad1x1(g, nc, p[10], nc, f.wpack, nullptr, k.gfeb, B, P, st));
     return feb_adjoint(x, k.gfeb, g, gx, p, d, f, B, nc, h, w, acc, st);
 }
@@ -409,8 +320,8 @@ int ffab_bwd_plan(const char* who, float* base, FfabBwdPlan& p, int B, int nc, i
     p.gpb = b.take(2 * U); p.gcat = b.take(2 * U);
     p.gax = b.take(U); p.gax1 = b.take(U); p.gax2 = b.take(U); p.gh = b.take(U); p.gt = b.take(U); p.gc = b.take(U);
     p.k.feb_out = b.take(2 * U); p.k.gfeb = b.take(2 * U);
-    const size_t c1 = wgrad_partial_floats(B, nc, 2 * nc, h * w), c2 = wgrad_partial_floats(B, nc, nc, h * w),
-                 c3 = wgrad_partial_floats(B, nc, nc, h * (w / 2 + 1));
+    const size_t c1 = wgrad1x1_partial_floats(B, nc, 2 * nc, h * w, true), c2 = wgrad1x1_partial_floats(B, nc, nc, h * w, true),
+                 c3 = wgrad1x1_partial_floats(B, nc, nc, h * (w / 2 + 1), true);
     size_t cap = c1 > c2 ? c1 : c2;
     if (cap < c3) cap = c3;
     feb_bwd_plan(b, p.f, B, 2 * nc, h, w, cap);
@@ -423,7 +334,7 @@ int run_ffab_backward(const FfabBwdPlan& q, const float* in, const float* g, flo
     const int P = h * w;
     const size_t U = (size_t)B * nc * P, per = (size_t)nc * P;
     const FebBwdBufs& f = q.f;
-    const Wgrad wg{f.wpart, f.wpart_cap, B, P, acc, st};
+    const Wgrad wg{"ffab backward", f.wpart, f.wpart_cap, B, P, acc, st};
     // state_dict order (rf_ffab.hip): conv0.0 at 0; the nc blocks conv0.1, conv1, conv2, conv3 at 2, 14, 26, 38; the 2 nc blocks and
     // their 1x1 back to nc: conv4 at 50 / 62, conv5 at 64 / 76, convout at 78 / 90
     const int tail_at[3] = {50, 64, 78};
@@ -494,31 +405,6 @@ size_t ffab_prm_floats(int i, int nc) {
     return j < 12 ? feb_prm_floats(j, 2 * nc) : j == 12 ? (size_t)2 * nc * nc : (size_t)nc;
 }
 
-bool overlaps(const void* a, size_t abytes, const void* b, size_t bbytes) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + bbytes && b0 < a0 + abytes;
-}
-
-// Everything the call writes (grad_in, the n gradients, the workspace) must be disjoint from everything it reads (in, grad_out, the
-// n parameters) and from everything else it writes.  Inputs may overlap each other.
-int check_no_alias(const char* who, const float* in, const float* gout, float* gin, size_t plane_bytes, const float* const* prm, float* const* grd,
-                   int n, size_t (*floats)(int, int), int nc, const void* ws, size_t ws_bytes) {
-    auto out_ptr = [&](int i) -> const void* { return i < n ? (const void*)grd[i] : i == n ? (const void*)gin : ws; };
-    auto out_bytes = [&](int i) { return i < n ? floats(i, nc) * sizeof(float) : i == n ? plane_bytes : ws_bytes; };
-    auto in_ptr = [&](int i) -> const void* { return i < n ? (const void*)prm[i] : i == n ? (const void*)in : (const void*)gout; };
-    auto in_bytes = [&](int i) { return i < n ? floats(i, nc) * sizeof(float) : plane_bytes; };
-    for (int a = 0; a < n + 2; ++a) {
-        for (int b = 0; b < n + 2; ++b)
-            RF_CHECK_ARG(!overlaps(out_ptr(a), out_bytes(a), in_ptr(b), in_bytes(b)),
-                         "%s: an output (gradient %d; %d = grad_in, %d = workspace) may not alias an input (parameter %d; %d = in, %d = grad_out)", who, a,
-                         n, n + 1, b, n, n + 1);
-        for (int b = a + 1; b < n + 2; ++b)
-            RF_CHECK_ARG(!overlaps(out_ptr(a), out_bytes(a), out_ptr(b), out_bytes(b)),
-                         "%s: outputs may not alias each other (gradients %d and %d; %d = grad_in, %d = workspace)", who, a, b, n, n + 1);
-    }
-    return RF_OK;
-}
-
 }  // namespace
 }  // namespace rf
 
@@ -535,9 +421,10 @@ int rf_rfft2_polar_backward(const float* in, const float* grad_mag, const float*
     RF_CHECK_ARG(in && grad_mag && grad_pha && grad_in && scratch && aligned16(in) && aligned16(grad_mag) && aligned16(grad_pha) &&
                      aligned16(grad_in) && aligned16(scratch),
                  "rf_rfft2_polar_backward: in, grad_mag, grad_pha, grad_in and scratch must be non-null and 16-byte aligned");
-    RF_CHECK_ARG(grad_in != in && grad_in != grad_mag && grad_in != grad_pha && scratch != in && scratch != grad_mag && scratch != grad_pha &&
-                     scratch != grad_in,
-                 "rf_rfft2_polar_backward: grad_in and scratch may not alias an input or each other");
+    const size_t nb = (size_t)planes * h * w * sizeof(float), nf = (size_t)planes * h * (w / 2 + 1) * sizeof(float);
+    const Span outs[] = {{grad_in, nb}, {scratch, (size_t)need}}, ins[] = {{in, nb}, {grad_mag, nf}, {grad_pha, nf}};
+    int a, b;
+    RF_CHECK_ARG(!first_alias(outs, 2, ins, 3, &a, &b), "rf_rfft2_polar_backward: grad_in and scratch may not alias an input or each other");
     return launch_rfft2_polar_backward(in, grad_mag, grad_pha, grad_in, (float2*)scratch, planes, h, w, (hipStream_t)stream);
 }
 
@@ -550,9 +437,10 @@ int rf_polar_irfft2_backward(const float* mag, const float* pha, const float* gr
     RF_CHECK_ARG(mag && pha && grad_out && grad_mag && grad_pha && scratch && aligned16(mag) && aligned16(pha) && aligned16(grad_out) &&
                      aligned16(grad_mag) && aligned16(grad_pha) && aligned16(scratch),
                  "rf_polar_irfft2_backward: mag, pha, grad_out, grad_mag, grad_pha and scratch must be non-null and 16-byte aligned");
-    RF_CHECK_ARG(grad_mag != grad_pha && grad_mag != mag && grad_mag != pha && grad_mag != grad_out && grad_pha != mag && grad_pha != pha &&
-                     grad_pha != grad_out && scratch != mag && scratch != pha && scratch != grad_out && scratch != grad_mag && scratch != grad_pha,
-                 "rf_polar_irfft2_backward: grad_mag, grad_pha and scratch may not alias an input or each other");
+    const size_t nb = (size_t)planes * h * w * sizeof(float), nf = (size_t)planes * h * (w / 2 + 1) * sizeof(float);
+    const Span outs[] = {{grad_mag, nf}, {grad_pha, nf}, {scratch, (size_t)need}}, ins[] = {{mag, nf}, {pha, nf}, {grad_out, nb}};
+    int a, b;
+    RF_CHECK_ARG(!first_alias(outs, 3, ins, 3, &a, &b), "rf_polar_irfft2_backward: grad_mag, grad_pha and scratch may not alias an input or each other");
     return launch_polar_irfft2_backward(mag, pha, grad_out, grad_mag, grad_pha, (float2*)scratch, planes, h, w, (hipStream_t)stream);
 }
 
@@ -566,16 +454,9 @@ int rf_feb_backward(const float* in, const float* grad_out, float* grad_in, cons
                     size_t workspace_bytes, int B, int nc, int h, int w, int accumulate, void* stream) {
     FebBwdPlan p;
     RF_TRY(feb_bwd_whole_plan("rf_feb_backward", (float*)workspace, p, B, nc, h, w));
-    RF_CHECK_ARG(in && grad_out && grad_in && prm && grad_prm && workspace && aligned16(in) && aligned16(grad_out) && aligned16(grad_in) &&
-                     aligned16(workspace),
-                 "rf_feb_backward: in, grad_out, grad_in, prm, grad_prm and workspace must be non-null and 16-byte aligned");
-    if (workspace_bytes < p.total * sizeof(float)) {
-        set_error("rf_feb_backward: workspace of %zu bytes, %zu needed", workspace_bytes, p.total * sizeof(float));
-        return RF_E_NOMEM;
-    }
-    for (int i = 0; i < 10; ++i) RF_CHECK_ARG(prm[i] != nullptr && grad_prm[i] != nullptr, "rf_feb_backward: parameter or gradient %d is null", i);
-    RF_TRY(check_no_alias("rf_feb_backward", in, grad_out, grad_in, (size_t)B * nc * h * w * sizeof(float), prm, grad_prm, 10, feb_prm_floats, nc, workspace,
-                          p.total * sizeof(float)));
+    RF_TRY(check_backward_args({"rf_feb_backward", in, grad_out, grad_in, (size_t)B * nc * h * w * sizeof(float), prm, grad_prm, 10, workspace,
+                                workspace_bytes, p.total * sizeof(float)},
+                               [=](int i) { return feb_prm_floats(i, nc); }));
     const hipStream_t st = (hipStream_t)stream;
     RF_TRY(feb_recompute(in, prm, p.f, B, nc, h, w, st));
     return feb_adjoint(in, grad_out, nullptr, grad_in, prm, grad_prm, p.f, B, nc, h, w, accumulate, st);
@@ -591,16 +472,9 @@ int rf_ffab_backward(const float* in, const float* grad_out, float* grad_in, con
                      size_t workspace_bytes, int B, int nc, int h, int w, int accumulate, void* stream) {
     FfabBwdPlan p;
     RF_TRY(ffab_bwd_plan("rf_ffab_backward", (float*)workspace, p, B, nc, h, w));
-    RF_CHECK_ARG(in && grad_out && grad_in && prm && grad_prm && workspace && aligned16(in) && aligned16(grad_out) && aligned16(grad_in) &&
-                     aligned16(workspace),
-                 "rf_ffab_backward: in, grad_out, grad_in, prm, grad_prm and workspace must be non-null and 16-byte aligned");
-    if (workspace_bytes < p.total * sizeof(float)) {
-        set_error("rf_ffab_backward: workspace of %zu bytes, %zu needed", workspace_bytes, p.total * sizeof(float));
-        return RF_E_NOMEM;
-    }
-    for (int i = 0; i < 92; ++i) RF_CHECK_ARG(prm[i] != nullptr && grad_prm[i] != nullptr, "rf_ffab_backward: parameter or gradient %d is null", i);
-    RF_TRY(check_no_alias("rf_ffab_backward", in, grad_out, grad_in, (size_t)B * nc * h * w * sizeof(float), prm, grad_prm, 92, ffab_prm_floats, nc, workspace,
-                          p.total * sizeof(float)));
+    RF_TRY(check_backward_args({"rf_ffab_backward", in, grad_out, grad_in, (size_t)B * nc * h * w * sizeof(float), prm, grad_prm, 92, workspace,
+                                workspace_bytes, p.total * sizeof(float)},
+                               [=](int i) { return ffab_prm_floats(i, nc); }));
     return run_ffab_backward(p, in, grad_out, grad_in, prm, grad_prm, B, nc, h, w, accumulate, (hipStream_t)stream);
 }
 

@@ -41,6 +41,8 @@ struct MambaBwdPlan {
     size_t u, g, gu, yg, dpre, dx, dxc, dxz, ddbc, slab, adj, adj_s, dA, dD, cw, cb, csum, wpart, wpart_cap;   // float offsets
     size_t t_in, t_in3, t_x, t_x3, t_dt, t_dt3, t_out, t_out3;                                                 // transposed packs
 };
+// floats of tensor i of the nine of the pointer arrays, in ops.mamba_param_shapes' order
+size_t mamba_prm_floats(int i, int D, int N, int K, int E);
 // the forward plan first (same offsets as mamba_plan on a fresh Bump), then the adjoint's buffers
 int mamba_bwd_plan(const char* who, int B, int L, int D, int N, int K, int E, MambaBwdPlan* p, Bump* b);
 // channel-major: u, g, du [B][D][L]; grd: the nine gradients in the order of prm, written or (acc) added to.  The plan's u, g and

@@ -3,10 +3,10 @@
 // Nothing is kept from a forward call.  mamba_forward_front (rf_mamba.hip) recomputes xz, xc, [dt ; Bm ; Cm], delta and the
 // state every chunk starts from; the rest, with g = dL/dout, everything channel-major [image][channel][L]:
 //
-//   dyg = W_out^T g                                      launch_conv1x1 on a transposed pack
+//   dyg = W_out^T g                                      dgrad1x1 (rf_grad.hip): launch_conv1x1 on a transposed pack
 //   reverse scan (below)                                 -> yg = y silu(z), dz, dx (scan part + D dy), dpre, dBm / dCm slabs,
 //                                                           per-chunk partials of dA_log and dD
-//   dW_out = sum g (x) yg, dD, dA_log                    weight-gradient GEMM, launch_reduce_rows
+//   dW_out = sum g (x) yg, dD, dA_log                    wgrad1x1 (rf_grad.hip), reduce_rows
 //   d dt_proj.bias = sum dpre, d dt_proj.weight = sum dpre (x) dt,  d dt = W_dt^T dpre
 //   dBm, dCm = slabs summed over the channel tiles       mamba_bc_reduce_kernel (fixed order)
 //   dW_x = sum d[dt;Bm;Cm] (x) xc,  dxc = dx + W_x^T d[dt;Bm;Cm]
@@ -31,6 +31,7 @@
 // __shfl_xor steps over the four lanes of a channel; the sums over the 16 channels of dBm_t[n], dCm_t[n] are four steps, all in
 // a fixed order.  Across channel tiles dBm / dCm are written as slabs [image][tile][64][L] and summed in tile order.
 // No atomics anywhere: two runs give the same bits.
+#include "rf_grad.h"
 #include "rf_mamba.h"
 
 namespace rf {
@@ -391,88 +392,7 @@ __global__ void __launch_bounds__(256) mamba_conv_bwd_kernel(const float* __rest
     }
 }
 
-// Weight gradient for token counts launch_gram2 does not take (L % 4 != 0: rows that are not 16-byte aligned):
-// partial[(image, slab)][i][j] = sum over the slab's tokens of a[i][t] b[j][t]; a workgroup owns a 16 x 16 tile of (i, j).
-__global__ void __launch_bounds__(256) mamba_wgrad_kernel(const float* __restrict__ a, int64_t a_bstride, int Ca, const float* __restrict__ b,
-                                                          int64_t b_bstride, int Cb, float* __restrict__ partial, int L, int slab_len, int ntj) {
-    __shared__ float sa[16][65], sb[16][65];
-    const int i0 = ((int)blockIdx.x / ntj) * 16, j0 = ((int)blockIdx.x % ntj) * 16, ti = threadIdx.x >> 4, tj = threadIdx.x & 15;
-    const float* ag = a + (size_t)blockIdx.z * a_bstride;
-    const float* bg = b + (size_t)blockIdx.z * b_bstride;
-    const int lo = blockIdx.y * slab_len, hi = min(L, lo + slab_len);
-    float acc = 0.f;
-    for (int t0 = lo; t0 < hi; t0 += 64) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int idx = threadIdx.x + 256 * q, r = idx >> 6, c = idx & 63;
-            const bool ok = t0 + c < hi;
-            sa[r][c] = (ok && i0 + r < Ca) ? ag[(size_t)(i0 + r) * L + t0 + c] : 0.f;
-            sb[r][c] = (ok && j0 + r < Cb) ? bg[(size_t)(j0 + r) * L + t0 + c] : 0.f;
-        }
-        __syncthreads();
-#pragma unroll 16
-        for (int c = 0; c < 64; ++c) acc = fmaf(sa[ti][c], sb[tj][c], acc);
-        __syncthreads();
-    }
-    if (i0 + ti < Ca && j0 + tj < Cb)
-        partial[(((size_t)blockIdx.z * gridDim.y + blockIdx.y) * Ca + i0 + ti) * Cb + j0 + tj] = acc;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
-static int wgrad_slabs(int L, int* slab_len) {
-    int len = cdiv(cdiv(L, 16), 64) * 64;
-    if (len < 1024) len = 1024;
-    *slab_len = len;
-    return cdiv(L, len);
-}
-
-static size_t wgrad_partial_floats(int B, int L, int Ca, int Cb) {
-    int len;
-    const size_t own = (size_t)B * wgrad_slabs(L, &len) * Ca * Cb;
-    const size_t g2 = L % 4 == 0 ? gram2_partial_floats(B, Ca, Cb, 1, L, 1) : 0;
-    return own > g2 ? own : g2;
-}
-
-// launch_reduce_rows inside a profiler bracket: out[e] (+)= sum over rows of partial[row][e]
-static int reduce_rows(const float* partial, float* out, int nrows, size_t n, int accumulate, hipStream_t st) {
-    ProfScope prof(st, "reduce_partials_kernel", (double)nrows * n, 4.0 * (nrows + 1.0) * n);
-    return launch_reduce_rows(partial, out, nrows, n, accumulate, st);
-}
-
-// out[Ca][Cb] (+)= sum over images and tokens of a[i][t] b[j][t]
-static int mamba_wgrad(const float* a, int64_t a_bstride, int Ca, const float* b, int64_t b_bstride, int Cb, float* out, float* partial,
-                       size_t partial_cap, int B, int L, int accumulate, hipStream_t st) {
-    if (L % 4 == 0) {
-        Gram2Launch g{};
-        g.a = a; g.a_bstride = a_bstride; g.Ca = Ca; g.b = b; g.b_bstride = b_bstride; g.Cb = Cb;
-        g.out = out; g.ld = Cb; g.partial = partial; g.partial_cap = partial_cap; g.B = B; g.h = 1; g.w = L; g.ntap = 1;
-        g.accumulate = accumulate != 0;
-        return launch_gram2(g, st);
-    }
-    int len;
-    const int nslab = wgrad_slabs(L, &len), ntj = cdiv(Cb, 16);
-    RF_CHECK_ARG((size_t)B * nslab * Ca * Cb <= partial_cap, "rf_mamba_backward: the weight-gradient partials exceed their buffer");
-    {
-        ProfScope prof(st, "mamba_wgrad_kernel", 2.0 * Ca * Cb * (double)B * L, 4.0 * (double)B * L * (Ca + Cb));
-        mamba_wgrad_kernel<<<dim3((unsigned)(cdiv(Ca, 16) * ntj), (unsigned)nslab, (unsigned)B), 256, 0, st>>>(a, a_bstride, Ca, b, b_bstride, Cb,
-                                                                                                                  partial, L, len, ntj);
-        RF_TRY(check_launch("mamba_wgrad"));
-    }
-    return reduce_rows(partial, out, B * nslab, (size_t)Ca * Cb, accumulate, st);
-}
-
-// data gradient of a projection: out [B][Cout][L] = W^T x (+ res), W [K][Cout] row-major, x [B][Kp >= K][L] (rows K .. Kp - 1 zero)
-static int mamba_dgrad(const float* x, int K, int Kp, int64_t x_bstride, const float* w, float* wp, float* wp3, const float* res, float* out,
-                       int64_t out_bstride, int Cout, int B, int L, hipStream_t st) {
-    RF_TRY(pack_1x1(w, wp, Cout, K, 1, Cout, st));
-    RF_TRY(pack_1x1_b3(w, wp3, Cout, K, 1, Cout, st));
-    Conv1x1Args a{};
-    a.x1 = x; a.C1 = Kp; a.x1_bstride = x_bstride; a.wp = wp; a.wp3 = wp3; a.ln_eps = 1e-5f;
-    a.res = res; a.res_bstride = (int64_t)Cout * L;
-    a.out = out; a.out_bstride = out_bstride; a.Cout = Cout; a.B = B; a.P = L; a.w = L;
-    return launch_conv1x1(a, st);
-}
-
 int mamba_bwd_plan(const char* who, int B, int L, int D, int N, int K, int E, MambaBwdPlan* p, Bump* b) {
     RF_TRY(mamba_plan(who, B, L, D, N, K, E, &p->m, b));
     const int Di = p->m.Di, R = p->m.R, NR = p->m.NR, nchunk = p->m.nchunk;
@@ -496,11 +416,10 @@ int mamba_bwd_plan(const char* who, int B, int L, int D, int N, int K, int E, Ma
     p->cw = b->off((size_t)B * Di * kDc);
     p->cb = b->off((size_t)B * Di);
     p->csum = b->off((size_t)B * chan_sum_nblk(L) * Di);
-    size_t cap = wgrad_partial_floats(B, L, D, Di);                        // dW_out
-    const size_t c2 = wgrad_partial_floats(B, L, Di, R), c3 = wgrad_partial_floats(B, L, NR, Di), c4 = wgrad_partial_floats(B, L, 2 * Di, D);
-    cap = cap > c2 ? cap : c2;
-    cap = cap > c3 ? cap : c3;
-    cap = cap > c4 ? cap : c4;
+    size_t cap = 0;                                                         // dW_out, d dt_proj.weight, dW_x, dW_in: no bias sums
+    for (const size_t c : {wgrad1x1_partial_floats(B, D, Di, L, false), wgrad1x1_partial_floats(B, Di, R, L, false),
+                           wgrad1x1_partial_floats(B, NR, Di, L, false), wgrad1x1_partial_floats(B, 2 * Di, D, L, false)})
+        cap = cap > c ? cap : c;
     p->wpart_cap = cap;
     p->wpart = b->off(cap);
     p->t_in = b->off(packed1x1_floats(2 * Di, D));
@@ -524,9 +443,14 @@ int run_mamba_backward(const MambaBwdPlan& p, const float* u, const float* g, fl
           *ddbc = ws + p.ddbc, *wpart = ws + p.wpart;
     const int64_t iDi = (int64_t)Di * L, iD = (int64_t)D * L;
     const double el = (double)B * Di * L, bc = 4.0 * B * kN * (double)L;
+    const Wgrad wg{"rf_mamba_backward", wpart, p.wpart_cap, B, L, acc, st};
+    // data gradient of a projection W [K][Cout]: out = W^T x (+ res) on the bf16x3 GEMM, x [B][Kp >= K][L] with rows K .. Kp - 1 zero
+    auto dgrad = [&](const float* x, int K, int Kp, const float* w, size_t t, size_t t3, const float* res, float* out, int64_t out_bstride, int Cout) {
+        return dgrad1x1(Dgrad1x1{x, K, Kp, (int64_t)Kp * L, w, ws + t, ws + t3, res, out, out_bstride, Cout, B, L}, st);
+    };
     RF_TRY(mamba_forward_front(m, u, prm, ws, B, L, st));
     // dyg = W_out^T g, into the buffer the scan turns into yg
-    RF_TRY(mamba_dgrad(g, D, D, iD, w_out, ws + p.t_out, ws + p.t_out3, nullptr, yg, iDi, Di, B, L, st));
+    RF_TRY(dgrad(g, D, D, w_out, p.t_out, p.t_out3, nullptr, yg, iDi, Di));
     AdjArgs a{};
     a.delta = ws + m.delta; a.x = xc; a.z = xz + (size_t)Di * L; a.z_bstride = 2 * iDi;
     a.bm = dbc + (size_t)R * L; a.bc_bstride = (int64_t)NR * L; a.A_log = A_log; a.Dp = prm[7]; a.state = ws + m.state;
@@ -551,14 +475,14 @@ int run_mamba_backward(const MambaBwdPlan& p, const float* u, const float* g, fl
     }
     RF_TRY(reduce_rows(a.dA_part, grd[6], B * nchunk, (size_t)Di * kN, acc, st));
     RF_TRY(reduce_rows(a.dD_part, grd[7], B * nchunk, (size_t)Di, acc, st));
-    RF_TRY(mamba_wgrad(g, iD, D, yg, iDi, Di, grd[8], wpart, p.wpart_cap, B, L, acc, st));                       // dW_out
+    RF_TRY(wgrad1x1(wg, g, iD, D, yg, iDi, Di, grd[8], nullptr));                                                // dW_out
     // dt_proj
     {
         ProfScope prof(st, "chan_sum_kernel", el, 4.0 * el);
         RF_TRY(launch_chan_sum(dpre, iDi, grd[5], ws + p.csum, B, Di, L, acc, st));
     }
-    RF_TRY(mamba_wgrad(dpre, iDi, Di, dbc, (int64_t)NR * L, R, grd[4], wpart, p.wpart_cap, B, L, acc, st));
-    RF_TRY(mamba_dgrad(dpre, Di, Di, iDi, w_dt, ws + p.t_dt, ws + p.t_dt3, nullptr, ddbc, (int64_t)NRp * L, R, B, L, st));
+    RF_TRY(wgrad1x1(wg, dpre, iDi, Di, dbc, (int64_t)NR * L, R, grd[4], nullptr));
+    RF_TRY(dgrad(dpre, Di, Di, w_dt, p.t_dt, p.t_dt3, nullptr, ddbc, (int64_t)NRp * L, R));
     {
         const int rows = 2 * kN + NRp - NR;
         ProfScope prof(st, "mamba_bc_reduce_kernel", 2.0 * kN * p.nct * (double)B * L, 2.0 * bc * (p.nct + 1));
@@ -566,8 +490,8 @@ int run_mamba_backward(const MambaBwdPlan& p, const float* u, const float* g, fl
         RF_TRY(check_launch("mamba_bc_reduce"));
     }
     // x_proj
-    RF_TRY(mamba_wgrad(ddbc, (int64_t)NRp * L, NR, xc, iDi, Di, grd[3], wpart, p.wpart_cap, B, L, acc, st));
-    RF_TRY(mamba_dgrad(ddbc, NR, NRp, (int64_t)NRp * L, w_x, ws + p.t_x, ws + p.t_x3, a.dx, dxc, iDi, Di, B, L, st));
+    RF_TRY(wgrad1x1(wg, ddbc, (int64_t)NRp * L, NR, xc, iDi, Di, grd[3], nullptr));
+    RF_TRY(dgrad(ddbc, NR, NRp, w_x, p.t_x, p.t_x3, a.dx, dxc, iDi, Di));
     // conv1d + SiLU
     {
         const size_t total = (size_t)B * Di * L;
@@ -585,8 +509,14 @@ int run_mamba_backward(const MambaBwdPlan& p, const float* u, const float* g, fl
     RF_TRY(reduce_rows(ws + p.cw, grd[1], B, (size_t)Di * kDc, acc, st));
     RF_TRY(reduce_rows(ws + p.cb, grd[2], B, (size_t)Di, acc, st));
     // in_proj
-    RF_TRY(mamba_wgrad(dxz, 2 * iDi, 2 * Di, u, iD, D, grd[0], wpart, p.wpart_cap, B, L, acc, st));
-    return mamba_dgrad(dxz, 2 * Di, 2 * Di, 2 * iDi, w_in, ws + p.t_in, ws + p.t_in3, nullptr, du, iD, D, B, L, st);
+    RF_TRY(wgrad1x1(wg, dxz, 2 * iDi, 2 * Di, u, iD, D, grd[0], nullptr));
+    return dgrad(dxz, 2 * Di, 2 * Di, w_in, p.t_in, p.t_in3, nullptr, du, iD, D);
+}
+
+size_t mamba_prm_floats(int i, int D, int N, int K, int E) {
+    const size_t Di = (size_t)E * D, R = cdiv(D, 16);
+    const size_t floats[9] = {2 * Di * D, Di * K, Di, (R + 2 * N) * Di, Di * R, Di, Di * N, Di, D * Di};
+    return floats[i];
 }
 
 }  // namespace rf
@@ -608,15 +538,11 @@ int rf_mamba_backward(const float* in, const float* grad_out, float* grad_in, co
     MambaBwdPlan p;
     Bump b;
     RF_TRY(mamba_bwd_plan("rf_mamba_backward", B, L, d_model, d_state, d_conv, expand, &p, &b));
-    RF_CHECK_ARG(in && grad_out && grad_in && prm && grad_prm && workspace && aligned16(in) && aligned16(grad_out) && aligned16(grad_in) &&
-                     aligned16(workspace),
-                 "rf_mamba_backward: in, grad_out, grad_in, prm, grad_prm and workspace must be non-null and 16-byte aligned");
-    if (workspace_bytes < b.used * sizeof(float)) {
-        set_error("rf_mamba_backward: workspace of %zu bytes, %zu needed", workspace_bytes, b.used * sizeof(float));
-        return RF_E_NOMEM;
-    }
-    RF_CHECK_ARG(in != grad_out && in != grad_in && grad_out != grad_in, "rf_mamba_backward: in, grad_out and grad_in may not alias each other");
-    for (int i = 0; i < 9; ++i) RF_CHECK_ARG(prm[i] != nullptr && grad_prm[i] != nullptr, "rf_mamba_backward: parameter or gradient %d is null", i);
+    // the workspace counts as an output whole: it holds the token-major call's u, g and gu copies too
+    RF_TRY(check_backward_args({"rf_mamba_backward", in, grad_out, grad_in, (size_t)B * L * d_model * sizeof(float), prm, grad_prm, 9, workspace,
+                                workspace_bytes, b.used * sizeof(float)},
+                               [=](int i) { return mamba_prm_floats(i, d_model, d_state, d_conv, expand); }));
+    RF_CHECK_ARG(in != grad_out, "rf_mamba_backward: in, grad_out and grad_in may not alias each other");
     hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)workspace;
     if (channel_major) return run_mamba_backward(p, in, grad_out, grad_in, prm, grad_prm, ws, B, L, accumulate, st);

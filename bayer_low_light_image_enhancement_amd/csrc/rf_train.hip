@@ -682,12 +682,6 @@ int red_grid(size_t n) {          // blocks of the slab reducers: 32 elements ea
     return (int)(g > 2048 ? 2048 : g < 1 ? 1 : g);
 }
 
-int grid1d(size_t n, int cap = 4096) {
-    int g = (int)((n + 255) / 256);
-    if (g > cap) g = cap;
-    return g < 1 ? 1 : g;
-}
-
 // ---- attention, small per-(head, image) kernel: softmax of the forward's Gram partials and its adjoint (AttnSmall, rf_common.h)
 // index of W[co][k] in a packed 1x1 weight matrix (rf_common.h)
 __device__ __forceinline__ size_t pk(int NT, int co, int k) { return ((size_t)(k >> 2) * NT + (co >> 4)) * 64 + (co & 15) + 16 * (k & 3); }

@@ -9,9 +9,10 @@
 //   convb.2   dW, db = wgrad(g_r, a1);         g_a1 = conv3x3(g_r, W2^T flipped) masked by a1 > 0
 //   convb.0   dW, db = wgrad(g_a1, x);         dL/dx = g_r + conv3x3(g_a1, W0^T flipped)
 //
-// wgrad = launch_gram2 with nine taps where w % 4 == 0, else conv3x3_wgrad_kernel (below).  The three transposed, tap-flipped
+// wgrad = wgrad3x3 (rf_grad.hip): launch_gram2 with nine taps where w % 4 == 0, else conv3x3_wgrad_kernel.  The three transposed, tap-flipped
 // packs are written by one launch_pack_batch.  Every sum over pixels or rows goes to per-workgroup slabs that a second kernel adds
 // in a fixed order: no atomics, two runs give the same bits.
+#include "rf_grad.h"
 #include "rf_mamba.h"
 
 namespace rf {
@@ -163,12 +164,6 @@ static int wm_ln_bwd_nblk(int B, int rows) {
     return ng < cap ? ng : cap;
 }
 
-// launch_reduce_rows inside a profiler bracket
-static int reduce_rows(const float* partial, float* out, int nrows, size_t n, int accumulate, hipStream_t st) {
-    ProfScope prof(st, "reduce_partials_kernel", (double)nrows * n, 4.0 * (nrows + 1.0) * n);
-    return launch_reduce_rows(partial, out, nrows, n, accumulate, st);
-}
-
 // partial: 2 B nblk cols floats
 static int launch_wm_ln_bwd(const float* in, const float* add, const float* g, const float* lw, float* dx, float* dlw, float* dlb, float* partial,
                             int B, int rows, int cols, int accumulate, hipStream_t st) {
@@ -182,77 +177,6 @@ static int launch_wm_ln_bwd(const float* in, const float* add, const float* g, c
     }
     RF_TRY(reduce_rows(dgam, dlw, B * nblk, (size_t)cols, accumulate, st));
     return reduce_rows(dbet, dlb, B * nblk, (size_t)cols, accumulate, st);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// 3x3 weight and bias gradient for the widths launch_gram2 does not take (w % 4 != 0: the small bands of the deep levels):
-//   dW[co][ci][dy][dx] = sum over images and pixels of a[co][y][x] b[ci][y + dy - 1][x + dx - 1],   db[co] = sum of a[co]
-// A thread owns one (ci, tap) of one output channel and one slab of `slab_px` consecutive pixels of the batch (images laid end
-// to end) and adds them in order; every thread of the workgroup reads the same a value (one broadcast load).  The partials have
-// the layout of the result, [slab][Ca][Cb][9] and [slab][Ca].
-__global__ void __launch_bounds__(256) conv3x3_wgrad_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ partial,
-                                                            float* __restrict__ bias_partial, int Ca, int Cb, int h, int w, long long total,
-                                                            long long slab_px) {
-    const int co = blockIdx.x, e = blockIdx.y * 256 + threadIdx.x;
-    if (e >= Cb * 9) return;
-    const int ci = e / 9, tap = e - 9 * ci, sy = tap / 3 - 1, sx = tap % 3 - 1;
-    const int P = h * w;
-    const long long q0 = (long long)blockIdx.z * slab_px, q1 = q0 + slab_px < total ? q0 + slab_px : total;
-    long long img = q0 / P;
-    int p = (int)(q0 - img * P);
-    float s = 0.f, sb = 0.f;
-    for (long long q = q0; q < q1; ++q) {
-        const float av = a[((size_t)img * Ca + co) * P + p];
-        const int y = p / w, x = p - y * w, yy = y + sy, xx = x + sx;
-        if (yy >= 0 && yy < h && xx >= 0 && xx < w) s = fmaf(av, b[((size_t)img * Cb + ci) * P + yy * w + xx], s);
-        sb += av;
-        if (++p == P) {
-            p = 0;
-            ++img;
-        }
-    }
-    partial[((size_t)blockIdx.z * Ca + co) * Cb * 9 + e] = s;
-    if (e == 0) bias_partial[(size_t)blockIdx.z * Ca + co] = sb;
-}
-
-static int wgrad3x3_slabs(int B, int P, long long* slab_px) {
-    const long long total = (long long)B * P;
-    long long px = (total + 32767) / 32768;
-    if (px < 4096) px = 4096;
-    *slab_px = px;
-    return (int)((total + px - 1) / px);
-}
-
-static size_t wgrad3x3_partial_floats(int B, int Ca, int Cb, int h, int w) {
-    if (w % 4 == 0) return gram2_partial_floats(B, Ca, Cb, h, w, 9);
-    long long px;
-    return (size_t)wgrad3x3_slabs(B, h * w, &px) * ((size_t)9 * Ca * Cb + Ca);
-}
-
-// dW [Ca][Cb][3][3] and db [Ca] (+)= the gradient of a 3x3 convolution with output gradient a [B][Ca][h][w] and input b [B][Cb][h][w]
-static int wm_wgrad3x3(const float* a, int Ca, const float* b, int Cb, float* dW, float* db, float* partial, size_t partial_cap, int B, int h,
-                       int w, int accumulate, hipStream_t st) {
-    if (w % 4 == 0) {
-        Gram2Launch g{};
-        g.a = a; g.a_bstride = (int64_t)Ca * h * w; g.Ca = Ca; g.b = b; g.b_bstride = (int64_t)Cb * h * w; g.Cb = Cb;
-        g.out = dW; g.ld = Cb; g.partial = partial; g.partial_cap = partial_cap; g.B = B; g.h = h; g.w = w; g.ntap = 9;
-        g.accumulate = accumulate != 0; g.db = db;
-        return launch_gram2(g, st);
-    }
-    long long px;
-    const int nslab = wgrad3x3_slabs(B, h * w, &px);
-    const size_t n = (size_t)9 * Ca * Cb;
-    RF_CHECK_ARG((size_t)nslab * (n + Ca) <= partial_cap, "rf_wm_backward: the weight-gradient partials exceed their buffer");
-    float* bias_partial = partial + (size_t)nslab * n;
-    {
-        const double px_all = (double)B * h * w;
-        ProfScope prof(st, "conv3x3_wgrad_kernel", 18.0 * Ca * Cb * px_all, 4.0 * px_all * (Ca + Cb));
-        conv3x3_wgrad_kernel<<<dim3((unsigned)Ca, (unsigned)cdiv(Cb * 9, 256), (unsigned)nslab), 256, 0, st>>>(a, b, partial, bias_partial, Ca, Cb, h,
-                                                                                                               w, (long long)B * h * w, px);
-        RF_TRY(check_launch("conv3x3_wgrad"));
-    }
-    RF_TRY(reduce_rows(partial, dW, nslab, n, accumulate, st));
-    return reduce_rows(bias_partial, db, nslab, (size_t)Ca, accumulate, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -279,15 +203,21 @@ static int wm_bwd_plan(const char* who, int n, int c, int h, int w, WmBwdPlan* p
     p->y = b->off(plane * c);
     p->ga1 = b->off(plane * 2 * c);
     p->lnp = b->off((size_t)2 * n * wm_ln_bwd_nblk(n, h * w) * c);
-    size_t cap = wgrad3x3_partial_floats(n, 2 * c, c, h, w);             // convb.0
-    const size_t c2 = wgrad3x3_partial_floats(n, c, 2 * c, h, w), c3 = wgrad3x3_partial_floats(n, c, c, h, w);
-    cap = cap > c2 ? cap : c2;
-    cap = cap > c3 ? cap : c3;
+    size_t cap = 0;                                                       // convb.0, convb.2, smooth
+    for (const size_t f : {wgrad3x3_partial_floats(n, 2 * c, c, h, w), wgrad3x3_partial_floats(n, c, 2 * c, h, w), wgrad3x3_partial_floats(n, c, c, h, w)})
+        cap = cap > f ? cap : f;
     p->wpart_cap = cap;
     p->wpart = b->off(cap);
     p->ks_floats = conv3x3_ksplit_floats(n, 2 * c, h, w);                // the widest output of the five convolutions
     p->ks = b->off(p->ks_floats);
     return RF_OK;
+}
+
+// floats of tensor i of the 17 of the pointer arrays, in ops.wm_param_shapes' order
+static size_t wm_prm_floats(int i, int c) {
+    if (i >= 6 && i < 15) return mamba_prm_floats(i - 6, c, kN, kDc, 2);                           // model1
+    const size_t C = c, floats[6] = {2 * C * C * 9, 2 * C, C * 2 * C * 9, C, C, C};                // convb.0, convb.2, ln
+    return i < 6 ? floats[i] : i == 15 ? C * C * 9 : C;                                            // smooth
 }
 
 static int wm_dgrad3x3(const float* dy, const float* wp, float* dx, float* ks, size_t ks_floats, int n, int cout, int cin, int h, int w,
@@ -301,8 +231,8 @@ static int run_wm_backward(const WmBwdPlan& p, const float* x, const float* g, f
                            int n, int c, int h, int w, int acc, hipStream_t st) {
     const int L = h * w;
     const size_t el = (size_t)n * c * L;
-    float *a1 = ws + p.a1, *r = ws + p.r, *y = ws + p.y, *ga1 = ws + p.ga1, *tok = ws + p.mb.u, *gy = ws + p.mb.g, *gtok = ws + p.mb.gu,
-          *wpart = ws + p.wpart;
+    float *a1 = ws + p.a1, *r = ws + p.r, *y = ws + p.y, *ga1 = ws + p.ga1, *tok = ws + p.mb.u, *gy = ws + p.mb.g, *gtok = ws + p.mb.gu;
+    const Wgrad wg{"rf_wm_backward", ws + p.wpart, p.wpart_cap, n, L, acc, st};
     float* gr = y;                                                          // y is dead once smooth's weight gradient is taken
     // dX weights of a 3x3 convolution [Cout][Cin][3][3]: rows and columns exchanged, taps flipped
     const PackDesc packs[3] = {{prm[0], ws + p.t0, 1, c, 2 * c, 9, (int64_t)c * 9, 1},
@@ -318,18 +248,18 @@ static int run_wm_backward(const WmBwdPlan& p, const float* x, const float* g, f
     fb.ks = ks; fb.ks_floats = p.ks_floats;
     RF_TRY(wm_forward_front(p.mb.m, x, prm, nullptr, ws, fb, n, c, h, w, st));
     // smooth
-    RF_TRY(wm_wgrad3x3(g, c, y, c, grd[15], grd[16], wpart, p.wpart_cap, n, h, w, acc, st));
+    RF_TRY(wgrad3x3(wg, g, c, y, c, grd[15], grd[16], w));
     RF_TRY(wm_dgrad3x3(g, ws + p.ts, gy, ks, p.ks_floats, n, c, c, h, w, st));
     // Mamba, channel-major
     RF_TRY(run_mamba_backward(p.mb, tok, gy, gtok, prm + 6, grd + 6, ws, n, L, acc, st));
     // LayerNorm over the runs of c floats + the transposition
     RF_TRY(launch_wm_ln_bwd(r, x, gtok, prm[4], gr, grd[4], grd[5], ws + p.lnp, n, L, c, acc, st));
     // convb.2
-    RF_TRY(wm_wgrad3x3(gr, c, a1, 2 * c, grd[2], grd[3], wpart, p.wpart_cap, n, h, w, acc, st));
+    RF_TRY(wgrad3x3(wg, gr, c, a1, 2 * c, grd[2], grd[3], w));
     RF_TRY(wm_dgrad3x3(gr, ws + p.t2, ga1, ks, p.ks_floats, n, c, 2 * c, h, w, st));
     RF_TRY(launch_ewise(ga1, a1, ga1, 2 * el, 2, 0.f, st));                 // ReLU: g_a1 where a1 > 0, else 0
     // convb.0 and the skip
-    RF_TRY(wm_wgrad3x3(ga1, 2 * c, x, c, grd[0], grd[1], wpart, p.wpart_cap, n, h, w, acc, st));
+    RF_TRY(wgrad3x3(wg, ga1, 2 * c, x, c, grd[0], grd[1], w));
     RF_TRY(wm_dgrad3x3(ga1, ws + p.t0, dx, ks, p.ks_floats, n, 2 * c, c, h, w, st));
     return launch_ewise(dx, gr, dx, el, 0, 0.f, st);
 }
@@ -352,15 +282,10 @@ int rf_wm_backward(const float* in, const float* grad_out, float* grad_in, const
     WmBwdPlan p;
     Bump b;
     RF_TRY(wm_bwd_plan("rf_wm_backward", n, c, h, w, &p, &b));
-    RF_CHECK_ARG(in && grad_out && grad_in && prm && grad_prm && workspace && aligned16(in) && aligned16(grad_out) && aligned16(grad_in) &&
-                     aligned16(workspace),
-                 "rf_wm_backward: in, grad_out, grad_in, prm, grad_prm and workspace must be non-null and 16-byte aligned");
-    if (workspace_bytes < b.used * sizeof(float)) {
-        set_error("rf_wm_backward: workspace of %zu bytes, %zu needed", workspace_bytes, b.used * sizeof(float));
-        return RF_E_NOMEM;
-    }
-    RF_CHECK_ARG(in != grad_out && in != grad_in && grad_out != grad_in, "rf_wm_backward: in, grad_out and grad_in may not alias each other");
-    for (int i = 0; i < 17; ++i) RF_CHECK_ARG(prm[i] != nullptr && grad_prm[i] != nullptr, "rf_wm_backward: parameter or gradient %d is null", i);
+    RF_TRY(check_backward_args({"rf_wm_backward", in, grad_out, grad_in, (size_t)n * c * h * w * sizeof(float), prm, grad_prm, 17, workspace,
+                                workspace_bytes, b.used * sizeof(float)},
+                               [=](int i) { return wm_prm_floats(i, c); }));
+    RF_CHECK_ARG(in != grad_out, "rf_wm_backward: in, grad_out and grad_in may not alias each other");
     return run_wm_backward(p, in, grad_out, grad_in, prm, grad_prm, (float*)workspace, n, c, h, w, accumulate, (hipStream_t)stream);
 }
 

@@ -688,21 +688,8 @@ def mamba_backward(u: torch.Tensor, params, grad_out: torch.Tensor, prefix: str 
     if u.dim() != 3 or tuple(grad_out.shape) != tuple(u.shape):
         raise RuntimeError(f"mamba_backward: expected 3-D u and grad_out of one shape, got {tuple(u.shape)} and {tuple(grad_out.shape)}")
     b, l, d = (u.shape[0], u.shape[2], u.shape[1]) if channel_major else tuple(u.shape)
-    shapes = mamba_param_shapes(d, d_state, d_conv, expand)
-    ts = _shaped(params, prefix, _MAMBA_KEYS, shapes, "mamba_backward")
-    accumulate = grads is not None
-    if grads is None:
-        grads = {prefix + k: torch.empty_like(t) for k, t in zip(_MAMBA_KEYS, ts)}
-    gs = _shaped(grads, prefix, _MAMBA_KEYS, shapes, "mamba_backward (grads)")
-    if any(t.data_ptr() != grads[prefix + k].data_ptr() for k, t in zip(_MAMBA_KEYS, gs)):
-        raise RuntimeError("mamba_backward: the tensors of grads must be contiguous (they are written in place)")
-    lib = _lib.load()
-    ws = _workspace(lib.rf_mamba_backward_workspace_bytes(b, l, d, d_state, d_conv, expand), "rf_mamba_backward_workspace_bytes", u)
-    grad_u = torch.empty_like(u)
-    with torch.cuda.device(u.device):
-        _lib.check(lib.rf_mamba_backward(_ptr(u), _ptr(grad_out), _ptr(grad_u), _ptr_array(ts), _ptr_array(gs), _ptr(ws), ws.numel(), b, l, d,
-                                         d_state, d_conv, expand, int(channel_major), int(accumulate), _stream(u)), "rf_mamba_backward")
-    return grad_u, grads
+    return _backward("mamba", _MAMBA_KEYS, mamba_param_shapes(d, d_state, d_conv, expand), u, params, grad_out, prefix, grads,
+                     (b, l, d, d_state, d_conv, expand), (int(channel_major),))
 
 
 def wm_param_shapes(c: int):
@@ -720,10 +707,7 @@ def wm(x: torch.Tensor, params, prefix: str = "") -> torch.Tensor:
     ``convb.0/2.*``, ``ln.*``, ``model1.*``, ``smooth.*``; ``model2`` is constructed by the reference but never called."""
     x = _chk(x, "x")
     n, c, h, w = x.shape
-    shapes = {"model1." + k: v for k, v in mamba_param_shapes(c).items()}
-    shapes.update({"convb.0.weight": (2 * c, c, 3, 3), "convb.0.bias": (2 * c,), "convb.2.weight": (c, 2 * c, 3, 3), "convb.2.bias": (c,),
-                   "ln.weight": (c,), "ln.bias": (c,), "smooth.weight": (c, c, 3, 3), "smooth.bias": (c,)})
-    ts = _shaped(params, prefix, _WM_KEYS, shapes, "wm")
+    ts = _shaped(params, prefix, _WM_KEYS, wm_param_shapes(c), "wm")
     lib = _lib.load()
     ws = _workspace(lib.rf_wm_workspace_bytes(n, c, h, w), "rf_wm_workspace_bytes", x)
     out = torch.empty_like(x)
@@ -738,25 +722,7 @@ def wm_backward(x: torch.Tensor, params, grad_out: torch.Tensor, prefix: str = "
     ``model2`` and ``softmax`` are never called by the reference and have none.  Passing the ``grads`` of an earlier call ADDS to its
     tensors; ``grad_x`` is always a new tensor.  The forward intermediates are recomputed: nothing is kept from a ``wm`` call, and
     ``x``, ``grad_out`` and ``params`` are not written."""
-    x, grad_out = _chk(x, "x"), _chk(grad_out, "grad_out")
-    if x.dim() != 4 or tuple(grad_out.shape) != tuple(x.shape):
-        raise RuntimeError(f"wm_backward: expected 4-D x and grad_out of one shape, got {tuple(x.shape)} and {tuple(grad_out.shape)}")
-    n, c, h, w = x.shape
-    shapes = wm_param_shapes(c)
-    ts = _shaped(params, prefix, _WM_KEYS, shapes, "wm_backward")
-    accumulate = grads is not None
-    if grads is None:
-        grads = {prefix + k: torch.empty_like(t) for k, t in zip(_WM_KEYS, ts)}
-    gs = _shaped(grads, prefix, _WM_KEYS, shapes, "wm_backward (grads)")
-    if any(t.data_ptr() != grads[prefix + k].data_ptr() for k, t in zip(_WM_KEYS, gs)):
-        raise RuntimeError("wm_backward: the tensors of grads must be contiguous (they are written in place)")
-    lib = _lib.load()
-    ws = _workspace(lib.rf_wm_backward_workspace_bytes(n, c, h, w), "rf_wm_backward_workspace_bytes", x)
-    grad_x = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.rf_wm_backward(_ptr(x), _ptr(grad_out), _ptr(grad_x), _ptr_array(ts), _ptr_array(gs), _ptr(ws), ws.numel(), n, c, h, w,
-                                      int(accumulate), _stream(x)), "rf_wm_backward")
-    return grad_x, grads
+    return _block_backward("wm", _WM_KEYS, wm_param_shapes, x, params, grad_out, prefix, grads)
 
 
 def feb_param_shapes(nc: int):
@@ -814,12 +780,10 @@ def polar_irfft2_backward(mag: torch.Tensor, pha: torch.Tensor, grad_out: torch.
     return grad_mag, grad_pha
 
 
-def _block_backward(name, keys, shapes_of, x, params, grad_out, prefix, grads):
-    x, grad_out = _chk(x, "x"), _chk(grad_out, "grad_out")
-    if x.dim() != 4 or tuple(grad_out.shape) != tuple(x.shape):
-        raise RuntimeError(f"{name}_backward: expected 4-D x and grad_out of one shape, got {tuple(x.shape)} and {tuple(grad_out.shape)}")
-    b, c, h, w = x.shape
-    shapes = shapes_of(c)
+def _backward(name, keys, shapes, x, params, grad_out, prefix, grads, geometry, trailing=()):
+    """What the ``*_backward`` wrappers share, ``x`` and ``grad_out`` checked by the caller: ``params`` and ``grads`` against
+    ``shapes``, the workspace ``rf_<name>_backward_workspace_bytes(*geometry)`` asks for, and the call
+    ``rf_<name>_backward(x, grad_out, grad_x, params, grads, workspace, bytes, *geometry, *trailing, accumulate, stream)``."""
     ts = _shaped(params, prefix, keys, shapes, f"{name}_backward")
     accumulate = grads is not None
     if grads is None:
@@ -829,12 +793,19 @@ def _block_backward(name, keys, shapes_of, x, params, grad_out, prefix, grads):
         raise RuntimeError(f"{name}_backward: the tensors of grads must be contiguous (they are written in place)")
     lib = _lib.load()
     query, call = getattr(lib, f"rf_{name}_backward_workspace_bytes"), getattr(lib, f"rf_{name}_backward")
-    ws = _workspace(query(b, c, h, w), f"rf_{name}_backward_workspace_bytes", x)
+    ws = _workspace(query(*geometry), f"rf_{name}_backward_workspace_bytes", x)
     grad_x = torch.empty_like(x)
     with torch.cuda.device(x.device):
-        _lib.check(call(_ptr(x), _ptr(grad_out), _ptr(grad_x), _ptr_array(ts), _ptr_array(gs), _ptr(ws), ws.numel(), b, c, h, w, int(accumulate),
-                        _stream(x)), f"rf_{name}_backward")
+        _lib.check(call(_ptr(x), _ptr(grad_out), _ptr(grad_x), _ptr_array(ts), _ptr_array(gs), _ptr(ws), ws.numel(), *geometry, *trailing,
+                        int(accumulate), _stream(x)), f"rf_{name}_backward")
     return grad_x, grads
+
+
+def _block_backward(name, keys, shapes_of, x, params, grad_out, prefix, grads):
+    x, grad_out = _chk(x, "x"), _chk(grad_out, "grad_out")
+    if x.dim() != 4 or tuple(grad_out.shape) != tuple(x.shape):
+        raise RuntimeError(f"{name}_backward: expected 4-D x and grad_out of one shape, got {tuple(x.shape)} and {tuple(grad_out.shape)}")
+    return _backward(name, keys, shapes_of(x.shape[1]), x, params, grad_out, prefix, grads, tuple(x.shape))
 
 
 def feb_backward(x: torch.Tensor, params, grad_out: torch.Tensor, prefix: str = "", grads=None):

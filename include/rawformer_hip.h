@@ -288,9 +288,10 @@ int rf_ffab(const float* in, float* out, const float* const* prm, void* scratch,
 /* The gradients of the four operators above.  Conventions of rf_wm_backward: a *_bytes query returns a negative error code for a
  * geometry the operator refuses (the forward's: nc % 4 == 0, even w; and the transforms': lengths 2 .. 4096, a length that is no
  * power of two at most 2048); every tensor pointer is 16-byte aligned; outputs and scratch may not alias an input or each other
- * (-22 with an rf_last_error message otherwise; rf_feb_backward / rf_ffab_backward check the byte ranges of in, grad_out, grad_in,
- * every parameter, every gradient and the workspace, inputs alone may overlap one another); inputs and parameters are not written; every sum runs in a fixed order (no float
- * atomics): two runs give the same bits.
+ * (-22 with an rf_last_error message otherwise; the byte ranges are compared, and rf_feb_backward / rf_ffab_backward, like
+ * rf_mamba_backward / rf_wm_backward below, take in, grad_out, grad_in, every parameter, every gradient and the workspace into
+ * that comparison; inputs alone may overlap one another); inputs and parameters are not written; every sum runs in a fixed order
+ * (no float atomics): two runs give the same bits.
  * rf_rfft2_polar_backward: (in [planes,h,w], dL/dmag, dL/dpha [planes,h,w/2+1]) -> grad_in = dL/din.  The spectrum F of `in` is
  *   recomputed; G = dL/dmag F/|F| + dL/dpha (-Im F, Re F)/|F|^2, and 0 where F = 0 (torch's abs / angle backward).
  * rf_polar_irfft2_backward: (mag, pha, grad_out = dL/d irfft2(mag e^{i pha}) [planes,h,w]) -> dL/dmag, dL/dpha.
@@ -414,8 +415,10 @@ int rf_mamba_forward(const float* in, float* out, const float* const* prm, void*
                      int B, int L, int d_model, int d_state, int d_conv, int expand, int channel_major, void* stream);
 /* The module's gradient: (in, grad_out = dL/d out, prm) -> grad_in = dL/d in and grad_prm, a HOST array of 9 device pointers
  * with prm's order and shapes (conv1d.weight's gradient is [Di,1,4]).  Nothing is kept from a forward call: the intermediates
- * are recomputed.  The limits and refusals are rf_mamba_forward's; in, grad_out, grad_in and workspace are 16-byte aligned and
- * in, grad_out, grad_in may not alias each other; in and grad_out are not written.  grad_in is always overwritten;
+ * are recomputed.  The limits and refusals are rf_mamba_forward's; in, grad_out, grad_in and workspace are 16-byte aligned.
+ * Nothing the call writes (grad_in, the nine gradients, the workspace) may overlap, in any byte, anything it reads (in, grad_out,
+ * the nine parameters) or anything else it writes, and in may not be grad_out (-22); in, grad_out and the parameters are not
+ * written.  grad_in is always overwritten;
  * accumulate != 0 ADDS to the nine grad_prm tensors (a training step sums several modules' calls), 0 overwrites them.
  * The adjoint recurrence runs in the forward's chunks, last to first, with every sum in a fixed order (no float atomics): two
  * runs give the same bits.  A workspace smaller than rf_mamba_backward_workspace_bytes is refused with -12. */
@@ -433,8 +436,8 @@ int rf_wm_forward(const float* in, float* out, const float* const* prm, void* wo
 /* WM's gradient: (in, grad_out = dL/d out, prm) -> grad_in = dL/d in and grad_prm, a HOST array of 17 device pointers with
  * prm's order and shapes.  Nothing is kept from a forward call: the intermediates are recomputed with the forward's own kernels.
  * Every shape rf_wm_forward accepts is accepted (widths that are no multiple of 4 take a plain 3x3 weight-gradient kernel).
- * in, grad_out, grad_in and workspace are 16-byte aligned; in, grad_out, grad_in may not alias each other; in, grad_out and
- * the parameters are not written.  grad_in is always overwritten; accumulate != 0 ADDS to the 17 grad_prm tensors, 0 overwrites
+ * in, grad_out, grad_in and workspace are 16-byte aligned; the alias rule is rf_mamba_backward's, over the 17 tensors; in,
+ * grad_out and the parameters are not written.  grad_in is always overwritten; accumulate != 0 ADDS to the 17 grad_prm tensors, 0 overwrites
  * them.  Every sum runs in a fixed order (no float atomics): two runs give the same bits.  A workspace smaller than
  * rf_wm_backward_workspace_bytes is refused with -12. */
 long long rf_wm_backward_workspace_bytes(int n, int c, int h, int w);

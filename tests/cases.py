@@ -391,3 +391,13 @@ def fft_plan(planes, h, w):
     _lib.check(_lib.load().rf_fft_plan(planes, h, w, out), "rf_fft_plan")
     l2w, l2h, L, tc, gx, gy, trips_r, trips_c, lds_r, lds_c = out
     return dict(log2w=l2w, log2h=l2h, L=L, TC=tc, grid=(gx, gy), trips=(trips_r, trips_c), lds=(lds_r, lds_c))
+
+
+def fake_addresses(nbytes):
+    """One fake device address per byte size: page aligned, in the order given, a free page between neighbours.  For the host-side
+    refusal tests, whose calls are turned away before anything is dereferenced but compare the byte ranges of their arguments."""
+    out, at = [], 1 << 30
+    for n in nbytes:
+        out.append(at)
+        at += (n + 4095) // 4096 * 4096 + 4096
+    return out

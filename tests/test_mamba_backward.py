@@ -21,7 +21,7 @@ underflow (1, 2Lc, 32)     delta around 5: exp(delta A) underflows to 0 for most
 =========================  =============================================================================================
 
 L % 4 == 0 (lc, underflow) takes launch_gram2 for the four weight gradients, every other case the scalar-row kernel
-mamba_wgrad_kernel.
+wgrad1x1_kernel<false> (csrc/rf_grad.hip), with the strides of the channel slices it reads.
 
 Bound, per gradient tensor (the scheme of tests/test_mamba.py and tests/test_train_shapes.py): e64 = max|hip - ref_f64| <=
 8 e32 + 2e-6 max|ref_f64|.  ``-s`` prints e64 / bound for every tensor of every case; DESIGN.md section 4, "Mamba backward", holds the table
@@ -143,10 +143,13 @@ def test_host_checks_refuse_unsupported_shapes_before_any_launch():
     order = ("B", "L", "d_model", "d_state", "d_conv", "expand")
     need = lib.rf_mamba_backward_workspace_bytes(*[good[k] for k in order])
     assert need >= lib.rf_mamba_workspace_bytes(*[good[k] for k in order]) > 0
-    # 16-byte aligned, distinct, never dereferenced: the checks come first
-    u, g, du, ws = (C.c_void_p(a << 12) for a in (1, 2, 3, 4))
-    prm = (C.c_void_p * 9)(*[5 << 12] * 9)
-    grd = (C.c_void_p * 9)(*[6 << 12] * 9)
+    # never dereferenced: the checks come first.  Every buffer has an address of its own, of its true size, clear of the others
+    n, plane = 9, 4 * good["B"] * good["L"] * good["d_model"]
+    tensors = [4 * math.prod(s) for s in ops.mamba_param_shapes(good["d_model"]).values()]
+    at = cases.fake_addresses([plane] * 3 + [need] + 2 * tensors)
+    u, g, du, ws = (C.c_void_p(v) for v in at[:4])
+    prm, grd = (C.c_void_p * n)(*at[4:4 + n]), (C.c_void_p * n)(*at[4 + n:])
+    call = lib.rf_mamba_backward
     for change, word in BAD:
         a = [{**good, **change}[k] for k in order]
         assert lib.rf_mamba_backward_workspace_bytes(*a) < 0
@@ -164,6 +167,21 @@ def test_host_checks_refuse_unsupported_shapes_before_any_launch():
         assert lib.rf_last_error().startswith(b"rf_mamba_backward: ") and b"alias" in lib.rf_last_error()
     assert lib.rf_mamba_backward(u, g, None, prm, grd, ws, 1 << 40, *a, 0, 0, None) == -22
     assert lib.rf_last_error().startswith(b"rf_mamba_backward: ")
+
+    def refused_as_alias(*args):
+        assert call(*args, 1 << 40, *a, 0, 0, None) == -22
+        assert lib.rf_last_error().startswith(b"rf_mamba_backward: ") and b"alias" in lib.rf_last_error(), lib.rf_last_error()
+
+    inside = lambda base, off: C.c_void_p(base.value + off)      # noqa: E731
+    refused_as_alias(u, g, inside(g, 4096), prm, grd, ws)         # grad_in inside grad_out
+    refused_as_alias(u, g, du, prm, grd, inside(u, 16))           # the workspace over in
+    refused_as_alias(u, g, du, prm, grd, inside(du, 64))          # ... over grad_in
+    refused_as_alias(u, g, du, prm, grd, C.c_void_p(prm[n - 1] - 256))      # ... over a parameter
+    for i, target in ((3, prm[5]), (0, du.value), (2, grd[7]), (1, ws.value + 1024), (n - 1, g.value + 32), (4, grd[5] - 16)):
+        bad_grd = (C.c_void_p * n)(*grd)
+        bad_grd[i] = target                                       # a gradient on a parameter, grad_in, another gradient, the workspace, ...
+        refused_as_alias(u, g, du, prm, bad_grd, ws)
+    assert call(u, inside(u, 16), du, prm, grd, ws, need - 1, *a, 0, 0, None) == -12      # inputs may overlap: refused for the workspace alone
 
 
 # ------------------------------------------------------------------------------------------ GPU

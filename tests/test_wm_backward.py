@@ -162,10 +162,13 @@ def test_host_checks_refuse_unsupported_shapes_before_any_launch():
     good = (6, 32, 16, 24)
     need = lib.rf_wm_backward_workspace_bytes(*good)
     assert need >= lib.rf_wm_workspace_bytes(*good) > 0
-    # 16-byte aligned, distinct, never dereferenced: the checks come first
-    x, g, dx, ws = (C.c_void_p(a << 12) for a in (1, 2, 3, 4))
-    prm = (C.c_void_p * 17)(*[5 << 12] * 17)
-    grd = (C.c_void_p * 17)(*[6 << 12] * 17)
+    # never dereferenced: the checks come first.  Every buffer has an address of its own, of its true size, clear of the others
+    n, plane, a = 17, 4 * math.prod(good), good
+    tensors = [4 * math.prod(s) for s in ops.wm_param_shapes(good[1]).values()]
+    at = cases.fake_addresses([plane] * 3 + [need] + 2 * tensors)
+    x, g, dx, ws = (C.c_void_p(v) for v in at[:4])
+    prm, grd = (C.c_void_p * n)(*at[4:4 + n]), (C.c_void_p * n)(*at[4 + n:])
+    call = lib.rf_wm_backward
     for bad, word in (((6, 18, 16, 24), b"c 18"), ((6, 516, 16, 24), b"c 516"), ((0, 32, 16, 24), b"n 0"), ((6, 32, 0, 24), b"0 x 24")):
         assert lib.rf_wm_backward_workspace_bytes(*bad) < 0
         msg = lib.rf_last_error()
@@ -182,8 +185,23 @@ def test_host_checks_refuse_unsupported_shapes_before_any_launch():
         assert lib.rf_last_error().startswith(b"rf_wm_backward: ") and b"alias" in lib.rf_last_error()
     assert lib.rf_wm_backward(x, g, None, prm, grd, ws, 1 << 40, *good, 0, None) == -22
     assert lib.rf_last_error().startswith(b"rf_wm_backward: ")
-    assert lib.rf_wm_backward(x, g, C.c_void_p((3 << 12) + 4), prm, grd, ws, 1 << 40, *good, 0, None) == -22
+    assert lib.rf_wm_backward(x, g, C.c_void_p(dx.value + 4), prm, grd, ws, 1 << 40, *good, 0, None) == -22
     assert lib.rf_last_error().startswith(b"rf_wm_backward: ") and b"aligned" in lib.rf_last_error()
+
+    def refused_as_alias(*args):
+        assert call(*args, 1 << 40, *a, 0, None) == -22
+        assert lib.rf_last_error().startswith(b"rf_wm_backward: ") and b"alias" in lib.rf_last_error(), lib.rf_last_error()
+
+    inside = lambda base, off: C.c_void_p(base.value + off)      # noqa: E731
+    refused_as_alias(x, g, inside(g, 4096), prm, grd, ws)         # grad_in inside grad_out
+    refused_as_alias(x, g, dx, prm, grd, inside(x, 16))           # the workspace over in
+    refused_as_alias(x, g, dx, prm, grd, inside(dx, 64))          # ... over grad_in
+    refused_as_alias(x, g, dx, prm, grd, C.c_void_p(prm[n - 1] - 256))      # ... over a parameter
+    for i, target in ((3, prm[5]), (0, dx.value), (2, grd[7]), (1, ws.value + 1024), (n - 1, g.value + 32), (4, grd[5] - 16)):
+        bad_grd = (C.c_void_p * n)(*grd)
+        bad_grd[i] = target                                       # a gradient on a parameter, grad_in, another gradient, the workspace, ...
+        refused_as_alias(x, g, dx, prm, bad_grd, ws)
+    assert call(x, inside(x, 16), dx, prm, grd, ws, need - 1, *a, 0, None) == -12      # inputs may overlap: refused for the workspace alone
 
 
 # ------------------------------------------------------------------------------------------ GPU
