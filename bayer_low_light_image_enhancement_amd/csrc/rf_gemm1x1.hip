@@ -41,6 +41,7 @@
 // attention / squeeze-excite matrices folded into the projection.
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 #include "rf_common.h"
 
 namespace rf {
@@ -655,46 +656,104 @@ __global__ void __launch_bounds__(PAIR ? 512 : 256, 2) conv1x1_b3_kernel(Conv1x1
 //   output tiles: the four waves load K / 4 channels each, reduce the two-pass statistics through LDS, write the three
 //   bf16 pieces of the normalised tile to LDS in B-operand order ([K block][pixel q][piece][lane], 12 KB per 32 channels),
 //   and then split the OUTPUT tiles: wave w computes tiles [w tpw, (w + 1) tpw) in chunks of NCO, reading the shared B
-//   pieces from LDS (once per chunk) and its A pieces straight from L2 (each weight element is used by exactly one wave of
-//   the workgroup), double-buffered one K block ahead.
+//   pieces from LDS (double-buffered per K block) and its A pieces straight from L2 (each weight element is used by exactly
+//   one wave of the workgroup).
+//
+//   Inside the pixel-tile loop no wait at the START of a chunk covers an output store, and no wait of the GEMM phase the
+//   next tile's input.  With the one in-order vmcnt that takes three things:
+//   * every load is OLDER than the stores that follow it.  A chunk's stores come last in the chunk; ahead of them go the A
+//     pieces of the first RING - 1 steps of the NEXT chunk (after a tile's last chunk: of the next tile's first chunk, the
+//     same weights), into the ring registers the finished chunk has vacated, and, in the tile's last chunk, the next
+//     tile's x (behind the chunk's last A load, so no wait for a ring slot covers it either).  A wave whose output tiles
+//     are ONE chunk (RESIDENT: tpw == NCO at K = 64, every level-1 launch) keeps the A pieces of all KB NCO steps in
+//     registers for all its pixel tiles instead, and its tile loop has x loads and stores only.  What one in-order counter
+//     leaves: a ring load issued INSIDE a chunk is younger than the stores of the chunk before, so from step RING - 1 on a
+//     chunk's waits cover those stores, RING - 1 steps after they were issued.
+//   * the loop holds no other load: gamma and beta sit in registers from before the loop (not at K = 128, see LNREG).
+//   * the stores are straight-line code.  A store under a lane condition is a block hipcc may branch around, and at the
+//     join its wait counts assume the path without the store: every later wait for an older load then drains the stores
+//     as well.  So every lane stores: the lanes past the end of a ragged last tile carry the tile's FIRST pixel group
+//     (the same loads, the same arithmetic, the same bits as lanes j = 0) and store it to the same addresses in the same
+//     instruction.  For the same reason the load of the next tile's x is unconditional: behind the last tile it reads 16
+//     bytes at the start of the image per instruction.
+//   The listing is the proof, not the source order (tools/loop_waits.py; profiles/b3ln_waits.md).
 // ---------------------------------------------------------------------------------------------
-template <int KB, int NCO>
-__global__ void __launch_bounds__(256, KB <= 4 ? 2 : 1) conv1x1_b3_ln_kernel(Conv1x1Args a, int tpw) {
-    __shared__ __attribute__((aligned(16))) u32x4 Bl[KB * 768];
-    __shared__ __attribute__((aligned(16))) float red[2 * 4 * 64];
-    __shared__ float bias_l[1024];
+template <int KB, int NCO, bool RESIDENT>
+__device__ __forceinline__ void b3_ln_tiles(const Conv1x1Args& a, const int tpw, u32x4* __restrict__ Bl, float* __restrict__ red,
+                                            const float* __restrict__ bias_l) {
     constexpr int KPW = KB >= 4 ? KB / 4 : 1; // K blocks each wave loads ...
     constexpr int CPT = KB >= 4 ? 8 : 4;      // ... and channels of a block per lane: K = 64 splits each block over two waves
     constexpr int K = 32 * KB;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // A pieces straight from L2: RESIDENT all STEPS (K block, tile) steps of the wave's one chunk; otherwise a ring of RING
+    // steps, a step's three 16-byte loads issued RING - 1 steps (x 24 MFMAs = 408 cycles each) before their use
+    constexpr int STEPS = KB * NCO, RING = RESIDENT ? STEPS : KB > 4 ? 12 : (STEPS < 5 ? STEPS : 5);
+    constexpr int AHEAD = RESIDENT ? STEPS : RING - 1;       // steps whose A pieces are loaded before their chunk begins
+    // the step of a tile's last chunk at which the next tile's x is loaded: behind the chunk's last A load -- except <4, 3>, two
+    // workgroups per CU with 60 ring and 96 B-piece registers: there x waits for the last K block, whose steps leave the
+    // other B buffer free
+    constexpr int XSTEP = (KB == 4 && NCO == 3) ? STEPS - NCO : STEPS - RING;
+    // The wave index lives in a scalar register, so every address below is (scalar base) + (ONE per-lane offset that the tile
+    // loop computes where it is used): left per-lane, each row and weight address is a loop-invariant register pair that
+    // hipcc hoists out of the tile loop, and together they do not fit next to the ring.
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 15, kq = lane >> 4;
     const int b = blockIdx.y, P = a.P;
     const int NT = a.Cout >> 4;
     const int ntile = (P + 63) >> 6;
+    const int tw0 = ((int)blockIdx.z * 4 + wave) * tpw;                   // this wave's first output tile (blockIdx.z: output-channel split of small launches)
     const float* xb = a.x1 + (size_t)b * a.x1_bstride;
-    const u32x4* wp3 = reinterpret_cast<const u32x4*>(reinterpret_cast<const float*>(a.wp3) + (size_t)b * a.wp3_bstride) + lane;
-    for (int i = tid; i < a.Cout; i += 256) bias_l[i] = a.bias ? a.bias[i] : 0.f;
+    float* outb = a.out + (size_t)b * a.out_bstride;
+    const char* wp3 = reinterpret_cast<const char*>(reinterpret_cast<const float*>(a.wp3) + (size_t)b * a.wp3_bstride);
+    const unsigned aoff = 16u * (unsigned)lane;                           // the lane's 16 bytes of a 64-lane weight piece
 
     // ---- input tile: wave w holds K blocks [w KPW, (w + 1) KPW), lane (j, kq) channels 8 kq .. 8 kq + 7 of each, 4 pixels.
-    // Persistent over pixel tiles: the next tile's loads are issued as soon as this one is split, i.e. behind its whole GEMM
-    // (without that the kernel ran at HBM time + MFMA time: all workgroups load, then all multiply).
+    // Persistent over pixel tiles with the next tile's x in flight behind the GEMM of this one (without that the kernel ran
+    // at HBM time + MFMA time: all workgroups load, then all multiply).
     const int kb0 = KB >= 4 ? wave * KPW : wave >> 1;                     // this wave's first K block
-    const int cbase = KB >= 4 ? 8 * kq : 8 * kq + 4 * (wave & 1);         // first of the lane's CPT channels inside a block
+    const int cwave = KB >= 4 ? 0 : 4 * (wave & 1);                       // the wave's part of ...
+    const int cbase = 8 * kq + cwave;                                     // ... the first of the lane's CPT channels inside a block
     float4 xr[KPW][CPT];
-    auto load_x = [&](int tile) {
+    auto load_x = [&](int tile, bool exists) {      // lanes past the end of the image take the tile's first pixel group
         const int q0 = tile * 64 + 4 * j;
-        const unsigned ql = (unsigned)(q0 < P ? q0 : 0);
+        size_t xoff = exists ? (size_t)(8 * kq) * (size_t)P + (size_t)(q0 < P ? q0 : tile * 64) : (size_t)0;
+        asm volatile("" : "+v"(xoff));              // computed here, once per tile
 #pragma unroll
         for (int i = 0; i < KPW; ++i)
 #pragma unroll
-            for (int c = 0; c < CPT; ++c) xr[i][c] = ldv(xb, (unsigned)(32 * (kb0 + i) + cbase + c) * (unsigned)P + ql);
+            for (int c = 0; c < CPT; ++c) xr[i][c] = *reinterpret_cast<const float4*>(xb + (size_t)(32 * (kb0 + i) + cwave + c) * (size_t)P + xoff);
     };
-    constexpr bool PREF = KB != 4;         // K = 128 runs two workgroups per CU with 48 B-piece registers: none left for a tile in flight
-    if (PREF) load_x(blockIdx.x);
+    u32x4 A[RING][3];
+    auto load_a = [&](int slot, int step, int t0) {
+        const int kb = step / NCO, t = step - kb * NCO;
+#pragma unroll
+        for (int pc = 0; pc < 3; ++pc)
+            A[slot][pc] = *reinterpret_cast<const u32x4*>(wp3 + (((size_t)kb * NT + t0 + t) * 192 + pc * 64) * 16 + aoff);
+    };
+    load_x(blockIdx.x, true);
+#pragma unroll
+    for (int i = 0; i < AHEAD; ++i) load_a(i, i, tw0);
+    // gamma and beta of the lane's channels, in registers for all tiles -- except at K = 128, where 16 more registers next
+    // to the ring spill: there every tile loads them again after its statistics, and THAT wait covers the stores of the
+    // tile before (issued two barriers earlier)
+    constexpr bool LNREG = KB != 4;
+    float gam[LNREG ? KPW : 1][CPT], bet[LNREG ? KPW : 1][CPT];
+    if constexpr (LNREG) {
+#pragma unroll
+        for (int i = 0; i < KPW; ++i)
+#pragma unroll
+            for (int c = 0; c < CPT; ++c) {
+                const int k = 32 * (kb0 + i) + cbase + c;
+                gam[i][c] = a.ln_w[k];
+                bet[i][c] = a.ln_b ? a.ln_b[k] : 0.f;
+            }
+    }
+    __builtin_amdgcn_s_waitcnt(0x0F70);    // vmcnt(0): the loop is entered with nothing of the prologue pending, as from its own back edge
+
     for (int tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
-    if (!PREF) load_x(tile);
-    const int p0 = tile * 64 + 4 * j;
-    const bool live = p0 < P;
+    const int tnext = tile + (int)gridDim.x;
+    const bool more = tnext < ntile;
+    const int q0 = tile * 64 + 4 * j;
+    const int p0 = q0 < P ? q0 : tile * 64;
     // two-pass statistics: lanes, then waves (fixed order)
     float mean[4], rstd[4];
     {
@@ -738,8 +797,8 @@ __global__ void __launch_bounds__(256, KB <= 4 ? 2 : 1) conv1x1_b3_ln_kernel(Con
 #pragma unroll
         for (int hp = 0; hp < CPT / 2; ++hp) {
             const int k = 32 * kb + cbase + 2 * hp;
-            const float ga = a.ln_w[k], gb = a.ln_w[k + 1];
-            const float ba = a.ln_b ? a.ln_b[k] : 0.f, bb = a.ln_b ? a.ln_b[k + 1] : 0.f;
+            const float ga = LNREG ? gam[LNREG ? i : 0][2 * hp] : a.ln_w[k], gb = LNREG ? gam[LNREG ? i : 0][2 * hp + 1] : a.ln_w[k + 1];
+            const float ba = LNREG ? bet[LNREG ? i : 0][2 * hp] : a.ln_b ? a.ln_b[k] : 0.f, bb = LNREG ? bet[LNREG ? i : 0][2 * hp + 1] : a.ln_b ? a.ln_b[k + 1] : 0.f;
             const float xa[4] = {xr[i][2 * hp].x, xr[i][2 * hp].y, xr[i][2 * hp].z, xr[i][2 * hp].w};
             const float xc[4] = {xr[i][2 * hp + 1].x, xr[i][2 * hp + 1].y, xr[i][2 * hp + 1].z, xr[i][2 * hp + 1].w};
 #pragma unroll
@@ -758,27 +817,18 @@ __global__ void __launch_bounds__(256, KB <= 4 ? 2 : 1) conv1x1_b3_ln_kernel(Con
             }
     }
     __syncthreads();
-    if (PREF && tile + (int)gridDim.x < ntile) load_x(tile + gridDim.x);
+    if constexpr (RESIDENT) load_x(tnext, more);
+    unsigned soff = 4u * ((unsigned)(4 * kq) * (unsigned)P + (unsigned)p0);     // channel 4 kq of an output tile, the lane's pixels: bytes
+    asm volatile("" : "+v"(soff));
 
-    // ---- output tiles of this wave, NCO at a time
-    for (int chunk = 0; chunk * NCO < tpw; ++chunk) {
-        const int t0 = ((int)blockIdx.z * 4 + wave) * tpw + chunk * NCO;    // blockIdx.z: output-channel split of small launches
+    // ---- output tiles of this wave, one chunk of NCO at a time; LAST: the tile's last chunk, which also fetches for the next tile
+    auto run_chunk = [&](const int t0, auto last_chunk) {
+        constexpr bool LAST = decltype(last_chunk)::value;
         f32x4 acc[NCO][4];
 #pragma unroll
         for (int t = 0; t < NCO; ++t)
 #pragma unroll
             for (int g = 0; g < 4; ++g) acc[t][g] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        // A pieces straight from L2, in a ring of RING (K block, tile) steps: a step's three 16-byte loads are issued
-        // RING - 1 steps (x 24 MFMAs = 408 cycles each) before their use.
-        constexpr int STEPS = KB * NCO, RING = KB > 4 ? 12 : (STEPS < 5 ? STEPS : 5);
-        u32x4 A[RING][3];
-        auto load_a = [&](int slot, int step) {
-            const int kb = step / NCO, t = step - kb * NCO;
-#pragma unroll
-            for (int pc = 0; pc < 3; ++pc) A[slot][pc] = wp3[((size_t)kb * NT + t0 + t) * 192 + pc * 64];
-        };
-#pragma unroll
-        for (int i = 0; i < RING - 1; ++i) load_a(i, i);
         // B pieces from LDS, double-buffered per K block: the 12 reads of block kb + 1 are spread over the NCO steps of block kb
         u32x4 bp[2][4][3];
         auto load_b = [&](int buf, int kb, int first, int last) {
@@ -789,14 +839,60 @@ __global__ void __launch_bounds__(256, KB <= 4 ? 2 : 1) conv1x1_b3_ln_kernel(Con
 #pragma unroll
         for (int step = 0; step < STEPS; ++step) {
             const int kb = step / NCO, t = step % NCO;
-            if (step + RING - 1 < STEPS) load_a((step + RING - 1) % RING, step + RING - 1);
+            if constexpr (!RESIDENT) {
+                if (step + RING - 1 < STEPS) load_a((step + RING - 1) % RING, step + RING - 1, t0);
+                if (LAST && step == XSTEP) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    load_x(tnext, more);
+                }
+            }
             if (kb + 1 < KB) load_b((kb + 1) & 1, kb + 1, 12 * t / NCO, 12 * (t + 1) / NCO);
             b3_mfma4(A[step % RING], bp[kb & 1], acc[t]);
             __builtin_amdgcn_sched_barrier(0);      // keep the ring: without it hipcc hoists every load to the top and spills
         }
-        epilogue<NCO, false>(a, acc, t0, NCO, bias_l + 16 * t0, nullptr, b, p0, kq, live);
-    }
+        if constexpr (!RESIDENT) {                  // loads before stores: the ring and both B buffers are dead here
+#pragma unroll
+            for (int i = 0; i < RING - 1; ++i) load_a(i, i, LAST ? tw0 : t0 + NCO);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // the stores (epilogue<NCO, false>'s arithmetic in mode 0; every channel exists: Cout % 64 == 0), every lane, straight-line:
+        // the row in scalar registers + the lane's byte offset (at most 52 P: plan_conv1x1 keeps 64 P below 4e9)
+#pragma unroll
+        for (int t = 0; t < NCO; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float bs = bias_l[16 * (t0 + t) + 4 * kq + r];
+                float v[4] = {acc[t][0][r] + bs, acc[t][1][r] + bs, acc[t][2][r] + bs, acc[t][3][r] + bs};
+                if (a.act == 1 || a.act == 3) {
+                    const float slope = a.act == 1 ? 0.2f : 0.1f;
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) v[g] = v[g] > 0.f ? v[g] : slope * v[g];
+                } else if (a.act == 2) {
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) v[g] = fmaxf(v[g], 0.f);
+                } else if (a.act == 4) {
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) v[g] = fminf(fmaxf(v[g], 0.f), 1e4f);
+                }
+                *reinterpret_cast<float4*>(reinterpret_cast<char*>(outb + (size_t)(16 * (t0 + t) + r) * (size_t)P) + soff) = make_float4(v[0], v[1], v[2], v[3]);
+            }
+    };
+    if constexpr (!RESIDENT)
+        for (int t0 = tw0; t0 + NCO < tw0 + tpw; t0 += NCO) run_chunk(t0, std::false_type{});
+    run_chunk(tw0 + tpw - NCO, std::true_type{});
     }   // pixel tiles (the first barrier of the next tile's statistics also frees Bl)
+}
+
+template <int KB, int NCO>
+__global__ void __launch_bounds__(256, KB <= 4 ? 2 : 1) conv1x1_b3_ln_kernel(Conv1x1Args a, int tpw) {
+    __shared__ __attribute__((aligned(16))) u32x4 Bl[KB * 768];
+    __shared__ __attribute__((aligned(16))) float red[2 * 4 * 64];
+    __shared__ float bias_l[1024];
+    for (int i = threadIdx.x; i < a.Cout; i += 256) bias_l[i] = a.bias ? a.bias[i] : 0.f;
+    if constexpr (KB == 2) {     // tpw is wave-uniform (a kernel argument)
+        if (tpw == NCO) return b3_ln_tiles<KB, NCO, true>(a, tpw, Bl, red, bias_l);
+    }
+    b3_ln_tiles<KB, NCO, false>(a, tpw, Bl, red, bias_l);
 }
 
 // ---------------------------------------------------------------------------------------------
