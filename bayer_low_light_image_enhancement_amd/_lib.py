@@ -106,6 +106,11 @@ SIGNATURES = {
     "rf_luma_film": (_i, [_vp, _vp, _vp, C.c_longlong, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "rf_dwgate3x3": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "rf_dwconv5x5": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "rf_wfb_ffn_nblk": (_i, [_i, _i]),
+    "rf_wfb_ffn_train_workspace_bytes": (C.c_longlong, [_i, _i, _i, _i, _i]),
+    "rf_wfb_ffn_train_forward": (_i, [_vp, _vp, C.POINTER(_vp), _vp, _vp, _sz, _i, _i, _i, _i, _i, _f, _f, _i, _vp]),
+    "rf_wfb_ffn_backward_workspace_bytes": (C.c_longlong, [_i, _i, _i, _i, _i]),
+    "rf_wfb_ffn_backward": (_i, [_vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _sz, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
     "rf_rfft2_polar_scratch_bytes": (_i, [_i, _i, _i, _psz]),
     "rf_rfft2_polar": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "rf_polar_irfft2": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

@@ -57,11 +57,12 @@ struct BackwardArgs {
     const float* const* prm; float* const* grad_prm; // n tensors each
     int n;
     const void* workspace; size_t workspace_bytes, need_bytes;
+    const Span* buffers = nullptr; int nbuffers = 0; // what the call reads besides (BatchNorm's running statistics): no gradient
 };
 // In this order: in, grad_out, grad_in, prm, grad_prm and workspace non-null and (the arrays apart) 16-byte aligned; the workspace
 // large enough (RF_E_NOMEM); no null tensor; then, with prm_floats(i) the floats of tensor i: everything the call writes (grad_in,
-// the n gradients, need_bytes of workspace) disjoint from everything it reads (in, grad_out, the n parameters) and from everything
-// else it writes.  Inputs may overlap each other.  Nothing is dereferenced but the two pointer arrays.
+// the n gradients, need_bytes of workspace) disjoint from everything it reads (in, grad_out, the n parameters, the buffers) and
+// from everything else it writes.  Inputs may overlap each other.  Nothing is dereferenced but the two pointer arrays.
 int check_backward_args(const BackwardArgs& c, const std::function<size_t(int)>& prm_floats);
 
 }  // namespace rf

@@ -200,7 +200,9 @@ int check_backward_args(const BackwardArgs& c, const std::function<size_t(int)>&
         return RF_E_NOMEM;
     }
     for (int i = 0; i < n; ++i) RF_CHECK_ARG(c.prm[i] != nullptr && c.grad_prm[i] != nullptr, "%s: parameter or gradient %d is null", c.who, i);
+    for (int i = 0; i < c.nbuffers; ++i) RF_CHECK_ARG(c.buffers[i].p != nullptr, "%s: buffer %d is null", c.who, i);
     std::vector<Span> outs(n + 2), ins(n + 2);              // tensors 0 .. n - 1, then grad_in | in, then the workspace | grad_out
+    ins.insert(ins.end(), c.buffers, c.buffers + c.nbuffers);      // ... and the read-only buffers behind the inputs
     for (int i = 0; i < n; ++i) {
         const size_t bytes = prm_floats(i) * sizeof(float);
         outs[i] = {c.grad_prm[i], bytes};
@@ -211,7 +213,9 @@ int check_backward_args(const BackwardArgs& c, const std::function<size_t(int)>&
     ins[n] = {c.in, c.plane_bytes};
     ins[n + 1] = {c.grad_out, c.plane_bytes};
     int a, b;
-    const int hit = first_alias(outs.data(), n + 2, ins.data(), n + 2, &a, &b);
+    const int hit = first_alias(outs.data(), n + 2, ins.data(), n + 2 + c.nbuffers, &a, &b);
+    RF_CHECK_ARG(hit != 1 || b < n + 2, "%s: an output (gradient %d; %d = grad_in, %d = workspace) may not alias read-only buffer %d", c.who, a, n, n + 1,
+                 b - n - 2);
     RF_CHECK_ARG(hit != 1, "%s: an output (gradient %d; %d = grad_in, %d = workspace) may not alias an input (parameter %d; %d = in, %d = grad_out)",
                  c.who, a, n, n + 1, b, n, n + 1);
     RF_CHECK_ARG(hit != 2, "%s: outputs may not alias each other (gradients %d and %d; %d = grad_in, %d = workspace)", c.who, a, b, n, n + 1);

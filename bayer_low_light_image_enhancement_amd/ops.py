@@ -780,11 +780,13 @@ def polar_irfft2_backward(mag: torch.Tensor, pha: torch.Tensor, grad_out: torch.
     return grad_mag, grad_pha
 
 
-def _backward(name, keys, shapes, x, params, grad_out, prefix, grads, geometry, trailing=()):
+def _backward(name, keys, shapes, x, params, grad_out, prefix, grads, geometry, trailing=(), buffers=()):
     """What the ``*_backward`` wrappers share, ``x`` and ``grad_out`` checked by the caller: ``params`` and ``grads`` against
     ``shapes``, the workspace ``rf_<name>_backward_workspace_bytes(*geometry)`` asks for, and the call
-    ``rf_<name>_backward(x, grad_out, grad_x, params, grads, workspace, bytes, *geometry, *trailing, accumulate, stream)``."""
+    ``rf_<name>_backward(x, grad_out, grad_x, params, grads, workspace, bytes, *geometry, *trailing, accumulate, stream)``.
+    ``buffers``: keys of ``shapes`` that the operator reads behind its parameters and that have no gradient."""
     ts = _shaped(params, prefix, keys, shapes, f"{name}_backward")
+    read = ts + _shaped(params, prefix, buffers, shapes, f"{name}_backward")
     accumulate = grads is not None
     if grads is None:
         grads = {prefix + k: torch.empty_like(t) for k, t in zip(keys, ts)}
@@ -796,7 +798,7 @@ def _backward(name, keys, shapes, x, params, grad_out, prefix, grads, geometry, 
     ws = _workspace(query(*geometry), f"rf_{name}_backward_workspace_bytes", x)
     grad_x = torch.empty_like(x)
     with torch.cuda.device(x.device):
-        _lib.check(call(_ptr(x), _ptr(grad_out), _ptr(grad_x), _ptr_array(ts), _ptr_array(gs), _ptr(ws), ws.numel(), *geometry, *trailing,
+        _lib.check(call(_ptr(x), _ptr(grad_out), _ptr(grad_x), _ptr_array(read), _ptr_array(gs), _ptr(ws), ws.numel(), *geometry, *trailing,
                         int(accumulate), _stream(x)), f"rf_{name}_backward")
     return grad_x, grads
 
@@ -821,6 +823,78 @@ def ffab_backward(x: torch.Tensor, params, grad_out: torch.Tensor, prefix: str =
     """The gradient of ``ffab``: ``(grad_x, grads)`` for ``grad_out`` = dL/d ``ffab(x, params)``, with ``feb_backward``'s contract and
     the 92 keys of ``ffab_param_shapes``."""
     return _block_backward("ffab", _FFAB_KEYS, ffab_param_shapes, x, params, grad_out, prefix, grads)
+
+
+_WFB_FF_KEYS = ("project_in.weight", "project_in.bias", "dwconv.weight", "dwconv.bias", "project_out.weight", "project_out.bias",
+                "rep_conv1.c.weight", "rep_conv1.bn.weight", "rep_conv1.bn.bias", "rep_conv2.c.weight", "rep_conv2.bn.weight", "rep_conv2.bn.bias")
+_WFB_FF_BUFFERS = ("rep_conv1.bn.running_mean", "rep_conv1.bn.running_var", "rep_conv2.bn.running_mean", "rep_conv2.bn.running_var")
+
+
+def wfb_ff_param_shapes(dim: int, hidden: int):
+    """Names and shapes of the 12 parameters of the WFB ``FeedForward`` and, behind them, of the 4 BatchNorm buffers the operators
+    below read or update, in the order of the C ABI's pointer array.  The gradients are those of the first 12."""
+    shapes = {"project_in.weight": (hidden, dim, 1, 1), "project_in.bias": (hidden,), "dwconv.weight": (hidden, 1, 3, 3), "dwconv.bias": (hidden,),
+              "project_out.weight": (dim, hidden, 1, 1), "project_out.bias": (dim,)}
+    for name, k in (("rep_conv1", 3), ("rep_conv2", 1)):
+        shapes.update({f"{name}.c.weight": (hidden, 1, k, k), f"{name}.bn.weight": (hidden,), f"{name}.bn.bias": (hidden,)})
+    shapes.update({k: (hidden,) for k in _WFB_FF_BUFFERS})
+    return shapes
+
+
+def _wfb_ff_geometry(x, params, prefix, who):
+    x = _chk(x, "x")
+    if x.dim() != 4:
+        raise RuntimeError(f"{who}: expected a 4-D x, got {tuple(x.shape)}")
+    b, dim, h, w = x.shape
+    return x, (b, dim, params[prefix + "project_in.weight"].shape[0], h, w)
+
+
+def wfb_feed_forward_train(x: torch.Tensor, params, prefix: str = "", eps: float = 1e-5, momentum: float = 0.1,
+                           update_running_stats: bool = True, batch_stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``FeedForward.forward`` under ``train()`` (RawFomer_WFB_FFAB/model.py:42-62): the two ``Conv2d_BN`` branches normalise with
+    the statistics of the batch (mean and biased variance over ``(B, h, w)``), which ``wfb_feed_forward``'s eval-mode fold cannot
+    express.  With ``update_running_stats`` the four ``running_mean`` / ``running_var`` tensors of ``params`` are updated IN PLACE as
+    ``nn.BatchNorm2d`` does (momentum, unbiased variance; they must be contiguous float32 device tensors), and
+    ``num_batches_tracked`` is incremented where ``params`` holds it.  ``batch_stats``: a contiguous float32 ``[4, hidden]`` tensor that
+    receives ``mu1, v1, mu2, v2``.  Refused where torch raises: fewer than two values per channel."""
+    x, geo = _wfb_ff_geometry(x, params, prefix, "wfb_feed_forward_train")
+    hidden = geo[2]
+    shapes = wfb_ff_param_shapes(geo[1], hidden)
+    ts = _shaped(params, prefix, _WFB_FF_KEYS + _WFB_FF_BUFFERS, shapes, "wfb_feed_forward_train")
+    if update_running_stats and any(t.data_ptr() != params[prefix + k].data_ptr() for k, t in zip(_WFB_FF_BUFFERS, ts[len(_WFB_FF_KEYS):])):
+        raise RuntimeError("wfb_feed_forward_train: the running statistics must be contiguous (they are updated in place)")
+    if batch_stats is None:
+        batch_stats = torch.empty((4, hidden), dtype=torch.float32, device=x.device)
+    elif (tuple(batch_stats.shape) != (4, hidden) or not batch_stats.is_contiguous() or batch_stats.dtype != torch.float32
+          or batch_stats.device != x.device):
+        raise RuntimeError(f"wfb_feed_forward_train: `batch_stats` must be a contiguous float32 tensor of shape {(4, hidden)} on {x.device}")
+    lib = _lib.load()
+    ws = _workspace(lib.rf_wfb_ffn_train_workspace_bytes(*geo), "rf_wfb_ffn_train_workspace_bytes", x)
+    out = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.rf_wfb_ffn_train_forward(_ptr(x), _ptr(out), _ptr_array(ts), _ptr(batch_stats), _ptr(ws), ws.numel(), *geo, float(eps),
+                                                float(momentum), int(update_running_stats), _stream(x)), "rf_wfb_ffn_train_forward")
+        if update_running_stats:
+            for name in ("rep_conv1", "rep_conv2"):
+                nbt = params.get(f"{prefix}{name}.bn.num_batches_tracked")
+                if nbt is not None:
+                    nbt += 1
+    return out
+
+
+def wfb_feed_forward_backward(x: torch.Tensor, params, grad_out: torch.Tensor, prefix: str = "", grads=None, training: bool = True,
+                              eps: float = 1e-5):
+    """The gradient of ``wfb_feed_forward_train`` (``training=True``: through the batch statistics) or of the eval-mode
+    ``wfb_feed_forward`` (``training=False``: the running statistics are constants): ``(grad_x, grads)`` for ``grad_out`` = dL/d out.
+    ``grads`` maps the 12 parameter keys of ``wfb_ff_param_shapes`` (``prefix`` included) to gradients of the parameters' shapes.
+    Passing the ``grads`` of an earlier call ADDS to its tensors; ``grad_x`` is always a new tensor.  The forward intermediates and
+    the batch statistics are recomputed: nothing is kept from a forward call, and ``x``, ``grad_out`` and ``params`` are not written."""
+    x, geo = _wfb_ff_geometry(x, params, prefix, "wfb_feed_forward_backward")
+    grad_out = _chk(grad_out, "grad_out")
+    if tuple(grad_out.shape) != tuple(x.shape):
+        raise RuntimeError(f"wfb_feed_forward_backward: expected x and grad_out of one shape, got {tuple(x.shape)} and {tuple(grad_out.shape)}")
+    return _backward("wfb_ffn", _WFB_FF_KEYS, wfb_ff_param_shapes(geo[1], geo[2]), x, params, grad_out, prefix, grads, geo,
+                     (int(training), float(eps)), _WFB_FF_BUFFERS)
 
 
 def wmb(x: torch.Tensor, params, prefix: str = "") -> torch.Tensor:

@@ -396,6 +396,39 @@ int rf_dwgate3x3(const float* in, float* out, const float* wa, const float* ba, 
 /* nn.Conv2d(C, C, 5, padding=2, groups=C) (+bias): Illumination_Estimator.depth_conv (model.py:182-183) */
 int rf_dwconv5x5(const float* in, float* out, const float* weight, const float* bias, int B, int C, int h, int w, void* stream);
 
+/* ---- the gated FeedForward in TRAINING mode and its gradient (RawFomer_WFB_FFAB/model.py:42-65; csrc/rf_wfb_train.hip) --------
+ * in, out [B,dim,h,w]; hidden = project_in's output channels.  prm = HOST array of 16 device pointers: the 12 parameters
+ *   project_in.{weight,bias}, dwconv.{weight,bias}, project_out.{weight,bias}, rep_conv1.c.weight, rep_conv1.bn.{weight,bias},
+ *   rep_conv2.c.weight, rep_conv2.bn.{weight,bias}
+ * then the 4 buffers rep_conv1.bn.running_{mean,var}, rep_conv2.bn.running_{mean,var}.
+ * rf_wfb_ffn_train_forward: FeedForward.forward under train(): both Conv2d_BN branches normalise with the mean and the BIASED
+ *   variance of their convolution's output over (B, h, w), N = B h w values per channel.  batch_stats [4][hidden] receives
+ *   mu1, v1, mu2, v2.  update_running != 0 also updates the four buffers as nn.BatchNorm2d does (running <- (1 - momentum) running
+ *   + momentum new, the variance UNBIASED, v N / (N - 1)); 0 leaves them unwritten (num_batches_tracked is the caller's).  The
+ *   statistics are summed around a per-channel pivot, so the variance survives |mean| >> std, and folded on the device into the
+ *   weights of rf_dwgate3x3: no host synchronisation.
+ * rf_wfb_ffn_backward: (in, grad_out = dL/d out, prm) -> grad_in = dL/d in and grad_prm, a HOST array of 12 device pointers with the
+ *   order and shapes of the 12 parameters.  training != 0: the gradient of rf_wfb_ffn_train_forward, through the batch statistics
+ *   (the buffers are not read); 0: the gradient of the eval-mode forward on the running statistics (what rf_dwgate3x3 computes on
+ *   FeedForward.fuse()'s weights).  Nothing is kept from a forward call: the intermediates and the statistics are recomputed.
+ *   grad_in is always overwritten; accumulate != 0 ADDS to the 12 grad_prm tensors, 0 overwrites them.
+ * Conventions of rf_wm_backward: a *_bytes query returns a negative error code for a geometry the operator refuses; refusals come
+ * before any launch, -22 with an rf_last_error message that starts with the entry point's name: dim % 4 != 0, hidden % 4 != 0,
+ * non-positive sizes, training mode with B h w < 2 (torch raises too), null or misaligned pointers (16 bytes: in, out, grad_out,
+ * grad_in, batch_stats, workspace), and any byte range the call writes (out / grad_in, batch_stats, the gradients, the workspace, the
+ * buffers of an updating forward) overlapping anything it reads or anything else it writes; a workspace smaller than the query's
+ * answer is refused with -12.  Inputs and parameters are not written.  Every sum over pixels goes through per-workgroup slabs added
+ * in a fixed order (no float atomics): two runs give the same bits.
+ * rf_wfb_ffn_nblk: the slabs per image and channel of those sums for an h x w plane (one per 256 tiles of 4 x 4 pixels, at most 32). */
+int rf_wfb_ffn_nblk(int h, int w);
+long long rf_wfb_ffn_train_workspace_bytes(int B, int dim, int hidden, int h, int w);
+int rf_wfb_ffn_train_forward(const float* in, float* out, float* const* prm, float* batch_stats, void* workspace, size_t workspace_bytes,
+                             int B, int dim, int hidden, int h, int w, float eps, float momentum, int update_running, void* stream);
+long long rf_wfb_ffn_backward_workspace_bytes(int B, int dim, int hidden, int h, int w);
+int rf_wfb_ffn_backward(const float* in, const float* grad_out, float* grad_in, const float* const* prm, float* const* grad_prm,
+                        void* workspace, size_t workspace_bytes, int B, int dim, int hidden, int h, int w, int training, float eps,
+                        int accumulate, void* stream);
+
 /* ---- Mamba selective scan and the WM block (RawFomer_WFB_FFAB/model.py:138-172): inference, and Mamba's gradient -------------------
  * mamba_ssm.modules.mamba_simple.Mamba(d_model, d_state, d_conv, expand).forward with the module's defaults
  * (dt_rank = ceil(d_model / 16), no projection biases, conv1d bias).  Di = expand * d_model, R = dt_rank.
