@@ -142,7 +142,18 @@ SIGNATURES = {
     "rf_wmb_front": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "rf_wmb_back": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "rf_wmb_ffn_sum": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "rf_tc_spatial": (_i, [_vp] * 9 + [_i, _i, _i, _i, _vp]),
+    "rf_wmb_front_backward_nblk": (_i, [_i, _i, _i, _i]),
+    "rf_wmb_front_backward_workspace_bytes": (C.c_longlong, [_i, _i, _i, _i]),
+    "rf_wmb_front_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _f, _i, _vp]),
+    "rf_wmb_back_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "rf_dwconv5x5_backward_nblk": (_i, [_i, _i]),
+    "rf_dwconv5x5_backward_workspace_bytes": (C.c_longlong, [_i, _i, _i, _i]),
+    "rf_dwconv5x5_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp]),
+    "rf_illumination_estimator_backward_workspace_bytes": (C.c_longlong, [_i, _i, _i, _i, _i, _i, _i]),
+    "rf_illumination_estimator_backward": (_i, [_vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "rf_layernorm2d_backward_workspace_bytes": (C.c_longlong, [_i, _i, _i, _i]),
+    "rf_layernorm2d_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _f, _i, _vp]),
+    "rf_tc_spatial":(_i, [_vp] * 9 + [_i, _i, _i, _i, _vp]),
     "rf_tc_nblk": (_i, [_i, _i]),
     "rf_tc_residual": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "rf_tc_color_head": (_i, [_vp] * 10 + [_i, _sz, _vp]),

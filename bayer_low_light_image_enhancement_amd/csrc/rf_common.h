@@ -610,4 +610,12 @@ int launch_wmb_ffn_tail(const float* t, const float* y, float* out, const float*
 int launch_wmb_fold(const float* ln_w, const float* ln_b, float* ln2, const float* rep1_w, const float* const* bn1, const float* rep2_w,
                     const float* const* bn2, float* rep_w, float* rep_b, const float* illu_w, float* illu_fold, int C, int hid, hipStream_t st);
 
+// ---- the adjoints of the front and back pass (rf_wmb_bwd.hip).  front: dx = the LayerNorm adjoint of g = gt + iwt_init(gb) (g is
+// never stored); partial [B * wmb_front_bwd_nblk][2][C]: the slabs of d w2 and d b2 times gscale, for reduce_rows.  back:
+// gbands = dwt_init(m go / 2), m the forward's clamp mask recomputed from bands
+int wmb_front_bwd_nblk(int B, int C, int h, int w);
+int launch_wmb_front_bwd(const float* x, const float* gt, const float* gb, const float* gamma, float* dx, float* partial, float gscale, int B, int C,
+                         int h, int w, hipStream_t st);
+int launch_wmb_back_bwd(const float* bands, const float* go, float* gbands, int B, int C, int h, int w, hipStream_t st);
+
 }  // namespace rf

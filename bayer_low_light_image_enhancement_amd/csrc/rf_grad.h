@@ -10,6 +10,23 @@ namespace rf {
 // launch_reduce_rows inside a profiler bracket: out[e] (+)= sum over rows of partial[row][e]
 int reduce_rows(const float* partial, float* out, int nrows, size_t n, int accumulate, hipStream_t st);
 
+#ifdef __HIPCC__
+// s[k] <- the sum of s[k] over a workgroup of 256 threads, in a fixed order: lanes by shuffles, then the four waves.  What a kernel
+// calls before it writes its slab
+template <int N>
+__device__ __forceinline__ void block_sums(float (&s)[N], float* lds /* [N][4] */) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_xor(s[k], o, 64);
+        if ((threadIdx.x & 63) == 0) lds[k * 4 + (threadIdx.x >> 6)] = s[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < N; ++k) s[k] = (lds[k * 4] + lds[k * 4 + 1]) + (lds[k * 4 + 2] + lds[k * 4 + 3]);
+}
+#endif
+
 // ---- weight gradients.  `who` prefixes the refusal of a partial buffer that is too small; B images of P pixels (tokens)
 struct Wgrad { const char* who; float* partial; size_t cap; int B, P, acc; hipStream_t st; };
 

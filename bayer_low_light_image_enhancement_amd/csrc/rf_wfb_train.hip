@@ -86,20 +86,6 @@ __device__ __forceinline__ void store_row4(float* __restrict__ plane, int y, int
     }
 }
 
-// s[k] <- the workgroup's sum of s[k], in a fixed order: lanes by shuffles, then the four waves
-template <int N>
-__device__ __forceinline__ void block_sums(float (&s)[N], float* lds /* [N][4] */) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_xor(s[k], o, 64);
-        if ((threadIdx.x & 63) == 0) lds[k * 4 + (threadIdx.x >> 6)] = s[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; ++k) s[k] = (lds[k * 4] + lds[k * 4 + 1]) + (lds[k * 4 + 2] + lds[k * 4 + 3]);
-}
-
 // the tiles [lo, hi) of workgroup blockIdx.x among the plane's `tiles`
 __device__ __forceinline__ void tile_run(int tiles, int nblk, int* lo, int* hi) {
     const int per = (tiles + nblk - 1) / nblk;

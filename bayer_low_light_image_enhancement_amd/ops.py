@@ -938,6 +938,147 @@ def wmb_back(bands: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _grad_pair(grads, like, who):
+    """``(pair, accumulate)`` for a ``(grad_weight, grad_bias)`` pair: a new one, or the caller's own, which the call adds to."""
+    if grads is None:
+        return (torch.empty_like(like), torch.empty_like(like)), 0
+    for g in grads:
+        if _chk(g, "grads") is not g or tuple(g.shape) != tuple(like.shape):
+            raise RuntimeError(f"{who}: the tensors of grads must be contiguous (they are written in place) and of shape {tuple(like.shape)}")
+    return grads, 1
+
+
+def wmb_front_backward(x: torch.Tensor, weight2: torch.Tensor, bias2: torch.Tensor, grad_t: torch.Tensor, grad_bands: torch.Tensor,
+                       grad_scale: float = 1.0, grads=None):
+    """The gradient of ``wmb_front``: ``(grad_x, (grad_weight2, grad_bias2))`` for ``grad_t`` = dL/d ``t`` and ``grad_bands`` = dL/d ``bands``.
+    One pass: ``g = grad_t + iwt_init(grad_bands)`` (``dwt_init``'s transpose) stays in registers and goes through the LayerNorm
+    adjoint.  ``grad_scale`` multiplies the two parameter gradients: a block that passes ``weight2 = 2 w`` gets the gradient of ``w``
+    with ``grad_scale=2``.  Passing the ``grads`` pair of an earlier call ADDS to its tensors; ``grad_x`` is always a new tensor.
+    ``bias2`` does not enter the gradient and is only checked."""
+    x, weight2, bias2 = _chk(x, "x"), _chk(weight2, "weight2"), _chk(bias2, "bias2")
+    grad_t, grad_bands = _chk(grad_t, "grad_t"), _chk(grad_bands, "grad_bands")
+    b, c, h2, w2 = x.shape
+    if (h2 % 2 or w2 % 4 or weight2.numel() != c or bias2.numel() != c or tuple(grad_t.shape) != tuple(x.shape)
+            or tuple(grad_bands.shape) != (4 * b, c, h2 // 2, w2 // 2)):
+        raise RuntimeError(f"wmb_front_backward: x {tuple(x.shape)}, grad_t {tuple(grad_t.shape)}, grad_bands {tuple(grad_bands.shape)}: needs an "
+                           f"even height, a width in multiples of 4, {c} LayerNorm weights and the shapes wmb_front returns")
+    pair, acc = _grad_pair(grads, weight2, "wmb_front_backward")
+    gw, gb = pair
+    geo = (b, c, h2 // 2, w2 // 2)
+    lib = _lib.load()
+    ws = _workspace(lib.rf_wmb_front_backward_workspace_bytes(*geo), "rf_wmb_front_backward_workspace_bytes", x)
+    grad_x = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.rf_wmb_front_backward(_ptr(x), _ptr(grad_t), _ptr(grad_x), _ptr(grad_bands), _ptr(weight2), _ptr(gw), _ptr(gb), _ptr(ws),
+                                             ws.numel(), *geo, float(grad_scale), acc, _stream(x)), "rf_wmb_front_backward")
+    return grad_x, pair
+
+
+def wmb_back_backward(bands: torch.Tensor, grad_out: torch.Tensor) -> torch.Tensor:
+    """The gradient of ``wmb_back`` with respect to ``bands`` (the one with respect to ``t`` is ``grad_out`` itself):
+    ``dwt_init(m * grad_out / 2)`` with ``m = 1`` where the value before the clamp lies in [0, 1], as ``torch.clamp``'s backward."""
+    bands, grad_out = _chk(bands, "bands"), _chk(grad_out, "grad_out")
+    b4, c, h, w = bands.shape
+    if b4 % 4 or w % 2 or tuple(grad_out.shape) != (b4 // 4, c, 2 * h, 2 * w):
+        raise RuntimeError(f"wmb_back_backward: bands {tuple(bands.shape)} and grad_out {tuple(grad_out.shape)} do not belong together "
+                           "(band width must be even)")
+    grad_bands = torch.empty_like(bands)
+    with torch.cuda.device(bands.device):
+        _lib.check(_lib.load().rf_wmb_back_backward(_ptr(bands), _ptr(grad_out), _ptr(grad_bands), b4 // 4, c, h, w, _stream(bands)),
+                   "rf_wmb_back_backward")
+    return grad_bands
+
+
+def dwconv5x5_backward(x: torch.Tensor, weight: torch.Tensor, grad_out: torch.Tensor, grads=None):
+    """The gradient of ``dwconv5x5``: ``(grad_x, grads)`` with ``grads = {"weight": [C,1,5,5], "bias": [C]}``.  Passing the ``grads`` of
+    an earlier call ADDS to its tensors; ``grad_x`` is always a new tensor."""
+    x, weight, grad_out = _chk(x, "x"), _chk(weight, "weight"), _chk(grad_out, "grad_out")
+    b, c, h, w = x.shape
+    if tuple(weight.shape) != (c, 1, 5, 5) or tuple(grad_out.shape) != tuple(x.shape):
+        raise RuntimeError(f"dwconv5x5_backward: weight {tuple(weight.shape)} / grad_out {tuple(grad_out.shape)} do not match x {tuple(x.shape)}")
+    shapes = {"weight": (c, 1, 5, 5), "bias": (c,)}
+    acc = grads is not None
+    if grads is None:
+        grads = {k: torch.empty(s, dtype=x.dtype, device=x.device) for k, s in shapes.items()}
+    gs = _shaped(grads, "", ("weight", "bias"), shapes, "dwconv5x5_backward (grads)")
+    if any(t.data_ptr() != grads[k].data_ptr() for k, t in zip(shapes, gs)):
+        raise RuntimeError("dwconv5x5_backward: the tensors of grads must be contiguous (they are written in place)")
+    lib = _lib.load()
+    ws = _workspace(lib.rf_dwconv5x5_backward_workspace_bytes(b, c, h, w), "rf_dwconv5x5_backward_workspace_bytes", x)
+    grad_x = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.rf_dwconv5x5_backward(_ptr(x), _ptr(grad_out), _ptr(grad_x), _ptr(weight), _ptr(gs[0]), _ptr(gs[1]), _ptr(ws), ws.numel(),
+                                             b, c, h, w, int(acc), _stream(x)), "rf_dwconv5x5_backward")
+    return grad_x, grads
+
+
+_ILLU_KEYS = ("conv1.weight", "conv1.bias", "depth_conv.weight", "depth_conv.bias", "conv2.weight", "conv2.bias")
+
+
+def illumination_estimator_backward(img: torch.Tensor, params, grad_fea: torch.Tensor, grad_map: Optional[torch.Tensor] = None,
+                                    prefix: str = "", grads=None):
+    """The gradient of ``illumination_estimator``: ``(grad_img, grads)`` for ``grad_fea`` = dL/d ``illu_fea`` and, optionally, ``grad_map``
+    = dL/d ``illu_map``; ``grads`` holds the six keys ``conv1.*``, ``depth_conv.*``, ``conv2.*`` (``prefix`` included).  ``x1`` is
+    recomputed, ``illu_fea`` only when ``grad_map`` is given.  Without ``grad_map`` (``WMB.forward`` discards ``illu_map``) the two
+    ``conv2.*`` gradients are zeros in a new ``grads`` and untouched in a passed one.  Passing the ``grads`` of an earlier call ADDS to
+    its tensors; ``grad_img`` is always a new tensor.  All three channel counts must be multiples of 4 in 4 .. 512."""
+    img, grad_fea = _chk(img, "img"), _chk(grad_fea, "grad_fea")
+    b, c, h, w = img.shape
+    cm, co = params[prefix + "conv1.weight"].shape[0], params[prefix + "conv2.weight"].shape[0]
+    shapes = {"conv1.weight": (cm, c + 1, 1, 1), "conv1.bias": (cm,), "depth_conv.weight": (cm, 1, 5, 5), "depth_conv.bias": (cm,),
+              "conv2.weight": (co, cm, 1, 1), "conv2.bias": (co,)}
+    ts = _shaped(params, prefix, _ILLU_KEYS, shapes, "illumination_estimator_backward")
+    if tuple(grad_fea.shape) != (b, cm, h, w):
+        raise RuntimeError(f"illumination_estimator_backward: grad_fea {tuple(grad_fea.shape)}, expected {(b, cm, h, w)}")
+    if grad_map is not None:
+        grad_map = _chk(grad_map, "grad_map")
+        if tuple(grad_map.shape) != (b, co, h, w):
+            raise RuntimeError(f"illumination_estimator_backward: grad_map {tuple(grad_map.shape)}, expected {(b, co, h, w)}")
+    acc = grads is not None
+    if grads is None:
+        grads = {prefix + k: (torch.zeros_like(t) if k.startswith("conv2.") and grad_map is None else torch.empty_like(t))
+                 for k, t in zip(_ILLU_KEYS, ts)}
+    gs = _shaped(grads, prefix, _ILLU_KEYS, shapes, "illumination_estimator_backward (grads)")
+    if any(t.data_ptr() != grads[prefix + k].data_ptr() for k, t in zip(_ILLU_KEYS, gs)):
+        raise RuntimeError("illumination_estimator_backward: the tensors of grads must be contiguous (they are written in place)")
+    geo = (b, c, cm, co, h, w)
+    lib = _lib.load()
+    ws = _workspace(lib.rf_illumination_estimator_backward_workspace_bytes(*geo, int(grad_map is not None)),
+                    "rf_illumination_estimator_backward_workspace_bytes", img)
+    grad_img = torch.empty_like(img)
+    with torch.cuda.device(img.device):
+        _lib.check(lib.rf_illumination_estimator_backward(_ptr(img), _ptr(grad_fea), _ptr(grad_map), _ptr(grad_img), _ptr_array(ts), _ptr_array(gs),
+                                                          _ptr(ws), ws.numel(), *geo, int(acc), _stream(img)), "rf_illumination_estimator_backward")
+    return grad_img, grads
+
+
+def layernorm2d_backward(x: torch.Tensor, weight: torch.Tensor, grad_out: torch.Tensor, residual: Optional[torch.Tensor] = None,
+                         eps: float = 1e-5, grads=None):
+    """The gradient of ``layernorm2d`` (with bias): ``(grad_x, grads)`` with ``grads = {"weight": [C], "bias": [C]}``; ``residual`` is
+    added to ``grad_x`` (``grad_u = grad_out + LN^T(grad_v)`` of a pre-norm block in one pass).  Passing the ``grads`` of an earlier
+    call ADDS to its tensors; ``grad_x`` is always a new tensor."""
+    x, weight, grad_out = _chk(x, "x"), _chk(weight, "weight"), _chk(grad_out, "grad_out")
+    b, c, h, w = x.shape
+    if weight.numel() != c or tuple(grad_out.shape) != tuple(x.shape) or (residual is not None and tuple(residual.shape) != tuple(x.shape)):
+        raise RuntimeError(f"layernorm2d_backward: x {tuple(x.shape)}, grad_out {tuple(grad_out.shape)}: equal shapes and {c} weights are needed")
+    residual = None if residual is None else _chk(residual, "residual")
+    shapes = {"weight": (c,), "bias": (c,)}
+    acc = grads is not None
+    if grads is None:
+        grads = {k: torch.empty(s, dtype=x.dtype, device=x.device) for k, s in shapes.items()}
+    gs = _shaped(grads, "", ("weight", "bias"), shapes, "layernorm2d_backward (grads)")
+    if any(t.data_ptr() != grads[k].data_ptr() for k, t in zip(shapes, gs)):
+        raise RuntimeError("layernorm2d_backward: the tensors of grads must be contiguous (they are written in place)")
+    lib = _lib.load()
+    ws = _workspace(lib.rf_layernorm2d_backward_workspace_bytes(b, c, h, w), "rf_layernorm2d_backward_workspace_bytes", x)
+    grad_x = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.rf_layernorm2d_backward(_ptr(x), _ptr(grad_out), _ptr(grad_x), _ptr(weight.reshape(-1)), _ptr(gs[0]), _ptr(gs[1]),
+                                               _ptr(residual), _ptr(ws), ws.numel(), b, c, h, w, float(eps), int(acc), _stream(x)),
+                   "rf_layernorm2d_backward")
+    return grad_x, grads
+
+
 def wmb_ffn_tail(t: torch.Tensor, y: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
     """``t + y + LayerNorm_c(t)``: the end of ``x + ffn(norm2(x))`` with ``y = project_out(..)``, FeedForward's identity
     ``norm2(x)`` recomputed per pixel instead of stored (model.py:58-65, 244)."""

@@ -490,6 +490,48 @@ int rf_wmb_back(const float* bands, const float* t, float* out, int B, int C, in
 int rf_wmb_ffn_sum(const float* t, const float* y, float* out, const float* ln_w, const float* ln_b, int B, int C, int h, int w,
                     void* stream);
 
+/* ---- the gradient pieces of a WMB block that the block operators above do not cover (csrc/rf_wmb_bwd.hip) ---------------------
+ * Conventions of rf_wm_backward: a *_bytes query returns a negative error code for a geometry the operator refuses; refusals come
+ * before any launch, -22 with an rf_last_error message that starts with the entry point's name; every tensor pointer is 16-byte
+ * aligned; nothing the call writes (grad_in, the gradients, the workspace) may overlap anything it reads or anything else it
+ * writes; a workspace smaller than the query's answer is refused with -12.  Nothing is kept from a forward call; inputs are not
+ * written; grad_in / grad_bands are always overwritten; accumulate != 0 ADDS to the parameter gradients, 0 overwrites them.  Every
+ * sum over pixels goes through per-workgroup slabs added in a fixed order (no float atomics): two runs give the same bits.
+ * rf_wmb_front_backward: the gradient of rf_wmb_front.  x, grad_t, grad_x [B,C,2h,2w], grad_bands [4B,C,h,w]; with
+ *   g = grad_t + iwt_init(grad_bands) (= dwt_init^T; never stored), grad_x = the LayerNorm adjoint of g under the weight w2 and
+ *   grad_w2 [C] (+)= grad_scale sum g xhat, grad_b2 [C] (+)= grad_scale sum g (a block passes w2 = 2 norm1.weight and grad_scale 2).
+ *   Limits of rf_wmb_front: 4 <= C <= 512, even w.  rf_wmb_front_backward_nblk: its slabs per image.
+ * rf_wmb_back_backward: the gradient of rf_wmb_back with respect to bands: grad_bands = dwt_init(m grad_out / 2), m = 1 where the
+ *   forward's value before the clamp lies in [0, 1] (torch.clamp's backward), recomputed in the forward's expression order.  The
+ *   gradient with respect to t is grad_out itself.  No parameters, no workspace.
+ * rf_dwconv5x5_backward: the gradient of rf_dwconv5x5: grad_in = the stencil of grad_out on the flipped taps, grad_weight [C,1,5,5]
+ *   and grad_bias [C].  rf_dwconv5x5_backward_nblk: the slabs per plane of the tap sums (one per 1024 groups of 4 pixels, at most 32).
+ * rf_illumination_estimator_backward: the gradient of Illumination_Estimator.forward (model.py:186-200).  img, grad_img [B,C,h,w],
+ *   grad_fea [B,Cm,h,w], grad_map [B,Co,h,w] or NULL (WMB.forward discards illu_map): then conv2's two gradients are not touched.
+ *   prm / grad_prm = HOST arrays of 6 device pointers: conv1.weight [Cm,C+1,1,1], conv1.bias, depth_conv.weight [Cm,1,5,5],
+ *   depth_conv.bias, conv2.weight [Co,Cm,1,1], conv2.bias.  C, Cm, Co are multiples of 4 in 4 .. 512.  with_map of the query: whether
+ *   grad_map will be given.
+ * rf_layernorm2d_backward: the gradient of rf_layernorm2d (with bias): grad_in = residual (NULL: none) + the adjoint, grad_weight,
+ *   grad_bias [C]; 1 <= C <= 512. */
+int rf_wmb_front_backward_nblk(int B, int C, int h, int w);
+long long rf_wmb_front_backward_workspace_bytes(int B, int C, int h, int w);
+int rf_wmb_front_backward(const float* x, const float* grad_t, float* grad_x, const float* grad_bands, const float* weight2, float* grad_weight2,
+                          float* grad_bias2, void* workspace, size_t workspace_bytes, int B, int C, int h, int w, float grad_scale, int accumulate,
+                          void* stream);
+int rf_wmb_back_backward(const float* bands, const float* grad_out, float* grad_bands, int B, int C, int h, int w, void* stream);
+int rf_dwconv5x5_backward_nblk(int h, int w);
+long long rf_dwconv5x5_backward_workspace_bytes(int B, int C, int h, int w);
+int rf_dwconv5x5_backward(const float* in, const float* grad_out, float* grad_in, const float* weight, float* grad_weight, float* grad_bias,
+                          void* workspace, size_t workspace_bytes, int B, int C, int h, int w, int accumulate, void* stream);
+long long rf_illumination_estimator_backward_workspace_bytes(int B, int C, int Cm, int Co, int h, int w, int with_map);
+int rf_illumination_estimator_backward(const float* img, const float* grad_fea, const float* grad_map, float* grad_img, const float* const* prm,
+                                       float* const* grad_prm, void* workspace, size_t workspace_bytes, int B, int C, int Cm, int Co, int h, int w,
+                                       int accumulate, void* stream);
+long long rf_layernorm2d_backward_workspace_bytes(int B, int C, int h, int w);
+int rf_layernorm2d_backward(const float* in, const float* grad_out, float* grad_in, const float* weight, float* grad_weight, float* grad_bias,
+                            const float* residual, void* workspace, size_t workspace_bytes, int B, int C, int h, int w, float eps, int accumulate,
+                            void* stream);
+
 /* ---- the element-wise kernels of RF_VARIANT_TRUECOLOR one by one (csrc/rf_truecolor.hip; BayerTORGBColorMultiLvl.py) ----------
  * No handle: the caller passes the raw parameter tensors.  Every argument is checked before any launch (RF_E_INVALID).
  * rf_tc_spatial: xs = feat * (1 + sigmoid(conv3x3(guide[0:5]; w_col, b_col)) + tanh(sigmoid(conv3x3(guide[5]; w_low, b_low)) +

@@ -5,7 +5,7 @@ Each case runs through the C ABI (ops.*) with the library's own HIP-event bracke
 (rf_profile_begin/end), so the figure is the kernel's time on its launch stream, without the
 weight-repack helper that the operator-level entry points run first.
 
-usage: python tools/kbench.py [conv1x1] [conv3x3] [dw] [attn] [flca] [dwt] [ssim] [sampler] [mcr_sampler] [mamba] [wfb] [ffab_bwd] [--dim 32] [--batch 8] [--size 512]
+usage: python tools/kbench.py [conv1x1] [conv3x3] [dw] [attn] [flca] [dwt] [ssim] [sampler] [mcr_sampler] [mamba] [wfb] [ffab_bwd] [wmb_bwd] [--dim 32] [--batch 8] [--size 512]
 """
 from __future__ import annotations
 
@@ -208,6 +208,60 @@ def main():
                 print(f"ffab {tag} ({bb},{c},{hw},{hw}): {total / 10:.3f} ms per call as the sum of its bracketed kernels on one stream"
                       + (f"; the four transform-adjoint kernels {adj / 10:.3f} ms = {100 * adj / total:.1f} %" if tag == "backward" else ""), flush=True)
             del xf, gf, pf
+    if "wmb_bwd" in a.what:   # the WMB backward pieces at level 0 and level 3 of RawFormer-S at the training patch, given as the
+        # full-resolution shape: HIP events around 4 calls per sample, 15 rounds that take one sample of every candidate in turn after
+        # 3 warm-up calls each; median (min - max) in ms per call.  front: the fused kernel against the same function composed from
+        # ops.iwt_init + rf_affine_clamp_add + ops.layernorm2d_backward; back and illumination: against their forward operators
+        import statistics
+
+        def rounds(cands, calls=4, n=15, warm=3):
+            for fn in cands.values():
+                for _ in range(warm):
+                    fn()
+            torch.cuda.synchronize()
+            ms = {k: [] for k in cands}
+            for _ in range(n):
+                for k, fn in cands.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(calls):
+                        fn()
+                    e1.record()
+                    e1.synchronize()
+                    ms[k].append(e0.elapsed_time(e1) / calls)
+            return {k: (statistics.median(v), min(v), max(v)) for k, v in ms.items()}
+
+        lib = _lib.load()
+        for bb, c, hh, ww in ((4, 32, 256, 256), (4, 256, 32, 32)):
+            u = lambda *s: torch.rand(*s, device=dev) * 2 - 1  # noqa: E731
+            xf, gt, gb = u(bb, c, hh, ww) * 2, u(bb, c, hh, ww), u(4 * bb, c, hh // 2, ww // 2)
+            w2, b2 = 2 * (u(c) * 0.5 + 1), u(c)
+            bands = u(4 * bb, c, hh // 2, ww // 2) * 2
+
+            def composed():
+                g = ops.iwt_init(gb)
+                _lib.check(lib.rf_affine_clamp_add(g.data_ptr(), gt.data_ptr(), g.data_ptr(), g.numel(), 1.0, 0.0, float("-inf"), float("inf"), None),
+                           "rf_affine_clamp_add")
+                return ops.layernorm2d_backward(xf, w2, g)
+
+            ch, cw = hh // 2, ww // 2
+            img, gfea = u(bb, c, ch, cw), u(bb, c, ch, cw)
+            pi = {"conv1.weight": u(c, c + 1, 1, 1) / c ** 0.5, "conv1.bias": u(c), "depth_conv.weight": u(c, 1, 5, 5) / 5, "depth_conv.bias": u(c),
+                  "conv2.weight": u(c, c, 1, 1) / c ** 0.5, "conv2.bias": u(c)}
+            res = rounds({"front fused": lambda: ops.wmb_front_backward(xf, w2, b2, gt, gb, grad_scale=2.0), "front composed": composed,
+                          "back backward": lambda: ops.wmb_back_backward(bands, gt), "back forward": lambda: ops.wmb_back(bands, gt),
+                          "illumination backward": lambda: ops.illumination_estimator_backward(img, pi, gfea),
+                          "illumination forward": lambda: ops.illumination_estimator(img, pi)})
+            for k, (med, lo, hi) in res.items():
+                print(f"wmb_bwd ({bb},{c},{hh},{ww})  {k:24s} {med:8.4f} ms  ({lo:.4f} - {hi:.4f})", flush=True)
+            el = bb * c * hh * ww
+            print(f"wmb_bwd ({bb},{c},{hh},{ww})  front fused / composed = {res['front fused'][0] / res['front composed'][0]:.3f}; fused "
+                  f"{16 * el / res['front fused'][0] / 1e6:.0f} GB/s of its 16 B / element; back backward / forward = "
+                  f"{res['back backward'][0] / res['back forward'][0]:.3f} ({12 * el / res['back backward'][0] / 1e6:.0f} GB/s of 12 B / element); "
+                  f"illumination backward / forward = {res['illumination backward'][0] / res['illumination forward'][0]:.3f}", flush=True)
+            for tag, fn in (("front fused", lambda: ops.wmb_front_backward(xf, w2, b2, gt, gb, grad_scale=2.0)),
+                            ("illumination backward", lambda: ops.illumination_estimator_backward(img, pi, gfea))):
+                report(f"wmb_bwd ({bb},{c},{hh},{ww}) {tag}", timed(fn))
     if "dwt" in a.what:
         x = r(B, d, S, S)
         report("dwt_init", timed(lambda: ops.dwt_init(x)))
