@@ -435,6 +435,8 @@ int rf_upcat_scratch_bytes(int C, size_t* bytes) {
 int rf_upcat(const float* x, const float* skip, float* out, const float* up_w, const float* up_b, const float* cr_w, const float* cr_b,
              void* scratch, int B, int C, int h, int w, void* stream) {
     RF_CHECK_ARG(x && skip && out && up_w && cr_w && scratch && aligned16(scratch), "upcat: bad arguments");
+    // launch_upcat's own check, made here as well: an unsupported shape is refused before pack_upcat launches anything
+    RF_CHECK_ARG(upcat_supported(C, h, w, x, skip, out) && B > 0 && B <= 65535, "upcat: unsupported shape C=%d %dx%d", C, h, w);
     hipStream_t st = (hipStream_t)stream;
     RF_TRY(pack_upcat(up_w, up_b, cr_w, cr_b, (float*)scratch, C, st));
     return launch_upcat(x, skip, out, (const float*)scratch, B, C, h, w, st);

@@ -354,6 +354,8 @@ def token_attention(qkv: torch.Tensor, heads: int, scale: Optional[float] = None
         raise RuntimeError(f"token_attention: {c3} channels are not 3 x {heads} heads x d")
     inner = c3 // 3
     d, n = inner // heads, h * w
+    if not 1 <= d <= 32:                                  # rf_token_attn's own check, ahead of the default scale d ** -0.5
+        raise RuntimeError(f"token_attention: head dimension {d} not in 1..32")
     out = torch.empty((b, inner, h, w), dtype=qkv.dtype, device=qkv.device)
     q = qkv.data_ptr()
     with torch.cuda.device(qkv.device):
