@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RF_LIB_PATH") or os.path.join(_HERE, "csrc", "librawformer_hip.so")  # override: diagnostic builds
 
@@ -187,3 +189,50 @@ def check(rc: int, what: str) -> None:
     if rc != 0:
         msg = load().rf_last_error()
         raise RuntimeError(f"{what} failed ({rc}): {msg.decode() if msg else 'unknown error'}")
+
+
+def call(name: str, *args) -> None:
+    """Checked call of an entry point that takes no stream (``rf_create``, ``rf_set_param``, ``rf_set_shard`` ...): the arguments
+    go to ctypes as they are, a failing status raises under the entry point's own name."""
+    check(getattr(load(), name)(*args), name)
+
+
+def size(name: str, *geometry) -> int:
+    """What a size query answers, whichever of the header's two conventions it follows (told apart by its ``restype`` in
+    ``SIGNATURES``): ``rf_*_scratch_bytes(..., size_t*)`` and its kin return a status and write the size,
+    ``rf_*_workspace_bytes(...)`` return it as ``long long``, negative for a status.  Either failure raises through ``check``."""
+    fn = getattr(load(), name)
+    if SIGNATURES[name][0] is C.c_longlong:
+        n = fn(*geometry)
+        if n < 0:
+            check(n, name)
+        return n
+    sz = C.c_size_t()
+    check(fn(*geometry, C.byref(sz)), name)
+    return sz.value
+
+
+def scratch(name: str, like, *geometry):
+    """The scratch area the size query ``name`` asks for at ``geometry``: uint8 on ``like``'s device, never under 16 bytes."""
+    return torch.empty(max(size(name, *geometry), 16), dtype=torch.uint8, device=like.device)
+
+
+_PLAIN = frozenset((int, float, type(None)))      # most arguments of a launch: asked for first, the host cost of a call is this loop
+
+
+def _argument(a):
+    if isinstance(a, torch.Tensor):
+        return a.data_ptr()
+    if isinstance(a, (list, tuple)):
+        return (C.c_void_p * len(a))(*[t.data_ptr() for t in a])
+    return int(a) if isinstance(a, bool) else a
+
+
+def launch(name: str, like, *args) -> None:
+    """Checked call of a launching entry point on ``like``'s device and that device's current stream, which every one of them
+    takes as its last argument.  A tensor goes in as its data pointer, ``None`` as a null pointer, a list or tuple of tensors as
+    a ``void*`` array, a ``bool`` as an ``int``; anything else (numbers, ready-made ctypes values, raw addresses) as it is.
+    ``args`` holds every tensor, a contiguous copy made by the caller's check included, until the call has returned."""
+    conv = [a if type(a) in _PLAIN else _argument(a) for a in args]
+    with torch.cuda.device(like.device):
+        check(getattr(load(), name)(*conv, torch.cuda.current_stream(like.device).cuda_stream), name)

@@ -106,10 +106,8 @@ class ResidentSID:
     def __len__(self) -> int:
         return self.n
 
-    def _sample(self, lib, table: torch.Tensor, x: torch.Tensor, gt: torch.Tensor, b: int, ph: int, pw: int, stream) -> None:
-        _lib.check(lib.rf_sid_sample(C.c_void_p(self.raw.data_ptr()), C.c_void_p(self.gt.data_ptr()), C.c_void_p(self.amp.data_ptr()),
-                                     C.c_void_p(table.data_ptr()), C.c_void_p(x.data_ptr()), C.c_void_p(gt.data_ptr()),
-                                     self.n, self.h, self.w, b, ph, pw, self.black, self.white, stream), "rf_sid_sample")
+    def _sample(self, table: torch.Tensor, x: torch.Tensor, gt: torch.Tensor, b: int, ph: int, pw: int) -> None:
+        _lib.launch("rf_sid_sample", x, self.raw, self.gt, self.amp, table, x, gt, self.n, self.h, self.w, b, ph, pw, self.black, self.white)
 
 
 class ResidentMCR:
@@ -143,10 +141,8 @@ class ResidentMCR:
     def __len__(self) -> int:
         return self.n
 
-    def _sample(self, lib, table: torch.Tensor, x: torch.Tensor, gt: torch.Tensor, b: int, ph: int, pw: int, stream) -> None:
-        _lib.check(lib.rf_mcr_sample(C.c_void_p(self.raw.data_ptr()), C.c_void_p(self.gt.data_ptr()), C.c_void_p(self.amp.data_ptr()),
-                                     C.c_void_p(table.data_ptr()), C.c_void_p(x.data_ptr()), C.c_void_p(gt.data_ptr()),
-                                     self.n, self.h, self.w, b, ph, pw, stream), "rf_mcr_sample")
+    def _sample(self, table: torch.Tensor, x: torch.Tensor, gt: torch.Tensor, b: int, ph: int, pw: int) -> None:
+        _lib.launch("rf_mcr_sample", x, self.raw, self.gt, self.amp, table, x, gt, self.n, self.h, self.w, b, ph, pw)
 
 
 class PatchSampler:
@@ -182,14 +178,11 @@ class PatchSampler:
         d = self.dataset
         b = len(desc)
         table = np.ascontiguousarray(np.asarray(desc, dtype=np.int64).reshape(b, 4).astype(np.int32))
-        lib = _lib.load()
-        _lib.check(lib.rf_sid_check_desc(table.ctypes.data_as(C.POINTER(C.c_int)), d.n, d.h, d.w, b, ph, pw), "rf_sid_check_desc")
-        with torch.cuda.device(d.device):
-            dev_table = torch.from_numpy(table).to(d.device)
-            x = torch.empty((b, 1, ph, pw), dtype=torch.float32, device=d.device)
-            gt = torch.empty((b, 3, ph, pw), dtype=torch.float32, device=d.device)
-            stream = C.c_void_p(torch.cuda.current_stream(d.device).cuda_stream)
-            d._sample(lib, dev_table, x, gt, b, ph, pw, stream)
+        _lib.call("rf_sid_check_desc", table.ctypes.data_as(C.POINTER(C.c_int)), d.n, d.h, d.w, b, ph, pw)
+        dev_table = torch.from_numpy(table).to(d.device)
+        x = torch.empty((b, 1, ph, pw), dtype=torch.float32, device=d.device)
+        gt = torch.empty((b, 3, ph, pw), dtype=torch.float32, device=d.device)
+        d._sample(dev_table, x, gt, b, ph, pw)
         return x, gt
 
     def batch(self, indices: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -15,7 +15,6 @@ definition -- ``ssim_u8`` below (scipy ``uniform_filter``) and the integral-imag
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Tuple
 
 import numpy as np
@@ -36,10 +35,6 @@ def correct_bayer_channels(rgb, pattern: str = "RGGB"):
     return rgb
 
 
-def _stream(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
 def to_uint8_hwc(pred: torch.Tensor) -> torch.Tensor:
     """``(clamp(pred,0,1)[b].cpu().numpy().transpose(1,2,0) * 255).astype(np.uint8)`` for every image
     (test.py:117-118): float32 ``[B,C,H,W]`` on the device -> uint8 ``[B,H,W,C]`` on the device."""
@@ -48,9 +43,7 @@ def to_uint8_hwc(pred: torch.Tensor) -> torch.Tensor:
     pred = pred.contiguous()
     b, c, h, w = pred.shape
     out = torch.empty((b, h, w, c), dtype=torch.uint8, device=pred.device)
-    with torch.cuda.device(pred.device):
-        _lib.check(_lib.load().rf_to_uint8_hwc(C.c_void_p(pred.data_ptr()), C.c_void_p(out.data_ptr()), b, c, h, w, _stream(pred)),
-                   "rf_to_uint8_hwc")
+    _lib.launch("rf_to_uint8_hwc", pred, pred, out, b, c, h, w)
     return out
 
 
@@ -59,9 +52,7 @@ def channel_means_u8(img: torch.Tensor) -> torch.Tensor:
     img = img.contiguous()
     b, h, w, c = img.shape
     sums = torch.empty((b, c), dtype=torch.int64, device=img.device)
-    with torch.cuda.device(img.device):
-        _lib.check(_lib.load().rf_u8_channel_sums(C.c_void_p(img.data_ptr()), C.c_void_p(sums.data_ptr()), b, c, h * w, _stream(img)),
-                   "rf_u8_channel_sums")
+    _lib.launch("rf_u8_channel_sums", img, img, sums, b, c, h * w)
     return sums.cpu().double() / float(h * w)
 
 
@@ -83,9 +74,7 @@ def psnr_u8(a: torch.Tensor, b: torch.Tensor) -> np.ndarray:
     a, b = a.contiguous(), b.contiguous()
     n = a[0].numel()
     sse = torch.empty((a.shape[0],), dtype=torch.int64, device=a.device)
-    with torch.cuda.device(a.device):
-        _lib.check(_lib.load().rf_u8_sse(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), C.c_void_p(sse.data_ptr()),
-                                         a.shape[0], n, _stream(a)), "rf_u8_sse")
+    _lib.launch("rf_u8_sse", a, a, b, sse, a.shape[0], n)
     mse = sse.cpu().numpy().astype(np.float64) / float(n)
     with np.errstate(divide="ignore"):
         return 10.0 * np.log10(255.0 ** 2 / mse)
@@ -122,14 +111,9 @@ def ssim_u8_channel_means(a: torch.Tensor, b: torch.Tensor) -> np.ndarray:
         raise RuntimeError("ssim_u8_device runs on the ROCm device only (ssim_u8 is the host restatement)")
     a, b = a.contiguous(), b.contiguous()
     n, h, w, c = a.shape
-    lib = _lib.load()
-    nbytes = C.c_size_t()
-    _lib.check(lib.rf_u8_ssim_scratch_bytes(n, c, h, w, C.byref(nbytes)), "rf_u8_ssim_scratch_bytes")
-    scratch = torch.empty((nbytes.value // 8,), dtype=torch.float64, device=a.device)
+    scratch = _lib.scratch("rf_u8_ssim_scratch_bytes", a, n, c, h, w)
     sums = torch.empty((n, c), dtype=torch.float64, device=a.device)
-    with torch.cuda.device(a.device):
-        _lib.check(lib.rf_u8_ssim(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), C.c_void_p(sums.data_ptr()),
-                                  C.c_void_p(scratch.data_ptr()), n, c, h, w, _stream(a)), "rf_u8_ssim")
+    _lib.launch("rf_u8_ssim", a, a, b, sums, scratch, n, c, h, w)
     return sums.cpu().numpy() / float((h - 6) * (w - 6))
 
 
@@ -192,7 +176,5 @@ def pack_raw(raw: torch.Tensor, black_level: int, white_level: int, ratio: float
     mode = _SID_MODES[layout]
     h, w = H2 // 2, W2 // 2
     out = torch.empty((B, 1, H2, W2) if mode == 2 else (B, 4, h, w), dtype=torch.float32, device=raw.device)
-    with torch.cuda.device(raw.device):
-        _lib.check(_lib.load().rf_sid_pack(C.c_void_p(raw.data_ptr()), C.c_void_p(out.data_ptr()), B, h, w, int(black_level),
-                                           int(white_level), float(ratio), mode, _stream(raw)), "rf_sid_pack")
+    _lib.launch("rf_sid_pack", raw, raw, out, B, h, w, int(black_level), int(white_level), float(ratio), mode)
     return out

@@ -140,7 +140,7 @@ class RawFormer(nn.Module):
         cfg = self._config()
         lib = _lib.load()
         probe = C.c_void_p()
-        _lib.check(lib.rf_create(C.byref(cfg), C.byref(probe)), "rf_create")
+        _lib.call("rf_create", C.byref(cfg), C.byref(probe))
         try:
             # _param_names: every tensor the handle borrows (parameters and, for 'wfb', the BatchNorm statistics, which are
             # module buffers); entries the reference registers and its forward never reads stay out of it
@@ -148,8 +148,8 @@ class RawFormer(nn.Module):
             self._buffer_names: List[str] = []
             name, shape, ndim, flags = C.c_char_p(), (C.c_int64 * 4)(), C.c_int(), C.c_int()
             for i in range(lib.rf_param_count(probe)):
-                _lib.check(lib.rf_param_info(probe, i, C.byref(name), C.byref(shape), C.byref(ndim)), "rf_param_info")
-                _lib.check(lib.rf_param_flags(probe, i, C.byref(flags)), "rf_param_flags")
+                _lib.call("rf_param_info", probe, i, C.byref(name), C.byref(shape), C.byref(ndim))
+                _lib.call("rf_param_flags", probe, i, C.byref(flags))
                 key, shp = name.value.decode(), tuple(shape[: ndim.value])
                 if flags.value & _lib.RF_PARAM_BUFFER:
                     self._param_names.append(key)
@@ -261,9 +261,27 @@ class RawFormer(nn.Module):
             if st is None:
                 st = _DeviceState()
                 cfg = self._config()
-                _lib.check(_lib.load().rf_create(C.byref(cfg), C.byref(st.handle)), "rf_create")
+                _lib.call("rf_create", C.byref(cfg), C.byref(st.handle))
                 self._rt[idx] = st
         return st
+
+    def _state_with_workspace(self, device: torch.device, b: int, H: int, W: int, sync: bool = True) -> _DeviceState:
+        """The device state with a workspace large enough for ``(b, H, W)``: kept while it is, dropped before a larger one is
+        allocated.  ``sync``: register (and repack) the parameters first; ``forward_window`` leaves that to ``_run``."""
+        st = self._state_for(device)
+        if sync:
+            self._sync_params(st, device)
+        need = _lib.size("rf_workspace_bytes", st.handle, b, H, W)
+        if st.workspace is None or st.workspace.numel() < need:
+            st.workspace = None
+            st.workspace = torch.empty(need, dtype=torch.uint8, device=device)
+        return st
+
+    @staticmethod
+    def _refuse_host_tensor(t: torch.Tensor) -> None:
+        if t.device.type != "cuda":
+            raise RuntimeError("RawFormer (HIP) needs a ROCm device tensor: there is no CPU path in this package "
+                               f"(input is on {t.device})")
 
     def invalidate_packed(self) -> None:
         """Force the next ``forward`` to re-register and repack the weights.
@@ -315,7 +333,6 @@ class RawFormer(nn.Module):
         ptrs = tuple(s[0] for s in sig)
         if sig == st.signature or (not pack and ptrs == st.ptrs):
             return
-        lib = _lib.load()
         for k in self._param_names:
             p = params[k]
             if p.device != device:
@@ -323,23 +340,19 @@ class RawFormer(nn.Module):
             if p.dtype != torch.float32 or not p.is_contiguous():
                 raise RuntimeError(f"parameter {k} must be contiguous float32")
             shape = (C.c_int64 * max(p.dim(), 1))(*p.shape)
-            _lib.check(lib.rf_set_param(st.handle, k.encode(), C.c_void_p(p.data_ptr()), shape, p.dim()), "rf_set_param")
+            _lib.call("rf_set_param", st.handle, k.encode(), p.data_ptr(), shape, p.dim())
         st.ptrs = ptrs
         if not pack:
             st.signature = None
             return
-        sz = C.c_size_t()
-        _lib.check(lib.rf_packed_bytes(st.handle, C.byref(sz)), "rf_packed_bytes")
-        if st.packed is None or st.packed.numel() < sz.value or st.packed.device != device:
-            st.packed = torch.empty(sz.value, dtype=torch.uint8, device=device)
-        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        _lib.check(lib.rf_pack_params(st.handle, C.c_void_p(st.packed.data_ptr()), sz.value, stream), "rf_pack_params")
+        need = _lib.size("rf_packed_bytes", st.handle)
+        if st.packed is None or st.packed.numel() < need or st.packed.device != device:
+            st.packed = torch.empty(need, dtype=torch.uint8, device=device)
+        _lib.launch("rf_pack_params", st.packed, st.handle, st.packed, need)
         st.signature = sig
 
     def _run(self, x: torch.Tensor, packed_input: bool) -> torch.Tensor:
-        if x.device.type != "cuda":
-            raise RuntimeError("RawFormer (HIP) needs a ROCm device tensor: there is no CPU path in this package "
-                               f"(input is on {x.device})")
+        self._refuse_host_tensor(x)
         if x.dim() != 4:
             raise RuntimeError(f"expected a 4-D input [B,C,H,W], got {tuple(x.shape)}")
         if torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters()):
@@ -365,20 +378,9 @@ class RawFormer(nn.Module):
         if H % 8 or W % 8:
             raise RuntimeError(f"mosaic size must be divisible by 16 (three 2x down-samplings after the Bayer pack); "
                                f"got {2 * H}x{2 * W}")
-        lib = _lib.load()
-        with torch.cuda.device(x.device):
-            st = self._state_for(x.device)
-            self._sync_params(st, x.device)
-            sz = C.c_size_t()
-            _lib.check(lib.rf_workspace_bytes(st.handle, b, H, W, C.byref(sz)), "rf_workspace_bytes")
-            if st.workspace is None or st.workspace.numel() < sz.value:
-                st.workspace = None
-                st.workspace = torch.empty(sz.value, dtype=torch.uint8, device=x.device)
-            out = torch.empty((b, self.out_channels, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
-            stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-            _lib.check(lib.rf_forward(st.handle, C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()),
-                                      C.c_void_p(st.workspace.data_ptr()), st.workspace.numel(), b, H, W,
-                                      int(packed_input), stream), "rf_forward")
+        st = self._state_with_workspace(x.device, b, H, W)
+        out = torch.empty((b, self.out_channels, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
+        _lib.launch("rf_forward", x, st.handle, x, out, st.workspace, st.workspace.numel(), b, H, W, packed_input)
         return out
 
     def _refuse_training_mode(self) -> None:
@@ -419,24 +421,18 @@ class RawFormer(nn.Module):
 
         cb = _lib.ALLREDUCE_FN(allreduce)
         with torch.cuda.device(x.device):
-            st = self._state_for(x.device)
             # the workspace must exist (and not move) before the callback sees pointers into it
-            sz = C.c_size_t()
-            _lib.check(lib.rf_workspace_bytes(st.handle, x.shape[0], x.shape[2] // 2, x.shape[3] // 2, C.byref(sz)), "rf_workspace_bytes")
-            if st.workspace is None or st.workspace.numel() < sz.value:
-                st.workspace = None
-                st.workspace = torch.empty(sz.value, dtype=torch.uint8, device=x.device)
+            st = self._state_with_workspace(x.device, x.shape[0], x.shape[2] // 2, x.shape[3] // 2, sync=False)
             if total_cols is None:
                 if x_lo or x_hi:
                     raise ValueError("forward_window: x_lo / x_hi need total_cols")
-                _lib.check(lib.rf_set_shard(st.handle, int(y_lo), int(y_hi), int(total_rows), cb, None), "rf_set_shard")
+                _lib.call("rf_set_shard", st.handle, int(y_lo), int(y_hi), int(total_rows), cb, None)
             else:
-                _lib.check(lib.rf_set_shard_grid(st.handle, int(y_lo), int(y_hi), int(total_rows), int(x_lo), int(x_hi), int(total_cols),
-                                                 cb, None), "rf_set_shard_grid")
+                _lib.call("rf_set_shard_grid", st.handle, int(y_lo), int(y_hi), int(total_rows), int(x_lo), int(x_hi), int(total_cols), cb, None)
             try:
                 out = self._run(x, packed_input=False)
             finally:
-                lib.rf_set_shard(st.handle, 0, 0, 0, _lib.ALLREDUCE_FN(0), None)
+                lib.rf_set_shard(st.handle, 0, 0, 0, _lib.ALLREDUCE_FN(0), None)      # unchecked: must not mask _run's own exception
         if failure:
             raise failure[0]
         return out
@@ -454,8 +450,7 @@ class RawFormer(nn.Module):
         ``[B, dim*2^l, H>>l, W>>l]``; ``packed``: the packed frame ``[B,4,H,W]`` the branch's guidance is derived from
         (``variant='flca'``, ``'multilvl'`` and ``'truecolor'``, whose front end -- ``EnhancedBayerProcessor`` with the model's
         own parameters -- runs on it first; for ``'plain'`` and ``'wfb'`` pass ``None`` and H, W are taken from ``x``)."""
-        if x.device.type != "cuda":
-            raise RuntimeError("RawFormer (HIP) needs a ROCm device tensor: there is no CPU path in this package")
+        self._refuse_host_tensor(x)
         self._refuse_training_mode()
         lvl = stage - 1 if stage <= 4 else 7 - stage
         x = x.detach().float().contiguous()
@@ -467,21 +462,9 @@ class RawFormer(nn.Module):
             packed = packed.detach().float().contiguous()
             if tuple(packed.shape) != (b, 4, H, W):
                 raise RuntimeError(f"packed frame must be {(b, 4, H, W)}, got {tuple(packed.shape)}")
-        lib = _lib.load()
-        with torch.cuda.device(x.device):
-            st = self._state_for(x.device)
-            self._sync_params(st, x.device)
-            sz = C.c_size_t()
-            _lib.check(lib.rf_workspace_bytes(st.handle, b, H, W, C.byref(sz)), "rf_workspace_bytes")
-            if st.workspace is None or st.workspace.numel() < sz.value:
-                st.workspace = None
-                st.workspace = torch.empty(sz.value, dtype=torch.uint8, device=x.device)
-            out = torch.empty_like(x)
-            stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-            _lib.check(lib.rf_forward_stage(st.handle, stage, C.c_void_p(x.data_ptr()),
-                                            C.c_void_p(packed.data_ptr() if packed is not None else None),
-                                            C.c_void_p(out.data_ptr()), C.c_void_p(st.workspace.data_ptr()),
-                                            st.workspace.numel(), b, H, W, stream), "rf_forward_stage")
+        st = self._state_with_workspace(x.device, b, H, W)
+        out = torch.empty_like(x)
+        _lib.launch("rf_forward_stage", x, st.handle, stage, x, packed, out, st.workspace, st.workspace.numel(), b, H, W)
         return out
 
     def tc_guidance(self, packed: torch.Tensor, level: int):
@@ -489,45 +472,25 @@ class RawFormer(nn.Module):
         guidance planes an ``EnhancedFLCA`` block sees at U-Net level ``level`` (0..3).  Returns ``(y [B,1,H,W], crcb [B,2,H,W],
         rgb [B,3,H,W], guide [B,7,H>>level,W>>level])``: ``EnhancedBayerProcessor``'s outputs (BayerTORGBColorMultiLvl.py:100-134)
         and ``[y, cr, cb, R, G, y_low, y_high]`` (:255-275)."""
-        if packed.device.type != "cuda":
-            raise RuntimeError("RawFormer (HIP) needs a ROCm device tensor: there is no CPU path in this package")
+        self._refuse_host_tensor(packed)
         if self.variant != "truecolor":
             raise RuntimeError(f"tc_guidance: variant 'truecolor' only, not {self.variant!r}")
         packed = packed.detach().float().contiguous()
         if packed.dim() != 4 or packed.shape[1] != 4:
             raise RuntimeError(f"expected a packed frame [B,4,H,W], got {tuple(packed.shape)}")
         b, _, H, W = packed.shape
-        lib = _lib.load()
-        with torch.cuda.device(packed.device):
-            st = self._state_for(packed.device)
-            self._sync_params(st, packed.device)
-            sz = C.c_size_t()
-            _lib.check(lib.rf_workspace_bytes(st.handle, b, H, W, C.byref(sz)), "rf_workspace_bytes")
-            if st.workspace is None or st.workspace.numel() < sz.value:
-                st.workspace = None
-                st.workspace = torch.empty(sz.value, dtype=torch.uint8, device=packed.device)
-            new = lambda c, hh, ww: torch.empty((b, c, hh, ww), dtype=torch.float32, device=packed.device)      # noqa: E731
-            y, crcb, rgb, guide = new(1, H, W), new(2, H, W), new(3, H, W), new(7, H >> max(level, 0), W >> max(level, 0))
-            stream = C.c_void_p(torch.cuda.current_stream(packed.device).cuda_stream)
-            _lib.check(lib.rf_tc_guidance(st.handle, C.c_void_p(packed.data_ptr()), int(level), C.c_void_p(y.data_ptr()),
-                                          C.c_void_p(crcb.data_ptr()), C.c_void_p(rgb.data_ptr()), C.c_void_p(guide.data_ptr()),
-                                          C.c_void_p(st.workspace.data_ptr()), st.workspace.numel(), b, H, W, stream), "rf_tc_guidance")
+        st = self._state_with_workspace(packed.device, b, H, W)
+        new = lambda c, hh, ww: torch.empty((b, c, hh, ww), dtype=torch.float32, device=packed.device)      # noqa: E731
+        y, crcb, rgb, guide = new(1, H, W), new(2, H, W), new(3, H, W), new(7, H >> max(level, 0), W >> max(level, 0))
+        _lib.launch("rf_tc_guidance", packed, st.handle, packed, int(level), y, crcb, rgb, guide, st.workspace, st.workspace.numel(), b, H, W)
         return y, crcb, rgb, guide
 
     def _ml_call(self, who: str, frame: torch.Tensor, H: int, W: int):
         """``variant='multilvl'`` diagnostics: the device state with parameters in place and a workspace for ``(B, H, W)``."""
-        if frame.device.type != "cuda":
-            raise RuntimeError("RawFormer (HIP) needs a ROCm device tensor: there is no CPU path in this package")
+        self._refuse_host_tensor(frame)
         if self.variant != "multilvl":
             raise RuntimeError(f"{who}: variant 'multilvl' only, not {self.variant!r}")
-        st = self._state_for(frame.device)
-        self._sync_params(st, frame.device)
-        sz = C.c_size_t()
-        _lib.check(_lib.load().rf_workspace_bytes(st.handle, frame.shape[0], H, W, C.byref(sz)), "rf_workspace_bytes")
-        if st.workspace is None or st.workspace.numel() < sz.value:
-            st.workspace = None
-            st.workspace = torch.empty(sz.value, dtype=torch.uint8, device=frame.device)
-        return st
+        return self._state_with_workspace(frame.device, frame.shape[0], H, W)
 
     def ml_guidance(self, packed: torch.Tensor, level: int):
         """``variant='multilvl'``: the guidance an ``FLCA_Pyramid`` block sees at U-Net level ``level`` (0..3) of a packed frame
@@ -539,14 +502,10 @@ class RawFormer(nn.Module):
         if packed.dim() != 4 or packed.shape[1] != 4:
             raise RuntimeError(f"expected a packed frame [B,4,H,W], got {tuple(packed.shape)}")
         b, _, H, W = packed.shape
-        with torch.cuda.device(packed.device):
-            st = self._ml_call("ml_guidance", packed, H, W)
-            guide = torch.empty((b, 2 * self.flca_levels + 2, H >> max(level, 0), W >> max(level, 0)), dtype=torch.float32, device=packed.device)
-            means = torch.zeros((b, 8), dtype=torch.float32, device=packed.device)
-            stream = C.c_void_p(torch.cuda.current_stream(packed.device).cuda_stream)
-            _lib.check(_lib.load().rf_ml_guidance(st.handle, C.c_void_p(packed.data_ptr()), int(level), C.c_void_p(guide.data_ptr()),
-                                                  C.c_void_p(means.data_ptr()), C.c_void_p(st.workspace.data_ptr()), st.workspace.numel(),
-                                                  b, H, W, stream), "rf_ml_guidance")
+        st = self._ml_call("ml_guidance", packed, H, W)
+        guide = torch.empty((b, 2 * self.flca_levels + 2, H >> max(level, 0), W >> max(level, 0)), dtype=torch.float32, device=packed.device)
+        means = torch.zeros((b, 8), dtype=torch.float32, device=packed.device)
+        _lib.launch("rf_ml_guidance", packed, st.handle, packed, int(level), guide, means, st.workspace, st.workspace.numel(), b, H, W)
         return guide, means
 
     def ml_tail(self, image: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
@@ -562,23 +521,18 @@ class RawFormer(nn.Module):
         if tuple(image.shape) != (b, 3, 2 * H, 2 * W) or image.device != x.device:
             raise RuntimeError(f"image must be {(b, 3, 2 * H, 2 * W)} on {x.device}, got {tuple(image.shape)} on {image.device}")
         out = image.detach().float().clone(memory_format=torch.contiguous_format)
-        with torch.cuda.device(x.device):
-            st = self._ml_call("ml_tail", x, H, W)
-            stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-            _lib.check(_lib.load().rf_ml_tail(st.handle, C.c_void_p(out.data_ptr()), C.c_void_p(x.data_ptr()), int(packed_input),
-                                              C.c_void_p(st.workspace.data_ptr()), st.workspace.numel(), b, H, W, stream), "rf_ml_tail")
+        st = self._ml_call("ml_tail", x, H, W)
+        _lib.launch("rf_ml_tail", x, st.handle, out, x, packed_input, st.workspace, st.workspace.numel(), b, H, W)
         return out
 
     def workspace_bytes(self, batch: int, H: int, W: int) -> int:
-        probe, sz = C.c_void_p(), C.c_size_t()
+        probe = C.c_void_p()
         cfg = self._config()
-        lib = _lib.load()
-        _lib.check(lib.rf_create(C.byref(cfg), C.byref(probe)), "rf_create")
+        _lib.call("rf_create", C.byref(cfg), C.byref(probe))
         try:
-            _lib.check(lib.rf_workspace_bytes(probe, batch, H, W, C.byref(sz)), "rf_workspace_bytes")
+            return _lib.size("rf_workspace_bytes", probe, batch, H, W)
         finally:
-            lib.rf_destroy(probe)
-        return sz.value
+            _lib.load().rf_destroy(probe)
 
     def __del__(self):
         try:

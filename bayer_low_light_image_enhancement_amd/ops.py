@@ -26,16 +26,19 @@ def _chk(t: torch.Tensor, name: str) -> torch.Tensor:
     return t.contiguous()
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
+def _opt(t: Optional[torch.Tensor], name: str) -> Optional[torch.Tensor]:
+    return None if t is None else _chk(t, name)
 
 
-def _stream(t: torch.Tensor):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
-def _scratch(nbytes: int, like: torch.Tensor) -> torch.Tensor:
-    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=like.device)
+def _out(out: Optional[torch.Tensor], like: torch.Tensor, who: str, shape=None, name: str = "out") -> torch.Tensor:
+    """The tensor an operator writes: a new one of ``shape`` (default: ``like``'s) beside ``like``, a checked float32 tensor, or
+    the caller's own, checked."""
+    if out is None:
+        return torch.empty_like(like) if shape is None else like.new_empty(shape)
+    shape = tuple(like.shape) if shape is None else tuple(shape)
+    if tuple(out.shape) != shape or not out.is_contiguous() or out.dtype != torch.float32 or out.device != like.device:
+        raise RuntimeError(f"{who}: `{name}` must be a contiguous float32 tensor of shape {shape} on {like.device}")
+    return out
 
 
 def downshuffle(x: torch.Tensor, r: int = 2) -> torch.Tensor:
@@ -47,8 +50,7 @@ def downshuffle(x: torch.Tensor, r: int = 2) -> torch.Tensor:
     if h2 % 2 or w2 % 2:
         raise RuntimeError(f"downshuffle: spatial size {h2}x{w2} not divisible by 2")
     out = torch.empty((b, 4 * c, h2 // 2, w2 // 2), dtype=x.dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().rf_pixel_unshuffle2(_ptr(x), _ptr(out), b, c, h2 // 2, w2 // 2, _stream(x)), "rf_pixel_unshuffle2")
+    _lib.launch("rf_pixel_unshuffle2", x, x, out, b, c, h2 // 2, w2 // 2)
     return out
 
 
@@ -61,8 +63,7 @@ def pixel_shuffle(x: torch.Tensor, r: int = 2) -> torch.Tensor:
     if c4 % 4:
         raise RuntimeError(f"pixel_shuffle: {c4} channels not divisible by 4")
     out = torch.empty((b, c4 // 4, 2 * h, 2 * w), dtype=x.dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().rf_pixel_shuffle2(_ptr(x), _ptr(out), b, c4 // 4, h, w, _stream(x)), "rf_pixel_shuffle2")
+    _lib.launch("rf_pixel_shuffle2", x, x, out, b, c4 // 4, h, w)
     return out
 
 
@@ -73,8 +74,7 @@ def dwt_init(x: torch.Tensor) -> torch.Tensor:
     if h2 % 2 or w2 % 2:
         raise RuntimeError(f"dwt_init: spatial size {h2}x{w2} not divisible by 2")
     out = torch.empty((4 * b, c, h2 // 2, w2 // 2), dtype=x.dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().rf_dwt_haar(_ptr(x), _ptr(out), b, c, h2 // 2, w2 // 2, _stream(x)), "rf_dwt_haar")
+    _lib.launch("rf_dwt_haar", x, x, out, b, c, h2 // 2, w2 // 2)
     return out
 
 
@@ -85,8 +85,7 @@ def iwt_init(x: torch.Tensor) -> torch.Tensor:
     if b4 % 4:
         raise RuntimeError(f"iwt_init: batch {b4} not divisible by 4")
     out = torch.empty((b4 // 4, c, 2 * h, 2 * w), dtype=x.dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().rf_idwt_haar(_ptr(x), _ptr(out), b4 // 4, c, h, w, _stream(x)), "rf_idwt_haar")
+    _lib.launch("rf_idwt_haar", x, x, out, b4 // 4, c, h, w)
     return out
 
 
@@ -107,9 +106,7 @@ def custom_dwt(x: torch.Tensor, kernel=DEFAULT_KERNEL, norm: bool = True) -> tor
     if h2 % 2 or w2 % 2:
         raise RuntimeError(f"CustomDWT: spatial size {h2}x{w2} not divisible by 2")
     out = torch.empty((b, 4 * c, h2 // 2, w2 // 2), dtype=x.dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().rf_dwt_custom(_ptr(x), _ptr(out), _k16(kernel), int(norm), b, c, h2 // 2, w2 // 2, _stream(x)),
-                   "rf_dwt_custom")
+    _lib.launch("rf_dwt_custom", x, x, out, _k16(kernel), int(norm), b, c, h2 // 2, w2 // 2)
     return out
 
 
@@ -120,9 +117,7 @@ def custom_idwt(x: torch.Tensor, kernel=DEFAULT_KERNEL, norm: bool = True) -> to
     if c4 % 4:
         raise RuntimeError(f"CustomIDWT: {c4} channels not divisible by 4")
     out = torch.empty((b, c4 // 4, 2 * h, 2 * w), dtype=x.dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().rf_idwt_custom(_ptr(x), _ptr(out), _k16(kernel), int(norm), b, c4 // 4, h, w, _stream(x)),
-                   "rf_idwt_custom")
+    _lib.launch("rf_idwt_custom", x, x, out, _k16(kernel), int(norm), b, c4 // 4, h, w)
     return out
 
 
@@ -131,23 +126,19 @@ def haar_dwt(x: torch.Tensor) -> Tuple[torch.Tensor, Tuple[torch.Tensor, torch.T
     x = _chk(x, "x")
     b, c, h, w = x.shape
     out = torch.empty((4, b, c, (h + 1) // 2, (w + 1) // 2), dtype=x.dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().rf_haar_dwt(_ptr(x), _ptr(out), b, c, h, w, _stream(x)), "rf_haar_dwt")
+    _lib.launch("rf_haar_dwt", x, x, out, b, c, h, w)
     return out[0], (out[1], out[2], out[3])
 
 
 def layernorm2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], eps: float = 1e-5) -> torch.Tensor:
     """``LayerNorm(dim)(x)`` on NCHW (FrequencyawareLumaChromaAttentionRAWFormer.py:180-187);
     ``bias=None`` is ``BiasFree_LayerNorm`` (RawFomer_WFB_FFAB/model.py:89-103)."""
-    x, weight = _chk(x, "x"), _chk(weight, "weight")
-    bias = None if bias is None else _chk(bias, "bias")
+    x, weight, bias = _chk(x, "x"), _chk(weight, "weight"), _opt(bias, "bias")
     b, c, h, w = x.shape
     if weight.numel() != c:
         raise RuntimeError(f"LayerNorm: weight has {weight.numel()} elements, input has {c} channels")
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().rf_layernorm2d(_ptr(x), _ptr(out), _ptr(weight), _ptr(bias), float(eps), b, c, h, w, _stream(x)),
-                   "rf_layernorm2d")
+    _lib.launch("rf_layernorm2d", x, x, out, weight, bias, float(eps), b, c, h, w)
     return out
 
 
@@ -165,29 +156,21 @@ def conv1x1(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] 
     cout = weight.shape[0]
     if weight.numel() != cout * (c1 + c2):
         raise RuntimeError(f"conv1x1: weight {tuple(weight.shape)} does not match {c1 + c2} input channels")
-    lib = _lib.load()
-    sz = C.c_size_t()
-    _lib.check(lib.rf_conv1x1_scratch_bytes(c1 + c2, cout, C.byref(sz)), "rf_conv1x1_scratch_bytes")
-    scratch = _scratch(sz.value, x)
+    scratch = _lib.scratch("rf_conv1x1_scratch_bytes", x, c1 + c2, cout)
     out = torch.empty((b, cout, h, w), dtype=x.dtype, device=x.device)
-    args = [None if t is None else _chk(t, "arg") for t in (bias, ln_weight, ln_bias, residual)]
-    with torch.cuda.device(x.device):
-        _lib.check(lib.rf_conv1x1(_ptr(x), _ptr(x2), _ptr(out), _ptr(weight), _ptr(args[0]), _ptr(args[1]), _ptr(args[2]),
-                                  _ptr(args[3]), _ptr(scratch), b, c1, c2, cout, h, w, _stream(x)), "rf_conv1x1")
+    args = [_opt(t, "arg") for t in (bias, ln_weight, ln_bias, residual)]
+    _lib.launch("rf_conv1x1", x, x, x2, out, weight, *args, scratch, b, c1, c2, cout, h, w)
     return out
 
 
 def dwconv3x3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, gelu: bool = False) -> torch.Tensor:
     """``nn.Conv2d(C, C, 3, padding=1, groups=C)`` (+ exact GELU)."""
-    x, weight = _chk(x, "x"), _chk(weight, "weight")
-    bias = None if bias is None else _chk(bias, "bias")
+    x, weight, bias = _chk(x, "x"), _chk(weight, "weight"), _opt(bias, "bias")
     b, c, h, w = x.shape
     if weight.numel() != c * 9:
         raise RuntimeError(f"dwconv3x3: weight {tuple(weight.shape)} does not match {c} channels")
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().rf_dwconv3x3(_ptr(x), _ptr(out), _ptr(weight), _ptr(bias), int(gelu), b, c, h, w, _stream(x)),
-                   "rf_dwconv3x3")
+    _lib.launch("rf_dwconv3x3", x, x, out, weight, bias, int(gelu), b, c, h, w)
     return out
 
 
@@ -195,95 +178,72 @@ def conv3x3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] 
             store: str = "plain") -> torch.Tensor:
     """``nn.Conv2d(Cin, Cout, 3, padding=1)``; ``act='lrelu'`` adds LeakyReLU(0.2), ``'relu'`` ReLU;
     ``store='unshuffle'`` = Downsample (a8), ``'shuffle'`` = conv_out + PixelShuffle (a10)."""
-    x, weight = _chk(x, "x"), _chk(weight, "weight")
-    bias = None if bias is None else _chk(bias, "bias")
+    x, weight, bias = _chk(x, "x"), _chk(weight, "weight"), _opt(bias, "bias")
     b, cin, h, w = x.shape
     cout = weight.shape[0]
     if tuple(weight.shape[1:]) != (cin, 3, 3):
         raise RuntimeError(f"conv3x3: weight {tuple(weight.shape)} does not match {cin} input channels")
     mode = {"plain": 0, "unshuffle": 1, "shuffle": 2}[store]
     shape = {0: (b, cout, h, w), 1: (b, cout * 4, h // 2, w // 2), 2: (b, cout // 4, 2 * h, 2 * w)}[mode]
-    lib = _lib.load()
-    sz = C.c_size_t()
-    _lib.check(lib.rf_conv3x3_scratch_bytes(cin, cout, C.byref(sz)), "rf_conv3x3_scratch_bytes")
-    scratch = _scratch(sz.value, x)
+    scratch = _lib.scratch("rf_conv3x3_scratch_bytes", x, cin, cout)
     out = torch.empty(shape, dtype=x.dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.rf_conv3x3(_ptr(x), _ptr(out), _ptr(weight), _ptr(bias), _ptr(scratch), {"none": 0, "lrelu": 1, "relu": 2}[act], mode,
-                                  b, cin, cout, h, w, _stream(x)), "rf_conv3x3")
+    _lib.launch("rf_conv3x3", x, x, out, weight, bias, scratch, {"none": 0, "lrelu": 1, "relu": 2}[act], mode, b, cin, cout, h, w)
     return out
 
 
 def conv_transpose2x2(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``nn.ConvTranspose2d(Cin, Cout, 2, stride=2)`` (RawFomer_WFB_FFAB/model.py:461)."""
-    x, weight = _chk(x, "x"), _chk(weight, "weight")
-    bias = None if bias is None else _chk(bias, "bias")
+    x, weight, bias = _chk(x, "x"), _chk(weight, "weight"), _opt(bias, "bias")
     b, cin, h, w = x.shape
     if weight.shape[0] != cin or tuple(weight.shape[2:]) != (2, 2):
         raise RuntimeError(f"ConvTranspose2d: weight {tuple(weight.shape)} does not match {cin} input channels")
     cout = weight.shape[1]
-    lib = _lib.load()
-    sz = C.c_size_t()
-    _lib.check(lib.rf_convT2x2_scratch_bytes(cin, cout, C.byref(sz)), "rf_convT2x2_scratch_bytes")
-    scratch = _scratch(sz.value, x)
+    scratch = _lib.scratch("rf_convT2x2_scratch_bytes", x, cin, cout)
     out = torch.empty((b, cout, 2 * h, 2 * w), dtype=x.dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.rf_convT2x2(_ptr(x), _ptr(out), _ptr(weight), _ptr(bias), _ptr(scratch), b, cin, cout, h, w, _stream(x)),
-                   "rf_convT2x2")
+    _lib.launch("rf_convT2x2", x, x, out, weight, bias, scratch, b, cin, cout, h, w)
     return out
 
 
 def channel_attention(x: torch.Tensor, qkv_w, qkv_b, dw_w, dw_b, temperature, proj_w, proj_b, heads: int) -> torch.Tensor:
     """``Attention(dim, heads, bias=True)(x)`` (FrequencyawareLumaChromaAttentionRAWFormer.py:212-235)."""
     x = _chk(x, "x")
-    ts = [None if t is None else _chk(t, "param") for t in (qkv_w, qkv_b, dw_w, dw_b, temperature, proj_w, proj_b)]
+    ts = [_opt(t, "param") for t in (qkv_w, qkv_b, dw_w, dw_b, temperature, proj_w, proj_b)]
     b, c, h, w = x.shape
     if c % heads:
         raise RuntimeError(f"Attention: {c} channels not divisible by {heads} heads")
-    lib = _lib.load()
-    sz = C.c_size_t()
-    _lib.check(lib.rf_chan_attn_scratch_bytes(b, c, heads, h, w, C.byref(sz)), "rf_chan_attn_scratch_bytes")
-    scratch = _scratch(sz.value, x)
+    scratch = _lib.scratch("rf_chan_attn_scratch_bytes", x, b, c, heads, h, w)
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.rf_chan_attn(_ptr(x), _ptr(out), *[_ptr(t) for t in ts], _ptr(scratch), b, c, heads, h, w, _stream(x)),
-                   "rf_chan_attn")
+    _lib.launch("rf_chan_attn", x, x, out, *ts, scratch, b, c, heads, h, w)
     return out
+
+
+def _guidance(x4: torch.Tensor, size: Optional[Tuple[int, int]], who: str):
+    """``rf_flca_guidance`` on the packed frame ``x4`` at feature size ``size`` (``None``: the frame's own): the four planes and
+    the scratch area, at whose head the kernels keep the base planes ``y, cr, cb`` (include/rawformer_hip.h)."""
+    x4 = _chk(x4, "x4")
+    b, c, h, w = x4.shape
+    if c != 4:
+        raise RuntimeError(f"{who} expects packed RGGB [B,4,H,W]")
+    scratch = _lib.scratch("rf_guidance_scratch_bytes", x4, b, h, w)
+    oh, ow = (h, w) if size is None else (size[0], size[1])
+    out = torch.empty((b, 4, oh, ow), dtype=x4.dtype, device=x4.device)
+    _lib.launch("rf_flca_guidance", x4, x4, out, scratch, b, h, w, oh, ow)
+    return out, scratch
 
 
 def flca_guidance(x4: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
     """Guidance planes ``[y_low, y_high, cr, cb]`` an FLCA block sees at feature size ``size``
     (``BayerLumaChroma`` + ``HaarDWT`` + bilinear ``F.interpolate``,
     FrequencyawareLumaChromaAttentionRAWFormer.py:79-97,138-149)."""
-    x4 = _chk(x4, "x4")
-    b, c, h, w = x4.shape
-    if c != 4:
-        raise RuntimeError("flca_guidance expects packed RGGB [B,4,H,W]")
-    lib = _lib.load()
-    sz = C.c_size_t()
-    _lib.check(lib.rf_guidance_scratch_bytes(b, h, w, C.byref(sz)), "rf_guidance_scratch_bytes")
-    scratch = _scratch(sz.value, x4)
-    out = torch.empty((b, 4, size[0], size[1]), dtype=x4.dtype, device=x4.device)
-    with torch.cuda.device(x4.device):
-        _lib.check(lib.rf_flca_guidance(_ptr(x4), _ptr(out), _ptr(scratch), b, h, w, size[0], size[1], _stream(x4)), "rf_flca_guidance")
-    return out
+    return _guidance(x4, size, "flca_guidance")[0]
 
 
 def bayer_luma_chroma(x4: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """``BayerLumaChroma()(x4)`` -> ``(y, cr, cb)``, each ``[B,1,H,W]``
     (FrequencyawareLumaChromaAttentionRAWFormer.py:79-97): the base planes the guidance kernels keep at the head of their
     scratch area (include/rawformer_hip.h, rf_flca_guidance)."""
-    x4 = _chk(x4, "x4")
-    b, c, h, w = x4.shape
-    if c != 4:
-        raise RuntimeError("bayer_luma_chroma expects packed RGGB [B,4,H,W]")
-    lib = _lib.load()
-    sz = C.c_size_t()
-    _lib.check(lib.rf_guidance_scratch_bytes(b, h, w, C.byref(sz)), "rf_guidance_scratch_bytes")
-    scratch = _scratch(sz.value, x4)
-    out = torch.empty((b, 4, h, w), dtype=x4.dtype, device=x4.device)
-    with torch.cuda.device(x4.device):
-        _lib.check(lib.rf_flca_guidance(_ptr(x4), _ptr(out), _ptr(scratch), b, h, w, h, w, _stream(x4)), "rf_flca_guidance")
+    scratch = _guidance(x4, None, "bayer_luma_chroma")[1]
+    b, _, h, w = x4.shape
     planes = scratch[: 3 * b * h * w * 4].view(torch.float32).reshape(3, b, 1, h, w)
     return planes[0].clone(), planes[1].clone(), planes[2].clone()
 
@@ -310,16 +270,9 @@ def transformer_block(x: torch.Tensor, params, heads: int, ffn_expansion_factor:
     x = _chk(x, "x")
     b, c, h, w = x.shape
     ts = [_chk(params[prefix + k], k) for k in _TB_KEYS]
-    lib = _lib.load()
-    sz = C.c_size_t()
-    _lib.check(lib.rf_transformer_block_scratch_bytes(b, c, heads, ffn_expansion_factor, h, w, C.byref(sz)),
-               "rf_transformer_block_scratch_bytes")
-    scratch = _scratch(sz.value, x)
+    scratch = _lib.scratch("rf_transformer_block_scratch_bytes", x, b, c, heads, ffn_expansion_factor, h, w)
     out = torch.empty_like(x)
-    ptrs = (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-    with torch.cuda.device(x.device):
-        _lib.check(lib.rf_transformer_block(_ptr(x), _ptr(out), ptrs, _ptr(scratch), b, c, heads, ffn_expansion_factor, h, w,
-                                            _stream(x)), "rf_transformer_block")
+    _lib.launch("rf_transformer_block", x, x, out, ts, scratch, b, c, heads, ffn_expansion_factor, h, w)
     return out
 
 
@@ -334,14 +287,9 @@ def flca(feat: torch.Tensor, x4: torch.Tensor, params, prefix: str = "") -> torc
     b, c, h, w = feat.shape
     guide = flca_guidance(x4, (h, w))
     ts = [_chk(params[prefix + k].reshape(-1) if params[prefix + k].dim() == 0 else params[prefix + k], k) for k in _FLCA_KEYS]
-    lib = _lib.load()
-    sz = C.c_size_t()
-    _lib.check(lib.rf_flca_scratch_bytes(b, c, h, w, C.byref(sz)), "rf_flca_scratch_bytes")
-    scratch = _scratch(sz.value, feat)
+    scratch = _lib.scratch("rf_flca_scratch_bytes", feat, b, c, h, w)
     out = torch.empty_like(feat)
-    ptrs = (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-    with torch.cuda.device(feat.device):
-        _lib.check(lib.rf_flca(_ptr(feat), _ptr(guide), _ptr(out), ptrs, _ptr(scratch), b, c, h, w, _stream(feat)), "rf_flca")
+    _lib.launch("rf_flca", feat, feat, guide, out, ts, scratch, b, c, h, w)
     return out
 
 
@@ -358,10 +306,8 @@ def token_attention(qkv: torch.Tensor, heads: int, scale: Optional[float] = None
         raise RuntimeError(f"token_attention: head dimension {d} not in 1..32")
     out = torch.empty((b, inner, h, w), dtype=qkv.dtype, device=qkv.device)
     q = qkv.data_ptr()
-    with torch.cuda.device(qkv.device):
-        _lib.check(_lib.load().rf_token_attn(C.c_void_p(q), C.c_void_p(q + 4 * inner * n), C.c_void_p(q + 8 * inner * n), _ptr(out),
-                                             3 * inner * n, inner * n, b, heads, d, n, float(d ** -0.5 if scale is None else scale),
-                                             _stream(qkv)), "rf_token_attn")
+    _lib.launch("rf_token_attn", qkv, q, q + 4 * inner * n, q + 8 * inner * n, out, 3 * inner * n, inner * n, b, heads, d, n,
+                float(d ** -0.5 if scale is None else scale))
     return out
 
 
@@ -379,31 +325,31 @@ def luma_film(qkv: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, luma: 
         if tuple(luma.shape) != (b, 1, h, w):
             raise RuntimeError(f"luma_film: luma {tuple(luma.shape)} must be {(b, 1, h, w)}")
         alpha = _chk(alpha, "alpha")
-    lib = _lib.load()
-    sz = C.c_size_t()
-    _lib.check(lib.rf_luma_film_scratch_bytes(b, h, w, C.byref(sz)), "rf_luma_film_scratch_bytes")
-    scratch = _scratch(sz.value, qkv)
+    scratch = _lib.scratch("rf_luma_film_scratch_bytes", qkv, b, h, w)
     out = torch.empty_like(qkv)
-    with torch.cuda.device(qkv.device):
-        _lib.check(lib.rf_luma_film(_ptr(qkv), _ptr(gamma), _ptr(beta), inner * h * w, _ptr(luma), _ptr(alpha), _ptr(out), _ptr(scratch),
-                                    b, inner, h, w, _stream(qkv)), "rf_luma_film")
+    _lib.launch("rf_luma_film", qkv, qkv, gamma, beta, inner * h * w, luma, alpha, out, scratch, b, inner, h, w)
     return out
 
 
-def luminance_aware_mhsa(x: torch.Tensor, luma: torch.Tensor, params, heads: int = 8, prefix: str = "") -> torch.Tensor:
-    """``LuminanceAwareMHSA.forward(x, luma)`` (Attenblock.py:161-220) from its state_dict ``params``
-    (``to_qkv``, ``proj``, ``luma_cond.net.{0,2}``, ``luma_cond.{gamma,beta}``, ``alpha``): 1x1 GEMM, two 3x3
-    convs + ReLU, two 1x1 GEMMs, FiLM + luma bias, flash token attention, 1x1 GEMM."""
+def _luma_attention(x, luma, params, prefix, heads, ln_weight=None, ln_bias=None, residual=None):
+    """The schedule of ``LuminanceAwareMHSA`` on the state_dict keys under ``prefix``; a LayerNorm (``ln_*``) rides in the prologue
+    of the ``to_qkv`` GEMM, ``residual`` in the epilogue of ``proj``."""
     p = lambda k: params[prefix + k]  # noqa: E731
-    qkv = conv1x1(x, p("to_qkv.weight"), params.get(prefix + "to_qkv.bias"))
+    qkv = conv1x1(x, p("to_qkv.weight"), params.get(prefix + "to_qkv.bias"), ln_weight=ln_weight, ln_bias=ln_bias)
     hcond = conv3x3(luma, p("luma_cond.net.0.weight"), p("luma_cond.net.0.bias"), act="relu")
     hcond = conv3x3(hcond, p("luma_cond.net.2.weight"), p("luma_cond.net.2.bias"), act="relu")
     gamma = conv1x1(hcond, p("luma_cond.gamma.weight"), p("luma_cond.gamma.bias"))
     beta = conv1x1(hcond, p("luma_cond.beta.weight"), p("luma_cond.beta.bias"))
     alpha = params.get(prefix + "alpha")
     qkv = luma_film(qkv, gamma, beta, luma if alpha is not None else None, None if alpha is None else alpha.reshape(1))
-    out = token_attention(qkv, heads)
-    return conv1x1(out, p("proj.weight"), params.get(prefix + "proj.bias"))
+    return conv1x1(token_attention(qkv, heads), p("proj.weight"), params.get(prefix + "proj.bias"), residual=residual)
+
+
+def luminance_aware_mhsa(x: torch.Tensor, luma: torch.Tensor, params, heads: int = 8, prefix: str = "") -> torch.Tensor:
+    """``LuminanceAwareMHSA.forward(x, luma)`` (Attenblock.py:161-220) from its state_dict ``params``
+    (``to_qkv``, ``proj``, ``luma_cond.net.{0,2}``, ``luma_cond.{gamma,beta}``, ``alpha``): 1x1 GEMM, two 3x3
+    convs + ReLU, two 1x1 GEMMs, FiLM + luma bias, flash token attention, 1x1 GEMM."""
+    return _luma_attention(x, luma, params, prefix, heads)
 
 
 def dwgate3x3(x: torch.Tensor, wa: torch.Tensor, ba: Optional[torch.Tensor], wb: torch.Tensor, bb: Optional[torch.Tensor]) -> torch.Tensor:
@@ -412,9 +358,7 @@ def dwgate3x3(x: torch.Tensor, wa: torch.Tensor, ba: Optional[torch.Tensor], wb:
     x, wa, wb = _chk(x, "x"), _chk(wa, "wa"), _chk(wb, "wb")
     b, c, h, w = x.shape
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().rf_dwgate3x3(_ptr(x), _ptr(out), _ptr(wa), _ptr(None if ba is None else _chk(ba, "ba")), _ptr(wb),
-                                            _ptr(None if bb is None else _chk(bb, "bb")), b, c, h, w, _stream(x)), "rf_dwgate3x3")
+    _lib.launch("rf_dwgate3x3", x, x, out, wa, _opt(ba, "ba"), wb, _opt(bb, "bb"), b, c, h, w)
     return out
 
 
@@ -425,9 +369,7 @@ def dwconv5x5(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor
     if tuple(weight.shape) != (c, 1, 5, 5):
         raise RuntimeError(f"dwconv5x5: weight {tuple(weight.shape)} does not match {c} channels")
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().rf_dwconv5x5(_ptr(x), _ptr(out), _ptr(weight), _ptr(None if bias is None else _chk(bias, "bias")),
-                                            b, c, h, w, _stream(x)), "rf_dwconv5x5")
+    _lib.launch("rf_dwconv5x5", x, x, out, weight, _opt(bias, "bias"), b, c, h, w)
     return out
 
 
@@ -479,14 +421,9 @@ def upsample_cat_reduce(x: torch.Tensor, skip: torch.Tensor, up_w: torch.Tensor,
     c = c2 // 2
     if tuple(skip.shape) != (b, c, 2 * h, 2 * w) or tuple(up_w.shape) != (c2, c, 2, 2) or tuple(cr_w.shape) != (c, c2, 1, 1):
         raise RuntimeError("upsample_cat_reduce: shapes do not describe ConvTranspose2d(2C,C,2,2) + cat + Conv2d(2C,C,1)")
-    lib = _lib.load()
-    sz = C.c_size_t()
-    _lib.check(lib.rf_upcat_scratch_bytes(c, C.byref(sz)), "rf_upcat_scratch_bytes")
-    scratch = _scratch(sz.value, x)
+    scratch = _lib.scratch("rf_upcat_scratch_bytes", x, c)
     out = torch.empty_like(skip)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.rf_upcat(_ptr(x), _ptr(skip), _ptr(out), _ptr(up_w), _ptr(None if up_b is None else _chk(up_b, "up_b")), _ptr(cr_w),
-                                _ptr(None if cr_b is None else _chk(cr_b, "cr_b")), _ptr(scratch), b, c, h, w, _stream(x)), "rf_upcat")
+    _lib.launch("rf_upcat", x, x, skip, out, up_w, _opt(up_b, "up_b"), cr_w, _opt(cr_b, "cr_b"), scratch, b, c, h, w)
     return out
 
 
@@ -495,15 +432,7 @@ def atten_transformer_block(x: torch.Tensor, luma: torch.Tensor, params, heads: 
     ``x + ffn(LN2(x))`` with ``LuminanceAwareMHSA`` and ``ConvFFN``.  Both LayerNorms ride in the prologue of the 1x1
     GEMM that consumes them, both residuals in the epilogue of the 1x1 GEMM that produces the branch."""
     p = lambda k: params.get(prefix + k)  # noqa: E731
-    a = prefix + "attn."
-    qkv = conv1x1(x, params[a + "to_qkv.weight"], params.get(a + "to_qkv.bias"), ln_weight=p("norm1.body.weight"), ln_bias=p("norm1.body.bias"))
-    hcond = conv3x3(luma, params[a + "luma_cond.net.0.weight"], params[a + "luma_cond.net.0.bias"], act="relu")
-    hcond = conv3x3(hcond, params[a + "luma_cond.net.2.weight"], params[a + "luma_cond.net.2.bias"], act="relu")
-    gamma = conv1x1(hcond, params[a + "luma_cond.gamma.weight"], params[a + "luma_cond.gamma.bias"])
-    beta = conv1x1(hcond, params[a + "luma_cond.beta.weight"], params[a + "luma_cond.beta.bias"])
-    alpha = params.get(a + "alpha")
-    qkv = luma_film(qkv, gamma, beta, luma if alpha is not None else None, None if alpha is None else alpha.reshape(1))
-    x1 = conv1x1(token_attention(qkv, heads), params[a + "proj.weight"], params.get(a + "proj.bias"), residual=x)
+    x1 = _luma_attention(x, luma, params, prefix + "attn.", heads, p("norm1.body.weight"), p("norm1.body.bias"), residual=x)
     f = prefix + "ffn."
     hid = conv1x1(x1, params[f + "pointwise1.weight"], params.get(f + "pointwise1.bias"), ln_weight=p("norm2.body.weight"), ln_bias=p("norm2.body.bias"))
     hid = dwconv3x3(hid, params[f + "depthwise.weight"], params.get(f + "depthwise.bias"), gelu=True)
@@ -517,13 +446,9 @@ def bayer_luma(mosaic: torch.Tensor, pattern: str = "rggb") -> torch.Tensor:
     if c != 1:
         raise RuntimeError("bayer_luma expects a one-channel mosaic")
     pat = {"rggb": 0, "bggr": 1, "grbg": 2, "gbrg": 3}[pattern.lower()]
-    lib = _lib.load()
-    sz = C.c_size_t()
-    _lib.check(lib.rf_bayer_luma_scratch_bytes(b, h, w, C.byref(sz)), "rf_bayer_luma_scratch_bytes")
-    scratch = _scratch(sz.value, mosaic)
+    scratch = _lib.scratch("rf_bayer_luma_scratch_bytes", mosaic, b, h, w)
     out = torch.empty_like(mosaic)
-    with torch.cuda.device(mosaic.device):
-        _lib.check(lib.rf_bayer_luma(_ptr(mosaic), _ptr(out), _ptr(scratch), b, h, w, pat, _stream(mosaic)), "rf_bayer_luma")
+    _lib.launch("rf_bayer_luma", mosaic, mosaic, out, scratch, b, h, w, pat)
     return out
 
 
@@ -542,14 +467,10 @@ def rfft2_polar(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """``f = torch.fft.rfft2(x, norm='ortho'); (f.abs() + 1e-6, f.angle())`` (FEB, RawFomer_WFB_FFAB/blocks.py:27-29)."""
     x = _chk(x, "x")
     b, c, h, w = x.shape
-    lib = _lib.load()
-    sz = C.c_size_t()
-    _lib.check(lib.rf_rfft2_polar_scratch_bytes(b * c, h, w, C.byref(sz)), "rf_rfft2_polar_scratch_bytes")
-    scratch = _scratch(sz.value, x)
+    scratch = _lib.scratch("rf_rfft2_polar_scratch_bytes", x, b * c, h, w)
     mag = torch.empty((b, c, h, w // 2 + 1), dtype=x.dtype, device=x.device)
     pha = torch.empty_like(mag)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.rf_rfft2_polar(_ptr(x), _ptr(mag), _ptr(pha), _ptr(scratch), b * c, h, w, _stream(x)), "rf_rfft2_polar")
+    _lib.launch("rf_rfft2_polar", x, x, mag, pha, scratch, b * c, h, w)
     return mag, pha
 
 
@@ -559,18 +480,10 @@ def polar_irfft2(mag: torch.Tensor, pha: torch.Tensor, width: int) -> torch.Tens
     b, c, h, wf = mag.shape
     if wf != width // 2 + 1:
         raise RuntimeError(f"half spectrum of width {wf} does not belong to an output width of {width}")
-    lib = _lib.load()
-    sz = C.c_size_t()
-    _lib.check(lib.rf_rfft2_polar_scratch_bytes(b * c, h, width, C.byref(sz)), "rf_rfft2_polar_scratch_bytes")
-    scratch = _scratch(sz.value, mag)
+    scratch = _lib.scratch("rf_rfft2_polar_scratch_bytes", mag, b * c, h, width)
     out = torch.empty((b, c, h, width), dtype=mag.dtype, device=mag.device)
-    with torch.cuda.device(mag.device):
-        _lib.check(lib.rf_polar_irfft2(_ptr(mag), _ptr(pha), _ptr(out), _ptr(scratch), b * c, h, width, _stream(mag)), "rf_polar_irfft2")
+    _lib.launch("rf_polar_irfft2", mag, mag, pha, out, scratch, b * c, h, width)
     return out
-
-
-def _ptr_array(ts):
-    return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
 
 
 def feb(x: torch.Tensor, params, prefix: str = "") -> torch.Tensor:
@@ -578,13 +491,9 @@ def feb(x: torch.Tensor, params, prefix: str = "") -> torch.Tensor:
     x = _chk(x, "x")
     b, c, h, w = x.shape
     ts = [_chk(params[prefix + k], k) for k in _FEB_KEYS]
-    lib = _lib.load()
-    sz = C.c_size_t()
-    _lib.check(lib.rf_feb_scratch_bytes(b, c, h, w, C.byref(sz)), "rf_feb_scratch_bytes")
-    scratch = _scratch(sz.value, x)
+    scratch = _lib.scratch("rf_feb_scratch_bytes", x, b, c, h, w)
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.rf_feb(_ptr(x), _ptr(out), _ptr_array(ts), _ptr(scratch), b, c, h, w, _stream(x)), "rf_feb")
+    _lib.launch("rf_feb", x, x, out, ts, scratch, b, c, h, w)
     return out
 
 
@@ -595,16 +504,16 @@ def ffab(x: torch.Tensor, params, prefix: str = "", out: Optional[torch.Tensor] 
     x = _chk(x, "x")
     b, c, h, w = x.shape
     ts = [_chk(params[prefix + k], k) for k in _FFAB_KEYS]
-    lib = _lib.load()
-    sz = C.c_size_t()
-    _lib.check(lib.rf_ffab_scratch_bytes(b, c, h, w, C.byref(sz)), "rf_ffab_scratch_bytes")
-    scratch = _scratch(sz.value, x)
-    if out is None:
-        out = torch.empty_like(x)
-    elif tuple(out.shape) != tuple(x.shape) or not out.is_contiguous() or out.dtype != torch.float32 or out.device != x.device:
-        raise RuntimeError(f"ffab: `out` must be a contiguous float32 tensor of shape {tuple(x.shape)} on {x.device}")
-    with torch.cuda.device(x.device):
-        _lib.check(lib.rf_ffab(_ptr(x), _ptr(out), _ptr_array(ts), _ptr(scratch), b, c, h, w, _stream(x)), "rf_ffab")
+    scratch = _lib.scratch("rf_ffab_scratch_bytes", x, b, c, h, w)
+    out = _out(out, x, "ffab")
+    _lib.launch("rf_ffab", x, x, out, ts, scratch, b, c, h, w)
+    return out
+
+
+def _affine_clamp_add(y: torch.Tensor, t: torch.Tensor, scale: float, shift: float, lo: float, hi: float) -> torch.Tensor:
+    """``t + clamp(scale * y + shift, lo, hi)`` (``rf_affine_clamp_add``) as a new tensor."""
+    out = torch.empty_like(t)
+    _lib.launch("rf_affine_clamp_add", t, y, t, out, t.numel(), scale, shift, lo, hi)
     return out
 
 
@@ -621,11 +530,7 @@ def wmb_ll_branch(x: torch.Tensor, params, prefix: str = "", high=None) -> torch
     if high is not None:
         d[n:].copy_(high(d[n:]))                                         # the caller's module (Mamba in the reference) on the high bands
     ffab(fea, params, prefix + "ffab.", out=d[:n])                        # LL band replaced in place: IWT reads [LL ; high] as it lies
-    y = iwt_init(d)
-    out = torch.empty_like(t)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().rf_affine_clamp_add(_ptr(y), _ptr(t), _ptr(out), t.numel(), 0.5, 0.5, 0.0, 1.0, _stream(x)), "rf_affine_clamp_add")
-    return out
+    return _affine_clamp_add(iwt_init(d), t, 0.5, 0.5, 0.0, 1.0)
 
 
 # ------------------------------------------------------------------------------------------ Mamba / WM / WMB
@@ -645,19 +550,22 @@ def mamba_param_shapes(d_model: int, d_state: int = 32, d_conv: int = 4, expand:
 
 
 def _shaped(params, prefix, keys, shapes, what):
+    """The tensors ``params[prefix + k]`` for ``k`` in ``keys``, each checked; against ``shapes[k]`` where that is given: a shape, or
+    an ``int`` for an element count.  A key ``None`` (a pointer the operator takes as null) gives ``None``."""
     ts = []
     for k in keys:
+        if k is None:
+            ts.append(None)
+            continue
         t = _chk(params[prefix + k], prefix + k)
-        if k in shapes and tuple(t.shape) != tuple(shapes[k]):
-            raise RuntimeError(f"{what}: {prefix + k} has shape {tuple(t.shape)}, expected {tuple(shapes[k])}")
+        want = shapes.get(k)
+        if isinstance(want, int):
+            if t.numel() != want:
+                raise RuntimeError(f"{what}: {prefix + k} has {t.numel()} elements, expected {want}")
+        elif want is not None and tuple(t.shape) != tuple(want):
+            raise RuntimeError(f"{what}: {prefix + k} has shape {tuple(t.shape)}, expected {tuple(want)}")
         ts.append(t)
     return ts
-
-
-def _workspace(nbytes: int, what: str, like: torch.Tensor) -> torch.Tensor:
-    if nbytes < 0:
-        _lib.check(nbytes, what)
-    return _scratch(nbytes, like)
 
 
 def mamba(u: torch.Tensor, params, prefix: str = "", d_state: int = 32, d_conv: int = 4, expand: int = 2,
@@ -670,12 +578,9 @@ def mamba(u: torch.Tensor, params, prefix: str = "", d_state: int = 32, d_conv: 
         raise RuntimeError(f"mamba: expected a 3-D tensor, got {tuple(u.shape)}")
     b, l, d = (u.shape[0], u.shape[2], u.shape[1]) if channel_major else tuple(u.shape)
     ts = _shaped(params, prefix, _MAMBA_KEYS, mamba_param_shapes(d, d_state, d_conv, expand), "mamba")
-    lib = _lib.load()
-    ws = _workspace(lib.rf_mamba_workspace_bytes(b, l, d, d_state, d_conv, expand), "rf_mamba_workspace_bytes", u)
+    ws = _lib.scratch("rf_mamba_workspace_bytes", u, b, l, d, d_state, d_conv, expand)
     out = torch.empty_like(u)
-    with torch.cuda.device(u.device):
-        _lib.check(lib.rf_mamba_forward(_ptr(u), _ptr(out), _ptr_array(ts), _ptr(ws), ws.numel(), b, l, d, d_state, d_conv, expand,
-                                        int(channel_major), _stream(u)), "rf_mamba_forward")
+    _lib.launch("rf_mamba_forward", u, u, out, ts, ws, ws.numel(), b, l, d, d_state, d_conv, expand, int(channel_major))
     return out
 
 
@@ -710,11 +615,9 @@ def wm(x: torch.Tensor, params, prefix: str = "") -> torch.Tensor:
     x = _chk(x, "x")
     n, c, h, w = x.shape
     ts = _shaped(params, prefix, _WM_KEYS, wm_param_shapes(c), "wm")
-    lib = _lib.load()
-    ws = _workspace(lib.rf_wm_workspace_bytes(n, c, h, w), "rf_wm_workspace_bytes", x)
+    ws = _lib.scratch("rf_wm_workspace_bytes", x, n, c, h, w)
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.rf_wm_forward(_ptr(x), _ptr(out), _ptr_array(ts), _ptr(ws), ws.numel(), n, c, h, w, _stream(x)), "rf_wm_forward")
+    _lib.launch("rf_wm_forward", x, x, out, ts, ws, ws.numel(), n, c, h, w)
     return out
 
 
@@ -756,12 +659,9 @@ def rfft2_polar_backward(x: torch.Tensor, grad_mag: torch.Tensor, grad_pha: torc
     if tuple(grad_mag.shape) != (b, c, h, w // 2 + 1) or tuple(grad_pha.shape) != tuple(grad_mag.shape):
         raise RuntimeError(f"rfft2_polar_backward: grad_mag / grad_pha must be {(b, c, h, w // 2 + 1)}, got {tuple(grad_mag.shape)} and "
                            f"{tuple(grad_pha.shape)}")
-    lib = _lib.load()
-    scratch = _workspace(lib.rf_rfft2_polar_backward_scratch_bytes(b * c, h, w), "rf_rfft2_polar_backward_scratch_bytes", x)
+    scratch = _lib.scratch("rf_rfft2_polar_backward_scratch_bytes", x, b * c, h, w)
     grad_x = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.rf_rfft2_polar_backward(_ptr(x), _ptr(grad_mag), _ptr(grad_pha), _ptr(grad_x), _ptr(scratch), b * c, h, w, _stream(x)),
-                   "rf_rfft2_polar_backward")
+    _lib.launch("rf_rfft2_polar_backward", x, x, grad_mag, grad_pha, grad_x, scratch, b * c, h, w)
     return grad_x
 
 
@@ -773,13 +673,23 @@ def polar_irfft2_backward(mag: torch.Tensor, pha: torch.Tensor, grad_out: torch.
     b, c, h, w = grad_out.shape
     if tuple(mag.shape) != (b, c, h, w // 2 + 1) or tuple(pha.shape) != tuple(mag.shape):
         raise RuntimeError(f"polar_irfft2_backward: mag / pha must be {(b, c, h, w // 2 + 1)}, got {tuple(mag.shape)} and {tuple(pha.shape)}")
-    lib = _lib.load()
-    scratch = _workspace(lib.rf_polar_irfft2_backward_scratch_bytes(b * c, h, w), "rf_polar_irfft2_backward_scratch_bytes", mag)
+    scratch = _lib.scratch("rf_polar_irfft2_backward_scratch_bytes", mag, b * c, h, w)
     grad_mag, grad_pha = torch.empty_like(mag), torch.empty_like(mag)
-    with torch.cuda.device(mag.device):
-        _lib.check(lib.rf_polar_irfft2_backward(_ptr(mag), _ptr(pha), _ptr(grad_out), _ptr(grad_mag), _ptr(grad_pha), _ptr(scratch), b * c, h, w,
-                                                _stream(mag)), "rf_polar_irfft2_backward")
+    _lib.launch("rf_polar_irfft2_backward", mag, mag, pha, grad_out, grad_mag, grad_pha, scratch, b * c, h, w)
     return grad_mag, grad_pha
+
+
+def _grads(grads, prefix, keys, shapes, like, who, zeros=()):
+    """The parameter gradients a backward operator writes, as ``(grads, its tensors in the order of keys, accumulate)``: new ones
+    of ``shapes`` beside ``like``, a checked tensor (``zeros``: the keys the operator may leave unwritten), or the caller's own, which the
+    operator adds to in place: they must be contiguous and of ``shapes``."""
+    accumulate = grads is not None
+    if grads is None:
+        grads = {prefix + k: (like.new_zeros if k in zeros else like.new_empty)(tuple(shapes[k])) for k in keys}
+    gs = _shaped(grads, prefix, keys, shapes, f"{who} (grads)")
+    if any(t is not grads[prefix + k] for k, t in zip(keys, gs)):
+        raise RuntimeError(f"{who}: the tensors of grads must be contiguous (they are written in place)")
+    return grads, gs, int(accumulate)
 
 
 def _backward(name, keys, shapes, x, params, grad_out, prefix, grads, geometry, trailing=(), buffers=()):
@@ -787,21 +697,11 @@ def _backward(name, keys, shapes, x, params, grad_out, prefix, grads, geometry, 
     ``shapes``, the workspace ``rf_<name>_backward_workspace_bytes(*geometry)`` asks for, and the call
     ``rf_<name>_backward(x, grad_out, grad_x, params, grads, workspace, bytes, *geometry, *trailing, accumulate, stream)``.
     ``buffers``: keys of ``shapes`` that the operator reads behind its parameters and that have no gradient."""
-    ts = _shaped(params, prefix, keys, shapes, f"{name}_backward")
-    read = ts + _shaped(params, prefix, buffers, shapes, f"{name}_backward")
-    accumulate = grads is not None
-    if grads is None:
-        grads = {prefix + k: torch.empty_like(t) for k, t in zip(keys, ts)}
-    gs = _shaped(grads, prefix, keys, shapes, f"{name}_backward (grads)")
-    if any(t.data_ptr() != grads[prefix + k].data_ptr() for k, t in zip(keys, gs)):
-        raise RuntimeError(f"{name}_backward: the tensors of grads must be contiguous (they are written in place)")
-    lib = _lib.load()
-    query, call = getattr(lib, f"rf_{name}_backward_workspace_bytes"), getattr(lib, f"rf_{name}_backward")
-    ws = _workspace(query(*geometry), f"rf_{name}_backward_workspace_bytes", x)
+    read = _shaped(params, prefix, tuple(keys) + tuple(buffers), shapes, f"{name}_backward")
+    grads, gs, accumulate = _grads(grads, prefix, keys, shapes, x, f"{name}_backward")
+    ws = _lib.scratch(f"rf_{name}_backward_workspace_bytes", x, *geometry)
     grad_x = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _lib.check(call(_ptr(x), _ptr(grad_out), _ptr(grad_x), _ptr_array(read), _ptr_array(gs), _ptr(ws), ws.numel(), *geometry, *trailing,
-                        int(accumulate), _stream(x)), f"rf_{name}_backward")
+    _lib.launch(f"rf_{name}_backward", x, x, grad_out, grad_x, read, gs, ws, ws.numel(), *geometry, *trailing, accumulate)
     return grad_x, grads
 
 
@@ -865,22 +765,16 @@ def wfb_feed_forward_train(x: torch.Tensor, params, prefix: str = "", eps: float
     ts = _shaped(params, prefix, _WFB_FF_KEYS + _WFB_FF_BUFFERS, shapes, "wfb_feed_forward_train")
     if update_running_stats and any(t.data_ptr() != params[prefix + k].data_ptr() for k, t in zip(_WFB_FF_BUFFERS, ts[len(_WFB_FF_KEYS):])):
         raise RuntimeError("wfb_feed_forward_train: the running statistics must be contiguous (they are updated in place)")
-    if batch_stats is None:
-        batch_stats = torch.empty((4, hidden), dtype=torch.float32, device=x.device)
-    elif (tuple(batch_stats.shape) != (4, hidden) or not batch_stats.is_contiguous() or batch_stats.dtype != torch.float32
-          or batch_stats.device != x.device):
-        raise RuntimeError(f"wfb_feed_forward_train: `batch_stats` must be a contiguous float32 tensor of shape {(4, hidden)} on {x.device}")
-    lib = _lib.load()
-    ws = _workspace(lib.rf_wfb_ffn_train_workspace_bytes(*geo), "rf_wfb_ffn_train_workspace_bytes", x)
+    batch_stats = _out(batch_stats, x, "wfb_feed_forward_train", (4, hidden), "batch_stats")
+    ws = _lib.scratch("rf_wfb_ffn_train_workspace_bytes", x, *geo)
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.rf_wfb_ffn_train_forward(_ptr(x), _ptr(out), _ptr_array(ts), _ptr(batch_stats), _ptr(ws), ws.numel(), *geo, float(eps),
-                                                float(momentum), int(update_running_stats), _stream(x)), "rf_wfb_ffn_train_forward")
-        if update_running_stats:
-            for name in ("rep_conv1", "rep_conv2"):
-                nbt = params.get(f"{prefix}{name}.bn.num_batches_tracked")
-                if nbt is not None:
-                    nbt += 1
+    _lib.launch("rf_wfb_ffn_train_forward", x, x, out, ts, batch_stats, ws, ws.numel(), *geo, float(eps), float(momentum),
+                int(update_running_stats))
+    if update_running_stats:
+        for name in ("rep_conv1", "rep_conv2"):
+            nbt = params.get(f"{prefix}{name}.bn.num_batches_tracked")
+            if nbt is not None:
+                nbt += 1
     return out
 
 
@@ -905,11 +799,7 @@ def wmb(x: torch.Tensor, params, prefix: str = "") -> torch.Tensor:
     t = wmb_ll_branch(x, params, prefix, high=lambda hi: wm(hi, params, prefix + "mb."))
     y = layernorm2d(t, params[prefix + "norm2.body.weight"], params.get(prefix + "norm2.body.bias"))
     hid = wfb_feed_forward(y, params, prefix + "ffn.")          # ffn(y) + y: the operator carries FeedForward's own identity
-    out = torch.empty_like(t)
-    with torch.cuda.device(t.device):                           # out = t + hid (an unbounded clamp is the identity)
-        _lib.check(_lib.load().rf_affine_clamp_add(_ptr(hid), _ptr(t), _ptr(out), t.numel(), 1.0, 0.0, float("-inf"), float("inf"), _stream(t)),
-                   "rf_affine_clamp_add")
-    return out
+    return _affine_clamp_add(hid, t, 1.0, 0.0, float("-inf"), float("inf"))     # t + hid (an unbounded clamp is the identity)
 
 
 # ------------------------------------------------------------------------------------------ the fused passes of the WFB handle's WMB block
@@ -922,9 +812,7 @@ def wmb_front(x: torch.Tensor, weight2: torch.Tensor, bias2: torch.Tensor) -> Tu
     if h2 % 2 or w2 % 4 or weight2.numel() != c or bias2.numel() != c:
         raise RuntimeError(f"wmb_front: needs an even height, a width in multiples of 4 and {c} LayerNorm weights (got {h2}x{w2})")
     t, bands = torch.empty_like(x), torch.empty((4 * b, c, h2 // 2, w2 // 2), dtype=x.dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().rf_wmb_front(_ptr(x), _ptr(t), _ptr(bands), _ptr(weight2), _ptr(bias2), b, c, h2 // 2, w2 // 2, _stream(x)),
-                   "rf_wmb_front")
+    _lib.launch("rf_wmb_front", x, x, t, bands, weight2, bias2, b, c, h2 // 2, w2 // 2)
     return t, bands
 
 
@@ -935,19 +823,16 @@ def wmb_back(bands: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
     if b4 % 4 or w % 2 or tuple(t.shape) != (b4 // 4, c, 2 * h, 2 * w):
         raise RuntimeError(f"wmb_back: bands {tuple(bands.shape)} and t {tuple(t.shape)} do not belong together (band width must be even)")
     out = torch.empty_like(t)
-    with torch.cuda.device(t.device):
-        _lib.check(_lib.load().rf_wmb_back(_ptr(bands), _ptr(t), _ptr(out), b4 // 4, c, h, w, _stream(t)), "rf_wmb_back")
+    _lib.launch("rf_wmb_back", t, bands, t, out, b4 // 4, c, h, w)
     return out
 
 
 def _grad_pair(grads, like, who):
     """``(pair, accumulate)`` for a ``(grad_weight, grad_bias)`` pair: a new one, or the caller's own, which the call adds to."""
-    if grads is None:
-        return (torch.empty_like(like), torch.empty_like(like)), 0
-    for g in grads:
-        if _chk(g, "grads") is not g or tuple(g.shape) != tuple(like.shape):
-            raise RuntimeError(f"{who}: the tensors of grads must be contiguous (they are written in place) and of shape {tuple(like.shape)}")
-    return grads, 1
+    shapes = {"weight": like.shape, "bias": like.shape}
+    named = None if grads is None else dict(zip(shapes, grads, strict=True))
+    _, gs, accumulate = _grads(named, "", tuple(shapes), shapes, like, who)
+    return (tuple(gs) if grads is None else grads), accumulate
 
 
 def wmb_front_backward(x: torch.Tensor, weight2: torch.Tensor, bias2: torch.Tensor, grad_t: torch.Tensor, grad_bands: torch.Tensor,
@@ -967,12 +852,9 @@ def wmb_front_backward(x: torch.Tensor, weight2: torch.Tensor, bias2: torch.Tens
     pair, acc = _grad_pair(grads, weight2, "wmb_front_backward")
     gw, gb = pair
     geo = (b, c, h2 // 2, w2 // 2)
-    lib = _lib.load()
-    ws = _workspace(lib.rf_wmb_front_backward_workspace_bytes(*geo), "rf_wmb_front_backward_workspace_bytes", x)
+    ws = _lib.scratch("rf_wmb_front_backward_workspace_bytes", x, *geo)
     grad_x = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.rf_wmb_front_backward(_ptr(x), _ptr(grad_t), _ptr(grad_x), _ptr(grad_bands), _ptr(weight2), _ptr(gw), _ptr(gb), _ptr(ws),
-                                             ws.numel(), *geo, float(grad_scale), acc, _stream(x)), "rf_wmb_front_backward")
+    _lib.launch("rf_wmb_front_backward", x, x, grad_t, grad_x, grad_bands, weight2, gw, gb, ws, ws.numel(), *geo, float(grad_scale), acc)
     return grad_x, pair
 
 
@@ -985,9 +867,7 @@ def wmb_back_backward(bands: torch.Tensor, grad_out: torch.Tensor) -> torch.Tens
         raise RuntimeError(f"wmb_back_backward: bands {tuple(bands.shape)} and grad_out {tuple(grad_out.shape)} do not belong together "
                            "(band width must be even)")
     grad_bands = torch.empty_like(bands)
-    with torch.cuda.device(bands.device):
-        _lib.check(_lib.load().rf_wmb_back_backward(_ptr(bands), _ptr(grad_out), _ptr(grad_bands), b4 // 4, c, h, w, _stream(bands)),
-                   "rf_wmb_back_backward")
+    _lib.launch("rf_wmb_back_backward", bands, bands, grad_out, grad_bands, b4 // 4, c, h, w)
     return grad_bands
 
 
@@ -999,18 +879,10 @@ def dwconv5x5_backward(x: torch.Tensor, weight: torch.Tensor, grad_out: torch.Te
     if tuple(weight.shape) != (c, 1, 5, 5) or tuple(grad_out.shape) != tuple(x.shape):
         raise RuntimeError(f"dwconv5x5_backward: weight {tuple(weight.shape)} / grad_out {tuple(grad_out.shape)} do not match x {tuple(x.shape)}")
     shapes = {"weight": (c, 1, 5, 5), "bias": (c,)}
-    acc = grads is not None
-    if grads is None:
-        grads = {k: torch.empty(s, dtype=x.dtype, device=x.device) for k, s in shapes.items()}
-    gs = _shaped(grads, "", ("weight", "bias"), shapes, "dwconv5x5_backward (grads)")
-    if any(t.data_ptr() != grads[k].data_ptr() for k, t in zip(shapes, gs)):
-        raise RuntimeError("dwconv5x5_backward: the tensors of grads must be contiguous (they are written in place)")
-    lib = _lib.load()
-    ws = _workspace(lib.rf_dwconv5x5_backward_workspace_bytes(b, c, h, w), "rf_dwconv5x5_backward_workspace_bytes", x)
+    grads, gs, acc = _grads(grads, "", tuple(shapes), shapes, x, "dwconv5x5_backward")
+    ws = _lib.scratch("rf_dwconv5x5_backward_workspace_bytes", x, b, c, h, w)
     grad_x = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.rf_dwconv5x5_backward(_ptr(x), _ptr(grad_out), _ptr(grad_x), _ptr(weight), _ptr(gs[0]), _ptr(gs[1]), _ptr(ws), ws.numel(),
-                                             b, c, h, w, int(acc), _stream(x)), "rf_dwconv5x5_backward")
+    _lib.launch("rf_dwconv5x5_backward", x, x, grad_out, grad_x, weight, *gs, ws, ws.numel(), b, c, h, w, acc)
     return grad_x, grads
 
 
@@ -1036,21 +908,12 @@ def illumination_estimator_backward(img: torch.Tensor, params, grad_fea: torch.T
         grad_map = _chk(grad_map, "grad_map")
         if tuple(grad_map.shape) != (b, co, h, w):
             raise RuntimeError(f"illumination_estimator_backward: grad_map {tuple(grad_map.shape)}, expected {(b, co, h, w)}")
-    acc = grads is not None
-    if grads is None:
-        grads = {prefix + k: (torch.zeros_like(t) if k.startswith("conv2.") and grad_map is None else torch.empty_like(t))
-                 for k, t in zip(_ILLU_KEYS, ts)}
-    gs = _shaped(grads, prefix, _ILLU_KEYS, shapes, "illumination_estimator_backward (grads)")
-    if any(t.data_ptr() != grads[prefix + k].data_ptr() for k, t in zip(_ILLU_KEYS, gs)):
-        raise RuntimeError("illumination_estimator_backward: the tensors of grads must be contiguous (they are written in place)")
+    grads, gs, acc = _grads(grads, prefix, _ILLU_KEYS, shapes, img, "illumination_estimator_backward",
+                            zeros=() if grad_map is not None else ("conv2.weight", "conv2.bias"))
     geo = (b, c, cm, co, h, w)
-    lib = _lib.load()
-    ws = _workspace(lib.rf_illumination_estimator_backward_workspace_bytes(*geo, int(grad_map is not None)),
-                    "rf_illumination_estimator_backward_workspace_bytes", img)
+    ws = _lib.scratch("rf_illumination_estimator_backward_workspace_bytes", img, *geo, int(grad_map is not None))
     grad_img = torch.empty_like(img)
-    with torch.cuda.device(img.device):
-        _lib.check(lib.rf_illumination_estimator_backward(_ptr(img), _ptr(grad_fea), _ptr(grad_map), _ptr(grad_img), _ptr_array(ts), _ptr_array(gs),
-                                                          _ptr(ws), ws.numel(), *geo, int(acc), _stream(img)), "rf_illumination_estimator_backward")
+    _lib.launch("rf_illumination_estimator_backward", img, img, grad_fea, grad_map, grad_img, ts, gs, ws, ws.numel(), *geo, acc)
     return grad_img, grads
 
 
@@ -1063,21 +926,12 @@ def layernorm2d_backward(x: torch.Tensor, weight: torch.Tensor, grad_out: torch.
     b, c, h, w = x.shape
     if weight.numel() != c or tuple(grad_out.shape) != tuple(x.shape) or (residual is not None and tuple(residual.shape) != tuple(x.shape)):
         raise RuntimeError(f"layernorm2d_backward: x {tuple(x.shape)}, grad_out {tuple(grad_out.shape)}: equal shapes and {c} weights are needed")
-    residual = None if residual is None else _chk(residual, "residual")
+    residual = _opt(residual, "residual")
     shapes = {"weight": (c,), "bias": (c,)}
-    acc = grads is not None
-    if grads is None:
-        grads = {k: torch.empty(s, dtype=x.dtype, device=x.device) for k, s in shapes.items()}
-    gs = _shaped(grads, "", ("weight", "bias"), shapes, "layernorm2d_backward (grads)")
-    if any(t.data_ptr() != grads[k].data_ptr() for k, t in zip(shapes, gs)):
-        raise RuntimeError("layernorm2d_backward: the tensors of grads must be contiguous (they are written in place)")
-    lib = _lib.load()
-    ws = _workspace(lib.rf_layernorm2d_backward_workspace_bytes(b, c, h, w), "rf_layernorm2d_backward_workspace_bytes", x)
+    grads, gs, acc = _grads(grads, "", tuple(shapes), shapes, x, "layernorm2d_backward")
+    ws = _lib.scratch("rf_layernorm2d_backward_workspace_bytes", x, b, c, h, w)
     grad_x = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.rf_layernorm2d_backward(_ptr(x), _ptr(grad_out), _ptr(grad_x), _ptr(weight.reshape(-1)), _ptr(gs[0]), _ptr(gs[1]),
-                                               _ptr(residual), _ptr(ws), ws.numel(), b, c, h, w, float(eps), int(acc), _stream(x)),
-                   "rf_layernorm2d_backward")
+    _lib.launch("rf_layernorm2d_backward", x, x, grad_out, grad_x, weight, *gs, residual, ws, ws.numel(), b, c, h, w, float(eps), acc)
     return grad_x, grads
 
 
@@ -1089,8 +943,7 @@ def wmb_ffn_tail(t: torch.Tensor, y: torch.Tensor, weight: torch.Tensor, bias: t
     if w % 4 or tuple(y.shape) != tuple(t.shape) or weight.numel() != c or bias.numel() != c:
         raise RuntimeError(f"wmb_ffn_tail: t {tuple(t.shape)}, y {tuple(y.shape)}: equal shapes and a width in multiples of 4 are needed")
     out = torch.empty_like(t)
-    with torch.cuda.device(t.device):
-        _lib.check(_lib.load().rf_wmb_ffn_sum(_ptr(t), _ptr(y), _ptr(out), _ptr(weight), _ptr(bias), b, c, h, w, _stream(t)), "rf_wmb_ffn_sum")
+    _lib.launch("rf_wmb_ffn_sum", t, t, y, out, weight, bias, b, c, h, w)
     return out
 
 
@@ -1104,25 +957,17 @@ def tc_spatial(feat: torch.Tensor, guide: torch.Tensor, params, prefix: str = ""
     b, c, h, w = feat.shape
     if tuple(guide.shape) != (b, 7, h, w):
         raise RuntimeError(f"tc_spatial: guide must be {(b, 7, h, w)}, got {tuple(guide.shape)}")
-    prm = []
-    for key, shape in (("color_attention.0.weight", (c, 5, 3, 3)), ("color_attention.0.bias", (c,)), ("low_attn.0.weight", (c, 1, 3, 3)),
-                       ("low_attn.0.bias", (c,)), ("high_attn.0.weight", (c, 1, 3, 3)), ("high_attn.0.bias", (c,))):
-        t = _chk(params[prefix + key], key)
-        if tuple(t.shape) != shape:
-            raise RuntimeError(f"tc_spatial: {key} must be {shape}, got {tuple(t.shape)}")
-        prm.append(t)
-    out = torch.empty_like(feat) if out is None else out
-    if tuple(out.shape) != tuple(feat.shape) or not out.is_contiguous() or out.dtype != torch.float32 or out.device != feat.device:
-        raise RuntimeError("tc_spatial: out must be a contiguous float32 tensor of feat's shape on its device")
-    with torch.cuda.device(feat.device):
-        _lib.check(_lib.load().rf_tc_spatial(_ptr(feat), _ptr(guide), *[_ptr(t) for t in prm], _ptr(out), b, c, h, w, _stream(feat)),
-                   "rf_tc_spatial")
+    shapes = {"color_attention.0.weight": (c, 5, 3, 3), "color_attention.0.bias": (c,), "low_attn.0.weight": (c, 1, 3, 3),
+              "low_attn.0.bias": (c,), "high_attn.0.weight": (c, 1, 3, 3), "high_attn.0.bias": (c,)}
+    prm = _shaped(params, prefix, tuple(shapes), shapes, "tc_spatial")
+    out = _out(out, feat, "tc_spatial")
+    _lib.launch("rf_tc_spatial", feat, feat, guide, *prm, out, b, c, h, w)
     return out
 
 
 def tc_nblk(h: int, w: int) -> int:
     """Blocks per image of ``tc_residual``'s pooling sums: 1024 consecutive pixels each where ``w % 4 == 0``, else 256."""
-    n = _lib.load().rf_tc_nblk(int(h), int(w))
+    n = _lib.load().rf_tc_nblk(int(h), int(w))     # a count, or a negative status: neither of _lib's two size conventions
     _lib.check(min(n, 0), "rf_tc_nblk")
     return n
 
@@ -1135,14 +980,11 @@ def tc_residual(xs: torch.Tensor, r: torch.Tensor, out: Optional[torch.Tensor] =
     b, c, h, w = xs.shape
     if tuple(r.shape) != tuple(xs.shape):
         raise RuntimeError(f"tc_residual: xs {tuple(xs.shape)} and r {tuple(r.shape)} differ")
-    out = torch.empty_like(xs) if out is None else out
-    if tuple(out.shape) != tuple(xs.shape) or not out.is_contiguous() or out.dtype != torch.float32 or out.device != xs.device:
-        raise RuntimeError("tc_residual: out must be a contiguous float32 tensor of xs's shape on its device")
+    out = _out(out, xs, "tc_residual")
     if c > 512:
         raise RuntimeError(f"tc_residual: C={c} > 512 not supported")
     partial = torch.empty((b, tc_nblk(h, w), c), dtype=torch.float32, device=xs.device)
-    with torch.cuda.device(xs.device):
-        _lib.check(_lib.load().rf_tc_residual(_ptr(xs), _ptr(r), _ptr(out), _ptr(partial), b, c, h, w, _stream(xs)), "rf_tc_residual")
+    _lib.launch("rf_tc_residual", xs, xs, r, out, partial, b, c, h, w)
     return out, partial
 
 
@@ -1152,18 +994,12 @@ def tc_color_head(x: torch.Tensor, params, prefix: str = "") -> torch.Tensor:
     x = _chk(x, "x")
     if x.dim() < 3 or x.shape[1] != 3:
         raise RuntimeError(f"tc_color_head: expected [B,3,...], got {tuple(x.shape)}")
-    prm = []
-    for key, n in (("gamma_param", 1), ("color_transform.0.weight", 192), ("color_transform.0.bias", 64), ("color_transform.2.weight", 192),
-                   ("color_transform.2.bias", 3), ("tone_curve.0.weight", 32), ("tone_curve.0.bias", 32), ("tone_curve.2.weight", 32),
-                   ("tone_curve.2.bias", 1)):
-        t = _chk(params[prefix + key], key)
-        if t.numel() != n:
-            raise RuntimeError(f"tc_color_head: {key} must have {n} elements, got {t.numel()}")
-        prm.append(t)
+    counts = {"gamma_param": 1, "color_transform.0.weight": 192, "color_transform.0.bias": 64, "color_transform.2.weight": 192,
+              "color_transform.2.bias": 3, "tone_curve.0.weight": 32, "tone_curve.0.bias": 32, "tone_curve.2.weight": 32,
+              "tone_curve.2.bias": 1}
+    prm = _shaped(params, prefix, tuple(counts), counts, "tc_color_head")      # element counts, not shapes
     out = x.clone()
-    b = x.shape[0]
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().rf_tc_color_head(_ptr(out), *[_ptr(t) for t in prm], b, x[0, 0].numel(), _stream(x)), "rf_tc_color_head")
+    _lib.launch("rf_tc_color_head", x, out, *prm, x.shape[0], x[0, 0].numel())
     return out
 
 
@@ -1176,8 +1012,7 @@ def tc_pyramid(src: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     b, _, h, w = src.shape
     ll = torch.empty((b, 1, (h + 1) // 2, (w + 1) // 2), dtype=torch.float32, device=src.device)
     mag = torch.empty_like(ll)
-    with torch.cuda.device(src.device):
-        _lib.check(_lib.load().rf_tc_pyramid(_ptr(src), _ptr(ll), _ptr(mag), b, h, w, _stream(src)), "rf_tc_pyramid")
+    _lib.launch("rf_tc_pyramid", src, src, ll, mag, b, h, w)
     return ll, mag
 
 
@@ -1185,21 +1020,12 @@ def tc_pyramid(src: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
 def _ml_step_params(params, prefix: str, step: int, levels: int, c: int, who: str):
     """The weights of one residual step of ``FLCA_Pyramid`` from the block's ``state_dict``: ``(w_a, w_b, gate_w, gate_b)``."""
     if step == levels:
-        spec = (("chroma_attn.0.weight", (c, 2, 3, 3)), None, ("chroma_gate.weight", (1, 1, 1, 1)), ("chroma_gate.bias", (1,)))
+        keys = ("chroma_attn.0.weight", None, "chroma_gate.weight", "chroma_gate.bias")
+        shapes = {"chroma_attn.0.weight": (c, 2, 3, 3), "chroma_gate.weight": (1, 1, 1, 1), "chroma_gate.bias": (1,)}
     else:
-        spec = ((f"low_attn.{step}.0.weight", (c, 1, 3, 3)), (f"high_attn.{step}.0.weight", (c, 1, 3, 3)),
-                (f"freq_gate_head.{step}.weight", (2, 2, 1, 1)), (f"freq_gate_head.{step}.bias", (2,)))
-    out = []
-    for item in spec:
-        if item is None:
-            out.append(None)
-            continue
-        key, shape = item
-        t = _chk(params[prefix + key], key)
-        if tuple(t.shape) != shape:
-            raise RuntimeError(f"{who}: {key} must be {shape}, got {tuple(t.shape)}")
-        out.append(t)
-    return out
+        keys = (f"low_attn.{step}.0.weight", f"high_attn.{step}.0.weight", f"freq_gate_head.{step}.weight", f"freq_gate_head.{step}.bias")
+        shapes = dict(zip(keys, ((c, 1, 3, 3), (c, 1, 3, 3), (2, 2, 1, 1), (2,))))
+    return _shaped(params, prefix, keys, shapes, who)
 
 
 def _ml_step_inputs(x, guide, means, step, levels, who):
@@ -1217,13 +1043,6 @@ def _ml_step_inputs(x, guide, means, step, levels, who):
     return x, guide, means, step, levels
 
 
-def _ml_out(out, x, who):
-    out = torch.empty_like(x) if out is None else out
-    if tuple(out.shape) != tuple(x.shape) or not out.is_contiguous() or out.dtype != torch.float32 or out.device != x.device:
-        raise RuntimeError(f"{who}: out must be a contiguous float32 tensor of x's shape on its device")
-    return out
-
-
 def ml_modulate(x: torch.Tensor, guide: torch.Tensor, means: torch.Tensor, step: int, levels: int, params, prefix: str = "",
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The gated spatial attention of one step of ``FLCA_Pyramid.forward`` (MultiLvlFrequencyawareLumaChromaAttentionRAWFormer.py
@@ -1233,10 +1052,8 @@ def ml_modulate(x: torch.Tensor, guide: torch.Tensor, means: torch.Tensor, step:
     x, guide, means, step, levels = _ml_step_inputs(x, guide, means, step, levels, "ml_modulate")
     b, c, h, w = x.shape
     prm = _ml_step_params(params, prefix, step, levels, c, "ml_modulate")
-    out = _ml_out(out, x, "ml_modulate")
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().rf_ml_modulate(_ptr(x), _ptr(guide), _ptr(means), step, levels, *[_ptr(t) for t in prm], _ptr(out), b, c, h, w,
-                                              _stream(x)), "rf_ml_modulate")
+    out = _out(out, x, "ml_modulate")
+    _lib.launch("rf_ml_modulate", x, x, guide, means, step, levels, *prm, out, b, c, h, w)
     return out
 
 
@@ -1249,17 +1066,12 @@ def ml_step_fused(x: torch.Tensor, guide: torch.Tensor, means: torch.Tensor, ste
     x, guide, means, step, levels = _ml_step_inputs(x, guide, means, step, levels, "ml_step_fused")
     b, c, h, w = x.shape
     prm = _ml_step_params(params, prefix, step, levels, c, "ml_step_fused")
-    for key, shape in (("res_proj.0.weight", (c, c, 1, 1)), ("res_proj.0.bias", (c,)), ("res_proj.2.weight", (c, c, 1, 1)), ("res_proj.2.bias", (c,))):
-        t = _chk(params[prefix + key], key)
-        if tuple(t.shape) != shape:
-            raise RuntimeError(f"ml_step_fused: {key} must be {shape}, got {tuple(t.shape)}")
-        prm.append(t)
-    out = _ml_out(out, x, "ml_step_fused")
+    res = {"res_proj.0.weight": (c, c, 1, 1), "res_proj.0.bias": (c,), "res_proj.2.weight": (c, c, 1, 1), "res_proj.2.bias": (c,)}
+    prm += _shaped(params, prefix, tuple(res), res, "ml_step_fused")
+    out = _out(out, x, "ml_step_fused")
     # the library refuses an unsupported shape before it reads `partial`: one block of 1024 pixels is the most any shape needs there
     partial = torch.empty((b, -(-h * w // 1024), c), dtype=torch.float32, device=x.device) if sums else None
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().rf_ml_step_fused(_ptr(x), _ptr(guide), _ptr(means), step, levels, *[_ptr(t) for t in prm], _ptr(out),
-                                                _ptr(partial), b, c, h, w, _stream(x)), "rf_ml_step_fused")
+    _lib.launch("rf_ml_step_fused", x, x, guide, means, step, levels, *prm, out, partial, b, c, h, w)
     return (out, partial) if sums else out
 
 
@@ -1271,8 +1083,7 @@ def ml_residual(x: torch.Tensor, r: torch.Tensor, out: Optional[torch.Tensor] = 
         raise RuntimeError(f"ml_residual: x {tuple(x.shape)} and r {tuple(r.shape)} differ")
     if x.numel() == 0:
         raise RuntimeError("ml_residual: empty tensor")
-    out = _ml_out(out, x, "ml_residual")
+    out = _out(out, x, "ml_residual")
     b, c, h, w = x.shape if x.dim() == 4 else (1, 1, 1, x.numel())
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().rf_ml_residual(_ptr(x), _ptr(r), _ptr(out), b, c, h, w, _stream(x)), "rf_ml_residual")
+    _lib.launch("rf_ml_residual", x, x, r, out, b, c, h, w)
     return out

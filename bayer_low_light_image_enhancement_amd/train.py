@@ -17,7 +17,6 @@ Around the step, ``fit`` is the reference's epoch loop (train.py:113-175): ``war
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 import os
 import random
@@ -108,23 +107,19 @@ class Trainer:
         self.loss_mode = {"l1": LOSS_L1, "charbonnier": LOSS_CHARBONNIER}[loss]
         self.loss_eps = float(charbonnier_eps)
         self.clamp_pred = bool(clamp_pred)       # the criterion sees clamp(pred, 0, 1): train.py:139
-        lib = _lib.load()
         self.state = model._state_for(dev)
-        n = C.c_size_t()
-        _lib.check(lib.rf_flat_param_floats(self.state.handle, C.byref(n)), "rf_flat_param_floats")
-        self.n = n.value
+        self.n = _lib.size("rf_flat_param_floats", self.state.handle)
         self.flat = torch.zeros(self.n, dtype=torch.float32, device=dev)
         params = dict(model.named_parameters())
-        off = C.c_size_t()
         self.slices = {}
         with torch.no_grad():
             for i, k in enumerate(model._param_names):
-                _lib.check(lib.rf_flat_offset(self.state.handle, i, C.byref(off)), "rf_flat_offset")
+                off = _lib.size("rf_flat_offset", self.state.handle, i)
                 p = params[k]
-                view = self.flat[off.value: off.value + p.numel()].view(p.shape)
+                view = self.flat[off: off + p.numel()].view(p.shape)
                 view.copy_(p)
                 p.data = view                       # the module's parameters ARE the flat buffer from now on
-                self.slices[k] = (off.value, p.numel())
+                self.slices[k] = (off, p.numel())
         self.grads = torch.zeros_like(self.flat)
         self.m = torch.zeros_like(self.flat)
         self.v = torch.zeros_like(self.flat)
@@ -149,7 +144,6 @@ class Trainer:
     def forward_backward(self, x: torch.Tensor, gt: torch.Tensor, want_pred: bool = False, loss_out: Optional[torch.Tensor] = None):
         """Loss (device scalar; written into ``loss_out``, one float32 on the device, when given) and, in ``self.grads``, this
         rank's gradient of the mean loss over ITS images."""
-        lib = _lib.load()
         x, gt = x.detach().float().contiguous(), gt.detach().float().contiguous()
         b, c, h, w = x.shape
         if c != 1 or h % 16 or w % 64:
@@ -159,25 +153,21 @@ class Trainer:
         H, W = h // 2, w // 2
         with torch.cuda.device(x.device):
             self.model._sync_params(self.state, x.device, pack=False)   # the (flat-buffer) pointers, once: rf_train_step reads raw weights
-            sz = C.c_size_t()
-            _lib.check(lib.rf_train_workspace_bytes(self.state.handle, b, H, W, C.byref(sz)), "rf_train_workspace_bytes")
-            if self.workspace is None or self.workspace.numel() < sz.value:
+            need = _lib.size("rf_train_workspace_bytes", self.state.handle, b, H, W)
+            if self.workspace is None or self.workspace.numel() < need:
                 self.workspace = None
-                self.workspace = torch.empty(sz.value, dtype=torch.uint8, device=x.device)
+                self.workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
             pred = torch.empty_like(gt) if want_pred else None
-            stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
             import torch.distributed as dist
             overlapped = self.overlap and dist.is_initialized() and (dist.get_world_size(self.group) > 1 or self.overlap_always)
-            _lib.check(lib.rf_set_grad_ready(self.state.handle, self._ready_cb if overlapped else _lib.GRAD_READY_FN(), None), "rf_set_grad_ready")
+            _lib.call("rf_set_grad_ready", self.state.handle, self._ready_cb if overlapped else _lib.GRAD_READY_FN(), None)
             self.reducer.begin()                # waits for a previous round's all-reduces: they write into self.grads
-            _lib.check(lib.rf_set_loss_clamp(self.state.handle, int(self.clamp_pred)), "rf_set_loss_clamp")
+            _lib.call("rf_set_loss_clamp", self.state.handle, int(self.clamp_pred))
             loss_dev = self.loss_dev if loss_out is None else loss_out
             if loss_dev.dtype != torch.float32 or loss_dev.numel() != 1 or loss_dev.device != x.device:
                 raise RuntimeError("loss_out must be one float32 on the input's device")
-            _lib.check(lib.rf_train_step(self.state.handle, C.c_void_p(x.data_ptr()), C.c_void_p(gt.data_ptr()), C.c_void_p(self.grads.data_ptr()),
-                                         C.c_void_p(loss_dev.data_ptr()), C.c_void_p(pred.data_ptr() if want_pred else None),
-                                         C.c_void_p(self.workspace.data_ptr()), self.workspace.numel(), b, H, W, self.loss_mode, self.loss_eps,
-                                         stream), "rf_train_step")
+            _lib.launch("rf_train_step", x, self.state.handle, x, gt, self.grads, loss_dev, pred, self.workspace, self.workspace.numel(),
+                        b, H, W, self.loss_mode, self.loss_eps)
             self._reduced = overlapped          # the buckets are on the wire (or done); optimizer_step waits for them
         return (loss_dev, pred) if want_pred else loss_dev
 
@@ -190,13 +180,8 @@ class Trainer:
         else:
             allreduce_flat(self.grads, self.group)
         self.step_no += 1
-        lib = _lib.load()
-        dev = self.flat.device
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(lib.rf_adam_step(C.c_void_p(self.flat.data_ptr()), C.c_void_p(self.grads.data_ptr()), C.c_void_p(self.m.data_ptr()),
-                                        C.c_void_p(self.v.data_ptr()), self.n, self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
-                                        int(self.decoupled), self.step_no, 1.0 / world, stream), "rf_adam_step")
+        _lib.launch("rf_adam_step", self.flat, self.flat, self.grads, self.m, self.v, self.n, self.lr, self.betas[0], self.betas[1], self.eps,
+                    self.wd, int(self.decoupled), self.step_no, 1.0 / world)
         self.model.invalidate_packed()          # the weights moved: packed copies are stale
 
     def step(self, x: torch.Tensor, gt: torch.Tensor, loss_out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -116,6 +116,37 @@ def test_layernorm(ops, g, device):
     close(ops.layernorm2d(x.to(device), w.to(device), b.to(device)), R.layernorm2d(x, w, b))
 
 
+def test_strided_optional_tensors_are_copied_and_kept(ops, device):
+    """An optional or parameter tensor that is not contiguous is copied for the kernel, and the copy lives until the launch has
+    been issued: a strided bias / residual gives the bits of its contiguous twin even when memory of the copy's size is freed
+    and allocated again before the device is synchronised, and the caller's tensors are not written.  (dwgate3x3 once released
+    its copy of ``ba`` before it made the one of ``bb``: the allocator handed the block out again and the kernel read ``bb`` twice.)"""
+    c = 8
+    x = rnd("st.x", (2, c, 4, 8)).to(device)
+    wide = {k: rnd("st." + k, (2 * c,)).to(device) for k in ("ln_b", "dw_b", "ba", "bb", "pw_b")}      # the vectors: every second element
+    res2 = rnd("st.res", (2, 2 * c, 4, 8)).to(device)                                                     # the residual: every second channel
+    ln_w, dw_w = rnd("st.ln_w", (c,), 0.5, 1.5).to(device), rnd("st.dw_w", (c, 1, 3, 3)).to(device)
+    wa, wb, pw_w = rnd("st.wa", (c, 1, 3, 3)).to(device), rnd("st.wb", (c, 1, 3, 3)).to(device), rnd("st.pw_w", (c, c, 1, 1)).to(device)
+    before = {**{k: v.clone() for k, v in wide.items()}, "res": res2.clone()}
+
+    def run(v, res):
+        return (ops.layernorm2d(x, ln_w, v["ln_b"]), ops.dwconv3x3(x, dw_w, v["dw_b"]), ops.dwgate3x3(x, wa, v["ba"], wb, v["bb"]),
+                ops.conv1x1(x, pw_w, v["pw_b"], residual=res))
+
+    want = run({k: v[::2].contiguous() for k, v in wide.items()}, res2[:, ::2].contiguous())
+    torch.cuda.synchronize()
+    strided, strided_res = {k: v[::2] for k, v in wide.items()}, res2[:, ::2]
+    assert not strided_res.is_contiguous() and not any(v.is_contiguous() for v in strided.values())
+    spare = [torch.empty(n, device=device) for n in (c, x.numel())]          # the sizes of the copies: a vector, the residual
+    got = run(strided, strided_res)
+    del spare
+    spare = [torch.full((n,), float("nan"), device=device) for n in (c, x.numel())]
+    torch.cuda.synchronize()
+    for name, a, b in zip(("layernorm2d", "dwconv3x3", "dwgate3x3", "conv1x1"), got, want):
+        assert torch.equal(a, b), name
+    assert all(torch.equal(wide[k], before[k]) for k in wide) and torch.equal(res2, before["res"])
+
+
 @pytest.mark.parametrize("c1,c2,cout,hw", [(32, 0, 96, (16, 16)), (64, 0, 32, (8, 24)), (16, 16, 16, (16, 8)),
                                            (48, 48, 48, (8, 8)), (256, 0, 768, (4, 4)), (24, 0, 80, (5, 7)),
                                            (128, 128, 128, (16, 16)), (32, 0, 64, (64, 64)),
