@@ -155,6 +155,8 @@ SIGNATURES = {
     "rf_illumination_estimator_backward": (_i, [_vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "rf_layernorm2d_backward_workspace_bytes": (C.c_longlong, [_i, _i, _i, _i]),
     "rf_layernorm2d_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _f, _i, _vp]),
+    "rf_wmb_backward_workspace_bytes": (C.c_longlong, [_i, _i, _i, _i, _i]),
+    "rf_wmb_backward": (_i, [_vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _sz, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
     "rf_tc_spatial":(_i, [_vp] * 9 + [_i, _i, _i, _i, _vp]),
     "rf_tc_nblk": (_i, [_i, _i]),
     "rf_tc_residual": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

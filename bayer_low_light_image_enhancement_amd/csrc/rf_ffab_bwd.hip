@@ -396,8 +396,10 @@ long long fft_bwd_scratch(const char* who, int planes, int h, int w) {
     return rc ? rc : (long long)((size_t)planes * h * p.wf * sizeof(float2));
 }
 
+}  // namespace
+
 // floats of tensor i of the pointer arrays (state_dict order: weight, bias, weight, bias, ...)
-size_t feb_prm_floats(int i, int nc) { return i % 2 == 0 ? (size_t)nc * nc : (size_t)nc; }
+static size_t feb_prm_floats(int i, int nc) { return i % 2 == 0 ? (size_t)nc * nc : (size_t)nc; }
 
 size_t ffab_prm_floats(int i, int nc) {
     if (i < 50) return feb_prm_floats(i, nc);                 // conv0.0 and the four nc blocks
@@ -405,7 +407,6 @@ size_t ffab_prm_floats(int i, int nc) {
     return j < 12 ? feb_prm_floats(j, 2 * nc) : j == 12 ? (size_t)2 * nc * nc : (size_t)nc;
 }
 
-}  // namespace
 }  // namespace rf
 
 using namespace rf;

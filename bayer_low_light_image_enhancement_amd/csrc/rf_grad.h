@@ -82,4 +82,11 @@ struct BackwardArgs {
 // from everything else it writes.  Inputs may overlap each other.  Nothing is dereferenced but the two pointer arrays.
 int check_backward_args(const BackwardArgs& c, const std::function<size_t(int)>& prm_floats);
 
+// floats of tensor i of an operator's pointer arrays, in the order of its ops.*_param_shapes: what a schedule over several
+// operators (rf_wmb_block_bwd.hip) hands to check_backward_args for the tensors of all of them
+size_t ffab_prm_floats(int i, int nc);                        // 92
+size_t wm_prm_floats(int i, int c);                           // 17
+size_t wfb_prm_floats(int i, int dim, int hidden);            // 12 parameters, then the 4 BatchNorm buffers
+size_t illu_prm_floats(int i, int C, int Cm, int Co);         // 6
+
 }  // namespace rf

@@ -409,6 +409,9 @@ int wfb_ffn_nblk(int h, int w) {
 enum { kWin, kBin, kWd, kBd, kWout, kBout, kW1, kG1, kB1, kW2, kG2, kB2, kRm1, kRv1, kRm2, kRv2, kTensors };
 constexpr int kParams = 12;
 
+}  // namespace
+
+// rf_grad.h declares this one: the block schedule of rf_wmb_block_bwd.hip checks ffn's tensors with it
 size_t wfb_prm_floats(int i, int dim, int hidden) {
     const size_t D = dim, C = hidden;
     switch (i) {
@@ -418,6 +421,8 @@ size_t wfb_prm_floats(int i, int dim, int hidden) {
         default: return C;
     }
 }
+
+namespace {
 
 int wfb_check_geometry(const char* who, int B, int dim, int hidden, int h, int w, bool training) {
     RF_CHECK_ARG(B > 0 && dim > 0 && hidden > 0 && h > 0 && w > 0, "%s: sizes must be positive (B %d, dim %d, hidden %d, %d x %d)", who, B, dim,

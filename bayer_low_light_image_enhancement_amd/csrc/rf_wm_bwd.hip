@@ -214,7 +214,7 @@ static int wm_bwd_plan(const char* who, int n, int c, int h, int w, WmBwdPlan* p
 }
 
 // floats of tensor i of the 17 of the pointer arrays, in ops.wm_param_shapes' order
-static size_t wm_prm_floats(int i, int c) {
+size_t wm_prm_floats(int i, int c) {
     if (i >= 6 && i < 15) return mamba_prm_floats(i - 6, c, kN, kDc, 2);                           // model1
     const size_t C = c, floats[6] = {2 * C * C * 9, 2 * C, C * 2 * C * 9, C, C, C};                // convb.0, convb.2, ln
     return i < 6 ? floats[i] : i == 15 ? C * C * 9 : C;                                            // smooth

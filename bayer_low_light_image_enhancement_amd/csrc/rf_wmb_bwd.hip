@@ -420,7 +420,7 @@ static int run_dw5_backward(const float* x, const float* dy, float* dx, const fl
 // ---- Illumination_Estimator.  prm: conv1.weight [Cm][C + 1], conv1.bias, depth_conv.weight [Cm][25], depth_conv.bias,
 // conv2.weight [Co][Cm], conv2.bias
 enum { kW1, kB1, kWd, kBd, kW2, kB2, kIlluPrm };
-static size_t illu_prm_floats(int i, int C, int Cm, int Co) {
+size_t illu_prm_floats(int i, int C, int Cm, int Co) {
     switch (i) {
         case kW1: return (size_t)Cm * (C + 1);
         case kWd: return (size_t)Cm * 25;

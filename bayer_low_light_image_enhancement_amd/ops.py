@@ -793,13 +793,68 @@ def wfb_feed_forward_backward(x: torch.Tensor, params, grad_out: torch.Tensor, p
                      (int(training), float(eps)), _WFB_FF_BUFFERS)
 
 
-def wmb(x: torch.Tensor, params, prefix: str = "") -> torch.Tensor:
-    """``WMB(dim)(x)`` (RawFomer_WFB_FFAB/model.py:203-245), eval mode: the wavelet branch with ``mb`` = ``WM`` on the three high
+def _wmb(x, params, prefix, ffn):
+    """``WMB.forward`` with ``ffn(y, params, prefix)`` as its FeedForward: the wavelet branch with ``mb`` = ``WM`` on the three high
     bands, then ``x + ffn(norm2(x))``."""
     t = wmb_ll_branch(x, params, prefix, high=lambda hi: wm(hi, params, prefix + "mb."))
     y = layernorm2d(t, params[prefix + "norm2.body.weight"], params.get(prefix + "norm2.body.bias"))
-    hid = wfb_feed_forward(y, params, prefix + "ffn.")          # ffn(y) + y: the operator carries FeedForward's own identity
+    hid = ffn(y, params, prefix + "ffn.")                       # ffn(y) + y: the operator carries FeedForward's own identity
     return _affine_clamp_add(hid, t, 1.0, 0.0, float("-inf"), float("inf"))     # t + hid (an unbounded clamp is the identity)
+
+
+def wmb(x: torch.Tensor, params, prefix: str = "") -> torch.Tensor:
+    """``WMB(dim)(x)`` (RawFomer_WFB_FFAB/model.py:203-245), eval mode: the wavelet branch with ``mb`` = ``WM`` on the three high
+    bands, then ``x + ffn(norm2(x))``."""
+    return _wmb(x, params, prefix, wfb_feed_forward)
+
+
+def wmb_train(x: torch.Tensor, params, prefix: str = "", eps: float = 1e-5, momentum: float = 0.1,
+              update_running_stats: bool = True) -> torch.Tensor:
+    """``WMB(dim)(x)`` under ``train()``: ``wmb`` with ``wfb_feed_forward_train`` in place of the folded eval-mode FeedForward, the
+    block's only module that train() changes (its two BatchNorms normalise with the statistics of the batch).  With
+    ``update_running_stats`` the four ``ffn.rep_conv*.bn.running_*`` tensors of ``params`` are updated IN PLACE, as that operator
+    does; ``eps`` and ``momentum`` are the BatchNorms'."""
+    return _wmb(x, params, prefix,
+                lambda y, p, pre: wfb_feed_forward_train(y, p, pre, eps=eps, momentum=momentum, update_running_stats=update_running_stats))
+
+
+_WMB_BUFFERS = tuple("ffn." + k for k in _WFB_FF_BUFFERS)
+
+
+def wmb_param_shapes(c: int, hidden: int):
+    """Names and shapes of the 131 parameters of ``WMB(c)`` in ``state_dict`` order -- ``norm1.body.*``, ``illu.*``, ``ffab.*``,
+    ``norm2.body.*``, ``ffn.*``, ``mb.*`` (the 17 ``wm`` reads) -- and, behind them, of ffn's 4 BatchNorm buffers: the order of the C
+    ABI's pointer array.  ``hidden`` = ``ffn.project_in``'s output channels.  The gradients are those of the first 131."""
+    ff = wfb_ff_param_shapes(c, hidden)
+    shapes = {"norm1.body.weight": (c,), "norm1.body.bias": (c,)}
+    shapes.update({"illu.conv1.weight": (c, c + 1, 1, 1), "illu.conv1.bias": (c,), "illu.depth_conv.weight": (c, 1, 5, 5),
+                   "illu.depth_conv.bias": (c,), "illu.conv2.weight": (c, c, 1, 1), "illu.conv2.bias": (c,)})
+    shapes.update({"ffab." + k: v for k, v in ffab_param_shapes(c).items()})
+    shapes.update({"norm2.body.weight": (c,), "norm2.body.bias": (c,)})
+    shapes.update({"ffn." + k: ff[k] for k in _WFB_FF_KEYS})
+    shapes.update({"mb." + k: v for k, v in wm_param_shapes(c).items()})
+    shapes.update({"ffn." + k: ff[k] for k in _WFB_FF_BUFFERS})
+    return shapes
+
+
+def wmb_backward(x: torch.Tensor, params, grad_out: torch.Tensor, prefix: str = "", grads=None, training: bool = True, eps: float = 1e-5):
+    """The gradient of ``wmb_train`` (``training=True``) or of ``wmb`` (``training=False``: ffn's running statistics are constants):
+    ``(grad_x, grads)`` for ``grad_out`` = dL/d out, with ``feb_backward``'s contract and the 131 parameter keys of ``wmb_param_shapes``.
+    One schedule over the block's operators on one workspace (csrc/rf_wmb_block_bwd.hip): the forward is recomputed, then
+    ``wfb_feed_forward_backward``, ``layernorm2d_backward`` (``residual = grad_out``), ``wmb_back_backward``, ``ffab_backward``,
+    ``illumination_estimator_backward``, ``wm_backward`` and ``wmb_front_backward`` (``grad_scale=2``) run in that order, and the result has
+    the bits of that composition.  ``illu.conv2.*`` feed only ``illu_map``, which ``WMB.forward`` discards: their gradients are zeros in a
+    new ``grads`` and untouched in a passed one.  ``eps`` is the BatchNorms'; the running statistics are read (``training=False``),
+    never written.  Needs C % 4 == 0 in 4 .. 512, hidden % 4 == 0, an even height, a width in multiples of 4 and band sides
+    (h / 2, w / 2) of 2 .. 4096, at most 2048 when no power of two."""
+    x, grad_out = _chk(x, "x"), _chk(grad_out, "grad_out")
+    if x.dim() != 4 or tuple(grad_out.shape) != tuple(x.shape):
+        raise RuntimeError(f"wmb_backward: expected 4-D x and grad_out of one shape, got {tuple(x.shape)} and {tuple(grad_out.shape)}")
+    b, c, h, w = x.shape
+    hidden = params[prefix + "ffn.project_in.weight"].shape[0]
+    shapes = wmb_param_shapes(c, hidden)
+    keys = tuple(k for k in shapes if k not in _WMB_BUFFERS)
+    return _backward("wmb", keys, shapes, x, params, grad_out, prefix, grads, (b, c, hidden, h, w), (int(training), float(eps)), _WMB_BUFFERS)
 
 
 # ------------------------------------------------------------------------------------------ the fused passes of the WFB handle's WMB block

@@ -532,6 +532,34 @@ int rf_layernorm2d_backward(const float* in, const float* grad_out, float* grad_
                             const float* residual, void* workspace, size_t workspace_bytes, int B, int C, int h, int w, float eps, int accumulate,
                             void* stream);
 
+/* ---- the gradient of a whole WMB block (RawFomer_WFB_FFAB/model.py:203-245; csrc/rf_wmb_block_bwd.hip) -------------------------
+ * rf_wmb_backward: (in, grad_out = dL/d out, prm) -> grad_in = dL/d in and grad_prm, for out = WMB.forward(in); in, grad_out,
+ *   grad_in [B,C,h,w], h x w the FULL-resolution plane.  One host schedule over the operators above: the forward is recomputed
+ *   (rf_wmb_front, illu.conv1 + rf_dwconv5x5, rf_ffab, rf_wm_forward, rf_wmb_back, rf_layernorm2d), then rf_wfb_ffn_backward,
+ *   rf_layernorm2d_backward with residual = grad_out, rf_wmb_back_backward, rf_ffab_backward, rf_illumination_estimator_backward,
+ *   rf_wm_backward and rf_wmb_front_backward with grad_scale 2 run in that order, each on the arguments the stand-alone call would
+ *   get: the results have the bits of that composition.  Nothing is kept from a forward call.
+ *   prm = HOST array of 135 device pointers: the block's 131 parameters in state_dict order -- norm1.body.{weight,bias}, illu.<the 6
+ *   of rf_illumination_estimator_backward, Cm = Co = C>, ffab.<92>, norm2.body.{weight,bias}, ffn.<the 12 parameters of
+ *   rf_wfb_ffn_backward>, mb.<the 17 of rf_wm_backward> -- then ffn's 4 BatchNorm buffers (rep_conv1.bn.running_{mean,var},
+ *   rep_conv2.bn.running_{mean,var}); grad_prm = HOST array of the 131 gradients.  hidden = ffn.project_in's output channels.
+ *   training != 0: ffn's gradient runs through the batch statistics (the buffers are not read); 0: on the running statistics.  eps
+ *   is the BatchNorms'; both LayerNorms use 1e-5.  grad_in is always overwritten; accumulate != 0 ADDS to the gradients, 0 overwrites
+ *   them.  illu.conv2.{weight,bias} feed only illu_map, which WMB.forward discards: their gradients are set to exact zeros
+ *   (accumulate == 0) or left untouched.
+ *   Limits, the intersection of the pieces': B <= 21845 (WM runs on 3 B images), C % 4 == 0 in 4 .. 512, hidden % 4 == 0, h even,
+ *   w % 4 == 0, h / 2 and w / 2 within the transform's lengths (2 .. 4096, at most 2048 when no power of two); B h w >= 16
+ *   follows, so the batch statistics of training mode always have more than one value per channel.  Conventions of rf_wm_backward: the query returns a negative error code for a refused geometry; every refusal comes before the first launch,
+ *   -22 with an rf_last_error message that starts with the entry point's name, -12 for a workspace smaller than the query's
+ *   answer; in, grad_out, grad_in and workspace are 16-byte aligned; nothing the call writes may overlap anything it reads or
+ *   anything else it writes; in, grad_out, the parameters and the buffers are not written; no float atomics: two calls give the
+ *   same bits.  The workspace holds six planes and two quarter planes of activations and ONE region, the largest of the pieces'
+ *   workspaces, that the pieces use in turn. */
+long long rf_wmb_backward_workspace_bytes(int B, int C, int hidden, int h, int w);
+int rf_wmb_backward(const float* in, const float* grad_out, float* grad_in, const float* const* prm, float* const* grad_prm,
+                    void* workspace, size_t workspace_bytes, int B, int C, int hidden, int h, int w, int training, float eps,
+                    int accumulate, void* stream);
+
 /* ---- the element-wise kernels of RF_VARIANT_TRUECOLOR one by one (csrc/rf_truecolor.hip; BayerTORGBColorMultiLvl.py) ----------
  * No handle: the caller passes the raw parameter tensors.  Every argument is checked before any launch (RF_E_INVALID).
  * rf_tc_spatial: xs = feat * (1 + sigmoid(conv3x3(guide[0:5]; w_col, b_col)) + tanh(sigmoid(conv3x3(guide[5]; w_low, b_low)) +
