@@ -317,7 +317,9 @@ int rf_chan_attn(const float* in, float* out, const float* qkv_w, const float* q
     RF_CHECK_ARG(in && out && qkv_w && dw_w && temperature && proj_w && scratch && aligned16(scratch), "chan_attn: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     AttnScratch s;
-    RF_TRY(attn_scratch(B, C, heads, h, w, &s));
+    RF_TRY(attn_scratch(B, C, heads, h, w, &s));      // gram_plan's checks of the head layout
+    // launch_attn_fold's and launch_gram's own checks, made here as well: they run after the qkv GEMM and the depthwise filter
+    RF_CHECK_ARG(B > 0 && B <= 65535 && h > 0 && w > 0 && C % 4 == 0, "chan_attn: unsupported shape B=%d C=%d heads=%d %dx%d", B, C, heads, h, w);
     float* ws = (float*)scratch;
     RF_TRY(pack_1x1(qkv_w, ws + s.wqkv, 3 * C, C, C, 1, st));
     RF_TRY(pack_1x1_b3(qkv_w, ws + s.wqkv3, 3 * C, C, C, 1, st));
@@ -401,6 +403,9 @@ int rf_flca(const float* feat, const float* guide, float* out, const float* cons
             int B, int C, int h, int w, void* stream) {
     RF_CHECK_ARG(feat && guide && out && prm && scratch && aligned16(scratch), "flca: bad arguments");
     for (int i = 0; i < 10; ++i) RF_CHECK_ARG(prm[i] != nullptr, "flca: parameter %d is null", i);
+    // launch_flca_se's own check, made here as well: it runs after the spatial kernel, which would have written `out` by then
+    RF_CHECK_ARG(B > 0 && B <= 65535 && h > 0 && w > 0 && C > 0 && C <= 512 && C % 8 == 0 && flca_hidden(C) <= 64,
+                 "flca: unsupported shape B=%d C=%d %dx%d", B, C, h, w);
     hipStream_t st = (hipStream_t)stream;
     const FlcaPrm p{prm[0], prm[1], prm[2], prm[3], prm[4], prm[5], {prm[6], prm[7], prm[8], prm[9]}};   // state_dict order = FlcaGroup's
     const FlcaScratch s = flca_scratch((float*)scratch, B, C, h, w);
