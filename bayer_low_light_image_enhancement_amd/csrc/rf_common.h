@@ -487,6 +487,25 @@ int launch_ml_step_fused(const float* x, float* out, const float* guide, const f
 int launch_ml_tail(float* out, const float* in, int mosaic, float* scratch, int B, int H, int W, int levels, hipStream_t st);
 
 // ---- training kernels (rf_train.hip)
+#ifdef __HIPCC__
+// s[k] <- the sum of s[k] over a workgroup of 256 threads, in a fixed order: lanes by shuffles, then the four waves.  What a kernel
+// calls before it writes its slab
+template <int N>
+__device__ __forceinline__ void block_sums(float (&s)[N], float* lds /* [N][4] */) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_xor(s[k], o, 64);
+        if ((threadIdx.x & 63) == 0) lds[k * 4 + (threadIdx.x >> 6)] = s[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < N; ++k) s[k] = (lds[k * 4] + lds[k * 4 + 1]) + (lds[k * 4 + 2] + lds[k * 4 + 3]);
+}
+#endif
+// pixel slabs of a contraction over pixels with `tiles` workgroups per slab: pixels per slab a multiple of 64, about 1024
+// workgroups in flight
+void gram2_slabs(int B, int P, int tiles, int* slab_px, int* per_image);
 size_t gram2_partial_floats(int B, int Ca, int Cb, int h, int w, int ntap);
 // out[(i * ld + j) * ntap + tap] (+)= sum over images and pixels of a[i][p] b[j][p + tap shift]: the weight gradient [Ca][ld >= Cb][ntap]
 // of a convolution with a = dOut and b = the layer's input
@@ -514,7 +533,10 @@ int launch_ln_bwd(const float* x, const float* dy, const float* gamma, float* dx
                   const float* res = nullptr, int64_t res_bstride = 0);
 size_t dw_wgrad_partial_floats(int B, int C, int P);
 int launch_dw_wgrad(const float* x, const float* dy, float* dw, float* db, float* partial, int B, int C, int h, int w, int accumulate, hipStream_t st);
-int launch_ewise(const float* a, const float* b, float* out, size_t n, int mode, float slope, hipStream_t st);
+// out = a + b | a gelu'(b) (a = dy, b = x) | a (b > 0 ? 1 : slope) (a = dy, b = y) | a | clamp(a, 0, 1).  ewise_kernel takes the
+// mode as a runtime argument: the values are part of what callers pass
+enum EwiseMode { EW_ADD = 0, EW_GELU_GRAD = 1, EW_LRELU_GRAD = 2, EW_COPY = 5, EW_CLAMP01 = 6 };
+int launch_ewise(const float* a, const float* b, float* out, size_t n, EwiseMode mode, float slope, hipStream_t st);
 int launch_split_halves(const float* src, float* a, float* b, int B, int C, int P, hipStream_t st);
 int loss_nblk();
 int launch_loss(const float* pred, const float* gt, float* grad, float* loss_out, float* partial, size_t n, int mode, float eps, int clamp, hipStream_t st);
@@ -534,6 +556,7 @@ struct AttnSmall {
 };
 int launch_attn_small(const AttnSmall& a, int B, hipStream_t st);
 
+// ---- FLCA branch, backward (rf_flca_bwd.hip)
 size_t flca_bwd_scratch_floats(int B, int C, int h, int w);
 // prm / grd: the FLCA parameters and their gradients (grd.se: four tensors adjacent in the flat gradient buffer, checked)
 int launch_flca_backward(const float* feat, const float* guide, const float* xs, const float* dz, int64_t dz_bstride, const float* ch,

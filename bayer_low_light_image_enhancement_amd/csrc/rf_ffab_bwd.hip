@@ -263,13 +263,13 @@ int feb_adjoint(const float* x, const float* g, const float* add, float* gx, con
     RF_TRY(launch_mask_range(f.gm, f.a, nullptr, f.gm, Uf, 0.f, 1e4f, st));
     RF_TRY(wgrad1x1(wf, f.gm, nc, f.t1, nc, d[4], d[5]));
     RF_TRY(dgrad1x1(f.gm, nc, p[4], nc, f.wpack, nullptr, f.gt, B, Pf, st));
-    RF_TRY(launch_ewise(f.gt, f.t1, f.gt, Uf, 2, 0.1f, st));               // LeakyReLU(0.1): t1 has the sign of its input
+    RF_TRY(launch_ewise(f.gt, f.t1, f.gt, Uf, EW_LRELU_GRAD, 0.1f, st));               // LeakyReLU(0.1): t1 has the sign of its input
     RF_TRY(wgrad1x1(wf, f.gt, nc, f.mag, nc, d[2], d[3]));
     RF_TRY(dgrad1x1(f.gt, nc, p[2], nc, f.wpack, nullptr, f.gmag, B, Pf, st));
     // phase MLP
     RF_TRY(wgrad1x1(wf, f.gp, nc, f.t2, nc, d[8], d[9]));
     RF_TRY(dgrad1x1(f.gp, nc, p[8], nc, f.wpack, nullptr, f.gt, B, Pf, st));
-    RF_TRY(launch_ewise(f.gt, f.t2, f.gt, Uf, 2, 0.1f, st));
+    RF_TRY(launch_ewise(f.gt, f.t2, f.gt, Uf, EW_LRELU_GRAD, 0.1f, st));
     RF_TRY(wgrad1x1(wf, f.gt, nc, f.pha, nc, d[6], d[7]));
     RF_TRY(dgrad1x1(f.gt, nc, p[6], nc, f.wpack, nullptr, f.gpha, B, Pf, st));
     // rfft2 + polar, fpre, the residual and the input clamp
@@ -364,11 +364,11 @@ int run_ffab_backward(const FfabBwdPlan& q, const float* in, const float* g, flo
     }
     // conv3 .. conv0.1: x2, x1 and x each have two consumers, summed as (concatenation half) + (next block)
     RF_TRY(block_backward(q.x2, q.gh, q.gt, prm + 38, grd + 38, f, q.k, B, nc, h, w, acc, st));
-    RF_TRY(launch_ewise(q.gax2, q.gt, q.gc, U, 0, 0.f, st));
+    RF_TRY(launch_ewise(q.gax2, q.gt, q.gc, U, EW_ADD, 0.f, st));
     RF_TRY(block_backward(q.x1, q.gc, q.gt, prm + 26, grd + 26, f, q.k, B, nc, h, w, acc, st));
-    RF_TRY(launch_ewise(q.gax1, q.gt, q.gh, U, 0, 0.f, st));
+    RF_TRY(launch_ewise(q.gax1, q.gt, q.gh, U, EW_ADD, 0.f, st));
     RF_TRY(block_backward(q.x, q.gh, q.gt, prm + 14, grd + 14, f, q.k, B, nc, h, w, acc, st));
-    RF_TRY(launch_ewise(q.gax, q.gt, q.gc, U, 0, 0.f, st));
+    RF_TRY(launch_ewise(q.gax, q.gt, q.gc, U, EW_ADD, 0.f, st));
     RF_TRY(block_backward(q.x0, q.gc, q.gt, prm + 2, grd + 2, f, q.k, B, nc, h, w, acc, st));
     RF_TRY(wgrad1x1(wg, q.gt, nc, in, nc, grd[0], grd[1]));
     return dgrad1x1(q.gt, nc, prm[0], nc, f.wpack, nullptr, gin, B, P, st);

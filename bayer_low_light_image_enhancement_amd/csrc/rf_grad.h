@@ -10,25 +10,14 @@ namespace rf {
 // launch_reduce_rows inside a profiler bracket: out[e] (+)= sum over rows of partial[row][e]
 int reduce_rows(const float* partial, float* out, int nrows, size_t n, int accumulate, hipStream_t st);
 
-#ifdef __HIPCC__
-// s[k] <- the sum of s[k] over a workgroup of 256 threads, in a fixed order: lanes by shuffles, then the four waves.  What a kernel
-// calls before it writes its slab
-template <int N>
-__device__ __forceinline__ void block_sums(float (&s)[N], float* lds /* [N][4] */) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_xor(s[k], o, 64);
-        if ((threadIdx.x & 63) == 0) lds[k * 4 + (threadIdx.x >> 6)] = s[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; ++k) s[k] = (lds[k * 4] + lds[k * 4 + 1]) + (lds[k * 4 + 2] + lds[k * 4 + 3]);
-}
-#endif
-
 // ---- weight gradients.  `who` prefixes the refusal of a partial buffer that is too small; B images of P pixels (tokens)
 struct Wgrad { const char* who; float* partial; size_t cap; int B, P, acc; hipStream_t st; };
+
+// The launch_gram2 call for "the weight gradient of this layer": dW [Ca][ld][ntap] and db [Ca] (nullptr: none) (+)= the gradient
+// for output gradient a and input b, planes of h = q.P / w rows.  Builds the launch only: the caller adds a second input, if any,
+// and launches on the stream of its choice.
+Gram2Launch gram2_of(const Wgrad& q, const float* a, int64_t a_bstride, int Ca, const float* b, int64_t b_bstride, int Cb, float* dW, int ld,
+                     float* db, int w, int ntap);
 
 // dW [Ca][Cb] and db [Ca] (nullptr: none) (+)= the gradient of a 1x1 convolution with output gradient a (rows i of image n at
 // a + n a_bstride + i P) and input b: launch_gram2 with one tap where P % 4 == 0, else wgrad1x1_kernel (16-byte alignment is

@@ -91,15 +91,16 @@ int wgrad3x3_slabs(int B, int P, long long* slab_px) {
     return (int)((total + px - 1) / px);
 }
 
-Gram2Launch gram2_of(const Wgrad& q, const float* a, int64_t a_bstride, int Ca, const float* b, int64_t b_bstride, int Cb, float* dW, float* db) {
+}  // namespace
+
+Gram2Launch gram2_of(const Wgrad& q, const float* a, int64_t a_bstride, int Ca, const float* b, int64_t b_bstride, int Cb, float* dW, int ld,
+                     float* db, int w, int ntap) {
     Gram2Launch g{};
     g.a = a; g.a_bstride = a_bstride; g.Ca = Ca; g.b = b; g.b_bstride = b_bstride; g.Cb = Cb;
-    g.out = dW; g.ld = Cb; g.partial = q.partial; g.partial_cap = q.cap; g.B = q.B;
+    g.out = dW; g.ld = ld; g.partial = q.partial; g.partial_cap = q.cap; g.B = q.B; g.h = q.P / w; g.w = w; g.ntap = ntap;
     g.accumulate = q.acc != 0; g.db = db;
     return g;
 }
-
-}  // namespace
 
 int reduce_rows(const float* partial, float* out, int nrows, size_t n, int accumulate, hipStream_t st) {
     ProfScope prof(st, "reduce_partials_kernel", (double)nrows * n, 4.0 * (nrows + 1.0) * n);
@@ -115,9 +116,7 @@ size_t wgrad1x1_partial_floats(int B, int Ca, int Cb, int P, bool with_bias) {
 int wgrad1x1(const Wgrad& q, const float* a, int64_t a_bstride, int Ca, const float* b, int64_t b_bstride, int Cb, float* dW, float* db) {
     const int B = q.B, P = q.P;
     if (P % 4 == 0) {
-        Gram2Launch g = gram2_of(q, a, a_bstride, Ca, b, b_bstride, Cb, dW, db);
-        g.h = 1; g.w = P; g.ntap = 1;
-        return launch_gram2(g, q.st);
+        return launch_gram2(gram2_of(q, a, a_bstride, Ca, b, b_bstride, Cb, dW, Cb, db, P, 1), q.st);
     }
     int len;
     const int nslab = wgrad1x1_slabs(P, &len), ntj = cdiv(Cb, 16);
@@ -144,9 +143,7 @@ size_t wgrad3x3_partial_floats(int B, int Ca, int Cb, int h, int w) {
 int wgrad3x3(const Wgrad& q, const float* a, int Ca, const float* b, int Cb, float* dW, float* db, int w) {
     const int B = q.B, P = q.P, h = P / w;
     if (w % 4 == 0) {
-        Gram2Launch g = gram2_of(q, a, (int64_t)Ca * P, Ca, b, (int64_t)Cb * P, Cb, dW, db);
-        g.h = h; g.w = w; g.ntap = 9;
-        return launch_gram2(g, q.st);
+        return launch_gram2(gram2_of(q, a, (int64_t)Ca * P, Ca, b, (int64_t)Cb * P, Cb, dW, Cb, db, w, 9), q.st);
     }
     long long px;
     const int nslab = wgrad3x3_slabs(B, P, &px);

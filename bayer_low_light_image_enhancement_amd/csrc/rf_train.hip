@@ -2,12 +2,20 @@
 // The reference trains through torch.autograd; here every adjoint is a hand-written gfx950 kernel or one of the forward
 // kernels run on transposed / flipped weights:
 //
-//   conv 1x1 / 3x3 / ConvTranspose2d   dX: the forward kernels on W^T (3x3: taps flipped);  dW: gram2_kernel (below)
-//   depthwise 3x3                      dX: the forward kernel on flipped taps;              dW, db: dw_wgrad_kernel
-//   LayerNorm over channels            ln_bwd_kernel (dx per pixel; dgamma, dbeta through fixed-order partials)
-//   GELU, LeakyReLU, residual adds     element-wise kernels
+//   conv 1x1 / 3x3 / ConvTranspose2d   dX: the forward kernels on W^T (3x3: taps flipped);  dW, db: gram2_kernel (below), its
+//                                      slabs added by reduce_gram2_kernel;  db alone: chan_sum_kernel
+//   depthwise 3x3                      dX: the forward kernel on flipped taps;  dW, db: dw_wgrad_kernel, reduce_dw_kernel
+//   LayerNorm over channels            ln_bwd_reg_kernel (C = 16 .. 512 in steps the registers hold: dx, dgamma, dbeta and the
+//                                      residual in one pass), else ln_bwd_kernel (dx per pixel) + ln_wgrad_kernel
+//   GELU, LeakyReLU, add, copy, clamp  ewise_kernel (EwiseMode, rf_common.h);  split_halves_kernel: the halves of a concatenation
+//   channel attention                  attn_small_kernel: per (head, image) the softmax of the forward's Gram partials and its
+//                                      adjoint, as packed per-image weights for the 1x1 GEMMs (AttnSmall, rf_common.h)
 //   L1 / Charbonnier loss              loss_kernel (value through fixed-order partials, gradient in the same pass)
 //   Adam                               adam_kernel on the flat parameter / gradient / moment buffers
+//   any slab table                     reduce_partials_kernel (launch_reduce_rows): rows added in order
+// and the launchers of all of them.  A sum over all 256 threads of a workgroup is block_sums (rf_common.h); the tile and row sums
+// of gram2_kernel and ln_bwd_reg_kernel have orders of their own.  The FLCA branch's adjoint is
+// rf_flca_bwd.hip; the block backward operators (rf_grad.hip and the *_bwd files) call the launchers here.
 //
 // gram2: G[i][j] = sum over images and pixels of A[i][p] * B[j][p + shift], the weight gradient of a convolution with A = dOut
 // and B = the layer input (zero padded), one shift per tap.  Like the attention Gram it is a contraction over pixels: the pixel
@@ -23,8 +31,8 @@ namespace {
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
 // ---------------------------------------------------------------------------------------------
-// gram2.  Workgroup = (slab of pixels of one image, tile ti of 16 A rows, group tj of TJ*16 B rows).  NTAP = 1: one shift
-// (sy, sx), TJ = 4 B tiles per workgroup; NTAP = 9: the nine taps of a 3x3 window at once, TJ = 1.
+// gram2.  Workgroup = (slab of pixels of one image, tile ti of 16 A rows, group tj of TJ*16 B rows).  Two forms: NTAP = 1, no
+// shift, TJ = 4 or 2 B tiles per workgroup; NTAP = 9: the nine taps of a 3x3 window at once, TJ = 1.
 // partial[((slab * NTAP + tap) * Ca + i) * Cb + j]
 // ---------------------------------------------------------------------------------------------
 struct Gram2Args {
@@ -32,7 +40,7 @@ struct Gram2Args {
     const float* b; int64_t b_bstride; int Cb;     // input [B][Cb][h][w]; rows >= Cb1 come from b2 (a concatenated input read in place)
     const float* b2; int64_t b2_bstride; int Cb1;
     float* partial;
-    int B, h, w, sy, sx, slab_px, slabs_per_image;
+    int B, h, w, sy, sx, slab_px, slabs_per_image; // sy, sx: always 0, read by no kernel; kept, with load_step's dead arm, for the kernels' code to stay what it was
     float* bias_partial;                           // [slab][Ca] row sums of A (the bias gradient of the same layer) or nullptr
     int nslab, nty, ntz;                           // grid decomposition (gram2_block)
 };
@@ -69,6 +77,8 @@ __global__ void __launch_bounds__(256) gram2_kernel(Gram2Args g) {
     const int img = slab / g.slabs_per_image, sl = slab - img * g.slabs_per_image;
     const int h = g.h, w = g.w, P = h * w;
     const int n_lo = sl * g.slab_px, n_hi = (n_lo + g.slab_px < P) ? n_lo + g.slab_px : P;
+    // nine-tap form: the lane's row of every A and B tile.  (Built in the single-tap form too, which never reads them: under
+    // `if constexpr (NTAP == 9)` hipcc emitted other code for the masked single-tap kernels.)
     const float* arow[NA];
 #pragma unroll
     for (int u = 0; u < NA; ++u) {
@@ -82,7 +92,7 @@ __global__ void __launch_bounds__(256) gram2_kernel(Gram2Args g) {
         brow[t] = jc < g.Cb1 ? g.b + (size_t)img * g.b_bstride + (size_t)jc * P : g.b2 + (size_t)img * g.b2_bstride + (size_t)(jc - g.Cb1) * P;
     }
     // single-tap form: wave-uniform tile bases + 32-bit lane offsets (the loads take the scalar-base addressing mode: one VALU
-    // addition per load instead of a 64-bit pointer sum), no row / column arithmetic (the shift is zero: launch_gram2 checks), and
+    // addition per load instead of a 64-bit pointer sum), no row / column arithmetic (there is no shift), and
     // no masks when every 16-pixel step of a wave is entirely inside the image (P % 16 == 0).  The VALU instructions of a step are
     // what limited this kernel: f32 MFMA time and VALU time add up, and there were four of them for every MFMA.
     const float* abase[NA];
@@ -117,7 +127,7 @@ __global__ void __launch_bounds__(256) gram2_kernel(Gram2Args g) {
     for (int u = 0; u < NA; ++u) bsum[u] = 0.f;
 
     // The 4 pixels of a lane sit in one row (w % 4 == 0).  A step's loads -- the A row, and per B tile three rows of (16 bytes +
-    // the two outer taps) for the 3x3 window, or one shifted row -- are all UNCONDITIONAL on clamped addresses (values masked
+    // the two outer taps) for the 3x3 window, or one row -- are all UNCONDITIONAL on clamped addresses (values masked
     // afterwards) and issued one step ahead: loads behind `if (row inside the image)` branches had been followed by
     // s_waitcnt vmcnt(0) each, 15 serialised round trips per step (gram2<9> ran at 16 % of the f32 matrix rate).
     constexpr int NROW = NTAP == 9 ? 3 : 1;
@@ -131,26 +141,24 @@ __global__ void __launch_bounds__(256) gram2_kernel(Gram2Args g) {
             for (int u = 0; u < NA; ++u) q.a[u] = ld4(abase[u] + (aoff[u] + (unsigned)n));
 #pragma unroll
             for (int t = 0; t < TJ; ++t) q.c[t][0] = ld4(bbase[t] + (boff[t] + (unsigned)n));
-            return;
-        }
-        const int y = n / w, x = n - y * w;
+        } else {
+            const int y = n / w, x = n - y * w;
 #pragma unroll
-        for (int u = 0; u < NA; ++u) q.a[u] = ld4(arow[u] + n);
-        q.lok = x > 0; q.rgk = x + 4 < w;
+            for (int u = 0; u < NA; ++u) q.a[u] = ld4(arow[u] + n);
+            q.lok = x > 0; q.rgk = x + 4 < w;
 #pragma unroll
-        for (int dy = 0; dy < NROW; ++dy) {
-            const int yy = y + (NTAP == 9 ? dy - 1 : g.sy);
-            q.rok[dy] = q.ok && yy >= 0 && yy < h;
-            const size_t off = (size_t)(q.rok[dy] ? yy : 0) * w + x;
+            for (int dy = 0; dy < NROW; ++dy) {
+                // (the dead `: g.sy` arm stays: it makes this lambda capture g, and without it hipcc emits the nine-tap kernels with
+                // 2-3 instructions more and other scalar registers -- the only edit of this kernel that moved its code)
+                const int yy = y + (NTAP == 9 ? dy - 1 : g.sy);
+                q.rok[dy] = q.ok && yy >= 0 && yy < h;
+                const size_t off = (size_t)(q.rok[dy] ? yy : 0) * w + x;
 #pragma unroll
-            for (int t = 0; t < TJ; ++t) {
-                const float* p = brow[t] + off;
-                q.c[t][dy] = ld4(p);
-                if constexpr (NTAP == 9) {        // the single-tap form only shifts rows (launch_gram2 checks sx == 0)
+                for (int t = 0; t < TJ; ++t) {
+                    const float* p = brow[t] + off;
+                    q.c[t][dy] = ld4(p);
                     q.l[t][dy] = p[q.lok ? -1 : 0];
                     q.rg[t][dy] = p[q.rgk ? 4 : 0];
-                } else {
-                    q.l[t][dy] = 0.f; q.rg[t][dy] = 0.f;
                 }
             }
         }
@@ -176,25 +184,18 @@ __global__ void __launch_bounds__(256) gram2_kernel(Gram2Args g) {
 #pragma unroll
                     for (int m = 0; m < 4; ++m) acc[u][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(aa[u][m], bv[m], acc[u][t], 0, 0, 0);
             }
-            return;
-        }
+        } else {
 #pragma unroll
-        for (int t = 0; t < TJ; ++t) {
-            float v[NROW][6];
+            for (int t = 0; t < TJ; ++t) {
+                float v[NROW][6];
 #pragma unroll
-            for (int dy = 0; dy < NROW; ++dy) {
-                const bool rk = q.rok[dy];
-                v[dy][0] = (rk && q.lok) ? q.l[t][dy] : 0.f;
-                v[dy][1] = rk ? q.c[t][dy].x : 0.f; v[dy][2] = rk ? q.c[t][dy].y : 0.f;
-                v[dy][3] = rk ? q.c[t][dy].z : 0.f; v[dy][4] = rk ? q.c[t][dy].w : 0.f;
-                v[dy][5] = (rk && q.rgk) ? q.rg[t][dy] : 0.f;
-            }
-            if constexpr (NTAP == 1) {
-#pragma unroll
-                for (int u = 0; u < NA; ++u)
-#pragma unroll
-                    for (int m = 0; m < 4; ++m) acc[u][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(aa[u][m], v[0][m + 1], acc[u][t], 0, 0, 0);
-            } else {
+                for (int dy = 0; dy < NROW; ++dy) {
+                    const bool rk = q.rok[dy];
+                    v[dy][0] = (rk && q.lok) ? q.l[t][dy] : 0.f;
+                    v[dy][1] = rk ? q.c[t][dy].x : 0.f; v[dy][2] = rk ? q.c[t][dy].y : 0.f;
+                    v[dy][3] = rk ? q.c[t][dy].z : 0.f; v[dy][4] = rk ? q.c[t][dy].w : 0.f;
+                    v[dy][5] = (rk && q.rgk) ? q.rg[t][dy] : 0.f;
+                }
 #pragma unroll
                 for (int k = 0; k < 9; ++k)
 #pragma unroll
@@ -352,12 +353,10 @@ __global__ void __launch_bounds__(256) chan_sum_kernel(const float* __restrict__
     } else {
         for (int p = lo + threadIdx.x; p < hi; p += 256) s += row[p];
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    __shared__ float wsum[4];
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[((size_t)img * nblk + blk) * C + c] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    float v[1] = {s};
+    __shared__ float red[4];
+    block_sums<1>(v, red);
+    if (threadIdx.x == 0) partial[((size_t)img * nblk + blk) * C + c] = v[0];
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -403,19 +402,18 @@ __global__ void __launch_bounds__(256) ln_wgrad_kernel(const float* __restrict__
     const float* mu = stats + (size_t)img * 2 * P;
     const float* rs = mu + P;
     const int per = ((P + nblk - 1) / nblk + 3) & ~3, lo = blk * per, hi = (lo + per < P) ? lo + per : P;
-    float a = 0.f, b = 0.f;
+    float s[2] = {0.f, 0.f};         // dgamma, dbeta
     for (int p = lo + threadIdx.x; p < hi; p += 256) {
         const float d = dr[p];
-        a = fmaf(d, (xr[p] - mu[p]) * rs[p], a);
-        b += d;
+        s[0] = fmaf(d, (xr[p] - mu[p]) * rs[p], s[0]);
+        s[1] += d;
     }
+    __shared__ float red[2 * 4];
+    block_sums<2>(s, red);
+    if (threadIdx.x == 0) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o); b += __shfl_xor(b, o); }
-    __shared__ float red[2][4];
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = a; red[1][threadIdx.x >> 6] = b; }
-    __syncthreads();
-    if (threadIdx.x < 2)
-        partial[(((size_t)img * nblk + blk) * 2 + threadIdx.x) * C + c] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+        for (int k = 0; k < 2; ++k) partial[(((size_t)img * nblk + blk) * 2 + k) * C + c] = s[k];
+    }
 }
 
 // Register-resident fused form (C = CPL * KS <= 128; the layout of layernorm2d_reg_kernel, rf_pointwise.hip): a lane keeps its
@@ -586,17 +584,12 @@ __global__ void __launch_bounds__(256) dw_wgrad_kernel(const float* __restrict__
             s[9] += d;
         }
     }
-    __shared__ float red[10][4];
+    __shared__ float red[10 * 4];
+    block_sums<10>(s, red);
+    if (threadIdx.x == 0) {
 #pragma unroll
-    for (int k = 0; k < 10; ++k) {
-        float v = s[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = v;
+        for (int k = 0; k < 10; ++k) partial[(((size_t)img * nblk + blk) * C + c) * 10 + k] = s[k];
     }
-    __syncthreads();
-    if (threadIdx.x < 10)
-        partial[(((size_t)img * nblk + blk) * C + c) * 10 + threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -606,30 +599,26 @@ __device__ __forceinline__ float gelu_grad(float v) {      // d/dv [ v Phi(v) ] 
     const float cdf = 0.5f * (1.0f + erff(v * 0.70710678118654752440f));
     return cdf + v * 0.39894228040143267794f * expf(-0.5f * v * v);
 }
-// mode 0: out = a + b;  1: out = dy * gelu'(x) (a = dy, b = x);  2: out = dy * (y > 0 ? 1 : slope) (a = dy, b = y);
-// 3: out = gelu(a) (exact erf);  4: out += a;  5: out = a;  6: out = clamp(a, 0, 1)
-__device__ __forceinline__ float ewise_op(float a, float b, float o, int mode, float slope) {
-    if (mode == 0) return a + b;
-    if (mode == 1) return a * gelu_grad(b);
-    if (mode == 2) return a * (b > 0.f ? 1.0f : slope);
-    if (mode == 3) return 0.5f * a * (1.0f + erff(a * 0.70710678118654752440f));
-    if (mode == 5) return a;
-    if (mode == 6) return fminf(fmaxf(a, 0.f), 1.f);
-    return o + a;
+// EwiseMode (rf_common.h); b is read by the three modes that take two operands
+__device__ __forceinline__ float ewise_op(float a, float b, int mode, float slope) {
+    if (mode == EW_ADD) return a + b;
+    if (mode == EW_GELU_GRAD) return a * gelu_grad(b);
+    if (mode == EW_LRELU_GRAD) return a * (b > 0.f ? 1.0f : slope);
+    if (mode == EW_COPY) return a;
+    return fminf(fmaxf(a, 0.f), 1.f);       // EW_CLAMP01
 }
 // VEC = 4: 16 bytes per lane and access (n % 4 == 0, 16-byte aligned operands); VEC = 1: any n
 template <int VEC>
 __global__ void __launch_bounds__(256) ewise_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, size_t n, int mode, float slope) {
-    const bool need_b = mode <= 2, need_o = mode == 4;
+    const bool need_b = mode <= EW_LRELU_GRAD;
     for (size_t i = (blockIdx.x * 256ull + threadIdx.x) * VEC; i < n; i += (size_t)gridDim.x * 256 * VEC) {
         if constexpr (VEC == 4) {
             const float4 av = *reinterpret_cast<const float4*>(a + i);
             const float4 bv = need_b ? *reinterpret_cast<const float4*>(b + i) : make_float4(0.f, 0.f, 0.f, 0.f);
-            const float4 ov = need_o ? *reinterpret_cast<const float4*>(out + i) : make_float4(0.f, 0.f, 0.f, 0.f);
-            *reinterpret_cast<float4*>(out + i) = make_float4(ewise_op(av.x, bv.x, ov.x, mode, slope), ewise_op(av.y, bv.y, ov.y, mode, slope),
-                                                              ewise_op(av.z, bv.z, ov.z, mode, slope), ewise_op(av.w, bv.w, ov.w, mode, slope));
+            *reinterpret_cast<float4*>(out + i) = make_float4(ewise_op(av.x, bv.x, mode, slope), ewise_op(av.y, bv.y, mode, slope),
+                                                              ewise_op(av.z, bv.z, mode, slope), ewise_op(av.w, bv.w, mode, slope));
         } else {
-            out[i] = ewise_op(a[i], need_b ? b[i] : 0.f, need_o ? out[i] : 0.f, mode, slope);
+            out[i] = ewise_op(a[i], need_b ? b[i] : 0.f, mode, slope);
         }
     }
 }
@@ -647,21 +636,18 @@ __global__ void __launch_bounds__(256) split_halves_kernel(const float4* __restr
 // clamp: the loss of clamp(pred, 0, 1) (train.py:139); the gradient passes where 0 <= pred <= 1 (torch.clamp's subgradient)
 __global__ void __launch_bounds__(256) loss_kernel(const float* __restrict__ pred, const float* __restrict__ gt, float* __restrict__ grad,
                                                    float* __restrict__ partial, size_t n, int mode, float eps, float inv_n, int clamp) {
-    float s = 0.f;
+    float s[1] = {0.f};
     for (size_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         float pr = pred[i];
         const float pass = !clamp || (pr >= 0.f && pr <= 1.f) ? inv_n : 0.f;
         if (clamp) pr = fminf(fmaxf(pr, 0.f), 1.f);
         const float d = pr - gt[i];
-        if (mode == 0) { s += fabsf(d); grad[i] = (d > 0.f ? pass : d < 0.f ? -pass : 0.f); }
-        else { const float r = sqrtf(fmaf(d, d, eps * eps)); s += r; grad[i] = d / r * pass; }
+        if (mode == 0) { s[0] += fabsf(d); grad[i] = (d > 0.f ? pass : d < 0.f ? -pass : 0.f); }
+        else { const float r = sqrtf(fmaf(d, d, eps * eps)); s[0] += r; grad[i] = d / r * pass; }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    __shared__ float wsum[4];
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = ((wsum[0] + wsum[1]) + (wsum[2] + wsum[3])) * inv_n;
+    __shared__ float red[4];
+    block_sums<1>(s, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s[0] * inv_n;
 }
 
 // torch.optim.Adam (train.py:113; weight_decay > 0 with decoupled = 1 gives AdamW), one launch over the flat buffers
@@ -792,8 +778,7 @@ __global__ void __launch_bounds__(256) attn_small_kernel(AttnSmall a) {
 }  // namespace
 
 // ---- launchers (shared with the training schedule, rf_trainstep.hip) --------------------------------------------
-// slabs: pixels per slab a multiple of 64, about 1024 workgroups in flight
-static void gram2_slabs(int B, int P, int tiles, int* slab_px, int* per_image) {
+void gram2_slabs(int B, int P, int tiles, int* slab_px, int* per_image) {
     int per = 1;
     while ((long)B * per * tiles < 1024 && P / (per + 1) >= 2048) ++per;
     int px = (P + per - 1) / per;
@@ -822,7 +807,7 @@ size_t gram2_partial_floats(int B, int Ca, int Cb, int h, int w, int ntap) {
     return (size_t)B * per * ((size_t)ntap * Ca * Cb + Ca);      // + the row sums of A (bias gradient)
 }
 
-// (Gram2Launch, rf_common.h)  The single-tap form has no shift: the kernel struct's sy / sx stay 0, and the nine-tap form reads neither.
+// (Gram2Launch, rf_common.h)
 int launch_gram2(const Gram2Launch& l, hipStream_t st) {
     const int Ca = l.Ca, Cb1 = l.Cb, Cb2 = l.Cb2, B = l.B, h = l.h, w = l.w, ntap = l.ntap;
     float *const partial = l.partial, *const db = l.db;
@@ -938,7 +923,7 @@ int launch_ln_bwd(const float* x, const float* dy, const float* gamma, float* dx
     if (res) {
         RF_CHECK_ARG(res_bstride == (int64_t)C * P, "ln_bwd: the generic path takes a contiguous residual");
         // dx = res (or dx += res), then the adjoint accumulates
-        if (int rc = launch_ewise(res, accumulate_dx ? dx : nullptr, dx, (size_t)B * C * P, accumulate_dx ? 0 : 5, 0.f, st)) return rc;
+        if (int rc = launch_ewise(res, accumulate_dx ? dx : nullptr, dx, (size_t)B * C * P, accumulate_dx ? EW_ADD : EW_COPY, 0.f, st)) return rc;
         accumulate_dx = 1;
     }
     ln_bwd_kernel<<<dim3((unsigned)cdiv(P, 256), (unsigned)B), 256, 0, st>>>(x, dy, gamma, dx, stats, C, P, eps, accumulate_dx);
@@ -967,8 +952,8 @@ int launch_dw_wgrad(const float* x, const float* dy, float* dw, float* db, float
     return check_launch("dw_wgrad");
 }
 
-int launch_ewise(const float* a, const float* b, float* out, size_t n, int mode, float slope, hipStream_t st) {
-    ProfScope prof(st, "ewise_kernel", 0.0, (mode == 3 || mode >= 5 ? 8.0 : 12.0) * n);
+int launch_ewise(const float* a, const float* b, float* out, size_t n, EwiseMode mode, float slope, hipStream_t st) {
+    ProfScope prof(st, "ewise_kernel", 0.0, (mode >= EW_COPY ? 8.0 : 12.0) * n);
     if (n % 4 == 0 && aligned16(a) && aligned16(out) && (!b || aligned16(b))) ewise_kernel<4><<<grid1d(n / 4), 256, 0, st>>>(a, b, out, n, mode, slope);
     else ewise_kernel<1><<<grid1d(n), 256, 0, st>>>(a, b, out, n, mode, slope);
     return check_launch("ewise");
@@ -995,413 +980,6 @@ int launch_adam(float* p, const float* g, float* m, float* v, size_t n, float lr
     ProfScope prof(st, "adam_kernel", 12.0 * n, 28.0 * n);
     adam_kernel<<<grid1d(n), 256, 0, st>>>(p, g, m, v, n, lr, b1, b2, eps, wd, decoupled, bc1, bc2, gscale);
     return check_launch("adam");
-}
-
-}  // namespace rf
-
-// =================================================================================================
-// FLCA branch, backward (FrequencyawareLumaChromaAttentionRAWFormer.py:103-162).  Forward:
-//   S = 1 + alpha sigmoid(conv(g_low; w_low)) + beta tanh(conv(g_high; w_high)) + gamma sigmoid(conv(g_cr, g_cb; w_chr))
-//   xs = feat S;   ch = sigmoid(W3 relu(W1 mean_p(xs) + b1) + b3) per image;   z = xs ch
-// Backward of z w.r.t. feat and the 10 parameter tensors (the guidance planes carry no gradient: they come from the input):
-//   dch[b][c] = sum_p dz xs           -> squeeze-excite MLP backward (tiny, per image) -> dm[b][c] (gradient of the pooled mean)
-//   dxs = dz ch + dm / P;   dfeat = dxs S;   dS = dxs feat;   dalpha = sum dS a_low, ...;   d(conv outputs) -> tap sums
-// =================================================================================================
-namespace rf {
-namespace {
-
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-// dch partial: partial[((b * nblk + blk) * C + c)] = sum over the block's pixels of dz * xs
-__global__ void __launch_bounds__(256) flca_dch_kernel(const float* __restrict__ dz, int64_t dz_bstride, const float* __restrict__ xs, float* __restrict__ partial,
-                                                       int C, int P, int nblk) {
-    const int blk = blockIdx.x, c = blockIdx.y, b = blockIdx.z;
-    const float* d = dz + (size_t)b * dz_bstride + (size_t)c * P;
-    const float* x = xs + ((size_t)b * C + c) * P;
-    const int per = (P + nblk - 1) / nblk, lo = blk * per, hi = (lo + per < P) ? lo + per : P;
-    float s = 0.f;
-    for (int p = lo + threadIdx.x; p < hi; p += 256) s = fmaf(d[p], x[p], s);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    __shared__ float ws[4];
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[((size_t)b * nblk + blk) * C + c] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
-}
-
-// squeeze-excite backward, one workgroup per image (a single workgroup walking the images in turn took 120 us per stage):
-// in: pooled sums partial (forward: flca partial / P = mean), dch partials;  out: dm[b][c] / P and the image's CONTRIBUTION to the
-// gradients of se.1.{w,b}, se.3.{w,b} in contrib[b][hid C | hid | C hid | C] (the order of the four tensors in the flat gradient
-// buffer), summed over the images in order by reduce_partials_kernel: deterministic.
-__global__ void __launch_bounds__(256) flca_se_bwd_kernel(const float* __restrict__ pool_partial, int pool_nblk, const float* __restrict__ dch_partial, int dch_nblk,
-                                                          const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w3, const float* __restrict__ b3,
-                                                          float* __restrict__ dmP, float* __restrict__ contrib, int C, int hid, int P) {
-    __shared__ float mean[512], dch[512], ds3[512], hv[64], dh[64];
-    __shared__ float part[2][256];
-    const size_t b = blockIdx.x;
-    // column sums of the two partial tables: cw channels x nsl row slices per pass, 8 loads in flight per thread, slices
-    // combined in a fixed order (the forward's flca_se_kernel sums its table the same way)
-    const int cw = C < 256 ? C : 256, nsl = 256 / cw;
-    for (int c0 = 0; c0 < C; c0 += cw) {
-        const int c = c0 + threadIdx.x % cw, sl = threadIdx.x / cw;
-        float s = 0.f, d = 0.f;
-        if (sl < nsl && c < C) {
-            const float* src = pool_partial + b * pool_nblk * C + c;
-            int k = sl;
-            for (; k + 7 * nsl < pool_nblk; k += 8 * nsl) {
-                float t[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) t[u] = src[(size_t)(k + u * nsl) * C];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) s += t[u];
-            }
-            for (; k < pool_nblk; k += nsl) s += src[(size_t)k * C];
-            const float* dsrc = dch_partial + b * dch_nblk * C + c;
-            for (int q = sl; q < dch_nblk; q += nsl) d += dsrc[(size_t)q * C];
-        }
-        part[0][threadIdx.x] = s;
-        part[1][threadIdx.x] = d;
-        __syncthreads();
-        if (threadIdx.x < cw && c0 + threadIdx.x < C) {
-            float t = 0.f, u = 0.f;
-            for (int q = 0; q < nsl; ++q) { t += part[0][q * cw + threadIdx.x]; u += part[1][q * cw + threadIdx.x]; }
-            mean[c0 + threadIdx.x] = t / (float)P;
-            dch[c0 + threadIdx.x] = u;
-        }
-        __syncthreads();
-    }
-    for (int m = threadIdx.x; m < hid; m += 256) {
-        float s = b1[m];
-        for (int c = 0; c < C; ++c) s = fmaf(w1[m * C + c], mean[c], s);
-        hv[m] = fmaxf(s, 0.f);
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < C; c += 256) {
-        float s = b3[c];
-        for (int m = 0; m < hid; ++m) s = fmaf(w3[c * hid + m], hv[m], s);
-        const float chv = sigm(s);
-        ds3[c] = dch[c] * chv * (1.0f - chv);
-    }
-    __syncthreads();
-    for (int m = threadIdx.x; m < hid; m += 256) {
-        float s = 0.f;
-        for (int c = 0; c < C; ++c) s = fmaf(w3[c * hid + m], ds3[c], s);
-        dh[m] = hv[m] > 0.f ? s : 0.f;
-    }
-    __syncthreads();
-    float* gw1 = contrib + b * (size_t)(2 * C * hid + hid + C);
-    float* gb1 = gw1 + (size_t)hid * C;
-    float* gw3 = gb1 + hid;
-    float* gb3 = gw3 + (size_t)C * hid;
-    for (int e = threadIdx.x; e < hid * C; e += 256) gw1[e] = dh[e / C] * mean[e % C];          // [hid][C]
-    for (int m = threadIdx.x; m < hid; m += 256) gb1[m] = dh[m];
-    for (int e = threadIdx.x; e < C * hid; e += 256) gw3[e] = ds3[e / hid] * hv[e % hid];       // [C][hid]
-    for (int c = threadIdx.x; c < C; c += 256) gb3[c] = ds3[c];
-    for (int c = threadIdx.x; c < C; c += 256) {
-        float s = 0.f;
-        for (int m = 0; m < hid; ++m) s = fmaf(w1[m * C + c], dh[m], s);
-        dmP[b * C + c] = s / (float)P;
-    }
-}
-
-// spatial part, element-wise: one thread per pixel, channels in a loop (the guidance neighbourhoods stay in registers).
-//   dfeat = dxs S;   ds_low = alpha dS a_l (1 - a_l),  ds_high = beta dS (1 - a_h^2),  ds_chr = gamma dS a_c (1 - a_c)   (dS = dxs feat)
-// are written out: the tap sums dW[c][tap] = sum_p ds[c][p] g[p + tap] are then weight gradients of a 3x3 convolution with a
-// 1- or 2-plane input = gram2<9>.  dalpha, dbeta, dgamma accumulate per thread over all channels: one block reduction at the end.
-struct FlcaBwdArgs {
-    const float* feat; const float* guide; const float* dz; int64_t dz_bstride; const float* ch; const float* dmP;
-    const float* w_low; const float* w_high; const float* w_chr; const float* alpha; const float* beta; const float* gamma;
-    float* dfeat; float* ds;        // ds: [3][B][C][P]
-    float* abg_partial;             // [(b * nblk + blk)][3]
-    int B, C, h, w, nblk, accumulate;
-};
-
-__global__ void __launch_bounds__(256) flca_spatial_bwd_kernel(FlcaBwdArgs a) {
-    const int blk = blockIdx.x;
-    const size_t b = blockIdx.y;
-    const int h = a.h, w = a.w, P = h * w, C = a.C;
-    const int p = blk * 256 + threadIdx.x;
-    const bool live = p < P;
-    const int y = live ? p / w : 0, x = live ? p % w : 0;
-    float nb[4][9];
-    const float* gb = a.guide + b * 4 * (size_t)P;
-#pragma unroll
-    for (int pl = 0; pl < 4; ++pl)
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
-            nb[pl][t] = (live && yy >= 0 && yy < h && xx >= 0 && xx < w) ? gb[(size_t)pl * P + (size_t)yy * w + xx] : 0.f;
-        }
-    const float al = *a.alpha, be = *a.beta, ga = *a.gamma;
-    const size_t plane = (size_t)a.B * C * P;
-    float sa = 0.f, sb = 0.f, sg = 0.f;
-    if (live) {
-        for (int c = 0; c < C; ++c) {
-            const float* wl = a.w_low + c * 9;
-            const float* wh = a.w_high + c * 9;
-            const float* wc = a.w_chr + c * 18;
-            float sl = 0.f, sh = 0.f, sc = 0.f;
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                sl = fmaf(wl[t], nb[0][t], sl);
-                sh = fmaf(wh[t], nb[1][t], sh);
-                sc = fmaf(wc[9 + t], nb[3][t], fmaf(wc[t], nb[2][t], sc));
-            }
-            const float a_l = sigm(sl), a_h = tanhf(sh), a_c = sigm(sc);
-            const size_t idx = (b * C + c) * (size_t)P + p;
-            const float dxs = a.dz[b * a.dz_bstride + (size_t)c * P + p] * a.ch[b * C + c] + a.dmP[b * C + c];
-            const float df = dxs * (1.0f + al * a_l + be * a_h + ga * a_c);
-            a.dfeat[idx] = a.accumulate ? a.dfeat[idx] + df : df;
-            const float dS = dxs * a.feat[idx];
-            a.ds[idx] = al * dS * a_l * (1.0f - a_l);
-            a.ds[plane + idx] = be * dS * (1.0f - a_h * a_h);
-            a.ds[2 * plane + idx] = ga * dS * a_c * (1.0f - a_c);
-            sa = fmaf(dS, a_l, sa); sb = fmaf(dS, a_h, sb); sg = fmaf(dS, a_c, sg);
-        }
-    }
-    __shared__ float red[3][4];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { sa += __shfl_xor(sa, o); sb += __shfl_xor(sb, o); sg += __shfl_xor(sg, o); }
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = sa; red[1][threadIdx.x >> 6] = sb; red[2][threadIdx.x >> 6] = sg; }
-    __syncthreads();
-    if (threadIdx.x < 3)
-        a.abg_partial[(b * a.nblk + blk) * 3 + threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
-}
-
-// Spatial part and tap sums in ONE kernel (w % 4 == 0): the element-wise kernel above writes the three ds tensors for a tap-sum pass to
-// read back (6 of the 9 streams of the pair).  Here a lane owns channel 16 ti + r and the 4 pixels of its pixel group kq -- the
-// A-operand layout of the tap contraction below -- recomputes the three gates of its channel at those pixels from the guidance
-// neighbourhood (36 weights of the channel in registers), writes dfeat, and feeds ds_low / ds_high / ds_chr straight into the
-// MFMAs whose B rows are the TAPS: G[c][col] = sum_p ds_k[c][p] * plane_k[p + tap] is a contraction over pixels; lane (r, kq) of
-// the B operand loads tap r of its plane at the lane's 4 pixels, four accumulator tiles per A tile: low x plane 0, high x plane 1,
-// chroma x plane 2, chroma x plane 3 (columns 0-8 = the 3 x 3 window).  dz and feat are read once, dfeat written once, nothing
-// else touches HBM (the guidance planes are cache resident).
-// partial[(slab * C + c) * 36 + {low 0-8, high 9-17, chroma 18-35}], slabs reduced in order by reduce_partials_kernel;
-// abg_partial[(slab * gridDim.y + ti) * 3 + k].
-__device__ __forceinline__ float fsig(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-
-__global__ void __launch_bounds__(256) flca_bwd_fused_kernel(FlcaBwdArgs a, float* __restrict__ partial, int slab_px, int slabs_per_image) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 15, kq = lane >> 4;
-    const int slab = blockIdx.x, ti = blockIdx.y;
-    const int img = slab / slabs_per_image, sl = slab - img * slabs_per_image;
-    const int h = a.h, w = a.w, P = h * w, C = a.C;
-    const int n_lo = sl * slab_px, n_hi = (n_lo + slab_px < P) ? n_lo + slab_px : P;
-    const bool cvalid = 16 * ti + r < C;
-    const int c = cvalid ? 16 * ti + r : C - 1;
-    float wl[9], wh[9], wc[18];
-#pragma unroll
-    for (int t = 0; t < 9; ++t) { wl[t] = a.w_low[c * 9 + t]; wh[t] = a.w_high[c * 9 + t]; wc[t] = a.w_chr[c * 18 + t]; wc[9 + t] = a.w_chr[c * 18 + 9 + t]; }
-    const float al = *a.alpha, be = *a.beta, ga = *a.gamma;
-    const float chv = a.ch[(size_t)img * C + c], dm = a.dmP[(size_t)img * C + c];
-    const float* dzr = a.dz + (size_t)img * a.dz_bstride + (size_t)c * P;
-    const float* fr = a.feat + ((size_t)img * C + c) * P;
-    float* dfr = a.dfeat + ((size_t)img * C + c) * P;
-    const float* gpl = a.guide + (size_t)img * 4 * P;
-    const int tdy = r < 9 ? r / 3 - 1 : 0, tdx = r < 9 ? r % 3 - 1 : 0;      // this lane's tap (B operand rows 9-15 are zero)
-    f32x4 acc[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    float sa = 0.f, sb = 0.f, sg = 0.f;
-    for (int n0 = n_lo + wave * 16; n0 < n_hi; n0 += 64) {
-        const int nn = n0 + 4 * kq;
-        const bool ok = nn < n_hi;
-        const int n = ok ? nn : n_lo;
-        const int y = n / w, x = n - y * w;
-        const float4 dz4 = ld4(dzr + n), f4 = ld4(fr + n);
-        // B operand: this lane's tap of the four planes at the lane's 4 pixels
-        float bv[4][4];
-        {
-            const int yy = y + tdy;
-            const bool rowok = ok && r < 9 && yy >= 0 && yy < h;
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const int xx = x + m + tdx;
-                const bool in = rowok && xx >= 0 && xx < w;
-                const size_t off = in ? (size_t)yy * w + xx : 0;
-#pragma unroll
-                for (int pl = 0; pl < 4; ++pl) { const float v = gpl[(size_t)pl * P + off]; bv[pl][m] = in ? v : 0.f; }
-            }
-        }
-        // gates of the lane's channel at its 4 pixels: pre-activations from the 3 x 6 neighbourhood of each plane
-        float s_l[4] = {0.f, 0.f, 0.f, 0.f}, s_h[4] = {0.f, 0.f, 0.f, 0.f}, s_c[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int dy = 0; dy < 3; ++dy) {
-            const int yy = y + dy - 1;
-            const bool rok = yy >= 0 && yy < h;
-            const size_t rowoff = (size_t)(rok ? yy : 0) * w + x;
-            float nb[4][6];
-#pragma unroll
-            for (int pl = 0; pl < 4; ++pl) {
-                const float* row = gpl + (size_t)pl * P + rowoff;
-                const float4 t = ld4(row);
-                const float lft = row[x > 0 ? -1 : 0], rgt = row[x + 4 < w ? 4 : 0];
-                nb[pl][0] = (rok && x > 0) ? lft : 0.f;
-                nb[pl][1] = rok ? t.x : 0.f; nb[pl][2] = rok ? t.y : 0.f; nb[pl][3] = rok ? t.z : 0.f; nb[pl][4] = rok ? t.w : 0.f;
-                nb[pl][5] = (rok && x + 4 < w) ? rgt : 0.f;
-            }
-#pragma unroll
-            for (int dx = 0; dx < 3; ++dx) {
-                const float k0 = wl[dy * 3 + dx], k1 = wh[dy * 3 + dx], k2 = wc[dy * 3 + dx], k3 = wc[9 + dy * 3 + dx];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    s_l[q] = fmaf(k0, nb[0][q + dx], s_l[q]);
-                    s_h[q] = fmaf(k1, nb[1][q + dx], s_h[q]);
-                    s_c[q] = fmaf(k3, nb[3][q + dx], fmaf(k2, nb[2][q + dx], s_c[q]));
-                }
-            }
-        }
-        const float dzv[4] = {dz4.x, dz4.y, dz4.z, dz4.w}, fv[4] = {f4.x, f4.y, f4.z, f4.w};
-        const float live = (ok && cvalid) ? 1.0f : 0.f;
-        float dsl[4], dsh[4], dsc[4], df[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float a_l = fsig(s_l[q]), a_h = 2.0f * fsig(2.0f * s_h[q]) - 1.0f, a_c = fsig(s_c[q]);
-            const float dxs = live * fmaf(dzv[q], chv, dm);
-            df[q] = dxs * (1.0f + al * a_l + be * a_h + ga * a_c);
-            const float dS = dxs * fv[q];
-            dsl[q] = al * dS * a_l * (1.0f - a_l);
-            dsh[q] = be * dS * (1.0f - a_h * a_h);
-            dsc[q] = ga * dS * a_c * (1.0f - a_c);
-            sa = fmaf(dS, a_l, sa); sb = fmaf(dS, a_h, sb); sg = fmaf(dS, a_c, sg);
-        }
-        if (ok && cvalid) {
-            float4 o = make_float4(df[0], df[1], df[2], df[3]);
-            if (a.accumulate) { const float4 p = ld4(dfr + n); o.x += p.x; o.y += p.y; o.z += p.z; o.w += p.w; }
-            *reinterpret_cast<float4*>(dfr + n) = o;
-        }
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(dsl[m], bv[0][m], acc[0], 0, 0, 0);
-            acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(dsh[m], bv[1][m], acc[1], 0, 0, 0);
-            acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(dsc[m], bv[2][m], acc[2], 0, 0, 0);
-            acc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(dsc[m], bv[3][m], acc[3], 0, 0, 0);
-        }
-    }
-    __shared__ float red[4][16][17];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 4; ++q) red[wave][4 * kq + q][r] = acc[t][q];
-        __syncthreads();
-        const int i = threadIdx.x >> 4, jj = threadIdx.x & 15;
-        const int gi = 16 * ti + i;
-        if (gi < C && jj < 9)
-            partial[((size_t)slab * C + gi) * 36 + 9 * t + jj] = ((red[0][i][jj] + red[1][i][jj]) + red[2][i][jj]) + red[3][i][jj];
-    }
-    // dalpha, dbeta, dgamma: wave butterflies, then the four waves in order
-    __syncthreads();
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { sa += __shfl_xor(sa, o); sb += __shfl_xor(sb, o); sg += __shfl_xor(sg, o); }
-    if (lane == 0) { red[0][0][wave] = sa; red[0][1][wave] = sb; red[0][2][wave] = sg; }
-    __syncthreads();
-    if (threadIdx.x < 3)
-        a.abg_partial[((size_t)slab * gridDim.y + ti) * 3 + threadIdx.x] =
-            (red[0][threadIdx.x][0] + red[0][threadIdx.x][1]) + (red[0][threadIdx.x][2] + red[0][threadIdx.x][3]);
-}
-
-// the 36 tap sums of a channel -> the three weight gradients: low [C][9], high [C][9], chroma [C][2][9]
-__global__ void __launch_bounds__(256) flca_taps_scatter_kernel(const float* __restrict__ sums, float* __restrict__ g_low, float* __restrict__ g_high,
-                                                                float* __restrict__ g_chr, int C) {
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < C * 36; e += gridDim.x * 256) {
-        const int c = e / 36, t = e % 36;
-        if (t < 9) g_low[c * 9 + t] += sums[e];
-        else if (t < 18) g_high[c * 9 + t - 9] += sums[e];
-        else g_chr[c * 18 + t - 18] += sums[e];
-    }
-}
-
-__global__ void __launch_bounds__(256) flca_abg_kernel(const float* __restrict__ partial, int nrec, float* __restrict__ ga, float* __restrict__ gb, float* __restrict__ gg) {
-    __shared__ float part[3][256];
-    float s[3] = {0.f, 0.f, 0.f};
-    for (int k = threadIdx.x; k < nrec; k += 256) {
-#pragma unroll
-        for (int t = 0; t < 3; ++t) s[t] += partial[(size_t)k * 3 + t];
-    }
-#pragma unroll
-    for (int t = 0; t < 3; ++t) part[t][threadIdx.x] = s[t];
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        float v = 0.f;
-        for (int q = 0; q < 256; ++q) v += part[threadIdx.x][q];      // fixed order
-        float* o = threadIdx.x == 0 ? ga : threadIdx.x == 1 ? gb : gg;
-        *o += v;
-    }
-}
-
-}  // namespace
-
-size_t flca_bwd_scratch_floats(int B, int C, int h, int w) {
-    const int P = h * w;
-    const int hid = flca_hidden(C);
-    return 3 * (size_t)B * C * P + (size_t)B * cdiv(P, 256) * 3 + (size_t)B * chan_sum_nblk(P) * C + 2 * (size_t)B * C + 256 +
-           (size_t)B * (2 * C * hid + hid + C) + 64 +
-           gram2_partial_floats(B, C, 2, h, w, 9) + gram2_partial_floats(B, C, 16, h, w, 1) * 3 + (size_t)C * 36 + 64;
-}
-
-int launch_flca_backward(const float* feat, const float* guide, const float* xs, const float* dz, int64_t dz_bstride, const float* ch,
-                         const float* pool_partial, int pool_nblk, const FlcaPrm& prm, const FlcaGrad& grd, float* dfeat, int accumulate,
-                         float* scratch, size_t scratch_floats, int B, int C, int h, int w, hipStream_t st) {
-    RF_CHECK_ARG(C <= 512 && B <= 65535 && w % 4 == 0, "flca backward: C=%d, w=%d unsupported", C, w);
-    const int P = h * w, nblk = cdiv(P, 256), dnblk = chan_sum_nblk(P), hid = flca_hidden(C);
-    const size_t plane = (size_t)B * C * P;
-    float* ds = scratch;
-    float* abg = ds + 3 * plane;
-    float* dch_part = abg + (size_t)B * nblk * 3;
-    float* dmP = dch_part + (size_t)B * dnblk * C;
-    float* se_contrib = dmP + (size_t)B * C + 64;
-    const size_t n_se = (size_t)2 * C * hid + hid + C;
-    float* gpart = se_contrib + align_up((size_t)B * n_se, 64);
-    RF_CHECK_ARG((size_t)(gpart - scratch) <= scratch_floats, "flca backward: scratch of %zu floats, the fixed part alone needs %zu",
-                 scratch_floats, (size_t)(gpart - scratch));
-    const size_t gcap = scratch_floats - (size_t)(gpart - scratch);      // the slab partials of the tap gradients (gram2 / fused kernel)
-    // the four squeeze-excite tensors follow each other in the flat gradient buffer (registry order, sizes multiples of 4)
-    RF_CHECK_ARG(grd.se.se1_b == grd.se.se1_w + (size_t)hid * C && grd.se.se3_w == grd.se.se1_b + hid && grd.se.se3_b == grd.se.se3_w + (size_t)C * hid,
-                 "flca backward: the gradients of se.1.weight, se.1.bias, se.3.weight, se.3.bias must be contiguous");
-    // squeeze-excite part: dch -> per-image MLP adjoint -> dm, the four se gradients
-    auto se_part = [&]() -> int {
-        flca_dch_kernel<<<dim3((unsigned)dnblk, (unsigned)C, (unsigned)B), 256, 0, st>>>(dz, dz_bstride, xs, dch_part, C, P, dnblk);
-        flca_se_bwd_kernel<<<B, 256, 0, st>>>(pool_partial, pool_nblk, dch_part, dnblk, prm.se.se1_w, prm.se.se1_b, prm.se.se3_w, prm.se.se3_b, dmP, se_contrib, C, hid, P);
-        reduce_partials_kernel<<<red_grid(n_se), 256, 0, st>>>(se_contrib, grd.se.se1_w, B, n_se, 1);      // all four at once
-        return check_launch("flca_backward (squeeze-excite)");
-    };
-    if (w % 4 == 0 && aligned16(dz) && dz_bstride % 4 == 0 && aligned16(feat) && aligned16(dfeat) && aligned16(guide)) {
-        // spatial part + tap sums in one kernel; abg partials live in the (unused) ds area
-        int slab_px, per_image;
-        gram2_slabs(B, P, cdiv(C, 16), &slab_px, &per_image);
-        const int nslab = B * per_image, nti = cdiv(C, 16);
-        RF_CHECK_ARG((size_t)(nslab + 1) * C * 36 <= gcap, "flca backward: %d slabs x %d floats exceed the %zu-float partial buffer",
-                     nslab, C * 36, gcap);
-        float* sums = gpart + (size_t)nslab * C * 36;
-        float* abg2 = ds;
-        ProfScope prof(st, "flca_backward(fused)", 2.0 * 36 * (double)B * C * P + 200.0 * B * C * P, 12.0 * (double)B * C * P + 8.0 * B * C * P);
-        if (int rc = se_part()) return rc;
-        FlcaBwdArgs a{feat, guide, dz, dz_bstride, ch, dmP, prm.w_low, prm.w_high, prm.w_chr, prm.alpha, prm.beta, prm.gamma, dfeat, nullptr, abg2, B, C, h, w, nblk, accumulate};
-        flca_bwd_fused_kernel<<<dim3((unsigned)nslab, (unsigned)nti), 256, 0, st>>>(a, gpart, slab_px, per_image);
-        flca_abg_kernel<<<1, 256, 0, st>>>(abg2, nslab * nti, grd.alpha, grd.beta, grd.gamma);
-        reduce_partials_kernel<<<red_grid((size_t)C * 36), 256, 0, st>>>(gpart, sums, nslab, (size_t)C * 36, 0);
-        flca_taps_scatter_kernel<<<cdiv(C * 36, 256), 256, 0, st>>>(sums, grd.w_low, grd.w_high, grd.w_chr, C);
-        return check_launch("flca_backward (fused)");
-    }
-    {
-        ProfScope prof(st, "flca_backward(elementwise)", 200.0 * B * C * P, 32.0 * B * C * P);
-        if (int rc = se_part()) return rc;
-        FlcaBwdArgs a{feat, guide, dz, dz_bstride, ch, dmP, prm.w_low, prm.w_high, prm.w_chr, prm.alpha, prm.beta, prm.gamma, dfeat, ds, abg, B, C, h, w, nblk, accumulate};
-        flca_spatial_bwd_kernel<<<dim3((unsigned)nblk, (unsigned)B), 256, 0, st>>>(a);
-        flca_abg_kernel<<<1, 256, 0, st>>>(abg, B * nblk, grd.alpha, grd.beta, grd.gamma);
-        if (int rc = check_launch("flca_backward")) return rc;
-    }
-    // tap gradients of the three gates: each dS plane against the guidance planes it gates (low: plane 0, high: 1, chroma: 2-3)
-    Gram2Launch g{};
-    g.a_bstride = (int64_t)C * P; g.Ca = C; g.b_bstride = (int64_t)4 * P;
-    g.partial = gpart; g.partial_cap = gcap; g.B = B; g.h = h; g.w = w; g.ntap = 9; g.accumulate = true;
-    g.a = ds; g.b = guide; g.Cb = g.ld = 1; g.out = grd.w_low;
-    if (int rc = launch_gram2(g, st)) return rc;
-    g.a = ds + plane; g.b = guide + P; g.out = grd.w_high;
-    if (int rc = launch_gram2(g, st)) return rc;
-    g.a = ds + 2 * plane; g.b = guide + 2 * (size_t)P; g.Cb = g.ld = 2; g.out = grd.w_chr;
-    return launch_gram2(g, st);
 }
 
 }  // namespace rf

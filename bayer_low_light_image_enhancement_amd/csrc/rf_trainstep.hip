@@ -17,7 +17,7 @@
 //       dS = A (dA - rowsum(dA A));  dT = sum dS c;  dc = T dS;
 //       dq = (rq dc rk) k - diag(rq^2 rowsum(dc c)) q;     dk = (rq dc rk)^T q - diag(rk^2 colsum(dc c)) k
 //     i.e. d[q;k] = M2 [q;k] with a per-image 2C x 2C matrix and dv = blockdiag(A^T) do: two 1x1 GEMMs with per-image weights.
-// Variants 'plain' (conv branch) and 'flca' (rf_train.hip: launch_flca_backward).
+// Variants 'plain' (conv branch) and 'flca' (rf_flca_bwd.hip: launch_flca_backward).
 //
 // Schedule-level choices (round 3): every packed / transposed / tap-flipped weight form of the step is written by three batched
 // launches before the forward (pack cache, laid out once by plan_training); bias gradients are row sums inside gram2; the depthwise 3x3 of the
@@ -31,6 +31,7 @@
 // offsets plan_training fixed at rf_create, gradients at the parameter's flat offset.
 #include <vector>
 #include "rf_handle.h"
+#include "rf_grad.h"
 
 using namespace rf;
 
@@ -224,25 +225,17 @@ int b_conv1x1_dx(const Ctx& c, const float* dy, int Cout, int w, int K, float* d
     return launch_conv1x1(a, c.st);
 }
 
-// dW of a convolution layer, accumulated into the flat gradient buffer on the weight-gradient stream: out [Cout][ld][ntap] +=
-// gram2(dy, x) over all images; the caller adds db / a second input and launches on c.wg (after c.side->fork)
-Gram2Launch wgrad(const Ctx& c, const float* dy, int64_t dy_bstride, int Cout, const float* x, int Cx, float* dW, int ld, int hh, int ww, int ntap) {
-    Gram2Launch g{};
-    g.a = dy; g.a_bstride = dy_bstride; g.Ca = Cout;
-    g.b = x; g.b_bstride = (int64_t)Cx * hh * ww; g.Cb = Cx;
-    g.out = dW; g.ld = ld;
-    g.partial = c.dw_part(); g.partial_cap = c.p->part_floats;
-    g.B = c.B; g.h = hh; g.w = ww; g.ntap = ntap; g.accumulate = true;
-    return g;
-}
+// dW of a convolution layer [Cout][ld][ntap] += gram2(dy, x) over all images, accumulated into the flat gradient buffer on the
+// weight-gradient stream (launched on c.wg after c.side->fork): what gram2_of (rf_grad.h) takes for it
+Wgrad wgrad(const Ctx& c, int P_) { return Wgrad{"rf_train_step", c.dw_part(), c.p->part_floats, c.B, P_, 1, c.wg}; }
 
 // dW [Cout][ld] columns [col0, col0 + Cx) += gram2(dy, x);  db = channel sums of dy, taken in the same pass
 // (x2 / Cx2: the layer's input is cat(x, x2) along channels, read in place)
 int b_conv1x1_dw(const Ctx& c, const float* dy, int Cout, const float* x, int Cx, float* dW, int ld, int col0, float* db, int hh, int ww,
                  int64_t dy_bstride = 0, const float* x2 = nullptr, int Cx2 = 0) {
     RF_TRY(c.side->fork(c.st, c.wg));
-    Gram2Launch g = wgrad(c, dy, dy_bstride ? dy_bstride : (int64_t)Cout * hh * ww, Cout, x, Cx, dW + col0, ld, hh, ww, 1);
-    g.db = col0 == 0 ? db : nullptr;
+    Gram2Launch g = gram2_of(wgrad(c, hh * ww), dy, dy_bstride ? dy_bstride : (int64_t)Cout * hh * ww, Cout, x, (int64_t)Cx * hh * ww, Cx,
+                             dW + col0, ld, col0 == 0 ? db : nullptr, ww, 1);
     if (Cx2 && Cx % 16 != 0) {       // the two-source contraction cuts the inputs at a tile boundary: otherwise one pass per input
         RF_TRY(launch_gram2(g, c.wg));
         g.b = x2; g.b_bstride = (int64_t)Cx2 * hh * ww; g.Cb = Cx2; g.out = dW + col0 + Cx; g.db = nullptr;
@@ -258,9 +251,7 @@ int b_conv3x3_dx(const Ctx& c, const float* dy, int Cout, int w, int Cin, float*
 
 int b_conv3x3_dw(const Ctx& c, const float* dy, int Cout, const float* x, int Cin, float* dW, float* db, int hh, int ww) {
     RF_TRY(c.side->fork(c.st, c.wg));
-    Gram2Launch g = wgrad(c, dy, (int64_t)Cout * hh * ww, Cout, x, Cin, dW, Cin, hh, ww, 9);
-    g.db = db;
-    return launch_gram2(g, c.wg);
+    return launch_gram2(gram2_of(wgrad(c, hh * ww), dy, (int64_t)Cout * hh * ww, Cout, x, (int64_t)Cin * hh * ww, Cin, dW, Cin, db, ww, 9), c.wg);
 }
 
 // depthwise 3x3 with weight `w`: dW, db on the weight-gradient stream, dX = the forward kernel on the flipped taps
@@ -353,7 +344,7 @@ int stage_backward(const Ctx& outer, hipStream_t wg, int i, float* dout, float* 
     float *d_pre = t.d_pre, *d_cr = t.d_cr, *d_cat = t.d_cat, *d_f2 = t.d_f2, *d_f1 = t.d_f1, *ln2 = t.ln2, *d_ln2 = t.d_ln2, *d_x1 = t.d_x1, *o = t.o,
           *d_o = t.d_o, *d_qkv = t.d_qkv, *d_qkvp = t.d_qkvp, *ln1 = t.ln1, *d_ln1 = t.d_ln1, *d_xs = t.d_xs, *d_tr = t.d_tr;
     // Conv_out + LeakyReLU
-    RF_TRY(launch_ewise(dout, s.out, d_pre, U, 2, 0.2f, c.st));                                      // d(pre-activation)
+    RF_TRY(launch_ewise(dout, s.out, d_pre, U, EW_LRELU_GRAD, 0.2f, c.st));                                      // d(pre-activation)
     RF_TRY(b_conv3x3_dw(c, d_pre, C, s.cr, C, c.G(x.out_w), c.G(x.out_b), hh, ww));
     RF_TRY(b_conv3x3_dx(c, d_pre, C, x.out_w, C, d_cr, hh, ww));
     // channel_reduce over cat[xs, trans]
@@ -373,14 +364,14 @@ int stage_backward(const Ctx& outer, hipStream_t wg, int i, float* dout, float* 
                                     c.flca_grad(x.flca), din, 0, c.p->flca_scr, c.p->flca_scr_floats, c.B, C, hh, ww, c.st));   // din = branch part
     } else {
         // conv branch
-        if (cfg.branch_lrelu) RF_TRY(launch_ewise(d_xs, s.xs, d_xs, U, 2, 0.2f, c.st));
+        if (cfg.branch_lrelu) RF_TRY(launch_ewise(d_xs, s.xs, d_xs, U, EW_LRELU_GRAD, 0.2f, c.st));
         RF_TRY(b_conv3x3_dw(c, d_xs, C, s.in, C, c.G(x.conv_w), c.G(x.conv_b), hh, ww));
         RF_TRY(b_conv3x3_dx(c, d_xs, C, x.conv_w, C, din, hh, ww));                  // din = branch part
     }
     // FFN:  trans = x1 + pw2(gelu(dw(pw1(LN2(x1)))))          dtr = dtrans (also the residual part of dx1)
     RF_TRY(b_conv1x1_dw(c, dtr, C, s.g, hc, c.G(x.pw2_w), hc, 0, c.G(x.pw2_b), hh, ww, half_bs));
     RF_TRY(b_conv1x1_dx(c, dtr, C, x.pw2_w, hc, d_f2, Pn, nullptr, half_bs));   // dg ...
-    RF_TRY(launch_ewise(d_f2, s.f2, d_f2, (size_t)c.B * hc * Pn, 1, 0.f, c.st));                      // ... -> df2, in place
+    RF_TRY(launch_ewise(d_f2, s.f2, d_f2, (size_t)c.B * hc * Pn, EW_GELU_GRAD, 0.f, c.st));                      // ... -> df2, in place
     RF_TRY(b_dw(c, d_f2, s.f1, x.dw_w, d_f1, c.G(x.dw_w), c.G(x.dw_b), hc, hh, ww));
     RF_TRY(launch_layernorm2d(s.x1, ln2, h->prm(x.ln2_w), h->prm(x.ln2_b), 1e-5f, c.B, C, Pn, c.st));   // LN2(x1) again
     RF_TRY(b_conv1x1_dw(c, d_f1, hc, ln2, C, c.G(x.pw1_w), C, 0, c.G(x.pw1_b), hh, ww));
@@ -567,7 +558,7 @@ int rf_train_step(rf_handle* h, const float* in, const float* gt, float* grads, 
 
     // ------------------------------------------------------------------ forward
     RF_TRY(launch_pixel_unshuffle2(in, p.x4, B, 1, H, W, st));
-    if (clamp_io) RF_TRY(launch_ewise(p.x4, nullptr, p.x4, (size_t)B * 4 * H * W, 6, 0.f, st));      // model.py:475
+    if (clamp_io) RF_TRY(launch_ewise(p.x4, nullptr, p.x4, (size_t)B * 4 * H * W, EW_CLAMP01, 0.f, st));      // model.py:475
     if (h->vt.branch == BR_FLCA) {
         RF_TRY(launch_guidance_base(p.x4, 0, 0, p.gscratch, B, H, W, st));
         for (int l = 0; l < 4; ++l) RF_TRY(launch_guidance_level(p.gscratch, p.guide[l], B, H, W, H >> l, W >> l, st));
@@ -596,7 +587,7 @@ int rf_train_step(rf_handle* h, const float* in, const float* gt, float* grads, 
     }
     RF_TRY(f_conv3x3(c, cur, d, h->conv_out_w, h->prm(h->conv_out_b), p.pred, 4 * oc, H, W, 1, 2));
     const size_t npred = (size_t)B * oc * 4 * H * W;
-    if (pred_out && clamp_io) RF_TRY(launch_ewise(p.pred, nullptr, pred_out, npred, 6, 0.f, st));    // model.py:508
+    if (pred_out && clamp_io) RF_TRY(launch_ewise(p.pred, nullptr, pred_out, npred, EW_CLAMP01, 0.f, st));    // model.py:508
     else if (pred_out) RF_TRY(check_hip(hipMemcpyAsync(pred_out, p.pred, npred * 4, hipMemcpyDeviceToDevice, st), "copy pred"));
 
     // ------------------------------------------------------------------ loss
@@ -607,7 +598,7 @@ int rf_train_step(rf_handle* h, const float* in, const float* gt, float* grads, 
     // conv_out + LeakyReLU + PixelShuffle
     RF_TRY(launch_pixel_unshuffle2(p.dpred, tA, B, oc, H, W, st));          // [B, 4 oc, H, W]
     RF_TRY(launch_pixel_unshuffle2(p.pred, tB, B, oc, H, W, st));
-    RF_TRY(launch_ewise(tA, tB, tA, (size_t)B * 4 * oc * H * W, 2, 0.2f, st));
+    RF_TRY(launch_ewise(tA, tB, tA, (size_t)B * 4 * oc * H * W, EW_LRELU_GRAD, 0.2f, st));
     RF_TRY(b_conv3x3_dw(c, tA, 4 * oc, p.st[7].out, d, c.G(h->conv_out_w), c.G(h->conv_out_b), H, W));
     // announce range k of h->grad_ranges (plan_training lists the order): final on st from here on
     auto ready = [&](int k) {
@@ -655,7 +646,7 @@ int rf_train_step(rf_handle* h, const float* in, const float* gt, float* grads, 
             RF_TRY(launch_pixel_shuffle2(gb, p.tA, B, C / 2, hh / 2, ww / 2, st));             // [B, C/2, hh, ww]
             RF_TRY(b_conv3x3_dw(c, p.tA, C / 2, p.st[i].out, C, c.G(h->down_w[i - 1]), nullptr, hh, ww));
             RF_TRY(b_conv3x3_dx(c, p.tA, C / 2, h->down_w[i - 1], C, ga, hh, ww));
-            RF_TRY(launch_ewise(ga, p.dskip[lvl], ga, (size_t)B * C * Pn, 0, 0.f, st));
+            RF_TRY(launch_ewise(ga, p.dskip[lvl], ga, (size_t)B * C * Pn, EW_ADD, 0.f, st));
         }
         RF_TRY(stage_backward(c, wg, i, ga, gb, H, W));                                       // gb = d(stage i input)
         ready(11 - i);                                                                         // conv_tran<i> and down_i, whose gradient came first

@@ -257,11 +257,11 @@ static int run_wm_backward(const WmBwdPlan& p, const float* x, const float* g, f
     // convb.2
     RF_TRY(wgrad3x3(wg, gr, c, a1, 2 * c, grd[2], grd[3], w));
     RF_TRY(wm_dgrad3x3(gr, ws + p.t2, ga1, ks, p.ks_floats, n, c, 2 * c, h, w, st));
-    RF_TRY(launch_ewise(ga1, a1, ga1, 2 * el, 2, 0.f, st));                 // ReLU: g_a1 where a1 > 0, else 0
+    RF_TRY(launch_ewise(ga1, a1, ga1, 2 * el, EW_LRELU_GRAD, 0.f, st));                 // ReLU: g_a1 where a1 > 0, else 0
     // convb.0 and the skip
     RF_TRY(wgrad3x3(wg, ga1, 2 * c, x, c, grd[0], grd[1], w));
     RF_TRY(wm_dgrad3x3(ga1, ws + p.t0, dx, ks, p.ks_floats, n, 2 * c, c, h, w, st));
-    return launch_ewise(dx, gr, dx, el, 0, 0.f, st);
+    return launch_ewise(dx, gr, dx, el, EW_ADD, 0.f, st);
 }
 
 }  // namespace rf

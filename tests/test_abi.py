@@ -135,11 +135,20 @@ def test_handle_plans_and_gradient_ranges(variant, dim):
 
 
 # rf_train_workspace_bytes(1, 64, 64) and (4, 512, 512) as the library returned them at 78881de, before the schedules' seven
-# bump allocators became one (same handles as above)
+# bump allocators became one (same handles as above).  The two 'flca' rows are those numbers less the scratch the element-wise FLCA
+# backward reserved and nothing could reach: the workspace ends with one FLCA scratch buffer, the largest over the four levels,
+# rounded up to a granule of 64 floats.  It held three [B][C][P] planes, the alpha / beta / gamma partials of cdiv(P, 256) blocks
+# per image and the gram2 partials of three tap-gradient launches; it now holds what the fused kernel writes (FlcaBwdPlan,
+# csrc/rf_flca_bwd.hip: every buffer a whole number of granules).  Floats of that buffer, old (granule-rounded) -> new:
+#   flca 16, (1, 64, 64):     200184 (200192), level 0     ->    13824, level 3     removed  186368 floats =    745472 bytes
+#   flca 16, (4, 512, 512): 50920608 (50920640), level 0   ->   299264, level 0     removed 50621376 floats = 202485504 bytes
+#   flca 32, (1, 64, 64):     399928 (399936), level 0     ->    35712, level 3     removed  364224 floats =   1456896 bytes
+#   flca 32, (4, 512, 512): 101828512 (101828544), level 0 ->   598464, level 0     removed 101230080 floats = 404920320 bytes
+# The 'plain' row has no such buffer and does not move.
 TRAIN_BYTES = {
     ("plain", 32): (121401088, 14426197504),
-    ("flca", 16): (42835968, 7732380160),
-    ("flca", 32): (109422336, 15341869568),
+    ("flca", 16): (42090496, 7529894656),          # 42835968 - 745472, 7732380160 - 202485504
+    ("flca", 32): (107965440, 14936949248),        # 109422336 - 1456896, 15341869568 - 404920320
 }
 
 

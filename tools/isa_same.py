@@ -45,6 +45,7 @@ def only_kernels(lines, kernels):
                 first = int(mm.group(2)) if first is None else first
                 return f"{mm.group(1)}{int(mm.group(2)) - first}_"
             ln = re.sub(r"(?<![.\w])BB\d+_", "BB_", ln)          # the function's number in the file, in the loop comments
+            ln = re.sub(r":\s+;", ": ;", ln)                     # ... whose column moves with the width of the label's number
             out.append(re.sub(r"(\.LBB|\.Lfunc_end|\.Lfunc_begin)(\d+)_?", renum, ln) if ".L" in ln else ln)
         if keep and (ln.startswith(".Lfunc_end") or ".end_amdhsa_kernel" in ln):
             keep = False
