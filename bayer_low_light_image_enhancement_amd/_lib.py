@@ -81,6 +81,7 @@ SIGNATURES = {
     "rf_dwconv3x3": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "rf_conv3x3_scratch_bytes": (_i, [_i, _i, _psz]),
     "rf_conv3x3": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "rf_conv3x3_plan": (_i, [_i] * 8 + [_sz, C.c_char_p, _sz, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "rf_convT2x2_scratch_bytes": (_i, [_i, _i, _psz]),
     "rf_convT2x2": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "rf_conv1x1_plan": (_i, [_i] * 10 + [C.c_char_p, _sz, C.POINTER(_i), C.POINTER(_i), _psz, C.POINTER(_i)]),

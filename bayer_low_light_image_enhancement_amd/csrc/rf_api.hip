@@ -226,6 +226,24 @@ int rf_conv3x3(const float* in, float* out, const float* weight, const float* bi
     return launch_conv3x3(a, st);
 }
 
+int rf_conv3x3_plan(int B, int Cin, int Cout, int h, int w, int store, int unshuffle_in, int aligned, size_t ks_floats,
+                    char* key, size_t key_len, int* grid, int* block, int* ksplit, int* level0) {
+    RF_CHECK_ARG(key && key_len > 0 && grid && block && ksplit && level0, "conv3x3_plan: bad arguments");
+    alignas(16) static float any[8];      // stands for every operand: a plan looks at presence and alignment only
+    float* buf = aligned ? any : any + 1;
+    Conv3x3Args a = conv3x3_dense(buf, any, any, buf, B, Cin, Cout, h, w, 0);
+    a.store = store; a.unshuffle_in = unshuffle_in;
+    a.ks_scratch = ks_floats ? buf : nullptr; a.ks_floats = ks_floats;
+    Conv3x3Plan p;
+    RF_TRY(plan_conv3x3(a, &p));
+    snprintf(key, key_len, "%s", p.key);
+    grid[0] = (int)p.grid.x; grid[1] = (int)p.grid.y; grid[2] = (int)p.grid.z;
+    *block = (int)p.block;
+    *ksplit = p.ksplit;
+    *level0 = p.l0 != 0;
+    return RF_OK;
+}
+
 int rf_convT2x2_scratch_bytes(int Cin, int Cout, size_t* bytes) {
     RF_CHECK_ARG(bytes && Cin > 0 && Cout > 0, "convT2x2_scratch_bytes: bad arguments");
     *bytes = packed1x1_floats(Cin, 4 * Cout) * sizeof(float);

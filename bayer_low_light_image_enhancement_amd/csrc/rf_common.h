@@ -267,6 +267,19 @@ struct Conv3x3Args {
     float* ks_scratch = nullptr;
     size_t ks_floats = 0;
 };
+// What launch_conv3x3 will launch for `a`, decided on the host alone (no HIP call): plan_conv3x3 in rf_conv3x3.hip is the single
+// statement of the selection rule.
+struct Conv3x3Plan {
+    int nco, log2_rw, rpw, nwv, ks, l0;    // the template arguments of conv3x3_kernel (ks: ksplit > 1)
+    int ngroups, tiles_x, ntiles, vec;     // the kernel's integer arguments
+    dim3 grid;                             // grid.z = ksplit
+    unsigned block;
+    int ksplit;                            // workgroups that share the input channels of a tile (1: no split); above 1 only where
+                                           // every workgroup has exactly one tile, grid.x == ngroups * ntiles
+    char key[64];                          // the profiler key: the instantiation's name (a split launch: the unsplit kernel's)
+    double flops, bytes;                   // of the whole launch, for ProfScope
+};
+int plan_conv3x3(const Conv3x3Args& a, Conv3x3Plan* p);    // RF_E_INVALID (and the error text) for arguments launch_conv3x3 refuses
 int launch_conv3x3(const Conv3x3Args& a, hipStream_t st);
 // dense NCHW source and destination (batch strides Cin h w / Cout h w, also through a pixel (un)shuffle); everything else zero
 inline Conv3x3Args conv3x3_dense(const float* x, const float* wp, const float* bias, float* out, int B, int Cin, int Cout, int h, int w, int act) {

@@ -12,11 +12,11 @@
 //
 // Workgroup = NWV waves; it owns a (NWV*RW*RPW rows) x (64/RW cols) pixel tile and NCO*16 output
 // channels, and is persistent over several such tiles.  Per 8-input-channel chunk the halo'd input tile and the matching slice of the
-// lane-ordered packed weights sit in LDS; every wave then walks 2 k-sets x 9 taps.
+// lane-ordered packed weights sit in LDS; every wave then walks 2 k-sets x 18 transformed taps.
 //   * B operand: lane (kq, j) owns 4 consecutive pixels of one row.  Two ds_read_b128 per
-//     (k-set, dy) fetch the 6 neighbours those pixels need; tap dx of pixel g is v[g + dx], so
-//     one LDS read feeds 12 * NCO MFMAs.  The plane stride (448 floats) keeps the four kq
-//     planes on disjoint LDS slots.
+//     (k-set, input row) fetch the 6 neighbours those pixels need; their transform B^T d is the operand of the
+//     row's 6 taps, so one LDS read feeds 6 * NCO MFMAs per output row it reaches.  The plane stride (448 floats)
+//     keeps the four kq planes on disjoint LDS slots.
 //   * A operand: ds_read_b32, lane-linear (conflict-free).
 //   * D: channels 16t + 4kq + r for the lane's 4 pixels -> 16-byte stores.
 // Pipeline: LDS is double buffered; the global loads of chunk c+1 (input tile with zero
@@ -43,7 +43,7 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 // (image, tile, output group) -- adds the partials in split order (deterministic whatever the arrival order), applies bias /
 // activation / clamp and stores.  One 16 x 16 frame at level 3 is a chain of 32 chunk barriers on 4 workgroups otherwise.
 //
-// L0 (wide level-0 launches with Cin <= 32, rows of whole aligned float4s; dispatched by launch_rw, nothing else changes):
+// L0 (wide level-0 launches with Cin <= 32, rows of whole aligned float4s; chosen by plan_conv3x3, nothing else changes):
 //   bit 0: the output group's complete Winograd weight set (Cin/4 k-sets x 18 taps x NCO x 64 floats, at most 72 KB) is loaded
 //          into LDS once per workgroup and stays there; the chunk loop stages input only.
 //   bit 1: the halo'd input tile is staged by row segments: the 64 interior floats of a (channel, row) as 16-byte loads,
@@ -304,176 +304,178 @@ __global__ void __launch_bounds__(64 * NWV, (NWV >= 8 || NCO >= 3) ? 1 : 2) conv
             buf ^= 1;
         }
 
-    // ---- epilogue of this tile (its stores drain behind the next tile's first MFMA block)
-    int kq_ = kq;                      // opaque per tile: keeps the bias values and output row pointers from being
-    asm volatile("" : "+v"(kq_));      // hoisted out of the tile loop (they would stay live across every MFMA block)
-    const int x = ex0 + 4 * cg;
-    // output transform A^T m of the lane's F(4,3) tiles: u[r][g], channel 16 (t0 + t) + 4 kq + r, pixel x + g
-    auto transform = [&](int rr, int t, float (&u)[4][4]) {
-        const f32x4* mm = acc[rr][t];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float s12 = mm[1][r] + mm[2][r], d12 = mm[1][r] - mm[2][r], s34 = mm[3][r] + mm[4][r], d34 = mm[3][r] - mm[4][r];
-            u[r][0] = (mm[0][r] + s12) + s34;
-            u[r][1] = fmaf(2.f, d34, d12);
-            u[r][2] = fmaf(4.f, s34, s12);
-            u[r][3] = fmaf(8.f, d34, d12) + mm[5][r];
-        }
-    };
-    // bias, activation, clamp.  The (uniform) choice of the activation is made once per 16 values: written per value it stayed
-    // a chain of six scalar branches around every one of them, and the bias a ds_read_b32 + lgkmcnt(0) per channel.
-    auto finish = [&](int t, float (&v)[4][4]) {
-        const float4 b4 = *reinterpret_cast<const float4*>(bias_l + 16 * t + 4 * kq_);
-        const float bs[4] = {b4.x, b4.y, b4.z, b4.w};
-        auto each = [&](auto f) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) v[r][g] = f(v[r][g] + bs[r]);
-        };
-        if (a.act == 1) each([](float u) { return u > 0.f ? u : 0.2f * u; });
-        else if (a.act == 2) each([](float u) { return fmaxf(u, 0.f); });
-        else if (a.act == 3) each([](float u) { return gelu_fast(u); });
-        else if (a.act == 4) each([](float u) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * u)); });      // tanh
-        else each([](float u) { return u; });
-        if (a.clamp_out) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) v[r][g] = fminf(fmaxf(v[r][g], 0.f), 1.f);
-        }
-    };
-    auto store_tile = [&](int t, int y, const float (&v)[4][4]) {
-        const int cobase = 16 * (t0 + t) + 4 * kq_;
-        if (a.store == 0) {
+        // ---- epilogue of this tile (its stores drain behind the next tile's first MFMA block)
+        int kq_ = kq;                      // opaque per tile: keeps the bias values and output row pointers from being
+        asm volatile("" : "+v"(kq_));      // hoisted out of the tile loop (they would stay live across every MFMA block)
+        const int x = ex0 + 4 * cg;
+        // output transform A^T m of the lane's F(4,3) tiles: u[r][g], channel 16 (t0 + t) + 4 kq + r, pixel x + g
+        auto transform = [&](int rr, int t, float (&u)[4][4]) {
+            const f32x4* mm = acc[rr][t];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int co = cobase + r;
-                if (co >= a.Cout) continue;
-                float* o = outb + ((size_t)co * h + y) * w + x;
+                const float s12 = mm[1][r] + mm[2][r], d12 = mm[1][r] - mm[2][r], s34 = mm[3][r] + mm[4][r], d34 = mm[3][r] - mm[4][r];
+                u[r][0] = (mm[0][r] + s12) + s34;
+                u[r][1] = fmaf(2.f, d34, d12);
+                u[r][2] = fmaf(4.f, s34, s12);
+                u[r][3] = fmaf(8.f, d34, d12) + mm[5][r];
+            }
+        };
+        // bias, activation, clamp.  The (uniform) choice of the activation is made once per 16 values: written per value it stayed
+        // a chain of six scalar branches around every one of them, and the bias a ds_read_b32 + lgkmcnt(0) per channel.
+        auto finish = [&](int t, float (&v)[4][4]) {
+            const float4 b4 = *reinterpret_cast<const float4*>(bias_l + 16 * t + 4 * kq_);
+            const float bs[4] = {b4.x, b4.y, b4.z, b4.w};
+            auto each = [&](auto f) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) v[r][g] = f(v[r][g] + bs[r]);
+            };
+            if (a.act == 1) each([](float u) { return u > 0.f ? u : 0.2f * u; });
+            else if (a.act == 2) each([](float u) { return fmaxf(u, 0.f); });
+            else if (a.act == 3) each([](float u) { return gelu_fast(u); });
+            else if (a.act == 4) each([](float u) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * u)); });      // tanh
+            else each([](float u) { return u; });
+            if (a.clamp_out) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) v[r][g] = fminf(fmaxf(v[r][g], 0.f), 1.f);
+            }
+        };
+        auto store_tile = [&](int t, int y, const float (&v)[4][4]) {
+            const int cobase = 16 * (t0 + t) + 4 * kq_;
+            if (a.store == 0) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int co = cobase + r;
+                    if (co >= a.Cout) continue;
+                    float* o = outb + ((size_t)co * h + y) * w + x;
+                    if (vec) {
+                        *reinterpret_cast<float4*>(o) = make_float4(v[r][0], v[r][1], v[r][2], v[r][3]);
+                    } else {
+#pragma unroll
+                        for (int g = 0; g < 4; ++g)
+                            if (x + g < w) o[g] = v[r][g];
+                    }
+                }
+            } else if (a.store == 1) {
+                // Downsample: out[4*co + 2*(y&1) + (x&1)][y>>1][x>>1]
+                const int h2 = h >> 1, w2 = w >> 1;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int co = cobase + r;
+                    if (co >= a.Cout) continue;
+                    float* o = outb + (((size_t)(4 * co + 2 * (y & 1))) * h2 + (y >> 1)) * w2 + (x >> 1);
+                    const size_t ps = (size_t)h2 * w2;
+                    if (vec) {
+                        *reinterpret_cast<float2*>(o) = make_float2(v[r][0], v[r][2]);
+                        *reinterpret_cast<float2*>(o + ps) = make_float2(v[r][1], v[r][3]);
+                    } else {
+#pragma unroll
+                        for (int g = 0; g < 4; ++g)
+                            if (x + g < w) o[(size_t)(g & 1) * ps + (g >> 1)] = v[r][g];
+                    }
+                }
+            } else {
+                // conv_out + PixelShuffle(2): GEMM row 4*c + 2*i + jj -> out[c][2y+i][2x+jj]
+                if (cobase >= a.Cout) return;
+                const int c = cobase >> 2;
+                float* op = outb + (size_t)c * 4 * h * w;
+                const int w2 = 2 * w;
                 if (vec) {
-                    *reinterpret_cast<float4*>(o) = make_float4(v[r][0], v[r][1], v[r][2], v[r][3]);
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) {
+                        float* row = op + (size_t)(2 * y + i) * w2 + 2 * x;
+                        *reinterpret_cast<float4*>(row) = make_float4(v[2 * i][0], v[2 * i + 1][0], v[2 * i][1], v[2 * i + 1][1]);
+                        *reinterpret_cast<float4*>(row + 4) = make_float4(v[2 * i][2], v[2 * i + 1][2], v[2 * i][3], v[2 * i + 1][3]);
+                    }
                 } else {
 #pragma unroll
                     for (int g = 0; g < 4; ++g)
-                        if (x + g < w) o[g] = v[r][g];
+                        if (x + g < w) {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r)
+                                op[(size_t)(2 * y + (r >> 1)) * w2 + 2 * (x + g) + (r & 1)] = v[r][g];
+                        }
                 }
             }
-        } else if (a.store == 1) {
-            // Downsample: out[4*co + 2*(y&1) + (x&1)][y>>1][x>>1]
-            const int h2 = h >> 1, w2 = w >> 1;
+        };
+        if constexpr (!KS) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int co = cobase + r;
-                if (co >= a.Cout) continue;
-                float* o = outb + (((size_t)(4 * co + 2 * (y & 1))) * h2 + (y >> 1)) * w2 + (x >> 1);
-                const size_t ps = (size_t)h2 * w2;
-                if (vec) {
-                    *reinterpret_cast<float2*>(o) = make_float2(v[r][0], v[r][2]);
-                    *reinterpret_cast<float2*>(o + ps) = make_float2(v[r][1], v[r][3]);
-                } else {
+            for (int rr = 0; rr < RPW; ++rr) {
+                const int y = ey0 + (wave * RPW + rr) * RW + rowj;
+                if (y >= h || x >= w) continue;
 #pragma unroll
-                    for (int g = 0; g < 4; ++g)
-                        if (x + g < w) o[(size_t)(g & 1) * ps + (g >> 1)] = v[r][g];
+                for (int t = 0; t < NCO; ++t) {
+                    if (t0 + t >= NT) break;
+                    float v[4][4];   // [r][g]
+                    transform(rr, t, v);
+                    finish(t, v);
+                    store_tile(t, y, v);
                 }
             }
         } else {
-            // conv_out + PixelShuffle(2): GEMM row 4*c + 2*i + jj -> out[c][2y+i][2x+jj]
-            if (cobase >= a.Cout) return;
-            const int c = cobase >> 2;
-            float* op = outb + (size_t)c * 4 * h * w;
-            const int w2 = 2 * w;
-            if (vec) {
+            // partial tiles [split][image][channel][y][x] (the launcher checks w % 4 == 0), then the ticket
+            unsigned* counter = reinterpret_cast<unsigned*>(a.ks_scratch) + ((size_t)b * ntiles + tile) * ngroups + grp;
+            float* part = a.ks_scratch + kKsCounters;
+            const size_t split_stride = (size_t)a.B * a.Cout * h * w;
+            float* mine = part + (size_t)kz * split_stride + (size_t)b * a.Cout * h * w;
 #pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    float* row = op + (size_t)(2 * y + i) * w2 + 2 * x;
-                    *reinterpret_cast<float4*>(row) = make_float4(v[2 * i][0], v[2 * i + 1][0], v[2 * i][1], v[2 * i + 1][1]);
-                    *reinterpret_cast<float4*>(row + 4) = make_float4(v[2 * i][2], v[2 * i + 1][2], v[2 * i][3], v[2 * i + 1][3]);
-                }
-            } else {
+            for (int rr = 0; rr < RPW; ++rr) {
+                const int y = ey0 + (wave * RPW + rr) * RW + rowj;
+                if (y >= h || x >= w) continue;
 #pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    if (x + g < w) {
+                for (int t = 0; t < NCO; ++t) {
+                    if (t0 + t >= NT) break;
+                    float v[4][4];
+                    transform(rr, t, v);
 #pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            op[(size_t)(2 * y + (r >> 1)) * w2 + 2 * (x + g) + (r & 1)] = v[r][g];
+                    for (int r = 0; r < 4; ++r) {
+                        const int co = 16 * (t0 + t) + 4 * kq_ + r;
+                        if (co < a.Cout) *reinterpret_cast<float4*>(mine + ((size_t)co * h + y) * w + x) = make_float4(v[r][0], v[r][1], v[r][2], v[r][3]);
                     }
-            }
-        }
-    };
-    if constexpr (!KS) {
-#pragma unroll
-        for (int rr = 0; rr < RPW; ++rr) {
-            const int y = ey0 + (wave * RPW + rr) * RW + rowj;
-            if (y >= h || x >= w) continue;
-#pragma unroll
-            for (int t = 0; t < NCO; ++t) {
-                if (t0 + t >= NT) break;
-                float v[4][4];   // [r][g]
-                transform(rr, t, v);
-                finish(t, v);
-                store_tile(t, y, v);
-            }
-        }
-    } else {
-        // partial tiles [split][image][channel][y][x] (the launcher checks w % 4 == 0), then the ticket
-        unsigned* counter = reinterpret_cast<unsigned*>(a.ks_scratch) + ((size_t)b * ntiles + tile) * ngroups + grp;
-        float* part = a.ks_scratch + kKsCounters;
-        const size_t split_stride = (size_t)a.B * a.Cout * h * w;
-        float* mine = part + (size_t)kz * split_stride + (size_t)b * a.Cout * h * w;
-#pragma unroll
-        for (int rr = 0; rr < RPW; ++rr) {
-            const int y = ey0 + (wave * RPW + rr) * RW + rowj;
-            if (y >= h || x >= w) continue;
-#pragma unroll
-            for (int t = 0; t < NCO; ++t) {
-                if (t0 + t >= NT) break;
-                float v[4][4];
-                transform(rr, t, v);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int co = 16 * (t0 + t) + 4 * kq_ + r;
-                    if (co < a.Cout) *reinterpret_cast<float4*>(mine + ((size_t)co * h + y) * w + x) = make_float4(v[r][0], v[r][1], v[r][2], v[r][3]);
                 }
             }
-        }
-        __shared__ unsigned ticket;
-        // release (every workgroup: its partial tile is written back before the ticket is taken) / acquire (the last workgroup
-        // only: it must not read stale lines).  A full __threadfence() on both sides made EVERY workgroup invalidate its L2.
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        __syncthreads();
-        if (tid == 0) ticket = atomicAdd(counter, 1u);
-        __syncthreads();
-        if (ticket != (unsigned)(ksplit - 1)) return;  // not the last split of this tile
-        if (tid == 0) *counter = 0u;                   // ready for the next launch (stream order)
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            __shared__ unsigned ticket;
+            // release (every workgroup: its partial tile is written back before the ticket is taken) / acquire (the last workgroup
+            // only: it must not read stale lines).  A full __threadfence() on both sides made EVERY workgroup invalidate its L2.
+            // The returns below leave the tile loop for good.  That is sound because a split launch gives every workgroup exactly
+            // one tile: plan_conv3x3 sets Conv3x3Plan::ksplit above 1 only where grid.x == ngroups * ntiles (nwg == ntiles).
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            __syncthreads();
+            if (tid == 0) ticket = atomicAdd(counter, 1u);
+            __syncthreads();
+            if (ticket != (unsigned)(ksplit - 1)) return;  // not the last split of this tile
+            if (tid == 0) *counter = 0u;                   // ready for the next launch (stream order)
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 #pragma unroll
-        for (int rr = 0; rr < RPW; ++rr) {
-            const int y = ey0 + (wave * RPW + rr) * RW + rowj;
-            if (y >= h || x >= w) continue;
+            for (int rr = 0; rr < RPW; ++rr) {
+                const int y = ey0 + (wave * RPW + rr) * RW + rowj;
+                if (y >= h || x >= w) continue;
 #pragma unroll
-            for (int t = 0; t < NCO; ++t) {
-                if (t0 + t >= NT) break;
-                float v[4][4];
+                for (int t = 0; t < NCO; ++t) {
+                    if (t0 + t >= NT) break;
+                    float v[4][4];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int co = 16 * (t0 + t) + 4 * kq_ + r;
-                    float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (co < a.Cout) {
-                        const float* src = part + (size_t)b * a.Cout * h * w + ((size_t)co * h + y) * w + x;
-                        for (int z = 0; z < ksplit; ++z) {          // split order, whatever the arrival order
-                            const float4 pz = *reinterpret_cast<const float4*>(src + (size_t)z * split_stride);
-                            sum.x += pz.x; sum.y += pz.y; sum.z += pz.z; sum.w += pz.w;
+                    for (int r = 0; r < 4; ++r) {
+                        const int co = 16 * (t0 + t) + 4 * kq_ + r;
+                        float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
+                        if (co < a.Cout) {
+                            const float* src = part + (size_t)b * a.Cout * h * w + ((size_t)co * h + y) * w + x;
+                            for (int z = 0; z < ksplit; ++z) {          // split order, whatever the arrival order
+                                const float4 pz = *reinterpret_cast<const float4*>(src + (size_t)z * split_stride);
+                                sum.x += pz.x; sum.y += pz.y; sum.z += pz.z; sum.w += pz.w;
+                            }
                         }
+                        v[r][0] = sum.x; v[r][1] = sum.y; v[r][2] = sum.z; v[r][3] = sum.w;
                     }
-                    v[r][0] = sum.x; v[r][1] = sum.y; v[r][2] = sum.z; v[r][3] = sum.w;
+                    finish(t, v);
+                    store_tile(t, y, v);
                 }
-                finish(t, v);
-                store_tile(t, y, v);
             }
+            return;
         }
-        return;
-    }
     }
 }
 
@@ -482,84 +484,10 @@ size_t conv3x3_ksplit_floats(int B, int Cout, int h, int w) {
     return ((long)B * h * w <= 16384) ? (size_t)kKsCounters + (size_t)8 * B * Cout * h * w : 0;
 }
 
-// input-channel split of a launch whose every tile has its own workgroup: 1 = none
-static int ksplit_for(const Conv3x3Args& a, int ntiles, int ngroups, int vec, const dim3& grid) {
-    if (!a.ks_scratch || !vec || !aligned16(a.ks_scratch)) return 1;
-    const long total = (long)ntiles * ngroups * a.B;
-    const int nchunks = cdiv(a.Cin, KC);
-    // only for launches of at most 64 workgroups, split into at most 256: a 256-workgroup launch split three ways was 2.2-2.8 x
-    // SLOWER (46 -> 103 us with release / acquire fences, 129 us with a full fence on both sides): the hand-over costs every
-    // workgroup an L2 write-back
-    if (total > 64 || total > kKsCounters || nchunks < 8 || (long)grid.x != (long)ngroups * ntiles) return 1;
-    int S = nchunks / 4;
-    if (S > 8) S = 8;
-    while (S > 1 && total * S > 256) --S;
-    if (S < 2 || (size_t)kKsCounters + (size_t)S * a.B * a.Cout * a.h * a.w > a.ks_floats) return 1;
-    return S;
-}
-
-// Shapes of the level-0 path (template argument L0 of the kernel): a wide launch that is not small, all of Cin in at most four
-// chunks (resident weights), one or two output tiles per group (the instantiations that exist), and input rows made of whole,
-// 16-byte aligned float4s.  The mosaic input of the embedding conv is gathered element by element and stays on the generic path.
-static bool level0_path(const Conv3x3Args& a, int nco, bool small) {
-    return !small && nco <= 2 && a.w > 32 && a.h >= 16 && a.Cin <= 32 && !a.unshuffle_in && a.w % 4 == 0 && aligned16(a.x) &&
-           a.x_bstride % 4 == 0;
-}
-
-template <int NCO>
-static void launch_rw(const Conv3x3Args& a, int ngroups, int vec, bool small, hipStream_t st) {
-    // Wide images (w > 32): 8 waves share one 18-tap weight slice, one workgroup per CU; a wave owns one pixel
-    // row of 64 (NCO >= 3) or two (NCO <= 2: 16x64 tile, 144 MFMAs per barrier).  Narrow images fall back to
-    // 4-wave tiles of 32x8 or 16x16 pixels.  Workgroups are persistent over tiles of one (image, output group).
-    const int lrw = a.w > 32 ? 0 : (a.w > 16 ? 1 : 2);
-    constexpr int RPWB = NCO <= 2 ? 2 : 1;
-    auto grid_for_tiles = [&](int ntiles) {
-        const long total = (long)ntiles * ngroups * a.B;
-        const int wgs = cdiv(ntiles, (int)((total + 255) / 256));      // one resident workgroup per CU
-        return dim3((unsigned)(ngroups * wgs), (unsigned)a.B);
-    };
-    if (small && lrw == 0) {
-        // few pixels (one frame at levels 2-3): 4-wave workgroups on 4x64 tiles, more of them
-        const int txs = cdiv(a.w, 64), ntiles = txs * cdiv(a.h, 4);
-        dim3 grid = grid_for_tiles(ntiles);
-        const int S = ksplit_for(a, ntiles, ngroups, vec, grid);
-        grid.z = (unsigned)S;
-        if (S > 1) conv3x3_kernel<NCO, 0, 1, 4, true><<<grid, 256, 0, st>>>(a, ngroups, txs, ntiles, vec);
-        else conv3x3_kernel<NCO, 0, 1, 4><<<grid, 256, 0, st>>>(a, ngroups, txs, ntiles, vec);
-    } else if (NCO == 1 && lrw == 0 && a.h >= 16) {
-        // one output tile: 16 waves of one row each (103 registers, four waves per SIMD cover each other's LDS and
-        // barrier waits) beat 8 waves of two rows by 7 %; with NCO = 2 the same shape spills at the 128-register cap
-        const int txs = cdiv(a.w, 64), ntiles = txs * cdiv(a.h, 16);
-        if (level0_path(a, NCO, small)) conv3x3_kernel<1, 0, 1, 16, false, 3><<<grid_for_tiles(ntiles), 1024, 0, st>>>(a, ngroups, txs, ntiles, vec);
-        else conv3x3_kernel<1, 0, 1, 16><<<grid_for_tiles(ntiles), 1024, 0, st>>>(a, ngroups, txs, ntiles, vec);
-    } else if (lrw == 0 && a.h >= 8 * RPWB) {
-        const int txs = cdiv(a.w, 64), ntiles = txs * cdiv(a.h, 8 * RPWB);
-        if constexpr (NCO == 2) {
-            if (level0_path(a, NCO, small)) {
-                conv3x3_kernel<2, 0, 2, 8, false, 3><<<grid_for_tiles(ntiles), 512, 0, st>>>(a, ngroups, txs, ntiles, vec);
-                return;
-            }
-        }
-        conv3x3_kernel<NCO, 0, RPWB, 8><<<grid_for_tiles(ntiles), 512, 0, st>>>(a, ngroups, txs, ntiles, vec);
-    } else if (lrw == 0 && a.h >= 8) {
-        const int txs = cdiv(a.w, 64), ntiles = txs * cdiv(a.h, 8);
-        conv3x3_kernel<NCO, 0, 1, 8><<<grid_for_tiles(ntiles), 512, 0, st>>>(a, ngroups, txs, ntiles, vec);
-    } else {
-        const int txs = cdiv(a.w, 64 >> lrw), ntiles = txs * cdiv(a.h, 4 << lrw);
-        dim3 grid = grid_for_tiles(ntiles);
-        const int S = ksplit_for(a, ntiles, ngroups, vec, grid);
-        grid.z = (unsigned)S;
-        if (S > 1) {
-            if (lrw == 0) conv3x3_kernel<NCO, 0, 1, 4, true><<<grid, 256, 0, st>>>(a, ngroups, txs, ntiles, vec);
-            else if (lrw == 1) conv3x3_kernel<NCO, 1, 1, 4, true><<<grid, 256, 0, st>>>(a, ngroups, txs, ntiles, vec);
-            else conv3x3_kernel<NCO, 2, 1, 4, true><<<grid, 256, 0, st>>>(a, ngroups, txs, ntiles, vec);
-        } else if (lrw == 0) conv3x3_kernel<NCO, 0, 1, 4><<<grid, 256, 0, st>>>(a, ngroups, txs, ntiles, vec);
-        else if (lrw == 1) conv3x3_kernel<NCO, 1, 1, 4><<<grid, 256, 0, st>>>(a, ngroups, txs, ntiles, vec);
-        else conv3x3_kernel<NCO, 2, 1, 4><<<grid, 256, 0, st>>>(a, ngroups, txs, ntiles, vec);
-    }
-}
-
-int launch_conv3x3(const Conv3x3Args& a, hipStream_t st) {
+// THE selection rule: argument checks, then the instantiation <NCO, LOG2_RW, RPW, NWV, KS, L0>, its geometry and its profiler key
+// (the name of the unsplit kernel: a split launch differs in grid.z alone).  No HIP call, no launch; a plan exists only for
+// arguments launch_conv3x3 accepts.
+int plan_conv3x3(const Conv3x3Args& a, Conv3x3Plan* p) {
     RF_CHECK_ARG(a.B > 0 && a.B <= 65535 && a.Cin > 0 && a.Cout > 0 && a.h > 0 && a.w > 0, "conv3x3: bad sizes");
     RF_CHECK_ARG(a.store == 0 || (a.store == 1 && a.h % 2 == 0 && a.w % 2 == 0) || (a.store == 2 && a.Cout % 4 == 0),
                  "conv3x3: store mode %d incompatible with Cout=%d h=%d w=%d", a.store, a.Cout, a.h, a.w);
@@ -580,26 +508,78 @@ int launch_conv3x3(const Conv3x3Args& a, hipStream_t st) {
             while (nco > 1 && t4 * cdiv(NT, nco) < 192) nco = (nco == 4 || nco == 2) ? nco / 2 : 1;
         }
     }
-    const int ngroups = cdiv(NT, nco);
-    const int vec = (a.w % 4 == 0) && aligned16(a.out) && (a.out_bstride % 4 == 0);
-    char key[64];
-    {
-        const int lrw = a.w > 32 ? 0 : (a.w > 16 ? 1 : 2), rpwb = nco <= 2 ? 2 : 1;
-        const int wide = lrw == 0 && a.h >= 8;
-        snprintf(key, sizeof(key), "conv3x3_kernel<%d, %d, %d, %d>", nco, lrw, (wide && a.h >= 8 * rpwb) ? rpwb : 1, wide ? 8 : 4);
-        if (nco == 1 && lrw == 0 && a.h >= 16) snprintf(key, sizeof(key), "conv3x3_kernel<1, 0, 1, 16>");
-        if (small) snprintf(key, sizeof(key), "conv3x3_kernel<%d, 0, 1, 4>", nco);
-        if (level0_path(a, nco, small)) snprintf(key, sizeof(key), "conv3x3_kernel<%d, 0, %d, %d, false, 3>", nco, nco == 1 ? 1 : 2, nco == 1 ? 16 : 8);
+    *p = Conv3x3Plan{};
+    p->nco = nco;
+    p->ngroups = cdiv(NT, nco);
+    p->vec = (a.w % 4 == 0) && aligned16(a.out) && (a.out_bstride % 4 == 0);
+    // Wide images (w > 32): 8 waves share one 18-tap weight slice, one workgroup per CU; a wave owns one pixel row of 64, or two
+    // where 16 rows exist and NCO = 2 (16x64 tile, 144 MFMAs per barrier).  One output tile: 16 waves of one row each (103 registers,
+    // four waves per SIMD cover each other's LDS and barrier waits) beat 8 waves of two rows by 7 %; with NCO = 2 the same shape
+    // spills at the 128-register cap.  Small launches (few pixels: one frame at levels 2-3) and images under 8 rows take 4-wave
+    // workgroups on 4x64 tiles, more of them; narrow images 4-wave tiles of 8x32 or 16x16 pixels.
+    p->log2_rw = a.w > 32 ? 0 : (a.w > 16 ? 1 : 2);
+    const bool wide = p->log2_rw == 0 && !small && a.h >= 8, rows16 = wide && nco <= 2 && a.h >= 16;
+    p->nwv = !wide ? 4 : (rows16 && nco == 1) ? 16 : 8;
+    p->rpw = (rows16 && nco == 2) ? 2 : 1;
+    // The level-0 path (template argument L0 of the kernel) for the 16-row tiles: all of Cin in at most four chunks (resident
+    // weights) and input rows made of whole, 16-byte aligned float4s.  The mosaic input of the embedding conv is gathered element
+    // by element and stays on the generic path.
+    p->l0 = (rows16 && a.Cin <= 32 && !a.unshuffle_in && a.w % 4 == 0 && aligned16(a.x) && a.x_bstride % 4 == 0) ? 3 : 0;
+    // workgroups are persistent over the tiles of one (image, output group): one resident workgroup per CU
+    p->tiles_x = cdiv(a.w, 64 >> p->log2_rw);
+    p->ntiles = p->tiles_x * cdiv(a.h, (p->nwv * p->rpw) << p->log2_rw);
+    const long total = (long)p->ntiles * p->ngroups * a.B;
+    p->grid = dim3((unsigned)(p->ngroups * cdiv(p->ntiles, (int)((total + 255) / 256))), (unsigned)a.B);
+    p->block = 64u * p->nwv;
+    // Input-channel split (KS) of a 4-wave launch whose every tile has its own workgroup, grid.x == ngroups * ntiles: the kernel's
+    // split epilogue returns from its tile loop on the strength of that.  Only for launches of at most 64 workgroups, split into
+    // at most 256: a 256-workgroup launch split three ways was 2.2-2.8 x SLOWER (46 -> 103 us with release / acquire fences, 129 us
+    // with a full fence on both sides): the hand-over costs every workgroup an L2 write-back
+    const int nchunks = cdiv(a.Cin, KC);
+    p->ksplit = 1;
+    if (p->nwv == 4 && a.ks_scratch && p->vec && aligned16(a.ks_scratch) && total <= 64 && nchunks >= 8 && (long)p->grid.x == (long)p->ngroups * p->ntiles) {
+        int S = nchunks / 4 < 8 ? nchunks / 4 : 8;
+        while (S > 1 && total * S > 256) --S;
+        if (S >= 2 && (size_t)kKsCounters + (size_t)S * a.B * a.Cout * a.h * a.w <= a.ks_floats) p->ksplit = S;
     }
+    static_assert(64 <= kKsCounters, "a ticket per workgroup of the unsplit launch");
+    p->ks = p->ksplit > 1;
+    p->grid.z = (unsigned)p->ksplit;
+    snprintf(p->key, sizeof(p->key), "conv3x3_kernel<%d, %d, %d, %d%s>", p->nco, p->log2_rw, p->rpw, p->nwv, p->l0 ? ", false, 3" : "");
     const double px = (double)a.B * a.h * a.w;
-    ProfScope prof(st, key, 18.0 * a.Cin * a.Cout * px, 4.0 * px * (a.Cin + a.Cout));
-    switch (nco) {
-        case 4: launch_rw<4>(a, ngroups, vec, small, st); break;
-        case 3: launch_rw<3>(a, ngroups, vec, small, st); break;
-        case 2: launch_rw<2>(a, ngroups, vec, small, st); break;
-        default: launch_rw<1>(a, ngroups, vec, small, st); break;
-    }
-    return check_launch("conv3x3");
+    p->flops = 18.0 * a.Cin * a.Cout * px;
+    p->bytes = 4.0 * px * (a.Cin + a.Cout);
+    return RF_OK;
+}
+
+// Every instantiation there is, one row each: its template arguments and its launch.
+struct Conv3x3Inst {
+    int nco, log2_rw, rpw, nwv, ks, l0;
+    void (*launch)(const Conv3x3Args&, const Conv3x3Plan&, hipStream_t);
+};
+template <int NCO, int LOG2_RW, int RPW, int NWV, bool KS, int L0>
+static void launch_inst(const Conv3x3Args& a, const Conv3x3Plan& p, hipStream_t st) {
+    conv3x3_kernel<NCO, LOG2_RW, RPW, NWV, KS, L0><<<p.grid, p.block, 0, st>>>(a, p.ngroups, p.tiles_x, p.ntiles, p.vec);
+}
+#define RF_INST(...) {__VA_ARGS__, launch_inst<__VA_ARGS__>}
+#define RF_NWV4(NCO, KS) RF_INST(NCO, 0, 1, 4, KS, 0), RF_INST(NCO, 1, 1, 4, KS, 0), RF_INST(NCO, 2, 1, 4, KS, 0)     // 4x64, 8x32, 16x16 tiles
+static const Conv3x3Inst kInst[] = {
+    RF_NWV4(1, false), RF_NWV4(2, false), RF_NWV4(3, false), RF_NWV4(4, false),
+    RF_NWV4(1, true), RF_NWV4(2, true), RF_NWV4(3, true), RF_NWV4(4, true),
+    RF_INST(1, 0, 1, 8, false, 0), RF_INST(2, 0, 1, 8, false, 0), RF_INST(3, 0, 1, 8, false, 0), RF_INST(4, 0, 1, 8, false, 0),      // 8x64
+    RF_INST(2, 0, 2, 8, false, 0), RF_INST(2, 0, 2, 8, false, 3), RF_INST(1, 0, 1, 16, false, 0), RF_INST(1, 0, 1, 16, false, 3),    // 16x64
+};
+
+int launch_conv3x3(const Conv3x3Args& a, hipStream_t st) {
+    Conv3x3Plan p;
+    RF_TRY(plan_conv3x3(a, &p));
+    ProfScope prof(st, p.key, p.flops, p.bytes);
+    for (const Conv3x3Inst& r : kInst)
+        if (r.nco == p.nco && r.log2_rw == p.log2_rw && r.rpw == p.rpw && r.nwv == p.nwv && r.ks == p.ks && r.l0 == p.l0) {
+            r.launch(a, p, st);
+            return check_launch("conv3x3");
+        }
+    RF_CHECK_ARG(false, "conv3x3: no kernel instantiation %s (split %d)", p.key, p.ksplit);
 }
 
 }  // namespace rf

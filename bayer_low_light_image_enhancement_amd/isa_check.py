@@ -99,6 +99,16 @@ def extract_code_objects(path: str, outdir: str):
     return sorted(os.path.join(outdir, f) for f in os.listdir(outdir) if "amdgcn-amd-amdhsa--gfx950" in f)
 
 
+def kernel_names(path: str):
+    """The (mangled) kernel names of a library's code objects -- the keys of :func:`scan_library`'s report -- without disassembling."""
+    names = set()
+    with tempfile.TemporaryDirectory(prefix="rf_isa_") as tmp:
+        for co in extract_code_objects(path, tmp):
+            notes = subprocess.run([_tool("llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
+            names.update(ln.split(":", 1)[1].strip() for ln in notes.splitlines() if ln.strip().startswith(".name:"))
+    return sorted(names)
+
+
 def scan_library(path: str):
     """{kernel: {'scratch': bytes/lane, 'vgpr_spill': n, 'sgpr_spill': n, 'vgprs': n, 'vulnerable': [instruction text, ...]}}"""
     report = {}

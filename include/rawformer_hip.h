@@ -224,6 +224,16 @@ int rf_dwconv3x3(const float* in, float* out, const float* weight, const float* 
 int rf_conv3x3_scratch_bytes(int Cin, int Cout, size_t* bytes);
 int rf_conv3x3(const float* in, float* out, const float* weight, const float* bias, void* scratch,
                int act, int store, int B, int Cin, int Cout, int h, int w, void* stream);
+/* Host only, no launch, no GPU needed: what a dense 3x3 convolution of these sizes launches.  store as for rf_conv3x3;
+ * unshuffle_in: the input is read through the Bayer pack (Cin = 4, the embedding conv of the forward pass); aligned: input, output
+ * and split scratch are 16-byte aligned, as rf_conv3x3's always are (0: none is: scalar stores, no level-0 path, no split; the
+ * batch strides Cin h w / Cout h w follow from the sizes); ks_floats: floats of scratch for the input-channel split of small
+ * launches (0: none, as in rf_conv3x3; the forward pass has 4096 + 8 B Cout h w where B h w <= 16384).  key: the kernel
+ * instantiation (= its profiler key; a split launch keeps the key of the unsplit kernel), grid[3] with grid[2] = *ksplit, the
+ * workgroups that share a tile's input channels (1: no split), block, and *level0: the level-0 path (resident weights, input
+ * staged by row segments) is taken.  Refuses what rf_conv3x3 refuses. */
+int rf_conv3x3_plan(int B, int Cin, int Cout, int h, int w, int store, int unshuffle_in, int aligned, size_t ks_floats,
+                    char* key, size_t key_len, int* grid, int* block, int* ksplit, int* level0);
 /* nn.ConvTranspose2d(Cin, Cout, 2, stride=2) with raw [Cin,Cout,2,2] weights
  * (RawFomer_WFB_FFAB/model.py:461).  [B,Cin,h,w] -> [B,Cout,2h,2w] */
 int rf_convT2x2_scratch_bytes(int Cin, int Cout, size_t* bytes);

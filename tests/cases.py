@@ -356,7 +356,64 @@ def conv1x1_case(tag):
     return t, run
 
 
-# ---- FFT lines: test_fft_lines.py.  tag -> ((planes, h, w), the regime the case is there for, as rf_fft_plan states it:
+# ---- 3x3 convolution selection: tools/make_conv3x3_keys.py records, test_conv3x3_plan.py compares.
+# tag -> (B, Cin, Cout, h, w, store), through ops.conv3x3 with bias and LeakyReLU.  Derived from the ladder of plan_conv3x3
+# (rf_conv3x3.hip), in its order, at the smallest frame that reaches each instantiation <NCO, LOG2_RW, RPW, NWV>.  NT = ceil(Cout / 16)
+# output tiles; NCO = 4, or at NT % 4 != 0: 3 at NT % 3 == 0, else 2 at an even NT, else 1 at NT == 1, else 4.
+#   small       w > 32, h >= 8 and fewer than 128 workgroups of the wide form: <N, 0, 1, 4>, NCO halved (3 -> 1) while 4 x 64 tiles x
+#               groups < 192.  NCO stays 4 / 3 / 2 only on one tall frame (192 tiles of 4 rows, under 128 of 8 or 16)
+#   <1,0,1,16>  NCO 1, w > 32, h >= 16; 128 workgroups = 8 frames of 16 tiles.  Level-0 form (", false, 3") at Cin <= 32, w % 4 == 0
+#   <2,0,2,8>   NCO 2, w > 32, h >= 16; its level-0 form likewise.  <N,0,1,8>: NCO 3 / 4 at h >= 8, NCO 1 / 2 at 8 <= h < 16 (128 frames
+#               of one workgroup: the small rule counts 16-row tiles for them)
+#   <N,L,1,4>   the rest: w > 32 and h < 8 (L = 0), 16 < w <= 32 (L = 1), w <= 16 (L = 2)
+# The input-channel split needs scratch that ops.conv3x3 does not pass: CONV3X3_SPLIT_STAGES pins it through forward_stage.
+CONV3X3_CASES = {
+    "small_n4_tall": (1, 8, 64, 768, 64, "plain"),
+    "small_n3_tall": (1, 12, 48, 766, 64, "unshuffle"),
+    "small_n2_tall": (1, 8, 32, 768, 62, "plain"),                # w % 4 != 0: scalar stores
+    "small_n4_to_n2": (1, 8, 64, 400, 64, "shuffle"),
+    "small_n4_to_n1": (1, 20, 64, 16, 64, "plain"),
+    "small_n3_to_n1": (1, 8, 48, 30, 70, "unshuffle"),            # ragged last tile in both directions
+    "small_n1": (1, 8, 16, 8, 33, "plain"),
+    "w16_n1": (8, 40, 16, 256, 64, "plain"),                      # exactly 128 workgroups
+    "w16_n1_ragged": (8, 44, 12, 250, 38, "shuffle"),             # Cin ends inside a chunk, w % 4 != 0
+    "w16_n1_l0": (8, 32, 16, 256, 64, "plain"),
+    "w16_n1_l0_ragged": (8, 20, 12, 250, 36, "unshuffle"),
+    "rpw2_n2": (8, 40, 32, 256, 64, "plain"),
+    "rpw2_n2_ragged": (8, 36, 32, 242, 34, "unshuffle"),
+    "rpw2_n2_l0": (8, 32, 32, 256, 64, "shuffle"),
+    "rpw2_n2_l0_ragged": (8, 20, 32, 250, 36, "plain"),
+    "wide8_n4": (16, 8, 64, 64, 64, "plain"),                     # exactly 128 workgroups
+    "wide8_n4_two_tiles": (4, 12, 64, 200, 200, "unshuffle"),     # 400 tiles on 200 workgroups: the persistent loop, ragged both ways
+    "wide8_n4_nt5": (16, 8, 80, 60, 62, "shuffle"),               # two groups, the second with one live tile of four
+    "wide8_n3": (16, 12, 48, 60, 62, "plain"),
+    "wide8_n1": (128, 8, 12, 9, 34, "plain"),
+    "wide8_n2": (128, 8, 32, 12, 36, "unshuffle"),
+    **{f"rw0_n{n}": (1, 8, 16 * n, 7, 66, "plain") for n in (1, 2, 3, 4)},
+    "rw1_n1": (2, 20, 16, 9, 21, "plain"), "rw1_n2": (2, 20, 32, 9, 32, "plain"),
+    "rw1_n3": (2, 20, 48, 10, 22, "unshuffle"), "rw1_n4": (2, 20, 64, 9, 24, "shuffle"),
+    "rw2_n1": (2, 20, 16, 17, 13, "plain"), "rw2_n2": (2, 20, 32, 17, 16, "plain"),
+    "rw2_n3": (2, 20, 48, 17, 15, "shuffle"), "rw2_n4": (2, 20, 64, 33, 9, "plain"),
+    "rw2_n4_unshuffle": (1, 8, 60, 18, 16, "unshuffle"),
+}
+# LAUNCH_CASES whose level-3 convolutions (128 / 256 channels on one 4 x 4 frame) run with their input channels split,
+# <4, 2, 1, 4, true>, which forward_launches.json records under the key of the unsplit kernel
+CONV3X3_SPLIT_STAGES = ("plain_d16_stage4", "flca_d32_stage4")
+
+
+def conv3x3_case(tag):
+    """Inputs of CONV3X3_CASES[tag] (ranges and weight scaling of test_conv3x3_level0.inputs) and ``run(ops, device)``, the case's
+    one call."""
+    b, cin, cout, h, w, store = CONV3X3_CASES[tag]
+    t = {"x": rnd(f"c3l0.x.{tag}", (b, cin, h, w)), "w": rnd(f"c3l0.w.{tag}", (cout, cin, 3, 3)) / np.sqrt(cin * 9 / 3),
+         "bias": rnd(f"c3l0.b.{tag}", (cout,))}
+
+    def run(ops, device):
+        return ops.conv3x3(t["x"].to(device), t["w"].to(device), t["bias"].to(device), act="lrelu", store=store)
+    return t, run
+
+
+# ---- FFT lines: test_fft_lines.py. tag -> ((planes, h, w), the regime the case is there for, as rf_fft_plan states it:
 # log2 w / log2 h (-1: direct DFT), L rows per row workgroup, TC columns per column workgroup, most trips of a row / of a column
 # workgroup through its persistent loop).  The shapes follow the plan's constants (rf_fft.hip, plan_fft: a line budget of 2048 values
 # per workgroup, TC <= 16, grids capped at 4096, lines <= 4096, direct lines <= 2048); if those change, these change with them.

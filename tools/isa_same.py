@@ -2,7 +2,7 @@
 """Is the gfx950 code of one source the same as at an earlier revision?  The gate of a kernel refactor: identical instruction
 streams have identical results and identical speed.  Needs hipcc and git, no GPU.
 
-    isa_same.py <rev> <path.hip> [--kernel NAME ...] [--was <old path.hip> [--was-kernel NAME ...]] [-DFOO ...]
+    isa_same.py <rev> <path.hip> [--kernel NAME ...] [--except NAME ...] [--was <old path.hip> [--was-kernel NAME ...]] [-DFOO ...]
 
 Compiles `git show <rev>:<path>` (next to that revision's headers) and the working-tree file with build.FLAGS to device assembly,
 drops the per-translation-unit __hip_cuid_* symbol and the source file name, and exits non-zero at the first difference.
@@ -10,18 +10,22 @@ With --kernel (repeatable) only the kernels whose mangled name contains NAME are
 their .amdhsa_kernel descriptors -- which is the question when a kernel has moved OUT of the file: did the ones that stayed change?
 For the kernel that moved, --was names the file it had at <rev> (and --was-kernel the name it had there, if that changed too); the
 kernels' own symbol names are then left out of the comparison.
+With --except (repeatable) every kernel of the working-tree file whose mangled name does NOT contain NAME is compared, each on its
+own and in name order: for a file that dropped a kernel or instantiates its kernels in another order.
 """
 import os, re, subprocess, sys, tempfile
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 from bayer_low_light_image_enhancement_amd import build as B  # noqa: E402
 
-rev, path, flags, kernels, was, was_kernels = sys.argv[1], os.path.relpath(os.path.abspath(sys.argv[2]), REPO), [], [], None, []
+rev, path, flags, kernels, was, was_kernels, excepted = sys.argv[1], os.path.relpath(os.path.abspath(sys.argv[2]), REPO), [], [], None, [], []
 rest = sys.argv[3:]
 while rest:
     a = rest.pop(0)
     if a == "--kernel":
         kernels.append(rest.pop(0))
+    elif a == "--except":
+        excepted.append(rest.pop(0))
     elif a == "--was":
         was = os.path.relpath(os.path.abspath(rest.pop(0)), REPO)
     elif a == "--was-kernel":
@@ -60,6 +64,12 @@ def listing(src, kernels):
     if r.returncode:
         sys.exit(r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if "__hip_cuid_" not in ln and not ln.lstrip().startswith(".file")]
+    if excepted:      # every other kernel of the working-tree file (compiled second: `kernels` is filled by then), one at a time
+        every = sorted(m.group(1) for ln in lines if (m := re.match(r"^\s*\.amdhsa_kernel\s+(\w+)", ln)))
+        if not kernels:
+            kernels.extend(k for k in every if not any(e in k for e in excepted))
+        print(f"{src}: {len(kernels)} of {len(every)} kernel(s)")
+        return [ln for k in kernels for ln in only_kernels(lines, [k])[0]]
     if kernels:
         lines, names = only_kernels(lines, kernels)
         if not names:
@@ -74,8 +84,9 @@ with tempfile.TemporaryDirectory(prefix="isa_same_") as tmp:
         os.makedirs(os.path.dirname(os.path.join(tmp, f)), exist_ok=True)
         with open(os.path.join(tmp, f), "wb") as out:
             out.write(subprocess.check_output(["git", "show", f"{rev}:{f}"], cwd=REPO))
-    old, new = listing(os.path.join(tmp, was or path), was_kernels or kernels), listing(os.path.join(REPO, path), kernels)
-what = f"{path} {' '.join(flags)}".strip() + (f" [{', '.join(kernels)}]" if kernels else "")
+    new = listing(os.path.join(REPO, path), kernels)
+    old = listing(os.path.join(tmp, was or path), was_kernels or kernels)
+what = f"{path} {' '.join(flags)}".strip() + (f" [all but {', '.join(excepted)}]" if excepted else f" [{', '.join(kernels)}]" if kernels else "")
 i = next((i for i, (a, b) in enumerate(zip(old, new)) if a != b), min(len(old), len(new)))
 if i == len(old) == len(new):
     print(f"identical: {what}: {len(new)} lines of gfx950 assembly, {rev} and the working tree")
