@@ -66,6 +66,11 @@ SIGNATURES = {
     "rf_grad_range": (_i, [_vp, _i, _psz, _psz]),
     "rf_train_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _f, _vp]),
     "rf_adam_step": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _i, _i, _f, _vp]),
+    "rf_optim_state_bytes": (_i, [_i, _sz, _psz]),
+    "rf_optim_init": (_i, [_psz, _psz, _i, _sz, _vp, _sz, _vp]),
+    "rf_grad_stats": (_i, [_vp, _sz, _i, _vp, _sz, _vp]),
+    "rf_adam_step_guarded": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _i, _f, _f, _i, _i, _vp, _sz, _vp]),
+    "rf_optim_set_steps": (_i, [_vp, _sz, C.c_longlong, _vp]),
     "rf_pixel_unshuffle2": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "rf_pixel_shuffle2": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "rf_dwt_haar": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
@@ -167,6 +172,13 @@ SIGNATURES = {
     "rf_ml_step_fused": (_i, [_vp, _vp, _vp, _i, _i] + [_vp] * 10 + [_i, _i, _i, _i, _vp]),
     "rf_ml_residual": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
 }
+
+# rf_optim_control and rf_optim_segment (include/rawformer_hip.h) as numpy record types, for reading the guarded step's device state
+OPTIM_CONTROL = [("grad_norm", "<f8"), ("grad_sumsq", "<f8"), ("clip_coef", "<f8"), ("nonfinite", "<i8"), ("steps_applied", "<i8"),
+                 ("steps_skipped", "<i8"), ("bias_corr1", "<f4"), ("bias_corr2", "<f4"), ("grad_mul", "<f4"), ("skip", "<i4"),
+                 ("n", "<i8"), ("nseg", "<i4"), ("nchunks", "<i4")]
+OPTIM_CONTROL_BYTES = 80
+OPTIM_SEGMENT = [("sumsq", "<f8"), ("nonfinite", "<i8")]
 
 _lib = None
 

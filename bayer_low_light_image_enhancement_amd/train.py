@@ -9,6 +9,8 @@ the default evaluates the criterion on the raw prediction) with torch.autograd r
 (train.py:108-111) by one process per GPU: every rank runs its own images, the flat gradient buffer is all-reduced in
 fixed-size buckets (RCCL with the ``nccl`` backend, ``gloo`` in the CPU tests), then ``rf_adam_step`` updates the flat
 parameter buffer.  PyTorch provides device memory, streams and the collective; no torch op computes anything.
+``Trainer(max_grad_norm=..., skip_nonfinite=True)`` replaces that last call by the guarded step (``rf_grad_stats`` +
+``rf_adam_step_guarded``): the reference's ``GradScaler.step`` / ``clip_grad_norm_`` pair, decided on the device.
 
 Around the step, ``fit`` is the reference's epoch loop (train.py:113-175): ``warmup_cosine_lr`` restates the learning rate its
 ``GradualWarmupScheduler`` + ``CosineAnnealingLR`` pair leaves in the optimiser, batches come from a device-resident set
@@ -92,11 +94,23 @@ class OverlappedReducer:
 
 
 class Trainer:
-    """Owns the flat parameter / gradient / moment buffers of a ``RawFormer`` and runs training steps on them."""
+    """Owns the flat parameter / gradient / moment buffers of a ``RawFormer`` and runs training steps on them.
+
+    ``max_grad_norm`` and ``skip_nonfinite`` switch on the GUARDED optimiser step (``rf_grad_stats`` +
+    ``rf_adam_step_guarded``), the reference loops' ``GradScaler.step`` (training.py:233,251-253: no step is applied when a
+    gradient holds an inf or a NaN) and ``torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm)``.  Norm, clip coefficient,
+    the decision to skip and the step count behind Adam's bias corrections are computed and kept ON THE DEVICE: a guarded
+    ``step`` reads nothing back and copies nothing to the device.  A skipped step leaves parameters and moments bit for bit as
+    they were and does not count as a step.  Clipping is applied on the way into the update: ``grads`` / ``grad_of`` keep the
+    unclipped gradient.  The decision is taken on the ALL-REDUCED buffer, which every rank holds bit for bit the same (one
+    collective result, the same kernels in the same fixed summation order), with ``grad_scale = 1 / world``: the ranks decide
+    alike and their weights cannot drift apart.  With both arguments left at their defaults ``optimizer_step`` is the plain
+    ``rf_adam_step`` and ``step_no`` a host integer."""
 
     def __init__(self, model: RawFormer, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  decoupled: bool = False, loss: str = "l1", charbonnier_eps: float = 1e-3, group=None, overlap_allreduce: bool = True,
-                 bucket_floats: int = 1 << 20, clamp_pred: bool = False):
+                 bucket_floats: int = 1 << 20, clamp_pred: bool = False, max_grad_norm: Optional[float] = None,
+                 skip_nonfinite: bool = False):
         if model.variant not in ("plain", "flca"):
             raise RuntimeError(f"Trainer: the adjoint schedule exists for variants 'plain' and 'flca', not {model.variant!r}")
         dev = next(model.parameters()).device
@@ -123,7 +137,20 @@ class Trainer:
         self.grads = torch.zeros_like(self.flat)
         self.m = torch.zeros_like(self.flat)
         self.v = torch.zeros_like(self.flat)
-        self.step_no = 0
+        self._step_no = 0
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.guarded = self.max_grad_norm is not None or self.skip_nonfinite
+        if self.guarded:
+            # the registry's parameters as segments of the flat buffer (offsets 16-byte aligned, gaps of up to 3 floats that belong
+            # to no segment); tables and counters go to the device once, here
+            self._segments = sorted((off, cnt, k) for k, (off, cnt) in self.slices.items())
+            nseg = len(self._segments)
+            self.opt_state = torch.zeros(_lib.size("rf_optim_state_bytes", nseg, self.n), dtype=torch.uint8, device=dev)
+            as_size_t = _lib.C.c_size_t * nseg
+            _lib.launch("rf_optim_init", self.flat, as_size_t(*[s[0] for s in self._segments]), as_size_t(*[s[1] for s in self._segments]),
+                        nseg, self.n, self.opt_state, self.opt_state.numel())
+            self._grad_scale = 1.0
         self.workspace: Optional[torch.Tensor] = None
         self.loss_dev = torch.zeros(1, dtype=torch.float32, device=dev)
         # gradient all-reduce started range by range from inside rf_train_step (several ranks only)
@@ -179,10 +206,61 @@ class Trainer:
             self._reduced = False
         else:
             allreduce_flat(self.grads, self.group)
-        self.step_no += 1
-        _lib.launch("rf_adam_step", self.flat, self.flat, self.grads, self.m, self.v, self.n, self.lr, self.betas[0], self.betas[1], self.eps,
-                    self.wd, int(self.decoupled), self.step_no, 1.0 / world)
+        if self.guarded:
+            # statistics -> control -> Adam on the current stream, behind the all-reduce it has just been made to wait for
+            nseg, nbytes = len(self._segments), self.opt_state.numel()
+            self._grad_scale = 1.0 / world
+            _lib.launch("rf_grad_stats", self.flat, self.grads, self.n, nseg, self.opt_state, nbytes)
+            _lib.launch("rf_adam_step_guarded", self.flat, self.flat, self.grads, self.m, self.v, self.n, self.lr, self.betas[0], self.betas[1],
+                        self.eps, self.wd, int(self.decoupled), self._grad_scale, math.inf if self.max_grad_norm is None else self.max_grad_norm,
+                        int(self.skip_nonfinite), nseg, self.opt_state, nbytes)
+        else:
+            self._step_no += 1
+            _lib.launch("rf_adam_step", self.flat, self.flat, self.grads, self.m, self.v, self.n, self.lr, self.betas[0], self.betas[1], self.eps,
+                        self.wd, int(self.decoupled), self._step_no, 1.0 / world)
         self.model.invalidate_packed()          # the weights moved: packed copies are stale
+
+    @property
+    def step_no(self) -> int:
+        """Optimiser steps applied so far.  Default mode: a host integer.  Guarded mode: the device's ``steps_applied`` (skipped
+        steps do not count), read with one SYNCHRONISING copy.  Setting it (``load_optimizer_state_dict`` does) also sets the
+        device counter, on the current stream."""
+        return int(self._control()["steps_applied"]) if self.guarded else self._step_no
+
+    @step_no.setter
+    def step_no(self, value: int) -> None:
+        self._step_no = int(value)
+        if self.guarded:
+            _lib.launch("rf_optim_set_steps", self.flat, self.opt_state, self.opt_state.numel(), self._step_no)
+
+    def _control(self, raw: Optional[bytes] = None):
+        """``rf_optim_control`` as a numpy record; read from the device (synchronising) unless its bytes are given."""
+        if raw is None:
+            raw = self.opt_state[:_lib.OPTIM_CONTROL_BYTES].cpu().numpy().tobytes()
+        return np.frombuffer(raw, dtype=np.dtype(_lib.OPTIM_CONTROL))[0]
+
+    def _need_guarded(self, what: str) -> None:
+        if not self.guarded:
+            raise RuntimeError(f"{what}: this Trainer runs the plain optimiser step; pass max_grad_norm and / or skip_nonfinite=True")
+
+    def optimizer_stats(self, raw: Optional[bytes] = None) -> dict:
+        """Guarded mode: the counters and the last step's decision, read from the device with one SYNCHRONISING copy:
+        ``steps_applied``, ``steps_skipped``, ``grad_norm`` (float64 norm of the all-reduced gradient times 1 / world, before
+        clipping), ``clip_coef`` (``min(1, max_grad_norm / (grad_norm + 1e-6))``, 1 without clipping), ``nonfinite`` (inf / NaN
+        elements of the gradient)."""
+        self._need_guarded("optimizer_stats")
+        c = self._control(raw)
+        return {"steps_applied": int(c["steps_applied"]), "steps_skipped": int(c["steps_skipped"]), "grad_norm": float(c["grad_norm"]),
+                "clip_coef": float(c["clip_coef"]), "nonfinite": int(c["nonfinite"])}
+
+    def grad_norms(self) -> dict:
+        """Guarded mode: ``{parameter name: (norm, non-finite count)}`` of the last step's gradient, the per-parameter NaN monitor the
+        reference keeps commented out (RawFomer_WFB_FFAB/train.py:185-188).  Norms are float64, scaled like ``grad_norm``.  One
+        SYNCHRONISING copy."""
+        self._need_guarded("grad_norms")
+        lo, nseg = _lib.OPTIM_CONTROL_BYTES, len(self._segments)
+        seg = np.frombuffer(self.opt_state[lo: lo + 16 * nseg].cpu().numpy().tobytes(), dtype=np.dtype(_lib.OPTIM_SEGMENT))
+        return {k: (self._grad_scale * math.sqrt(float(seg[i]["sumsq"])), int(seg[i]["nonfinite"])) for i, (_, _, k) in enumerate(self._segments)}
 
     def step(self, x: torch.Tensor, gt: torch.Tensor, loss_out: Optional[torch.Tensor] = None) -> torch.Tensor:
         loss = self.forward_backward(x, gt, loss_out=loss_out)
@@ -279,7 +357,11 @@ def fit(trainer: Trainer, sampler, val_sampler, epochs: int, batch_size: int, ou
     ``{'epoch', 'state_dict', 'optimizer'}`` in ``out_dir`` on a new best PSNR (:165-172; host tensors) and one line of :175's
     format appended to ``out_dir/log_name``.  No progress bar, no image writing.  To resume, load a checkpoint's ``state_dict``
     into the model and its ``optimizer`` with ``Trainer.load_optimizer_state_dict``, then pass ``start_epoch = epoch + 1``.
-    Returns one dict per epoch: ``epoch``, ``lr``, ``loss``, ``psnr``, ``best_psnr``, ``best_epoch``."""
+    Returns one dict per epoch: ``epoch``, ``lr``, ``loss``, ``psnr``, ``best_psnr``, ``best_epoch``; with a guarded trainer
+    (``Trainer(max_grad_norm=..., skip_nonfinite=...)``) also ``skipped``, the steps of this epoch that were not applied, and
+    ``grad_norm``, the gradient norm of its last step -- the control block is read in the epoch's one host read.  The loss of a
+    skipped step still enters the epoch's sum, as in the reference, so one NaN batch makes that epoch's logged loss NaN while
+    the weights stay clean."""
     model = trainer.model
     os.makedirs(out_dir, exist_ok=True)
     base_lr = trainer.lr if base_lr is None else float(base_lr)
@@ -288,6 +370,7 @@ def fit(trainer: Trainer, sampler, val_sampler, epochs: int, batch_size: int, ou
     steps = (n + batch_size - 1) // batch_size
     losses = torch.zeros(steps, dtype=torch.float32, device=trainer.flat.device)
     best_psnr, best_epoch, history = 0, 0, []
+    skipped_before = trainer.optimizer_stats()["steps_skipped"] if trainer.guarded else 0      # one read before the first epoch
     with open(os.path.join(out_dir, log_name), "a") as log_f:
         for epoch in range(start_epoch, epochs + 1):
             start_time = time.time()
@@ -299,7 +382,14 @@ def fit(trainer: Trainer, sampler, val_sampler, epochs: int, batch_size: int, ou
                 x, gt = sampler.batch(order[k * batch_size: (k + 1) * batch_size])
                 trainer.step(x, gt, loss_out=losses[k: k + 1])
             epoch_loss = 0
-            for v in losses.cpu().tolist():          # the epoch's one host read; added in step order, as `+= loss.item()`
+            if trainer.guarded:                      # the control block rides along in the epoch's one host read
+                ctl_bytes = trainer.opt_state[:_lib.OPTIM_CONTROL_BYTES]
+                host = torch.cat([losses.view(torch.uint8), ctl_bytes]).cpu()
+                epoch_losses = host[:4 * steps].view(torch.float32).tolist()
+                stats = trainer.optimizer_stats(host[4 * steps:].numpy().tobytes())
+            else:
+                epoch_losses, stats = losses.cpu().tolist(), None
+            for v in epoch_losses:                   # the epoch's one host read; added in step order, as `+= loss.item()`
                 epoch_loss += v
             avg_psnr = validate(model, val_sampler)
             if avg_psnr > best_psnr:
@@ -310,4 +400,7 @@ def fit(trainer: Trainer, sampler, val_sampler, epochs: int, batch_size: int, ou
             log_f.write(f"Epoch {epoch}/{epochs} | Time: {epoch_time:.2f}s | Loss: {epoch_loss:.4f} | Avg PSNR: {avg_psnr:.4f} | Best PSNR: {best_psnr:.4f} (Epoch {best_epoch})\n")
             log_f.flush()
             history.append({"epoch": epoch, "lr": trainer.lr, "loss": epoch_loss, "psnr": avg_psnr, "best_psnr": best_psnr, "best_epoch": best_epoch})
+            if stats is not None:
+                history[-1].update(skipped=stats["steps_skipped"] - skipped_before, grad_norm=stats["grad_norm"])
+                skipped_before = stats["steps_skipped"]
     return history

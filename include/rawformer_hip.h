@@ -176,6 +176,67 @@ int rf_train_step(rf_handle* h, const float* in, const float* gt, float* grads, 
 int rf_adam_step(float* params, const float* grads, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
                  float weight_decay, int decoupled, int step, float grad_scale, void* stream);
 
+/* ---- guarded optimiser step (csrc/rf_optim.hip) ----
+ * What the reference's loops put around optimizer.step(): torch.cuda.amp.GradScaler.step, which applies NO step when a gradient
+ * holds an inf or a NaN (training.py:233,251-253; RawFomer_WFB_FFAB/train.py:139,183-190), and torch.nn.utils.clip_grad_norm_.
+ * Every decision is taken on the device: no entry point below reads device memory or waits for the stream (rf_optim_init waits
+ * once, for its own copy).  Handle-free; all memory comes from the caller.
+ *
+ * The gradient buffer is described by nseg SEGMENTS [offset_i, offset_i + count_i) of floats: ascending, disjoint, every offset
+ * a multiple of 4 floats (16 bytes) -- for a model, rf_flat_offset(i) and the element count of parameter i.  Floats between
+ * segments (alignment gaps) belong to no segment and are never read by the statistics.
+ *
+ * Device state, one caller-owned buffer of rf_optim_state_bytes(nseg, n) bytes, 16-byte aligned, set up once by rf_optim_init:
+ *   byte 0                              rf_optim_control (below)
+ *   byte 80                             rf_optim_segment[nseg]: the per-segment results of the last rf_grad_stats
+ *   behind them                         the segment -> chunk table, the chunk table and the chunk partials (private)
+ * Every later call takes the same nseg, n and state; a state buffer smaller than the query's answer is refused.
+ *
+ * rf_grad_stats: per segment and in total, the sum of g^2 and the number of non-finite elements (inf or NaN) of the RAW
+ *   buffer (no grad_scale).  Squares and sums are float64 (a float32 square is exact there: a finite gradient cannot overflow).
+ *   Each segment is cut into chunks of 4096 floats; a chunk is summed by one workgroup in a fixed order, a segment's chunks are
+ *   added in chunk order and the segments in a fixed order, whatever the grid: two runs give the same bits.  No float atomics.
+ *   Writes rf_optim_segment[], grad_sumsq and nonfinite.  grads is 16-byte aligned.
+ * rf_adam_step_guarded: called BEHIND rf_grad_stats on the same buffer and stream.  One workgroup writes the control block:
+ *     grad_norm = grad_scale sqrt(grad_sumsq)                        (float64; the norm of segment i is grad_scale sqrt(sumsq_i))
+ *     clip_coef = min(1, max_norm / (grad_norm + 1e-6))              (clip_grad_norm_'s formula; 1 with max_norm = +inf and for
+ *                                                                     a NaN norm)
+ *     skip      = skip_nonfinite && nonfinite > 0
+ *     skip: steps_skipped += 1;  else steps_applied += 1 and bias_corr{1,2} = 1 - beta{1,2}^steps_applied, computed in float64
+ *     and rounded to float32;  grad_mul = (float)(grad_scale clip_coef)
+ *   then rf_adam_step's arithmetic runs element for element with g[i] * grad_mul and the two bias corrections.  On skip nothing is
+ *   read or written in params, m and v (no decoupled weight decay either: GradScaler does not call optimizer.step()).  With
+ *   skip_nonfinite = 0 a non-finite gradient IS applied and the weights become non-finite, as with rf_adam_step.  grads is
+ *   const: clipping happens on the way into the update and the buffer keeps the unclipped gradient.
+ * rf_optim_set_steps: sets steps_applied on the stream (resume from a checkpoint); steps_skipped stays.
+ * Refusals come before any launch, -22 with an rf_last_error message: null buffers, nseg <= 0, a segment that passes n, starts
+ * off a 16-byte boundary or overlaps its predecessor, max_norm <= 0 or NaN, a state buffer that is too small or misaligned. */
+typedef struct rf_optim_control {
+    double grad_norm;            /*  0  grad_scale * sqrt(grad_sumsq), last rf_adam_step_guarded                   */
+    double grad_sumsq;           /*  8  sum of g^2 over all segments, last rf_grad_stats                           */
+    double clip_coef;            /* 16                                                                             */
+    long long nonfinite;         /* 24  inf / NaN elements over all segments, last rf_grad_stats                   */
+    long long steps_applied;     /* 32                                                                             */
+    long long steps_skipped;     /* 40                                                                             */
+    float bias_corr1, bias_corr2;/* 48, 52  1 - beta^steps_applied of the last applied step                        */
+    float grad_mul;              /* 56  what the update multiplies g[i] by                                         */
+    int skip;                    /* 60  the last step's decision                                                   */
+    long long n;                 /* 64  set by rf_optim_init, with the next two                                    */
+    int nseg, nchunks;           /* 72, 76                                                                         */
+} rf_optim_control;
+typedef struct rf_optim_segment {
+    double sumsq;                /* sum of g^2 over the segment  */
+    long long nonfinite;         /* its inf / NaN elements       */
+} rf_optim_segment;
+int rf_optim_state_bytes(int nseg, size_t n, size_t* bytes);
+/* offsets, counts: HOST arrays of nseg entries, in floats.  Zeroes the control block (both counters) and the results. */
+int rf_optim_init(const size_t* offsets, const size_t* counts, int nseg, size_t n, void* state, size_t state_bytes, void* stream);
+int rf_grad_stats(const float* grads, size_t n, int nseg, void* state, size_t state_bytes, void* stream);
+int rf_adam_step_guarded(float* params, const float* grads, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
+                         float weight_decay, int decoupled, float grad_scale, float max_norm, int skip_nonfinite, int nseg, void* state,
+                         size_t state_bytes, void* stream);
+int rf_optim_set_steps(void* state, size_t state_bytes, long long steps_applied, void* stream);
+
 /* ---- operators (parity-test surface) -----------------------------------------------------------
  * Each entry runs the kernels the forward uses for that operator at that shape.  Where the forward
  * fuses ACROSS operators the fused kernel belongs to the wider entry point: rf_chan_attn (no LayerNorm
