@@ -94,6 +94,8 @@ SIGNATURES = {
     "rf_chan_attn": (_i, [_vp] * 10 + [_i] * 5 + [_vp]),
     "rf_transformer_block_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _i, _psz]),
     "rf_transformer_block": (_i, [_vp, _vp, C.POINTER(_vp), _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "rf_transformer_block_window": (_i, [_vp, _vp, C.POINTER(_vp), _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "rf_attn_front_plan": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_longlong)]),
     "rf_flca_scratch_bytes": (_i, [_i, _i, _i, _i, _psz]),
     "rf_flca": (_i, [_vp, _vp, _vp, C.POINTER(_vp), _vp, _i, _i, _i, _i, _vp]),
     "rf_guidance_scratch_bytes": (_i, [_i, _i, _i, _psz]),

@@ -362,6 +362,16 @@ static void tb_scratch(int B, int C, int heads, int hc, int h, int w, TbScratch*
     s->total = b.used + transformer_scratch_floats(B, C, heads, hc, h, w, &s->o);
 }
 
+int rf_attn_front_plan(int B, int C, int heads, int h, int w, long long out[4]) {
+    RF_CHECK_ARG(out && B > 0 && heads > 0 && h > 0 && w > 0, "attn_front_plan: bad arguments");
+    RF_CHECK_ARG(fused_attn_supported(C, heads, h, w), "attn_front_plan: attn_front does not run at C=%d heads=%d %dx%d", C, heads, h, w);
+    int nslab = 0, tall = 0;
+    size_t pf = 0, reserve = 0;
+    RF_TRY(fused_attn_plan(h, w, &nslab, &pf, B, C, &tall, &reserve));
+    out[0] = tall; out[1] = nslab; out[2] = (long long)pf; out[3] = (long long)reserve;
+    return RF_OK;
+}
+
 int rf_transformer_block_scratch_bytes(int B, int C, int heads, int ffn_expansion, int h, int w, size_t* bytes) {
     RF_CHECK_ARG(bytes && B > 0 && C > 0 && heads > 0 && C % heads == 0 && ffn_expansion > 0 && h > 0 && w > 0, "transformer_block_scratch_bytes: bad arguments");
     { int ns, sl; size_t pf; RF_TRY(gram_plan(B, C, heads, h * w, &ns, &sl, &pf)); }
@@ -373,7 +383,15 @@ int rf_transformer_block_scratch_bytes(int B, int C, int heads, int ffn_expansio
 
 int rf_transformer_block(const float* in, float* out, const float* const* prm, void* scratch,
                          int B, int C, int heads, int ffn_expansion, int h, int w, void* stream) {
+    return rf_transformer_block_window(in, out, prm, scratch, B, C, heads, ffn_expansion, h, w, 0, 0, 0, 0, stream);
+}
+
+int rf_transformer_block_window(const float* in, float* out, const float* const* prm, void* scratch,
+                                int B, int C, int heads, int ffn_expansion, int h, int w, int y_lo, int y_hi, int x_lo, int x_hi, void* stream) {
     RF_CHECK_ARG(in && out && prm && scratch && aligned16(scratch), "transformer_block: bad arguments");
+    RF_CHECK_ARG((y_hi == 0 && y_lo == 0) || (0 <= y_lo && y_lo < y_hi && y_hi <= h), "transformer_block: interior rows [%d, %d) of %d", y_lo, y_hi, h);
+    RF_CHECK_ARG((x_hi == 0 && x_lo == 0) || (y_hi > 0 && 0 <= x_lo && x_lo < x_hi && x_hi <= w && x_lo % 4 == 0 && (x_hi % 4 == 0 || x_hi == w)),
+                 "transformer_block: interior columns [%d, %d) of %d: whole groups of 4, and interior rows with them", x_lo, x_hi, w);
     RF_CHECK_ARG(B > 0 && C % 4 == 0 && heads > 0 && C % heads == 0 && C / heads <= 64, "transformer_block: unsupported C=%d heads=%d", C, heads);
     for (int i = 0; i < 17; ++i) RF_CHECK_ARG(prm[i] != nullptr, "transformer_block: parameter %d is null", i);
     hipStream_t st = (hipStream_t)stream;
@@ -397,6 +415,7 @@ int rf_transformer_block(const float* in, float* out, const float* const* prm, v
     RF_TRY(pack_1x1_b3(qkv_w, ws + s.wqkv3, 3 * C, C, C, 1, st));
     RF_TRY(pack_1x1_b3(pw1_w, ws + s.w13, hc, C, C, 1, st));
     RF_TRY(pack_1x1_b3(pw2_w, ws + s.w23, C, hc, hc, 1, st));
+    p.ylo = y_lo; p.yhi = y_hi; p.xlo = x_lo; p.xhi = x_hi;
     return run_transformer(p, in, out, ws + s.bufs, s.o, B, C, heads, hc, h, w, st);
 }
 

@@ -16,7 +16,7 @@ size_t transformer_scratch_floats(int B, int C, int heads, int hc, int h, int w,
     int ns, sl;
     size_t pf = 0, pf2 = 0;
     if (gram_plan(B, C, heads, (int)P, &ns, &sl, &pf)) return 0;   // unsupported head layout: rf_last_error() says why
-    if (fused_attn_supported(C, heads, h, w)) fused_attn_plan(h, w, &ns, &pf2, B, C);
+    if (fused_attn_supported(C, heads, h, w)) { size_t used; fused_attn_plan(h, w, &ns, &used, B, C, nullptr, &pf2); }
     if (attn_mid_supported(C, heads, h, w)) attn_mid_plan(h, w, &ns, &pf2, B, C);
     o->partial = b.off(pf > pf2 ? pf : pf2);
     o->wfold = b.off((size_t)B * packed1x1_floats(C, C));

@@ -386,8 +386,12 @@ struct AttnFrontArgs {     // LN1 -> qkv 1x1 -> depthwise 3x3 -> Gram partials o
     int xlo, xhi;          // ... and columns [xlo, xhi) of them, both multiples of 4 or xhi = w: whole 4-pixel groups; xhi = 0: all
 };
 bool fused_attn_supported(int C, int heads, int h, int w);
-int fused_attn_plan(int h, int w, int* nslab, size_t* partial_floats, int B, int C);
+// The one statement of the launch geometry, from (h, w) alone: the workgroups per image (= partials), the floats of partials they
+// write, in *tall_form whether the eight-wave kernel on 12-row tiles runs (above 256 x 256 packed) or the 4-row kernel, and in
+// *reserve_floats what a scratch layout sets aside for the partial buffer (>= *partial_floats; the same for either form).
+int fused_attn_plan(int h, int w, int* nslab, size_t* partial_floats, int B, int C, int* tall_form = nullptr, size_t* reserve_floats = nullptr);
 int launch_attn_front(AttnFrontArgs a, int C, hipStream_t st);
+int launch_attn_front_tall32(const AttnFrontArgs& a, dim3 grid, hipStream_t st);      // rf_attn_front_tall.hip; called by launch_attn_front
 
 struct AttnMidArgs {       // qkv [B,3C,h,w] -> depthwise 3x3 -> Gram partials of (q, k) + v, for C = 64 / 128
     const float* qkv;      // [B][3C][h][w]

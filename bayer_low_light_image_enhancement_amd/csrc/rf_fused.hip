@@ -5,7 +5,8 @@
 // phase_a_step_b3 and tile_range; all four share stencil4, and ffn_fused8_kernel and attn_front_kernel tile_origin.  Every helper is __forceinline__, and tools/isa_same.py shows whether an edit to one
 // of them left the compiled code alone.  The helpers and ffn_fused_kernel live in rf_fused_tile.h: rf_fused_tail.hip builds the
 // second instantiation, ffn_fused_kernel<32, true>, which a whole-model stage uses at level 0 -- the FFN with the stage's
-// channel_reduce on top (FfnTail, rf_common.h), launched from here by launch_ffn_fused.
+// channel_reduce on top (FfnTail, rf_common.h), launched from here by launch_ffn_fused.  rf_attn_front_tall.hip builds
+// attn_front_tall_kernel<32>, attn_front on tiles of 12 rows and eight waves, which launch_attn_front takes above 256 x 256.
 //
 // Un-fused, one TransformerBlock moves ~26 C floats per pixel through HBM (qkv 1x1: C in / 3C out,
 // depthwise 3x3: 3C/3C, Gram: 2C, ...; ffn: C/2C, 2C/2C, 2C+C/C).  Here the wide intermediates
@@ -410,9 +411,29 @@ __global__ void __launch_bounds__(256, 2) attn_front_kernel(AttnFrontArgs a) {
 static bool attn_front_shape_ok(int C, int h, int w) { return C == 32 && (w % 4 == 0) && ((double)C * h * w * 4.0 < 4.0e9); }
 bool fused_attn_supported(int C, int heads, int h, int w) { return heads_fit_tiles(C, heads) && attn_front_shape_ok(C, h, w); }
 
-int fused_attn_plan(int h, int w, int* nslab, size_t* partial_floats, int B, int C) {
+// Which form runs, from (h, w) alone -- never from B: an image's reduction order is batch-invariant.  The 12-row kernel on eight
+// waves (rf_attn_front_tall.hip) takes over where the 4-row plan puts several tiles into a workgroup, i.e. above 256 x 256 packed,
+// with TWO tall tiles (1536 px), consecutive down a column, per workgroup.  Measured on MI355X (DESIGN sections 5 and 7; ms per
+// step of the whole forward on one box, the 4-row kernel at 7.67 - 7.71 for 8 images of 512 x 512 and 1.710 - 1.714 for one):
+// one tile 7.58 | 1.71 - 1.73, two 7.52 - 7.53 | 1.692 - 1.694, three 7.50 - 7.52 | 1.693 - 1.700, four 7.53 - 7.54 | 1.74.  A
+// workgroup pays its start, the 18 KB of weights and the reduction once, with no second workgroup on the CU to hide them, so one
+// tile is too few; from four on a single frame leaves CUs idle (344 tiles: 86 workgroups).  Unequal shares (one or two tiles:
+// the 4-row plan's workgroup count) lost to every equal split: 7.75.
+static int attn_front_tall_slabs(int h, int w) {      // workgroups per image; 0: the 4-row kernel
+    const int ntall = cdiv(w, fused::TW) * cdiv(h, fused::TH_TALL);
+    if (cdiv(w, fused::TW) * cdiv(h, fused::TH) <= 256) return 0;
+    int per = 2;
+#ifdef RF_DIAG   // diagnostic build only: RF_ATTN_TALL=0 keeps the 4-row kernel everywhere, =T gives a workgroup T tall tiles
+    if (const char* e = getenv("RF_ATTN_TALL")) per = atoi(e);
+    if (per <= 0) return 0;
+#endif
+    return cdiv(ntall, per);
+}
+
+int fused_attn_plan(int h, int w, int* nslab, size_t* partial_floats, int B, int C, int* tall_form, size_t* reserve_floats) {
     const int ntiles = cdiv(w, fused::TW) * cdiv(h, fused::TH);
-    int ns = cdiv(ntiles, 4);                   // 4 tiles (1024 px) per workgroup: ONE 1024x1024 frame gives the chip 256 workgroups
+    int ns = cdiv(ntiles, 4);                   // the 4-row kernel above 256 tiles (now the diagnostic build's RF_ATTN_TALL=0 only):
+                                                // 4 tiles (1024 px) per workgroup: ONE 1024x1024 frame gives the chip 256 workgroups
                                                 // (8 tiles: 131 us per launch for one frame, 4 tiles: 75 us; a batch of 8 pays
                                                 // 0.6 %); depends on the image only, never on B: an image's reduction order is
                                                 // batch-invariant
@@ -420,8 +441,14 @@ int fused_attn_plan(int h, int w, int* nslab, size_t* partial_floats, int B, int
                                                 // chain of ~15 us each: 62 -> 25 us per launch for one 128 x 128 frame)
                                                 // (two tiles per workgroup at 512 x 512: -17 % for one frame, +11 % for a batch of 8)
     if (ns < 1) ns = 1;
+    const int ns4 = ns, tall = attn_front_tall_slabs(h, w);
+    if (tall) ns = tall;
     *nslab = ns;
     *partial_floats = (size_t)B * ns * (C / 16) * 16 * 66;
+    if (tall_form) *tall_form = tall > 0;
+    // what the scratch layouts set aside: the larger of the two forms' buffers, i.e. what the 4-row plan always took (the tall form
+    // writes fewer partials), so no scratch or workspace size moves with the form
+    if (reserve_floats) *reserve_floats = (size_t)B * (ns > ns4 ? ns : ns4) * (C / 16) * 16 * 66;
     return RF_OK;
 }
 
@@ -429,13 +456,18 @@ int launch_attn_front(AttnFrontArgs a, int C, hipStream_t st) {
     const int B = a.B, h = a.h, w = a.w;
     RF_CHECK_ARG(attn_front_shape_ok(C, h, w) && B <= 65535, "attn_front: unsupported shape C=%d %dx%d", C, h, w);
     RF_CHECK_ARG(aligned16(a.x) && aligned16(a.v), "attn_front: buffers must be 16-byte aligned");
+    int nslab = 0, tall = 0;
+    size_t pf = 0;
+    fused_attn_plan(h, w, &nslab, &pf, B, C, &tall);
+    RF_CHECK_ARG(a.nslab == nslab, "attn_front: %d slabs, the plan for %dx%d has %d", a.nslab, h, w, nslab);
     a.tiles_x = cdiv(w, fused::TW);
-    a.ntiles = a.tiles_x * cdiv(h, fused::TH);
+    a.ntiles = a.tiles_x * cdiv(h, tall ? fused::TH_TALL : fused::TH);
     if (!(a.yhi > 0 && a.yhi < h)) a.yhi = h;
     if (!(a.xhi > 0 && a.xhi < w)) a.xhi = w;
     const double px = (double)B * h * w;
     ProfScope prof(st, "attn_front_kernel<32>", px * (6.0 * C * C + 54.0 * C + 4.0 * C * 16), px * 8.0 * C);
     const dim3 grid((unsigned)a.nslab, (unsigned)B);
+    if (tall) return launch_attn_front_tall32(a, grid, st);
     attn_front_kernel<32><<<grid, 256, 0, st>>>(a);
     return check_launch("attn_front");
 }

@@ -46,19 +46,25 @@ constexpr int PART = 32;                // intermediate channels per part
 // groups are conflict-free iff (PSG j + 4 kq) mod 64 are 16 distinct multiples of 4: PSG = 8 mod 64.  (452 = 4 mod 64 made
 // lanes (j, 1) and (j + 1, 0) collide: SQ_LDS_BANK_CONFLICT was 55 % of the LDS-active cycles of attn_front.)
 constexpr int PSG = 456;
+// The tall attention tile (rf_attn_front_tall.hip): 12 output rows on eight waves, 14 halo'd rows x 18 groups = 252 groups as two
+// MFMA steps per wave (8 x 32 = 256 slots).  Plane strides: 14 x 72 = 1008 floats, padded to 8 mod 64 for the Gram rounds (see PSG)
+// and to a multiple of 64 for the v parts.
+constexpr int TH_TALL = 12, HR_TALL = TH_TALL + 2, GPW_TALL = 32;
+constexpr int PSG_TALL = 1032, PSV_TALL = 1024;
 }  // namespace fused
 
 // ---- shared phase-A machinery ------------------------------------------------------------------
 // A wave's share of the halo'd pixel groups, G of them in steps of 16 (G <= 16: step 0 only; the last wave's share may then run
-// past the tile): geometry of step st for lane j.
+// past the tile): geometry of step st for lane j.  ROWS = halo'd rows of the tile (fused::HR; the tall attention tile: 14).
 struct GroupGeom {
     int lds_off;     // row * HC + 4 * cg
     int goff;        // y * w + x  (clamped to 0 when outside)
     bool valid;
 };
-template <int G>
+template <int G, int ROWS = fused::HR>
 __device__ __forceinline__ GroupGeom group_geom(int wave, int st, int j, int y0, int x0, int h, int w) {
     using namespace fused;
+    constexpr int NG = ROWS * (HC / 4);
     GroupGeom g;
     const int gi = wave * G + st * 16 + j;
     const bool in_step = j < G - st * 16 && (NG % G == 0 || gi < NG);
@@ -81,9 +87,10 @@ __device__ __forceinline__ TileRange tile_range(int ntiles, int tiles_x, int nwg
     const int begin = wg * per, end = (begin + per < ntiles) ? begin + per : ntiles;
     return {tiles_y, begin, end};
 }
+template <int ROWS = fused::TH>                                           // output rows of a tile
 __device__ __forceinline__ int2 tile_origin(int tile, int tiles_y) {      // (x0, y0) of a tile
     const int tx = tile / tiles_y, ty = tile % tiles_y;
-    return make_int2(tx * fused::TW, ty * fused::TH);
+    return make_int2(tx * fused::TW, ty * ROWS);
 }
 
 // ---- phase-A helpers in b3 form (rf_common.h): lane (j, kq) holds channels 32 kb + 8 kq + i, i = 0..7 ------------------------
@@ -198,34 +205,56 @@ __device__ __forceinline__ float dpp_row_shl1(float keep, float v) {   // lane i
 }
 
 enum class Edge { Dpp, Wide };
+// the six taps of one row: the pixel left of the four, the four, the pixel right of them
+template <Edge E>
+__device__ __forceinline__ void row_taps(const float* __restrict__ row, int j, float (&v)[6]) {
+    float4 m;
+    float vl, vr;                                    // the taps left and right of m
+    if constexpr (E == Edge::Dpp) {
+        m = *reinterpret_cast<const float4*>(row);
+        float el = 0.f, er = 0.f;
+        if (j == 0) el = row[-1];
+        if (j == 15) er = row[4];
+        vl = dpp_row_shr1(el, m.w);
+        vr = dpp_row_shl1(er, m.x);
+    } else {
+        const float4 lft = *reinterpret_cast<const float4*>(row - 4);
+        m = *reinterpret_cast<const float4*>(row);
+        const float4 rgt = *reinterpret_cast<const float4*>(row + 4);
+        vl = lft.w;
+        vr = rgt.x;
+    }
+    v[0] = vl; v[1] = m.x; v[2] = m.y; v[3] = m.z; v[4] = m.w; v[5] = vr;
+}
 template <Edge E>
 __device__ __forceinline__ void stencil4(const float* __restrict__ p, const int (&ro)[3], int j, const float* __restrict__ k9, float bias, float (&out)[4]) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) out[q] = bias;
 #pragma unroll
     for (int dy = 0; dy < 3; ++dy) {
-        const float* row = p + ro[dy];
-        float4 m;
-        float vl, vr;                                    // the taps left and right of m
-        if constexpr (E == Edge::Dpp) {
-            m = *reinterpret_cast<const float4*>(row);
-            float el = 0.f, er = 0.f;
-            if (j == 0) el = row[-1];
-            if (j == 15) er = row[4];
-            vl = dpp_row_shr1(el, m.w);
-            vr = dpp_row_shl1(er, m.x);
-        } else {
-            const float4 lft = *reinterpret_cast<const float4*>(row - 4);
-            m = *reinterpret_cast<const float4*>(row);
-            const float4 rgt = *reinterpret_cast<const float4*>(row + 4);
-            vl = lft.w;
-            vr = rgt.x;
-        }
-        const float v[6] = {vl, m.x, m.y, m.z, m.w, vr};
+        float v[6];
+        row_taps<E>(p + ro[dy], j, v);
         const float k0 = k9[dy * 3], k1 = k9[dy * 3 + 1], k2 = k9[dy * 3 + 2];
 #pragma unroll
         for (int q = 0; q < 4; ++q) out[q] = fmaf(k2, v[q + 2], fmaf(k1, v[q + 1], fmaf(k0, v[q], out[q])));
     }
+}
+
+// The same stencil down a strip of consecutive rows, each input row read ONCE: input row i feeds output rows i - 2, i - 1 and i
+// (numbered by their first input row) with kernel rows 2, 1 and 0.  acc[0] is the output row that this input row completes,
+// acc[1] and acc[2] the two still open; the caller consumes acc[0] (from the third input row on) and calls roll_shift.  Every
+// output is the fmaf chain of stencil4 in stencil4's order -- bias, kernel row 0, 1, 2 -- so the values are the same bit for bit.
+__device__ __forceinline__ void roll_row(const float (&v)[6], const float (&k)[9], float bias, float (&acc)[3][4]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        acc[0][q] = fmaf(k[8], v[q + 2], fmaf(k[7], v[q + 1], fmaf(k[6], v[q], acc[0][q])));
+        acc[1][q] = fmaf(k[5], v[q + 2], fmaf(k[4], v[q + 1], fmaf(k[3], v[q], acc[1][q])));
+        acc[2][q] = fmaf(k[2], v[q + 2], fmaf(k[1], v[q + 1], fmaf(k[0], v[q], bias)));
+    }
+}
+__device__ __forceinline__ void roll_shift(float (&acc)[3][4]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { acc[0][q] = acc[1][q]; acc[1][q] = acc[2][q]; }
 }
 
 // ================================================================================================

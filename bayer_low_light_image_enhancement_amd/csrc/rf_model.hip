@@ -66,8 +66,8 @@ int make_plan(const rf_handle* h, int B, int H, int W, Plan& p) {
         if (rc) return rc;
         if (pf > gp) gp = pf;
         if (fused_attn_supported(C, c.heads[l], H >> l, W >> l)) {
-            size_t pf2;
-            fused_attn_plan(H >> l, W >> l, &ns, &pf2, B, C);
+            size_t pf2, used;
+            fused_attn_plan(H >> l, W >> l, &ns, &used, B, C, nullptr, &pf2);
             if (pf2 > gp) gp = pf2;
         }
         if (attn_mid_supported(C, c.heads[l], H >> l, W >> l)) {

@@ -262,17 +262,21 @@ _TB_KEYS = ("norm1.body.weight", "norm1.body.bias", "attn.temperature", "attn.qk
             "ffn.depthwise.weight", "ffn.depthwise.bias", "ffn.pointwise2.weight", "ffn.pointwise2.bias")
 
 
-def transformer_block(x: torch.Tensor, params, heads: int, ffn_expansion_factor: int = 2, prefix: str = "") -> torch.Tensor:
+def transformer_block(x: torch.Tensor, params, heads: int, ffn_expansion_factor: int = 2, prefix: str = "", interior=None) -> torch.Tensor:
     """``TransformerBlock(dim, heads, ffn_expansion_factor, bias=True)(x)``
     (FrequencyawareLumaChromaAttentionRAWFormer.py:238-254).  ``params`` maps the block's
     state_dict keys (``norm1.body.weight`` ...) to device tensors.  Same schedule as the whole
-    forward, i.e. the fused gfx950 kernels where the shape allows."""
+    forward, i.e. the fused gfx950 kernels where the shape allows.  ``interior = (y_lo, y_hi, x_lo, x_hi)``: ``x`` is one window
+    of a sharded frame and only that part of it enters the attention's Gram statistics (``rf_transformer_block_window``)."""
     x = _chk(x, "x")
     b, c, h, w = x.shape
     ts = [_chk(params[prefix + k], k) for k in _TB_KEYS]
     scratch = _lib.scratch("rf_transformer_block_scratch_bytes", x, b, c, heads, ffn_expansion_factor, h, w)
     out = torch.empty_like(x)
-    _lib.launch("rf_transformer_block", x, x, out, ts, scratch, b, c, heads, ffn_expansion_factor, h, w)
+    if interior is None:
+        _lib.launch("rf_transformer_block", x, x, out, ts, scratch, b, c, heads, ffn_expansion_factor, h, w)
+    else:
+        _lib.launch("rf_transformer_block_window", x, x, out, ts, scratch, b, c, heads, ffn_expansion_factor, h, w, *(int(v) for v in interior))
     return out
 
 

@@ -322,6 +322,18 @@ int rf_chan_attn(const float* in, float* out, const float* qkv_w, const float* q
 int rf_transformer_block_scratch_bytes(int B, int C, int heads, int ffn_expansion, int h, int w, size_t* bytes);
 int rf_transformer_block(const float* in, float* out, const float* const* prm, void* scratch,
                          int B, int C, int heads, int ffn_expansion, int h, int w, void* stream);
+/* The same on one window of a spatially sharded frame, as rf_forward runs it after rf_set_shard_grid: only rows [y_lo, y_hi) and
+ * columns [x_lo, x_hi) of the window enter the attention's Gram sums and norms (x_lo and x_hi whole groups of 4 pixels, or x_hi = w;
+ * all four 0: everything; x_lo = x_hi = 0: all columns; column bounds only together with row bounds: -22 otherwise).  No all-reduce: the statistics are the interior's alone.  Scratch: rf_transformer_block_scratch_bytes. */
+int rf_transformer_block_window(const float* in, float* out, const float* const* prm, void* scratch,
+                                int B, int C, int heads, int ffn_expansion, int h, int w, int y_lo, int y_hi, int x_lo, int x_hi, void* stream);
+/* Host only, no launch, no GPU needed: how the fused attention front (LayerNorm -> qkv 1x1 -> depthwise 3x3 -> Gram partials + v;
+ * C = 32, w % 4 == 0, heads that divide 16-channel tiles: -22 otherwise) is launched for [B,C,h,w].  out[0]: 1 = the eight-wave
+ * kernel on tiles of 12 rows x 64 px, two per workgroup (above 256 x 256), 0 = the four-wave kernel on tiles of 4 x 64; out[1]:
+ * workgroups per image = Gram partials per image; out[2]: floats of partials written, [B][out[1]][C/16][16][66]; out[3]: floats the
+ * scratch layouts set aside for them (>= out[2]).  out[0] and out[1] depend on (h, w) alone, so an image's sums are added in the same
+ * order whatever the batch. */
+int rf_attn_front_plan(int B, int C, int heads, int h, int w, long long out[4]);
 /* FLCA.forward given the guidance planes: FrequencyawareLumaChromaAttentionRAWFormer.py:134-162.
  * guide = [B,4,h,w] from rf_flca_guidance at the feature size; prm = HOST array of 10 device pointers:
  * alpha, beta, gamma, low_attn.0.w, high_attn.0.w, chroma_attn.0.w, se.1.{w,b}, se.3.{w,b}. */
