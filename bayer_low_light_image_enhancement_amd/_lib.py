@@ -173,6 +173,12 @@ SIGNATURES = {
     "rf_ml_modulate": (_i, [_vp, _vp, _vp, _i, _i] + [_vp] * 5 + [_i, _i, _i, _i, _vp]),
     "rf_ml_step_fused": (_i, [_vp, _vp, _vp, _i, _i] + [_vp] * 10 + [_i, _i, _i, _i, _vp]),
     "rf_ml_residual": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "rf_flca_pyramid_workspace_bytes": (C.c_longlong, [_i] * 7),
+    "rf_flca_pyramid_forward": (_i, [_vp, _vp, _vp, C.POINTER(_vp), _vp, _sz] + [_i] * 7 + [_vp]),
+    "rf_flca_pyramid_backward_workspace_bytes": (C.c_longlong, [_i] * 7),
+    "rf_flca_pyramid_backward": (_i, [_vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _sz] + [_i] * 8 + [_vp]),
+    "rf_ml_corrections_backward_workspace_bytes": (C.c_longlong, [_i, _i, _i]),
+    "rf_ml_corrections_backward": (_i, [_vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
 }
 
 # rf_optim_control and rf_optim_segment (include/rawformer_hip.h) as numpy record types, for reading the guarded step's device state

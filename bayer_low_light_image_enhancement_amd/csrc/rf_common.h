@@ -503,6 +503,48 @@ int launch_ml_step_fused(const float* x, float* out, const float* guide, const f
                          const float* b2, float* partial, int B, int C, int h, int w, hipStream_t st);
 int launch_ml_tail(float* out, const float* in, int mosaic, float* scratch, int B, int H, int W, int levels, hipStream_t st);
 
+// ---- FLCA_Pyramid as an operator (rf_flca_pyramid.hip): what rf_flca_pyramid_forward and the backward (rf_flca_pyramid_bwd.hip)
+// share.  PyrGroup: the 4 L + 11 tensors of the block in state_dict order (= the C ABI's pointer arrays), by name.
+template <class T> struct PyrGroup {
+    T low[3], high[3], gate_w[3], gate_b[3];      // low_attn.<l>.0 / high_attn.<l>.0 [C][1][3][3], freq_gate_head.<l> [2][2], [2]
+    T chr_w, cgate_w, cgate_b;                    // chroma_attn.0 [C][2][3][3], chroma_gate [1], [1]
+    SeGroup<T> se;
+    T r0_w, r0_b, r2_w, r2_b;                     // res_proj.0 / .2: [C][C], [C]
+};
+template <class T> PyrGroup<T> pyr_group(T const* a, int L) {
+    PyrGroup<T> g{};
+    for (int l = 0; l < L; ++l) { g.low[l] = a[l]; g.high[l] = a[L + l]; g.gate_w[l] = a[2 * L + 2 * l]; g.gate_b[l] = a[2 * L + 2 * l + 1]; }
+    a += 4 * L;
+    g.chr_w = a[0]; g.cgate_w = a[1]; g.cgate_b = a[2];
+    g.se = {a[3], a[4], a[5], a[6]};
+    g.r0_w = a[7]; g.r0_b = a[8]; g.r2_w = a[9]; g.r2_b = a[10];
+    return g;
+}
+size_t pyr_prm_floats(int i, int C, int levels);  // floats of tensor i of the pointer arrays
+// Float offsets of what the forward schedule uses, at the head of either entry point's workspace.  m, t, r and the two packed
+// matrices exist where a step is composed, and for the backward, which composes every step it differentiates.
+struct PyrFwdPlan {
+    bool fused;                                   // the steps run as launch_ml_step_fused
+    int nblk;                                     // pooling blocks per image: tc_nblk(h, w), the layout both step forms leave
+    size_t gscratch, guide, m, t, r, wp0, wp2, pool, ch;
+};
+// the shape checks of both entry points (`who` prefixes the refusal), then the layout
+int pyr_fwd_plan(const char* who, int B, int C, int h, int w, int H, int W, int levels, bool backward, PyrFwdPlan* p, Bump* b);
+// guidance and means at (h, w), then x_{s+1} -> x_next[s] for s = 0 .. levels (x_next[s] may be x_next[s - 1]: a step runs in
+// place); leaves the pooling sums of x_{levels+1} in ws + p.pool
+int pyr_forward_steps(const PyrFwdPlan& p, float* ws, const float* feat, const float* packed, float* const* x_next,
+                      const PyrGroup<const float*>& prm, int B, int C, int h, int w, int H, int W, int levels, hipStream_t st);
+// one residual step's m = x S_s, t = relu(W0 m + b0), r = W2 t + b2 into ws + p.m / p.t / p.r (the packs in p.wp0 / p.wp2 are
+// pyr_forward_steps's or, with `pack`, written first)
+int pyr_step_mtr(const PyrFwdPlan& p, float* ws, const float* x, int step, const PyrGroup<const float*>& prm, bool pack, int B, int C,
+                 int h, int w, int H, int W, int levels, hipStream_t st);
+const float* pyr_means(const PyrFwdPlan& p, const float* ws, int B, int H, int W, int levels);   // [B][8] at (h, w): ml_means's table
+// Squeeze-excite gate of every image from the pooling sums: ch [B][C].  With dch_part ([B][dnblk][C], per-block sums of dz x) also
+// its adjoint: dmP [B][C] = (gradient of the pooled mean) / P and contrib, each image's share of the gradients of se.1.weight,
+// se.1.bias, se.3.weight, se.3.bias as four arrays back to back: [B][hid C], [B][hid], [B][C hid], [B][C]
+int launch_pyr_se(const float* pool, int nblk, int P, const SePrm& se, float* ch, const float* dch_part, int dnblk, float* dmP, float* contrib,
+                  int B, int C, hipStream_t st);
+
 // ---- training kernels (rf_train.hip)
 #ifdef __HIPCC__
 // s[k] <- the sum of s[k] over a workgroup of 256 threads, in a fixed order: lanes by shuffles, then the four waves.  What a kernel

@@ -696,16 +696,17 @@ def _grads(grads, prefix, keys, shapes, like, who, zeros=()):
     return grads, gs, int(accumulate)
 
 
-def _backward(name, keys, shapes, x, params, grad_out, prefix, grads, geometry, trailing=(), buffers=()):
+def _backward(name, keys, shapes, x, params, grad_out, prefix, grads, geometry, trailing=(), buffers=(), extra=()):
     """What the ``*_backward`` wrappers share, ``x`` and ``grad_out`` checked by the caller: ``params`` and ``grads`` against
     ``shapes``, the workspace ``rf_<name>_backward_workspace_bytes(*geometry)`` asks for, and the call
-    ``rf_<name>_backward(x, grad_out, grad_x, params, grads, workspace, bytes, *geometry, *trailing, accumulate, stream)``.
-    ``buffers``: keys of ``shapes`` that the operator reads behind its parameters and that have no gradient."""
+    ``rf_<name>_backward(x, *extra, grad_out, grad_x, params, grads, workspace, bytes, *geometry, *trailing, accumulate, stream)``.
+    ``buffers``: keys of ``shapes`` that the operator reads behind its parameters and that have no gradient.  ``extra``: checked
+    tensors the operator reads beside ``x`` and that have no gradient either."""
     read = _shaped(params, prefix, tuple(keys) + tuple(buffers), shapes, f"{name}_backward")
     grads, gs, accumulate = _grads(grads, prefix, keys, shapes, x, f"{name}_backward")
     ws = _lib.scratch(f"rf_{name}_backward_workspace_bytes", x, *geometry)
     grad_x = torch.empty_like(x)
-    _lib.launch(f"rf_{name}_backward", x, x, grad_out, grad_x, read, gs, ws, ws.numel(), *geometry, *trailing, accumulate)
+    _lib.launch(f"rf_{name}_backward", x, x, *extra, grad_out, grad_x, read, gs, ws, ws.numel(), *geometry, *trailing, accumulate)
     return grad_x, grads
 
 
@@ -1146,3 +1147,70 @@ def ml_residual(x: torch.Tensor, r: torch.Tensor, out: Optional[torch.Tensor] = 
     b, c, h, w = x.shape if x.dim() == 4 else (1, 1, 1, x.numel())
     _lib.launch("rf_ml_residual", x, x, r, out, b, c, h, w)
     return out
+
+
+# ------------------------------------------------------------------------------------------ FLCA_Pyramid as an operator, and its gradient
+def flca_pyramid_param_shapes(c: int, levels: int = 2):
+    """Names and shapes of the 4 ``levels`` + 11 tensors ``flca_pyramid`` reads, in the order of the reference's ``state_dict`` (=
+    the C ABI's pointer array).  The squeeze-excite hidden width is ``max(8, c // 8)``."""
+    hid = max(8, c // 8)
+    shapes = {f"low_attn.{l}.0.weight": (c, 1, 3, 3) for l in range(levels)}
+    shapes.update({f"high_attn.{l}.0.weight": (c, 1, 3, 3) for l in range(levels)})
+    for l in range(levels):
+        shapes.update({f"freq_gate_head.{l}.weight": (2, 2, 1, 1), f"freq_gate_head.{l}.bias": (2,)})
+    shapes.update({"chroma_attn.0.weight": (c, 2, 3, 3), "chroma_gate.weight": (1, 1, 1, 1), "chroma_gate.bias": (1,),
+                   "se.1.weight": (hid, c, 1, 1), "se.1.bias": (hid,), "se.3.weight": (c, hid, 1, 1), "se.3.bias": (c,),
+                   "res_proj.0.weight": (c, c, 1, 1), "res_proj.0.bias": (c,), "res_proj.2.weight": (c, c, 1, 1), "res_proj.2.bias": (c,)})
+    return shapes
+
+
+def _flca_pyramid_inputs(feat, x4, levels, who):
+    feat, x4 = _chk(feat, "feat"), _chk(x4, "x4")
+    if feat.dim() != 4 or x4.dim() != 4 or x4.shape[1] != 4 or x4.shape[0] != feat.shape[0]:
+        raise RuntimeError(f"{who}: expected feat [B,C,h,w] and packed RGGB x4 [B,4,H,W], got {tuple(feat.shape)} and {tuple(x4.shape)}")
+    b, c, h, w = feat.shape
+    return feat, x4, (b, c, h, w, x4.shape[2], x4.shape[3], int(levels))
+
+
+def flca_pyramid(feat: torch.Tensor, x4: torch.Tensor, params, prefix: str = "", levels: int = 2) -> torch.Tensor:
+    """``FLCA_Pyramid(channels, levels)(feat, *BayerLumaChroma()(x4))`` (MultiLvlFrequencyawareLumaChromaAttentionRAWFormer.py
+    :86-183): the guidance pyramid from the packed RGGB frame ``x4`` [B,4,H,W] resized to ``feat``'s size, ``levels`` + 1 gated
+    residual steps through one ``res_proj``, squeeze-excite.  ``params``: the block's ``state_dict`` (``flca_pyramid_param_shapes``).
+    1 <= C <= 512, ``levels`` 1..3, H and W multiples of 8, any feature size; anything else raises with the library's message."""
+    feat, x4, geometry = _flca_pyramid_inputs(feat, x4, levels, "flca_pyramid")
+    ws = _lib.scratch("rf_flca_pyramid_workspace_bytes", feat, *geometry)
+    shapes = flca_pyramid_param_shapes(feat.shape[1], geometry[-1])
+    ts = _shaped(params, prefix, tuple(shapes), shapes, "flca_pyramid")
+    out = torch.empty_like(feat)
+    _lib.launch("rf_flca_pyramid_forward", feat, feat, x4, out, ts, ws, ws.numel(), *geometry)
+    return out
+
+
+def flca_pyramid_backward(feat: torch.Tensor, x4: torch.Tensor, params, grad_out: torch.Tensor, prefix: str = "", levels: int = 2,
+                          grads=None):
+    """The gradient of ``flca_pyramid``: ``(grad_feat, grads)`` for ``grad_out`` = dL/d ``flca_pyramid(feat, x4, params)``.  ``grads``
+    maps the 4 ``levels`` + 11 keys (``prefix`` included) to gradients of the parameters' shapes; ``x4`` and the guidance carry no
+    gradient.  Passing the ``grads`` of an earlier call ADDS to its tensors; ``grad_feat`` is always a new tensor.  The forward
+    intermediates are recomputed: nothing is kept from a ``flca_pyramid`` call, and ``feat``, ``x4``, ``grad_out`` and ``params``
+    are not written."""
+    feat, x4, geometry = _flca_pyramid_inputs(feat, x4, levels, "flca_pyramid_backward")
+    grad_out = _chk(grad_out, "grad_out")
+    if tuple(grad_out.shape) != tuple(feat.shape):
+        raise RuntimeError(f"flca_pyramid_backward: feat {tuple(feat.shape)} and grad_out {tuple(grad_out.shape)} differ")
+    _lib.size("rf_flca_pyramid_backward_workspace_bytes", *geometry)      # an unsupported geometry raises here, with the library's message
+    shapes = flca_pyramid_param_shapes(feat.shape[1], geometry[-1])
+    return _backward("flca_pyramid", tuple(shapes), shapes, feat, params, grad_out, prefix, grads, geometry, extra=(x4,))
+
+
+def ml_tail_backward(grad_out: torch.Tensor) -> torch.Tensor:
+    """The adjoint of the multi-level variant's output corrections (``RawFormer.ml_tail``; MultiLvlFrequencyawareLumaChromaAttention
+    RAWFormer.py:270-288, :403-414) with respect to the image: ``grad_image`` [B,3,h2,w2] for ``grad_out`` = dL/d (corrected image).
+    The map is affine in the image with constant coefficients, so nothing else is read."""
+    grad_out = _chk(grad_out, "grad_out")
+    if grad_out.dim() != 4 or grad_out.shape[1] != 3:
+        raise RuntimeError(f"ml_tail_backward: expected grad_out [B,3,h2,w2], got {tuple(grad_out.shape)}")
+    b, _, h2, w2 = grad_out.shape
+    ws = _lib.scratch("rf_ml_corrections_backward_workspace_bytes", grad_out, b, h2, w2)
+    grad_image = torch.empty_like(grad_out)
+    _lib.launch("rf_ml_corrections_backward", grad_out, grad_out, grad_image, ws, ws.numel(), b, h2, w2)
+    return grad_image

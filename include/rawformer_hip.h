@@ -685,6 +685,43 @@ int rf_ml_step_fused(const float* x, const float* guide, const float* means, int
                      float* out, float* partial, int B, int C, int h, int w, void* stream);
 int rf_ml_residual(const float* x, const float* r, float* out, int B, int C, int h, int w, void* stream);
 
+/* ---- FLCA_Pyramid as an operator and its gradient (csrc/rf_flca_pyramid.hip, csrc/rf_flca_pyramid_bwd.hip;
+ * MultiLvlFrequencyawareLumaChromaAttentionRAWFormer.py:86-183) ----------
+ * No handle.  feat, out [B,C,h,w]; packed [B,4,H,W], the packed Bayer frame the guidance is made from inside the call (the planes
+ * resized to (h, w), the means those of the resized planes; (h, w) need not be (H >> k, W >> k)).  prm = HOST array of
+ * 4 levels + 11 device pointers in state_dict order: low_attn.<l>.0.weight [C,1,3,3] for every l, high_attn.<l>.0.weight for every
+ * l, freq_gate_head.<l>.{weight [2,2], bias [2]} for every l, chroma_attn.0.weight [C,2,3,3], chroma_gate.{weight [1], bias [1]},
+ * se.1.{weight [hid,C], bias [hid]}, se.3.{weight [C,hid], bias [C]} with hid = max(8, C / 8), res_proj.0.{weight [C,C], bias [C]},
+ * res_proj.2.{weight, bias}.
+ *   x_0 = feat;  x_{s+1} = x_s + 0.2 tanh(res_proj(x_s S_s)), s = 0 .. levels (S_s: rf_ml_modulate's gate of step s);
+ *   out = x_{levels+1} sigmoid(se.3 relu(se.1 mean_p(x_{levels+1})))
+ * Supported: 1 <= B <= 65535, 1 <= C <= 512, levels 1..3, H % 8 == 0, W % 8 == 0, any h, w >= 1 with h w <= 2^28.  Anything else is
+ * refused before the first launch: the *_bytes queries return the negative error code, the entry points -22, with an rf_last_error
+ * message that starts with the entry point's name.  -12 for a workspace smaller than the query's answer.
+ * rf_flca_pyramid_forward: feat, packed, out and workspace 16-byte aligned; out may not overlap feat.  A step is one kernel where
+ * rf_ml_step_fused runs (C = 16, 32, 48, 64, w % 4 == 0, h w % 64 == 0), elsewhere rf_ml_modulate, two 1x1 GEMMs and the residual.
+ * rf_flca_pyramid_backward: (feat, packed, grad_out = dL/d out) -> grad_in = dL/d feat and the 4 levels + 11 parameter gradients
+ * (shapes of prm).  packed and the guidance carry no gradient.  Conventions of rf_wm_backward: nothing is kept from a forward call
+ * (x_1 .. x_{levels+1} are recomputed, then each step's intermediates in turn); feat, packed, grad_out and the parameters are not
+ * written; grad_in is always overwritten; accumulate != 0 ADDS to the grad_prm tensors, 0 overwrites them (res_proj's are the sum
+ * over the levels + 1 steps either way); every pointer but the two arrays is 16-byte aligned; nothing the call writes (grad_in,
+ * the gradients, the workspace) may overlap anything it reads (feat, grad_out, the parameters, packed) or anything else it writes;
+ * every sum runs in a fixed order (no float atomics): two runs give the same bits.
+ * rf_ml_corrections_backward: the adjoint of rf_ml_tail's map image -> image (affine in the image with constant coefficients, so no other
+ * input): with G = sum_c g_c and w = (0.299, 0.587, 0.114), g1_c = g_c - 0.03 w_c G and grad_image_c = g1_c - 0.12 mean_p(g1_c).
+ * grad_out, grad_image [B,3,h2,w2], 16-byte aligned, not overlapping; any h2 w2 >= 1 (<= 2^30), B <= 65535; 16 bytes per lane where
+ * w2 % 4 == 0.  workspace >= rf_ml_corrections_backward_workspace_bytes(B, h2, w2). */
+long long rf_flca_pyramid_workspace_bytes(int B, int C, int h, int w, int H, int W, int levels);
+int rf_flca_pyramid_forward(const float* feat, const float* packed, float* out, const float* const* prm, void* workspace,
+                            size_t workspace_bytes, int B, int C, int h, int w, int H, int W, int levels, void* stream);
+long long rf_flca_pyramid_backward_workspace_bytes(int B, int C, int h, int w, int H, int W, int levels);
+int rf_flca_pyramid_backward(const float* feat, const float* packed, const float* grad_out, float* grad_in, const float* const* prm,
+                             float* const* grad_prm, void* workspace, size_t workspace_bytes, int B, int C, int h, int w, int H, int W,
+                             int levels, int accumulate, void* stream);
+long long rf_ml_corrections_backward_workspace_bytes(int B, int h2, int w2);
+int rf_ml_corrections_backward(const float* grad_out, float* grad_image, void* workspace, size_t workspace_bytes, int B, int h2, int w2,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
