@@ -55,6 +55,9 @@ __device__ __forceinline__ float gelu_fast(float v) {
     const float h = 0.5f * v;
     return h + fmaf(-fabsf(h), q, fabsf(h));
 }
+// the accurate sigmoid (expf) of the gradient kernels and the squeeze-excite gates; the forward's spatial gates use fast forms of their own
+__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }   // p 16-byte aligned
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -617,6 +620,9 @@ int launch_attn_small(const AttnSmall& a, int B, hipStream_t st);
 
 // ---- FLCA branch, backward (rf_flca_bwd.hip)
 size_t flca_bwd_scratch_floats(int B, int C, int h, int w);
+// partial[(b * nblk + blk) * C + c] = sum over pixel block blk of dz x: dz with dz_bstride floats between images, x [B][C][P].  nblk
+// fixes the order of the sum and is the caller's (chan_sum_nblk here, pyr_dch_nblk in rf_flca_pyramid_bwd.hip)
+int launch_flca_dch(const float* dz, int64_t dz_bstride, const float* x, float* partial, int nblk, int B, int C, int P, hipStream_t st);
 // prm / grd: the FLCA parameters and their gradients (grd.se: four tensors adjacent in the flat gradient buffer, checked)
 int launch_flca_backward(const float* feat, const float* guide, const float* xs, const float* dz, int64_t dz_bstride, const float* ch,
                          const float* pool_partial, int pool_nblk, const FlcaPrm& prm, const FlcaGrad& grd, float* dfeat, int accumulate,

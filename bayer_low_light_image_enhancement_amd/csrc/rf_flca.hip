@@ -7,7 +7,7 @@
 //   flca_se_fold  : SE MLP, then folds the per-image channel gate into the following
 //                   channel_reduce 1x1:  W_cr [x*ch ; trans] = [W_a diag(ch) | W_b] [x ; trans]
 #include <type_traits>
-#include "rf_common.h"
+#include "rf_flca_adjoint.h"
 
 namespace rf {
 
@@ -339,51 +339,17 @@ int launch_flca_spatial(const FlcaSpatialArgs& a, hipStream_t st) {
     return check_launch("flca_spatial");
 }
 
-// squeeze-excite gate of one image: pooled mean (fixed-order reduction of the per-block sums,
-// all 256 threads busy: thread = (block slice, channel)), 2-layer MLP, sigmoid
+// squeeze-excite gate of one image: pooled mean (fixed-order reduction of the per-block sums, all 256 threads busy:
+// se_column_sums; C is a multiple of 8), 2-layer MLP, sigmoid
 __global__ void __launch_bounds__(256) flca_se_kernel(const float* __restrict__ partial, int nblk, int P,
                                                       const float* __restrict__ se1_w, const float* __restrict__ se1_b,
                                                       const float* __restrict__ se3_w, const float* __restrict__ se3_b, int hidden,
                                                       float* __restrict__ ch_out, int C) {
     const size_t b = blockIdx.x;
     __shared__ float part[256], mean[512], hid[64];
-    const int cw = C < 256 ? C : 256;          // channels handled per pass
-    const int nsl = 256 / cw;                  // block slices summed in parallel (C is a multiple of 8)
-    for (int c0 = 0; c0 < C; c0 += cw) {
-        const int c = c0 + threadIdx.x % cw, sl = threadIdx.x / cw;
-        float s = 0.f;
-        if (sl < nsl && c < C) {
-            const float* src = partial + b * nblk * C + c;
-            int k = sl;
-            for (; k + 7 * nsl < nblk; k += 8 * nsl) {      // 8 loads in flight, summed in block order
-                float t[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) t[u] = src[(size_t)(k + u * nsl) * C];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) s += t[u];
-            }
-            for (; k < nblk; k += nsl) s += src[(size_t)k * C];
-        }
-        part[threadIdx.x] = s;
-        __syncthreads();
-        if (threadIdx.x < cw && c0 + threadIdx.x < C) {
-            float t = 0.f;
-            for (int q = 0; q < nsl; ++q) t += part[q * cw + threadIdx.x];
-            mean[c0 + threadIdx.x] = t / (float)P;
-        }
-        __syncthreads();
-    }
-    for (int m = threadIdx.x; m < hidden; m += 256) {
-        float s = se1_b[m];
-        for (int c = 0; c < C; ++c) s = fmaf(se1_w[m * C + c], mean[c], s);
-        hid[m] = fmaxf(s, 0.f);
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < C; c += 256) {
-        float s = se3_b[c];
-        for (int m = 0; m < hidden; ++m) s = fmaf(se3_w[c * hidden + m], hid[m], s);
-        ch_out[b * C + c] = 1.0f / (1.0f + expf(-s));
-    }
+    se_column_sums(partial, b, nblk, C, part, [&](int c, float t) { mean[c] = t / (float)P; });
+    se_hidden(se1_w, se1_b, mean, hid, C, hidden);
+    for (int c = threadIdx.x; c < C; c += 256) ch_out[b * C + c] = se_gate(se3_w, se3_b, hid, c, hidden);
 }
 
 // wp_out[b] = pack([W_a diag(ch_b) | W_b]) in MFMA operand order

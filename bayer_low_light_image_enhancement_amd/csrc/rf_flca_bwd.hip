@@ -4,19 +4,19 @@
 // Backward of z w.r.t. feat and the 10 parameter tensors (the guidance planes carry no gradient: they come from the input):
 //   dch[b][c] = sum_p dz xs           -> squeeze-excite MLP backward (tiny, per image) -> dm[b][c] (gradient of the pooled mean)
 //   dxs = dz ch + dm / P;   dfeat = dxs S;   dS = dxs feat;   dalpha = sum dS a_low, ...;   d(conv outputs) -> tap sums
-// Kernels: flca_dch_kernel, flca_se_bwd_kernel (squeeze-excite part), flca_bwd_fused_kernel (spatial part and tap sums in one
-// pass), flca_abg_kernel and flca_taps_scatter_kernel (the last step of their sums).  Slabs are split by gram2_slabs and added in
-// order by launch_reduce_rows (rf_train.hip): two runs give the same bits.  FlcaBwdPlan is the scratch layout, launch_flca_backward
-// the schedule.
-#include "rf_common.h"
+// Kernels: flca_dch_kernel (launch_flca_dch: FLCA_Pyramid's backward runs it too), flca_se_bwd_kernel (squeeze-excite part),
+// flca_bwd_fused_kernel (spatial part and tap sums in one pass), flca_abg_kernel and flca_taps_scatter_kernel (the last step of
+// their sums).  The squeeze-excite MLP and the steps of the MFMA tap contraction -- B operand, neighbourhood row, fold of the
+// accumulator tiles -- are rf_flca_adjoint.h's, shared with rf_flca.hip and rf_flca_pyramid*.hip.  Slabs are split by gram2_slabs
+// and added in order by launch_reduce_rows (rf_train.hip): two runs give the same bits.  FlcaBwdPlan is the scratch layout,
+// launch_flca_backward the schedule.
+#include "rf_flca_adjoint.h"
 
 namespace rf {
 namespace {
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-// dch partial: partial[((b * nblk + blk) * C + c)] = sum over the block's pixels of dz * xs
+// dch partial: partial[(b * nblk + blk) * C + c] = sum over the block's pixels of dz x.  dz has dz_bstride floats between images,
+// x is [B][C][P]; the caller's nblk fixes the order of the sum
 __global__ void __launch_bounds__(256) flca_dch_kernel(const float* __restrict__ dz, int64_t dz_bstride, const float* __restrict__ xs, float* __restrict__ partial,
                                                        int C, int P, int nblk) {
     const int blk = blockIdx.x, c = blockIdx.y, b = blockIdx.z;
@@ -33,76 +33,24 @@ __global__ void __launch_bounds__(256) flca_dch_kernel(const float* __restrict__
 // squeeze-excite backward, one workgroup per image (a single workgroup walking the images in turn took 120 us per stage):
 // in: pooled sums partial (forward: flca partial / P = mean), dch partials;  out: dm[b][c] / P and the image's CONTRIBUTION to the
 // gradients of se.1.{w,b}, se.3.{w,b} in contrib[b][hid C | hid | C hid | C] (the order of the four tensors in the flat gradient
-// buffer), summed over the images in order by reduce_partials_kernel: deterministic.
+// buffer), summed over the images in order by reduce_partials_kernel: deterministic.  Both tables are summed the way the
+// forward's flca_se_kernel sums its own (se_column_sums).
 __global__ void __launch_bounds__(256) flca_se_bwd_kernel(const float* __restrict__ pool_partial, int pool_nblk, const float* __restrict__ dch_partial, int dch_nblk,
                                                           const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w3, const float* __restrict__ b3,
                                                           float* __restrict__ dmP, float* __restrict__ contrib, int C, int hid, int P) {
-    __shared__ float mean[512], dch[512], ds3[512], hv[64], dh[64];
-    __shared__ float part[2][256];
+    __shared__ float mean[512], ds3[512], hv[64], dh[64], part[256];
     const size_t b = blockIdx.x;
-    // column sums of the two partial tables: cw channels x nsl row slices per pass, 8 loads in flight per thread, slices
-    // combined in a fixed order (the forward's flca_se_kernel sums its table the same way)
-    const int cw = C < 256 ? C : 256, nsl = 256 / cw;
-    for (int c0 = 0; c0 < C; c0 += cw) {
-        const int c = c0 + threadIdx.x % cw, sl = threadIdx.x / cw;
-        float s = 0.f, d = 0.f;
-        if (sl < nsl && c < C) {
-            const float* src = pool_partial + b * pool_nblk * C + c;
-            int k = sl;
-            for (; k + 7 * nsl < pool_nblk; k += 8 * nsl) {
-                float t[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) t[u] = src[(size_t)(k + u * nsl) * C];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) s += t[u];
-            }
-            for (; k < pool_nblk; k += nsl) s += src[(size_t)k * C];
-            const float* dsrc = dch_partial + b * dch_nblk * C + c;
-            for (int q = sl; q < dch_nblk; q += nsl) d += dsrc[(size_t)q * C];
-        }
-        part[0][threadIdx.x] = s;
-        part[1][threadIdx.x] = d;
-        __syncthreads();
-        if (threadIdx.x < cw && c0 + threadIdx.x < C) {
-            float t = 0.f, u = 0.f;
-            for (int q = 0; q < nsl; ++q) { t += part[0][q * cw + threadIdx.x]; u += part[1][q * cw + threadIdx.x]; }
-            mean[c0 + threadIdx.x] = t / (float)P;
-            dch[c0 + threadIdx.x] = u;
-        }
-        __syncthreads();
-    }
-    for (int m = threadIdx.x; m < hid; m += 256) {
-        float s = b1[m];
-        for (int c = 0; c < C; ++c) s = fmaf(w1[m * C + c], mean[c], s);
-        hv[m] = fmaxf(s, 0.f);
-    }
-    __syncthreads();
+    se_column_sums(pool_partial, b, pool_nblk, C, part, [&](int c, float t) { mean[c] = t / (float)P; });
+    se_column_sums(dch_partial, b, dch_nblk, C, part, [&](int c, float t) { ds3[c] = t; });      // dch, until the gate is known
+    se_hidden(w1, b1, mean, hv, C, hid);
     for (int c = threadIdx.x; c < C; c += 256) {
-        float s = b3[c];
-        for (int m = 0; m < hid; ++m) s = fmaf(w3[c * hid + m], hv[m], s);
-        const float chv = sigm(s);
-        ds3[c] = dch[c] * chv * (1.0f - chv);
+        const float chv = se_gate(w3, b3, hv, c, hid);
+        ds3[c] = ds3[c] * chv * (1.0f - chv);
     }
-    __syncthreads();
-    for (int m = threadIdx.x; m < hid; m += 256) {
-        float s = 0.f;
-        for (int c = 0; c < C; ++c) s = fmaf(w3[c * hid + m], ds3[c], s);
-        dh[m] = hv[m] > 0.f ? s : 0.f;
-    }
-    __syncthreads();
     float* gw1 = contrib + b * (size_t)(2 * C * hid + hid + C);
     float* gb1 = gw1 + (size_t)hid * C;
     float* gw3 = gb1 + hid;
-    float* gb3 = gw3 + (size_t)C * hid;
-    for (int e = threadIdx.x; e < hid * C; e += 256) gw1[e] = dh[e / C] * mean[e % C];          // [hid][C]
-    for (int m = threadIdx.x; m < hid; m += 256) gb1[m] = dh[m];
-    for (int e = threadIdx.x; e < C * hid; e += 256) gw3[e] = ds3[e / hid] * hv[e % hid];       // [C][hid]
-    for (int c = threadIdx.x; c < C; c += 256) gb3[c] = ds3[c];
-    for (int c = threadIdx.x; c < C; c += 256) {
-        float s = 0.f;
-        for (int m = 0; m < hid; ++m) s = fmaf(w1[m * C + c], dh[m], s);
-        dmP[b * C + c] = s / (float)P;
-    }
+    se_adjoint(w1, w3, mean, hv, ds3, dh, gw1, gb1, gw3, gw3 + (size_t)C * hid, dmP + b * C, C, hid, P);
 }
 
 struct FlcaBwdArgs {
@@ -155,37 +103,15 @@ __global__ void __launch_bounds__(256) flca_bwd_fused_kernel(FlcaBwdArgs a, floa
         const int n = ok ? nn : n_lo;
         const int y = n / w, x = n - y * w;
         const float4 dz4 = ld4(dzr + n), f4 = ld4(fr + n);
-        // B operand: this lane's tap of the four planes at the lane's 4 pixels
         float bv[4][4];
-        {
-            const int yy = y + tdy;
-            const bool rowok = ok && r < 9 && yy >= 0 && yy < h;
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const int xx = x + m + tdx;
-                const bool in = rowok && xx >= 0 && xx < w;
-                const size_t off = in ? (size_t)yy * w + xx : 0;
-#pragma unroll
-                for (int pl = 0; pl < 4; ++pl) { const float v = gpl[(size_t)pl * P + off]; bv[pl][m] = in ? v : 0.f; }
-            }
-        }
+        tap_operand<4>(gpl, P, h, w, y, x, r, tdy, tdx, ok, bv);
         // gates of the lane's channel at its 4 pixels: pre-activations from the 3 x 6 neighbourhood of each plane
         float s_l[4] = {0.f, 0.f, 0.f, 0.f}, s_h[4] = {0.f, 0.f, 0.f, 0.f}, s_c[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int dy = 0; dy < 3; ++dy) {
             const int yy = y + dy - 1;
-            const bool rok = yy >= 0 && yy < h;
-            const size_t rowoff = (size_t)(rok ? yy : 0) * w + x;
             float nb[4][6];
-#pragma unroll
-            for (int pl = 0; pl < 4; ++pl) {
-                const float* row = gpl + (size_t)pl * P + rowoff;
-                const float4 t = ld4(row);
-                const float lft = row[x > 0 ? -1 : 0], rgt = row[x + 4 < w ? 4 : 0];
-                nb[pl][0] = (rok && x > 0) ? lft : 0.f;
-                nb[pl][1] = rok ? t.x : 0.f; nb[pl][2] = rok ? t.y : 0.f; nb[pl][3] = rok ? t.z : 0.f; nb[pl][4] = rok ? t.w : 0.f;
-                nb[pl][5] = (rok && x + 4 < w) ? rgt : 0.f;
-            }
+            neighbour_row<4>(gpl, P, w, x, yy, yy >= 0 && yy < h, nb);
 #pragma unroll
             for (int dx = 0; dx < 3; ++dx) {
                 const float k0 = wl[dy * 3 + dx], k1 = wh[dy * 3 + dx], k2 = wc[dy * 3 + dx], k3 = wc[9 + dy * 3 + dx];
@@ -225,17 +151,7 @@ __global__ void __launch_bounds__(256) flca_bwd_fused_kernel(FlcaBwdArgs a, floa
         }
     }
     __shared__ float red[4][16][17];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 4; ++q) red[wave][4 * kq + q][r] = acc[t][q];
-        __syncthreads();
-        const int i = threadIdx.x >> 4, jj = threadIdx.x & 15;
-        const int gi = 16 * ti + i;
-        if (gi < C && jj < 9)
-            partial[((size_t)slab * C + gi) * 36 + 9 * t + jj] = ((red[0][i][jj] + red[1][i][jj]) + red[2][i][jj]) + red[3][i][jj];
-    }
+    fold_tap_tiles<4>(acc, red, wave, kq, r, ti, C, [=](int t, int gi, int jj) { return partial + ((size_t)slab * C + gi) * 36 + 9 * t + jj; });
     // dalpha, dbeta, dgamma of the workgroup (red is free again after the barrier)
     __syncthreads();
     float abg[3] = {sa, sb, sg};
@@ -311,6 +227,11 @@ FlcaBwdPlan flca_bwd_plan(int B, int C, int h, int w) {
 
 size_t flca_bwd_scratch_floats(int B, int C, int h, int w) { return flca_bwd_plan(B, C, h, w).floats; }
 
+int launch_flca_dch(const float* dz, int64_t dz_bstride, const float* x, float* partial, int nblk, int B, int C, int P, hipStream_t st) {
+    flca_dch_kernel<<<dim3((unsigned)nblk, (unsigned)C, (unsigned)B), 256, 0, st>>>(dz, dz_bstride, x, partial, C, P, nblk);
+    return check_launch("flca_dch");
+}
+
 int launch_flca_backward(const float* feat, const float* guide, const float* xs, const float* dz, int64_t dz_bstride, const float* ch,
                          const float* pool_partial, int pool_nblk, const FlcaPrm& prm, const FlcaGrad& grd, float* dfeat, int accumulate,
                          float* scratch, size_t scratch_floats, int B, int C, int h, int w, hipStream_t st) {
@@ -329,7 +250,7 @@ int launch_flca_backward(const float* feat, const float* guide, const float* xs,
                  "flca backward: the gradients of se.1.weight, se.1.bias, se.3.weight, se.3.bias must be contiguous");
     ProfScope prof(st, "flca_backward(fused)", 2.0 * 36 * (double)B * C * P + 200.0 * B * C * P, 12.0 * (double)B * C * P + 8.0 * B * C * P);
     // squeeze-excite part: dch -> per-image MLP adjoint -> dm, the four se gradients (all four reduced at once)
-    flca_dch_kernel<<<dim3((unsigned)p.dnblk, (unsigned)C, (unsigned)B), 256, 0, st>>>(dz, dz_bstride, xs, dch_part, C, P, p.dnblk);
+    RF_TRY(launch_flca_dch(dz, dz_bstride, xs, dch_part, p.dnblk, B, C, P, st));
     flca_se_bwd_kernel<<<B, 256, 0, st>>>(pool_partial, pool_nblk, dch_part, p.dnblk, prm.se.se1_w, prm.se.se1_b, prm.se.se3_w, prm.se.se3_b, dmP,
                                           se_contrib, C, p.hid, P);
     RF_TRY(launch_reduce_rows(se_contrib, grd.se.se1_w, B, p.n_se, 1, st));

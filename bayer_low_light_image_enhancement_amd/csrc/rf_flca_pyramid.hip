@@ -6,18 +6,17 @@
 // launch_ml_modulate, two 1x1 GEMMs (weights packed per call) and launch_ml_residual / launch_tc_residual; the last step leaves the
 // pooling sums.  The model folds ch into channel_reduce; here pyr_se_kernel computes it and launch_scale_channels_to applies it.
 // pyr_se_kernel is the block's own: launch_flca_se takes multiples of 8 channels only, and the backward (rf_flca_pyramid_bwd.hip)
-// runs the same kernel with the adjoint switched on.  PyrFwdPlan is the one layout behind the size query and the pointers.
-#include "rf_common.h"
+// runs the same kernel with the adjoint switched on; the MLP and its adjoint are rf_flca_adjoint.h's, the in-order column sums
+// are its own.  PyrFwdPlan is the one layout behind the size query and the pointers.
+#include "rf_flca_adjoint.h"
 
 namespace rf {
 
 namespace {
 
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 // One workgroup per image.  pool [B][nblk][C]: per-block channel sums of x_{L+1}, added in block order.  dch_part == nullptr: the
-// gate alone.  Otherwise dch_part [B][dnblk][C] (per-block sums of dz x_{L+1}) and the MLP adjoint:
-//   ds3 = dch ch (1 - ch);  dh = (W3^T ds3) [hv > 0];  dmP = W1^T dh / P;  the image's share of the four gradients -> g_*[b]
+// gate alone.  Otherwise dch_part [B][dnblk][C] (per-block sums of dz x_{L+1}, added in block order) and the MLP adjoint
+// (se_adjoint): the image's share of the four gradients -> g_*[b], dmP
 __global__ void __launch_bounds__(256) pyr_se_kernel(const float* __restrict__ pool, int nblk, const float* __restrict__ dch_part, int dnblk,
                                                      const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w3,
                                                      const float* __restrict__ b3, float* __restrict__ ch, float* __restrict__ dmP,
@@ -31,16 +30,9 @@ __global__ void __launch_bounds__(256) pyr_se_kernel(const float* __restrict__ p
         mean[c] = s / (float)P;
     }
     __syncthreads();
-    for (int m = threadIdx.x; m < hid; m += 256) {
-        float s = b1[m];
-        for (int c = 0; c < C; ++c) s = fmaf(w1[m * C + c], mean[c], s);
-        hv[m] = fmaxf(s, 0.f);
-    }
-    __syncthreads();
+    se_hidden(w1, b1, mean, hv, C, hid);
     for (int c = threadIdx.x; c < C; c += 256) {
-        float s = b3[c];
-        for (int m = 0; m < hid; ++m) s = fmaf(w3[c * hid + m], hv[m], s);
-        const float chv = sigm(s);
+        const float chv = se_gate(w3, b3, hv, c, hid);
         ch[b * C + c] = chv;
         if (dch_part) {      // kernel argument: uniform
             float d = 0.f;
@@ -49,23 +41,8 @@ __global__ void __launch_bounds__(256) pyr_se_kernel(const float* __restrict__ p
         }
     }
     if (!dch_part) return;
-    __syncthreads();
-    for (int m = threadIdx.x; m < hid; m += 256) {
-        float s = 0.f;
-        for (int c = 0; c < C; ++c) s = fmaf(w3[c * hid + m], ds3[c], s);
-        dh[m] = hv[m] > 0.f ? s : 0.f;
-    }
-    __syncthreads();
     const size_t n = (size_t)hid * C;
-    for (int e = threadIdx.x; e < hid * C; e += 256) g_w1[b * n + e] = dh[e / C] * mean[e % C];          // [hid][C]
-    for (int m = threadIdx.x; m < hid; m += 256) g_b1[b * hid + m] = dh[m];
-    for (int e = threadIdx.x; e < C * hid; e += 256) g_w3[b * n + e] = ds3[e / hid] * hv[e % hid];       // [C][hid]
-    for (int c = threadIdx.x; c < C; c += 256) {
-        g_b3[b * C + c] = ds3[c];
-        float s = 0.f;
-        for (int m = 0; m < hid; ++m) s = fmaf(w1[m * C + c], dh[m], s);
-        dmP[b * C + c] = s / (float)P;
-    }
+    se_adjoint(w1, w3, mean, hv, ds3, dh, g_w1 + b * n, g_b1 + b * hid, g_w3 + b * n, g_b3 + b * C, dmP + b * C, C, hid, P);
 }
 
 }  // namespace

@@ -6,7 +6,7 @@
 //   S_L = gamma sigmoid(conv3([cr, cb]; w_chr)),  gamma = sigmoid(chroma_gate(mean sqrt(cr^2 + cb^2 + 1e-8)))
 // Nothing is kept from a forward call: pyr_forward_steps recomputes x_1 .. x_{L+1} (and the guidance, which carries no gradient),
 // then, with dz = dL/dz:
-//   squeeze-excite   dch = sum_p dz x_{L+1} (pyr_dch_kernel) -> pyr_se_kernel's adjoint -> dmean / P and the four se gradients;
+//   squeeze-excite   dch = sum_p dz x_{L+1} (launch_flca_dch, rf_flca_bwd.hip) -> pyr_se_kernel's adjoint -> dmean / P and the four se gradients;
 //                    dx = dz ch + dmean / P (pyr_dx_kernel), kept in grad_in from here on
 //   for s = L .. 0   m, t, r again (pyr_step_mtr);  dr = 0.2 (1 - tanh^2 r) dx in place of r (pyr_dtanh_kernel)
 //                    dW2, db2 += wgrad1x1(dr, t);  dpre = (W2^T dr) [t > 0];  dW0, db0 += wgrad1x1(dpre, m);  dm = W0^T dpre
@@ -18,9 +18,10 @@
 // accumulate, is added to) the caller's tensors once, so an accumulating call adds exactly what a plain call writes.  The backward
 // recomputes its gates with expf / tanhf, not the forward's fast forms.
 //
-// pyr_spatial_bwd has two forms over one slab layout.  w % 4 == 0: flca_bwd_fused_kernel's pattern (rf_flca_bwd.hip) -- a lane owns
-// one channel of a 16-channel tile and 4 pixels, recomputes the gate there from the two guidance planes with the channel's 18
-// weights in registers, and feeds the two d(conv output) values into 16x16x4 MFMAs whose B rows are the taps.  Any other width:
+// pyr_spatial_bwd has two forms over one slab layout and one prologue (PyrSpLane).  w % 4 == 0: the MFMA tap contraction of
+// rf_flca_adjoint.h, which flca_bwd_fused_kernel (rf_flca_bwd.hip) runs on four planes -- a lane owns one channel of a 16-channel
+// tile and 4 pixels, recomputes the gate there from the two guidance planes with the channel's 18 weights in registers, and feeds
+// the two d(conv output) values into 16x16x4 MFMAs whose B rows are the taps.  Any other width:
 // a thread owns one channel and every 16th pixel of the slab and keeps the 18 tap sums in registers.  dm, x_s and dx are read
 // once and dx written once.  Slabs are pixel ranges of one image (pyr_slabs).
 //
@@ -29,6 +30,7 @@
 //   g1_c = g_c - 0.03 w_c G;   grad_c = g1_c - 0.12 mean_p(g1_c)
 // ml_tail_bwd_sums_kernel leaves per-block sums of g1_c, ml_tail_bwd_apply_kernel adds them in block order and applies.
 // No float atomics anywhere: two calls give the same bits.
+#include "rf_flca_adjoint.h"
 #include "rf_grad.h"
 
 namespace rf {
@@ -38,22 +40,6 @@ namespace {
 constexpr int kMeans = 8;            // floats per image in ml_means's table (rf_multilvl.hip): 2 l, 2 l + 1 the level's, 6 the chroma magnitude's
 constexpr int kTailSumBlocks = 256;  // most workgroups per image of ml_tail_bwd_sums_kernel (= partial sums per channel)
 constexpr int kTailApplyBlocks = 1024;   // ... of ml_tail_bwd_apply_kernel
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-// dch partial: partial[(b * nblk + blk) * C + c] = sum over the block's pixels of dz x
-__global__ void __launch_bounds__(256) pyr_dch_kernel(const float* __restrict__ dz, const float* __restrict__ x, float* __restrict__ partial, int C,
-                                                      int P, int nblk) {
-    const int blk = blockIdx.x, c = blockIdx.y, b = blockIdx.z;
-    const size_t row = ((size_t)b * C + c) * P;
-    const int per = (P + nblk - 1) / nblk, lo = blk * per, hi = (lo + per < P) ? lo + per : P;
-    float s[1] = {0.f};
-    for (int p = lo + threadIdx.x; p < hi; p += 256) s[0] = fmaf(dz[row + p], x[row + p], s[0]);
-    __shared__ float red[4];
-    block_sums<1>(s, red);
-    if (threadIdx.x == 0) partial[((size_t)b * nblk + blk) * C + c] = s[0];
-}
 
 // dx = dz ch[b][c] + dmP[b][c];  PX = 4: P % 4 == 0, 16 bytes per lane
 template <int PX>
@@ -136,75 +122,77 @@ __device__ __forceinline__ size_t tap_index(const PyrSpArgs& a, int slab, int c,
     return CHROMA ? ((size_t)slab * a.C + c) * 18 + 9 * plane + tap : (((size_t)plane * a.nslab + slab) * a.C + c) * 9 + tap;
 }
 
+// What both tap kernels set up for a thread that owns channel 16 ti + r (clamped to C - 1, cvalid = false, past the last) of the
+// workgroup's slab: the slab's pixel range [n_lo, n_hi) of image img, the channel's 18 weights, the step's gates, its rows
+template <bool CHROMA>
+struct PyrSpLane {
+    int slab, ti, img, sl, h, w, P, C, n_lo, n_hi, c;
+    bool cvalid;
+    float wa[9], wb[9], g0, g1;
+    const float *dmr, *xr, *gpl;
+    float* dxr;
+    __device__ __forceinline__ PyrSpLane(const PyrSpArgs& a, int r) {
+        slab = blockIdx.x; ti = blockIdx.y;
+        img = slab / a.per_image; sl = slab - img * a.per_image;
+        h = a.h; w = a.w; P = h * w; C = a.C;
+        n_lo = sl * a.slab_px; n_hi = (n_lo + a.slab_px < P) ? n_lo + a.slab_px : P;
+        cvalid = 16 * ti + r < C;
+        c = cvalid ? 16 * ti + r : C - 1;
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            wa[t] = CHROMA ? a.w_a[c * 18 + t] : a.w_a[c * 9 + t];
+            wb[t] = CHROMA ? a.w_a[c * 18 + 9 + t] : a.w_b[c * 9 + t];
+        }
+        step_gates<CHROMA>(a, (size_t)img, g0, g1);
+        const size_t row = ((size_t)img * C + c) * P;
+        dmr = a.dm + row; xr = a.x + row; dxr = a.dx + row;
+        gpl = a.planes + (size_t)img * a.plane_bstride;
+    }
+};
+
+// the workgroup's two gate sums -> its row of a.gsum; lds: 8 floats no thread still reads
+__device__ __forceinline__ void store_gate_sums(const PyrSpArgs& a, int sl, int ti, int img, float sa, float sb, float* lds) {
+    float gs[2] = {sa, sb};
+    block_sums<2>(gs, lds);
+    if (threadIdx.x == 0) {
+        float* o = a.gsum + (((size_t)sl * gridDim.y + ti) * (a.nslab / a.per_image) + img) * 2;
+        o[0] = gs[0];
+        o[1] = gs[1];
+    }
+}
+
 // w % 4 == 0.  Workgroup (slab, 16-channel tile); lane (r = lane & 15, kq = lane >> 4) owns channel 16 ti + r and, per trip of
 // its wave, pixels n0 + 4 kq .. + 3: the A-operand layout of the tap contraction G[c][tap] = sum_p ds[c][p] plane[p + tap], whose B
-// operand is tap r of the plane at the lane's 4 pixels (rows 9 .. 15 zero), one accumulator tile per plane.
+// operand is tap r of the plane at the lane's 4 pixels (rows 9 .. 15 zero), one accumulator tile per plane.  The steps of the
+// contraction are rf_flca_adjoint.h's, as in flca_bwd_fused_kernel; the gate arithmetic (expf / tanhf) is this kernel's.
 template <bool CHROMA>
 __global__ void __launch_bounds__(256) pyr_spatial_bwd_vec_kernel(PyrSpArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 15, kq = lane >> 4;
-    const int slab = blockIdx.x, ti = blockIdx.y;
-    const int img = slab / a.per_image, sl = slab - img * a.per_image;
-    const int h = a.h, w = a.w, P = h * w, C = a.C;
-    const int n_lo = sl * a.slab_px, n_hi = (n_lo + a.slab_px < P) ? n_lo + a.slab_px : P;
-    const bool cvalid = 16 * ti + r < C;
-    const int c = cvalid ? 16 * ti + r : C - 1;
-    float wa[9], wb[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-        wa[t] = CHROMA ? a.w_a[c * 18 + t] : a.w_a[c * 9 + t];
-        wb[t] = CHROMA ? a.w_a[c * 18 + 9 + t] : a.w_b[c * 9 + t];
-    }
-    float g0, g1;
-    step_gates<CHROMA>(a, (size_t)img, g0, g1);
-    const size_t row = ((size_t)img * C + c) * P;
-    const float* dmr = a.dm + row;
-    const float* xr = a.x + row;
-    float* dxr = a.dx + row;
-    const float* gpl = a.planes + (size_t)img * a.plane_bstride;
+    const PyrSpLane<CHROMA> L(a, r);
+    const int h = L.h, w = L.w, P = L.P;
     const int tdy = r < 9 ? r / 3 - 1 : 0, tdx = r < 9 ? r % 3 - 1 : 0;      // this lane's tap
     f32x4 acc[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
     float sa = 0.f, sb = 0.f;
-    for (int n0 = n_lo + wave * 16; n0 < n_hi; n0 += 64) {
+    for (int n0 = L.n_lo + wave * 16; n0 < L.n_hi; n0 += 64) {
         const int nn = n0 + 4 * kq;
-        const bool ok = nn < n_hi;
-        const int n = ok ? nn : n_lo;
+        const bool ok = nn < L.n_hi;
+        const int n = ok ? nn : L.n_lo;
         const int y = n / w, x = n - y * w;
-        const float4 dm4 = ld4(dmr + n), x4 = ld4(xr + n), d4 = ld4(dxr + n);
+        const float4 dm4 = ld4(L.dmr + n), x4 = ld4(L.xr + n), d4 = ld4(L.dxr + n);
         float bv[2][4];
-        {
-            const int yy = y + tdy;
-            const bool rowok = ok && r < 9 && yy >= 0 && yy < h;
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const int xx = x + m + tdx;
-                const bool in = rowok && xx >= 0 && xx < w;
-                const size_t off = in ? (size_t)yy * w + xx : 0;
-#pragma unroll
-                for (int pl = 0; pl < 2; ++pl) { const float v = gpl[(size_t)pl * P + off]; bv[pl][m] = in ? v : 0.f; }
-            }
-        }
+        tap_operand<2>(L.gpl, P, h, w, y, x, r, tdy, tdx, ok, bv);
         float s_a[4] = {0.f, 0.f, 0.f, 0.f}, s_b[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int dy = 0; dy < 3; ++dy) {
             const int yy = y + dy - 1;
-            const bool rok = yy >= 0 && yy < h;
-            const size_t rowoff = (size_t)(rok ? yy : 0) * w + x;
             float nb[2][6];
-#pragma unroll
-            for (int pl = 0; pl < 2; ++pl) {
-                const float* prow = gpl + (size_t)pl * P + rowoff;
-                const float4 t = ld4(prow);
-                const float lft = prow[x > 0 ? -1 : 0], rgt = prow[x + 4 < w ? 4 : 0];
-                nb[pl][0] = (rok && x > 0) ? lft : 0.f;
-                nb[pl][1] = rok ? t.x : 0.f; nb[pl][2] = rok ? t.y : 0.f; nb[pl][3] = rok ? t.z : 0.f; nb[pl][4] = rok ? t.w : 0.f;
-                nb[pl][5] = (rok && x + 4 < w) ? rgt : 0.f;
-            }
+            neighbour_row<2>(L.gpl, P, w, x, yy, yy >= 0 && yy < h, nb);
 #pragma unroll
             for (int dx = 0; dx < 3; ++dx) {
-                const float k0 = wa[dy * 3 + dx], k1 = wb[dy * 3 + dx];
+                const float k0 = L.wa[dy * 3 + dx], k1 = L.wb[dy * 3 + dx];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     s_a[q] = fmaf(k0, nb[0][q + dx], s_a[q]);
@@ -213,16 +201,16 @@ __global__ void __launch_bounds__(256) pyr_spatial_bwd_vec_kernel(PyrSpArgs a) {
             }
         }
         const float dmv[4] = {dm4.x, dm4.y, dm4.z, dm4.w}, xv[4] = {x4.x, x4.y, x4.z, x4.w}, dv[4] = {d4.x, d4.y, d4.z, d4.w};
-        const float live = (ok && cvalid) ? 1.0f : 0.f;
+        const float live = (ok && L.cvalid) ? 1.0f : 0.f;
         float ds0[4], ds1[4], o[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const float dmq = live * dmv[q];
             float S;
-            gate_adjoint<CHROMA>(s_a[q], s_b[q], g0, g1, dmq * xv[q], S, ds0[q], ds1[q], sa, sb);
+            gate_adjoint<CHROMA>(s_a[q], s_b[q], L.g0, L.g1, dmq * xv[q], S, ds0[q], ds1[q], sa, sb);
             o[q] = fmaf(dmq, S, dv[q]);
         }
-        if (ok && cvalid) *reinterpret_cast<float4*>(dxr + n) = make_float4(o[0], o[1], o[2], o[3]);
+        if (ok && L.cvalid) *reinterpret_cast<float4*>(L.dxr + n) = make_float4(o[0], o[1], o[2], o[3]);
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
             acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ds0[m], bv[0][m], acc[0], 0, 0, 0);
@@ -230,24 +218,10 @@ __global__ void __launch_bounds__(256) pyr_spatial_bwd_vec_kernel(PyrSpArgs a) {
         }
     }
     __shared__ float red[4][16][17];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 4; ++q) red[wave][4 * kq + q][r] = acc[t][q];
-        __syncthreads();
-        const int i = threadIdx.x >> 4, jj = threadIdx.x & 15;
-        const int gi = 16 * ti + i;
-        if (gi < C && jj < 9) a.taps[tap_index<CHROMA>(a, slab, gi, t, jj)] = ((red[0][i][jj] + red[1][i][jj]) + red[2][i][jj]) + red[3][i][jj];
-    }
+    const int slab = L.slab;
+    fold_tap_tiles<2>(acc, red, wave, kq, r, L.ti, L.C, [=](int t, int gi, int jj) { return a.taps + tap_index<CHROMA>(a, slab, gi, t, jj); });
     __syncthreads();      // red is free again
-    float gs[2] = {sa, sb};
-    block_sums<2>(gs, &red[0][0][0]);
-    if (threadIdx.x == 0) {
-        float* o = a.gsum + (((size_t)sl * gridDim.y + ti) * (a.nslab / a.per_image) + img) * 2;
-        o[0] = gs[0];
-        o[1] = gs[1];
-    }
+    store_gate_sums(a, L.sl, L.ti, L.img, sa, sb, &red[0][0][0]);
 }
 
 // Any width.  Workgroup (slab, 16-channel tile); thread (r = tid >> 4, q = tid & 15) owns channel 16 ti + r and pixels
@@ -255,30 +229,13 @@ __global__ void __launch_bounds__(256) pyr_spatial_bwd_vec_kernel(PyrSpArgs a) {
 template <bool CHROMA>
 __global__ void __launch_bounds__(256) pyr_spatial_bwd_kernel(PyrSpArgs a) {
     const int r = threadIdx.x >> 4, q = threadIdx.x & 15;
-    const int slab = blockIdx.x, ti = blockIdx.y;
-    const int img = slab / a.per_image, sl = slab - img * a.per_image;
-    const int h = a.h, w = a.w, P = h * w, C = a.C;
-    const int n_lo = sl * a.slab_px, n_hi = (n_lo + a.slab_px < P) ? n_lo + a.slab_px : P;
-    const bool cvalid = 16 * ti + r < C;
-    const int c = cvalid ? 16 * ti + r : C - 1;
-    float wa[9], wb[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-        wa[t] = CHROMA ? a.w_a[c * 18 + t] : a.w_a[c * 9 + t];
-        wb[t] = CHROMA ? a.w_a[c * 18 + 9 + t] : a.w_b[c * 9 + t];
-    }
-    float g0, g1;
-    step_gates<CHROMA>(a, (size_t)img, g0, g1);
-    const size_t row = ((size_t)img * C + c) * P;
-    const float* dmr = a.dm + row;
-    const float* xr = a.x + row;
-    float* dxr = a.dx + row;
-    const float* gpl = a.planes + (size_t)img * a.plane_bstride;
+    const PyrSpLane<CHROMA> L(a, r);
+    const int h = L.h, w = L.w, P = L.P;
     float ta[9], tb[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t) { ta[t] = 0.f; tb[t] = 0.f; }
     float sa = 0.f, sb = 0.f;
-    for (int n = n_lo + q; n < n_hi; n += 16) {
+    for (int n = L.n_lo + q; n < L.n_hi; n += 16) {
         const int y = n / w, x = n - y * w;
         float nb[2][9];
         float s_a = 0.f, s_b = 0.f;
@@ -289,16 +246,16 @@ __global__ void __launch_bounds__(256) pyr_spatial_bwd_kernel(PyrSpArgs a) {
                 const int yy = y + dy - 1, xx = x + dx - 1;
                 const bool in = yy >= 0 && yy < h && xx >= 0 && xx < w;
                 const size_t off = in ? (size_t)yy * w + xx : 0;
-                const float v0 = gpl[off], v1 = gpl[(size_t)P + off];
+                const float v0 = L.gpl[off], v1 = L.gpl[(size_t)P + off];
                 nb[0][dy * 3 + dx] = in ? v0 : 0.f;
                 nb[1][dy * 3 + dx] = in ? v1 : 0.f;
-                s_a = fmaf(wa[dy * 3 + dx], nb[0][dy * 3 + dx], s_a);
-                s_b = fmaf(wb[dy * 3 + dx], nb[1][dy * 3 + dx], s_b);
+                s_a = fmaf(L.wa[dy * 3 + dx], nb[0][dy * 3 + dx], s_a);
+                s_b = fmaf(L.wb[dy * 3 + dx], nb[1][dy * 3 + dx], s_b);
             }
-        const float dmq = cvalid ? dmr[n] : 0.f;
+        const float dmq = L.cvalid ? L.dmr[n] : 0.f;
         float S, ds0, ds1;
-        gate_adjoint<CHROMA>(s_a, s_b, g0, g1, dmq * xr[n], S, ds0, ds1, sa, sb);
-        if (cvalid) dxr[n] = fmaf(dmq, S, dxr[n]);
+        gate_adjoint<CHROMA>(s_a, s_b, L.g0, L.g1, dmq * L.xr[n], S, ds0, ds1, sa, sb);
+        if (L.cvalid) L.dxr[n] = fmaf(dmq, S, L.dxr[n]);
 #pragma unroll
         for (int t = 0; t < 9; ++t) { ta[t] = fmaf(ds0, nb[0][t], ta[t]); tb[t] = fmaf(ds1, nb[1][t], tb[t]); }
     }
@@ -307,21 +264,15 @@ __global__ void __launch_bounds__(256) pyr_spatial_bwd_kernel(PyrSpArgs a) {
 #pragma unroll
         for (int o = 8; o > 0; o >>= 1) { ta[t] += __shfl_xor(ta[t], o, 64); tb[t] += __shfl_xor(tb[t], o, 64); }
     }
-    if (q == 0 && cvalid) {
+    if (q == 0 && L.cvalid) {
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
-            a.taps[tap_index<CHROMA>(a, slab, c, 0, t)] = ta[t];
-            a.taps[tap_index<CHROMA>(a, slab, c, 1, t)] = tb[t];
+            a.taps[tap_index<CHROMA>(a, L.slab, L.c, 0, t)] = ta[t];
+            a.taps[tap_index<CHROMA>(a, L.slab, L.c, 1, t)] = tb[t];
         }
     }
     __shared__ float red[8];
-    float gs[2] = {sa, sb};
-    block_sums<2>(gs, red);
-    if (threadIdx.x == 0) {
-        float* o = a.gsum + (((size_t)sl * gridDim.y + ti) * (a.nslab / a.per_image) + img) * 2;
-        o[0] = gs[0];
-        o[1] = gs[1];
-    }
+    store_gate_sums(a, L.sl, L.ti, L.img, sa, sb, red);
 }
 
 // The gate sums of every image, dg [B][2] = (sum dS a_l, sum dS a_h) or (sum dS a_c, -), through the gate head's sigmoid:
@@ -455,7 +406,7 @@ void pyr_slabs(int B, int P, int nti, int* slab_px, int* per_image) {
 // The workspace as float offsets: the one layout behind the size query and the run.
 struct PyrBwdPlan {
     PyrFwdPlan f;                        // guidance, one step's m, t, r / dr, the res_proj packs, pooling sums, ch
-    int dnblk, hid, nti;                 // pyr_dch_kernel's pixel blocks; squeeze-excite hidden width; 16-channel tiles
+    int dnblk, hid, nti;                 // flca_dch_kernel's pixel blocks (pyr_dch_nblk); squeeze-excite hidden width; 16-channel tiles
     int slab_px, per_image, nslab;       // pixel slabs of pyr_spatial_bwd (pyr_slabs)
     size_t xs;                           // [L + 1][B][C][P]   x_1 .. x_{L+1}  (x_0 is feat)
     size_t d;                            // [B][C][P]          dpre; dm lands in f.t, dead by then
@@ -544,8 +495,7 @@ int run_pyr_backward(const PyrBwdPlan& p, const float* feat, const float* packed
     // squeeze-excite: dch -> the MLP adjoint per image -> dmean / P and the four gradients; dx = dz ch + dmean / P
     {
         ProfScope prof(st, "pyr_dch_kernel", 2.0 * el, 8.0 * el);
-        pyr_dch_kernel<<<dim3((unsigned)p.dnblk, (unsigned)C, (unsigned)B), 256, 0, st>>>(dz, x_next[levels], ws + p.dch_part, C, P, p.dnblk);
-        RF_TRY(check_launch("pyr_dch"));
+        RF_TRY(launch_flca_dch(dz, (int64_t)C * P, x_next[levels], ws + p.dch_part, p.dnblk, B, C, P, st));
     }
     RF_TRY(launch_pyr_se(ws + p.f.pool, p.f.nblk, P, prm.se, ch, ws + p.dch_part, p.dnblk, dmP, contrib, B, C, st));
     const size_t n1 = (size_t)p.hid * C;

@@ -28,8 +28,6 @@ namespace rf {
 
 namespace {
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-
 // ---------------------------------------------------------------------------------------------
 // gram2.  Workgroup = (slab of pixels of one image, tile ti of 16 A rows, group tj of TJ*16 B rows).  Two forms: NTAP = 1, no
 // shift, TJ = 4 or 2 B tiles per workgroup; NTAP = 9: the nine taps of a 3x3 window at once, TJ = 1.

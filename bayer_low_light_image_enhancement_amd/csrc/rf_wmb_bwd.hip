@@ -32,7 +32,6 @@ namespace {
 
 constexpr int kBlk = 256;
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ float2 ld2(const float* p) { return *reinterpret_cast<const float2*>(p); }
 
 // iwt_init (blocks.py:123-134) of one band pixel, wmb_back_kernel's expression order: r00, r01 the upper, r10, r11 the lower row
