@@ -90,6 +90,7 @@ SIGNATURES = {
     "rf_convT2x2_scratch_bytes": (_i, [_i, _i, _psz]),
     "rf_convT2x2": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "rf_conv1x1_plan": (_i, [_i] * 10 + [C.c_char_p, _sz, C.POINTER(_i), C.POINTER(_i), _psz, C.POINTER(_i)]),
+    "rf_conv1x1_dw3_plan": (_i, [_i] * 5 + [C.c_char_p, _sz, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "rf_chan_attn_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _psz]),
     "rf_chan_attn": (_i, [_vp] * 10 + [_i] * 5 + [_vp]),
     "rf_transformer_block_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _i, _psz]),

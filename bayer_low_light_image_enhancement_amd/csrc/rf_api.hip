@@ -284,6 +284,21 @@ int rf_conv1x1_plan(int B, int C1, int C2, int Cout, int h, int w, int ln, int r
     return RF_OK;
 }
 
+int rf_conv1x1_dw3_plan(int B, int C, int hc, int h, int w, char* key, size_t key_len, int* grid, int* block, int* on_the_fly) {
+    RF_CHECK_ARG(key && key_len > 0 && grid && block && on_the_fly && C > 0 && hc > 0 && h > 0 && w > 0, "conv1x1_dw3_plan: bad arguments");
+    alignas(16) static float any[4];      // stands for every operand: a plan looks at presence and alignment only
+    Conv1x1Args a = conv1x1_api_args(any, any, any, nullptr, any, any, nullptr, nullptr, nullptr, B, C, C, C, h, w);
+    a.x3 = any; a.C3 = hc; a.x3_bstride = (int64_t)hc * h * w;
+    const Conv1x1Dw3 d{any, any, h, w};
+    Conv1x1Plan p;
+    RF_TRY(plan_conv1x1(a, &p, &d));
+    snprintf(key, key_len, "%s", p.key);
+    grid[0] = (int)p.grid[0]; grid[1] = (int)p.grid[1]; grid[2] = (int)p.grid[2];
+    *block = (int)p.block;
+    *on_the_fly = p.dw3;
+    return RF_OK;
+}
+
 int rf_fft_plan(int planes, int h, int w, int out[10]) {
     RF_CHECK_ARG(out, "fft_plan: bad arguments");
     FftPlan p;

@@ -148,6 +148,8 @@ int run_transformer_ffn(const TbParams& p, float* out, float* ws, const TbBufOff
             f1.x1 = bufB; f1.ln_w = nullptr; f1.ln_b = nullptr;
         }
         RF_TRY(launch_conv1x1(f1, st));
+        RF_CHECK_ARG(!p.defer_dw || p.defer_pw2, "transformer: the depthwise convolution is deferred only together with pointwise2");
+        if (p.defer_dw) return RF_OK;
 
         DwConvArgs d2{};
         d2.x = bufA; d2.x_bstride = (int64_t)hc * Pn; d2.out = bufB; d2.out_bstride = (int64_t)hc * Pn;

@@ -225,9 +225,23 @@ struct Conv1x1Plan {
     int karg[2];           // the kernel's integer arguments: (ntw, ngroups) resident-input | (ngroups) streaming, b3 | (tpw) b3_ln
     double flops, bytes;   // of the whole launch, for ProfScope
     bool ln_single_pass;   // the LayerNorm prologue (if any) reads x once: see conv1x1_ln_single_pass
+    bool dw3;              // the form whose third source is produced on the fly (rf_gemm1x1_dw3.hip): `inst` is unset
 };
-int plan_conv1x1(const Conv1x1Args& a, Conv1x1Plan* p);    // RF_E_INVALID (and the error text) for arguments launch_conv1x1 refuses
-int launch_conv1x1(const Conv1x1Args& a, hipStream_t st);
+// Optional descriptor of source 3: x3 holds the tensor BEFORE a depthwise 3x3 (padding 1) + GELU, and the GEMM applies both while
+// it reads (conv1x1_b3_dw3_kernel; the composed stage tail of levels 1-3, whose hidden tensor then crosses HBM twice instead of
+// four times).  It travels beside Conv1x1Args and not inside it: that struct is the by-value parameter of every 1x1 kernel, and
+// a member more moves the kernels' trailing arguments, i.e. changes the code of all of them.
+struct Conv1x1Dw3 {
+    const float* w;        // depthwise weights [C3][9]
+    const float* bias;     // [C3] or nullptr
+    int h, w_;             // the image: h * w_ == P
+};
+constexpr int kDw3MaxC3 = 256;      // depthwise weights and bias of all C3 channels are staged in LDS
+// RF_E_INVALID (and the error text) for arguments launch_conv1x1 refuses; `dw3` is honoured only where the plan takes the new
+// form (p->dw3) -- everywhere else x3 must hold the finished source, and the caller asks the plan which it is
+int plan_conv1x1(const Conv1x1Args& a, Conv1x1Plan* p, const Conv1x1Dw3* dw3 = nullptr);
+int launch_conv1x1(const Conv1x1Args& a, hipStream_t st, const Conv1x1Dw3* dw3 = nullptr);
+int launch_conv1x1_b3_dw3(const Conv1x1Args& a, const Conv1x1Dw3& d, const Conv1x1Plan& p, hipStream_t st);      // rf_gemm1x1_dw3.hip; called by launch_conv1x1
 // one dense NCHW source and a dense destination (batch strides C1 P / Cout P); everything else zero
 inline Conv1x1Args conv1x1_dense(const float* x1, int C1, const float* wp, const void* wp3, const float* bias, float* out, int Cout, int B, int P, int w) {
     Conv1x1Args a{};
@@ -428,6 +442,9 @@ struct TbParams {
     // hidden tensor in bufB, `out` is not written; the caller's channel_reduce GEMM applies pointwise2 (transformer_ffn_is_fused
     // tells it which path runs)
     bool defer_pw2 = false;
+    // ... and stop one launch earlier still, after pointwise1: the hidden tensor stays in bufA before its depthwise 3x3 + GELU, which
+    // the caller's GEMM applies as it reads (Conv1x1Dw3; the caller has asked plan_conv1x1).  Only with defer_pw2.
+    bool defer_dw = false;
     // fused stage tail: on the fused FFN path (C = 32) the kernel applies the caller's channel_reduce too, `out` receives
     // channel_reduce(cat(tail.xs, block output)); tail_bias = the composed bias
     FfnTail tail{nullptr, nullptr, 0};

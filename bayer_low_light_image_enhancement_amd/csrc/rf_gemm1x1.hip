@@ -27,7 +27,9 @@
 //   3. conv1x1_b3_kernel      b3 weights present, K >= 128, sources cut at multiples of 32 channels (up to three): the
 //                             streaming form on the bf16 pipe, accumulators resident, K in blocks of 32; LayerNorm prologue
 //                             (K = 512) at 4 tiles per workgroup only; without LayerNorm two output groups may share a
-//                             512-thread workgroup and the x it fetches (PAIR) where the launch still fills the CUs.
+//                             512-thread workgroup and the x it fetches (PAIR) where the launch still fills the CUs.  With a
+//                             Conv1x1Dw3 descriptor, one output group of four tiles and a large enough launch, the form whose
+//                             third source is stencilled on the fly (conv1x1_b3_dw3_kernel, rf_gemm1x1_dw3.hip).
 //   4. conv1x1_res_kernel     K <= 64, or K <= 128 without LayerNorm and residual (U-Net levels 0-1, HBM-bound): persistent
 //                             workgroups; a wave keeps its whole [K x 64 px] input tile in registers, computes exact two-pass
 //                             LayerNorm statistics on it, then sweeps ALL output-channel groups over the resident tile (x is
@@ -42,7 +44,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
-#include "rf_common.h"
+#include "rf_gemm1x1_tile.h"   // ldv, b3_split_pair, epilogue, stage_bias, b3_load_x_block: shared with rf_gemm1x1_dw3.hip
 
 namespace rf {
 
@@ -55,10 +57,6 @@ __device__ __forceinline__ const float* kset_base(const Conv1x1Args& a, int b, i
     return src + off;
 }
 
-__device__ __forceinline__ float4 ldv(const float* __restrict__ base, unsigned off) {
-    return *reinterpret_cast<const float4*>(base + off);
-}
-
 // ---- pieces the kernels share (operands by value or by reference-to-array: see the note at b3_load_x_block's call site)
 template <int NCO>
 __device__ __forceinline__ void zero_acc(f32x4 (&acc)[NCO][4]) {
@@ -66,98 +64,6 @@ __device__ __forceinline__ void zero_acc(f32x4 (&acc)[NCO][4]) {
     for (int t = 0; t < NCO; ++t)
 #pragma unroll
         for (int g = 0; g < 4; ++g) acc[t][g] = (f32x4){0.f, 0.f, 0.f, 0.f};
-}
-
-// channel pair (2 hp, 2 hp + 1) of pixel g -> dword hp of the three bf16 pieces of that pixel's B operand, bp[g][piece][hp]
-template <class BP>
-__device__ __forceinline__ void b3_split_pair(float xa, float xb, BP& bp, int g, int hp) {
-    unsigned a0, a1, a2, b0, b1, b2;
-    b3_split(xa, a0, a1, a2);
-    b3_split(xb, b0, b1, b2);
-    bp[g][0][hp] = b3_pack(a0, b0);
-    bp[g][1][hp] = b3_pack(a1, b1);
-    bp[g][2][hp] = b3_pack(a2, b2);
-}
-
-// Store NCO accumulator tiles.  bias_l: LDS bias of the first tile; res: prefetched residual rows
-// (RES) laid out [tile][r] as float4.
-template <int NCO, bool RES>
-__device__ __forceinline__ void epilogue(const Conv1x1Args& a, f32x4 (&acc)[NCO][4], int tfirst, int ntiles,
-                                         const float* __restrict__ bias_l, const float4* res,
-                                         int b, int p0, int kq, bool live) {
-    const int P = a.P;
-    float* outb = a.out + (size_t)b * a.out_bstride;
-    if (a.mode == 0) {
-        const unsigned voff = (unsigned)(4 * kq) * (unsigned)P + (unsigned)p0;   // channel 4kq of a tile
-#pragma unroll
-        for (int t = 0; t < NCO; ++t) {
-            if (t >= ntiles) break;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int cu = 16 * (tfirst + t) + r;                  // wave-uniform part of the channel
-                const float bs = bias_l[16 * t + 4 * kq + r];
-                float v[4] = {acc[t][0][r] + bs, acc[t][1][r] + bs, acc[t][2][r] + bs, acc[t][3][r] + bs};
-                if constexpr (RES) {
-                    const float4 rv = res[t * 4 + r];
-                    v[0] += rv.x; v[1] += rv.y; v[2] += rv.z; v[3] += rv.w;
-                }
-                if (a.act == 1 || a.act == 3) {
-                    const float slope = a.act == 1 ? 0.2f : 0.1f;
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) v[g] = v[g] > 0.f ? v[g] : slope * v[g];
-                } else if (a.act == 2) {
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) v[g] = fmaxf(v[g], 0.f);
-                } else if (a.act == 4) {
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) v[g] = fminf(fmaxf(v[g], 0.f), 1e4f);
-                }
-                if (live && cu + 4 * kq < a.Cout)
-                    *reinterpret_cast<float4*>(outb + (size_t)cu * P + voff) = make_float4(v[0], v[1], v[2], v[3]);
-            }
-        }
-    } else {
-        // ConvTranspose2d(k=2, s=2): GEMM row 4*o + 2*i + jj is output channel o at sub-position
-        // (i, jj); the lane holds the whole 2x2 patch of each of its pixels for channel o.  The width only has to be
-        // even: pixels (p0, p0+1) and (p0+2, p0+3) are each inside one row (p0 % 4 == 0), so every pixel PAIR is one
-        // aligned 16-byte store per output row (at w = 266, level 3 of a 1424x2128 frame, the two pairs of a lane may
-        // sit in different rows).
-        const int w = a.w, w2 = 2 * a.w;
-        const int ya = p0 / w, xa = p0 - ya * w;
-        const int yb = (p0 + 2) / w, xb = (p0 + 2) - yb * w;
-#pragma unroll
-        for (int t = 0; t < NCO; ++t) {
-            if (t >= ntiles) break;
-            const int co = 16 * (tfirst + t) + 4 * kq;
-            const int o = co >> 2;
-            const float bs = bias_l[4 * t + kq];      // bias per real output channel o (staged as [NT*4])
-            float* op = outb + (size_t)o * 4 * P;
-            if (live && co < a.Cout) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    *reinterpret_cast<float4*>(op + (size_t)(2 * ya + i) * w2 + 2 * xa) =
-                        make_float4(acc[t][0][2 * i] + bs, acc[t][0][2 * i + 1] + bs, acc[t][1][2 * i] + bs, acc[t][1][2 * i + 1] + bs);
-                    *reinterpret_cast<float4*>(op + (size_t)(2 * yb + i) * w2 + 2 * xb) =
-                        make_float4(acc[t][2][2 * i] + bs, acc[t][2][2 * i + 1] + bs, acc[t][3][2 * i] + bs, acc[t][3][2 * i + 1] + bs);
-                }
-            }
-        }
-    }
-}
-
-// bias (or zeros) for tiles [tbeg, tbeg + tpad) into LDS; mode 1 stores one value per output channel o
-__device__ __forceinline__ void stage_bias(const Conv1x1Args& a, float* bias_l, int tbeg, int tpad, int tid) {
-    if (a.mode == 0) {
-        for (int i = tid; i < tpad * 16; i += 256) {
-            const int co = 16 * tbeg + i;
-            bias_l[i] = (a.bias && co < a.Cout) ? a.bias[co] : 0.f;
-        }
-    } else {
-        for (int i = tid; i < tpad * 4; i += 256) {
-            const int o = 4 * tbeg + i;
-            bias_l[i] = (a.bias && 4 * o < a.Cout) ? a.bias[o] : 0.f;
-        }
-    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -474,22 +380,6 @@ __global__ void __launch_bounds__(256, 2) conv1x1_stream_kernel(Conv1x1Args a, i
 // 24 * NCO MFMAs of 17 cycles (f32 form: 32 * NCO MFMAs of 33 cycles).  The next block's x is loaded into the registers
 // the split has just vacated, its weights go registers -> LDS behind the MFMAs; one barrier per block.
 // ---------------------------------------------------------------------------------------------
-// channels 32c + 8kq + i (i = 0..7) of K block c, 4 pixels each: the block lies in ONE of up to three sources (launch_conv1x1
-// checks that they are cut at multiples of 32 channels); selects, not branches (see kset_base)
-__device__ __forceinline__ void b3_load_x_block(float4 (&xr)[8], const float* xb1, const float* xb2, const float* xb3, int C1, int C2, int C3,
-                                                int c, int kq, unsigned P, unsigned pl) {
-    const int cb = 32 * c;
-    const bool first = cb < C1, third = cb >= C1 + C2;
-    const float* src = first ? xb1 : third ? xb3 : xb2;
-    const int cloc = first ? cb : third ? cb - C1 - C2 : cb - C1, cmax = (first ? C1 : third ? C3 : C2) - 1;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        int ch = cloc + 8 * kq + i;
-        ch = ch < cmax ? ch : cmax;
-        xr[i] = ldv(src, (unsigned)ch * P + pl);
-    }
-}
-
 // PAIR (launch_conv1x1: no LayerNorm, more than one output group, a launch that still gives every CU a workgroup): the output
 // groups of a pixel tile share the x they fetch.  A workgroup is 512 threads = two halves of four waves; half h runs output group
 // 2 gp + h of the SAME 256 pixels with its own bias and double-buffered weight slice, so wave w and wave w + 4 issue the same x
@@ -1012,12 +902,14 @@ static bool b3_supported(const Conv1x1Args& a) {
 // THE selection rule (summary at the top of this file): argument checks, then the family in the order scalar, b3_ln, b3, res,
 // stream, and inside a family the template arguments and the grid.  No HIP call, no launch; a plan exists only for arguments
 // launch_conv1x1 accepts.
-int plan_conv1x1(const Conv1x1Args& a, Conv1x1Plan* p) {
+int plan_conv1x1(const Conv1x1Args& a, Conv1x1Plan* p, const Conv1x1Dw3* dw3) {
     bool b3_ok = a.wp3 != nullptr;
     int force_pair = -1;      // -1: by launch size
-#ifdef RF_DIAG   // diagnostic build only (build.py --diag): RF_NO_B3 forces the f32 MFMA kernels; RF_B3_PAIR=1 takes the paired form at any launch size, =0 never
+    int force_dw3 = -1;
+#ifdef RF_DIAG   // diagnostic build only (build.py --diag): RF_NO_B3 forces the f32 MFMA kernels; RF_B3_PAIR=1 takes the paired form at any launch size, =0 never; RF_TAIL_DW likewise for the on-the-fly third source
     if (getenv("RF_NO_B3")) b3_ok = false;
     if (const char* e = getenv("RF_B3_PAIR")) force_pair = e[0] != '0';
+    if (const char* e = getenv("RF_TAIL_DW")) force_dw3 = e[0] != '0';
 #endif
     RF_CHECK_ARG(a.B > 0 && a.P > 0 && a.C1 > 0 && a.C2 >= 0 && a.Cout > 0, "conv1x1: bad sizes B=%d P=%d C1=%d C2=%d Cout=%d",
                  a.B, a.P, a.C1, a.C2, a.Cout);
@@ -1077,6 +969,18 @@ int plan_conv1x1(const Conv1x1Args& a, Conv1x1Plan* p) {
         // 6 tiles per workgroup where that divides the output evenly; never with the LayerNorm prologue (that instantiation
         // needs 2 registers more than the 256 a wave has at two waves per SIMD)
         int nco = (!ln && (NT % 6 == 0 || (NT % 4 != 0 && NT > 8))) ? 6 : 4;
+        // Third source on the fly (conv1x1_b3_dw3_kernel): ONE output group of four tiles (two groups would both repeat the
+        // stencil), workgroups of 4 rows x 64 columns that tile the image exactly, and a launch of at least 512 such units: a
+        // smaller one leaves CUs idle either way and has no HBM time to save (RF_TAIL_DW=1: any size the kernel supports).
+        if (dw3 && force_dw3 != 0 && !ln && !a.res && a.mode == 0 && nco == 4 && NT == 4 && a.Cout == 64 && a.C3 > 0 && a.C3 <= kDw3MaxC3 &&
+            a.C1 % 32 == 0 && a.C2 % 32 == 0 && a.C3 % 32 == 0 && dw3->w && dw3->h > 0 && dw3->w_ > 0 && (long)dw3->h * dw3->w_ == a.P &&
+            dw3->w_ % 64 == 0 && dw3->h % 4 == 0 && (double)a.C3 * a.P < 4.0e9 && (force_dw3 == 1 || units >= 512)) {
+            p->dw3 = true;
+            p->inst = -1; p->key = "conv1x1_b3_kernel<4, false, dw3>"; p->block = 256;
+            p->grid[0] = (unsigned)ptiles;
+            p->flops += 18.0 * a.C3 * px;      // the stencil, counted as launch_dwconv3x3 counts it; bytes: every source once, as above
+            return RF_OK;
+        }
         // Paired form (two output groups per 512-thread workgroup, the pairs of a pixel tile on one XCD): x is fetched once per
         // pixel tile instead of once per group.  It halves the workgroup count, so it is taken where every CU still gets one;
         // smaller launches keep the unpaired form and the rule below.
@@ -1131,12 +1035,15 @@ bool conv1x1_ln_single_pass(const Conv1x1Args& a) {
     return plan_conv1x1(a, &p) != RF_OK || p.ln_single_pass;      // arguments without a plan: launch_conv1x1 reports them
 }
 
-int launch_conv1x1(const Conv1x1Args& a, hipStream_t st) {
+int launch_conv1x1(const Conv1x1Args& a, hipStream_t st, const Conv1x1Dw3* dw3) {
     Conv1x1Plan p;
-    RF_TRY(plan_conv1x1(a, &p));
+    RF_TRY(plan_conv1x1(a, &p, dw3));
+    // no other kernel applies the stencil: the caller asks the plan first and runs launch_dwconv3x3 itself where this is false
+    RF_CHECK_ARG(!dw3 || p.dw3, "conv1x1: no kernel produces source 3 on the fly for this shape (K = %d, Cout = %d, P = %d)", a.C1 + a.C2 + a.C3, a.Cout, a.P);
     {
         ProfScope prof(st, p.key, p.flops, p.bytes);
-        kInst[p.inst].launch(a, p, st);
+        if (p.dw3) RF_TRY(launch_conv1x1_b3_dw3(a, *dw3, p, st));
+        else kInst[p.inst].launch(a, p, st);
     }
     return check_launch("conv1x1");
 }

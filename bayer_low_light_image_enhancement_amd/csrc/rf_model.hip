@@ -293,6 +293,21 @@ int run_stage(rf_handle* h, int i, const float* in, float* out, float* ws, const
     if (c.fuse_tail) { c.tp.tail.xs = c.xs; c.tp.tail.wp = c.fold_wp; c.tp.tail_bias = c.composed + (size_t)C * hc; }
     c.r = conv1x1_dense(c.xs, C, nullptr, nullptr, h->prm(x.cr_b), c.crb, C, B, Pn, ww);
     c.r.x2 = c.trans; c.r.C2 = C; c.r.x2_bstride = (int64_t)C * Pn;
+    // Composed tail with the depthwise 3x3 + GELU inside the GEMM (conv1x1_b3_dw3_kernel; cfg2: level 1): where plan_conv1x1 takes
+    // that form for the GEMM of `compose`, the block stops after pointwise1 and the GEMM reads the hidden tensor from bufA.  The
+    // plan looks at shapes, presence and alignment only, so the weights the branch has yet to name stand in as the packed buffer.
+    const Conv1x1Dw3 dw3{c.tp.dw_w, c.tp.dw_b, hh, ww};
+    bool tail_dw = false;
+    if (c.compose && !vt.branch_after) {      // (a branch that follows the block borrows bufA)
+        Conv1x1Args probe = c.r;
+        probe.x2 = ws + p.x1;
+        probe.x3 = ws + p.bufA; probe.C3 = hc; probe.x3_bstride = (int64_t)hc * Pn;
+        probe.wp3 = h->packed;
+        Conv1x1Plan pl;
+        RF_TRY(plan_conv1x1(probe, &pl, &dw3));
+        tail_dw = pl.dw3;
+    }
+    c.tp.defer_dw = tail_dw;
 
     // the branch is launched first (on the branch stream when there is one), the block beside it; a branch that borrows bufA
     // follows the block on the same stream instead
@@ -318,10 +333,10 @@ int run_stage(rf_handle* h, int i, const float* in, float* out, float* ws, const
     if (c.compose) {
         c.r.wp = nullptr;
         c.r.x2 = ws + p.x1;
-        c.r.x3 = ws + p.bufB; c.r.C3 = hc; c.r.x3_bstride = (int64_t)hc * Pn;
+        c.r.x3 = ws + (tail_dw ? p.bufA : p.bufB); c.r.C3 = hc; c.r.x3_bstride = (int64_t)hc * Pn;
         c.r.bias = c.composed + (size_t)C * hc;
     }
-    if (!c.fuse_tail) RF_TRY(launch_conv1x1(c.r, st));
+    if (!c.fuse_tail) RF_TRY(launch_conv1x1(c.r, st, tail_dw ? &dw3 : nullptr));
 
     Conv3x3Args co = conv3x3_dense(c.crb, h->pk(x.out_w), h->prm(x.out_b), out, B, C, C, hh, ww, 1);
     if (p.ks_floats) { co.ks_scratch = ws + p.ks; co.ks_floats = p.ks_floats; }

@@ -307,6 +307,11 @@ int rf_convT2x2(const float* in, float* out, const float* weight, const float* b
  * input once (the schedules run LayerNorm as its own pass where it would not). */
 int rf_conv1x1_plan(int B, int C1, int C2, int Cout, int h, int w, int ln, int res, int transposed, int b3_weights,
                     char* key, size_t key_len, int* grid, int* block, size_t* lds_bytes, int* ln_single_pass);
+/* The same for the GEMM that closes a Conv_Transformer stage where pointwise2 is composed into channel_reduce: three sources
+ * [xs (C) ; x1 (C) ; hidden (hc)] -> C channels of B images of h x w, asked WITH the descriptor that lets the GEMM apply the FFN's
+ * depthwise 3x3 + GELU to the hidden source as it reads.  *on_the_fly: the plan takes that form (the stage then launches no
+ * depthwise convolution); otherwise key / grid / block are those of the GEMM over the finished hidden tensor. */
+int rf_conv1x1_dw3_plan(int B, int C, int hc, int h, int w, char* key, size_t key_len, int* grid, int* block, int* on_the_fly);
 /* Attention.forward: FrequencyawareLumaChromaAttentionRAWFormer.py:212-235.
  * Takes the 6 raw parameter tensors; scratch from rf_chan_attn_scratch_bytes. */
 int rf_chan_attn_scratch_bytes(int B, int C, int heads, int h, int w, size_t* bytes);

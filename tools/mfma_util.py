@@ -27,6 +27,7 @@ def main():
         for row in csv.DictReader(open(f)):
             k = re.sub(r"\(.*", "", row["Kernel_Name"].replace("(anonymous namespace)::", "").replace("void rf::", "").replace("void ", "").replace("rf::", ""))
             k = k.replace("attn_front_tall_kernel<", "attn_front_kernel<")      # the 12-row form files under the library's profiler key (launch_attn_front)
+            k = k.replace("conv1x1_b3_dw3_kernel<4>", "conv1x1_b3_kernel<4, false, dw3>")      # likewise (plan_conv1x1)
             if k.startswith(("__amd", "at::", "void at::")):
                 continue
             a = acc[k][row["Counter_Name"]]
