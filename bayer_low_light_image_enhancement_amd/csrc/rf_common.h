@@ -55,7 +55,8 @@ __device__ __forceinline__ float gelu_fast(float v) {
     const float h = 0.5f * v;
     return h + fmaf(-fabsf(h), q, fabsf(h));
 }
-// the accurate sigmoid (expf) of the gradient kernels and the squeeze-excite gates; the forward's spatial gates use fast forms of their own
+// the accurate sigmoid (expf) of the gradient kernels and the squeeze-excite gates; the forward's spatial gates use fast_sigmoid /
+// fast_tanh (rf_guidance.h)
 __device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }   // p 16-byte aligned
 
@@ -507,6 +508,7 @@ int launch_tc_spatial(const float* feat, float* xs, const float* guide, const fl
 int launch_tc_residual(const float* xs, const float* r, float* x2, float* partial, int B, int C, int h, int w, hipStream_t st);
 int launch_tc_color_head(float* x, const float* const* prm, int B, size_t P, hipStream_t st);
 int launch_tc_pyramid(const float* src, float* ll, float* mag, int B, int hs, int ws, hipStream_t st);
+int check_gate_shape(const char* who, int B, int C, int h, int w);   // the shape checks the rf_tc_* and rf_ml_* entry points share
 
 // ---- multi-level FLCA RawFormer extras (rf_multilvl.hip): guidance pyramid, per-stage planes and pooled means, the gated
 // modulation of one residual step (step = pyramid level, or `levels` for the chroma form), the output corrections
@@ -652,6 +654,7 @@ int launch_guidance_base(const float* in, int mosaic, int clamp_in, float* scrat
                          void (*allreduce)(void*, float*, size_t, int, void*) = nullptr, void* allreduce_user = nullptr);
 int launch_guidance_level(const float* scratch, float* guide, int B, int H, int W, int hf, int wf, hipStream_t st);
 void guidance_planes(float* scratch, int B, int H, int W, float** y, float** cr, float** cb, float** ll, float** mag);
+void launch_guide_init(int* amax, int B, hipStream_t st);   // amax[0 .. B) = -inf: before the first block_max_atomic (rf_guidance.h)
 struct FlcaSpatialArgs {
     const float* feat; float* xs; const float* guide;   // feat/xs [B][C][P], guide [B][4][h][w]
     const float* w_low; const float* w_high; const float* w_chr;   // [C][1][3][3], [C][1][3][3], [C][2][3][3]

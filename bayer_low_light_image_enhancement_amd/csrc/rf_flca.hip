@@ -8,6 +8,7 @@
 //                   channel_reduce 1x1:  W_cr [x*ch ; trans] = [W_a diag(ch) | W_b] [x ; trans]
 #include <type_traits>
 #include "rf_flca_adjoint.h"
+#include "rf_guidance.h"
 
 namespace rf {
 
@@ -38,21 +39,11 @@ void guidance_planes(float* scratch, int B, int H, int W, float** y, float** cr,
     *y = g.y; *cr = g.cr; *cb = g.cb; *ll = g.ll; *mag = g.mag;
 }
 
-__device__ __forceinline__ void atomic_max_float(int* addr, float v) {
-    if (v >= 0.f) atomicMax(addr, __float_as_int(v));
-    else atomicMin(reinterpret_cast<unsigned int*>(addr), __float_as_uint(v));
-}
-
-__device__ __forceinline__ float packed_at(const float* in, int mosaic, int clamp_in, size_t b, int ch, int y, int x, int H, int W) {
-    float v = mosaic ? in[(b * 2 * H + 2 * y + (ch >> 1)) * (size_t)(2 * W) + 2 * x + (ch & 1)]
-                     : in[((b * 4 + ch) * H + y) * (size_t)W + x];
-    return clamp_in ? fminf(fmaxf(v, 0.f), 1.f) : v;
-}
-
 __global__ void guide_init_kernel(int* amax, int B) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < B) amax[i] = (int)0xff800000u;   // -inf
 }
+void launch_guide_init(int* amax, int B, hipStream_t st) { guide_init_kernel<<<cdiv(B, 256), 256, 0, st>>>(amax, B); }
 
 // y_raw = 0.299 R + 0.587 * 0.5 (G1 + G2) + 0.114 B and its per-image maximum
 __global__ void __launch_bounds__(256) guide_luma_kernel(const float* __restrict__ in, int mosaic, int clamp_in,
@@ -69,15 +60,7 @@ __global__ void __launch_bounds__(256) guide_luma_kernel(const float* __restrict
         yraw[b * hw + p] = v;
         m = fmaxf(m, v);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    __shared__ float wm[4];
-    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {   // one atomic per workgroup: all of an image's atomics hit one address
-        m = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
-        if (m > -INFINITY) atomic_max_float(amax + b, m);
-    }
+    block_max_atomic(m, amax + b);
 }
 
 // normalise luma, chroma differences, Haar LL / high-band magnitude (one thread per 2x2 block)
@@ -101,12 +84,7 @@ __global__ void __launch_bounds__(256) guide_haar_kernel(const float* __restrict
             g.cb[b * hw + p] = packed_at(in, mosaic, clamp_in, b, 3, y, x, H, W) - yn;
             yv[t] = yn;
         }
-        const float ll = (yv[0] + yv[1] + yv[2] + yv[3]) * 0.5f;
-        const float lh = (yv[0] - yv[1] + yv[2] - yv[3]) * 0.5f;
-        const float hl = (yv[0] + yv[1] - yv[2] - yv[3]) * 0.5f;
-        const float hh = (yv[0] - yv[1] - yv[2] + yv[3]) * 0.5f;
-        g.ll[b * hw4 + q] = ll;
-        g.mag[b * hw4 + q] = sqrtf(lh * lh + hl * hl + hh * hh + 1e-8f);
+        haar_ll_mag(yv, g.ll[b * hw4 + q], g.mag[b * hw4 + q]);
     }
 }
 
@@ -115,7 +93,7 @@ int launch_guidance_base(const float* in, int mosaic, int clamp_in, float* scrat
     RF_CHECK_ARG(H % 2 == 0 && W % 2 == 0 && B <= 65535, "guidance: H=%d W=%d must be even", H, W);
     const GuideLayout g = guide_layout(scratch, B, H, W);
     ProfScope prof(st, "guidance_base(3 kernels)", 0.0, 4.0 * B * H * W * (4 + 1 + 1 + 4 + 3.5));
-    guide_init_kernel<<<cdiv(B, 256), 256, 0, st>>>(g.amax, B);
+    launch_guide_init(g.amax, B, st);
     const size_t hw = (size_t)H * W;
     int gx = (int)((hw + 255) / 256);
     const int cap = 2048 / B > 32 ? 2048 / B : 32;   // grid-stride: few workgroups (= few atomics) per image
@@ -128,20 +106,6 @@ int launch_guidance_base(const float* in, int mosaic, int clamp_in, float* scrat
     if (gx2 > 1024) gx2 = 1024;
     guide_haar_kernel<<<dim3((unsigned)gx2, (unsigned)B), 256, 0, st>>>(in, mosaic, clamp_in, scratch, B, H, W);
     return check_launch("guidance_base");
-}
-
-// F.interpolate(mode='bilinear', align_corners=False)
-__device__ __forceinline__ float bilerp(const float* __restrict__ src, int hi, int wi, int ho, int wo, int y, int x) {
-    const float sy = fmaxf(((float)y + 0.5f) * ((float)hi / (float)ho) - 0.5f, 0.f);
-    const float sx = fmaxf(((float)x + 0.5f) * ((float)wi / (float)wo) - 0.5f, 0.f);
-    int y0 = (int)sy, x0 = (int)sx;
-    if (y0 > hi - 1) y0 = hi - 1;
-    if (x0 > wi - 1) x0 = wi - 1;
-    const int y1 = y0 + (y0 < hi - 1), x1 = x0 + (x0 < wi - 1);
-    const float ly = sy - (float)y0, lx = sx - (float)x0;
-    const float top = src[(size_t)y0 * wi + x0] * (1.f - lx) + src[(size_t)y0 * wi + x1] * lx;
-    const float bot = src[(size_t)y1 * wi + x0] * (1.f - lx) + src[(size_t)y1 * wi + x1] * lx;
-    return top * (1.f - ly) + bot * ly;
 }
 
 __global__ void __launch_bounds__(256) guide_level_kernel(const float* __restrict__ scratch, float* __restrict__ guide,
@@ -171,14 +135,11 @@ int launch_guidance_level(const float* scratch, float* guide, int B, int H, int 
 // Spatial modulation.  Vector path (w % 4 == 0): a lane owns 4 consecutive pixels of a row and
 // keeps their 3x6 guidance neighbourhoods of all four planes in registers (72 floats); the channel
 // loop prefetches the next channel's feature float4 while the current one is in the VALU;
-// sigmoid / tanh use v_exp_f32 + v_rcp_f32 (about 1 ulp each, far below the parity budget).
+// sigmoid / tanh are the fast forms of rf_guidance.h.
 // The 36 weights of a channel are wave-uniform (scalar loads).  Per-block channel sums feed the
 // squeeze-excite pooling without atomics.
 static constexpr int kFlcaCG = 32;   // channels per workgroup: (pixel block, channel group, image) grid keeps small levels parallel
 int flca_nblk(int h, int w) { return (w % 4 == 0) ? cdiv(h * w, 1024) : (w % 2 == 0) ? cdiv(h * w, 512) : cdiv(h * w, 256); }
-
-__device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float fast_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
 
 template <int PX>   // pixels of a row per lane: 4 (w % 4 == 0) or 2 (w % 4 == 2, e.g. level 3 of a 2848 x 4256 frame: w = 266)
 __global__ void __launch_bounds__(256) flca_spatial_vec_kernel(FlcaSpatialArgs a, const float* __restrict__ w_low,
@@ -277,18 +238,8 @@ __global__ void __launch_bounds__(256) flca_spatial_kernel(FlcaSpatialArgs a) {
     const bool live = p < P;
     const int y = live ? p / w : 0, x = live ? p % w : 0;
     const bool counted = y >= a.ylo && y < (a.yhi > 0 ? a.yhi : h) && x >= a.xlo && x < (a.xhi > 0 ? a.xhi : w);
-    // 3x3 neighbourhoods of the four guidance planes, zero padded
-    float nb[4][9];
-    const float* gb = a.guide + b * 4 * (size_t)P;
-#pragma unroll
-    for (int pl = 0; pl < 4; ++pl)
-#pragma unroll
-        for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < 3; ++dx) {
-                const int yy = y + dy - 1, xx = x + dx - 1;
-                nb[pl][dy * 3 + dx] = (live && yy >= 0 && yy < h && xx >= 0 && xx < w) ? gb[(size_t)pl * P + (size_t)yy * w + xx] : 0.f;
-            }
+    float nb[4][3][3];
+    guide_nb<4, 1>(nb, a.guide + b * 4 * (size_t)P, P, y, x, h, w, live);
     const float al = *a.alpha, be = *a.beta, ga = *a.gamma;
     __shared__ float red[512][4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -300,11 +251,14 @@ __global__ void __launch_bounds__(256) flca_spatial_kernel(FlcaSpatialArgs a) {
         const float* wc = a.w_chr + c * 18;
         float sl = 0.f, sh = 0.f, sc = 0.f;
 #pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            sl = fmaf(wl[t], nb[0][t], sl);
-            sh = fmaf(wh[t], nb[1][t], sh);
-            sc = fmaf(wc[9 + t], nb[3][t], fmaf(wc[t], nb[2][t], sc));
-        }
+        for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx) {
+                const int t = dy * 3 + dx;
+                sl = fmaf(wl[t], nb[0][dy][dx], sl);
+                sh = fmaf(wh[t], nb[1][dy][dx], sh);
+                sc = fmaf(wc[9 + t], nb[3][dy][dx], fmaf(wc[t], nb[2][dy][dx], sc));
+            }
         float v = 0.f;
         if (live) {
             v = fb[(size_t)c * P + p] * (1.0f + al * fast_sigmoid(sl) + be * fast_tanh(sh) + ga * fast_sigmoid(sc));

@@ -11,6 +11,7 @@
 // and added in order by launch_reduce_rows (rf_train.hip): two runs give the same bits.  FlcaBwdPlan is the scratch layout,
 // launch_flca_backward the schedule.
 #include "rf_flca_adjoint.h"
+#include "rf_guidance.h"      // fast_sigmoid: the gates recomputed here are the forward's
 
 namespace rf {
 namespace {
@@ -72,8 +73,6 @@ struct FlcaBwdArgs {
 // else touches HBM (the guidance planes are cache resident).
 // partial[(slab * C + c) * 36 + {low 0-8, high 9-17, chroma 18-35}], slabs reduced in order by reduce_partials_kernel;
 // abg_partial[(slab * gridDim.y + ti) * 3 + k].
-__device__ __forceinline__ float fsig(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-
 __global__ void __launch_bounds__(256) flca_bwd_fused_kernel(FlcaBwdArgs a, float* __restrict__ partial, int slab_px, int slabs_per_image) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 15, kq = lane >> 4;
@@ -128,7 +127,7 @@ __global__ void __launch_bounds__(256) flca_bwd_fused_kernel(FlcaBwdArgs a, floa
         float dsl[4], dsh[4], dsc[4], df[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const float a_l = fsig(s_l[q]), a_h = 2.0f * fsig(2.0f * s_h[q]) - 1.0f, a_c = fsig(s_c[q]);
+            const float a_l = fast_sigmoid(s_l[q]), a_h = 2.0f * fast_sigmoid(2.0f * s_h[q]) - 1.0f, a_c = fast_sigmoid(s_c[q]);
             const float dxs = live * fmaf(dzv[q], chv, dm);
             df[q] = dxs * (1.0f + al * a_l + be * a_h + ga * a_c);
             const float dS = dxs * fv[q];

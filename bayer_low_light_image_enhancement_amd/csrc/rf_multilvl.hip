@@ -17,7 +17,8 @@
 // Elsewhere (C > 64, widths that are no multiple of 4) a step is composed: ml_modulate, the shared GEMM kernels twice, ml_residual or,
 // for a block's last step, tc_residual_kernel (rf_truecolor.hip), which leaves the pooling sums; the
 // squeeze-excite gate is folded into channel_reduce by flca_se_fold (rf_flca.hip).  No float atomics: two forwards are bit-identical.
-#include "rf_common.h"
+// The bilinear sampling, the Bayer read, the neighbourhood load and the gate heads are rf_guidance.h's, shared with the other variants.
+#include "rf_guidance.h"
 
 namespace rf {
 
@@ -26,27 +27,6 @@ namespace {
 constexpr int kMlMeans = 8;          // floats per (level, image) in the means table: 2 L + 1 <= 7 used
 constexpr int kMlGuideBlocks = 256;  // most workgroups per image of ml_guide_level_kernel (= partial sums per plane)
 constexpr int kMlTailBlocks = 1024;  // most workgroups per image of ml_tail_sums_kernel
-
-__device__ __forceinline__ float sigmoid_f(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float tanh_f(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
-
-__device__ __forceinline__ float packed_at(const float* in, int mosaic, size_t b, int ch, int y, int x, int H, int W) {
-    return mosaic ? in[(b * 2 * H + 2 * y + (ch >> 1)) * (size_t)(2 * W) + 2 * x + (ch & 1)] : in[((b * 4 + ch) * H + y) * (size_t)W + x];
-}
-
-// F.interpolate(mode='bilinear', align_corners=False)
-__device__ __forceinline__ float bilerp(const float* __restrict__ src, int hi, int wi, int ho, int wo, int y, int x) {
-    const float sy = fmaxf(((float)y + 0.5f) * ((float)hi / (float)ho) - 0.5f, 0.f);
-    const float sx = fmaxf(((float)x + 0.5f) * ((float)wi / (float)wo) - 0.5f, 0.f);
-    int y0 = (int)sy, x0 = (int)sx;
-    if (y0 > hi - 1) y0 = hi - 1;
-    if (x0 > wi - 1) x0 = wi - 1;
-    const int y1 = y0 + (y0 < hi - 1), x1 = x0 + (x0 < wi - 1);
-    const float ly = sy - (float)y0, lx = sx - (float)x0;
-    const float top = src[(size_t)y0 * wi + x0] * (1.f - lx) + src[(size_t)y0 * wi + x1] * lx;
-    const float bot = src[(size_t)y1 * wi + x0] * (1.f - lx) + src[(size_t)y1 * wi + x1] * lx;
-    return top * (1.f - ly) + bot * ly;
-}
 
 // sum over the 256 threads of a workgroup, the same order every time; valid in thread 0.  `red` holds 4 floats.
 __device__ __forceinline__ float block_sum(float s, float* red) {
@@ -60,16 +40,15 @@ __device__ __forceinline__ float block_sum(float s, float* red) {
 
 struct MlGuideSrc {
     const float* cr; const float* cb;    // [B][H][W]
-    const float* ll[3]; const float* mag[3];   // pyramid level i, [B][lh[i]][lw[i]]
-    int lh[3], lw[3];
-    int levels;
+    GuidePyramid pyr;                    // its first `levels` levels
 };
 
 // guide [B][2 L + 2][hf][wf]; partial [B][gridDim.x][kMlMeans]
 __global__ void __launch_bounds__(256) ml_guide_level_kernel(MlGuideSrc s, float* __restrict__ guide, float* __restrict__ partial,
                                                              int H, int W, int hf, int wf) {
     const size_t b = blockIdx.y, hw = (size_t)H * W, pf = (size_t)hf * wf;
-    const int L = s.levels, NP = 2 * L + 2;
+    const GuidePyramid& r = s.pyr;
+    const int L = r.levels, NP = 2 * L + 2;
     float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (size_t p = blockIdx.x * 256ull + threadIdx.x; p < pf; p += (size_t)gridDim.x * 256) {
         const int y = (int)(p / wf), x = (int)(p % wf);
@@ -77,9 +56,9 @@ __global__ void __launch_bounds__(256) ml_guide_level_kernel(MlGuideSrc s, float
 #pragma unroll
         for (int i = 0; i < 3; ++i)
             if (i < L) {
-                const size_t off = b * (size_t)s.lh[i] * s.lw[i];
-                const float lo = bilerp(s.ll[i] + off, s.lh[i], s.lw[i], hf, wf, y, x);
-                const float hi = bilerp(s.mag[i] + off, s.lh[i], s.lw[i], hf, wf, y, x);
+                const size_t off = b * (size_t)r.lh[i] * r.lw[i];
+                const float lo = bilerp(r.ll[i] + off, r.lh[i], r.lw[i], hf, wf, y, x);
+                const float hi = bilerp(r.mag[i] + off, r.lh[i], r.lw[i], hf, wf, y, x);
                 o[(2 * i) * pf] = lo;
                 o[(2 * i + 1) * pf] = hi;
                 acc[2 * i] += lo;
@@ -132,28 +111,10 @@ __global__ void __launch_bounds__(256) ml_modulate_kernel(MlModArgs a) {
     const int p = (blockIdx.x * 256 + threadIdx.x) * PX;
     const bool live = p < P;
     const int y = live ? p / w : 0, x = live ? p - (p / w) * w : 0;
-    // the gate heads of this stage (wave-uniform)
-    const float* mn = a.means + b * kMlMeans;
-    float g0, g1 = 0.f;
-    if constexpr (CHROMA) {
-        g0 = sigmoid_f(fmaf(a.gate_w[0], mn[6], a.gate_b[0]));
-    } else {
-        const float lo = mn[2 * a.level], hi = mn[2 * a.level + 1];
-        g0 = sigmoid_f(fmaf(a.gate_w[1], hi, fmaf(a.gate_w[0], lo, a.gate_b[0])));
-        g1 = sigmoid_f(fmaf(a.gate_w[3], hi, fmaf(a.gate_w[2], lo, a.gate_b[1])));
-    }
+    float g0, g1 = 0.f;      // the gate heads of this stage (wave-uniform)
+    ml_gate_heads<CHROMA>(a.means + b * kMlMeans, a.gate_w, a.gate_b, a.level, g0, g1);
     float nb[2][3][PX + 2];
-    const float* gb = a.planes + b * a.plane_bstride;
-#pragma unroll
-    for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-        for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < PX + 2; ++dx) {
-                const int yy = y + dy - 1, xx = x + dx - 1;
-                const bool ok = live && yy >= 0 && yy < h && xx >= 0 && xx < w;
-                nb[pl][dy][dx] = ok ? gb[(size_t)pl * P + (size_t)yy * w + xx] : 0.f;
-            }
+    guide_nb<2, PX>(nb, a.planes + b * a.plane_bstride, P, y, x, h, w, live);
     const float* fb = a.x + b * (size_t)C * P + (live ? p : 0);
     float* ob = a.out + b * (size_t)C * P + p;
     for (int c = c_lo; c < c_hi; ++c) {
@@ -175,19 +136,13 @@ __global__ void __launch_bounds__(256) ml_modulate_kernel(MlModArgs a) {
             }
         if (live) {
             float fv[PX], v[PX];
-            if constexpr (PX == 4) {
-                const float4 f4 = *reinterpret_cast<const float4*>(fb + (size_t)c * P);
-                fv[0] = f4.x; fv[1] = f4.y; fv[2] = f4.z; fv[3] = f4.w;
-            } else {
-                fv[0] = fb[(size_t)c * P];
-            }
+            load_px<PX>(fb + (size_t)c * P, fv);
 #pragma unroll
             for (int q = 0; q < PX; ++q) {
-                if constexpr (CHROMA) v[q] = fv[q] * (g0 * sigmoid_f(sa[q] + sb[q]));
-                else v[q] = fv[q] * (g0 * sigmoid_f(sa[q]) + g1 * tanh_f(sb[q]));
+                if constexpr (CHROMA) v[q] = fv[q] * (g0 * fast_sigmoid(sa[q] + sb[q]));
+                else v[q] = fv[q] * (g0 * fast_sigmoid(sa[q]) + g1 * fast_tanh(sb[q]));
             }
-            if constexpr (PX == 4) *reinterpret_cast<float4*>(ob + (size_t)c * P) = make_float4(v[0], v[1], v[2], v[3]);
-            else ob[(size_t)c * P] = v[0];
+            store_px<PX>(ob + (size_t)c * P, v);
         }
     }
 }
@@ -200,9 +155,9 @@ __global__ void __launch_bounds__(256) ml_residual_kernel(const float* x, const 
     if (i >= n) return;
     if constexpr (PX == 4) {
         const float4 a = *reinterpret_cast<const float4*>(x + i), t = *reinterpret_cast<const float4*>(r + i);
-        *reinterpret_cast<float4*>(out + i) = make_float4(a.x + 0.2f * tanh_f(t.x), a.y + 0.2f * tanh_f(t.y), a.z + 0.2f * tanh_f(t.z), a.w + 0.2f * tanh_f(t.w));
+        *reinterpret_cast<float4*>(out + i) = make_float4(a.x + 0.2f * fast_tanh(t.x), a.y + 0.2f * fast_tanh(t.y), a.z + 0.2f * fast_tanh(t.z), a.w + 0.2f * fast_tanh(t.w));
     } else {
-        out[i] = x[i] + 0.2f * tanh_f(r[i]);
+        out[i] = x[i] + 0.2f * fast_tanh(r[i]);
     }
 }
 
@@ -248,15 +203,8 @@ __global__ void __launch_bounds__(256) ml_step_fused_kernel(MlStepArgs a) {
     __syncthreads();
     const size_t b = blockIdx.y;
     const int h = a.h, w = a.w, P = h * w;
-    const float* mn = a.means + b * kMlMeans;
     float g0, g1 = 0.f;
-    if constexpr (CHROMA) {
-        g0 = sigmoid_f(fmaf(a.gate_w[0], mn[6], a.gate_b[0]));
-    } else {
-        const float lo = mn[2 * a.level], hi = mn[2 * a.level + 1];
-        g0 = sigmoid_f(fmaf(a.gate_w[1], hi, fmaf(a.gate_w[0], lo, a.gate_b[0])));
-        g1 = sigmoid_f(fmaf(a.gate_w[3], hi, fmaf(a.gate_w[2], lo, a.gate_b[1])));
-    }
+    ml_gate_heads<CHROMA>(a.means + b * kMlMeans, a.gate_w, a.gate_b, a.level, g0, g1);
     const float* gb = a.planes + b * a.plane_bstride;
     const float* xb = a.x + b * (size_t)C * P;
     float* ob = a.out + b * (size_t)C * P;
@@ -267,16 +215,7 @@ __global__ void __launch_bounds__(256) ml_step_fused_kernel(MlStepArgs a) {
     for (int p0 = p_lo + wave * 16; p0 < p_hi; p0 += 64) {
         const int p = p0 + j, y = p / w, x = p - y * w;
         float nb[2][3][3];
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-            for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-                for (int dx = 0; dx < 3; ++dx) {
-                    const int yy = y + dy - 1, xx = x + dx - 1;
-                    const bool ok = yy >= 0 && yy < h && xx >= 0 && xx < w;
-                    nb[pl][dy][dx] = ok ? gb[(size_t)pl * P + (size_t)yy * w + xx] : 0.f;
-                }
+        guide_nb<2, 1>(nb, gb, P, y, x, h, w, true);
         float xv[KS];
         f32x4 acc[NT], acc2[NT];
 #pragma unroll
@@ -295,7 +234,7 @@ __global__ void __launch_bounds__(256) ml_step_fused_kernel(MlStepArgs a) {
                     sa = fmaf(s_ca[c * 9 + dy * 3 + dx], nb[0][dy][dx], sa);
                     sb = fmaf(s_cb[c * 9 + dy * 3 + dx], nb[1][dy][dx], sb);
                 }
-            const float m = CHROMA ? xv[ks] * (g0 * sigmoid_f(sa + sb)) : xv[ks] * (g0 * sigmoid_f(sa) + g1 * tanh_f(sb));
+            const float m = CHROMA ? xv[ks] * (g0 * fast_sigmoid(sa + sb)) : xv[ks] * (g0 * fast_sigmoid(sa) + g1 * fast_tanh(sb));
 #pragma unroll
             for (int to = 0; to < NT; ++to) acc[to] = __builtin_amdgcn_mfma_f32_16x16x4f32(s_w0[(ks * NT + to) * 64 + lane], m, acc[to], 0, 0, 0);
         }
@@ -308,7 +247,7 @@ __global__ void __launch_bounds__(256) ml_step_fused_kernel(MlStepArgs a) {
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const int c = 16 * (ks >> 2) + 4 * q + (ks & 3);
-            const float v = xv[ks] + 0.2f * tanh_f(acc2[ks >> 2][ks & 3]);
+            const float v = xv[ks] + 0.2f * fast_tanh(acc2[ks >> 2][ks & 3]);
             ob[(size_t)c * P + p] = v;
             csum[ks] += v;
         }
@@ -342,9 +281,9 @@ __global__ void __launch_bounds__(256) ml_tail_sums_kernel(const float* __restri
     }
     for (size_t p = blockIdx.x * 256ull + threadIdx.x; p < hw; p += (size_t)gridDim.x * 256) {
         const int y = (int)(p / W), x = (int)(p % W);
-        acc[3] += packed_at(in, mosaic, b, 0, y, x, H, W);
-        acc[4] += 0.5f * (packed_at(in, mosaic, b, 1, y, x, H, W) + packed_at(in, mosaic, b, 2, y, x, H, W));
-        acc[5] += packed_at(in, mosaic, b, 3, y, x, H, W);
+        acc[3] += packed_at(in, mosaic, 0, b, 0, y, x, H, W);
+        acc[4] += 0.5f * (packed_at(in, mosaic, 0, b, 1, y, x, H, W) + packed_at(in, mosaic, 0, b, 2, y, x, H, W));
+        acc[5] += packed_at(in, mosaic, 0, b, 3, y, x, H, W);
     }
     __shared__ float red[4];
     float* o = partial + (b * gridDim.x + blockIdx.x) * 8;
@@ -407,9 +346,8 @@ int pyr_levels(int levels) { return levels > 2 ? levels : 2; }   // the model-le
 struct MlBufs {
     float* base;                 // guidance_base's planes (rf_flca.hip)
     float *y, *cr, *cb;
-    float *ll[3], *mag[3];
-    int lh[3], lw[3];
-    float* means;                // [4 U-Net levels][B][kMlMeans]
+    GuidePyramid pyr;            // pyr_levels(levels) levels; level 0 is guidance_base's
+    float* means;               // [4 U-Net levels][B][kMlMeans]
     float* gpart;                // [B][kMlGuideBlocks][kMlMeans]
     float* tpart;                // [B][kMlTailBlocks][8]
     float* delta;                // [B][4]
@@ -420,14 +358,9 @@ MlBufs ml_layout(float* s, int B, int H, int W, int levels) {
     MlBufs f{};
     Bump b{s};
     f.base = b.take(guidance_scratch_floats(B, H, W));
-    float *ll1 = nullptr, *mag1 = nullptr;
-    if (s) guidance_planes(f.base, B, H, W, &f.y, &f.cr, &f.cb, &ll1, &mag1);
-    f.ll[0] = ll1; f.mag[0] = mag1; f.lh[0] = H / 2; f.lw[0] = W / 2;
-    for (int i = 1; i < pyr_levels(levels); ++i) {
-        f.lh[i] = (f.lh[i - 1] + 1) / 2; f.lw[i] = (f.lw[i - 1] + 1) / 2;
-        f.ll[i] = b.take((size_t)B * f.lh[i] * f.lw[i]);
-        f.mag[i] = b.take((size_t)B * f.lh[i] * f.lw[i]);
-    }
+    if (s) guidance_planes(f.base, B, H, W, &f.y, &f.cr, &f.cb, &f.pyr.ll[0], &f.pyr.mag[0]);
+    f.pyr.lh[0] = H / 2; f.pyr.lw[0] = W / 2;
+    pyramid_layout(f.pyr, b, B, H / 2, W / 2, 1, pyr_levels(levels));
     f.means = b.take((size_t)4 * B * kMlMeans);
     f.gpart = b.take((size_t)B * kMlGuideBlocks * kMlMeans);
     f.tpart = b.take((size_t)B * kMlTailBlocks * 8);
@@ -445,8 +378,9 @@ int launch_ml_guidance(const float* in, int mosaic, float* scratch, int B, int H
     RF_CHECK_ARG(levels >= 1 && levels <= 3 && H % 8 == 0 && W % 8 == 0 && B <= 65535, "multilvl guidance: levels=%d H=%d W=%d unsupported", levels, H, W);
     const MlBufs f = ml_layout(scratch, B, H, W, levels);
     RF_TRY(launch_guidance_base(in, mosaic, 0, f.base, B, H, W, st));
-    for (int i = 1; i < pyr_levels(levels); ++i)
-        RF_TRY(launch_tc_pyramid(f.ll[i - 1], f.ll[i], f.mag[i], B, f.lh[i - 1], f.lw[i - 1], st));
+    const GuidePyramid& r = f.pyr;
+    for (int i = 1; i < r.levels; ++i)
+        RF_TRY(launch_tc_pyramid(r.ll[i - 1], r.ll[i], r.mag[i], B, r.lh[i - 1], r.lw[i - 1], st));
     return RF_OK;
 }
 
@@ -455,8 +389,7 @@ int launch_ml_guide_level(float* scratch, float* guide, int lvl, int B, int H, i
     RF_CHECK_ARG(lvl >= 0 && lvl < 4, "multilvl guidance: level %d", lvl);
     const MlBufs f = ml_layout(scratch, B, H, W, levels);
     MlGuideSrc s{};
-    s.cr = f.cr; s.cb = f.cb; s.levels = levels;
-    for (int i = 0; i < levels; ++i) { s.ll[i] = f.ll[i]; s.mag[i] = f.mag[i]; s.lh[i] = f.lh[i]; s.lw[i] = f.lw[i]; }
+    s.cr = f.cr; s.cb = f.cb; s.pyr = f.pyr; s.pyr.levels = levels;
     int nblk = cdiv(hf * wf, 256);
     if (nblk > kMlGuideBlocks) nblk = kMlGuideBlocks;
     ProfScope prof(st, "ml_guide_level_kernel", 0.0, 4.0 * B * hf * wf * (2 * levels + 2) * 2);
@@ -543,7 +476,7 @@ int launch_ml_tail(float* out, const float* in, int mosaic, float* scratch, int 
     ProfScope prof(st, "ml_tail_apply_kernel", 0.0, 4.0 * B * 6.0 * P4);
     int gx = (int)((P4 / 4 + 255) / 256);
     if (gx > 4096) gx = 4096;
-    ml_tail_apply_kernel<<<dim3((unsigned)gx, (unsigned)B), 256, 0, st>>>(out, f.delta, f.ll[1], f.lh[1], f.lw[1], 2 * H, 2 * W);
+    ml_tail_apply_kernel<<<dim3((unsigned)gx, (unsigned)B), 256, 0, st>>>(out, f.delta, f.pyr.ll[1], f.pyr.lh[1], f.pyr.lw[1], 2 * H, 2 * W);
     return check_launch("ml_tail");
 }
 
@@ -556,9 +489,7 @@ namespace {
 
 // what the modulation and the fused step index with int: B and the channel groups in the grid, h * w pixels
 int ml_check_step(const char* who, int B, int C, int h, int w, int step, int levels) {
-    RF_CHECK_ARG(B >= 1 && B <= 65535 && C >= 1 && h >= 1 && w >= 1, "%s: B=%d C=%d h=%d w=%d: every size must be positive and B <= 65535", who, B, C, h, w);
-    RF_CHECK_ARG(C <= 512, "%s: C=%d > 512 not supported", who, C);
-    RF_CHECK_ARG((size_t)h * w <= (1u << 28), "%s: a %dx%d plane exceeds 2^28 pixels", who, h, w);
+    RF_TRY(check_gate_shape(who, B, C, h, w));
     RF_CHECK_ARG(levels >= 1 && levels <= 3, "%s: levels=%d (1..3)", who, levels);
     RF_CHECK_ARG(step >= 0 && step <= levels, "%s: step=%d (0..levels-1: a pyramid level; levels = %d: the chroma form)", who, step, levels);
     return RF_OK;

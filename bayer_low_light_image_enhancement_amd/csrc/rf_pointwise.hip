@@ -7,13 +7,7 @@
 
 namespace rf {
 
-static constexpr int kBlock = 256;
-static inline int grid_for(size_t items) {
-    size_t g = (items + kBlock - 1) / kBlock;
-    if (g > 256 * 16) g = 256 * 16;   // grid-stride the rest: 16 blocks per CU keeps the chip full
-    if (g < 1) g = 1;
-    return (int)g;
-}
+static constexpr int kBlock = 256;   // grids are grid1d's: at most 4096 workgroups (16 per CU keeps the chip full), grid-stride the rest
 
 // ------------------------------------------------------------------------------------------
 // a1: downshuffle(var, 2)  (RawFomer_WFB_FFAB/model.py:287-298)
@@ -50,9 +44,9 @@ int launch_pixel_unshuffle2(const float* in, float* out, int B, int C, int h, in
     const int planes = B * C;
     ProfScope prof(st, "pixel_unshuffle2_kernel", 0.0, 32.0 * planes * h * w);
     if ((w & 3) == 0 && aligned16(in) && aligned16(out))
-        pixel_unshuffle2_kernel<4><<<grid_for((size_t)planes * h * (w / 4)), kBlock, 0, st>>>(in, out, planes, h, w);
+        pixel_unshuffle2_kernel<4><<<grid1d((size_t)planes * h * (w / 4)), kBlock, 0, st>>>(in, out, planes, h, w);
     else
-        pixel_unshuffle2_kernel<1><<<grid_for((size_t)planes * h * w), kBlock, 0, st>>>(in, out, planes, h, w);
+        pixel_unshuffle2_kernel<1><<<grid1d((size_t)planes * h * w), kBlock, 0, st>>>(in, out, planes, h, w);
     return check_launch("pixel_unshuffle2");
 }
 
@@ -87,9 +81,9 @@ int launch_pixel_shuffle2(const float* in, float* out, int B, int C, int h, int 
     const int planes = B * C;
     ProfScope prof(st, "pixel_shuffle2_kernel", 0.0, 32.0 * planes * h * w);
     if ((w & 3) == 0 && aligned16(in) && aligned16(out))
-        pixel_shuffle2_kernel<4><<<grid_for((size_t)planes * h * (w / 4)), kBlock, 0, st>>>(in, out, planes, h, w);
+        pixel_shuffle2_kernel<4><<<grid1d((size_t)planes * h * (w / 4)), kBlock, 0, st>>>(in, out, planes, h, w);
     else
-        pixel_shuffle2_kernel<1><<<grid_for((size_t)planes * h * w), kBlock, 0, st>>>(in, out, planes, h, w);
+        pixel_shuffle2_kernel<1><<<grid1d((size_t)planes * h * w), kBlock, 0, st>>>(in, out, planes, h, w);
     return check_launch("pixel_shuffle2");
 }
 
@@ -170,9 +164,9 @@ int launch_dwt2x2(const float* in, float* out, const float kk[16], int layout, i
     // algorithmic traffic: 4 B read + 4 B written per input element
     ProfScope prof(st, vec ? "dwt2x2_kernel<4>" : "dwt2x2_kernel<1>", 7.0 * 4 * B * C * hw, 8.0 * 4 * B * C * hw);
     if (vec)
-        dwt2x2_kernel<4><<<grid_for((size_t)B * C * h * (w / 4)), kBlock, 0, st>>>(in, out, k, exact_haar, B, C, h, w, hin, win, ob, os, hw);
+        dwt2x2_kernel<4><<<grid1d((size_t)B * C * h * (w / 4)), kBlock, 0, st>>>(in, out, k, exact_haar, B, C, h, w, hin, win, ob, os, hw);
     else
-        dwt2x2_kernel<1><<<grid_for((size_t)B * C * hw), kBlock, 0, st>>>(in, out, k, exact_haar, B, C, h, w, hin, win, ob, os, hw);
+        dwt2x2_kernel<1><<<grid1d((size_t)B * C * hw), kBlock, 0, st>>>(in, out, k, exact_haar, B, C, h, w, hin, win, ob, os, hw);
     return check_launch("dwt2x2");
 }
 
@@ -239,9 +233,9 @@ int launch_idwt2x2(const float* in, float* out, const float kk[16], int layout, 
     ProfScope prof(st, ((w & 3) == 0 && aligned16(in) && aligned16(out)) ? "idwt2x2_kernel<4>" : "idwt2x2_kernel<1>",
                    7.0 * 4 * B * C * hw, 8.0 * 4 * B * C * hw);
     if ((w & 3) == 0 && aligned16(in) && aligned16(out))
-        idwt2x2_kernel<4><<<grid_for((size_t)B * C * h * (w / 4)), kBlock, 0, st>>>(in, out, k, exact_haar, B, C, h, w, ib, is, hw);
+        idwt2x2_kernel<4><<<grid1d((size_t)B * C * h * (w / 4)), kBlock, 0, st>>>(in, out, k, exact_haar, B, C, h, w, ib, is, hw);
     else
-        idwt2x2_kernel<1><<<grid_for((size_t)B * C * hw), kBlock, 0, st>>>(in, out, k, exact_haar, B, C, h, w, ib, is, hw);
+        idwt2x2_kernel<1><<<grid1d((size_t)B * C * hw), kBlock, 0, st>>>(in, out, k, exact_haar, B, C, h, w, ib, is, hw);
     return check_launch("idwt2x2");
 }
 
@@ -396,9 +390,9 @@ int launch_layernorm2d(const float* in, float* out, const float* w, const float*
         }
     }
     if ((P & 3) == 0 && aligned16(in) && aligned16(out))
-        layernorm2d_kernel<4><<<grid_for((size_t)B * (P / 4)), kBlock, 0, st>>>(in, out, w, b, eps, B, C, P);
+        layernorm2d_kernel<4><<<grid1d((size_t)B * (P / 4)), kBlock, 0, st>>>(in, out, w, b, eps, B, C, P);
     else
-        layernorm2d_kernel<1><<<grid_for((size_t)B * P), kBlock, 0, st>>>(in, out, w, b, eps, B, C, P);
+        layernorm2d_kernel<1><<<grid1d((size_t)B * P), kBlock, 0, st>>>(in, out, w, b, eps, B, C, P);
     return check_launch("layernorm2d");
 }
 
@@ -595,16 +589,16 @@ int launch_dwconv3x3(const DwConvArgs& a, hipStream_t st) {
                    18.0 * el, 8.0 * el);
     if (tall) {
         const size_t items = (size_t)a.B * a.C * (a.h / 8) * (a.w_ / 4);
-        dwconv3x3_halo_kernel<8><<<grid_for((items + 61) / 62 * 64), kBlock, 0, st>>>(a);
+        dwconv3x3_halo_kernel<8><<<grid1d((items + 61) / 62 * 64), kBlock, 0, st>>>(a);
     } else if (vec) {
         const size_t items = (size_t)a.B * a.C * cdiv(a.h, 4) * (a.w_ / 4);
-        dwconv3x3_halo_kernel<4><<<grid_for((items + 61) / 62 * 64), kBlock, 0, st>>>(a);
+        dwconv3x3_halo_kernel<4><<<grid1d((items + 61) / 62 * 64), kBlock, 0, st>>>(a);
     } else if (vec2) {
         const size_t items = (size_t)a.B * a.C * cdiv(a.h, 8) * (a.w_ / 2);
-        dwconv3x3_kernel<2, 8><<<grid_for(items), kBlock, 0, st>>>(a);
+        dwconv3x3_kernel<2, 8><<<grid1d(items), kBlock, 0, st>>>(a);
     } else {
         const size_t items = (size_t)a.B * a.C * cdiv(a.h, 4) * a.w_;
-        dwconv3x3_kernel<1, 4><<<grid_for(items), kBlock, 0, st>>>(a);
+        dwconv3x3_kernel<1, 4><<<grid1d(items), kBlock, 0, st>>>(a);
     }
     return check_launch("dwconv3x3");
 }

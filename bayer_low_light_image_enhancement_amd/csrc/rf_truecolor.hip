@@ -9,31 +9,15 @@
 //   tc_residual     x + 0.2 tanh(res_proj(x)) and the per-block channel sums for the squeeze-excite pooling (:285-292); the
 //                   two 1x1 convolutions of res_proj are the GEMM kernels of rf_gemm1x1.hip
 //   tc_color_head   CameraAwareColorCorrection (:160-176) per pixel: clamp, pow(1/gamma), 3->64->3 MLP, per-channel tone curve
-// All HBM-bound or VALU-bound element-wise work; the dense parts of the variant run on the shared conv / GEMM kernels.
-#include "rf_common.h"
+// All HBM-bound or VALU-bound element-wise work; the dense parts of the variant run on the shared conv / GEMM kernels.  The Bayer
+// read, the bilinear sampling, the Haar step, the luma maximum and the steps of the gate kernel are rf_guidance.h's.
+#include "rf_guidance.h"
 
 namespace rf {
 
 namespace {
 
 __device__ __forceinline__ float softplus_f(float x) { return x > 20.f ? x : log1pf(expf(x)); }
-__device__ __forceinline__ float sigmoid_f(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float tanh_f(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
-
-__device__ __forceinline__ void atomic_max_float(int* addr, float v) {
-    if (v >= 0.f) atomicMax(addr, __float_as_int(v));
-    else atomicMin(reinterpret_cast<unsigned int*>(addr), __float_as_uint(v));
-}
-
-__device__ __forceinline__ float packed_at(const float* in, int mosaic, size_t b, int ch, int y, int x, int H, int W) {
-    return mosaic ? in[(b * 2 * H + 2 * y + (ch >> 1)) * (size_t)(2 * W) + 2 * x + (ch & 1)] : in[((b * 4 + ch) * H + y) * (size_t)W + x];
-}
-
-__global__ void tc_init_kernel(int* amax, int B) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < B) amax[i] = (int)0xff800000u;   // -inf
-}
-
 // cin4 [B,4,H,W] = (r, g, b, y_raw) after white balance; lin3 [B,3,H,W] = colour matrix output
 __global__ void __launch_bounds__(256) tc_front_kernel(const float* __restrict__ in, int mosaic, const float* __restrict__ wb_gains,
                                                        const float* __restrict__ cm, float* __restrict__ cin4, float* __restrict__ lin3,
@@ -47,9 +31,9 @@ __global__ void __launch_bounds__(256) tc_front_kernel(const float* __restrict__
     float mx = -INFINITY;
     for (size_t p = blockIdx.x * 256ull + threadIdx.x; p < hw; p += (size_t)gridDim.x * 256) {
         const int y = (int)(p / W), x = (int)(p % W);
-        const float r = packed_at(in, mosaic, b, 0, y, x, H, W) * gn[0];
-        const float g = 0.5f * (packed_at(in, mosaic, b, 1, y, x, H, W) * gn[1] + packed_at(in, mosaic, b, 2, y, x, H, W) * gn[2]);
-        const float bl = packed_at(in, mosaic, b, 3, y, x, H, W) * gn[3];
+        const float r = packed_at(in, mosaic, 0, b, 0, y, x, H, W) * gn[0];
+        const float g = 0.5f * (packed_at(in, mosaic, 0, b, 1, y, x, H, W) * gn[1] + packed_at(in, mosaic, 0, b, 2, y, x, H, W) * gn[2]);
+        const float bl = packed_at(in, mosaic, 0, b, 3, y, x, H, W) * gn[3];
         float l[3];
 #pragma unroll
         for (int o = 0; o < 3; ++o) l[o] = ((r * m[4 * o] + g * m[4 * o + 1]) + bl * m[4 * o + 2]) + m[4 * o + 3];
@@ -60,15 +44,7 @@ __global__ void __launch_bounds__(256) tc_front_kernel(const float* __restrict__
         l3[0] = l[0]; l3[hw] = l[1]; l3[2 * hw] = l[2];
         mx = fmaxf(mx, yr);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    __shared__ float wm[4];
-    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        mx = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
-        if (mx > -INFINITY) atomic_max_float(amax + b, mx);
-    }
+    block_max_atomic(mx, amax + b);
 }
 
 // y = y_raw / max(amax, eps) written back into plane 3 of cin4; first pyramid level (LL1, mag1) from 2x2 blocks of y.
@@ -88,9 +64,7 @@ __global__ void __launch_bounds__(256) tc_normalise_kernel(float* __restrict__ c
             v[t] = yp[p] * inv;
             yp[p] = v[t];
         }
-        const float lh = (v[0] - v[1] + v[2] - v[3]) * 0.5f, hl = (v[0] + v[1] - v[2] - v[3]) * 0.5f, hh = (v[0] - v[1] - v[2] + v[3]) * 0.5f;
-        ll1[b * (size_t)H2 * W2 + q] = (v[0] + v[1] + v[2] + v[3]) * 0.5f;
-        mag1[b * (size_t)H2 * W2 + q] = sqrtf(lh * lh + hl * hl + hh * hh + 1e-8f);
+        haar_ll_mag(v, ll1[b * (size_t)H2 * W2 + q], mag1[b * (size_t)H2 * W2 + q]);
     }
 }
 
@@ -109,33 +83,15 @@ __global__ void __launch_bounds__(256) tc_pyramid_kernel(const float* __restrict
             if (x >= ws) x = ws - 2;
             v[t] = s[(size_t)(y < 0 ? 0 : y) * ws + (x < 0 ? 0 : x)];
         }
-        const float lh = (v[0] - v[1] + v[2] - v[3]) * 0.5f, hl = (v[0] + v[1] - v[2] - v[3]) * 0.5f, hh = (v[0] - v[1] - v[2] + v[3]) * 0.5f;
-        ll[b * (size_t)h2 * w2 + q] = (v[0] + v[1] + v[2] + v[3]) * 0.5f;
-        mag[b * (size_t)h2 * w2 + q] = sqrtf(lh * lh + hl * hl + hh * hh + 1e-8f);
+        haar_ll_mag(v, ll[b * (size_t)h2 * w2 + q], mag[b * (size_t)h2 * w2 + q]);
     }
-}
-
-__device__ __forceinline__ float bilerp(const float* __restrict__ src, int hi, int wi, int ho, int wo, int y, int x) {
-    const float sy = fmaxf(((float)y + 0.5f) * ((float)hi / (float)ho) - 0.5f, 0.f);
-    const float sx = fmaxf(((float)x + 0.5f) * ((float)wi / (float)wo) - 0.5f, 0.f);
-    int y0 = (int)sy, x0 = (int)sx;
-    if (y0 > hi - 1) y0 = hi - 1;
-    if (x0 > wi - 1) x0 = wi - 1;
-    const int y1 = y0 + (y0 < hi - 1), x1 = x0 + (x0 < wi - 1);
-    const float ly = sy - (float)y0, lx = sx - (float)x0;
-    const float top = src[(size_t)y0 * wi + x0] * (1.f - lx) + src[(size_t)y0 * wi + x1] * lx;
-    const float bot = src[(size_t)y1 * wi + x0] * (1.f - lx) + src[(size_t)y1 * wi + x1] * lx;
-    return top * (1.f - ly) + bot * ly;
 }
 
 struct TcGuideSrc {
     const float* y;        // plane 3 of cin4, image stride 4 * H * W
     const float* crcb;     // [B,2,H,W]
     const float* rgb;      // refined rgb [B,3,H,W]
-    const float* ll[3];    // LL of pyramid level i (size level_h[i] x level_w[i])
-    const float* mag[3];
-    int lh[3], lw[3];
-    int levels;
+    GuidePyramid pyr;
 };
 
 __global__ void __launch_bounds__(256) tc_guide_level_kernel(TcGuideSrc s, float* __restrict__ guide, int H, int W, int hf, int wf) {
@@ -148,11 +104,12 @@ __global__ void __launch_bounds__(256) tc_guide_level_kernel(TcGuideSrc s, float
         o[2 * pf] = bilerp(s.crcb + (b * 2 + 1) * hw, H, W, hf, wf, y, x);
         o[3 * pf] = bilerp(s.rgb + b * 3 * hw, H, W, hf, wf, y, x);
         o[4 * pf] = bilerp(s.rgb + (b * 3 + 1) * hw, H, W, hf, wf, y, x);
-        const int L = s.levels - 1;
-        o[5 * pf] = bilerp(s.ll[L] + b * (size_t)s.lh[L] * s.lw[L], s.lh[L], s.lw[L], hf, wf, y, x);
+        const GuidePyramid& r = s.pyr;
+        const int L = r.levels - 1;
+        o[5 * pf] = bilerp(r.ll[L] + b * (size_t)r.lh[L] * r.lw[L], r.lh[L], r.lw[L], hf, wf, y, x);
         float hsum = 0.f;
-        for (int i = 0; i < s.levels; ++i) hsum += bilerp(s.mag[i] + b * (size_t)s.lh[i] * s.lw[i], s.lh[i], s.lw[i], hf, wf, y, x);
-        o[6 * pf] = s.levels > 1 ? hsum / (float)s.levels : hsum;
+        for (int i = 0; i < r.levels; ++i) hsum += bilerp(r.mag[i] + b * (size_t)r.lh[i] * r.lw[i], r.lh[i], r.lw[i], hf, wf, y, x);
+        o[6 * pf] = r.levels > 1 ? hsum / (float)r.levels : hsum;
     }
 }
 
@@ -174,7 +131,7 @@ __global__ void __launch_bounds__(256) tc_spatial_kernel(TcSpatialArgs a) {
     const bool live = p < P;
     const int y = live ? p / w : 0, x = live ? p - (p / w) * w : 0;
     float nb[7][3][PX + 2];
-    const float* gb = a.guide + b * 7 * (size_t)P;
+    const float* gb = a.guide + b * 7 * (size_t)P;      // guide_nb<7, PX> written out: as the helper it ran slower at level 1
 #pragma unroll
     for (int pl = 0; pl < 7; ++pl)
 #pragma unroll
@@ -210,16 +167,10 @@ __global__ void __launch_bounds__(256) tc_spatial_kernel(TcSpatialArgs a) {
             }
         if (live) {
             float fv[PX], v[PX];
-            if constexpr (PX == 4) {
-                const float4 f4 = *reinterpret_cast<const float4*>(fb + (size_t)c * P);
-                fv[0] = f4.x; fv[1] = f4.y; fv[2] = f4.z; fv[3] = f4.w;
-            } else {
-                fv[0] = fb[(size_t)c * P];
-            }
+            load_px<PX>(fb + (size_t)c * P, fv);
 #pragma unroll
-            for (int q = 0; q < PX; ++q) v[q] = fv[q] * (1.0f + sigmoid_f(sc[q]) + tanh_f(sigmoid_f(sl[q]) + tanh_f(sh[q])));
-            if constexpr (PX == 4) *reinterpret_cast<float4*>(xb + (size_t)c * P) = make_float4(v[0], v[1], v[2], v[3]);
-            else xb[(size_t)c * P] = v[0];
+            for (int q = 0; q < PX; ++q) v[q] = fv[q] * (1.0f + fast_sigmoid(sc[q]) + fast_tanh(fast_sigmoid(sl[q]) + fast_tanh(sh[q])));
+            store_px<PX>(xb + (size_t)c * P, v);
         }
     }
 }
@@ -241,11 +192,11 @@ __global__ void __launch_bounds__(256) tc_residual_kernel(const float* __restric
             if constexpr (PX == 4) {
                 const float4 a = *reinterpret_cast<const float4*>(xs + base + (size_t)c * P);
                 const float4 t = *reinterpret_cast<const float4*>(r + base + (size_t)c * P);
-                const float4 v = make_float4(a.x + 0.2f * tanh_f(t.x), a.y + 0.2f * tanh_f(t.y), a.z + 0.2f * tanh_f(t.z), a.w + 0.2f * tanh_f(t.w));
+                const float4 v = make_float4(a.x + 0.2f * fast_tanh(t.x), a.y + 0.2f * fast_tanh(t.y), a.z + 0.2f * fast_tanh(t.z), a.w + 0.2f * fast_tanh(t.w));
                 *reinterpret_cast<float4*>(x2 + base + (size_t)c * P) = v;
                 s = (v.x + v.y) + (v.z + v.w);
             } else {
-                const float v = xs[base + (size_t)c * P] + 0.2f * tanh_f(r[base + (size_t)c * P]);
+                const float v = xs[base + (size_t)c * P] + 0.2f * fast_tanh(r[base + (size_t)c * P]);
                 x2[base + (size_t)c * P] = v;
                 s = v;
             }
@@ -300,24 +251,17 @@ __global__ void __launch_bounds__(256) tc_color_head_kernel(float* __restrict__ 
     }
 }
 
-int grid_for(size_t n, int cap = 4096) {
-    int g = (int)((n + 255) / 256);
-    if (g > cap) g = cap;
-    return g < 1 ? 1 : g;
-}
-
 }  // namespace
 
 // scratch of the front end (floats): cin4 4hw | lin3 3hw | t16 16hw | crcb 2hw | t32 32hw | d3 3hw | rgb 3hw | pyramid | amax
 size_t tc_front_scratch_floats(int B, int H, int W, int levels) {
     const size_t hw = (size_t)H * W;
-    size_t pyr = 0;
-    int h = H, w = W;
-    for (int i = 0; i < levels; ++i) { h = (h + 1) / 2; w = (w + 1) / 2; pyr += 2 * (size_t)h * w; }
-    return (size_t)B * ((4 + 3 + 16 + 2 + 32 + 3 + 3) * hw + pyr) + align_up((size_t)B, 64) + 64 * 16;
+    GuidePyramid pyr{};
+    Bump none;
+    return (size_t)B * (4 + 3 + 16 + 2 + 32 + 3 + 3) * hw + pyramid_layout(pyr, none, B, H, W, 0, levels) + align_up((size_t)B, 64) + 64 * 16;
 }
 
-struct TcFrontBufs { float *cin4, *lin3, *t16, *crcb, *t32, *d3, *rgb, *ll[3], *mag[3]; int lh[3], lw[3]; int* amax; };
+struct TcFrontBufs { float *cin4, *lin3, *t16, *crcb, *t32, *d3, *rgb; GuidePyramid pyr; int* amax; };
 
 static TcFrontBufs tc_front_layout(float* s, int B, int H, int W, int levels) {
     const size_t hw = (size_t)H * W;
@@ -325,12 +269,7 @@ static TcFrontBufs tc_front_layout(float* s, int B, int H, int W, int levels) {
     Bump b{s};
     f.cin4 = b.take(B * 4 * hw); f.lin3 = b.take(B * 3 * hw); f.t16 = b.take(B * 16 * hw); f.crcb = b.take(B * 2 * hw);
     f.t32 = b.take(B * 32 * hw); f.d3 = b.take(B * 3 * hw); f.rgb = b.take(B * 3 * hw);
-    int h = H, w = W;
-    for (int i = 0; i < levels; ++i) {
-        h = (h + 1) / 2; w = (w + 1) / 2;
-        f.lh[i] = h; f.lw[i] = w;
-        f.ll[i] = b.take((size_t)B * h * w); f.mag[i] = b.take((size_t)B * h * w);
-    }
+    pyramid_layout(f.pyr, b, B, H, W, 0, levels);
     f.amax = reinterpret_cast<int*>(b.take(B));
     return f;
 }
@@ -343,12 +282,13 @@ int launch_tc_front(const float* in, int mosaic, const float* wb_gains, const fl
     const TcFrontBufs f = tc_front_layout(scratch, B, H, W, levels);
     const size_t hw = (size_t)H * W;
     ProfScope prof(st, "tc_front(EnhancedBayerProcessor)", 2.0 * B * hw * 9.0 * (4 * 16 + 16 * 2 + 3 * 32 + 32 * 3), 4.0 * B * hw * 80.0);
-    tc_init_kernel<<<cdiv(B, 256), 256, 0, st>>>(f.amax, B);
+    launch_guide_init(f.amax, B, st);
     const int cap = 2048 / B > 32 ? 2048 / B : 32;
-    tc_front_kernel<<<dim3((unsigned)grid_for(hw, cap), (unsigned)B), 256, 0, st>>>(in, mosaic, wb_gains, color_matrix, f.cin4, f.lin3, f.amax, H, W);
-    tc_normalise_kernel<<<dim3((unsigned)grid_for(hw / 4, 1024), (unsigned)B), 256, 0, st>>>(f.cin4, f.amax, f.ll[0], f.mag[0], H, W);
+    tc_front_kernel<<<dim3((unsigned)grid1d(hw, cap), (unsigned)B), 256, 0, st>>>(in, mosaic, wb_gains, color_matrix, f.cin4, f.lin3, f.amax, H, W);
+    const GuidePyramid& r = f.pyr;
+    tc_normalise_kernel<<<dim3((unsigned)grid1d(hw / 4, 1024), (unsigned)B), 256, 0, st>>>(f.cin4, f.amax, r.ll[0], r.mag[0], H, W);
     for (int i = 1; i < levels; ++i)
-        tc_pyramid_kernel<<<dim3((unsigned)grid_for((size_t)f.lh[i] * f.lw[i], 1024), (unsigned)B), 256, 0, st>>>(f.ll[i - 1], f.ll[i], f.mag[i], f.lh[i - 1], f.lw[i - 1]);
+        tc_pyramid_kernel<<<dim3((unsigned)grid1d((size_t)r.lh[i] * r.lw[i], 1024), (unsigned)B), 256, 0, st>>>(r.ll[i - 1], r.ll[i], r.mag[i], r.lh[i - 1], r.lw[i - 1]);
     if (int rc = check_launch("tc_front")) return rc;
     auto conv = [&](const float* x, float* out, const float* wp, const float* bias, int cin, int cout, int act) {
         Conv3x3Args a{};
@@ -360,7 +300,7 @@ int launch_tc_front(const float* in, int mosaic, const float* wb_gains, const fl
     if (int rc = conv(f.t16, f.crcb, wp_c2, b_c2, 16, 2, 4)) return rc;
     if (int rc = conv(f.lin3, f.t32, wp_d0, b_d0, 3, 32, 3)) return rc;       // demosaic_refine: conv, GELU, conv (+ residual)
     if (int rc = conv(f.t32, f.d3, wp_d2, b_d2, 32, 3, 0)) return rc;
-    tc_add_kernel<<<grid_for(B * 3 * hw), 256, 0, st>>>(f.lin3, f.d3, f.rgb, B * 3 * hw);
+    tc_add_kernel<<<grid1d(B * 3 * hw), 256, 0, st>>>(f.lin3, f.d3, f.rgb, B * 3 * hw);
     return check_launch("tc_front");
 }
 
@@ -369,17 +309,16 @@ int launch_tc_pyramid(const float* src, float* ll, float* mag, int B, int hs, in
     RF_CHECK_ARG(B <= 65535 && hs >= 2 && ws >= 2, "pyramid level of a %dx%d plane", hs, ws);
     const size_t n = (size_t)((hs + 1) / 2) * ((ws + 1) / 2);
     ProfScope prof(st, "tc_pyramid_kernel", 0.0, 4.0 * B * n * 6);
-    tc_pyramid_kernel<<<dim3((unsigned)grid_for(n, 1024), (unsigned)B), 256, 0, st>>>(src, ll, mag, hs, ws);
+    tc_pyramid_kernel<<<dim3((unsigned)grid1d(n, 1024), (unsigned)B), 256, 0, st>>>(src, ll, mag, hs, ws);
     return check_launch("tc_pyramid");
 }
 
 int launch_tc_guide_level(const float* scratch, float* guide, int B, int H, int W, int levels, int hf, int wf, hipStream_t st) {
     const TcFrontBufs f = tc_front_layout(const_cast<float*>(scratch), B, H, W, levels);
     TcGuideSrc s{};
-    s.y = f.cin4 + 3 * (size_t)H * W; s.crcb = f.crcb; s.rgb = f.rgb; s.levels = levels;
-    for (int i = 0; i < levels; ++i) { s.ll[i] = f.ll[i]; s.mag[i] = f.mag[i]; s.lh[i] = f.lh[i]; s.lw[i] = f.lw[i]; }
+    s.y = f.cin4 + 3 * (size_t)H * W; s.crcb = f.crcb; s.rgb = f.rgb; s.pyr = f.pyr;
     ProfScope prof(st, "tc_guide_level_kernel", 0.0, 4.0 * B * hf * wf * 14);
-    tc_guide_level_kernel<<<dim3((unsigned)grid_for((size_t)hf * wf, 1024), (unsigned)B), 256, 0, st>>>(s, guide, H, W, hf, wf);
+    tc_guide_level_kernel<<<dim3((unsigned)grid1d((size_t)hf * wf, 1024), (unsigned)B), 256, 0, st>>>(s, guide, H, W, hf, wf);
     return check_launch("tc_guide_level");
 }
 
@@ -419,8 +358,16 @@ int launch_tc_color_head(float* x, const float* const* prm /* gamma, ct.0.w, ct.
                          int B, size_t P, hipStream_t st) {
     ProfScope prof(st, "tc_color_head_kernel", 2.0 * B * P * (3 * 64 * 2 + 3 * 64), 24.0 * B * P);
     const int cap = 4096 / B > 64 ? 4096 / B : 64;
-    tc_color_head_kernel<<<dim3((unsigned)grid_for(P, cap), (unsigned)B), 256, 0, st>>>(x, prm[0], prm[1], prm[2], prm[3], prm[4], prm[5], prm[6], prm[7], prm[8], P);
+    tc_color_head_kernel<<<dim3((unsigned)grid1d(P, cap), (unsigned)B), 256, 0, st>>>(x, prm[0], prm[1], prm[2], prm[3], prm[4], prm[5], prm[6], prm[7], prm[8], P);
     return check_launch("tc_color_head");
+}
+
+// what the gate and residual kernels of this file and of rf_multilvl.hip index with int: B in the grid, h * w pixels
+int check_gate_shape(const char* who, int B, int C, int h, int w) {
+    RF_CHECK_ARG(B >= 1 && B <= 65535 && C >= 1 && h >= 1 && w >= 1, "%s: B=%d C=%d h=%d w=%d: every size must be positive and B <= 65535", who, B, C, h, w);
+    RF_CHECK_ARG(C <= 512, "%s: C=%d > 512 not supported", who, C);
+    RF_CHECK_ARG((size_t)h * w <= (1u << 28), "%s: a %dx%d plane exceeds 2^28 pixels", who, h, w);
+    return RF_OK;
 }
 
 }  // namespace rf
@@ -428,24 +375,12 @@ int launch_tc_color_head(float* x, const float* const* prm /* gamma, ct.0.w, ct.
 using namespace rf;
 
 // ---- the kernels one by one (include/rawformer_hip.h): argument checks, then the launch functions above ----------------------
-namespace {
-
-// what the spatial and residual kernels index with int: B in the grid, h * w pixels
-int tc_check_shape(const char* who, int B, int C, int h, int w) {
-    RF_CHECK_ARG(B >= 1 && B <= 65535 && C >= 1 && h >= 1 && w >= 1, "%s: B=%d C=%d h=%d w=%d: every size must be positive and B <= 65535", who, B, C, h, w);
-    RF_CHECK_ARG(C <= 512, "%s: C=%d > 512 not supported", who, C);
-    RF_CHECK_ARG((size_t)h * w <= (1u << 28), "%s: a %dx%d plane exceeds 2^28 pixels", who, h, w);
-    return RF_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 int rf_tc_spatial(const float* feat, const float* guide, const float* w_col, const float* b_col, const float* w_low, const float* b_low,
                   const float* w_high, const float* b_high, float* xs, int B, int C, int h, int w, void* stream) {
     RF_CHECK_ARG(feat && guide && w_col && b_col && w_low && b_low && w_high && b_high && xs, "rf_tc_spatial: null argument");
-    RF_TRY(tc_check_shape("rf_tc_spatial", B, C, h, w));
+    RF_TRY(check_gate_shape("rf_tc_spatial", B, C, h, w));
     RF_CHECK_ARG(aligned4(feat) && aligned4(guide) && aligned4(xs) && aligned4(w_col) && aligned4(b_col) && aligned4(w_low) && aligned4(b_low) &&
                      aligned4(w_high) && aligned4(b_high), "rf_tc_spatial: buffers must be 4-byte aligned");
     return launch_tc_spatial(feat, xs, guide, w_col, b_col, w_low, b_low, w_high, b_high, B, C, h, w, (hipStream_t)stream);
@@ -458,7 +393,7 @@ int rf_tc_nblk(int h, int w) {
 
 int rf_tc_residual(const float* xs, const float* r, float* x2, float* partial, int B, int C, int h, int w, void* stream) {
     RF_CHECK_ARG(xs && r && x2 && partial, "rf_tc_residual: null argument");
-    RF_TRY(tc_check_shape("rf_tc_residual", B, C, h, w));
+    RF_TRY(check_gate_shape("rf_tc_residual", B, C, h, w));
     RF_CHECK_ARG(aligned4(xs) && aligned4(r) && aligned4(x2) && aligned4(partial), "rf_tc_residual: buffers must be 4-byte aligned");
     RF_CHECK_ARG(w % 4 != 0 || (aligned16(xs) && aligned16(r) && aligned16(x2)),
                  "rf_tc_residual: buffers must be 16-byte aligned where the width is a multiple of 4");
