@@ -59,6 +59,23 @@ __device__ __forceinline__ float gelu_fast(float v) {
 // fast_tanh (rf_guidance.h)
 __device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }   // p 16-byte aligned
+// The exact Haar pair of RawFomer_WFB_FFAB/blocks.py: halve first, then the sums in the order Python evaluates them.  t / r: the 2x2
+// quad, row then column.  dwt_init (blocks.py:104-113): x1 = (0,0), x2 = (1,0), x3 = (0,1), x4 = (1,1)
+__device__ __forceinline__ void haar_analysis(float t00, float t01, float t10, float t11, float& ll, float& hl, float& lh, float& hh) {
+    const float x1 = t00 / 2, x2 = t10 / 2, x3 = t01 / 2, x4 = t11 / 2;
+    ll = ((x1 + x2) + x3) + x4;
+    hl = ((-x1 - x2) + x3) + x4;
+    lh = ((-x1 + x2) - x3) + x4;
+    hh = ((x1 - x2) - x3) + x4;
+}
+// iwt_init (blocks.py:123-134)
+__device__ __forceinline__ void haar_synthesis(float ll, float hl, float lh, float hh, float& r00, float& r01, float& r10, float& r11) {
+    const float b1 = ll / 2, b2 = hl / 2, b3 = lh / 2, b4 = hh / 2;
+    r00 = ((b1 - b2) - b3) + b4;
+    r10 = ((b1 - b2) + b3) - b4;
+    r01 = ((b1 + b2) - b3) - b4;
+    r11 = ((b1 + b2) + b3) + b4;
+}
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }

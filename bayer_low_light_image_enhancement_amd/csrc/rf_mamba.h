@@ -50,6 +50,40 @@ int mamba_bwd_plan(const char* who, int B, int L, int D, int N, int K, int E, Ma
 int run_mamba_backward(const MambaBwdPlan& p, const float* u, const float* g, float* du, const float* const* prm, float* const* grd,
                        float* ws, int B, int L, int acc, hipStream_t st);
 
+// ---- the row LayerNorm of tok_transpose_kernel<true> and its adjoint wm_ln_bwd_kernel (rf_wm_bwd.hip): mean and rstd of the 32 rows
+// r0 .. r0 + 31 of [rows][cols], cols <= 512, into smean / srstd [32].  Each of the four waves of the workgroup takes 8 rows, a row's
+// values in registers over both passes; val(o) is the element at offset o (the forward's optional `add` included).  The caller
+// synchronises before it reads the two arrays.
+template <class V>
+__device__ __forceinline__ void tok_row_stats(V&& val, int r0, int rows, int cols, float eps, float* smean, float* srstd) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int i = 0; i < 8; ++i) {
+        const int r = r0 + wave * 8 + i;
+        float v[8], s = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int k = lane + 64 * j;
+            v[j] = (r < rows && k < cols) ? val((size_t)r * cols + k) : 0.f;
+            s += v[j];
+        }
+#pragma unroll
+        for (int m = 32; m > 0; m >>= 1) s += __shfl_xor(s, m, 64);
+        const float mean = s / (float)cols;
+        float q = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float dv = lane + 64 * j < cols ? v[j] - mean : 0.f;
+            q = fmaf(dv, dv, q);
+        }
+#pragma unroll
+        for (int m = 32; m > 0; m >>= 1) q += __shfl_xor(q, m, 64);
+        if (lane == 0) {
+            smean[wave * 8 + i] = mean;
+            srstd[wave * 8 + i] = 1.0f / sqrtf(q / (float)cols + eps);
+        }
+    }
+}
+
 // ---- WM (rf_mamba.hip): what rf_wm_forward and the WM backward share
 int wm_check_shape(const char* who, int n, int c, int h, int w);      // the refusals of rf_wm_forward, each naming its argument
 struct WmFrontBufs {

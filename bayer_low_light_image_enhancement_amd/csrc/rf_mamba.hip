@@ -39,36 +39,7 @@ __global__ void __launch_bounds__(256) tok_transpose_kernel(const float* __restr
     if (add) add += img;
     const int r0 = blockIdx.x * 32;
     if constexpr (LN) {
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        for (int i = 0; i < 8; ++i) {
-            const int r = r0 + wave * 8 + i;
-            float v[8], s = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int k = lane + 64 * j;
-                v[j] = 0.f;
-                if (r < rows && k < cols) {
-                    const size_t o = (size_t)r * cols + k;
-                    v[j] = add ? in[o] + add[o] : in[o];
-                }
-                s += v[j];
-            }
-#pragma unroll
-            for (int m = 32; m > 0; m >>= 1) s += __shfl_xor(s, m, 64);
-            const float mean = s / (float)cols;
-            float q = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float dv = lane + 64 * j < cols ? v[j] - mean : 0.f;
-                q = fmaf(dv, dv, q);
-            }
-#pragma unroll
-            for (int m = 32; m > 0; m >>= 1) q += __shfl_xor(q, m, 64);
-            if (lane == 0) {
-                smean[wave * 8 + i] = mean;
-                srstd[wave * 8 + i] = 1.0f / sqrtf(q / (float)cols + eps);
-            }
-        }
+        tok_row_stats([&](size_t o) { return add ? in[o] + add[o] : in[o]; }, r0, rows, cols, eps, smean, srstd);
         __syncthreads();
     }
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;

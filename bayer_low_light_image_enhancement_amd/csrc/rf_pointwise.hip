@@ -3,7 +3,7 @@
 // (16-byte accesses, 1 KiB per wave instruction) whenever the row length allows; a scalar
 // path covers ragged widths (e.g. w = 266 at level 3 of a 1424x2128 frame).
 #include <cstdlib>
-#include "rf_common.h"
+#include "rf_layernorm.h"
 
 namespace rf {
 
@@ -97,13 +97,7 @@ struct K16 { float v[16]; };
 __device__ __forceinline__ void analysis4(const K16& k, int exact, float t0, float t1, float t2, float t3,
                                           float& s0, float& s1, float& s2, float& s3) {
     if (exact) {
-        // dwt_init, RawFomer_WFB_FFAB/blocks.py:104-113: x1=(0,0) x2=(1,0) x3=(0,1) x4=(1,1), each /2,
-        // then the sums exactly in the order Python evaluates them.
-        const float x1 = t0 / 2, x2 = t2 / 2, x3 = t1 / 2, x4 = t3 / 2;
-        s0 = ((x1 + x2) + x3) + x4;
-        s1 = ((-x1 - x2) + x3) + x4;
-        s2 = ((-x1 + x2) - x3) + x4;
-        s3 = ((x1 - x2) - x3) + x4;
+        haar_analysis(t0, t1, t2, t3, s0, s1, s2, s3);
     } else {
         s0 = fmaf(k.v[3], t3, fmaf(k.v[2], t2, fmaf(k.v[1], t1, k.v[0] * t0)));
         s1 = fmaf(k.v[7], t3, fmaf(k.v[6], t2, fmaf(k.v[5], t1, k.v[4] * t0)));
@@ -174,12 +168,7 @@ int launch_dwt2x2(const float* in, float* out, const float kk[16], int layout, i
 __device__ __forceinline__ void synthesis4(const K16& k, int exact, float b0, float b1, float b2, float b3,
                                            float& t0, float& t1, float& t2, float& t3) {
     if (exact) {
-        // iwt_init, RawFomer_WFB_FFAB/blocks.py:123-134
-        const float x1 = b0 / 2, x2 = b1 / 2, x3 = b2 / 2, x4 = b3 / 2;
-        t0 = ((x1 - x2) - x3) + x4;   // (0,0)
-        t2 = ((x1 - x2) + x3) - x4;   // (1,0)
-        t1 = ((x1 + x2) - x3) - x4;   // (0,1)
-        t3 = ((x1 + x2) + x3) + x4;   // (1,1)
+        haar_synthesis(b0, b1, b2, b3, t0, t1, t2, t3);
     } else {
         t0 = fmaf(k.v[12], b3, fmaf(k.v[8], b2, fmaf(k.v[4], b1, k.v[0] * b0)));
         t1 = fmaf(k.v[13], b3, fmaf(k.v[9], b2, fmaf(k.v[5], b1, k.v[1] * b0)));
@@ -261,8 +250,7 @@ __global__ void __launch_bounds__(kBlock) layernorm2d_kernel(const float* __rest
         for (int v = 0; v < VEC; ++v) { mu[v] = 0.f; var[v] = 0.f; }
         for (int c = 0; c < C; ++c) {
             if constexpr (VEC == 4) {
-                const float4 t = *reinterpret_cast<const float4*>(x + (size_t)c * P);
-                mu[0] += t.x; mu[1] += t.y; mu[2] += t.z; mu[3] += t.w;
+                acc4(mu, ld4(x + (size_t)c * P));
             } else {
                 mu[0] += x[(size_t)c * P];
             }
@@ -271,9 +259,7 @@ __global__ void __launch_bounds__(kBlock) layernorm2d_kernel(const float* __rest
         for (int v = 0; v < VEC; ++v) mu[v] *= invC;
         for (int c = 0; c < C; ++c) {
             if constexpr (VEC == 4) {
-                const float4 t = *reinterpret_cast<const float4*>(x + (size_t)c * P);
-                var[0] += (t.x - mu[0]) * (t.x - mu[0]); var[1] += (t.y - mu[1]) * (t.y - mu[1]);
-                var[2] += (t.z - mu[2]) * (t.z - mu[2]); var[3] += (t.w - mu[3]) * (t.w - mu[3]);
+                sq4(var, ld4(x + (size_t)c * P), mu);
             } else {
                 const float d = x[(size_t)c * P] - mu[0];
                 var[0] += d * d;
@@ -282,17 +268,13 @@ __global__ void __launch_bounds__(kBlock) layernorm2d_kernel(const float* __rest
         float rs[VEC], sh[VEC];
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
-            rs[v] = 1.0f / sqrtf(var[v] * invC + eps);
+            rs[v] = ln_rstd(var[v], invC, eps);
             sh[v] = gb ? mu[v] : 0.f;   // BiasFree_LayerNorm keeps the mean in the numerator
         }
         for (int c = 0; c < C; ++c) {
             const float g = gw[c], bb = gb ? gb[c] : 0.f;
             if constexpr (VEC == 4) {
-                const float4 t = *reinterpret_cast<const float4*>(x + (size_t)c * P);
-                float4 r;
-                r.x = (t.x - sh[0]) * rs[0] * g + bb; r.y = (t.y - sh[1]) * rs[1] * g + bb;
-                r.z = (t.z - sh[2]) * rs[2] * g + bb; r.w = (t.w - sh[3]) * rs[3] * g + bb;
-                *reinterpret_cast<float4*>(o + (size_t)c * P) = r;
+                *reinterpret_cast<float4*>(o + (size_t)c * P) = norm4(ld4(x + (size_t)c * P), sh, rs, g, bb);
             } else {
                 o[(size_t)c * P] = (x[(size_t)c * P] - sh[0]) * rs[0] * g + bb;
             }
@@ -330,7 +312,7 @@ __global__ void __launch_bounds__(kBlock) layernorm2d_reg_kernel(const float* __
         for (int s = 0; s < CPL; ++s) x[s] = *reinterpret_cast<const float4*>(xb + (size_t)(ks + KS * s) * P + off);
         float mu[4] = {0.f, 0.f, 0.f, 0.f}, var[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int s = 0; s < CPL; ++s) { mu[0] += x[s].x; mu[1] += x[s].y; mu[2] += x[s].z; mu[3] += x[s].w; }
+        for (int s = 0; s < CPL; ++s) acc4(mu, x[s]);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
 #pragma unroll
@@ -347,47 +329,29 @@ __global__ void __launch_bounds__(kBlock) layernorm2d_reg_kernel(const float* __
         for (int q = 0; q < 4; ++q) {
 #pragma unroll
             for (int o = G; o < 64; o <<= 1) var[q] += __shfl_xor(var[q], o);
-            rs[q] = 1.0f / sqrtf(var[q] * invC + eps);
+            rs[q] = ln_rstd(var[q], invC, eps);
             sh[q] = gb ? mu[q] : 0.f;              // BiasFree_LayerNorm keeps the mean in the numerator
         }
         if (ok) {
 #pragma unroll
-            for (int s = 0; s < CPL; ++s) {
-                float4 r;
-                r.x = (x[s].x - sh[0]) * rs[0] * gam[s] + bet[s]; r.y = (x[s].y - sh[1]) * rs[1] * gam[s] + bet[s];
-                r.z = (x[s].z - sh[2]) * rs[2] * gam[s] + bet[s]; r.w = (x[s].w - sh[3]) * rs[3] * gam[s] + bet[s];
-                *reinterpret_cast<float4*>(ob + (size_t)(ks + KS * s) * P + off) = r;
-            }
+            for (int s = 0; s < CPL; ++s)
+                *reinterpret_cast<float4*>(ob + (size_t)(ks + KS * s) * P + off) = norm4(x[s], sh, rs, gam[s], bet[s]);
         }
     }
-}
-
-template <int CPL, int KS>
-static void launch_ln_reg(const float* in, float* out, const float* w, const float* b, float eps, int B, int C, int P, hipStream_t st) {
-    const int per_wg = 4 * (64 / KS);
-    int gx = cdiv(P / 4, per_wg);
-    const int cap = cdiv(256 * 8, B);              // about eight workgroups per CU over the batch, grid-stride beyond
-    if (gx > cap) gx = cap;
-    layernorm2d_reg_kernel<CPL, KS><<<dim3((unsigned)gx, (unsigned)B), kBlock, 0, st>>>(in, out, w, b, eps, C, P);
 }
 
 int launch_layernorm2d(const float* in, float* out, const float* w, const float* b, float eps,
                        int B, int C, int P, hipStream_t st) {
     ProfScope prof(st, "layernorm2d_kernel", 8.0 * B * C * P, 8.0 * B * C * P);
     if ((P & 3) == 0 && aligned16(in) && aligned16(out) && B <= 65535) {
+#define RF_LN_FWD(C_, CPL, KS) /* about eight workgroups per CU over the batch */                                                              \
+    case C_: layernorm2d_reg_kernel<CPL, KS><<<dim3((unsigned)ln_slice_grid(B, P, KS, 8), (unsigned)B), kBlock, 0, st>>>(in, out, w, b, eps, C, P); \
+             return check_launch("layernorm2d");
         switch (C) {
-            case 16: launch_ln_reg<4, 4>(in, out, w, b, eps, B, C, P, st); return check_launch("layernorm2d");
-            case 32: launch_ln_reg<8, 4>(in, out, w, b, eps, B, C, P, st); return check_launch("layernorm2d");
-            case 48: launch_ln_reg<12, 4>(in, out, w, b, eps, B, C, P, st); return check_launch("layernorm2d");
-            case 64: launch_ln_reg<16, 4>(in, out, w, b, eps, B, C, P, st); return check_launch("layernorm2d");
-            case 96: launch_ln_reg<12, 8>(in, out, w, b, eps, B, C, P, st); return check_launch("layernorm2d");
-            case 128: launch_ln_reg<16, 8>(in, out, w, b, eps, B, C, P, st); return check_launch("layernorm2d");
-            case 192: launch_ln_reg<12, 16>(in, out, w, b, eps, B, C, P, st); return check_launch("layernorm2d");
-            case 256: launch_ln_reg<16, 16>(in, out, w, b, eps, B, C, P, st); return check_launch("layernorm2d");
-            case 384: launch_ln_reg<12, 32>(in, out, w, b, eps, B, C, P, st); return check_launch("layernorm2d");
-            case 512: launch_ln_reg<16, 32>(in, out, w, b, eps, B, C, P, st); return check_launch("layernorm2d");
+            RF_LN_SLICE_TABLE(RF_LN_FWD)
             default: break;
         }
+#undef RF_LN_FWD
     }
     if ((P & 3) == 0 && aligned16(in) && aligned16(out))
         layernorm2d_kernel<4><<<grid1d((size_t)B * (P / 4)), kBlock, 0, st>>>(in, out, w, b, eps, B, C, P);

@@ -22,7 +22,7 @@
 // axis is the MFMA K dimension (v_mfma_f32_16x16x4_f32, f32 accumulate: reference numerics), every lane streams rows of 4
 // consecutive pixels.  Pixel slabs are reduced through per-slab partials summed in a fixed order: gradients are bitwise
 // reproducible run to run (no float atomics).
-#include "rf_common.h"
+#include "rf_layernorm.h"
 
 namespace rf {
 
@@ -450,7 +450,7 @@ __global__ void __launch_bounds__(256) ln_bwd_reg_kernel(const float* __restrict
         }
         float mu[4] = {0.f, 0.f, 0.f, 0.f}, var[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int s = 0; s < CPL; ++s) { mu[0] += xv[s].x; mu[1] += xv[s].y; mu[2] += xv[s].z; mu[3] += xv[s].w; }
+        for (int s = 0; s < CPL; ++s) acc4(mu, xv[s]);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
 #pragma unroll
@@ -468,7 +468,7 @@ __global__ void __launch_bounds__(256) ln_bwd_reg_kernel(const float* __restrict
         for (int q = 0; q < 4; ++q) {
 #pragma unroll
             for (int o = G; o < 64; o <<= 1) var[q] += __shfl_xor(var[q], o);
-            rstd[q] = 1.0f / sqrtf(var[q] * invC + eps);
+            rstd[q] = ln_rstd(var[q], invC, eps);
         }
         const float m = ok ? 1.0f : 0.f;              // lanes past the end contribute nothing to the channel sums
 #pragma unroll
@@ -874,42 +874,24 @@ int launch_chan_sum(const float* x, int64_t bstride, float* out, float* partial,
 // partial: ln_bwd_partial_floats floats = per-pixel statistics + the per-block sums.  dx must not alias dy (the weight pass
 // reads dy after dx has been written).
 static int ln_nblk(int P) { int n = P / 4096; return n < 1 ? 1 : n > 64 ? 64 : n; }
-static int ln_reg_nblk(int B, int P, int per_wg) {
-    int gx = cdiv(P / 4, per_wg);
-    const int cap = cdiv(256 * 4, B);              // about four workgroups per CU over the batch: each loops over its pixel chunks
-    return gx > cap ? cap : gx;
-}
 template <int CPL, int KS>
 static int launch_ln_bwd_reg(const float* x, const float* dy, const float* gamma, const float* res, int64_t res_bstride, float* dx, float* dgb,
                              float* partial, int B, int C, int P, float eps, int accumulate_dx, int accumulate_w, hipStream_t st) {
-    const int nblk = ln_reg_nblk(B, P, 4 * (64 / KS));
+    const int nblk = ln_slice_grid(B, P, KS, 4);   // about four workgroups per CU over the batch: each loops over its pixel chunks
     ln_bwd_reg_kernel<CPL, KS><<<dim3((unsigned)nblk, (unsigned)B), 256, 0, st>>>(x, dy, gamma, res, res_bstride, dx, partial, C, P, eps, accumulate_dx);
     reduce_partials_kernel<<<red_grid(2 * C), 256, 0, st>>>(partial, dgb, B * nblk, (size_t)2 * C, accumulate_w);
     return check_launch("ln_bwd");
 }
 // channel counts of the register-resident kernel (which also takes a strided residual); anything else runs the generic path
-bool ln_bwd_fused_shape(int C, int P) {
-    switch (C) {
-        case 16: case 32: case 48: case 64: case 96: case 128: case 192: case 256: case 384: case 512: return (P & 3) == 0;
-        default: return false;
-    }
-}
+bool ln_bwd_fused_shape(int C, int P) { return ln_slice_channels(C) && (P & 3) == 0; }
 int launch_ln_bwd(const float* x, const float* dy, const float* gamma, float* dx, float* dgb, float* partial,
                   int B, int C, int P, float eps, int accumulate_dx, int accumulate_w, hipStream_t st, const float* res, int64_t res_bstride) {
     ProfScope prof(st, "ln_bwd", 14.0 * B * C * P, (res ? 16.0 : 12.0) * B * C * P);
     if ((P & 3) == 0 && aligned16(x) && aligned16(dy) && aligned16(dx) && (!res || (aligned16(res) && res_bstride % 4 == 0)) && B <= 65535) {
-#define RF_LN_BWD(CPL, KS) return launch_ln_bwd_reg<CPL, KS>(x, dy, gamma, res, res_bstride, dx, dgb, partial, B, C, P, eps, accumulate_dx, accumulate_w, st)
+#define RF_LN_BWD(C_, CPL, KS) \
+    case C_: return launch_ln_bwd_reg<CPL, KS>(x, dy, gamma, res, res_bstride, dx, dgb, partial, B, C, P, eps, accumulate_dx, accumulate_w, st);
         switch (C) {
-            case 16: RF_LN_BWD(4, 4);
-            case 32: RF_LN_BWD(8, 4);
-            case 48: RF_LN_BWD(12, 4);
-            case 64: RF_LN_BWD(16, 4);
-            case 96: RF_LN_BWD(12, 8);
-            case 128: RF_LN_BWD(16, 8);
-            case 192: RF_LN_BWD(12, 16);
-            case 256: RF_LN_BWD(16, 16);
-            case 384: RF_LN_BWD(12, 32);
-            case 512: RF_LN_BWD(16, 32);
+            RF_LN_SLICE_TABLE(RF_LN_BWD)
             default: break;
         }
 #undef RF_LN_BWD

@@ -39,7 +39,6 @@ __global__ void __launch_bounds__(256) wm_ln_bwd_kernel(const float* __restrict_
     add += img;
     g += img;
     dx += img;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     for (int k = tx; k < cols; k += 32) {
         acc[0][ty][k] = 0.f;
@@ -49,35 +48,7 @@ __global__ void __launch_bounds__(256) wm_ln_bwd_kernel(const float* __restrict_
     const int ngroups = (rows + 31) / 32;
     for (int rg = blockIdx.x; rg < ngroups; rg += gridDim.x) {
         const int r0 = rg * 32;
-        for (int i = 0; i < 8; ++i) {                          // mean and rstd: the forward's arithmetic
-            const int r = r0 + wave * 8 + i;
-            float v[8], s = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int k = lane + 64 * j;
-                v[j] = 0.f;
-                if (r < rows && k < cols) {
-                    const size_t o = (size_t)r * cols + k;
-                    v[j] = in[o] + add[o];
-                }
-                s += v[j];
-            }
-#pragma unroll
-            for (int m = 32; m > 0; m >>= 1) s += __shfl_xor(s, m, 64);
-            const float mean = s / (float)cols;
-            float q = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float dv = lane + 64 * j < cols ? v[j] - mean : 0.f;
-                q = fmaf(dv, dv, q);
-            }
-#pragma unroll
-            for (int m = 32; m > 0; m >>= 1) q += __shfl_xor(q, m, 64);
-            if (lane == 0) {
-                smean[wave * 8 + i] = mean;
-                srstd[wave * 8 + i] = 1.0f / sqrtf(q / (float)cols + eps);
-            }
-        }
+        tok_row_stats([&](size_t o) { return in[o] + add[o]; }, r0, rows, cols, eps, smean, srstd);   // the forward's mean and rstd
         __syncthreads();
         float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
         for (int c0 = 0; c0 < cols; c0 += 32) {                // pass 1: row means of dyh and dyh xh, column sums

@@ -17,7 +17,7 @@
 //   front  4 read (x) + 4 written (t) + 4 written (bands) = 12     (layernorm2d 8 + dwt 8 = 16 as separate passes)
 //   back   4 read (bands) + 4 read (t) + 4 written        = 12     (iwt 8 + affine_clamp_add 12 = 20)
 //   tail   4 read (t) + 4 read (y) + 4 written            = 12     (layernorm2d 8 + residual read in the GEMM 4 + add 12 = 24)
-#include "rf_common.h"
+#include "rf_layernorm.h"
 #include "rf_handle.h"
 
 namespace rf {
@@ -27,23 +27,6 @@ static inline unsigned wmb_grid(size_t items) {
     size_t g = (items + kWb - 1) / kWb;
     if (g > 4096) g = 4096;
     return (unsigned)(g < 1 ? 1 : g);
-}
-
-__device__ __forceinline__ void acc4(float (&s)[4], const float4& v) { s[0] += v.x; s[1] += v.y; s[2] += v.z; s[3] += v.w; }
-__device__ __forceinline__ void sq4(float (&q)[4], const float4& v, const float (&m)[4]) {
-    q[0] += (v.x - m[0]) * (v.x - m[0]); q[1] += (v.y - m[1]) * (v.y - m[1]);
-    q[2] += (v.z - m[2]) * (v.z - m[2]); q[3] += (v.w - m[3]) * (v.w - m[3]);
-}
-__device__ __forceinline__ float4 norm4(const float4& v, const float (&m)[4], const float (&r)[4], float g, float b) {
-    return make_float4((v.x - m[0]) * r[0] * g + b, (v.y - m[1]) * r[1] * g + b, (v.z - m[2]) * r[2] * g + b, (v.w - m[3]) * r[3] * g + b);
-}
-// dwt_init (blocks.py:104-113): halve first, then the sums in the order Python evaluates them
-__device__ __forceinline__ void haar_quad(float t00, float t01, float t10, float t11, float& ll, float& hl, float& lh, float& hh) {
-    const float x1 = t00 / 2, x2 = t10 / 2, x3 = t01 / 2, x4 = t11 / 2;
-    ll = ((x1 + x2) + x3) + x4;
-    hl = ((-x1 - x2) + x3) + x4;
-    lh = ((-x1 + x2) - x3) + x4;
-    hh = ((x1 - x2) - x3) + x4;
 }
 
 // x, t [B][C][2h][2w], bands [4B][C][h][w] (band s of image b at batch index s B + b); 2w % 4 == 0
@@ -72,7 +55,7 @@ __global__ void __launch_bounds__(kWb) wmb_front_kernel(const float* __restrict_
             sq4(q1, *reinterpret_cast<const float4*>(r1 + c * P), m1);
         }
 #pragma unroll
-        for (int v = 0; v < 4; ++v) { q0[v] = 1.0f / sqrtf(q0[v] * invC + eps); q1[v] = 1.0f / sqrtf(q1[v] * invC + eps); }
+        for (int v = 0; v < 4; ++v) { q0[v] = ln_rstd(q0[v], invC, eps); q1[v] = ln_rstd(q1[v], invC, eps); }
         float* bo = bands + (b * C * h + y) * (size_t)w + 2 * xv;
         for (int c = 0; c < C; ++c) {
             const float g = w2[c], s = b2[c];
@@ -81,8 +64,8 @@ __global__ void __launch_bounds__(kWb) wmb_front_kernel(const float* __restrict_
             *reinterpret_cast<float4*>(t + o0 + c * P) = a;
             *reinterpret_cast<float4*>(t + o0 + c * P + W) = d;
             float2 ll, hl, lh, hh;
-            haar_quad(a.x, a.y, d.x, d.y, ll.x, hl.x, lh.x, hh.x);
-            haar_quad(a.z, a.w, d.z, d.w, ll.y, hl.y, lh.y, hh.y);
+            haar_analysis(a.x, a.y, d.x, d.y, ll.x, hl.x, lh.x, hh.x);
+            haar_analysis(a.z, a.w, d.z, d.w, ll.y, hl.y, lh.y, hh.y);
             float* o = bo + (size_t)c * h * w;
             *reinterpret_cast<float2*>(o) = ll;
             *reinterpret_cast<float2*>(o + bs) = hl;
@@ -106,13 +89,8 @@ __global__ void __launch_bounds__(kWb) wmb_back_kernel(const float* __restrict__
         const float4 ta = *reinterpret_cast<const float4*>(t + o), tb = *reinterpret_cast<const float4*>(t + o + W);
         float r[2][4];
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const float x1 = (k ? p0.y : p0.x) / 2, x2 = (k ? p1.y : p1.x) / 2, x3 = (k ? p2.y : p2.x) / 2, x4 = (k ? p3.y : p3.x) / 2;
-            r[0][2 * k] = ((x1 - x2) - x3) + x4;        // (0,0)
-            r[1][2 * k] = ((x1 - x2) + x3) - x4;        // (1,0)
-            r[0][2 * k + 1] = ((x1 + x2) - x3) - x4;    // (0,1)
-            r[1][2 * k + 1] = ((x1 + x2) + x3) + x4;    // (1,1)
-        }
+        for (int k = 0; k < 2; ++k)
+            haar_synthesis(k ? p0.y : p0.x, k ? p1.y : p1.x, k ? p2.y : p2.x, k ? p3.y : p3.x, r[0][2 * k], r[0][2 * k + 1], r[1][2 * k], r[1][2 * k + 1]);
         auto f = [](float tv, float v) { return tv + fminf(fmaxf((v + 1.0f) * 0.5f, 0.0f), 1.0f); };
         *reinterpret_cast<float4*>(out + o) = make_float4(f(ta.x, r[0][0]), f(ta.y, r[0][1]), f(ta.z, r[0][2]), f(ta.w, r[0][3]));
         *reinterpret_cast<float4*>(out + o + W) = make_float4(f(tb.x, r[1][0]), f(tb.y, r[1][1]), f(tb.z, r[1][2]), f(tb.w, r[1][3]));
@@ -133,7 +111,7 @@ __global__ void __launch_bounds__(kWb) wmb_ffn_tail_kernel(const float* __restri
         for (int v = 0; v < 4; ++v) m[v] *= invC;
         for (int c = 0; c < C; ++c) sq4(q, *reinterpret_cast<const float4*>(t + o0 + c * P), m);
 #pragma unroll
-        for (int v = 0; v < 4; ++v) q[v] = 1.0f / sqrtf(q[v] * invC + eps);
+        for (int v = 0; v < 4; ++v) q[v] = ln_rstd(q[v], invC, eps);
         for (int c = 0; c < C; ++c) {
             const float4 tv = *reinterpret_cast<const float4*>(t + o0 + c * P), yv = *reinterpret_cast<const float4*>(y + o0 + c * P);
             const float4 n = norm4(tv, m, q, gw[c], gb[c]);

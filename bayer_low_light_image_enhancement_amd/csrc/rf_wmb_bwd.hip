@@ -25,6 +25,7 @@
 // calls give the same bits.  The entry points follow rf_grad.h: check_backward_args, a *_workspace_bytes query, an accumulate flag,
 // nothing kept from a forward call, inputs never written.
 #include "rf_grad.h"
+#include "rf_layernorm.h"
 
 namespace rf {
 
@@ -33,15 +34,6 @@ namespace {
 constexpr int kBlk = 256;
 
 __device__ __forceinline__ float2 ld2(const float* p) { return *reinterpret_cast<const float2*>(p); }
-
-// iwt_init (blocks.py:123-134) of one band pixel, wmb_back_kernel's expression order: r00, r01 the upper, r10, r11 the lower row
-__device__ __forceinline__ void haar_synth(float ll, float hl, float lh, float hh, float& r00, float& r01, float& r10, float& r11) {
-    const float x1 = ll / 2, x2 = hl / 2, x3 = lh / 2, x4 = hh / 2;
-    r00 = ((x1 - x2) - x3) + x4;
-    r10 = ((x1 - x2) + x3) - x4;
-    r01 = ((x1 + x2) - x3) - x4;
-    r11 = ((x1 + x2) + x3) + x4;
-}
 
 // ---- front.  x, gt, dx [B][C][2h][2w], gb [4B][C][h][w]; grid (nblk, B); partial[(image, workgroup)][2][C]: the slabs of d w2 and
 // d b2, gscale applied
@@ -82,8 +74,8 @@ __global__ void __launch_bounds__(kBlk) wmb_front_bwd_kernel(const float* __rest
             const float* bp = bb + (size_t)cs[s] * hw + o1;
             const float2 p0 = ld2(bp), p1 = ld2(bp + bs), p2 = ld2(bp + 2 * bs), p3 = ld2(bp + 3 * bs);
             float r[8];
-            haar_synth(p0.x, p1.x, p2.x, p3.x, r[0], r[1], r[4], r[5]);
-            haar_synth(p0.y, p1.y, p2.y, p3.y, r[2], r[3], r[6], r[7]);
+            haar_synthesis(p0.x, p1.x, p2.x, p3.x, r[0], r[1], r[4], r[5]);
+            haar_synthesis(p0.y, p1.y, p2.y, p3.y, r[2], r[3], r[6], r[7]);
             xs[s][0] = xa.x; xs[s][1] = xa.y; xs[s][2] = xa.z; xs[s][3] = xa.w;
             xs[s][4] = xd.x; xs[s][5] = xd.y; xs[s][6] = xd.z; xs[s][7] = xd.w;
             gs[s][0] = ta.x + r[0]; gs[s][1] = ta.y + r[1]; gs[s][2] = ta.z + r[2]; gs[s][3] = ta.w + r[3];
@@ -111,7 +103,7 @@ __global__ void __launch_bounds__(kBlk) wmb_front_bwd_kernel(const float* __rest
             }
 #pragma unroll
             for (int o = G; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
-            rstd[q] = 1.0f / sqrtf(v * invC + eps);
+            rstd[q] = ln_rstd(v, invC, eps);
             s1[q] = 0.f;
             s2[q] = 0.f;
         }
@@ -180,8 +172,8 @@ __global__ void __launch_bounds__(kBlk) wmb_back_bwd_kernel(const float* __restr
         const size_t o = (pl * 2 * h + 2 * y) * (size_t)W + 4 * xv;
         const float4 ga = ld4(go + o), gd = ld4(go + o + W);
         float r[8];
-        haar_synth(p0.x, p1.x, p2.x, p3.x, r[0], r[1], r[4], r[5]);
-        haar_synth(p0.y, p1.y, p2.y, p3.y, r[2], r[3], r[6], r[7]);
+        haar_synthesis(p0.x, p1.x, p2.x, p3.x, r[0], r[1], r[4], r[5]);
+        haar_synthesis(p0.y, p1.y, p2.y, p3.y, r[2], r[3], r[6], r[7]);
         const float g[8] = {ga.x, ga.y, ga.z, ga.w, gd.x, gd.y, gd.z, gd.w};
         float m[8];
 #pragma unroll
@@ -189,15 +181,9 @@ __global__ void __launch_bounds__(kBlk) wmb_back_bwd_kernel(const float* __restr
             const float v = (r[q] + 1.0f) * 0.5f;      // the forward's value before the clamp; torch.clamp passes the gradient on [0, 1]
             m[q] = (v >= 0.0f && v <= 1.0f) ? 0.5f * g[q] : 0.f;
         }
-        float2 ll, hl, lh, hh;
-        {   // dwt_init (blocks.py:104-113) of the quad (m0 m1 / m4 m5), then of (m2 m3 / m6 m7)
-            const float x1 = m[0] / 2, x2 = m[4] / 2, x3 = m[1] / 2, x4 = m[5] / 2;
-            ll.x = ((x1 + x2) + x3) + x4; hl.x = ((-x1 - x2) + x3) + x4; lh.x = ((-x1 + x2) - x3) + x4; hh.x = ((x1 - x2) - x3) + x4;
-        }
-        {
-            const float x1 = m[2] / 2, x2 = m[6] / 2, x3 = m[3] / 2, x4 = m[7] / 2;
-            ll.y = ((x1 + x2) + x3) + x4; hl.y = ((-x1 - x2) + x3) + x4; lh.y = ((-x1 + x2) - x3) + x4; hh.y = ((x1 - x2) - x3) + x4;
-        }
+        float2 ll, hl, lh, hh;      // dwt_init of the quad (m0 m1 / m4 m5), then of (m2 m3 / m6 m7)
+        haar_analysis(m[0], m[1], m[4], m[5], ll.x, hl.x, lh.x, hh.x);
+        haar_analysis(m[2], m[3], m[6], m[7], ll.y, hl.y, lh.y, hh.y);
         float* ob = gbands + ib;
         *reinterpret_cast<float2*>(ob) = ll;
         *reinterpret_cast<float2*>(ob + bs) = hl;
@@ -343,7 +329,8 @@ static int band_geometry(const char* who, int B, int C, int h, int w) {
 }
 
 // lanes per item of wmb_front_bwd_kernel, and its workgroups per image: one per 4 * (64 / KS) items, at most about 512 over the batch
-// (at up to 192 registers a CU holds two of them: 512 are resident at once, and every slab is a row for reduce_rows to add)
+// (at up to 192 registers a CU holds two of them: 512 are resident at once, and every slab is a row for reduce_rows to add).
+// Not RF_LN_SLICE_TABLE of rf_layernorm.h: with 8 pixels and x and g per slot the rule here is at most 4 channels per lane, for any C
 static int front_ks(int C) {
     int ks = 4;
     while (ks < 64 && cdiv(C, ks) > 4) ks <<= 1;
