@@ -22,7 +22,7 @@ LIB = os.path.join(CSRC, "librawformer_hip.so")
 DIAG_LIB = os.path.join(CSRC, "librawformer_hip_diag.so")
 DIAG_SOURCES = ["rf_block.hip", "rf_model.hip", "rf_gemm1x1.hip", "rf_fused.hip"]
 SOURCES = ["rf_api.hip", "rf_registry.hip", "rf_model.hip", "rf_pack.hip", "rf_pointwise.hip", "rf_gemm1x1.hip", "rf_gemm1x1_dw3.hip",
-           "rf_conv3x3.hip", "rf_attn.hip", "rf_flca.hip", "rf_fused.hip", "rf_fused_tail.hip", "rf_attn_front_tall.hip", "rf_attn_mid.hip", "rf_block.hip", "rf_harness.hip", "rf_ssim.hip", "rf_tokattn.hip", "rf_wfb.hip", "rf_upcat.hip", "rf_fft.hip", "rf_ffab.hip", "rf_truecolor.hip", "rf_multilvl.hip", "rf_train.hip", "rf_optim.hip", "rf_flca_bwd.hip", "rf_trainstep.hip", "rf_sampler.hip", "rf_mamba.hip", "rf_mamba_bwd.hip", "rf_wm_bwd.hip", "rf_wmb.hip", "rf_ffab_bwd.hip", "rf_grad.hip", "rf_wfb_train.hip", "rf_wmb_bwd.hip", "rf_wmb_block_bwd.hip", "rf_flca_pyramid.hip", "rf_flca_pyramid_bwd.hip"]
+           "rf_conv3x3.hip", "rf_attn.hip", "rf_flca.hip", "rf_fused.hip", "rf_fused_tail.hip", "rf_fused_proj.hip", "rf_attn_front_tall.hip", "rf_attn_mid.hip", "rf_block.hip", "rf_harness.hip", "rf_ssim.hip", "rf_tokattn.hip", "rf_wfb.hip", "rf_upcat.hip", "rf_fft.hip", "rf_ffab.hip", "rf_truecolor.hip", "rf_multilvl.hip", "rf_train.hip", "rf_optim.hip", "rf_flca_bwd.hip", "rf_trainstep.hip", "rf_sampler.hip", "rf_mamba.hip", "rf_mamba_bwd.hip", "rf_wm_bwd.hip", "rf_wmb.hip", "rf_ffab_bwd.hip", "rf_grad.hip", "rf_wfb_train.hip", "rf_wmb_bwd.hip", "rf_wmb_block_bwd.hip", "rf_flca_pyramid.hip", "rf_flca_pyramid_bwd.hip"]
 # every header a source may include: ONE list for the product and the diagnostic objects (a stale *_diag.o linked with fresh
 # product objects would disagree on struct rf_handle)
 HEADERS = [os.path.join(CSRC, "rf_common.h"), os.path.join(CSRC, "rf_handle.h"), os.path.join(CSRC, "rf_fused_tile.h"), os.path.join(CSRC, "rf_gemm1x1_tile.h"), os.path.join(CSRC, "rf_mamba.h"), os.path.join(CSRC, "rf_fft_lines.h"), os.path.join(CSRC, "rf_grad.h"), os.path.join(CSRC, "rf_flca_adjoint.h"), os.path.join(CSRC, "rf_guidance.h"), os.path.join(CSRC, "rf_layernorm.h"), os.path.join(HERE, "..", "include", "rawformer_hip.h"),

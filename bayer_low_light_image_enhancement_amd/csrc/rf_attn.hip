@@ -222,7 +222,7 @@ __host__ __device__ static inline int fold_stage(int NT, int c) { return NT * 16
 __global__ void __launch_bounds__(kFoldThreads) attn_fold_kernel(const float* __restrict__ partial, int nslab,
                                                                  const float* __restrict__ temperature,
                                                                  const float* __restrict__ w_out, float* __restrict__ wp_out,
-                                                                 unsigned short* __restrict__ wp3_out, int C, int heads, int log_temperature) {
+                                                                 unsigned short* __restrict__ wp3_out, int C, int heads, int log_temperature, int perm) {
     const int hd = blockIdx.x, b = blockIdx.y;
     const int c = C / heads;
     const int NT = (C + 15) >> 4;
@@ -315,7 +315,7 @@ __global__ void __launch_bounds__(kFoldThreads) attn_fold_kernel(const float* __
     }
     __syncthreads();
     // 3. W'[co][hd*c + j] = sum_i W_out[co][hd*c + i] * attn[i][j], stored in MFMA operand order
-    float* dst = wp_out + (size_t)b * NT * (C / 4) * 64;
+    float* dst = wp_out ? wp_out + (size_t)b * NT * (C / 4) * 64 : nullptr;      // nullptr: the caller reads the b3 form only
     const int NB = (C + 31) >> 5;
     unsigned short* dst3 = wp3_out ? wp3_out + (size_t)b * NT * NB * 1536 : nullptr;   // b3 form of the same matrix (rf_common.h)
     // the head's slice of w_out, [co][hd*c .. hd*c + c), goes through LDS a block of rows at a time (each element was read from
@@ -338,8 +338,8 @@ __global__ void __launch_bounds__(kFoldThreads) attn_fold_kernel(const float* __
                 for (int ii = 0; ii < c; ++ii) s = fmaf(wr[ii], S[ii][jj], s);
             }
             const int k = hd * c + jj;
-            dst[((size_t)(k >> 2) * NT + (co >> 4)) * 64 + (co & 15) + 16 * (k & 3)] = s;
-            if (dst3) b3_store(dst3, NT, co, k, s);
+            if (dst) dst[((size_t)(k >> 2) * NT + (co >> 4)) * 64 + (co & 15) + 16 * (k & 3)] = s;
+            if (dst3) b3_store(dst3, NT, perm ? fold_row_perm32(co) : co, k, s);      // perm: C = 32, the rows as proj_step_b3 wants them
         }
     }
     // columns C .. 32 NB - 1 of the padded b3 matrix (C not a multiple of 32): zero, written by the last head's workgroup
@@ -349,11 +349,12 @@ __global__ void __launch_bounds__(kFoldThreads) attn_fold_kernel(const float* __
 }
 
 int launch_attn_fold(const float* partial, int nslab, const float* temperature, const float* w_out,
-                     float* wp_out, void* wp3_out, int B, int C, int heads, hipStream_t st, int log_temperature) {
+                     float* wp_out, void* wp3_out, int B, int C, int heads, hipStream_t st, int log_temperature, bool perm) {
     RF_CHECK_ARG(C % heads == 0 && C / heads <= 64 && C % 4 == 0, "attn_fold: unsupported C=%d heads=%d", C, heads);
+    RF_CHECK_ARG((wp_out || wp3_out) && (!perm || (C == 32 && wp3_out)), "attn_fold: no destination, or permuted rows at C=%d", C);
     ProfScope prof(st, "attn_fold_kernel", 0.0, 0.0);
     const int c = C / heads, nthr = fold_threads(c);
-    attn_fold_kernel<<<dim3((unsigned)heads, (unsigned)B), nthr, (size_t)(nthr + fold_stage((C + 15) >> 4, c)) * sizeof(float), st>>>(partial, nslab, temperature, w_out, wp_out, (unsigned short*)wp3_out, C, heads, log_temperature);
+    attn_fold_kernel<<<dim3((unsigned)heads, (unsigned)B), nthr, (size_t)(nthr + fold_stage((C + 15) >> 4, c)) * sizeof(float), st>>>(partial, nslab, temperature, w_out, wp_out, (unsigned short*)wp3_out, C, heads, log_temperature, perm ? 1 : 0);
     return check_launch("attn_fold");
 }
 

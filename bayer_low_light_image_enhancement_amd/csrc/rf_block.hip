@@ -32,7 +32,7 @@ bool transformer_ffn_is_fused(const TbParams& p, int C, int hc, int hh, int ww) 
 }
 
 int run_chan_attn(const TbParams& p, const float* in, float* out, bool residual, const AttnBufs& buf, int B, int C, int heads, int hh, int ww,
-                  hipStream_t st, bool no_fuse, bool no_fuse_attn) {
+                  hipStream_t st, bool no_fuse, bool no_fuse_attn, FfnProj* proj) {
     const int Pn = hh * ww;
     float* const partial = buf.partial;
     Conv1x1Args av{};
@@ -91,6 +91,14 @@ int run_chan_attn(const TbParams& p, const float* in, float* out, bool residual,
     // spatial shard: every rank holds the same slab grid (equal local shapes), so the element-wise sum of the partial buffers is
     // the partial buffer of the whole frame; the fold then sums the slabs as always
     if (p.allreduce) p.allreduce(p.allreduce_user, partial, partial_floats, 0, (void*)st);
+    if (proj) {
+        // the fused FFN kernel applies the projection (launch_ffn_fused): the fold writes the b3 form alone, rows permuted, and the
+        // attention half ends here
+        RF_CHECK_ARG(residual && C == 32, "chan_attn: the projection moves into the FFN kernel at C = 32, with the residual (C = %d)", C);
+        RF_TRY(launch_attn_fold(partial, nslab, p.temperature, p.proj_w, nullptr, buf.wfold3, B, C, heads, st, p.log_temperature, true));
+        *proj = FfnProj{av.x1, av.x1_bstride, buf.wfold3, p.proj_b};
+        return RF_OK;
+    }
     RF_TRY(launch_attn_fold(partial, nslab, p.temperature, p.proj_w, buf.wfold, buf.wfold3, B, C, heads, st, p.log_temperature));
     av.C1 = C;
     av.wp = buf.wfold; av.wp_bstride = (int64_t)packed1x1_floats(C, C);
@@ -109,7 +117,7 @@ int run_transformer(const TbParams& p, const float* in, float* out, float* ws, c
 
 // x + attn(LN1(x)) -> x1 ---------------------------------------------------------------------
 int run_transformer_attn(const TbParams& p, const float* in, float* ws, const TbBufOffsets& o, int B, int C, int heads, int hh, int ww,
-                         hipStream_t st) {
+                         hipStream_t st, FfnProj* proj) {
 #ifdef RF_DIAG   // diagnostic build only (build.py --diag): force the op-by-op path; the shipped library has no switch
     const bool no_fuse = getenv("RF_NO_FUSE") != nullptr;
     const bool no_fuse_attn = no_fuse || getenv("RF_NO_FUSE_ATTN") != nullptr;
@@ -118,25 +126,27 @@ int run_transformer_attn(const TbParams& p, const float* in, float* ws, const Tb
 #endif
 
     return run_chan_attn(p, in, ws + o.x1, true, AttnBufs{ws + o.bufA, ws + o.bufB, ws + o.partial, ws + o.wfold, ws + o.wfold3}, B, C, heads,
-                         hh, ww, st, no_fuse, no_fuse_attn);
+                         hh, ww, st, no_fuse, no_fuse_attn, proj);
 }
 
 // x1 + ffn(LN2(x1)) -> out -------------------------------------------------------------------
-int run_transformer_ffn(const TbParams& p, float* out, float* ws, const TbBufOffsets& o, int B, int C, int hc, int hh, int ww, hipStream_t st) {
+int run_transformer_ffn(const TbParams& p, float* out, float* ws, const TbBufOffsets& o, int B, int C, int hc, int hh, int ww, hipStream_t st,
+                        const float* proj_in, const FfnProj* proj) {
     const int Pn = hh * ww;
     float* bufA = ws + o.bufA;
     float* bufB = ws + o.bufB;
     float* x1 = ws + o.x1;
     const bool fused = transformer_ffn_is_fused(p, C, hc, hh, ww);
     RF_CHECK_ARG(!p.tail.xs || (fused && fused_ffn_tail_supported(C)), "transformer: the stage tail needs the fused FFN kernel (C = %d)", C);
+    RF_CHECK_ARG(!proj || (p.tail.xs && proj_in), "transformer: the projection moves into the FFN kernel only with the stage tail");
     if (fused) {
         // LN2 -> 1x1 -> depthwise 3x3 -> GELU -> 1x1 + residual in one kernel: the hidden tensor stays on chip
         FfnArgs f{};
-        f.x = x1; f.out = out;
+        f.x = proj ? proj_in : x1; f.out = out;      // proj: the kernel forms x1 itself
         f.ln_w = p.ln2_w; f.ln_b = p.ln2_b; f.w1p = p.pw1_wp3; f.b1 = p.pw1_b; f.wd = p.dw_w; f.bd = p.dw_b; f.w2p = p.pw2_wp; f.b2 = p.pw2_b;
         f.B = B; f.h = hh; f.w = ww;
         if (p.tail.xs) f.b2 = p.tail_bias;      // ... and the caller's channel_reduce on top
-        RF_TRY(launch_ffn_fused(f, C, st, p.tail));
+        RF_TRY(launch_ffn_fused(f, C, st, p.tail, proj));
     } else {
         Conv1x1Args f1{};
         f1.x1 = x1; f1.C1 = C; f1.x1_bstride = (int64_t)C * Pn;

@@ -375,9 +375,15 @@ struct GramArgs {
 int gram_plan(int B, int C, int heads, int P, int* nslab, int* slab, size_t* partial_floats);
 int launch_gram(const GramArgs& a, hipStream_t st);
 // softmax + fold into project_out: wp_out[b] = pack(W_out * blockdiag(attn_b))
+// wp_out == nullptr: the b3 form only.  perm (C = 32): the b3 form's rows in the order the fused FFN kernel's projection step
+// wants them (fold_row_perm32).
 int launch_attn_fold(const float* partial, int nslab, const float* temperature, const float* w_out,
-                     float* wp_out, void* wp3_out /* b3 form too, or nullptr */, int B, int C, int heads, hipStream_t st,
-                     int log_temperature = 0);
+                     float* wp_out /* or nullptr */, void* wp3_out /* b3 form too, or nullptr */, int B, int C, int heads, hipStream_t st,
+                     int log_temperature = 0, bool perm = false);
+// Row of the folded 32 x 32 projection that holds output channel `co` in the permuted b3 form: row 16 t + 4 a + r <-> channel
+// 8 a + 4 t + r, so that the MFMA's output rows 16 t + 4 kq + r of lane (j, kq) are its LayerNorm channels 8 kq + (4 t + r)
+// (proj_step_b3, rf_fused_tile.h)
+__host__ __device__ static inline int fold_row_perm32(int co) { return 16 * ((co >> 2) & 1) + 4 * (co >> 3) + (co & 3); }
 
 // ---- fused transformer-block kernels (rf_fused.hip).  The kernels take these structs by value: their layout is the kernels'.
 // The caller fills the tensors, B / h / w, nslab (from the plan) and the shard window; the launcher fills tiles_x, ntiles and
@@ -402,9 +408,22 @@ struct FfnTail {
     const float* wp;           // [Wa' | Wb | Wb W2] in f32 MFMA operand order [(2C + 2C)/4][C/16][64] (flca_fold_kernel's wp_out)
     int64_t wp_bstride;        // floats between the images' sets (0: one static set)
 };
+// The attention projection inside the kernel too (with a tail only): FfnArgs.x is then the BLOCK's input and the kernel forms
+//   x1 = x + Wf_b v + bias       per halo'd tile, in place of reading it,
+// so the projection GEMM's launch and x1's trip through HBM go.  Carried beside FfnArgs / FfnTail: their layout is the kernels'.
+struct FfnProj {
+    const float* v;            // [B][C][h][w] at v_bstride floats per image: the attention front's depthwise-convolved v
+    int64_t v_bstride;
+    const void* wf3;           // [B] folded projection weights, b3 form with permuted rows (launch_attn_fold, perm)
+    const float* bias;         // [C] project_out's bias
+};
 bool fused_ffn_supported(int C, int hidden, int h, int w);
 bool fused_ffn_tail_supported(int C);
-int launch_ffn_fused(FfnArgs a, int C, hipStream_t st, FfnTail tail = FfnTail{nullptr, nullptr, 0});
+// Does a level-`lvl` stage with the fused tail take the projection form?  From the level and (h, w) alone, never from B (the
+// two forms round differently: see fused_attn_plan).
+bool fused_ffn_proj_rule(int lvl, int h, int w);
+int launch_ffn_fused(FfnArgs a, int C, hipStream_t st, FfnTail tail = FfnTail{nullptr, nullptr, 0}, const FfnProj* proj = nullptr);
+int launch_ffn_fused_proj32(const FfnArgs& a, const FfnTail& tail, const FfnProj& pj, dim3 grid, hipStream_t st);   // rf_fused_proj.hip; called by launch_ffn_fused
 int launch_ffn_fused_tail32(const FfnArgs& a, const FfnTail& tail, dim3 grid, hipStream_t st);   // rf_fused_tail.hip; called by launch_ffn_fused
 
 struct AttnFrontArgs {     // LN1 -> qkv 1x1 -> depthwise 3x3 -> Gram partials of (q, k) + v, for C = 32
@@ -475,9 +494,12 @@ int run_transformer(const TbParams& p, const float* in, float* out, float* ws, c
                     int B, int C, int heads, int hc, int hh, int ww, hipStream_t st);
 // its two halves: x1 = in + attn(LN1(in)) into the x1 buffer, then out = x1 + ffn(LN2(x1)) (a caller may order other work
 // between them: run_stage joins the branch there when the FFN kernel carries the stage tail)
+// `proj` (run_stage, where fused_ffn_proj_rule holds): the attention half stops after the fold and says there what the FFN kernel
+// needs to apply the projection itself; the FFN half then reads `proj_in`, the block's input, and x1 is never written.
 int run_transformer_attn(const TbParams& p, const float* in, float* ws, const TbBufOffsets& o, int B, int C, int heads, int hh, int ww,
-                         hipStream_t st);
-int run_transformer_ffn(const TbParams& p, float* out, float* ws, const TbBufOffsets& o, int B, int C, int hc, int hh, int ww, hipStream_t st);
+                         hipStream_t st, FfnProj* proj = nullptr);
+int run_transformer_ffn(const TbParams& p, float* out, float* ws, const TbBufOffsets& o, int B, int C, int hc, int hh, int ww, hipStream_t st,
+                        const float* proj_in = nullptr, const FfnProj* proj = nullptr);
 // The attention half of the block, also the whole of rf_chan_attn:  out = [in +] W_out softmax(T q^ k^T) v + b  with
 // q, k, v = depthwise3x3(W_qkv [LN1](in)).  Reads the attention fields of `p`; p.ln1_w == nullptr: no LayerNorm (and never the
 // attn_front kernel, which has one built in).  The no_fuse switches are the diagnostic build's (run_transformer sets them).
@@ -488,7 +510,7 @@ struct AttnBufs {
     void* wfold3;         // [B] packed1x1_b3_floats(C, C)
 };
 int run_chan_attn(const TbParams& p, const float* in, float* out, bool residual, const AttnBufs& buf, int B, int C, int heads, int hh, int ww,
-                  hipStream_t st, bool no_fuse = false, bool no_fuse_attn = false);
+                  hipStream_t st, bool no_fuse = false, bool no_fuse_attn = false, FfnProj* proj = nullptr);
 
 // ---- rfft2 / irfft2 with the polar maps of FEB (rf_fft.hip); cscratch: planes * h * (w/2 + 1) complex values
 // What both launchers launch for [planes][h][w], decided on the host alone (no HIP call): plan_fft is the single statement of the

@@ -5,7 +5,8 @@
 // phase_a_step_b3 and tile_range; all four share stencil4, and ffn_fused8_kernel and attn_front_kernel tile_origin.  Every helper is __forceinline__, and tools/isa_same.py shows whether an edit to one
 // of them left the compiled code alone.  The helpers and ffn_fused_kernel live in rf_fused_tile.h: rf_fused_tail.hip builds the
 // second instantiation, ffn_fused_kernel<32, true>, which a whole-model stage uses at level 0 -- the FFN with the stage's
-// channel_reduce on top (FfnTail, rf_common.h), launched from here by launch_ffn_fused.  rf_attn_front_tall.hip builds
+// channel_reduce on top (FfnTail, rf_common.h), launched from here by launch_ffn_fused; rf_fused_proj.hip the third,
+// <32, true, FfnProj>, with the attention projection ahead of it (FfnProj; fused_ffn_proj_rule).  rf_attn_front_tall.hip builds
 // attn_front_tall_kernel<32>, attn_front on tiles of 12 rows and eight waves, which launch_attn_front takes above 256 x 256.
 //
 // Un-fused, one TransformerBlock moves ~26 C floats per pixel through HBM (qkv 1x1: C in / 3C out,
@@ -14,6 +15,7 @@
 //
 //   ffn_fused_kernel    x1 -> LN2 -> 1x1 (C->2C) -> dw3x3 -> GELU -> 1x1 (2C->C) + x1      reads C, writes C
 //     ... <32, true>    the same, then channel_reduce(cat(xs, .)): [xs ; x1 ; g] x [Wa' | Wb | Wb W2]    reads 2C, writes C
+//     ... <32, true, FfnProj>   the same on x1 = x + Wf v + b, formed per tile (the attention projection)     reads 3C, writes C
 //   attn_front_kernel   x  -> LN1 -> 1x1 (C->3C) -> dw3x3 -> { Gram partials of q,k ; v }   reads C, writes C
 //
 // Tile = 4 rows x 64 px per workgroup (4 waves, one output row each) plus a 1-pixel halo, held as
@@ -235,12 +237,27 @@ static bool ffn_diag64() {
 bool fused_ffn_supported(int C, int hidden, int h, int w) { return ffn_shape_ok(C, hidden, h, w, ffn_diag64()); }
 bool fused_ffn_tail_supported(int C) { return C == 32; }      // the four-wave kernel only
 
-int launch_ffn_fused(FfnArgs a, int C, hipStream_t st, FfnTail tail) {
+// The projection form (ffn_fused_kernel<32, true, FfnProj>, rf_fused_proj.hip) of a stage with the fused tail: at level 0, in the size
+// class of the tall attention front (attn_front_tall_slabs: above 256 tiles of 4 x 64, i.e. 256 x 256 packed).  From the level and
+// (h, w) alone -- never from B: the two forms round differently, and an image's result must not depend on its neighbours
+// (fused_attn_plan).  Both extra conditions keep the two-launch path in use, and thereby tested: every dim-32 frame of the launch
+// census (tests/golden/forward_launches.json) is at most 64 x 72 packed, and its 1032 x 1024 frame at dim 16 reaches the fused tail
+// with C = 32 at LEVEL 1 (516 x 512), where the projection GEMM stays a launch of its own.
+bool fused_ffn_proj_rule(int lvl, int h, int w) {
+#ifdef RF_DIAG   // diagnostic build only: the projection launch at any size
+    if (getenv("RF_NO_FUSE_PROJ")) return false;
+#endif
+    return lvl == 0 && cdiv(w, fused::TW) * cdiv(h, fused::TH) > 256;
+}
+
+int launch_ffn_fused(FfnArgs a, int C, hipStream_t st, FfnTail tail, const FfnProj* proj) {
     const int B = a.B, h = a.h, w = a.w;
     RF_CHECK_ARG(ffn_shape_ok(C, 2 * C, h, w, ffn_diag64()) && B <= 65535, "ffn_fused: unsupported shape C=%d %dx%d", C, h, w);
     RF_CHECK_ARG(aligned16(a.x) && aligned16(a.out) && aligned16(a.w1p), "ffn_fused: buffers must be 16-byte aligned");
     RF_CHECK_ARG(!tail.xs || (fused_ffn_tail_supported(C) && tail.wp && aligned16(tail.xs) && aligned16(tail.wp) && tail.wp_bstride % 4 == 0),
                  "ffn_fused: the stage tail needs C = 32 and 16-byte aligned operands (C = %d)", C);
+    RF_CHECK_ARG(!proj || (tail.xs && proj->v && proj->wf3 && proj->bias && aligned16(proj->v) && aligned16(proj->wf3) && proj->v_bstride % 4 == 0),
+                 "ffn_fused: the projection form needs the stage tail and 16-byte aligned operands (C = %d)", C);
     a.tiles_x = cdiv(w, fused::TW);
     a.ntiles = a.tiles_x * cdiv(h, fused::TH);
     int wgs = cdiv(512, B);                       // persistent: two workgroups per CU over the whole batch
@@ -256,6 +273,10 @@ int launch_ffn_fused(FfnArgs a, int C, hipStream_t st, FfnTail tail) {
         if (C == 64) ffn_fused8_kernel<64><<<grid8, 512, 0, st>>>(a);
         else ffn_fused8_kernel<48><<<grid8, 512, 0, st>>>(a);
         return check_launch("ffn_fused8");
+    }
+    if (proj) {      // four tensors of C floats per pixel: x, v and xs in, out
+        ProfScope prof(st, "ffn_fused_kernel<32, true, proj>", px * (8.0 * C * C + 36.0 * C + 2.0 * 2 * C * C + 2.0 * C * C), px * 4.0 * 4 * C);
+        return launch_ffn_fused_proj32(a, tail, *proj, grid, st);
     }
     if (tail.xs) {
         ProfScope prof(st, "ffn_fused_kernel<32, true>", px * (8.0 * C * C + 36.0 * C + 2.0 * 2 * C * C), px * 4.0 * 3 * C);

@@ -1,7 +1,8 @@
 // The tile machinery of the fused transformer-block kernels (rf_fused.hip has the overview) and ffn_fused_kernel itself, in a
-// header because the kernel is instantiated in two translation units: rf_fused.hip builds <32, false>, rf_fused_tail.hip
-// <32, true>.  hipcc compiles a translation unit's kernels together, and a second instantiation beside the first changed the
-// code of the first AND of attn_front_kernel / attn_mid_kernel (tools/isa_same.py); on its own each compiles as before.
+// header because the kernel is instantiated in three translation units: rf_fused.hip builds <32, false>, rf_fused_tail.hip
+// <32, true>, rf_fused_proj.hip <32, true, FfnProj>.  hipcc compiles a translation unit's kernels together, and a second
+// instantiation beside the first changed the code of the first AND of attn_front_kernel / attn_mid_kernel (tools/isa_same.py); on
+// its own each compiles as before.
 #pragma once
 #include "rf_common.h"
 
@@ -257,6 +258,43 @@ __device__ __forceinline__ void roll_shift(float (&acc)[3][4]) {
     for (int q = 0; q < 4; ++q) { acc[0][q] = acc[1][q]; acc[1][q] = acc[2][q]; }
 }
 
+// ---- the attention projection ahead of the FFN (ffn_fused_kernel<32, true, FfnProj>; FfnProj: rf_common.h) -----------------------
+// x1 = x + Wf v + b of one step, into the registers that hold x.  One b3 GEMM step against the image's folded weights `wa` (two
+// output tiles of three pieces).  The MFMA leaves lane (j, kq) with output rows 16 t + 4 kq + r of its group; ln_step_b3 wants
+// channel 8 kq + s in xh[s].  attn_fold_kernel wrote row 16 t + 4 a + r as channel 8 a + 4 t + r (fold_row_perm32), so
+// acc[t][.][r] IS channel 8 kq + 4 t + r = xh[4 t + r]: no shuffle.  The bias is read by true channel.
+template <int C>
+__device__ __forceinline__ void proj_step_b3(const float4 (&vh)[C / 4], const u32x4 (&wa)[2][3], const float* __restrict__ bias, int kq, float4 (&xh)[C / 4]) {
+    static_assert(C == 32, "one k-block, two output tiles");
+    u32x4 bv[1][4][3];
+    split_step<C>(vh, bv);
+    f32x4 acc[2][4];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[t][q] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        b3_mfma4(wa[t], bv[0], acc[t]);
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int s = 4 * t + r;
+            const float bs = bias[8 * kq + s];
+            xh[s].x += acc[t][0][r] + bs; xh[s].y += acc[t][1][r] + bs;
+            xh[s].z += acc[t][2][r] + bs; xh[s].w += acc[t][3][r] + bs;
+        }
+}
+// ... and x1 of the step's groups into the LDS planes, at the offsets phase A uses (a group outside the image holds what offset 0
+// gave: phase A zero-fills ITS output there, and the interior tile reads such a group only into lanes that never store)
+template <int C>
+__device__ __forceinline__ void stage_step(const float4 (&xh)[C / 4], float* __restrict__ mid, int PS, int kq, const GroupGeom& g) {
+    if (g.lds_off >= 0) {
+#pragma unroll
+        for (int s = 0; s < C / 4; ++s) *reinterpret_cast<float4*>(mid + (32 * (s >> 3) + 8 * kq + (s & 7)) * PS + g.lds_off) = xh[s];
+    }
+}
+
 // ================================================================================================
 // FFN:  out = x1 + W2 gelu(dw3x3(W1 LN2(x1) + b1) + bd) + b2          (FfnArgs: rf_common.h)
 // TAIL: the stage's channel_reduce on top,  out = Wa'_b xs + Wb x1 + (Wb W2) g + (Wb b2 + b_cr)  with g = gelu(..): Wb W2 takes
@@ -265,9 +303,20 @@ __device__ __forceinline__ void roll_shift(float (&acc)[3][4]) {
 // one float4 of channel 4 s + kq), loaded where the tail-less kernel loads its residual rows -- behind the last phase A, when
 // the b3 pieces are dead, and ahead of the tile's stores -- together with their A operands, which come from L2 (no LDS left for
 // them); the MFMAs follow the last phase B.  No residual add: x1 arrives through Wb.
+// PROJ (with TAIL): the attention projection on top, x1 = x + Wf_b v + b_proj per halo'd step ahead of LayerNorm (proj_step_b3), so
+// x1 never exists in HBM: a.x is the block's input.  The interior x1 of the tail's k-steps is then not loadable: the lanes pass
+// x1 of their groups through `mid` (free until part 0's phase A), every wave reads its row in the tail's lane map and issues the
+// Wb x1 k-steps first, into the still-zero accumulators; only xs is loaded behind the last phase A.
 // ================================================================================================
-template <int C, bool TAIL>
-__global__ void __launch_bounds__(256, 2) ffn_fused_kernel(FfnArgs a, FfnTail tl) {
+// Its operands (FfnProj) are a parameter pack, empty in the two other forms: their kernel arguments, and with them their code, are
+// what they were without it (through a shared __device__ body, or with an empty third argument, they were not: tools/isa_same.py).
+__device__ __forceinline__ FfnProj ffn_proj_of() { return FfnProj{nullptr, 0, nullptr, nullptr}; }
+__device__ __forceinline__ FfnProj ffn_proj_of(const FfnProj& pj) { return pj; }
+template <int C, bool TAIL, typename... PJ>
+__global__ void __launch_bounds__(256, 2) ffn_fused_kernel(FfnArgs a, FfnTail tl, PJ... pjs) {
+    constexpr bool PROJ = sizeof...(PJ) == 1;
+    static_assert(sizeof...(PJ) <= 1 && (TAIL || !PROJ), "the projection form carries the stage tail");
+    const FfnProj pj = ffn_proj_of(pjs...);
     using namespace fused;
     const int ro[3] = {0, HC, 2 * HC};   // a tile's halo'd rows are contiguous in LDS
     constexpr int NS = C / 4;            // k-sets of the first GEMM
@@ -281,8 +330,8 @@ __global__ void __launch_bounds__(256, 2) ffn_fused_kernel(FfnArgs a, FfnTail tl
     __shared__ __attribute__((aligned(16))) float w2_l[(2 * C / 4) * NTO * 64];
     __shared__ float wd_l[2 * C * 9], bd_l[2 * C], b1_l[2 * C], b2_l[C], gam_l[C], bet_l[C];
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int j = lane & 15, kq = lane >> 4;
+    const int tid = threadIdx.x, lane0 = tid & 63, wave = tid >> 6;
+    const int j0 = lane0 & 15, kq0 = lane0 >> 4;
     const int b = blockIdx.y;
     const int h = a.h, w = a.w, P = h * w;
     const float* xb = a.x + (size_t)b * C * P;
@@ -299,20 +348,68 @@ __global__ void __launch_bounds__(256, 2) ffn_fused_kernel(FfnArgs a, FfnTail tl
     __syncthreads();
     STAMP_DECL
     const float* xsb = TAIL ? tl.xs + (size_t)b * C * P : nullptr;
+    const float* vb = PROJ ? pj.v + (size_t)b * pj.v_bstride : nullptr;
+    const u32x4* wf = PROJ ? reinterpret_cast<const u32x4*>(pj.wf3) + (size_t)b * (2 * 192) : nullptr;
 
     const TileRange tr = tile_range(a.ntiles, a.tiles_x, (int)gridDim.x, blockIdx.x);
     for (int tile = tr.begin; tile < tr.end; ++tile) {
         const int tx = tile / tr.tiles_y, ty = tile % tr.tiles_y;      // tile_origin, spelled out: through the helper this kernel's
         const int x0 = tx * TW, y0 = ty * TH;                          // prologue is scheduled differently (tools/isa_same.py)
+        // PROJ: the lane coordinates are made opaque once per tile, as in ffn_fused8_kernel -- everything derived from them (LDS plane,
+        // weight and stencil addresses: some 40 registers) is otherwise hoisted out of the tile loop, and with the projection's
+        // operands on top of the parent's 226 registers 22 of them were spilled
+        int j = j0, kq = kq0, lane = lane0;
+        if constexpr (PROJ) asm volatile("" : "+v"(j), "+v"(kq), "+v"(lane));
         STAMP(0);
         // input tile, loaded here (see attn_front_kernel: the b3 pieces take the registers a tile in flight would need):
         // LayerNorm in registers, then the three-piece split that both parts of phase A reuse
         const GroupGeom gw0 = group_geom<GPW>(wave, 0, j, y0, x0, h, w), gw1 = group_geom<GPW>(wave, 1, j, y0, x0, h, w);
         u32x4 bp0[C / 32][4][3], bp1[C / 32][4][3];
+        f32x4 accp[PROJ ? NTO : 1][4];                     // PROJ: Wb x1, the tile's first k-steps
         {
             float4 xh0[NS], xh1[NS];
             load_step_b3<C>(xb, P, kq, gw0, xh0);
             load_step_b3<C>(xb, P, kq, gw1, xh1);
+            if constexpr (PROJ) {
+                // v goes where x goes and is dead after its split; the folded weights come from L2 like the tail's A operands
+                float4 vh0[NS], vh1[NS];
+                load_step_b3<C>(vb, P, kq, gw0, vh0);
+                load_step_b3<C>(vb, P, kq, gw1, vh1);
+                const unsigned lo = (unsigned)lane;
+                u32x4 wa[2][3];
+#pragma unroll
+                for (int t = 0; t < 2; ++t)
+#pragma unroll
+                    for (int pc = 0; pc < 3; ++pc) wa[t][pc] = (wf + (t * 3 + pc) * 64)[lo];
+                proj_step_b3<C>(vh0, wa, pj.bias, kq, xh0);
+                proj_step_b3<C>(vh1, wa, pj.bias, kq, xh1);
+                // interior x1 in the lane map of the tail's k-steps (lane (j, kq): one float4 of channel 4 s + kq), through mid
+                lds_barrier();                             // the previous tile's last phase B is done with mid
+                stage_step<C>(xh0, mid, PS, kq, gw0);
+                stage_step<C>(xh1, mid, PS, kq, gw1);
+                lds_barrier();
+#pragma unroll
+                for (int t = 0; t < NTO; ++t)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) accp[t][q] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                float4 t1[C / 4];
+                float a1[C / 4][NTO];
+#pragma unroll
+                for (int s = 0; s < C / 4; ++s) {
+                    t1[s] = *reinterpret_cast<const float4*>(mid + (4 * s + kq) * PS + (wave + 1) * HC + 4 * j + 4);
+#pragma unroll
+                    for (int t = 0; t < NTO; ++t) a1[s][t] = (tw + ((C / 4 + s) * NTO + t) * 64)[lo];
+                }
+#pragma unroll
+                for (int s = 0; s < C / 4; ++s) {
+                    const float v[4] = {t1[s].x, t1[s].y, t1[s].z, t1[s].w};
+#pragma unroll
+                    for (int t = 0; t < NTO; ++t)
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) accp[t][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[s][t], v[q], accp[t][q], 0, 0, 0);
+                }
+                // (the barrier at the top of the part loop keeps phase A off mid until every wave has read its row)
+            }
             ln_step_b3<C>(kq, gam_l, bet_l, 1e-5f, xh0);
             ln_step_b3<C>(kq, gam_l, bet_l, 1e-5f, xh1);
             split_step<C>(xh0, bp0);
@@ -330,7 +427,10 @@ __global__ void __launch_bounds__(256, 2) ffn_fused_kernel(FfnArgs a, FfnTail tl
 #pragma unroll
         for (int t = 0; t < NTO; ++t)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) acc[t][q] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            for (int q = 0; q < 4; ++q) {
+                if constexpr (PROJ) acc[t][q] = accp[t][q];
+                else acc[t][q] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            }
 
 #pragma unroll
         for (int part = 0; part < NPART; ++part) {
@@ -347,7 +447,7 @@ __global__ void __launch_bounds__(256, 2) ffn_fused_kernel(FfnArgs a, FfnTail tl
 #pragma unroll
                     for (int s = 0; s < C / 4; ++s) {
                         tb[s] = *reinterpret_cast<const float4*>(xsb + (size_t)(4 * s) * P + voffb);
-                        tb[C / 4 + s] = *reinterpret_cast<const float4*>(xb + (size_t)(4 * s) * P + voffb);
+                        if constexpr (!PROJ) tb[C / 4 + s] = *reinterpret_cast<const float4*>(xb + (size_t)(4 * s) * P + voffb);
                     }
                 } else {
                 // this tile's residual rows, behind the last phase B (issued before this tile's stores)
@@ -379,15 +479,16 @@ __global__ void __launch_bounds__(256, 2) ffn_fused_kernel(FfnArgs a, FfnTail tl
         if constexpr (TAIL) {
             // uniform base + 32-bit lane offset, the lane made opaque per tile: per-lane 64-bit pointers to the 8 KB of weights would
             // be hoisted out of the tile loop and spilled
+            constexpr int KT = PROJ ? C / 4 : 2 * C / 4;      // PROJ: the x1 k-steps went first
             unsigned lo = (unsigned)lane;
             asm volatile("" : "+v"(lo));
 #pragma unroll
-            for (int s = 0; s < 2 * C / 4; ++s)
+            for (int s = 0; s < KT; ++s)
 #pragma unroll
                 for (int t = 0; t < NTO; ++t) ta[s][t] = (tw + (s * NTO + t) * 64)[lo];
             // ---- the stage tail's k-steps: [Wa' | Wb] [xs ; x1] (a dead lane's columns hold whatever offset 0 gave: never stored)
 #pragma unroll
-            for (int s = 0; s < 2 * C / 4; ++s) {
+            for (int s = 0; s < KT; ++s) {
                 const float v[4] = {tb[s].x, tb[s].y, tb[s].z, tb[s].w};
 #pragma unroll
                 for (int t = 0; t < NTO; ++t)

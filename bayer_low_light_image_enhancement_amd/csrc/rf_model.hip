@@ -322,10 +322,14 @@ int run_stage(rf_handle* h, int i, const float* in, float* out, float* ws, const
     }
     if (rc) return rc;
     if (c.fuse_tail) {
-        // the FFN kernel reads the branch's output and weights, and writes channel_reduce's: the join sits between the block's halves
-        RF_TRY(run_transformer_attn(c.tp, in, ws, tb_bufs(p), B, C, c.heads, hh, ww, st));
+        // the FFN kernel reads the branch's output and weights, and writes channel_reduce's: the join sits between the block's halves.
+        // Where fused_ffn_proj_rule holds it applies the attention projection as well: the attention half stops after the fold, and
+        // x1 never reaches HBM.
+        FfnProj pj{};
+        FfnProj* const proj = fused_ffn_proj_rule(lvl, hh, ww) ? &pj : nullptr;
+        RF_TRY(run_transformer_attn(c.tp, in, ws, tb_bufs(p), B, C, c.heads, hh, ww, st, proj));
         RF_TRY(h->side.join(st, side));
-        RF_TRY(run_transformer_ffn(c.tp, c.crb, ws, tb_bufs(p), B, C, hc, hh, ww, st));
+        RF_TRY(run_transformer_ffn(c.tp, c.crb, ws, tb_bufs(p), B, C, hc, hh, ww, st, in, proj));
     } else if (!vt.branch_after) {
         RF_TRY(run_block(c));
         RF_TRY(h->side.join(st, side));
